@@ -17,6 +17,9 @@ commitments (32 B per segment), inside the timed region.
 
 Output: ONE JSON line on rank 0 (see the repository contract) — the COMPACT record (compact_line: under 6 000 bytes, strict JSON, every
 string under 120 characters); the full record of the run (kernel tables, notes, every sub-benchmark) goes to bench_full.json (--full-out).
+
+A plain run measures the headline only; --full adds every other leg and check (CPU baseline, the other proof kind, trace-generation
+variants, multi_segment, C3, copy ceiling, live PMC). --dump-outputs DIR writes the last timed step's results as .npy files.
 """
 from __future__ import annotations
 
@@ -104,7 +107,18 @@ def parse_args():
     ap.add_argument("--full-out", default=None,
                     help="where the full record of the run is written (default: bench_full.json next to this script; also POWDR_BENCH_FULL). "
                          "stdout carries the compact line only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the headline figure does not need: the CPU baseline, the second proof kind, the trace-generation "
+                         "variants, the multi_segment and C3 legs, the copy ceiling, the live PMC passes and the segment checks (each one can "
+                         "still be left out with its --no-* option). Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, rank 0): the proof "
+                         "words, the periphery histograms and a fixed seeded sample of the trace (C2 / T shapes), or the merged "
+                         "per-segment commitments (C4 / C5)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_logup_leg = args.no_callmajor_leg = args.no_live_pmc = True
+        args.no_copy_ceiling = args.no_segment_leg = args.no_c3_leg = True
     args.logup = not args.constraints_only
     global FULL_OUT
     FULL_OUT = args.full_out
@@ -610,7 +624,7 @@ def _shape_record(seg, shapes, cells, heights):
                            "log2 heights in air_names order" if SEGMENT_SHAPES == "own" else "every segment at the caps (round 5's legs)")
 
 
-def segment_bench_inproc(kind, n_segments, max_log_height, steps, warmup, logup, queries, pow_bits, n_workers, abi):
+def segment_bench_inproc(kind, n_segments, max_log_height, steps, warmup, logup, queries, pow_bits, n_workers, abi, checks=True):
     """The same strong-scaling workload as segment_bench, driven from ONE process through the C ABI's multi-device entry
     pw_prove_segments_multi: one host thread per worker (worker w on GPU w mod #GPUs) with its own launch stream and its own
     replica of the segment (trace generators, provers, buffers); placement by cells; the only exchange is the RCCL all-gather of
@@ -673,15 +687,17 @@ def segment_bench_inproc(kind, n_segments, max_log_height, steps, warmup, logup,
                note="pw_prove_segments_multi: one process, one host thread + launch stream per worker; per segment: trace generation of every AIR + one "
                     "pw-stark v1 proof (segment_workload.HonestSegment: one resident segment per worker, regenerated and proven for every unit)")
     rec["distinct_segments"] = True
+    LAST_OUTPUTS["segment_commitments"] = np.array(last["merged"], copy=True)
     prover.set_device_budget(0)
-    with torch.cuda.device(devices[0]):
-        _segment_checks(seg0, sorted(mine0), rec, shapes=shapes)
+    if checks:
+        with torch.cuda.device(devices[0]):
+            _segment_checks(seg0, sorted(mine0), rec, shapes=shapes)
     for wk in workers:
         wk.close()
     return rec
 
 
-def segment_bench(kind, n_segments, max_log_height, steps, warmup, logup, queries, pow_bits, rank, world, abi, barrier):
+def segment_bench(kind, n_segments, max_log_height, steps, warmup, logup, queries, pow_bits, rank, world, abi, barrier, checks=True):
     """Multi-AIR segments, STRONG scaling: a fixed number of independent segments is placed on the
     ranks by cell count; every rank handles its segments one after the other — trace generation of EVERY AIR of the segment (APC
     AIRs: gather + derived columns + bus replay; instruction AIRs: record expansion + replay of their lookups; periphery AIRs from
@@ -766,8 +782,9 @@ def segment_bench(kind, n_segments, max_log_height, steps, warmup, logup, querie
                     "generated traces, the 13 RV32IM instruction AIRs with the reference's real constraints / interactions on traces expanded from "
                     "records, the 3 lookup periphery AIRs from the histograms; the other 5 system AIRs of the reference's 19 (connector, program, "
                     "memory boundary, Merkle, Poseidon2: 357 of 819 columns) are external chips and are left out")
+    LAST_OUTPUTS["segment_commitments"] = np.array(last["merged"], copy=True)
     prover.set_device_budget(0)
-    if rank == 0:
+    if rank == 0 and checks:
         _segment_checks(seg, list(last["mine"]), rec, shapes=shapes)
     seg.close()
     import gc
@@ -955,6 +972,23 @@ def c3_leg(queries, pow_bits, steps=2, constraints_only_too=True, segment_too=Tr
     return rec
 
 
+LAST_OUTPUTS = {}  # name -> array: what the last timed step of the headline computed (--dump-outputs)
+DUMP_LIMIT = 64 << 20  # bytes over all files
+
+
+def dump_outputs(out_dir, rank):
+    """--dump-outputs DIR: LAST_OUTPUTS as DIR/<name>.npy in float64 (exact for u32 words), rank 0 only."""
+    if not out_dir or rank != 0:
+        return
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in LAST_OUTPUTS.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert arrays and total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes in {sorted(arrays)}"
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", a)
+
+
 def build_info():
     """How the library this process loaded was built (the driver's build() runs before the bench; *.so is git-ignored and travels
     with the snapshot): path, size, age relative to its sources, and whether hipcc is present to rebuild it here."""
@@ -1046,7 +1080,8 @@ def main():
 
     if args.shape in ("C4", "C5") and args.inproc and world == 1:
         rec = segment_bench_inproc(args.shape, args.segments, args.segment_log_height, args.steps, args.warmup, args.logup, args.queries,
-                                   args.pow_bits, max(1, args.gpus), abi)
+                                   args.pow_bits, max(1, args.gpus), abi, checks=args.full)
+        dump_outputs(args.dump_outputs, 0)
         whole = rec["value"] / max(1, args.gpus) * ALGO_BYTES_PER_CELL / 1e9
         emit(dict(
             metric="STARK cells/sec (trace rows x cols), multi-segment " + ("guest-pairing-shaped" if args.shape == "C4" else "reth-shaped")
@@ -1065,7 +1100,8 @@ def main():
     if args.shape in ("C4", "C5"):
         # BASELINE configs[3] / configs[4]: multi-AIR segments sharded over the GPUs of the node, strong scaling
         rec = segment_bench(args.shape, args.segments, args.segment_log_height, args.steps, args.warmup, args.logup, args.queries,
-                            args.pow_bits, rank, world, abi, barrier)
+                            args.pow_bits, rank, world, abi, barrier, checks=args.full)
+        dump_outputs(args.dump_outputs, rank)
         jit_cache = jit_cache_by_rank(world)
         if rank == 0:
             whole = rec["value"] / world * ALGO_BYTES_PER_CELL / 1e9
@@ -1166,6 +1202,17 @@ def main():
     phase("headline: warm-up + timed steps start")
     elapsed, timing = timed_leg(run_steps, args.steps, max(args.warmup, len(workers) if args.warmup else 0), barrier, abi, world)
     phase("headline: done")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed step: the proof words, the periphery histograms, and the trace (a fixed
+        # seeded sample of its cells: the whole of it is 8 GB at C2). Taken now, before any other leg reuses the buffers.
+        LAST_OUTPUTS["proof_words"] = np.array(last["proof"], copy=True)
+        per = main_worker["per"]
+        for name in ("var_hist", "tuple_hist", "bitwise_hist"):
+            LAST_OUTPUTS["periphery_" + name] = getattr(per, name).cpu().numpy().view(np.uint32)
+        flat = main_worker["out"].reshape(-1)
+        pick = np.sort(np.random.default_rng(20261015).integers(0, flat.numel(), size=min(flat.numel(), 1 << 20), dtype=np.int64))
+        LAST_OUTPUTS["trace_sample"] = flat[torch.from_numpy(pick).to(flat.device)].cpu().numpy().view(np.uint32)
+    dump_outputs(args.dump_outputs, rank)
     per_rank_ms = [t / args.steps * 1e3 for t in LAST_PER_RANK_S]
     cells_per_step = wl["W"] * wl["H"]
     total_cells = cells_per_step * args.steps * world

@@ -7,7 +7,8 @@ ROOT = Path(__file__).resolve().parent.parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-REFERENCE = Path("/root/reference")
+# the reference checkout's data fixtures the tests read, under their paths there (tests/golden/make_reference_fixtures.py)
+REFERENCE_FIXTURES = ROOT / "tests" / "golden" / "reference_fixtures.tar.gz"
 
 # the test suite keeps the specialised kernels' code objects under the system temporary directory instead of ~/.cache/powdr_jit
 # (the product's default): nothing outside the repository and /tmp is written by running the tests
@@ -38,10 +39,18 @@ def pytest_configure(config):
 
 
 @pytest.fixture(scope="session")
-def reference_dir():
-    if not REFERENCE.exists():
-        pytest.skip("/root/reference is not mounted on this machine")
-    return REFERENCE
+def reference_dir(tmp_path_factory):
+    """REFERENCE_FIXTURES unpacked once per session into a temporary directory (regular files under relative paths only)."""
+    import tarfile
+
+    out = tmp_path_factory.mktemp("reference")
+    with tarfile.open(REFERENCE_FIXTURES) as tar:
+        for m in tar.getmembers():
+            assert m.isfile() and not m.name.startswith("/") and ".." not in Path(m.name).parts, m.name
+            dst = out / m.name
+            dst.parent.mkdir(parents=True, exist_ok=True)
+            dst.write_bytes(tar.extractfile(m).read())
+    return out
 
 
 def pytest_collection_modifyitems(config, items):

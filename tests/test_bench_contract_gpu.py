@@ -60,7 +60,8 @@ def check_line(stdout, full_path):
 
 
 def run_bench(*extra, env=None, argv_prefix=None, base=("--log-height", "12", "--steps", "2", "--warmup", "1", "--cpu-log-height", "8"), timeout=900):
-    """Runs bench.py, checks the stdout line (check_line) and returns the FULL record of the run (bench_full.json, --full-out)."""
+    """Runs bench.py --full (every leg and check, which these tests read), checks the stdout line (check_line) and returns the FULL
+    record of the run (bench_full.json, --full-out)."""
     import tempfile
 
     if "torch" in sys.modules:  # this process's cached HBM back to the device: the ranks of the run below share it with us
@@ -70,7 +71,7 @@ def run_bench(*extra, env=None, argv_prefix=None, base=("--log-height", "12", "-
         sys.modules["torch"].cuda.empty_cache()
     with tempfile.TemporaryDirectory() as td:
         fp = Path(td) / "bench_full.json"
-        cmd = (argv_prefix or [sys.executable]) + [str(ROOT / "bench.py"), *base, "--full-out", str(fp), *extra]
+        cmd = (argv_prefix or [sys.executable]) + [str(ROOT / "bench.py"), "--full", *base, "--full-out", str(fp), *extra]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
         assert out.returncode == 0, out.stderr[-3000:]
         assert len(out.stderr) < 4000, out.stderr[-1000:]  # the driver's tail holds stdout AND stderr: nothing large may follow the line
@@ -262,3 +263,36 @@ def test_inproc_eight_workers_on_one_device():
     ms = d["multi_segment"]
     assert d["n_gpus"] == 8 and ms["workers"] == 8 and ms["devices"] == [0] * 8 and sum(ms["segments_per_worker"]) == 8
     assert ms["verify_rc"] == 0 and ms["constraint_violations"] == 0 and ms["distinct_segments"] is True
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full: the headline's set-up, warm-up and timed steps, nothing else (no CPU baseline, no other legs, no segment checks);
+    --steps sets the timed steps. --dump-outputs writes what the last timed step computed, and two runs with the same arguments write
+    the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        full = run_bench_plain("--dump-outputs", str(d), full_out=tmp_path / f"full{k}.json")
+        assert full["steps"] == 3 and full["warmup"] == 1 and full["ms_per_step"] > 0
+        assert abs(full["value"] - full["config"]["rows"] * full["config"]["cols"] / (full["ms_per_step"] * 1e-3)) < 1e-3 * full["value"]
+        for leg in ("cpu_baseline", "constraints_only", "logup", "multi_segment", "c3", "tracegen_callmajor", "tracegen_from_records",
+                    "hbm_copy_GBps_measured"):
+            assert full.get(leg) is None, leg
+        files = sorted(p.name for p in d.glob("*.npy"))
+        assert files == ["periphery_bitwise_hist.npy", "periphery_tuple_hist.npy", "periphery_var_hist.npy", "proof_words.npy", "trace_sample.npy"]
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert len(arrays["proof_words.npy"]) * 4 == full["config"]["proof_bytes"] and arrays["periphery_var_hist.npy"].sum() > 0
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def run_bench_plain(*extra, full_out):
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--log-height", "12", "--steps", "3", "--warmup", "1", "--full-out", str(full_out),
+                          *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    c, full = check_line(out.stdout, full_out)
+    return full

@@ -102,3 +102,28 @@ def test_a_record_that_cannot_be_shrunk_still_prints_a_line(bench, canned, tmp_p
     bench.emit(full)
     out = capsys.readouterr()
     assert len([l for l in out.out.splitlines() if l.strip()]) == 1 and "contract fields only" in out.err
+
+
+def test_extras_run_only_with_full(bench, monkeypatch):
+    """A plain run measures the headline only: every leg, baseline and extra measurement is behind --full (each --no-* still applies)."""
+    extras = ("no_cpu_baseline", "no_logup_leg", "no_callmajor_leg", "no_live_pmc", "no_copy_ceiling", "no_segment_leg", "no_c3_leg")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None and all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-c3-leg", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full and a.no_c3_leg and a.dump_outputs == "out" and not any(getattr(a, k) for k in extras if k != "no_c3_leg")
+
+
+def test_dump_outputs_writes_float64_within_the_limit(bench, monkeypatch, tmp_path):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "LAST_OUTPUTS", {"proof_words": np.array([0, 1, 0x78000000], np.uint32)})
+    bench.dump_outputs(str(tmp_path / "d"), 1)  # ranks other than 0 write nothing
+    assert not (tmp_path / "d").exists()
+    bench.dump_outputs(str(tmp_path / "d"), 0)
+    a = np.load(tmp_path / "d" / "proof_words.npy")
+    assert a.dtype == np.float64 and a.tolist() == [0, 1, 0x78000000]
+    monkeypatch.setattr(bench, "LAST_OUTPUTS", {"big": np.zeros((64 << 20) // 8 + 1, np.uint32)})
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), 0)

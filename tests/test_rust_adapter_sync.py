@@ -2,6 +2,7 @@
 keeps it honest against the C headers it binds: every symbol a header declares has an `extern "C"` declaration with the
 same number of parameters, nothing extra is declared, and every `#[repr(C)]` struct lists the header struct's fields in
 the same order. The first block must also match the reference's own FFI (openvm/src/cuda_abi.rs:8-64) name for name."""
+import json
 import re
 from pathlib import Path
 
@@ -69,14 +70,11 @@ def test_repr_c_structs_list_the_header_fields_in_order():
 
 
 def test_reference_ffi_names_are_unchanged(reference_dir):
-    ref = (reference_dir / "openvm" / "src" / "cuda_abi.rs").read_text()
-    block = ref[ref.index('extern "C"'):ref.index("#[repr(C)]")]
-    ref_fns = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (\w+)\s*\((.*?)\)\s*->", block, flags=re.S)}
+    # the parameter names of the reference's extern "C" block in openvm/src/cuda_abi.rs (tests/golden/make_reference_fixtures.py)
+    ref_fns = json.loads((reference_dir / "reference_interfaces.json").read_text())["cuda_abi_extern_c_params"]
     assert set(ref_fns) == {"_apc_tracegen", "_apc_apply_derived_expr", "_apc_apply_bus"}
     mine = rust_functions()
-    strip = lambda s: re.sub(r"//[^\n]*", "", s)
-    for name, params in ref_fns.items():
-        ref_names = re.findall(r"(\w+)\s*:", strip(params))
+    for name, ref_names in ref_fns.items():
         my_params = re.search(r"pub fn " + name + r"\s*\((.*?)\)\s*->", FFI, flags=re.S).group(1)
         assert re.findall(r"(\w+)\s*:", my_params) == ref_names, name
         assert mine[name] == len(ref_names)
@@ -99,9 +97,8 @@ def test_every_isa_member_the_crate_uses_exists(reference_dir):
     """round 3 called `ISA::create_dummy_chip_complex_hip`, which `OpenVmISA` does not have. Every member taken from
     `OpenVmISA` must exist in the reference's isa.rs; every member taken from the crate's own extension trait `OpenVmIsaHip` must be
     declared in src/isa_hip.rs; a bare `ISA::member` is not allowed (it would not say which trait it means)."""
-    isa_rs = (reference_dir / "openvm" / "src" / "isa.rs").read_text()
-    trait = isa_rs[isa_rs.index("pub trait OpenVmISA"):]
-    upstream = set(re.findall(r"\bfn (\w+)", trait)) | set(re.findall(r"\btype (\w+)", trait))
+    # the members of the reference's `OpenVmISA` trait in openvm/src/isa.rs (tests/golden/make_reference_fixtures.py)
+    upstream = set(json.loads((reference_dir / "reference_interfaces.json").read_text())["openvm_isa_members"])
     src = _rust_sources()
     ext = src["isa_hip.rs"]
     ext_trait = ext[ext.index("pub trait OpenVmIsaHip"):]
