@@ -158,14 +158,21 @@ int pw_prove_segment(const PwSegmentAir* airs, size_t n_airs, int logup, const u
  * trace was overwritten; returns the number of AIRs. */
 int pw_prove_segment_consuming(const PwSegmentAir* airs, size_t n_airs, int logup, const uint32_t** proof_words, size_t* n_words);
 size_t pw_segment_last_modes(uint32_t* out, size_t cap);
-/* The memory plan of the calling thread's last segment proof (bytes; zero when the mode was forced by POWDR_STREAM_LOG_BLOCKS):
+/* The memory plan of the calling thread's last segment proof (bytes; zero when the modes were forced by POWDR_STREAM_LOG_BLOCKS or,
+ * AIR by AIR, POWDR_STREAM_LOG_BLOCKS_BY_AIR):
  * with every AIR resident | as chosen | what the policy had to work with (free + held, head room, pw_set_device_budget). */
 void pw_segment_last_plan(size_t* resident_bytes, size_t* planned_bytes, size_t* available_bytes);
+/* Device bytes the calling thread's segment context holds now (mixed trees, injected digests, FRI layers, tables, parked sponge
+ * states). After a segment proof, this + pw_prover_device_bytes of its provers is what the call left allocated: at most the
+ * planned bytes of pw_segment_last_plan. */
+size_t pw_segment_context_bytes(void);
 
-/* Device memory the provers of this process may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
- * POWDR_DEVICE_BUDGET_BYTES read once). A proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove;
- * segments: the largest AIRs first), exactly as when the device itself is short: an embedder that shares a GPU between engines
- * sets this instead of relying on hipMemGetInfo at the moment of the call. */
+/* Device memory ONE proof call may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
+ * POWDR_DEVICE_BUDGET_BYTES read once). It is applied per call, to what that call's provers and (segments) the calling thread's
+ * segment context hold: a proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove; segments:
+ * the largest AIRs first), exactly as when the device itself is short. Calls that run at the same time each get the whole budget:
+ * an embedder that shares a GPU between engines sets this instead of relying on hipMemGetInfo at the moment of the call, and one
+ * that runs N proofs at once on a device sets its share divided by N. */
 void pw_set_device_budget(size_t bytes);
 size_t pw_get_device_budget(void);
 

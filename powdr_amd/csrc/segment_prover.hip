@@ -43,6 +43,9 @@ struct SegCtx {
     std::vector<uint32_t> proof;
     size_t last_plan[3] = {0, 0, 0};   // bytes of the last call's plan: all AIRs resident | as chosen | what the policy had to work with
     std::vector<uint32_t> last_modes;  // per AIR of the last call: log2(sub-cosets) | 0x100 if the trace was eaten (pw_segment_last_modes)
+    // the byte tables the last call's memory policy planned with (pw::plan_segment_streams; tests: pw_segment_last_plan_tables)
+    std::vector<size_t> plan_resident, plan_streamed;
+    std::vector<int> plan_b_max;
     // side streams for the per-AIR stages of a segment with many AIRs (fork from / join into the caller's stream by events)
     hipStream_t side[kMaxSide] = {};
     hipEvent_t fork_ev = nullptr, done_ev[kMaxSide] = {};
@@ -125,6 +128,35 @@ int ensure_air(PwProver* p, const Shape& s, bool logup, CommitLayout& Lc) {
 
 }  // namespace
 
+namespace pw {
+// The streaming plan of a segment under a device budget, as a pure function of byte tables (CPU tests: pw_segment_stream_plan).
+// resident[a]: AIR a with its LDE resident; streamed[a * 5 + b - 1]: streamed over 2^b sub-cosets (incl. its level's parked sponge
+// states); b_max[a]: 0 = may not be streamed, else the most log2(sub-cosets) it may take. Round by round: first the largest AIRs with
+// TWO sub-cosets each until the segment fits; only when every AIR that may be streamed is, four sub-cosets (largest first again), and
+// so on. (Round 5's order — one AIR taken to 32 sub-cosets before the next is touched — cost a C4 segment under a 0.8 budget 905 ms
+// instead of 452: a sub-coset pass has a fixed cost per column, and 2 sub-cosets of three AIRs re-read far less than 32 of one.
+// profiles/r06_c4_budget_sweep.txt.) Equal sizes keep index order. sbv[a] := log2(sub-cosets) (0 = resident); returns the bytes
+// planned, own + what every AIR needs in its mode: more than avail when nothing more helps.
+size_t plan_segment_streams(size_t A, const size_t* resident, const size_t* streamed, const int* b_max, size_t own, size_t avail, int* sbv) {
+    std::vector<size_t> bytes(resident, resident + A), order(A);
+    size_t need = own;
+    for (size_t a = 0; a < A; ++a) { need += bytes[a]; sbv[a] = 0; order[a] = a; }
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return bytes[x] > bytes[y]; });
+    for (int b = 1; b <= 5 && need > avail; ++b) {
+        for (size_t k = 0; k < A && need > avail; ++k) {
+            const size_t a = order[k];
+            if (b > b_max[a]) continue;
+            const size_t nb = streamed[a * 5 + (b - 1)];
+            if (nb >= bytes[a]) continue;
+            need = need - bytes[a] + nb;
+            bytes[a] = nb;
+            sbv[a] = b;
+        }
+    }
+    return need;
+}
+}  // namespace pw
+
 // honour_flags: pw_prove_segment_consuming — PwSegmentAir::flags is read (PW_AIR_HAND_OVER); pw_prove_segment ignores the word
 // (callers of the older struct left it uninitialised)
 static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup_flag, bool honour_flags, const uint32_t** proof_words,
@@ -151,6 +183,20 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         for (size_t a = 0; a < A; ++a) seen[a] = airs[a].prover;
         std::sort(seen.begin(), seen.end());
         if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return (int)hipErrorInvalidValue;
+    }
+    // POWDR_STREAM_LOG_BLOCKS_BY_AIR=b0,b1,... (tests): the mode of every AIR of the call, 0 = resident, clamped to what the AIR may
+    // take (ignored for AIRs too short to stream); before POWDR_STREAM_LOG_BLOCKS. A list of another length is refused here, before
+    // any trace is touched.
+    std::vector<int> by_air;
+    if (const char* e = getenv("POWDR_STREAM_LOG_BLOCKS_BY_AIR")) {
+        for (const char* c = e; *c;) {
+            char* end = nullptr;
+            const long v = strtol(c, &end, 10);
+            if (end == c || v < 0 || (*end && *end != ',')) return (int)hipErrorInvalidValue;
+            by_air.push_back((int)std::min<long>(v, 31));
+            c = *end ? end + 1 : end;
+        }
+        if (by_air.size() != A) return (int)hipErrorInvalidValue;
     }
     (void)hipGetLastError();
     hipStream_t st = stream();
@@ -257,10 +303,13 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     // ---- which AIRs are streamed (sbv[a] = log2 of the number of sub-cosets, 0 = LDE resident) ------------------------------
     std::vector<int> sbv(A, 0);
     cx.last_plan[0] = cx.last_plan[1] = cx.last_plan[2] = 0;
+    cx.plan_resident.clear(); cx.plan_streamed.clear(); cx.plan_b_max.clear();
     {
         auto may_stream = [&](size_t a) { return sh[a].log_h >= 3; };  // (AIRs that share a height: their level is hashed run by run)
         auto b_max = [&](size_t a) { return std::min((int)sh[a].log_h - 1, 5); };
-        if (const char* e = getenv("POWDR_STREAM_LOG_BLOCKS")) {  // forced (tests): every AIR that may be streamed is
+        if (!by_air.empty()) {  // forced per AIR (tests: mixed levels)
+            for (size_t a = 0; a < A; ++a) if (may_stream(a) && by_air[a] > 0) sbv[a] = std::min(by_air[a], b_max(a));
+        } else if (const char* e = getenv("POWDR_STREAM_LOG_BLOCKS")) {  // forced (tests): every AIR that may be streamed is
             const int v = atoi(e);
             for (size_t a = 0; a < A && v > 0; ++a) if (may_stream(a)) sbv[a] = std::min(v, b_max(a));
         } else {
@@ -271,31 +320,22 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                 // (streamed; a handed-over trace needs no tcoef) would (not the one-AIR plan, which counts trees and FRI layers
                 // per AIR that a segment shares)
                 const size_t own = (n_trees * tree_words + fri_words) * 4 + (Nmax + 1) * 32 + ext_words * sizeof(bb::Ext) + misc_bytes;
+                std::vector<size_t>& resident = cx.plan_resident;
+                std::vector<size_t>& streamed = cx.plan_streamed;
+                std::vector<int>& bm = cx.plan_b_max;
+                resident.assign(A, 0); streamed.assign(A * 5, 0); bm.assign(A, 0);
                 size_t need = own;
-                std::vector<size_t> bytes(A);
-                for (size_t a = 0; a < A; ++a) { bytes[a] = plan_air(airs[a].prover, sh[a], lg).total(); need += bytes[a]; }
+                for (size_t a = 0; a < A; ++a) {
+                    resident[a] = plan_air(airs[a].prover, sh[a], lg).total();
+                    need += resident[a];
+                    if (!may_stream(a) || sh[a].log_h < stream_min_log_height()) continue;
+                    bm[a] = b_max(a);
+                    for (int b = 1; b <= bm[a]; ++b)  // + the parked sponge states of its level (cx.state)
+                        streamed[a * 5 + (b - 1)] = proof_plan_bytes(airs[a].prover, sh[a].log_h, b, handed[a] != 0) + (size_t)16 * 4 * ((size_t)1 << sh[a].logN);
+                }
                 cx.last_plan[0] = need;  // everything resident
                 cx.last_plan[2] = avail;
-                // Round by round: first the largest AIRs with TWO sub-cosets each until the segment fits; only when every AIR that may be
-                // streamed is, four sub-cosets (largest first again), and so on. (Round 5's order — one AIR taken to 32 sub-cosets before
-                // the next is touched — cost a C4 segment under a 0.8 budget 905 ms instead of 452: a sub-coset pass has a fixed cost per
-                // column, and 2 sub-cosets of three AIRs re-read far less than 32 of one. profiles/r06_c4_budget_sweep.txt)
-                std::vector<size_t> order(A);
-                for (size_t a = 0; a < A; ++a) order[a] = a;
-                std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return bytes[x] > bytes[y]; });
-                for (int b = 1; b <= 5 && need > avail; ++b) {
-                    for (size_t k = 0; k < A && need > avail; ++k) {
-                        const size_t a = order[k];
-                        if (!may_stream(a) || sh[a].log_h < stream_min_log_height() || b > b_max(a)) continue;
-                        size_t nb = proof_plan_bytes(airs[a].prover, sh[a].log_h, b, handed[a] != 0);
-                        nb += (size_t)16 * 4 * ((size_t)1 << sh[a].logN);  // + the parked sponge states of its level (cx.state)
-                        if (nb >= bytes[a]) continue;
-                        need = need - bytes[a] + nb;
-                        bytes[a] = nb;
-                        sbv[a] = b;
-                    }
-                }
-                cx.last_plan[1] = need;  // as planned
+                cx.last_plan[1] = plan_segment_streams(A, resident.data(), streamed.data(), bm.data(), own, avail, sbv.data());  // as planned
             }
         }
     }
@@ -751,16 +791,43 @@ extern "C" int pw_prove_segment_consuming(const PwSegmentAir* airs, size_t n_air
     return prove_segment_impl(airs, n_airs, logup_flag, true, proof_words, n_words);
 }
 
-// the mode the AIRs of the calling thread's LAST segment proof ran in: out[a] = log2 of the number of sub-cosets (0 = resident),
-// + 0x100 when the trace was overwritten by its coefficient arrays (pw_trace_from_coefficients restores it)
 extern "C" void pw_segment_last_plan(size_t* resident_bytes, size_t* planned_bytes, size_t* available_bytes) {
     if (resident_bytes) *resident_bytes = g_ctx.last_plan[0];
     if (planned_bytes) *planned_bytes = g_ctx.last_plan[1];
     if (available_bytes) *available_bytes = g_ctx.last_plan[2];
 }
 
+// the mode the AIRs of the calling thread's LAST segment proof ran in: out[a] = log2 of the number of sub-cosets (0 = resident),
+// + 0x100 when the trace was overwritten by its coefficient arrays (pw_trace_from_coefficients restores it); out may be NULL (count only)
 extern "C" size_t pw_segment_last_modes(uint32_t* out, size_t cap) {
     const std::vector<uint32_t>& m = g_ctx.last_modes;
-    for (size_t a = 0; a < m.size() && a < cap; ++a) out[a] = m[a];
+    for (size_t a = 0; out && a < m.size() && a < cap; ++a) out[a] = m[a];
     return m.size();
+}
+
+// device bytes the calling thread's segment context holds (the mixed trees, injected digests, FRI layers, tables, parked sponge states):
+// with pw_prover_device_bytes of its provers, what a segment proof keeps allocated after the call
+extern "C" size_t pw_segment_context_bytes(void) {
+    const SegCtx& cx = g_ctx;
+    return cx.dig.bytes + cx.inject.bytes + cx.ext.bytes + cx.misc.bytes + cx.state.bytes;
+}
+
+// ---- test hooks (not declared in include/: the CPU tests of the memory policy) ----------------------------------------------------
+// pw::plan_segment_streams on caller-made tables (streamed: n x 5; b_max: 0 = may not stream); returns the bytes planned
+extern "C" size_t pw_segment_stream_plan(size_t n, const size_t* resident, const size_t* streamed, const int* b_max, size_t own, size_t avail,
+                                         int* sbv) {
+    return pw::plan_segment_streams(n, resident, streamed, b_max, own, avail, sbv);
+}
+
+// the tables the calling thread's last segment proof planned with (empty when no policy ran: forced modes, no device information);
+// returns the number of AIRs, fills up to cap of them
+extern "C" size_t pw_segment_last_plan_tables(size_t* resident, size_t* streamed, int* b_max, size_t cap) {
+    const SegCtx& cx = g_ctx;
+    const size_t n = cx.plan_resident.size();
+    for (size_t a = 0; a < n && a < cap; ++a) {
+        if (resident) resident[a] = cx.plan_resident[a];
+        if (b_max) b_max[a] = cx.plan_b_max[a];
+        for (int b = 0; streamed && b < 5; ++b) streamed[a * 5 + b] = cx.plan_streamed[a * 5 + b];
+    }
+    return n;
 }

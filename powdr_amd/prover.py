@@ -18,7 +18,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_lde_batch", "pw_lde_fused", "pw_lde_subcoset", "pw_merkle_commit", "pw_poseidon2_permute_host",
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
-                  "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise"]
+                  "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
+                  "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -47,6 +48,12 @@ lib.pw_lde_subcoset.restype = C.c_int
 lib.pw_lde_subcoset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.pw_segment_last_modes.restype = C.c_size_t
 lib.pw_segment_last_modes.argtypes = [C.c_void_p, C.c_size_t]
+lib.pw_segment_context_bytes.restype = C.c_size_t
+lib.pw_segment_context_bytes.argtypes = []
+lib.pw_segment_stream_plan.restype = C.c_size_t
+lib.pw_segment_stream_plan.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+lib.pw_segment_last_plan_tables.restype = C.c_size_t
+lib.pw_segment_last_plan_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
 lib.pw_set_device_budget.restype = None
 lib.pw_set_device_budget.argtypes = [C.c_size_t]
 lib.pw_get_device_budget.restype = C.c_size_t
@@ -231,6 +238,34 @@ def segment_last_plan():
     a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
     lib.pw_segment_last_plan(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def segment_context_bytes() -> int:
+    """pw_segment_context_bytes: device bytes this thread's segment context holds (with its provers' bytes: <= the planned bytes)."""
+    return int(lib.pw_segment_context_bytes())
+
+
+def segment_stream_plan(resident, streamed, b_max, own: int, avail: int):
+    """The segment memory policy on given byte tables (test hook pw_segment_stream_plan): resident[n], streamed[n x 5] (column b - 1:
+    2^b sub-cosets), b_max[n] (0 = may not stream) -> (log2 sub-cosets per AIR, bytes planned)."""
+    n = len(resident)
+    r = np.ascontiguousarray(resident, dtype=np.uint64)
+    s = np.ascontiguousarray(streamed, dtype=np.uint64).reshape(n, 5)
+    b = np.ascontiguousarray(b_max, dtype=np.int32)
+    out = np.zeros(max(n, 1), np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    need = int(lib.pw_segment_stream_plan(n, vp(r), vp(s), vp(b), int(own), int(avail), vp(out)))
+    return out[:n].tolist(), need
+
+
+def segment_last_plan_tables():
+    """The byte tables this thread's last segment proof planned with: (resident[n], streamed[n x 5], b_max[n]); n = 0 when no policy
+    ran (forced modes)."""
+    n = int(lib.pw_segment_last_plan_tables(None, None, None, 0))
+    r, s, b = np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 5), np.uint64), np.zeros(max(n, 1), np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    lib.pw_segment_last_plan_tables(vp(r), vp(s), vp(b), n)
+    return r[:n].tolist(), s[:n].tolist(), b[:n].tolist()
 
 
 def specialise_all(provers) -> int:

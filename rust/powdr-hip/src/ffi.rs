@@ -310,13 +310,16 @@ extern "C" {
     /// Same proof, same words; AIRs flagged `PW_AIR_HAND_OVER` that are proven STREAMED keep their coefficient arrays in the caller's buffer.
     pub fn pw_prove_segment_consuming(airs: *const PwSegmentAir, n_airs: usize, logup: c_int, proof_words: *mut *const u32,
                                       n_words: *mut usize) -> c_int;
-    /// per AIR of the calling thread's last segment proof: log2(#sub-cosets) | 0x100 if the trace was overwritten
     /// the specialised kernels of n provers in one concurrent compile batch, whatever the heights; returns how many are specialised
     pub fn pw_provers_specialise(provers: *const *mut PwProver, n: usize) -> usize;
+    /// per AIR of the calling thread's last segment proof: log2(#sub-cosets) | 0x100 if the trace was overwritten (out may be null)
     pub fn pw_segment_last_modes(out: *mut u32, cap: usize) -> usize;
     /// bytes of the last segment proof's memory plan: all AIRs resident | as chosen | available to the policy
     pub fn pw_segment_last_plan(resident_bytes: *mut usize, planned_bytes: *mut usize, available_bytes: *mut usize);
-    /// bytes the provers of this process may plan for on a device (0 = what the device has free)
+    /// device bytes the calling thread's segment context holds (with its provers' bytes: at most the planned bytes)
+    pub fn pw_segment_context_bytes() -> usize;
+    /// bytes ONE proof call may plan for, over what its provers and the thread's segment context hold (0 = what the device has
+    /// free); concurrent calls each get the whole budget
     pub fn pw_set_device_budget(bytes: usize);
     pub fn pw_get_device_budget() -> usize;
     pub fn pw_verify_segment(cfg: *const PwStarkConfig, airs: *const PwAirDescription, n_airs: usize, logup: c_int,

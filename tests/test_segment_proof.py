@@ -244,14 +244,20 @@ def test_streamed_airs_that_share_a_height(gpu, monkeypatch, logup, log_blocks, 
 
 
 # ---- traces handed over per AIR (pw_prove_segment_consuming) ----------------------------------------------------------
-def hip_segment_consuming(gpu, airs, nq, pow_bits, logup, mask):
+def hip_segment_consuming(gpu, airs, nq, pow_bits, logup, mask, offsets=None):
     """pw_prove_segment_consuming with the AIRs of `mask` handed over -> (words, modes). Checks what the call promises about the
     buffers: a handed-over trace that was streamed holds its coefficient arrays afterwards and pw_trace_from_coefficients restores
-    it exactly; every other trace is untouched; a second proof on the restored traces gives the same words."""
+    it exactly; every other trace is untouched; a second proof on the restored traces gives the same words. offsets: per AIR, the
+    trace starts that many words into its allocation (only 4-byte aligned when odd)."""
     torch, abi, prover = gpu
     provers = [prover.Prover(a[1], a[3], a[4], num_queries=nq, pow_bits=pow_bits, interactions=a[5] if logup else None) for a in airs]
+    offsets = offsets or [0] * len(airs)
     orig = [to_dev(torch, a[0]) for a in airs]
-    traces = [t.clone() for t in orig]
+    traces = []
+    for t, o in zip(orig, offsets):
+        buf = torch.zeros(t.numel() + o, dtype=t.dtype, device=t.device)
+        buf[o:] = t
+        traces.append(buf[o:])
     seg = [(pr, t.data_ptr(), a[2]) for pr, t, a in zip(provers, traces, airs)]
     out = []
     for _ in range(2):
@@ -307,6 +313,25 @@ def test_hip_segment_consuming_words_equal_the_oracle(gpu, monkeypatch, spec, nq
     pr.close()
 
 
+def check_the_real_plan(modes):
+    """This thread's last segment proof under the memory policy: its modes are what the policy makes of the byte tables it planned
+    with (the restated rule, the library's pure function), in round-by-round order; planned == resident when nothing is streamed."""
+    from powdr_amd import prover
+    from tests.test_segment_plan import check_round_order, model_plan
+
+    resident, streamed, b_max = prover.segment_last_plan_tables()
+    res_plan, planned, avail = prover.segment_last_plan()
+    assert len(resident) == len(modes) and res_plan >= sum(resident)
+    own = res_plan - sum(resident)
+    sbv = [b for b, _ in modes]
+    assert model_plan(resident, streamed, b_max, own, avail) == (sbv, planned)
+    assert prover.segment_stream_plan(resident, streamed, b_max, own, avail) == (sbv, planned)
+    check_round_order(resident, b_max, sbv, streamed)
+    if not any(sbv):
+        assert planned == res_plan
+    return res_plan, planned, avail
+
+
 @pytest.mark.gpu
 def test_the_memory_policy_streams_the_largest_air_first_under_a_budget(gpu, monkeypatch):
     """pw_set_device_budget + the automatic policy (no POWDR_STREAM_LOG_BLOCKS): with room for everything no AIR is streamed; as the
@@ -316,25 +341,99 @@ def test_the_memory_policy_streams_the_largest_air_first_under_a_budget(gpu, mon
     spec, nq = [("C1", 600), ("T1", 5000), ("T0", 40), ("T1", 1000), ("T0", 33)], 8
     airs, want = _oracle_segment(spec, nq, 0, True)
     monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS", raising=False)
+    monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS_BY_AIR", raising=False)
     monkeypatch.setenv("POWDR_STREAM_MIN_LOG_HEIGHT", "9")
     cells = [a[1] << a[2] for a in airs]
     largest = int(np.argmax(cells))
-    seen = []
+    seen, levels = [], []
     try:
         for budget in (0, 1 << 34, 1 << 27, 1 << 26, 1 << 25, 1 << 24, 1 << 23, 1 << 22):
             prover.set_device_budget(budget)
             got, modes = hip_segment_consuming(gpu, airs, nq, 0, True, [True] * len(airs))
             assert (got == want).all(), budget
+            # (hip_segment_consuming's last call is a plain proof on the same provers: the same plan, nothing handed over)
+            check_the_real_plan(prover.segment_last_modes())
             streamed = [k for k, (b, _) in enumerate(modes) if b]
-            seen.append(streamed)
+            seen.append(set(streamed))
+            levels.append([b for b, _ in modes])
             if budget in (0, 1 << 34):
                 assert streamed == []
             if streamed:
                 assert largest in streamed
     finally:
         prover.set_device_budget(0)
-    assert any(len(x) == 1 for x in seen) or any(len(x) >= 1 for x in seen), seen
+    for a, b in zip(seen, seen[1:]):
+        assert a <= b, seen  # a smaller budget streams at least the AIRs a larger one did
+    for a, b in zip(levels, levels[1:]):
+        assert all(y >= x for x, y in zip(a, b)), levels
     assert seen[-1] and len(seen[-1]) >= len(seen[2])
+
+
+@pytest.mark.gpu
+def test_what_a_segment_proof_holds_is_what_it_planned(gpu, monkeypatch):
+    """After a segment proof on fresh provers in a fresh host thread, the device bytes its provers and the thread's segment context
+    hold are at most the planned bytes (and within the room the policy had, when the plan fits), under budgets that keep everything
+    resident, stream some AIRs or cannot be met. The device's free memory drops by at most the plan + an allowance (see below)."""
+    import threading
+
+    torch, abi, prover = gpu
+    spec, nq = [("C1", 600), ("T1", 5000), ("T0", 40), ("T1", 1000), ("T0", 33)], 8
+    airs, want = _oracle_segment(spec, nq, 0, True)
+    monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS", raising=False)
+    monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS_BY_AIR", raising=False)
+    monkeypatch.setenv("POWDR_STREAM_MIN_LOG_HEIGHT", "9")
+    monkeypatch.setenv("POWDR_JIT", "0")  # (no code objects loaded during the measured call)
+    traces = [to_dev(torch, a[0]) for a in airs]
+    torch.cuda.synchronize()
+
+    def run(out):
+        try:
+            free0 = torch.cuda.mem_get_info()[0]
+            provers = [prover.Prover(a[1], a[3], a[4], num_queries=nq, interactions=a[5]) for a in airs]
+            pf = prover.prove_segment([(pr, t.data_ptr(), a[2]) for pr, t, a in zip(provers, traces, airs)], logup=True)
+            torch.cuda.synchronize()
+            free1 = torch.cuda.mem_get_info()[0]
+            modes = prover.segment_last_modes()
+            out.update(pf=pf, modes=modes, plan=check_the_real_plan(modes), drop=free0 - free1,
+                       held=sum(pr.device_bytes() for pr in provers) + prover.segment_context_bytes())
+            for pr in provers:
+                pr.close()
+        except Exception as e:  # noqa: BLE001 - re-raised on the test's thread
+            out["error"] = e
+
+    def in_fresh_thread():
+        out = {}
+        th = threading.Thread(target=run, args=(out,))
+        th.start()
+        th.join()
+        if "error" in out:
+            raise out["error"]
+        return out
+
+    # warm-up: the twiddle tables of these heights and the runtime's own first-use allocations happen outside the measured calls
+    in_fresh_thread()
+    # Allowance for the free-memory drop: hipMalloc hands out whole 2 MiB pages (every DeviceBuf of the 5 provers and the context,
+    # and the 7 small tables a prover keeps — constraint / interaction programs — are at most one page over their size), plus
+    # 64 MiB for what the runtime takes per host thread (its 4 side streams, kernel-argument and signal pools).
+    allowance = (2 << 20) * (len(airs) * (14 + 7) + 5) + (64 << 20)
+    try:
+        kinds = set()
+        for budget in (0, 1 << 26, 1 << 25, 1 << 24, 1 << 23, 1 << 20):
+            prover.set_device_budget(budget)
+            r = in_fresh_thread()
+            assert (r["pf"] == want).all(), budget
+            res_plan, planned, avail = r["plan"]
+            assert r["held"] <= planned, (budget, r["held"], planned)
+            if planned <= avail:
+                assert r["held"] <= avail
+            if budget:
+                assert avail <= budget
+            assert r["drop"] <= planned + allowance, (budget, r["drop"], planned, allowance)
+            kinds.add("resident" if not any(b for b, _ in r["modes"]) else ("fits" if planned <= avail else "over"))
+            print(f"budget {budget}: resident {res_plan} planned {planned} avail {avail} held {r['held']} drop {r['drop']} modes {r['modes']}")
+        assert "resident" in kinds and len(kinds) >= 2, kinds  # (every budget above streams, or cannot be met, or both)
+    finally:
+        prover.set_device_budget(0)
 
 
 @pytest.mark.gpu

@@ -196,7 +196,29 @@ def test_prove_segments_multi_on_one_gpu(n_workers, steal, monkeypatch):
     """pw_prove_segments_multi with every worker on GPU 0 (one-GPU box): host threads with their own streams and prover
     replicas prove 7 segments of different sizes concurrently; commitments and proofs equal the ones made one after the
     other; the merge went through an RCCL communicator of size 1 (or says that RCCL is missing)."""
+    _multi_on_one_gpu(n_workers, steal, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("steal", [True, False])
+def test_prove_segments_multi_with_a_slow_worker(steal, monkeypatch):
+    """Worker 0's callback is slow. With stealing, the other two run dry and take the unstarted segments of worker 0's queue: at
+    least one segment is proven by a worker the plan did not give it to, and the records (proof, owner) say so. With
+    POWDR_MULTI_STEAL=0 the same slow worker proves exactly its planned segments."""
+    _multi_on_one_gpu(3, steal, monkeypatch, slow_worker0=True)
+
+
+@pytest.mark.gpu
+def test_prove_segments_multi_each_worker_plans_for_the_whole_budget(monkeypatch):
+    """pw_set_device_budget holds per proof call (include/powdr_prover.h): three workers on GPU 0 prove their segments at the same
+    time, and every call — read on its own worker thread — planned within the budget with nothing streamed, although the three
+    together hold more than the budget; the words equal the proofs made one after the other."""
+    _multi_on_one_gpu(3, False, monkeypatch, budget=True)
+
+
+def _multi_on_one_gpu(n_workers, steal, monkeypatch, slow_worker0=False, budget=False):
     import threading
+    import time
 
     import torch
     from powdr_amd import prover, synth
@@ -221,33 +243,67 @@ def test_prove_segments_multi_on_one_gpu(n_workers, steal, monkeypatch):
         a, b = s, (s + 1) % len(shapes)
         return prover.prove_segment([(provers[a], traces[a].data_ptr(), shapes[a][1]), (provers[b], traces[b].data_ptr(), shapes[b][1])], logup=True)
 
+    if budget:
+        # every AIR could be streamed (2^3 rows and up) if the policy had to share the budget among the workers
+        monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS", raising=False)
+        monkeypatch.delenv("POWDR_STREAM_LOG_BLOCKS_BY_AIR", raising=False)
+        monkeypatch.setenv("POWDR_STREAM_MIN_LOG_HEIGHT", "3")
     seq = make_provers()
-    want = [prove_with(seq, s) for s in range(len(shapes))]
+    want, resident_plan = [], []
+    for s in range(len(shapes)):
+        want.append(prove_with(seq, s))
+        resident_plan.append(prover.segment_last_plan()[0])
+    limit = int(1.25 * max(resident_plan)) if budget else 0
     hdr = 5 + 4 * 2
     per_worker = [make_provers() for _ in range(n_workers)]
-    proofs, lock = {}, threading.Lock()
+    proofs, plans, lock = {}, {}, threading.Lock()
+    cells = [(shapes[s][0] << shapes[s][1]) + (shapes[(s + 1) % 7][0] << shapes[(s + 1) % 7][1]) for s in range(7)]
+    plan = prover.assign_units(cells, n_workers)
 
     def prove_segment(s, worker, device):
         assert device == 0
+        if slow_worker0 and worker == 0:
+            # steal: wait (bounded) until the other workers have proven every other segment — worker 0's unstarted ones included;
+            # no steal: they cannot, so this is a plain 0.3 s delay per segment
+            deadline = time.time() + (60 if steal else 0.3)
+            while time.time() < deadline and len(proofs) < len(shapes) - 1:
+                time.sleep(0.01)
         pf = prove_with(per_worker[worker], s)
         with lock:
             proofs[s] = (worker, pf)
+            plans[s] = (prover.segment_last_plan(), prover.segment_last_modes())  # this worker thread's own last call
         return pf[hdr:hdr + 8]
 
-    cells = [(shapes[s][0] << shapes[s][1]) + (shapes[(s + 1) % 7][0] << shapes[(s + 1) % 7][1]) for s in range(7)]
     monkeypatch.setenv("POWDR_MULTI_STEAL", "1" if steal else "0")
-    commitments, owner, merge = prover.prove_segments_multi([0] * n_workers, cells, prove_segment)
+    if budget:
+        prover.set_device_budget(limit)
+    try:
+        commitments, owner, merge = prover.prove_segments_multi([0] * n_workers, cells, prove_segment)
+    finally:
+        if budget:
+            prover.set_device_budget(0)
     assert merge in (1, 2)
     if steal and n_workers > 1:
         # the placement by cells is the plan; a worker that runs dry steals the smallest unstarted segment of the busiest queue: whoever
         # proved a segment is reported as its owner, every segment is proven exactly once (the proofs below), by a worker that exists
         assert len(proofs) == 7 and all(0 <= int(o) < n_workers for o in owner)
+        if slow_worker0:
+            assert (plan == 0).sum() >= 2  # (worker 0 has something to be stolen)
+            assert (owner != plan).any(), (owner, plan)
     else:
-        assert (owner == prover.assign_units(cells, n_workers)).all() and len(set(owner.tolist())) == n_workers
+        assert (owner == plan).all() and len(set(owner.tolist())) == n_workers
     for s in range(7):
         assert proofs[s][0] == owner[s]
         assert (proofs[s][1] == want[s]).all()
         assert (commitments[s] == want[s][hdr:hdr + 8]).all()
+    if budget:
+        # per call: the whole budget was this call's to plan for, and it needed no streaming (3 workers x the largest resident plan
+        # is more than the budget: a process-wide budget would have streamed)
+        assert 3 * max(resident_plan) > limit
+        for s in range(7):
+            (res, planned, avail), modes = plans[s]
+            assert res == resident_plan[s] and planned == res <= avail <= limit, (s, plans[s], limit)
+            assert all(b == 0 for b, _ in modes), (s, modes)
     for ps in per_worker + [seq]:
         for p in ps:
             p.close()
