@@ -236,6 +236,15 @@ int powdr_original_row_expand_host(const PowdrOrigInstr* instr, const uint32_t* 
 int powdr_periphery_var_range_trace(const uint32_t* d_var_hist, size_t var_num_bins, PowdrFp* d_out);
 int powdr_periphery_tuple2_trace(const uint32_t* d_tuple2_hist, uint32_t tuple2_sz0, uint32_t tuple2_sz1, PowdrFp* d_out);
 int powdr_periphery_bitwise_trace(const uint32_t* d_bitwise_hist, PowdrFp* d_out);
+/* The same tables split into the part the proving key fixes and the part each proof supplies (the chips' own layout: the tuples in
+ * preprocessed columns, pw_prover_create_preprocessed; the multiplicities in the main trace). Column-major, Montgomery:
+ *   var_range_table  [value, bits] x n_bins (a power of two)     tuple2_table  [v0, v1] x sz0 * sz1     bitwise_table  [x, y, x^y] x 65 536
+ *   multiplicities   out[i] = hist[i] mod p, i < n — the var-range / tuple2 main column, and for bitwise the [range | xor] histogram
+ *                    (n = 2 x 65 536) is already the two main columns [mult_range, mult_xor]. */
+int powdr_periphery_var_range_table(size_t var_num_bins, PowdrFp* d_out);
+int powdr_periphery_tuple2_table(uint32_t tuple2_sz0, uint32_t tuple2_sz1, PowdrFp* d_out);
+int powdr_periphery_bitwise_table(PowdrFp* d_out);
+int powdr_periphery_multiplicities(const uint32_t* d_hist, size_t n, PowdrFp* d_out);
 
 /* All launches of this library go to this stream (default: the null stream,
  * like the reference, cuda/mod.rs:374-378). Pass a hipStream_t as void*. */

@@ -8,7 +8,9 @@
  *               /root/reference/openvm-riscv/src/lib.rs:327-341 (sdk.app_prover(exe).prove + verify_app_proof)
  *   engines     /root/reference/openvm/src/lib.rs:69-95 (BabyBearPoseidon2CpuEngine / ...GpuEngine)
  *   the AIR     /root/reference/openvm/src/powdr_extension/chip.rs:94-130 (PowdrAir::eval: current-row
- *               constraints `assert_zero(expr)`, no public values, no cached/preprocessed trace)
+ *               constraints `assert_zero(expr)`, no public values, no cached/preprocessed trace; the periphery
+ *               chips that receive its lookups DO keep their tables in preprocessed columns — segment proofs take
+ *               those through pw_prover_create_preprocessed, "pw-stark v1 + preprocessed" below)
  * The trait's method list lives in the un-vendored `openvm-stark-backend` crate, so this
  * header is the plain-C surface a third engine `E` (beside the CPU and CUDA engines) would
  * call from its `prove`: one AIR = one prover object built from the AIR's constraint
@@ -67,6 +69,28 @@ int pw_prover_set_bus_seed(PwProver* p, const uint32_t* seed8);
  * half of the expressions are small forms; POWDR_LOGUP_INTERPRET=1 at creation forces 1 (tests). */
 int pw_prover_logup_path(const PwProver* p);
 void pw_prover_destroy(PwProver* p);
+
+/* ---- preprocessed (fixed) columns: "pw-stark v1 + preprocessed"  --------------------------------------------------
+ * An AIR whose tables the proving key fixes (the periphery chips' VariableRangeCheckerAir, BitwiseOperationLookupAir<8>,
+ * RangeTupleCheckerAir<2>, openvm/src/powdr_extension/trace_generator/cuda/periphery.rs:33-85): `pre_width` fixed
+ * columns at height 2^log_height, d_pre = the fixed matrix (device, column-major, Montgomery; copied). In the constraint and
+ * interaction programs an operand c < width is main column c, width <= c < width + pre_width is preprocessed column c - width — every
+ * check of the programs (NULL for a malformed one, pw_prover_max_constraint_degree, pw_jit_compile_check with width + pre_width as the
+ * width) uses that combined bound. Other arguments as pw_prover_create_logup; interactions == NULL: a constraints-only AIR (proven in
+ * segments with logup = 0), n_interactions = 0 with tables: an AIR of a LogUp segment without interactions. At creation the prover
+ * extends and commits the fixed matrix once and keeps it, its LDE and its tree (counted by pw_prover_device_bytes).
+ * Such a prover proves in segments only, at exactly 2^log_height rows (pw_prove_segment / _consuming; another height: -1), always with
+ * its extension resident (never streamed, whatever POWDR_STREAM_LOG_BLOCKS* say; pw_segment_last_modes reports 0); pw_prover_prove,
+ * pw_prover_prove_consuming, pw_prover_trace_root and pw_prove_airs return -1. pw_prover_check_constraints reads operands >= width from
+ * the fixed matrix. The proof of a segment with at least one such AIR carries magic PWS4. */
+PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                        const uint32_t* d_pre, const uint32_t* cons_bytecode, size_t bytecode_len,
+                                        const uint32_t* cons_spans, size_t n_constraints, const uint32_t* interactions,
+                                        size_t n_interactions, const uint32_t* inter_spans, size_t n_inter_spans,
+                                        const uint32_t* inter_bytecode, size_t inter_bytecode_len);
+/* The preprocessed commitment (8 canonical words): the verifying key's part, PwAirPreprocessed::root8. -1: no preprocessed columns. */
+int pw_prover_preprocessed_root(const PwProver* p, uint32_t* root8);
+uint32_t pw_prover_preprocessed_width(const PwProver* p); /* 0: none */
 
 /* Prove one trace (column-major, width x 2^log_height, Montgomery words, device).
  * *proof_words points at host memory owned by the prover, valid until the next call. */
@@ -205,6 +229,20 @@ typedef struct PwAirDescription {
  * total_sum4 (may be NULL) receives the sum of the cumulative sums. */
 int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescription* airs, size_t n_airs, int logup,
                       const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
+
+/* The verifying key's part of an AIR with preprocessed columns: their number and pw_prover_preprocessed_root (canonical);
+ * width = 0: the AIR has none. */
+typedef struct PwAirPreprocessed {
+    uint32_t width;
+    uint32_t root8[8];
+} PwAirPreprocessed;
+
+/* pw_verify_segment for segments whose AIRs may have preprocessed columns (pre: one entry per AIR; NULL or every width 0 = exactly
+ * pw_verify_segment). Column operands of the descriptions below width + pre[i].width are valid. Additional code 16 = a preprocessed
+ * row does not open against its root; a PWS3 proof checked against a description that claims preprocessed columns, or a PWS4 proof
+ * against one that claims none, returns 1. */
+int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
+                                   int logup, const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
 
 /* Host verification of pw_prove_airs' proofs. With shared_bus_seed the seed is recomputed from the trace roots inside the
  * proofs and every proof must have used it. Returns 0; ((air index + 1) << 8) | code of the first failing proof

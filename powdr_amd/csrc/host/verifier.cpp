@@ -331,18 +331,21 @@ extern "C" int pw_verify_logup(const PwStarkConfig* cfg, uint32_t width, uint32_
 // ---- pw-stark v1: one proof per segment (protocol: oracle/stark_segment.inc; prover: csrc/segment_prover.hip) ----------
 namespace {
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3"
+constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": at least one AIR has preprocessed columns
 
 struct SegShapeV {
     uint32_t W, nc, n_int, log_h;
+    uint32_t Wf, W1;  // preprocessed columns, W + Wf
+    Digest pre_root;  // Montgomery
     size_t H, N, n_g, Wp, K, koff;
     int logN;
     std::vector<uint32_t> gstarts;
     uint32_t max_args;
 };
-}  // namespace
 
-extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescription* airs, size_t n_airs, int logup_flag,
-                                 const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+// pre: NULL = no AIR has preprocessed columns (pw_verify_segment)
+int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs, int logup_flag,
+                        const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
     if (!cfg || !airs || !n_airs || !proof) return 15;
     const bool lg = logup_flag != 0;
     const size_t A = n_airs;
@@ -354,6 +357,13 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
         SegShapeV& s = sh[a];
         if (d.log_height < 1 || d.log_height > 26 || !d.width) return 15;
         s.W = d.width; s.nc = (uint32_t)d.n_constraints; s.log_h = d.log_height; s.n_int = lg ? (uint32_t)d.n_interactions : 0;
+        s.Wf = pre ? pre[a].width : 0;
+        if ((uint64_t)s.W + s.Wf > 0xffffffffull) return 15;
+        s.W1 = s.W + s.Wf;
+        for (int k = 0; k < 8; ++k) {
+            if (s.Wf && pre[a].root8[k] >= bb::P) return 15;
+            s.pre_root.w[k] = s.Wf ? bb::to_monty(pre[a].root8[k]) : 0;
+        }
         s.H = (size_t)1 << s.log_h; s.N = 2 * s.H; s.logN = (int)s.log_h + 1;
         s.max_args = 0; s.n_g = 0; s.Wp = 0;
         for (size_t k = 0; k < d.n_constraints; ++k)
@@ -371,7 +381,7 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
             s.n_g = s.gstarts.size() - 1;
             s.Wp = 4 * (s.n_g + 1);
         }
-        s.K = (size_t)s.W + 2 * s.Wp + 8;
+        s.K = (size_t)s.W1 + 2 * s.Wp + 8;
         s.koff = K_total;
         K_total += s.K;
         if (s.logN > L) L = s.logN;
@@ -384,12 +394,21 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
     auto get_digest = [&]() { Digest d; for (auto& w : d.w) w = get_m(); return d; };
     auto get_ext = [&]() { Ext e; for (auto& w : e.c) w = get_m(); return e; };
 
-    std::vector<uint32_t> hdr = {kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries, cfg->pow_bits};
+    bool any_pre = false;
+    for (size_t a = 0; a < A; ++a) any_pre = any_pre || sh[a].Wf;
+    std::vector<uint32_t> hdr = {any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries, cfg->pow_bits};
     for (size_t a = 0; a < A; ++a) for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) hdr.push_back(x);
     for (uint32_t h : hdr) if (get() != h) return 1;
     for (size_t i = 0; i < len; ++i) if (proof[i] >= bb::P) return 13;
     Transcript ch;
     for (uint32_t h : hdr) ch.observe(bb::to_monty(h % bb::P));
+    // the verifying key's preprocessed commitments (not in the proof)
+    for (size_t a = 0; a < A; ++a) {
+        if (!sh[a].Wf) continue;
+        ch.observe(bb::to_monty((uint32_t)a % bb::P));
+        ch.observe(bb::to_monty(sh[a].Wf % bb::P));
+        ch.observe_n(sh[a].pre_root.w, 8);
+    }
 
     const Digest t_root = get_digest();
     ch.observe_n(t_root.w, 8);
@@ -411,13 +430,13 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
     for (auto& e : opened) { e = get_ext(); ch.observe_n(e.c, 4); }
     if (short_read) return 10;
 
-    // constraint identities at zeta, AIR by AIR (per-AIR layout: main | perm at zeta | quotient | perm at g zeta)
+    // constraint identities at zeta, AIR by AIR (per-AIR layout: main | preprocessed | perm at zeta | quotient | perm at g zeta)
     std::vector<Ext> gzeta(A);
     for (size_t a = 0; a < A; ++a) {
         const PwAirDescription& d = airs[a];
         const SegShapeV& s = sh[a];
         const Ext* o = &opened[s.koff];
-        const size_t K1 = (size_t)s.W + s.Wp + 8;
+        const size_t K1 = (size_t)s.W1 + s.Wp + 8;
         const uint32_t g_h = pw::field::root_of_unity((int)s.log_h), g_inv = bb::inv(g_h);
         gzeta[a] = bb::ext_scale(zeta, g_h);
         auto combine = [&](size_t base) {
@@ -432,7 +451,7 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
         Ext acc = bb::ext_zero();
         for (size_t k = 0; k < d.n_constraints; ++k) {
             Ext v;
-            if (!eval_ext(d.cons_bytecode + d.cons_spans[2 * k], d.cons_spans[2 * k + 1], o, s.W, v)) return 15;
+            if (!eval_ext(d.cons_bytecode + d.cons_spans[2 * k], d.cons_spans[2 * k + 1], o, s.W1, v)) return 15;
             acc = bb::ext_add(bb::ext_mul(acc, alpha), v);
         }
         const Ext zH = bb::ext_pow(zeta, s.H);
@@ -448,19 +467,19 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
                     const uint32_t* sp = d.inter_spans + 2 * (size_t)d.interactions[3 * i + 2];
                     Ext dd = bb::ext_add(al, bb::ext_from_base(bb::to_monty(bus % bb::P))), m, arg;
                     for (uint32_t j = 0; j < na; ++j) {
-                        if (!eval_ext(d.inter_bytecode + sp[2 + 2 * j], sp[3 + 2 * j], o, s.W, arg)) return 15;
+                        if (!eval_ext(d.inter_bytecode + sp[2 + 2 * j], sp[3 + 2 * j], o, s.W1, arg)) return 15;
                         dd = bb::ext_add(dd, bb::ext_mul(blpow[j + 1], arg));
                     }
-                    if (!eval_ext(d.inter_bytecode + sp[0], sp[1], o, s.W, m)) return 15;
+                    if (!eval_ext(d.inter_bytecode + sp[0], sp[1], o, s.W1, m)) return 15;
                     num = bb::ext_add(bb::ext_mul(num, dd), bb::ext_mul(den, m));
                     den = bb::ext_mul(den, dd);
                 }
-                const Ext qi = combine(s.W + 4 * g), qn = combine(K1 + 4 * g);
+                const Ext qi = combine(s.W1 + 4 * g), qn = combine(K1 + 4 * g);
                 sumq = bb::ext_add(sumq, qi);
                 sumq_next = bb::ext_add(sumq_next, qn);
                 acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_sub(bb::ext_mul(qi, den), num));
             }
-            const Ext phi = combine(s.W + 4 * s.n_g), phin = combine(K1 + 4 * s.n_g);
+            const Ext phi = combine(s.W1 + 4 * s.n_g), phin = combine(K1 + 4 * s.n_g);
             const Ext is_trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
             const Ext is_first = bb::ext_mul(zh, bb::ext_inv(bb::ext_sub(zeta, bb::ext_one())));
             const Ext is_last = bb::ext_mul(zh, bb::ext_inv(is_trans));
@@ -468,7 +487,7 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
             acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_trans, bb::ext_sub(bb::ext_sub(phin, phi), sumq_next)));
             acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_last, bb::ext_sub(phi, S[a])));
         }
-        const Ext qlo = combine(s.W + s.Wp), qhi = combine(s.W + s.Wp + 4);
+        const Ext qlo = combine(s.W1 + s.Wp), qhi = combine(s.W1 + s.Wp + 4);
         if (!bb::ext_eq(acc, bb::ext_mul(zh, bb::ext_add(qlo, bb::ext_mul(zH, qhi))))) return (int)((a + 1) << 8) | 2;
     }
 
@@ -476,7 +495,7 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
     std::vector<Ext> gpow(K_total), sum1(A, bb::ext_zero()), sum2(A, bb::ext_zero());
     { Ext g = bb::ext_one(); for (auto& x : gpow) { x = g; g = bb::ext_mul(g, gamma); } }
     for (size_t a = 0; a < A; ++a) {
-        const size_t K1 = (size_t)sh[a].W + sh[a].Wp + 8;
+        const size_t K1 = (size_t)sh[a].W1 + sh[a].Wp + 8;
         for (size_t k = 0; k < K1; ++k) sum1[a] = bb::ext_add(sum1[a], bb::ext_mul(gpow[sh[a].koff + k], opened[sh[a].koff + k]));
         for (size_t k = K1; k < sh[a].K; ++k) sum2[a] = bb::ext_add(sum2[a], bb::ext_mul(gpow[sh[a].koff + k], opened[sh[a].koff + k]));
     }
@@ -496,7 +515,7 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
     if (cfg->pow_bits && ch.sample_bits((int)cfg->pow_bits) != 0) return 3;
 
     // one opening of a mixed-height tree: rows[a] = AIR a's row (Montgomery), the siblings follow in the proof
-    std::vector<std::vector<uint32_t>> trow(A), prow(A), qrow(A);
+    std::vector<std::vector<uint32_t>> trow(A), frow(A), prow(A), qrow(A);
     auto check_mixed = [&](const std::vector<std::vector<uint32_t>>& rows, size_t q, const Digest& root) {
         auto level_hash = [&](size_t n, bool& any) {
             std::vector<uint32_t> cat;
@@ -531,6 +550,21 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
         for (size_t a = 0; a < A; ++a) { trow[a].resize(sh[a].W); for (auto& w : trow[a]) w = get_m(); }
         if (short_read) return 10;
         if (!check_mixed(trow, q, t_root)) return short_read ? 10 : 5;
+        // each preprocessed row at q mod N_a against that AIR's own root (a one-matrix tree of the same kind)
+        for (size_t a = 0; a < A; ++a) {
+            if (!sh[a].Wf) continue;
+            frow[a].resize(sh[a].Wf);
+            for (auto& w : frow[a]) w = get_m();
+            Digest cur = hash_row(frow[a].data(), frow[a].size());
+            size_t p = q & (sh[a].N - 1);
+            for (size_t n = sh[a].N / 2; n >= 1; n >>= 1) {
+                const Digest sib = get_digest();
+                cur = (p & n) ? compress(sib, cur) : compress(cur, sib);
+                p &= n - 1;
+            }
+            if (short_read) return 10;
+            if (!same(cur, sh[a].pre_root)) return 16;
+        }
         if (lg) {
             for (size_t a = 0; a < A; ++a) { prow[a].resize(sh[a].Wp); for (auto& w : prow[a]) w = get_m(); }
             if (!check_mixed(prow, q, p_root)) return short_read ? 10 : 11;
@@ -545,16 +579,17 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
                 if (sh[a].logN != logn) continue;
                 any = true;
                 const SegShapeV& s = sh[a];
-                const size_t K1 = (size_t)s.W + s.Wp + 8;
+                const size_t K1 = (size_t)s.W1 + s.Wp + 8;
                 const Ext* gp = &gpow[s.koff];
                 const uint32_t x = bb::mul(shift0, bb::pow_u32(pw::field::root_of_unity(logn), (uint32_t)(q & (s.N - 1))));
                 Ext a1 = bb::ext_zero(), a2 = bb::ext_zero();
                 for (size_t k = 0; k < s.W; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[k], trow[a][k]));
+                for (size_t k = 0; k < s.Wf; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W + k], frow[a][k]));
                 for (size_t k = 0; k < s.Wp; ++k) {
-                    a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W + k], prow[a][k]));
+                    a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W1 + k], prow[a][k]));
                     a2 = bb::ext_add(a2, bb::ext_scale(gp[K1 + k], prow[a][k]));
                 }
-                for (size_t k = 0; k < 8; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W + s.Wp + k], qrow[a][k]));
+                for (size_t k = 0; k < 8; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W1 + s.Wp + k], qrow[a][k]));
                 Ext t = bb::ext_mul(bb::ext_sub(a1, sum1[a]), bb::ext_inv(bb::ext_sub(bb::ext_from_base(x), zeta)));
                 if (lg) t = bb::ext_add(t, bb::ext_mul(bb::ext_sub(a2, sum2[a]), bb::ext_inv(bb::ext_sub(bb::ext_from_base(x), gzeta[a]))));
                 r = bb::ext_add(r, t);
@@ -589,6 +624,18 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
     if (total_sum4) for (int k = 0; k < 4; ++k) total_sum4[k] = bb::from_monty(total.c[k]);
     if (lg && check_balance && !bb::ext_eq(total, bb::ext_zero())) return 14;
     return 0;
+}
+}  // namespace
+
+extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescription* airs, size_t n_airs, int logup_flag,
+                                 const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+    return verify_segment_impl(cfg, airs, nullptr, n_airs, logup_flag, proof, len, check_balance, total_sum4);
+}
+
+// "pw-stark v1 + preprocessed" (DESIGN.md §5g): pre[a] = the verifying key's part of AIR a (width 0: none)
+extern "C" int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
+                                              int logup_flag, const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+    return verify_segment_impl(cfg, airs, pre, n_airs, logup_flag, proof, len, check_balance, total_sum4);
 }
 
 // Boundaries of the LogUp groups the prover and the verifier derive from an interaction table (logup_groups.hpp):

@@ -162,6 +162,58 @@ extern "C" PwProver* pw_prover_create_logup(const PwStarkConfig* cfg, uint32_t w
     return create_prover_logup(cfg, width, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true);
 }
 
+// Preprocessed (fixed) columns: the programs name them as operands width .. width + pre_width - 1, so every check of
+// the programs runs against the combined bound; the prover then keeps `width` as its main width. At creation the fixed matrix is
+// copied behind room for one trace, extended (blow-up 2, shift 31) and committed with the segment tree's own leaf sponge and
+// compression — the root is the main commitment a one-AIR segment proof of the fixed matrix would carry.
+extern "C" PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                                   const uint32_t* d_pre, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
+                                                   size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
+                                                   size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
+    if (!cfg || !width || !pre_width || !d_pre || log_height < 1 || log_height > 26 || (uint64_t)width + pre_width > 0xffffffffull) return nullptr;
+    PwProver* p = inter ? create_prover_logup(cfg, width + pre_width, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true)
+                        : create_prover(cfg, width + pre_width, bc, bc_len, spans, n_constraints, true);
+    if (!p) return nullptr;
+    p->width = width;
+    p->pre_width = pre_width;
+    p->pre_log_h = log_height;
+    const size_t H = (size_t)1 << log_height, N = 2 * H;
+    const int L = (int)log_height + 1;
+    auto fail = [&]() { (void)hipGetLastError(); pw_prover_destroy(p); return nullptr; };
+    (void)hipGetLastError();
+    if (poseidon2_upload_params()) return fail();
+    CommitLayout Lc{};
+    Lc.H = H; Lc.N = N; Lc.panel_cols = lde_panel_cols(H, pre_width);
+    if (p->pre_vals.ensure(((size_t)width + pre_width) * H * 4) || p->pre_lde.ensure((size_t)pre_width * N * 4) ||
+        p->pre_tree.ensure(merkle_words(N) * 4) || p->coef.ensure(Lc.panel_cols * H * 4) || p->misc.ensure((size_t)pre_width * 8 + 64))
+        return fail();
+    hipStream_t st = stream();
+    uint32_t* fixed = p->pre_vals.as<uint32_t>() + (size_t)width * H;
+    if (hipMemcpyAsync(fixed, d_pre, (size_t)pre_width * H * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail();
+    if (lde_matrix(p, Lc, log_height, fixed, pre_width, p->pre_lde.as<uint32_t>())) return fail();
+    std::vector<const uint32_t*> cols(pre_width);
+    for (uint32_t c = 0; c < pre_width; ++c) cols[c] = p->pre_lde.as<uint32_t>() + (size_t)c * N;
+    const uint32_t** d_cols = p->misc.as<const uint32_t*>();
+    if (hipMemcpyAsync(d_cols, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return fail();
+    std::vector<MixedLevelCols> by_log(L + 1, MixedLevelCols{nullptr, 0});
+    by_log[L] = MixedLevelCols{d_cols, pre_width};
+    if (merkle_commit_mixed(by_log.data(), L, p->pre_tree.as<uint32_t>(), nullptr)) return fail();
+    uint32_t root[8];
+    if (hipMemcpyAsync(root, p->pre_tree.as<uint32_t>() + merkle_words(N) - 8, 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail();
+    for (int k = 0; k < 8; ++k) p->pre_root[k] = bb::from_monty(root[k]);
+    return p;
+}
+
+extern "C" int pw_prover_preprocessed_root(const PwProver* p, uint32_t* root8) {
+    if (!p || !root8 || !p->pre_width) return -1;
+    for (int k = 0; k < 8; ++k) root8[k] = p->pre_root[k];
+    return 0;
+}
+
+extern "C" uint32_t pw_prover_preprocessed_width(const PwProver* p) { return p ? p->pre_width : 0; }
+
 // Code generation + hiprtc compilation of an AIR's specialised kernels WITHOUT a GPU (hiprtc cross-compiles): what
 // pw_prover_specialise would build for a prover created from the same tables. interactions == NULL: constraints only.
 extern "C" int pw_jit_compile_check(uint32_t width, const uint32_t* bc, size_t bc_len, const uint32_t* spans, size_t n_constraints,
@@ -471,6 +523,7 @@ int ensure_proof_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bo
 // Trace commitment only (LDE + Merkle root): what a segment's AIRs exchange before the bus seed can be formed.
 extern "C" int pw_prover_trace_root(PwProver* p, const uint32_t* d_trace, uint32_t log_h, uint32_t* root8) {
     if (!p || !d_trace || !root8 || log_h < 1 || log_h > 26) return (int)hipErrorInvalidValue;
+    if (p->pre_width) return -1;  // preprocessed columns are a segment-proof feature
     (void)hipGetLastError();
     TRY(poseidon2_upload_params());
     CommitLayout L;
@@ -527,7 +580,7 @@ static PwProver::OpenedMailbox* opened_mailbox(PwProver* p, size_t K) {
 extern "C" void pw_prover_destroy(PwProver* p) {
     if (!p) return;
     for (DeviceBuf* b : {&p->coef, &p->lde, &p->digests, &p->q, &p->qcoef, &p->qlde, &p->ext_arena, &p->misc, &p->perm, &p->plde, &p->qpart, &p->tcoef,
-                         &p->fscale, &p->gbuf})
+                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree})
         b->release();
     for (void* q : {(void*)p->d_inter, (void*)p->d_ixspans, (void*)p->d_icode, (void*)p->d_gstarts, (void*)p->d_iforms}) if (q) (void)hipFree(q);
     if (p->d_bytecode) (void)hipFree(p->d_bytecode);
@@ -560,7 +613,8 @@ extern "C" int pw_prover_stream_log_blocks(const PwProver* p, uint32_t log_h) {
 
 extern "C" size_t pw_prover_device_bytes(const PwProver* p) {
     return p->coef.bytes + p->lde.bytes + p->digests.bytes + p->q.bytes + p->qcoef.bytes + p->qlde.bytes +
-           p->ext_arena.bytes + p->misc.bytes + p->perm.bytes + p->plde.bytes + p->qpart.bytes + p->tcoef.bytes + p->fscale.bytes + p->gbuf.bytes;
+           p->ext_arena.bytes + p->misc.bytes + p->perm.bytes + p->plde.bytes + p->qpart.bytes + p->tcoef.bytes + p->fscale.bytes + p->gbuf.bytes +
+           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes;
 }
 
 
@@ -568,7 +622,7 @@ namespace {
 // consume: pw_prover_prove_consuming — d_trace is the caller's to give away. Only a STREAMED proof uses that: the coefficient arrays
 // of the trace end up in d_trace itself (no tcoef buffer: 62.6 GB at configs[2], which is what lets it run on 2 sub-cosets instead of 4).
 int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint32_t** proof_words, size_t* n_words, bool consume) {
-    if (!p || !d_trace || log_h < 1 || log_h > 26) return -1;
+    if (!p || !d_trace || log_h < 1 || log_h > 26 || p->pre_width) return -1;  // (preprocessed columns: segment proofs only)
     // a handed-over trace becomes a coefficient array that is read 2 / 4 words at a time (fold loads, the DEEP combination)
     if (consume && ((uintptr_t)d_trace & 15)) return (int)hipErrorInvalidValue;
     (void)hipGetLastError();
@@ -1033,9 +1087,13 @@ extern "C" int pw_trace_from_coefficients(uint32_t* d_coeffs, uint32_t width, ui
 
 extern "C" int pw_prover_check_constraints(PwProver* p, const uint32_t* d_trace, uint32_t log_h, uint64_t* n_violations,
                                            uint64_t* first_row, uint32_t* first_constraint) {
-    if (!p || !d_trace || log_h > 40) return -1;
+    if (!p || !d_trace || log_h > 40 || (p->pre_width && log_h != p->pre_log_h)) return -1;
     (void)hipGetLastError();
     const size_t H = (size_t)1 << log_h;
+    if (p->pre_width) {  // operands >= width read the fixed matrix: the trace goes in front of it
+        PW_HIP_TRY(hipMemcpyAsync(p->pre_vals.as<uint32_t>(), d_trace, (size_t)p->width * H * 4, hipMemcpyDeviceToDevice, stream()));
+        d_trace = p->pre_vals.as<uint32_t>();
+    }
     TRY(p->misc.ensure(4096));
     unsigned long long* d = p->misc.as<unsigned long long>();
     unsigned long long init[2] = {~0ull, 0ull}, res[2];

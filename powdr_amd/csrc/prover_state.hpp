@@ -14,6 +14,7 @@ namespace pw {
 constexpr uint32_t kMagic = 0x31535750u;   // "PWS1"
 constexpr uint32_t kMagic2 = 0x32535750u;  // "PWS2": with the LogUp extension
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3": one proof per segment (segment_prover.hip)
+constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": a segment proof in which at least one AIR has preprocessed columns
 
 // ---- duplex-sponge challenger on Montgomery words (spec: oracle/stark_oracle.cpp Challenger) ----
 struct Challenger {
@@ -110,6 +111,14 @@ struct PwProver {
         int n_events = 0;
     } opened_mb;
     std::vector<uint32_t> proof;
+    // preprocessed (fixed) columns (pw_prover_create_preprocessed; segment proofs only): operands width .. width +
+    // pre_width - 1 of the programs. Made once at creation: `pre_vals` = (width + pre_width) x 2^pre_log_h, the fixed matrix in its tail
+    // and, per proof, the caller's trace copied in front of it (what the LogUp kernels, the ζ openings and the mock prover read); the
+    // fixed matrix's LDE (copied behind the main columns of `lde` per proof: the quotient kernels read lde[c N + r]) and its
+    // mixed-height tree (the query siblings)
+    uint32_t pre_width = 0, pre_log_h = 0;
+    uint32_t pre_root[8] = {0};  // canonical: the verifying key's part
+    pw::DeviceBuf pre_vals, pre_lde, pre_tree;
     // host copies of the plan-compiled (xbc) programs: the source of the run-time specialised kernels (jit_codegen.hpp)
     std::vector<uint32_t> h_xcode, h_xspans, h_icode, h_ixspans, h_gstarts;
     std::vector<pw::LogupInteraction> h_inter;

@@ -74,6 +74,7 @@ thread_local SegCtx g_ctx;  // one per host thread (= per launch stream)
 
 struct Shape {
     uint32_t W, nc, n_int, n_g, Wp, M, K, log_h;
+    uint32_t Wf, W1;  // preprocessed columns, W1 = W + Wf: the columns the programs and the ζ openings see
     size_t H, N, koff;
     int logN;
 };
@@ -88,7 +89,7 @@ AirPlan plan_air(const PwProver* p, const Shape& s, bool logup) {
     AirPlan B;
     B.panel_cols = lde_panel_cols(s.H, logup ? std::max<size_t>(s.W, s.Wp) : s.W);
     B.coef = B.panel_cols * s.H * 4;
-    B.lde = (size_t)s.W * s.N * 4;
+    B.lde = (size_t)s.W1 * s.N * 4;  // the fixed matrix's LDE rides behind the main columns
     if (logup) {  // + the uncommitted per-row-sum columns of the specialised path
         B.perm = (size_t)(s.Wp + kJitExtraPermCols) * s.H * 4;
         B.plde = (size_t)(s.Wp + kJitExtraPermCols) * s.N * 4;
@@ -104,7 +105,7 @@ AirPlan plan_air(const PwProver* p, const Shape& s, bool logup) {
     B.qlde = 8 * s.N * 4;
     B.ext_arena = (3 * s.H + s.H / 4096 + 32) * sizeof(bb::Ext);  // weights | weights at g zeta | row sums + block totals
     const uint32_t n_chunks = div_up(s.H, 8192);
-    const uint32_t dot_cols = std::max({s.W, s.Wp, 8u});
+    const uint32_t dot_cols = std::max({s.W1, s.Wp, 8u});
     B.misc = (2 * (size_t)dot_cols * n_chunks + s.M + p->max_args + 64) * sizeof(bb::Ext) + 4096;  // ext_dot_columns2: two sets of partial sums
     if (s.log_h >= kDeepComboMinLogHeight) B.gbuf = (size_t)24 * s.H * 4;  // the DEEP combinations and their LDE
     return B;
@@ -173,6 +174,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         if (handed[a] && ((uintptr_t)airs[a].d_trace & 15)) return (int)hipErrorInvalidValue;
         if (!airs[a].prover || !airs[a].d_trace || airs[a].log_height < 1 || airs[a].log_height > 26) return (int)hipErrorInvalidValue;
         if (lg && !airs[a].prover->logup) return (int)hipErrorInvalidValue;  // needs the interaction tables (pw_prover_create_logup)
+        if (airs[a].prover->pre_width && airs[a].log_height != airs[a].prover->pre_log_h) return -1;  // the fixed matrix's height
         // the per-AIR device buffers live in the prover object and the AIRs of a segment run concurrently on side streams: one
         // prover cannot serve two AIRs of the same segment; one FRI / query phase means one configuration for all of them
         if (airs[a].prover->cfg.num_queries != airs[0].prover->cfg.num_queries || airs[a].prover->cfg.pow_bits != airs[0].prover->cfg.pow_bits)
@@ -248,7 +250,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         s.W = p->width; s.nc = p->n_constraints; s.log_h = airs[a].log_height;
         s.n_int = lg ? p->n_inter : 0; s.n_g = lg ? p->n_groups : 0; s.Wp = lg ? 4 * (s.n_g + 1) : 0;
         s.M = s.nc + (lg ? s.n_g + 3 : 0);
-        s.K = s.W + 2 * s.Wp + 8;
+        s.Wf = p->pre_width; s.W1 = s.W + s.Wf;
+        s.K = s.W1 + 2 * s.Wp + 8;
         s.H = (size_t)1 << s.log_h; s.N = 2 * s.H; s.logN = (int)s.log_h + 1;
         s.koff = K_total;
         K_total += s.K;
@@ -278,10 +281,14 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     size_t cols_total = 0;
     for (size_t a = 0; a < A; ++a) cols_total += std::max<size_t>({sh[a].W, sh[a].Wp, 8});
     size_t row_words = 0;  // query answers: rows of every tree
-    for (size_t a = 0; a < A; ++a) row_words += (size_t)nq * (sh[a].W + sh[a].Wp + 8);
-    const size_t n_dig = (size_t)nq * ((size_t)n_trees * L + (size_t)rounds * L) + 16;  // upper bound of digest records
+    size_t n_pre_dig = 0;  // the preprocessed trees' siblings (each AIR's own tree)
+    for (size_t a = 0; a < A; ++a) {
+        row_words += (size_t)nq * (sh[a].W1 + sh[a].Wp + 8);
+        if (sh[a].Wf) n_pre_dig += (size_t)nq * sh[a].logN;
+    }
+    const size_t n_dig = (size_t)nq * ((size_t)n_trees * L + (size_t)rounds * L) + n_pre_dig + 16;  // upper bound of digest records
     const size_t misc_bytes = cols_total * 8 + 4 * A * 8 + 2 * K_total * sizeof(bb::Ext) + (size_t)A * nq * 4 + row_words * 4 + n_dig * (8 + 32) +
-                              (size_t)nq * rounds * (8 + 16) + 4 * A * 4 + 3 * A * sizeof(GatherRowsJob) + 8192;
+                              (size_t)nq * rounds * (8 + 16) + 4 * A * 4 + 4 * A * sizeof(GatherRowsJob) + 8192;
     TRY(cx.misc.ensure(misc_bytes));
     uint32_t* d_dig = cx.dig.as<uint32_t>();
     uint32_t* d_fdig = d_dig + n_trees * tree_words;
@@ -290,7 +297,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     uint8_t* mp = cx.misc.as<uint8_t>();
     const uint32_t** d_cols = reinterpret_cast<const uint32_t**>(mp); mp += cols_total * 8;
     const uint32_t** d_sptrs = reinterpret_cast<const uint32_t**>(mp); mp += 4 * A * 8;
-    GatherRowsJob* d_jobs = reinterpret_cast<GatherRowsJob*>(mp); mp += 3 * A * sizeof(GatherRowsJob);  // query phase: one per AIR and tree
+    GatherRowsJob* d_jobs = reinterpret_cast<GatherRowsJob*>(mp); mp += 4 * A * sizeof(GatherRowsJob);  // query phase: one per AIR and tree
     uint64_t* d_offs = reinterpret_cast<uint64_t*>(mp); mp += n_dig * 8 + (size_t)nq * rounds * 8;
     bb::Ext* d_opened = reinterpret_cast<bb::Ext*>(mp); mp += K_total * sizeof(bb::Ext);
     bb::Ext* d_gpow = reinterpret_cast<bb::Ext*>(mp); mp += K_total * sizeof(bb::Ext);
@@ -305,7 +312,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     cx.last_plan[0] = cx.last_plan[1] = cx.last_plan[2] = 0;
     cx.plan_resident.clear(); cx.plan_streamed.clear(); cx.plan_b_max.clear();
     {
-        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3; };  // (AIRs that share a height: their level is hashed run by run)
+        // (AIRs that share a height: their level is hashed run by run); an AIR with preprocessed columns is always resident
+        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3 && !sh[a].Wf; };
         auto b_max = [&](size_t a) { return std::min((int)sh[a].log_h - 1, 5); };
         if (!by_air.empty()) {  // forced per AIR (tests: mixed levels)
             for (size_t a = 0; a < A; ++a) if (may_stream(a) && by_air[a] > 0) sbv[a] = std::min(by_air[a], b_max(a));
@@ -357,9 +365,18 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     auto put = [&](uint32_t canonical) { pf.push_back(canonical); };
     auto put_monty = [&](const uint32_t* w, size_t n) { for (size_t i = 0; i < n; ++i) pf.push_back(bb::from_monty(w[i])); };
     Challenger ch;
-    for (uint32_t x : {kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg.num_queries, cfg.pow_bits}) { ch.observe_canonical(x % bb::P); put(x); }
+    bool any_pre = false;
+    for (size_t a = 0; a < A; ++a) any_pre = any_pre || sh[a].Wf;
+    for (uint32_t x : {any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg.num_queries, cfg.pow_bits}) { ch.observe_canonical(x % bb::P); put(x); }
     for (size_t a = 0; a < A; ++a)
         for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) { ch.observe_canonical(x % bb::P); put(x); }
+    // the verifying key's preprocessed commitments: observed, not written
+    for (size_t a = 0; a < A; ++a) {
+        if (!sh[a].Wf) continue;
+        ch.observe_canonical((uint32_t)a % bb::P);
+        ch.observe_canonical(sh[a].Wf % bb::P);
+        for (int k = 0; k < 8; ++k) ch.observe_canonical(airs[a].prover->pre_root[k]);
+    }
 
     // mixed commitment of one matrix per AIR: matrix(a) = (device pointer, width); heights are the AIRs' LDE heights
     std::vector<const uint32_t*> h_cols;
@@ -425,6 +442,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     // commitment, so the coefficients wait in the (still empty) permutation buffer until then (prover.hip prove_impl does the same).
     auto tcoef_of = [&](size_t a) { return eat[a] ? const_cast<uint32_t*>(airs[a].d_trace) : airs[a].prover->tcoef.as<uint32_t>(); };
     auto coef_first = [&](size_t a) { return eat[a] && lg ? airs[a].prover->perm.as<uint32_t>() : tcoef_of(a); };
+    // the values the programs read on the trace domain: with preprocessed columns the prover's (trace | fixed matrix) copy
+    auto values_of = [&](size_t a) -> const uint32_t* { return sh[a].Wf ? airs[a].prover->pre_vals.as<uint32_t>() : airs[a].d_trace; };
     uint32_t root[8];
     TRY(fork());
     for (size_t a = 0; a < A; ++a) {
@@ -434,6 +453,11 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         if (sbv[a]) {  // streamed: the trace's coefficient arrays; its LDE rows exist one sub-coset at a time from here on
             TRY(intt_dif(airs[a].d_trace, coef_first(a), sh[a].H, sh[a].H, sh[a].W, (int)sh[a].log_h));
         } else {
+            if (sh[a].Wf) {  // the trace in front of the fixed matrix, the fixed LDE behind the main columns (the tree hashes the first W)
+                PW_HIP_TRY(hipMemcpyAsync(p->pre_vals.as<uint32_t>(), airs[a].d_trace, (size_t)sh[a].W * sh[a].H * 4, hipMemcpyDeviceToDevice, stream()));
+                PW_HIP_TRY(hipMemcpyAsync(p->lde.as<uint32_t>() + (size_t)sh[a].W * sh[a].N, p->pre_lde.as<uint32_t>(), (size_t)sh[a].Wf * sh[a].N * 4,
+                                          hipMemcpyDeviceToDevice, stream()));
+            }
             TRY(lde_matrix(p, Lc[a], sh[a].log_h, airs[a].d_trace, sh[a].W, p->lde.as<uint32_t>()));
         }
     }
@@ -449,7 +473,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     // per-AIR scratch pointers
     auto weights_of = [&](size_t a) { return airs[a].prover->ext_arena.as<bb::Ext>(); };
     auto scratch_of = [&](size_t a) { return airs[a].prover->misc.as<bb::Ext>(); };
-    auto apow_of = [&](size_t a) { return scratch_of(a) + 2 * (size_t)std::max({sh[a].W, sh[a].Wp, 8u}) * div_up(sh[a].H, 8192); };
+    auto apow_of = [&](size_t a) { return scratch_of(a) + 2 * (size_t)std::max({sh[a].W1, sh[a].Wp, 8u}) * div_up(sh[a].H, 8192); };
     auto blpow_of = [&](size_t a) { return apow_of(a) + sh[a].M + 4; };
     auto logup_program = [&](size_t a) {
         const PwProver* p = airs[a].prover;
@@ -471,8 +495,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
             bb::Ext* rowsum = weights_of(a) + 2 * sh[a].H;
             // eat: the matrix's VALUES live in the sub-coset buffer (idle between two passes) until its coefficient arrays exist
             uint32_t* d_pval = eat[a] ? p->lde.as<uint32_t>() : p->perm.as<uint32_t>();
-            if (specialised(p)) TRY(logup_perm_trace_jit(p, airs[a].d_trace, sh[a].H, al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
-            else TRY(logup_perm_trace(airs[a].d_trace, sh[a].H, logup_program(a), al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
+            if (specialised(p)) TRY(logup_perm_trace_jit(p, values_of(a), sh[a].H, al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
+            else TRY(logup_perm_trace(values_of(a), sh[a].H, logup_program(a), al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
             if (sbv[a]) {
                 // streamed: only phi and the per-row sums are extended for good (the boundary terms read them at rows j and j + 2); S is
                 // saved before the matrix becomes its coefficient arrays in place
@@ -559,7 +583,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     put_monty(root, 8);
     ch.observe_words(root, 8);
 
-    // ---- 4. openings: per AIR main | perm at zeta | quotient | perm at g zeta ----------------------------------
+    // ---- 4. openings: per AIR main | preprocessed | perm at zeta | quotient | perm at g zeta ---------------------
     const bb::Ext zeta = ch.sample_ext();
     std::vector<bb::Ext> gzeta(A);
     TRY(fork());
@@ -571,22 +595,23 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         bb::Ext* w1 = weights_of(a);
         bb::Ext* w2 = w1 + s.H;
         gzeta[a] = bb::ext_scale(zeta, field::root_of_unity((int)s.log_h));
-        // trace columns: barycentric evaluation straight from the caller's trace; quotient chunks from their coefficients
+        // trace columns: barycentric evaluation straight from the caller's trace (with preprocessed columns: the (trace | fixed) copy,
+        // both in one pass); quotient chunks from their coefficients
         if (!eat[a]) {
             TRY(barycentric_weights(zeta, (int)s.log_h, w1));
-            TRY(ext_dot_columns(airs[a].d_trace, s.H, s.W, s.H, w1, o, scratch_of(a)));
+            TRY(ext_dot_columns(values_of(a), s.H, s.W1, s.H, w1, o, scratch_of(a)));
         }
         if (lg && !sbv[a]) {  // the permutation matrix at zeta and at g zeta: one pass over its columns
             TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
-            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W, o + s.W + s.Wp + 8, scratch_of(a)));
+            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W1, o + s.W1 + s.Wp + 8, scratch_of(a)));
         }
         TRY(zeta_weights(zeta, (int)s.log_h, w1));
         if (eat[a]) TRY(ext_dot_columns(tcoef_of(a), s.H, s.W, s.H, w1, o, scratch_of(a)));  // the trace is its coefficient arrays by now
         if (lg && sbv[a]) {  // streamed: p->perm holds the matrix's coefficient arrays
             TRY(zeta_weights(gzeta[a], (int)s.log_h, w2));
-            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W, o + s.W + s.Wp + 8, scratch_of(a)));
+            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W1, o + s.W1 + s.Wp + 8, scratch_of(a)));
         }
-        TRY(ext_dot_columns(p->qcoef.as<uint32_t>(), s.H, 8, s.H, w1, o + s.W + s.Wp, scratch_of(a)));
+        TRY(ext_dot_columns(p->qcoef.as<uint32_t>(), s.H, 8, s.H, w1, o + s.W1 + s.Wp, scratch_of(a)));
     }
     TRY(join());
     std::vector<bb::Ext> opened(K_total);
@@ -608,7 +633,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         for (size_t a = 0; a < A; ++a) {
             PwProver* p = airs[a].prover;
             const Shape& s = sh[a];
-            const size_t K1 = (size_t)s.W + s.Wp + 8;
+            const size_t K1 = (size_t)s.W1 + s.Wp + 8;
             bb::Ext sum1 = bb::ext_zero(), sum2 = bb::ext_zero();
             for (size_t k = 0; k < K1; ++k) sum1 = bb::ext_add(sum1, bb::ext_mul(gpow[s.koff + k], opened[s.koff + k]));
             for (size_t k = K1; k < s.K; ++k) sum2 = bb::ext_add(sum2, bb::ext_mul(gpow[s.koff + k], opened[s.koff + k]));
@@ -617,7 +642,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
             if (sbv[a])
                 TRY(streamed::deep_from_coefficients(sctx(a), lg, tcoef_of(a), p->perm.as<uint32_t>(), p->qlde.as<uint32_t>(), s.logN,
                                                      d_gpow + s.koff, [] {}, sum1, sum2, zeta, gzeta[a], out));
-            else if (s.log_h >= kDeepComboMinLogHeight && !getenv("POWDR_DEEP_DIRECT") && !((uintptr_t)airs[a].d_trace & 7)) {
+            else if (s.log_h >= kDeepComboMinLogHeight && !s.Wf && !getenv("POWDR_DEEP_DIRECT") && !((uintptr_t)airs[a].d_trace & 7)) {
                 // resident and tall: the numerator is combined on the evaluations over <g_n> — the caller's trace, the permutation
                 // matrix: half the bytes their LDE holds — and extended as 4 (+ 4) columns, like the one-AIR prover does
                 uint32_t* d_gev = p->gbuf.as<uint32_t>();
@@ -626,10 +651,10 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                 TRY(lde_matrix(p, Lc[a], s.log_h, d_gev, lg ? 8u : 4u, d_glde));
                 TRY(deep_from_combo(d_glde, p->qlde.as<uint32_t>(), s.N, s.logN, d_gpow + s.koff + s.W + s.Wp, sum1, sum2, zeta, gzeta[a], lg ? 1 : 0, out));
             } else if (lg)
-                TRY(deep_quotient_logup(p->lde.as<uint32_t>(), s.W, p->plde.as<uint32_t>(), s.Wp, p->qlde.as<uint32_t>(), s.N, s.logN,
+                TRY(deep_quotient_logup(p->lde.as<uint32_t>(), s.W1, p->plde.as<uint32_t>(), s.Wp, p->qlde.as<uint32_t>(), s.N, s.logN,
                                         d_gpow + s.koff, sum1, sum2, zeta, gzeta[a], out));
             else
-                TRY(deep_quotient(p->lde.as<uint32_t>(), s.W, p->qlde.as<uint32_t>(), 8, s.N, s.logN, d_gpow + s.koff, sum1, zeta, out));
+                TRY(deep_quotient(p->lde.as<uint32_t>(), s.W1, p->qlde.as<uint32_t>(), 8, s.N, s.logN, d_gpow + s.koff, sum1, zeta, out));
             if (started[s.logN]) TRY(ext_axpy(target, nullptr, out, s.N));
             started[s.logN] = 1;
         }
@@ -715,6 +740,22 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
             }
         }
         TRY(join());
+        // the preprocessed rows (the fixed LDE the prover keeps) go into the same launch; their siblings come from each AIR's own tree
+        std::vector<size_t> pre_row_off(A, 0), pre_dig_off(A, 0);
+        std::vector<uint64_t> pre_offs;
+        for (size_t a = 0; a < A; ++a) {
+            if (!sh[a].Wf) continue;
+            pre_row_off[a] = ro;
+            jobs.push_back(GatherRowsJob{airs[a].prover->pre_lde.as<uint32_t>(), (uint64_t)sh[a].N, sh[a].Wf, (uint32_t)(a * nq), (uint64_t)ro});
+            max_w = std::max(max_w, sh[a].Wf);
+            ro += (size_t)nq * sh[a].Wf;
+            pre_dig_off[a] = pre_offs.size();
+            for (uint32_t qi = 0; qi < nq; ++qi)
+                for (int l = 0; l < sh[a].logN; ++l) {
+                    const size_t size = sh[a].N >> l, p = qs[qi] & (size - 1);
+                    pre_offs.push_back(merkle_level_offset(sh[a].N, l) + (((p + size / 2) & (size - 1)) * 8));
+                }
+        }
         if (!jobs.empty()) {  // the resident matrices' rows: one launch for all AIRs and trees
             PW_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(GatherRowsJob), hipMemcpyHostToDevice, st));
             TRY(gather_rows_multi(d_jobs, (uint32_t)jobs.size(), max_w, d_idx, nq, d_rows));
@@ -738,21 +779,27 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                     dig_offs.push_back((size_t)n_trees * tree_words + ftree_off[l] + merkle_level_offset(half, lv) + (((leaf >> lv) ^ 1) * 8));
             }
         }
-        const size_t nd = dig_offs.size(), ne = ext_offs.size();
-        if (nd > n_dig) return (int)hipErrorInvalidValue;
+        const size_t nd = dig_offs.size(), ne = ext_offs.size(), npd = pre_offs.size();
+        if (nd + npd > n_dig) return (int)hipErrorInvalidValue;
         uint64_t* d_dig_offs = d_offs;
         uint64_t* d_ext_offs = d_offs + nd;
+        uint64_t* d_pre_offs = d_ext_offs + ne;
         PW_HIP_TRY(hipMemcpyAsync(d_dig_offs, dig_offs.data(), nd * 8, hipMemcpyHostToDevice, st));
         if (ne) PW_HIP_TRY(hipMemcpyAsync(d_ext_offs, ext_offs.data(), ne * 8, hipMemcpyHostToDevice, st));
+        if (npd) PW_HIP_TRY(hipMemcpyAsync(d_pre_offs, pre_offs.data(), npd * 8, hipMemcpyHostToDevice, st));
         TRY(gather_records(d_dig, d_dig_offs, 8u, (uint32_t)nd, d_dig_out));
         TRY(gather_records(reinterpret_cast<const uint32_t*>(d_v), d_ext_offs, 4u, (uint32_t)ne, d_ext_out));
+        for (size_t a = 0; a < A; ++a)  // (after the main siblings in d_dig_out)
+            if (sh[a].Wf)
+                TRY(gather_records(airs[a].prover->pre_tree.as<uint32_t>(), d_pre_offs + pre_dig_off[a], 8u, nq * (uint32_t)sh[a].logN,
+                                   d_dig_out + (nd + pre_dig_off[a]) * 8));
         // the answers leave the device as canonical words
         TRY(canonicalize_words(d_rows, ro));
-        TRY(canonicalize_words(d_dig_out, nd * 8));
+        TRY(canonicalize_words(d_dig_out, (nd + npd) * 8));
         TRY(canonicalize_words(d_ext_out, ne * 4));
-        std::vector<uint32_t> rows(ro + 1), dig(nd * 8 + 1), ext(ne * 4 + 1);
+        std::vector<uint32_t> rows(ro + 1), dig((nd + npd) * 8 + 1), ext(ne * 4 + 1);
         PW_HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, ro * 4, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipMemcpyAsync(dig.data(), d_dig_out, nd * 32, hipMemcpyDeviceToHost, st));
+        PW_HIP_TRY(hipMemcpyAsync(dig.data(), d_dig_out, (nd + npd) * 32, hipMemcpyDeviceToHost, st));
         if (ne) PW_HIP_TRY(hipMemcpyAsync(ext.data(), d_ext_out, ne * 16, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
         auto put_raw = [&](const uint32_t* w, size_t n) { pf.insert(pf.end(), w, w + n); };
@@ -768,6 +815,13 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                 }
                 put_raw(&dig[dpos * 8], (size_t)L * 8);
                 dpos += L;
+                if (ph != 0) continue;
+                // after the main tree's answer: each preprocessed row and its path in that AIR's own tree
+                for (size_t a = 0; a < A; ++a) {
+                    if (!sh[a].Wf) continue;
+                    put_raw(&rows[pre_row_off[a] + (size_t)qi * sh[a].Wf], sh[a].Wf);
+                    put_raw(&dig[(nd + pre_dig_off[a] + (size_t)qi * sh[a].logN) * 8], (size_t)sh[a].logN * 8);
+                }
             }
             for (int l = 0; l < rounds; ++l) {
                 put_raw(&ext[epos * 4], 4);

@@ -19,7 +19,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
-                  "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables"]
+                  "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables",
+                  "pw_prover_create_preprocessed", "pw_prover_preprocessed_root", "pw_prover_preprocessed_width", "pw_verify_segment_preprocessed"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -27,6 +28,13 @@ lib.pw_prover_create_logup.restype = C.c_void_p
 lib.pw_prover_create_logup.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
 lib.pw_prover_destroy.argtypes = [C.c_void_p]
+lib.pw_prover_create_preprocessed.restype = C.c_void_p
+lib.pw_prover_create_preprocessed.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+lib.pw_prover_preprocessed_root.restype = C.c_int
+lib.pw_prover_preprocessed_root.argtypes = [C.c_void_p, C.c_void_p]
+lib.pw_prover_preprocessed_width.restype = C.c_uint32
+lib.pw_prover_preprocessed_width.argtypes = [C.c_void_p]
 lib.pw_prover_prove.restype = C.c_int
 lib.pw_prover_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
 lib.pw_prover_check_constraints.restype = C.c_int
@@ -134,6 +142,15 @@ lib.pw_prove_segment_consuming.restype = C.c_int
 lib.pw_prove_segment_consuming.argtypes = lib.pw_prove_segment.argtypes
 lib.pw_verify_segment.restype = C.c_int
 lib.pw_verify_segment.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+
+
+class PwAirPreprocessed(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("root8", C.c_uint32 * 8)]
+
+
+lib.pw_verify_segment_preprocessed.restype = C.c_int
+lib.pw_verify_segment_preprocessed.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.POINTER(PwAirPreprocessed), C.c_size_t, C.c_int,
+                                               C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
 lib.pw_verify_airs.restype = C.c_int
 lib.pw_verify_airs.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.c_size_t, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p]
@@ -283,16 +300,31 @@ def set_device_budget(n_bytes: int) -> None:
     lib.pw_set_device_budget(int(n_bytes))
 
 
-def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logup: bool = False, check_balance: bool = False):
+def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logup: bool = False, check_balance: bool = False,
+                   preprocessed=None):
     """Host verification of a segment proof. descs: [(width, log_height, cons_bytecode, cons_spans, interactions-or-None)]
     -> (code, sum of the AIRs' cumulative bus sums). 0 = valid; ((i+1) << 8) | 2 = constraint identity of AIR i;
-    14 = the bus sums do not cancel (check_balance)."""
+    14 = the bus sums do not cancel (check_balance); 16 = a preprocessed row does not open against its root.
+    preprocessed: None (pw_verify_segment) or, per AIR, None | (width, root8) — the verifying key's preprocessed commitments
+    (pw_verify_segment_preprocessed)."""
     recs, keep = _air_descriptions(descs)
     pr = np.ascontiguousarray(proof, dtype=np.uint32)
     cfg = PwStarkConfig(num_queries, pow_bits)
     total = np.zeros(4, np.uint32)
-    rc = int(lib.pw_verify_segment(C.byref(cfg), recs, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr), int(check_balance),
-                                   total.ctypes.data_as(C.c_void_p)))
+    if preprocessed is None:
+        rc = int(lib.pw_verify_segment(C.byref(cfg), recs, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr), int(check_balance),
+                                       total.ctypes.data_as(C.c_void_p)))
+        return rc, total
+    assert len(preprocessed) == len(descs)
+    pre = (PwAirPreprocessed * max(len(descs), 1))()
+    for i, e in enumerate(preprocessed):
+        if e is not None:
+            w, root = e
+            pre[i].width = int(w)
+            for k, x in enumerate(np.asarray(root, dtype=np.uint32).reshape(8)):
+                pre[i].root8[k] = int(x)
+    rc = int(lib.pw_verify_segment_preprocessed(C.byref(cfg), recs, pre, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr),
+                                                int(check_balance), total.ctypes.data_as(C.c_void_p)))
     return rc, total
 
 
@@ -463,14 +495,32 @@ class Prover:
     """One AIR = one prover (constraint programs fixed at construction).
 
     interactions = (inter[n x 3] = {bus, n_args, first span}, spans[m x 2], bytecode) — the output of
-    host.compile_bus(apc, 1) — switches the prover to "pw-stark v0 + LogUp" (proof magic PWS2)."""
+    host.compile_bus(apc, 1) — switches the prover to "pw-stark v0 + LogUp" (proof magic PWS2).
 
-    def __init__(self, width: int, cons_bytecode, cons_spans, num_queries: int = 100, pow_bits: int = 0, interactions=None):
+    preprocessed = (device tensor of the fixed matrix (column-major, Montgomery), pre_width, log_height): operands width ..
+    width + pre_width - 1 of the programs are those columns (pw_prover_create_preprocessed; segment proofs only, at that height)."""
+
+    def __init__(self, width: int, cons_bytecode, cons_spans, num_queries: int = 100, pow_bits: int = 0, interactions=None,
+                 preprocessed=None):
         bc = np.ascontiguousarray(cons_bytecode, dtype=np.uint32)
         sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
         cfg = PwStarkConfig(num_queries, pow_bits)
         self.width = width
-        if interactions is None:
+        self.pre_width = 0
+        if preprocessed is not None:
+            t, pw_, lh = preprocessed
+            assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            if interactions is None:
+                tables = (None, 0, None, 0, None, 0)
+            else:
+                it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
+                isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
+                ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
+                tables = (vp(it), len(it), vp(isp), len(isp), vp(ibc), len(ibc))
+            self._h = lib.pw_prover_create_preprocessed(C.byref(cfg), width, pw_, lh, t.data_ptr(), vp(bc), len(bc), vp(sp), len(sp), *tables)
+            self.pre_width = pw_
+        elif interactions is None:
             self._h = lib.pw_prover_create(C.byref(cfg), width, bc.ctypes.data_as(C.c_void_p), len(bc),
                                            sp.ctypes.data_as(C.c_void_p), len(sp))
         else:
@@ -482,6 +532,12 @@ class Prover:
                                                  isp.ctypes.data_as(C.c_void_p), len(isp), ibc.ctypes.data_as(C.c_void_p), len(ibc))
         if not self._h:
             raise RuntimeError("pw_prover_create failed")
+
+    def preprocessed_root(self) -> np.ndarray:
+        """pw_prover_preprocessed_root: the commitment to the fixed matrix (8 canonical words; the verifying key's part)."""
+        root = np.zeros(8, np.uint32)
+        abi.check(lib.pw_prover_preprocessed_root(self._h, root.ctypes.data_as(C.c_void_p)), "pw_prover_preprocessed_root")
+        return root
 
     def prove(self, d_trace_ptr: int, log_height: int, copy: bool = True, consume: bool = False) -> np.ndarray:
         """pw_prover_prove; consume=True: pw_prover_prove_consuming — the trace is handed over (a streamed proof leaves its

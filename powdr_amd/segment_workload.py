@@ -264,8 +264,14 @@ class HonestSegment:
     kind "C5": reth-shaped — the APC AIRs of synth.segment_shape("C5") (log-uniform heights and widths) + the same system AIRs."""
 
     def __init__(self, kind: str, max_log_height: int = 20, seed: int = 0, queries: int = 100, pow_bits: int = 16, logup: bool = True,
-                 max_apc_airs: int | None = None, specialise_all: bool = False):
+                 max_apc_airs: int | None = None, specialise_all: bool = False, periphery_layout: str = "main"):
+        """periphery_layout "main": the periphery AIRs' tables are main columns next to the multiplicities (nothing constrains them:
+        the lookup balance then only shows that trace generation was consistent); "preprocessed": the chips' own layout — the tables
+        are preprocessed columns the proving key fixes (pw_prover_create_preprocessed), the main traces hold only the multiplicities,
+        and the balance is a range / bitwise / tuple check."""
+        assert periphery_layout in ("main", "preprocessed")
         self.kind, self.logup, self.queries, self.pow_bits = kind, logup, queries, pow_bits
+        self.periphery_layout = periphery_layout
         shrink = 20 - max_log_height
         self.per = tg.Periphery.fresh()
         self.airs = []  # dict(name, role, width, log_h, cons, inter, trace(tensor), prover)
@@ -297,18 +303,33 @@ class HonestSegment:
             bc, sp, it = synth.reference_air_programs(n)
             self.airs.append(dict(name=n, role="instruction", width=oc.WIDTHS[k], log_h=heights[k].bit_length() - 1, cons=(bc, sp), inter=it, trace=t))
             self.replays.append((_BusReplay(it, heights[k]), t))
-        # ---- periphery AIRs (no constraints: lookup tables with multiplicity columns; the chips are external, the layouts ours)
+        # ---- periphery AIRs (no constraints: lookup tables with multiplicity columns; the chips are external). Layout "main": the
+        # tables in main columns (ours); "preprocessed": the chips' own — the tables fixed by the key, the multiplicities in the main trace
         empty = (np.zeros(0, np.uint32), np.zeros((0, 2), np.uint32))
-        self.per_traces = {}
-        for name, w, rows, it in (("var_range", 3, self.per.var_hist.numel(), periphery.var_range_interactions(self.per.var_bus)),
-                                  ("tuple2", 3, self.per.tuple_hist.numel(), periphery.tuple2_interactions(self.per.tuple_bus)),
-                                  ("bitwise", 5, 65536, periphery.bitwise_interactions(self.per.bitwise_bus))):
+        self.per_traces, self.pre_tables = {}, {}
+        pre = periphery_layout == "preprocessed"
+        if pre:
+            per_airs = (("var_range", 1, self.per.var_hist.numel(), periphery.var_range_interactions_pre(self.per.var_bus),
+                         lambda: periphery.var_range_table(self.per.var_hist.numel()), 2),
+                        ("tuple2", 1, self.per.tuple_hist.numel(), periphery.tuple2_interactions_pre(self.per.tuple_bus),
+                         lambda: periphery.tuple2_table(self.per.tuple_sizes), 2),
+                        ("bitwise", 2, 65536, periphery.bitwise_interactions_pre(self.per.bitwise_bus), periphery.bitwise_table, 3))
+        else:
+            per_airs = (("var_range", 3, self.per.var_hist.numel(), periphery.var_range_interactions(self.per.var_bus), None, 0),
+                        ("tuple2", 3, self.per.tuple_hist.numel(), periphery.tuple2_interactions(self.per.tuple_bus), None, 0),
+                        ("bitwise", 5, 65536, periphery.bitwise_interactions(self.per.bitwise_bus), None, 0))
+        for name, w, rows, it, table, pre_w in per_airs:
             t = torch.zeros(w * rows, dtype=torch.int32, device="cuda")
             self.per_traces[name] = t
-            self.airs.append(dict(name=name, role="periphery", width=w, log_h=rows.bit_length() - 1, cons=empty, inter=it, trace=t))
+            lh = rows.bit_length() - 1
+            if table is not None:
+                self.pre_tables[name] = (table(), pre_w, lh)
+            self.airs.append(dict(name=name, role="periphery", width=w, log_h=lh, cons=empty, inter=it, trace=t, pre=self.pre_tables.get(name)))
+        if pre:
+            torch.cuda.synchronize()  # the tables exist before the provers copy them (on the library's stream)
         for a in self.airs:
             a["prover"] = prover.Prover(a["width"], a["cons"][0], a["cons"][1], num_queries=queries, pow_bits=pow_bits,
-                                        interactions=a["inter"] if logup else None)
+                                        interactions=a["inter"] if logup else None, preprocessed=a.get("pre"))
         # the AIR set of an execution is fixed at key generation and proven in every segment: its specialised kernels are compiled once,
         # for EVERY AIR (pw_provers_specialise), not only for those whose first trace happens to be tall (the library's own rule when it
         # meets a prover for the first time inside a proof)
@@ -437,6 +458,10 @@ class HonestSegment:
         oc.expand(self.records.data_ptr(), self.calls, self.table, self.instr_bufs)
         for replay, t in self.replays:
             replay(t.data_ptr(), p)
+        if self.periphery_layout == "preprocessed":  # the tables are the key's: the traces are the multiplicities alone
+            for name, hist in (("var_range", p.var_hist), ("tuple2", p.tuple_hist), ("bitwise", p.bitwise_hist)):
+                abi.check(abi.lib.powdr_periphery_multiplicities(hist.data_ptr(), hist.numel(), self.per_traces[name].data_ptr()), "multiplicities")
+            return
         abi.check(abi.lib.powdr_periphery_var_range_trace(p.var_hist.data_ptr(), p.var_hist.numel(), self.per_traces["var_range"].data_ptr()), "var_range_trace")
         abi.check(abi.lib.powdr_periphery_tuple2_trace(p.tuple_hist.data_ptr(), p.tuple_sizes[0], p.tuple_sizes[1], self.per_traces["tuple2"].data_ptr()), "tuple2_trace")
         abi.check(abi.lib.powdr_periphery_bitwise_trace(p.bitwise_hist.data_ptr(), self.per_traces["bitwise"].data_ptr()), "bitwise_trace")
@@ -452,9 +477,25 @@ class HonestSegment:
     def descriptions(self, buses=None):
         return [(a["width"], a["log_h"], a["cons"][0], a["cons"][1], a["inter"] if buses is None else periphery.select_buses(a["inter"], buses)) for a in self.airs]
 
+    def preprocessed_keys(self):
+        """per AIR None | (preprocessed width, root8): the verifying key's part (None for the whole list: layout "main")"""
+        if self.periphery_layout != "preprocessed":
+            return None
+        keys = []
+        for a in self.airs:
+            pr = a.get("prover")
+            if a.get("pre") is None:
+                keys.append(None)
+            else:
+                if pr is None:  # (released provers: a throw-away one recomputes the key)
+                    pr = prover.Prover(a["width"], a["cons"][0], a["cons"][1], num_queries=1, interactions=a["inter"], preprocessed=a["pre"])
+                keys.append((a["pre"][1], pr.preprocessed_root()))
+        return keys
+
     def verify(self, proof) -> int:
-        """pw_verify_segment on the whole statement (every constraint identity, every LogUp column, openings, FRI, queries)."""
-        return int(prover.verify_segment(self.descriptions(), proof, self.queries, self.pow_bits, self.logup)[0])
+        """pw_verify_segment on the whole statement (every constraint identity, every LogUp column, openings, FRI, queries;
+        with the preprocessed layout: pw_verify_segment_preprocessed against the key's preprocessed commitments)."""
+        return int(prover.verify_segment(self.descriptions(), proof, self.queries, self.pow_bits, self.logup, preprocessed=self.preprocessed_keys())[0])
 
     def check_constraints(self) -> int:
         """the device's mock prover on the current traces: violated (row, constraint) pairs over all AIRs"""
@@ -465,10 +506,14 @@ class HonestSegment:
         every AIR restricted to those buses, proven and verified with check_balance — the senders' LogUp sums and the periphery AIRs'
         cancel exactly. Returns (verify code, total sum words)."""
         provers = [prover.Prover(a["width"], a["cons"][0], a["cons"][1], num_queries=min(self.queries, 8), pow_bits=0,
-                                 interactions=periphery.select_buses(a["inter"], LOOKUP_BUSES)) for a in self.airs]
+                                 interactions=periphery.select_buses(a["inter"], LOOKUP_BUSES), preprocessed=a.get("pre")) for a in self.airs]
         seg = [(pr, a["trace"].data_ptr(), a["log_h"]) for pr, a in zip(provers, self.airs)]
         proof = prover.prove_segment(seg, logup=True, copy=True)
-        rc, total = prover.verify_segment(self.descriptions(LOOKUP_BUSES), proof, min(self.queries, 8), 0, True, check_balance=True)[:2]
+        keys = None
+        if self.periphery_layout == "preprocessed":
+            keys = [None if a.get("pre") is None else (a["pre"][1], pr.preprocessed_root()) for pr, a in zip(provers, self.airs)]
+        rc, total = prover.verify_segment(self.descriptions(LOOKUP_BUSES), proof, min(self.queries, 8), 0, True, check_balance=True,
+                                          preprocessed=keys)[:2]
         for pr in provers:
             pr.close()
         return int(rc), total

@@ -130,6 +130,10 @@ extern "C" {
     pub fn powdr_periphery_var_range_trace(d_var_hist: *const u32, var_num_bins: usize, d_out: *mut PowdrFp) -> i32;
     pub fn powdr_periphery_tuple2_trace(d_tuple2_hist: *const u32, tuple2_sz0: u32, tuple2_sz1: u32, d_out: *mut PowdrFp) -> i32;
     pub fn powdr_periphery_bitwise_trace(d_bitwise_hist: *const u32, d_out: *mut PowdrFp) -> i32;
+    pub fn powdr_periphery_var_range_table(var_num_bins: usize, d_out: *mut PowdrFp) -> i32;
+    pub fn powdr_periphery_tuple2_table(tuple2_sz0: u32, tuple2_sz1: u32, d_out: *mut PowdrFp) -> i32;
+    pub fn powdr_periphery_bitwise_table(d_out: *mut PowdrFp) -> i32;
+    pub fn powdr_periphery_multiplicities(d_hist: *const u32, n: usize, d_out: *mut PowdrFp) -> i32;
     pub fn powdr_gpu_set_stream(hip_stream: *mut c_void);
     pub fn powdr_gpu_get_stream() -> *mut c_void;
     pub fn powdr_gpu_timing_enable(enable: c_int);
@@ -274,6 +278,13 @@ pub struct PwAirDescription {
     pub inter_bytecode: *const u32,
     pub inter_bytecode_len: usize,
 }
+/// The verifying key's part of an AIR with preprocessed columns (`width` 0: none); `root8` = `pw_prover_preprocessed_root`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct PwAirPreprocessed {
+    pub width: u32,
+    pub root8: [u32; 8],
+}
 
 extern "C" {
     pub fn pw_prover_create(cfg: *const PwStarkConfig, width: u32, cons_bytecode: *const u32, bytecode_len: usize,
@@ -286,6 +297,12 @@ extern "C" {
     pub fn pw_prover_set_bus_seed(p: *mut PwProver, seed8: *const u32) -> c_int;
     pub fn pw_prover_logup_path(p: *const PwProver) -> c_int;
     pub fn pw_prover_destroy(p: *mut PwProver);
+    pub fn pw_prover_create_preprocessed(cfg: *const PwStarkConfig, width: u32, pre_width: u32, log_height: u32, d_pre: *const u32,
+                                         cons_bytecode: *const u32, bytecode_len: usize, cons_spans: *const u32, n_constraints: usize,
+                                         interactions: *const u32, n_interactions: usize, inter_spans: *const u32, n_inter_spans: usize,
+                                         inter_bytecode: *const u32, inter_bytecode_len: usize) -> *mut PwProver;
+    pub fn pw_prover_preprocessed_root(p: *const PwProver, root8: *mut u32) -> c_int;
+    pub fn pw_prover_preprocessed_width(p: *const PwProver) -> u32;
     pub fn pw_prover_prove(p: *mut PwProver, d_trace: *const u32, log_height: u32, proof_words: *mut *const u32,
                            n_words: *mut usize) -> c_int;
     /// The trace is handed over (the engine owns `common_main`): a streamed proof leaves the coefficient arrays in its place.
@@ -324,6 +341,9 @@ extern "C" {
     pub fn pw_get_device_budget() -> usize;
     pub fn pw_verify_segment(cfg: *const PwStarkConfig, airs: *const PwAirDescription, n_airs: usize, logup: c_int,
                              proof_words: *const u32, n_words: usize, check_balance: c_int, total_sum4: *mut u32) -> c_int;
+    pub fn pw_verify_segment_preprocessed(cfg: *const PwStarkConfig, airs: *const PwAirDescription, pre: *const PwAirPreprocessed,
+                                          n_airs: usize, logup: c_int, proof_words: *const u32, n_words: usize, check_balance: c_int,
+                                          total_sum4: *mut u32) -> c_int;
     pub fn pw_prove_airs(airs: *const PwSegmentAir, n_airs: usize, shared_bus_seed: c_int, n_workers: c_uint,
                          proofs: *mut *const u32, n_words: *mut usize, bus_seed8: *mut u32) -> c_int;
     pub fn pw_verify_airs(cfg: *const PwStarkConfig, airs: *const PwAirDescription, n_airs: usize,
