@@ -92,6 +92,33 @@ PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uint32_t width
 int pw_prover_preprocessed_root(const PwProver* p, uint32_t* root8);
 uint32_t pw_prover_preprocessed_width(const PwProver* p); /* 0: none */
 
+/* ---- next-row operands and row selectors: "pw-stark v1 + rows"  --------------------------------------------------
+ * An AIR whose constraints read the next row or Plonky3's row selectors (OpenVM's `main.row_slice(1)`, `when_first_row()`,
+ * `when_transition()`; powdr's OpenVmReference::{WitnessColumn(_, next), IsFirstRow, IsLastRow, IsTransition}). With W1 = width +
+ * pre_width, an operand c of a CONSTRAINT program is
+ *     c < W1             main (c < width) or preprocessed column c on the current row, as pw_prover_create_preprocessed;
+ *     W1 <= c < 2 W1     column c - W1 on the NEXT row (the row after the last is row 0);
+ *     2 W1               is_first_row  = Z_H(x) / (x - 1)      (H at row 0, 0 elsewhere on the trace domain)
+ *     2 W1 + 1           is_last_row   = Z_H(x) / (x - g^-1)   (H g at row H - 1, 0 elsewhere)
+ *     2 W1 + 2           is_transition = x - g^-1              (g^j - g^-1 at row j)
+ * Degrees (Plonky3's degree_multiple): a column of either row and the first / last row selectors 1, is_transition 0; every constraint
+ * at most 3 (pw_prover_max_constraint_degree reports by this rule). INTERACTION operands stay below W1 (current-row columns only).
+ * NULL for an operand outside these bounds, a constraint of degree > 3 or a malformed program. pre_width = 0: no fixed matrix
+ * (log_height, d_pre unused; any height >= 2 rows); pre_width > 0: as pw_prover_create_preprocessed. Other arguments as there.
+ * An AIR is ROW-AWARE if one of its constraint programs reads an operand >= W1, TWO-POINT if one reads a next-row operand
+ * (pw_prover_row_flags: bit 0 two-point, bit 1 reads a selector; 0: neither — the prover then proves exactly as the plain or
+ * preprocessed one). Such a prover proves in segments only (pw_prove_segment / _consuming); pw_prover_prove, _prove_consuming,
+ * _trace_root and pw_prove_airs return -1. A row-aware AIR is never streamed (pw_segment_last_modes reports 0). The proof of a segment
+ * with at least one row-aware AIR carries magic PWS5; other segments keep their PWS3 / PWS4 words.
+ * pw_prover_check_constraints reads the next row as (j + 1) mod H and the selectors' exact values on the trace domain (heights up to
+ * 2^26 rows, the segment limit; above: -1). */
+PwProver* pw_prover_create_transition(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                      const uint32_t* d_pre, const uint32_t* cons_bytecode, size_t bytecode_len,
+                                      const uint32_t* cons_spans, size_t n_constraints, const uint32_t* interactions,
+                                      size_t n_interactions, const uint32_t* inter_spans, size_t n_inter_spans,
+                                      const uint32_t* inter_bytecode, size_t inter_bytecode_len);
+uint32_t pw_prover_row_flags(const PwProver* p);
+
 /* Prove one trace (column-major, width x 2^log_height, Montgomery words, device).
  * *proof_words points at host memory owned by the prover, valid until the next call. */
 int pw_prover_prove(PwProver* p, const uint32_t* d_trace, uint32_t log_height, const uint32_t** proof_words,
@@ -243,6 +270,13 @@ typedef struct PwAirPreprocessed {
  * against one that claims none, returns 1. */
 int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
                                    int logup, const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
+
+/* pw_verify_segment_preprocessed for segments whose AIRs may be row-aware (pw_prover_create_transition; pre may be NULL). Constraint
+ * operands below 2 (width + pre[i].width) + 3 and interaction operands below width + pre[i].width are valid, anything else returns 15.
+ * The row flags of every AIR are derived from its constraint programs; a PWS5 proof against descriptions with no row-aware AIR, or
+ * another proof against descriptions with one, returns 1. Without a row-aware AIR: exactly pw_verify_segment_preprocessed. */
+int pw_verify_segment_transition(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
+                                 int logup, const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
 
 /* Host verification of pw_prove_airs' proofs. With shared_bus_seed the seed is recomputed from the trace roots inside the
  * proofs and every proof must have used it. Returns 0; ((air index + 1) << 8) | code of the first failing proof

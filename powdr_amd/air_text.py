@@ -34,8 +34,8 @@ class _Parser:
     """expr := term (('+' | '-') term)* ; term := unary ('*' unary)* ; unary := '-' unary | atom ; atom := num | id | '(' expr ')'
     emitting post-fix code as it goes (left-associative, like the Display it reads)."""
 
-    def __init__(self, toks, col_index):
-        self.t, self.i, self.col, self.code = toks, 0, col_index, []
+    def __init__(self, toks, col_index, rows=None):
+        self.t, self.i, self.col, self.rows, self.code = toks, 0, col_index, rows, []
 
     def peek(self):
         return self.t[self.i] if self.i < len(self.t) else (None, None)
@@ -76,9 +76,16 @@ class _Parser:
             self.code += [OP_PUSH_CONST, v]
         elif k == "id":
             self.eat()
+            if v not in self.col and self.rows is not None and v in _SELECTORS:
+                self.code += [OP_PUSH_COL, getattr(self.rows, v)]
+                return
             if v not in self.col:
                 raise ValueError(f"unknown column {v}")
-            self.code += [OP_PUSH_COL, self.col[v]]
+            c = self.col[v]
+            if self.rows is not None and self.peek() == ("sym", "'"):  # `name'`: the column on the next row
+                self.eat()
+                c = self.rows.next(c)
+            self.code += [OP_PUSH_COL, c]
         elif (k, v) == ("sym", "("):
             self.eat()
             self.expr()
@@ -87,8 +94,14 @@ class _Parser:
             raise ValueError(f"unexpected token {self.peek()}")
 
 
-def compile_expr(text: str, col_index: dict) -> list:
-    p = _Parser(_tokens(text), col_index)
+# the row selectors as OpenVmReference's Display prints them (openvm/src/utils.rs:31-41)
+_SELECTORS = ("is_first_row", "is_last_row", "is_transition")
+
+
+def compile_expr(text: str, col_index: dict, rows=None) -> list:
+    """rows: the row layout (prover.RowOperands) — `name'` is that column on the next row and is_first_row / is_last_row /
+    is_transition are the selectors; without it both are rejected."""
+    p = _Parser(_tokens(text), col_index, rows)
     p.expr()
     if p.i != len(p.t):
         raise ValueError(f"trailing tokens in {text!r}")

@@ -332,10 +332,12 @@ extern "C" int pw_verify_logup(const PwStarkConfig* cfg, uint32_t width, uint32_
 namespace {
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3"
 constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": at least one AIR has preprocessed columns
+constexpr uint32_t kMagic5 = 0x35535750u;  // "PWS5": at least one AIR is row-aware
 
 struct SegShapeV {
     uint32_t W, nc, n_int, log_h;
     uint32_t Wf, W1;  // preprocessed columns, W + Wf
+    uint32_t rf, Wg;  // the row layout: kRowsNext | kRowsSelector of the constraint programs; W1 if two-point, else 0
     Digest pre_root;  // Montgomery
     size_t H, N, n_g, Wp, K, koff;
     int logN;
@@ -343,9 +345,9 @@ struct SegShapeV {
     uint32_t max_args;
 };
 
-// pre: NULL = no AIR has preprocessed columns (pw_verify_segment)
+// pre: NULL = no AIR has preprocessed columns (pw_verify_segment); rows: constraint operands over the row layout
 int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs, int logup_flag,
-                        const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+                        const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4, bool rows = false) {
     if (!cfg || !airs || !n_airs || !proof) return 15;
     const bool lg = logup_flag != 0;
     const size_t A = n_airs;
@@ -358,7 +360,7 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         if (d.log_height < 1 || d.log_height > 26 || !d.width) return 15;
         s.W = d.width; s.nc = (uint32_t)d.n_constraints; s.log_h = d.log_height; s.n_int = lg ? (uint32_t)d.n_interactions : 0;
         s.Wf = pre ? pre[a].width : 0;
-        if ((uint64_t)s.W + s.Wf > 0xffffffffull) return 15;
+        if ((uint64_t)s.W + s.Wf > (rows ? 0x7ffffff0ull : 0xffffffffull)) return 15;
         s.W1 = s.W + s.Wf;
         for (int k = 0; k < 8; ++k) {
             if (s.Wf && pre[a].root8[k] >= bb::P) return 15;
@@ -366,8 +368,15 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         }
         s.H = (size_t)1 << s.log_h; s.N = 2 * s.H; s.logN = (int)s.log_h + 1;
         s.max_args = 0; s.n_g = 0; s.Wp = 0;
-        for (size_t k = 0; k < d.n_constraints; ++k)
+        s.rf = 0;
+        for (size_t k = 0; k < d.n_constraints; ++k) {
             if ((size_t)d.cons_spans[2 * k] + d.cons_spans[2 * k + 1] > d.bytecode_len) return 15;
+            if (!rows) continue;
+            const uint32_t* c = d.cons_bytecode + d.cons_spans[2 * k];
+            if (!pw::postfix_columns_below(c, d.cons_spans[2 * k + 1], 2 * s.W1 + 3)) return 15;  // (before the flags pick the magic)
+            s.rf |= pw::postfix_row_flags(c, d.cons_spans[2 * k + 1], s.W1);
+        }
+        s.Wg = (s.rf & pw::kRowsNext) ? s.W1 : 0;
         if (lg) {
             for (size_t i = 0; i < d.n_interactions; ++i) {
                 const uint32_t na = d.interactions[3 * i + 1], first = d.interactions[3 * i + 2];
@@ -381,7 +390,7 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             s.n_g = s.gstarts.size() - 1;
             s.Wp = 4 * (s.n_g + 1);
         }
-        s.K = (size_t)s.W1 + 2 * s.Wp + 8;
+        s.K = (size_t)s.W1 + 2 * s.Wp + 8 + s.Wg;
         s.koff = K_total;
         K_total += s.K;
         if (s.logN > L) L = s.logN;
@@ -394,9 +403,9 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
     auto get_digest = [&]() { Digest d; for (auto& w : d.w) w = get_m(); return d; };
     auto get_ext = [&]() { Ext e; for (auto& w : e.c) w = get_m(); return e; };
 
-    bool any_pre = false;
-    for (size_t a = 0; a < A; ++a) any_pre = any_pre || sh[a].Wf;
-    std::vector<uint32_t> hdr = {any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries, cfg->pow_bits};
+    bool any_pre = false, any_rows = false;
+    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; }
+    std::vector<uint32_t> hdr = {any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries, cfg->pow_bits};
     for (size_t a = 0; a < A; ++a) for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) hdr.push_back(x);
     for (uint32_t h : hdr) if (get() != h) return 1;
     for (size_t i = 0; i < len; ++i) if (proof[i] >= bb::P) return 13;
@@ -408,6 +417,12 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         ch.observe(bb::to_monty((uint32_t)a % bb::P));
         ch.observe(bb::to_monty(sh[a].Wf % bb::P));
         ch.observe_n(sh[a].pre_root.w, 8);
+    }
+    // the row-aware AIRs and their flags (not in the proof)
+    for (size_t a = 0; a < A; ++a) {
+        if (!sh[a].rf) continue;
+        ch.observe(bb::to_monty((uint32_t)a % bb::P));
+        ch.observe(bb::to_monty(sh[a].rf));
     }
 
     const Digest t_root = get_digest();
@@ -430,7 +445,8 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
     for (auto& e : opened) { e = get_ext(); ch.observe_n(e.c, 4); }
     if (short_read) return 10;
 
-    // constraint identities at zeta, AIR by AIR (per-AIR layout: main | preprocessed | perm at zeta | quotient | perm at g zeta)
+    // constraint identities at zeta, AIR by AIR (per-AIR layout: main | preprocessed | perm at zeta | quotient | perm at g zeta, and for a
+    // two-point AIR then main | preprocessed at g zeta)
     std::vector<Ext> gzeta(A);
     for (size_t a = 0; a < A; ++a) {
         const PwAirDescription& d = airs[a];
@@ -448,14 +464,30 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             }
             return r;
         };
+        const Ext zH = bb::ext_pow(zeta, s.H);
+        const Ext zh = bb::ext_sub(zH, bb::ext_one());
+        // the values the constraint operands name: the W1 openings at zeta; with the row layout also those at g zeta (zero when not
+        // opened: no operand of such an AIR reads them) and the selectors at zeta
+        const Ext* cv = o;
+        uint32_t cw = s.W1;
+        std::vector<Ext> rv;
+        if (rows) {
+            rv.assign(2 * (size_t)s.W1 + 3, bb::ext_zero());
+            for (size_t k = 0; k < s.W1; ++k) rv[k] = o[k];
+            for (size_t k = 0; k < s.Wg; ++k) rv[s.W1 + k] = o[K1 + s.Wp + k];
+            const Ext trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
+            rv[2 * (size_t)s.W1] = bb::ext_mul(zh, bb::ext_inv(bb::ext_sub(zeta, bb::ext_one())));
+            rv[2 * (size_t)s.W1 + 1] = bb::ext_mul(zh, bb::ext_inv(trans));
+            rv[2 * (size_t)s.W1 + 2] = trans;
+            cv = rv.data();
+            cw = 2 * s.W1 + 3;
+        }
         Ext acc = bb::ext_zero();
         for (size_t k = 0; k < d.n_constraints; ++k) {
             Ext v;
-            if (!eval_ext(d.cons_bytecode + d.cons_spans[2 * k], d.cons_spans[2 * k + 1], o, s.W1, v)) return 15;
+            if (!eval_ext(d.cons_bytecode + d.cons_spans[2 * k], d.cons_spans[2 * k + 1], cv, cw, v)) return 15;
             acc = bb::ext_add(bb::ext_mul(acc, alpha), v);
         }
-        const Ext zH = bb::ext_pow(zeta, s.H);
-        const Ext zh = bb::ext_sub(zH, bb::ext_one());
         if (lg) {
             std::vector<Ext> blpow(s.max_args + 2);
             { Ext b = bb::ext_one(); for (auto& x : blpow) { x = b; b = bb::ext_mul(b, bl); } }
@@ -585,13 +617,16 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
                 Ext a1 = bb::ext_zero(), a2 = bb::ext_zero();
                 for (size_t k = 0; k < s.W; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[k], trow[a][k]));
                 for (size_t k = 0; k < s.Wf; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W + k], frow[a][k]));
+                // a two-point AIR: the same rows at g zeta, powers from K1 + Wp on
+                for (size_t k = 0; k < s.Wg; ++k)
+                    a2 = bb::ext_add(a2, bb::ext_scale(gp[K1 + s.Wp + k], k < s.W ? trow[a][k] : frow[a][k - s.W]));
                 for (size_t k = 0; k < s.Wp; ++k) {
                     a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W1 + k], prow[a][k]));
                     a2 = bb::ext_add(a2, bb::ext_scale(gp[K1 + k], prow[a][k]));
                 }
                 for (size_t k = 0; k < 8; ++k) a1 = bb::ext_add(a1, bb::ext_scale(gp[s.W1 + s.Wp + k], qrow[a][k]));
                 Ext t = bb::ext_mul(bb::ext_sub(a1, sum1[a]), bb::ext_inv(bb::ext_sub(bb::ext_from_base(x), zeta)));
-                if (lg) t = bb::ext_add(t, bb::ext_mul(bb::ext_sub(a2, sum2[a]), bb::ext_inv(bb::ext_sub(bb::ext_from_base(x), gzeta[a]))));
+                if (lg || s.Wg) t = bb::ext_add(t, bb::ext_mul(bb::ext_sub(a2, sum2[a]), bb::ext_inv(bb::ext_sub(bb::ext_from_base(x), gzeta[a]))));
                 r = bb::ext_add(r, t);
             }
             return r;
@@ -636,6 +671,13 @@ extern "C" int pw_verify_segment(const PwStarkConfig* cfg, const PwAirDescriptio
 extern "C" int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
                                               int logup_flag, const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
     return verify_segment_impl(cfg, airs, pre, n_airs, logup_flag, proof, len, check_balance, total_sum4);
+}
+
+// "pw-stark v1 + rows" (DESIGN.md §5h): constraint operands over the row layout (next rows, selectors); pre may be NULL. Without a
+// row-aware AIR: exactly pw_verify_segment_preprocessed.
+extern "C" int pw_verify_segment_transition(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
+                                            int logup_flag, const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+    return verify_segment_impl(cfg, airs, pre, n_airs, logup_flag, proof, len, check_balance, total_sum4, true);
 }
 
 // Boundaries of the LogUp groups the prover and the verifier derive from an interaction table (logup_groups.hpp):

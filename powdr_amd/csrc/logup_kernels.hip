@@ -276,10 +276,13 @@ __global__ __launch_bounds__(kBlock) void rowsum_combine_kernel(const uint32_t* 
 
 // ---- DEEP with two opening points ------------------------------------------------------------------------
 // v[j] = (sum_{k<K1} g^k f_k(x_j) - sum1) / (x_j - zeta) + (sum_{k<Wp} g^(K1+k) p_k(x_j) - sum2) / (x_j - g zeta)
+// TWO (a two-point AIR): the W columns are opened at g zeta as well, with powers gK g^k — their row combination R(x_j)
+// is kept apart and enters the second term as gK R(x_j): every LDE cell is still read once
+template <bool TWO>
 __global__ __launch_bounds__(kBlock) void deep_logup_kernel(const uint32_t* __restrict__ lde, uint32_t W, const uint32_t* __restrict__ plde,
                                                              uint32_t Wp, const uint32_t* __restrict__ qlde, size_t N,
                                                              const Ext* __restrict__ gpow, Ext sum1, Ext sum2, Ext zeta, Ext gzeta,
-                                                             uint32_t shift, uint32_t wN, Ext* __restrict__ v) {
+                                                             uint32_t shift, uint32_t wN, Ext gK, Ext* __restrict__ v) {
     const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= N) return;
     // centred gamma powers (host) x centred cells in signed 64-bit accumulators, folded every fourth column (bb::ExtCentredAcc)
@@ -294,6 +297,11 @@ __global__ __launch_bounds__(kBlock) void deep_logup_kernel(const uint32_t* __re
     }
     for (; k < W; ++k) w1.fma_uniform(g[k], bb::centred(lde[(size_t)k * N + j]));
     w1.fold();
+    Ext row = bb::ext_zero();
+    if (TWO) {
+        row = w1.result();
+        w1 = bb::ExtCentredAcc{};
+    }
     for (k = 0; k + 4 <= Wp; k += 4) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -316,7 +324,11 @@ __global__ __launch_bounds__(kBlock) void deep_logup_kernel(const uint32_t* __re
         for (int u = 0; u < 4; ++u) w1.fma_uniform(g[W + Wp + k + u], bb::centred(qlde[(size_t)(k + u) * N + j]));
         w1.fold();
     }
-    const Ext a1 = w1.result(), a2 = w2.result();
+    Ext a1 = w1.result(), a2 = w2.result();
+    if (TWO) {
+        a1 = bb::ext_add(a1, row);
+        a2 = bb::ext_add(a2, bb::ext_mul(gK, row));
+    }
     const uint32_t xj = bb::mul(shift, bb::pow_u32(wN, (uint32_t)j));
     const Ext xe = bb::ext_from_base(xj);
     const Ext t1 = bb::ext_mul(bb::ext_sub(a1, sum1), bb::ext_inv(bb::ext_sub(xe, zeta)));
@@ -381,8 +393,16 @@ int quotient_eval_logup(const uint32_t* lde, const uint32_t* plde, size_t N, int
 int deep_quotient_logup(const uint32_t* lde, uint32_t W, const uint32_t* plde, uint32_t Wp, const uint32_t* qlde, size_t N, int logN,
                         const bb::Ext* d_gpow, bb::Ext sum1, bb::Ext sum2, bb::Ext zeta, bb::Ext gzeta, bb::Ext* v) {
     ScopedKernelTimer t("deep_logup_kernel");
-    hipLaunchKernelGGL(deep_logup_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), lde, W, plde, Wp, qlde, N, d_gpow, sum1,
-                       sum2, zeta, gzeta, bb::to_monty(field::kCosetShift), field::root_of_unity(logN), v);
+    hipLaunchKernelGGL(deep_logup_kernel<false>, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), lde, W, plde, Wp, qlde, N, d_gpow, sum1,
+                       sum2, zeta, gzeta, bb::to_monty(field::kCosetShift), field::root_of_unity(logN), bb::ext_zero(), v);
+    return (int)hipGetLastError();
+}
+
+int deep_quotient_two_point(const uint32_t* lde, uint32_t W, const uint32_t* plde, uint32_t Wp, const uint32_t* qlde, size_t N, int logN,
+                            const bb::Ext* d_gpow, bb::Ext gK, bb::Ext sum1, bb::Ext sum2, bb::Ext zeta, bb::Ext gzeta, bb::Ext* v) {
+    ScopedKernelTimer t("deep_two_point_kernel");
+    hipLaunchKernelGGL(deep_logup_kernel<true>, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), lde, W, plde, Wp, qlde, N, d_gpow, sum1,
+                       sum2, zeta, gzeta, bb::to_monty(field::kCosetShift), field::root_of_unity(logN), gK, v);
     return (int)hipGetLastError();
 }
 

@@ -47,23 +47,69 @@ extern "C" size_t pw_prover_device_bytes(const PwProver* p);
 extern "C" int pw_prover_specialise(PwProver* p);
 extern "C" int pw_prover_specialised(const PwProver* p, size_t* n_kernels, size_t* code_bytes, size_t* n_chunks);
 
-// `device` = false: host tables only (pw_jit_compile_check: code generation + hiprtc need no GPU)
+// The row layout: the constraint programs of a row-aware AIR rewritten onto the compact device layout (prover_state.hpp
+// PwProver::row_flags), one program after the other; fills next_cols, *row_cols and new spans. Operands are in bounds (checked before).
+static std::vector<uint32_t> remap_row_programs(const uint32_t* bc, const uint32_t* spans, size_t n_constraints, uint32_t w1, uint32_t flags,
+                                                std::vector<uint32_t>& next_cols, uint32_t* row_cols, std::vector<uint32_t>& new_spans) {
+    // the next-row columns read, ascending (a sorted list, not a table of W1 entries: W1 comes from the caller)
+    next_cols.clear();
+    for (size_t k = 0; k < n_constraints; ++k)
+        for (uint32_t ip = spans[2 * k], end = spans[2 * k] + spans[2 * k + 1]; ip < end;) {
+            const uint32_t op = bc[ip++];
+            if (op != POWDR_OP_PUSH_APC && op != POWDR_OP_PUSH_CONST) continue;
+            const uint32_t a = bc[ip++];
+            if (op == POWDR_OP_PUSH_APC && a >= w1 && a < 2 * w1) next_cols.push_back(a - w1);
+        }
+    std::sort(next_cols.begin(), next_cols.end());
+    next_cols.erase(std::unique(next_cols.begin(), next_cols.end()), next_cols.end());
+    auto slot = [&](uint32_t c) { return (uint32_t)(std::lower_bound(next_cols.begin(), next_cols.end(), c) - next_cols.begin()); };
+    const uint32_t n_next = (uint32_t)next_cols.size();
+    *row_cols = n_next + ((flags & pw::kRowsSelector) ? 3u : 0u);
+    std::vector<uint32_t> out;
+    new_spans.clear();
+    for (size_t k = 0; k < n_constraints; ++k) {
+        new_spans.push_back((uint32_t)out.size());
+        new_spans.push_back(spans[2 * k + 1]);
+        for (uint32_t ip = spans[2 * k], end = spans[2 * k] + spans[2 * k + 1]; ip < end;) {
+            const uint32_t op = bc[ip++];
+            out.push_back(op);
+            if (op != POWDR_OP_PUSH_APC && op != POWDR_OP_PUSH_CONST) continue;
+            uint32_t a = bc[ip++];
+            if (op == POWDR_OP_PUSH_APC && a >= w1) a = a < 2 * w1 ? w1 + slot(a - w1) : w1 + n_next + (a - 2 * w1);
+            out.push_back(a);
+        }
+    }
+    return out;
+}
+
+// `device` = false: host tables only (pw_jit_compile_check: code generation + hiprtc need no GPU). rows_w1 != 0: the row layout over
+// rows_w1 (= width) columns — constraint operands below 2 rows_w1 + 3, is_transition of degree 0
 static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const uint32_t* bc, size_t bc_len,
-                               const uint32_t* spans, size_t n_constraints, bool device) {
+                               const uint32_t* spans, size_t n_constraints, bool device, uint32_t rows_w1 = 0) {
     if (!cfg || !width) return nullptr;
     PwProver* p = new PwProver();
     p->cfg = *cfg;
     p->width = width;
     p->n_constraints = (uint32_t)n_constraints;
     p->h_spans.assign(spans, spans + 2 * n_constraints);
+    const uint32_t bound = rows_w1 ? 2 * rows_w1 + 3 : width, deg0 = rows_w1 ? 2 * rows_w1 + 2 : 0xffffffffu;
     for (size_t k = 0; k < n_constraints; ++k) {
         const uint32_t off = spans[2 * k], len = spans[2 * k + 1];
-        const int d = (size_t)off + len <= bc_len ? pw::postfix_degree(bc + off, len) : pw::kBadDegree;
+        const int d = (size_t)off + len <= bc_len ? pw::postfix_degree(bc + off, len, deg0) : pw::kBadDegree;
         // a span past the bytecode, an unknown opcode, an unbalanced or too deep stack, a column the trace does not have: no prover — the
         // post-fix fallback below is for well-formed programs the xbc compiler declines, not for these (they would index past the
         // bytecode or the trace on the device)
-        if (d == pw::kBadDegree || !pw::postfix_columns_below(bc + off, len, width)) { delete p; return nullptr; }
+        if (d == pw::kBadDegree || !pw::postfix_columns_below(bc + off, len, bound)) { delete p; return nullptr; }
         if (d > p->max_degree) p->max_degree = d;
+        if (rows_w1) p->row_flags |= pw::postfix_row_flags(bc + off, len, rows_w1);
+    }
+    // a row-aware AIR's programs go to the device (and to the xbc compiler) rewritten onto the compact layout of its values
+    std::vector<uint32_t> row_bc, row_spans;
+    if (p->row_flags) {
+        row_bc = remap_row_programs(bc, spans, n_constraints, rows_w1, p->row_flags, p->h_next_cols, &p->row_cols, row_spans);
+        bc = row_bc.data();
+        bc_len = row_bc.size();
+        spans = row_spans.data();
     }
     // compile the post-fix constraint programs to xbc (xbc.hpp); fall back to the post-fix interpreter if
     // any program is malformed or too deep
@@ -93,6 +139,11 @@ static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const u
     }
     if (up_bc_len) (void)hipMemcpy(p->d_bytecode, up_bc, up_bc_len * 4, hipMemcpyHostToDevice);
     if (n_constraints) (void)hipMemcpy(p->d_spans, up_sp, 2 * n_constraints * 4, hipMemcpyHostToDevice);
+    if (!p->h_next_cols.empty() && (hipMalloc(&p->d_next_cols, p->h_next_cols.size() * 4) != hipSuccess ||
+                                    hipMemcpy(p->d_next_cols, p->h_next_cols.data(), p->h_next_cols.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        pw_prover_destroy(p);
+        return nullptr;
+    }
     return p;
 }
 
@@ -101,10 +152,12 @@ extern "C" PwProver* pw_prover_create(const PwStarkConfig* cfg, uint32_t width, 
     return create_prover(cfg, width, bc, bc_len, spans, n_constraints, true);
 }
 
+// (interaction operands stay below `width` with the row layout too)
 static PwProver* create_prover_logup(const PwStarkConfig* cfg, uint32_t width, const uint32_t* bc, size_t bc_len,
                                      const uint32_t* spans, size_t n_constraints, const uint32_t* inter, size_t n_inter,
-                                     const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len, bool device) {
-    PwProver* p = create_prover(cfg, width, bc, bc_len, spans, n_constraints, device);
+                                     const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len, bool device,
+                                     uint32_t rows_w1 = 0) {
+    PwProver* p = create_prover(cfg, width, bc, bc_len, spans, n_constraints, device, rows_w1);
     if (!p) return nullptr;
     // interactions: {bus, n_args, first span}; spans [mult, arg0, ...] into ibc (post-fix, column operands)
     std::vector<pw::LogupInteraction> li(n_inter);
@@ -166,14 +219,8 @@ extern "C" PwProver* pw_prover_create_logup(const PwStarkConfig* cfg, uint32_t w
 // the programs runs against the combined bound; the prover then keeps `width` as its main width. At creation the fixed matrix is
 // copied behind room for one trace, extended (blow-up 2, shift 31) and committed with the segment tree's own leaf sponge and
 // compression — the root is the main commitment a one-AIR segment proof of the fixed matrix would carry.
-extern "C" PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
-                                                   const uint32_t* d_pre, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
-                                                   size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
-                                                   size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
-    if (!cfg || !width || !pre_width || !d_pre || log_height < 1 || log_height > 26 || (uint64_t)width + pre_width > 0xffffffffull) return nullptr;
-    PwProver* p = inter ? create_prover_logup(cfg, width + pre_width, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true)
-                        : create_prover(cfg, width + pre_width, bc, bc_len, spans, n_constraints, true);
-    if (!p) return nullptr;
+// the fixed matrix of a prover made with the combined width: kept, extended and committed (NULL: failed, p destroyed)
+static PwProver* attach_preprocessed(PwProver* p, uint32_t width, uint32_t pre_width, uint32_t log_height, const uint32_t* d_pre) {
     p->width = width;
     p->pre_width = pre_width;
     p->pre_log_h = log_height;
@@ -205,6 +252,41 @@ extern "C" PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uin
     for (int k = 0; k < 8; ++k) p->pre_root[k] = bb::from_monty(root[k]);
     return p;
 }
+
+extern "C" PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                                   const uint32_t* d_pre, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
+                                                   size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
+                                                   size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
+    if (!cfg || !width || !pre_width || !d_pre || log_height < 1 || log_height > 26 || (uint64_t)width + pre_width > 0xffffffffull) return nullptr;
+    PwProver* p = inter ? create_prover_logup(cfg, width + pre_width, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true)
+                        : create_prover(cfg, width + pre_width, bc, bc_len, spans, n_constraints, true);
+    if (!p) return nullptr;
+    return attach_preprocessed(p, width, pre_width, log_height, d_pre);
+}
+
+// Next-row operands and row selectors: constraint operands over the row layout of W1 = width + pre_width columns,
+// interaction operands below W1, constraint degrees by Plonky3's rule at most 3. pre_width = 0: no fixed matrix (log_height and d_pre
+// unused; any height >= 2 rows). A prover whose constraints read only current-row columns acts exactly as the plain (or preprocessed) one.
+extern "C" PwProver* pw_prover_create_transition(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                                 const uint32_t* d_pre, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
+                                                 size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
+                                                 size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
+    if (!cfg || !width || (uint64_t)width + pre_width > 0x7ffffff0ull) return nullptr;  // (2 W1 + 3 operands fit in 32 bits)
+    if (pre_width && (!d_pre || log_height < 1 || log_height > 26)) return nullptr;
+    const uint32_t w1 = width + pre_width;
+    PwProver* p = inter ? create_prover_logup(cfg, w1, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true, w1)
+                        : create_prover(cfg, w1, bc, bc_len, spans, n_constraints, true, w1);
+    if (!p) return nullptr;
+    if (p->max_degree > 3) { pw_prover_destroy(p); return nullptr; }  // a blow-up-2 quotient carries degree 3
+    p->transition = true;
+    if (!pre_width) { p->width = width; return p; }
+    return attach_preprocessed(p, width, pre_width, log_height, d_pre);
+}
+
+extern "C" uint32_t pw_prover_row_flags(const PwProver* p) { return p ? p->row_flags : 0; }
+namespace pw {
+bool prover_segment_only(const PwProver* p) { return p && (p->pre_width || p->transition); }
+}  // namespace pw
 
 extern "C" int pw_prover_preprocessed_root(const PwProver* p, uint32_t* root8) {
     if (!p || !root8 || !p->pre_width) return -1;
@@ -523,7 +605,7 @@ int ensure_proof_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bo
 // Trace commitment only (LDE + Merkle root): what a segment's AIRs exchange before the bus seed can be formed.
 extern "C" int pw_prover_trace_root(PwProver* p, const uint32_t* d_trace, uint32_t log_h, uint32_t* root8) {
     if (!p || !d_trace || !root8 || log_h < 1 || log_h > 26) return (int)hipErrorInvalidValue;
-    if (p->pre_width) return -1;  // preprocessed columns are a segment-proof feature
+    if (p->pre_width || p->transition) return -1;  // preprocessed columns and the row layout are segment-proof features
     (void)hipGetLastError();
     TRY(poseidon2_upload_params());
     CommitLayout L;
@@ -580,8 +662,9 @@ static PwProver::OpenedMailbox* opened_mailbox(PwProver* p, size_t K) {
 extern "C" void pw_prover_destroy(PwProver* p) {
     if (!p) return;
     for (DeviceBuf* b : {&p->coef, &p->lde, &p->digests, &p->q, &p->qcoef, &p->qlde, &p->ext_arena, &p->misc, &p->perm, &p->plde, &p->qpart, &p->tcoef,
-                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree})
+                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree, &p->row_vals})
         b->release();
+    if (p->d_next_cols) (void)hipFree(p->d_next_cols);
     for (void* q : {(void*)p->d_inter, (void*)p->d_ixspans, (void*)p->d_icode, (void*)p->d_gstarts, (void*)p->d_iforms}) if (q) (void)hipFree(q);
     if (p->d_bytecode) (void)hipFree(p->d_bytecode);
     if (p->d_spans) (void)hipFree(p->d_spans);
@@ -614,7 +697,7 @@ extern "C" int pw_prover_stream_log_blocks(const PwProver* p, uint32_t log_h) {
 extern "C" size_t pw_prover_device_bytes(const PwProver* p) {
     return p->coef.bytes + p->lde.bytes + p->digests.bytes + p->q.bytes + p->qcoef.bytes + p->qlde.bytes +
            p->ext_arena.bytes + p->misc.bytes + p->perm.bytes + p->plde.bytes + p->qpart.bytes + p->tcoef.bytes + p->fscale.bytes + p->gbuf.bytes +
-           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes;
+           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes + p->row_vals.bytes;
 }
 
 
@@ -622,7 +705,7 @@ namespace {
 // consume: pw_prover_prove_consuming — d_trace is the caller's to give away. Only a STREAMED proof uses that: the coefficient arrays
 // of the trace end up in d_trace itself (no tcoef buffer: 62.6 GB at configs[2], which is what lets it run on 2 sub-cosets instead of 4).
 int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint32_t** proof_words, size_t* n_words, bool consume) {
-    if (!p || !d_trace || log_h < 1 || log_h > 26 || p->pre_width) return -1;  // (preprocessed columns: segment proofs only)
+    if (!p || !d_trace || log_h < 1 || log_h > 26 || p->pre_width || p->transition) return -1;  // (preprocessed columns, rows: segment proofs only)
     // a handed-over trace becomes a coefficient array that is read 2 / 4 words at a time (fold loads, the DEEP combination)
     if (consume && ((uintptr_t)d_trace & 15)) return (int)hipErrorInvalidValue;
     (void)hipGetLastError();
@@ -1090,7 +1173,21 @@ extern "C" int pw_prover_check_constraints(PwProver* p, const uint32_t* d_trace,
     if (!p || !d_trace || log_h > 40 || (p->pre_width && log_h != p->pre_log_h)) return -1;
     (void)hipGetLastError();
     const size_t H = (size_t)1 << log_h;
-    if (p->pre_width) {  // operands >= width read the fixed matrix: the trace goes in front of it
+    if (p->row_flags) {
+        // the row layout on the trace domain: (trace | fixed) and behind it the next rows (j + 1 mod H) and the
+        // selectors' exact values — what the remapped programs read (heights a segment can prove: the roots of unity and the
+        // kernel's 32-bit row powers end there)
+        if (log_h < 1 || log_h > 26) return -1;
+        const uint32_t w1 = p->width + p->pre_width;
+        TRY(p->row_vals.ensure(((size_t)w1 + p->row_cols) * H * 4));
+        uint32_t* v = p->row_vals.as<uint32_t>();
+        PW_HIP_TRY(hipMemcpyAsync(v, d_trace, (size_t)p->width * H * 4, hipMemcpyDeviceToDevice, stream()));
+        if (p->pre_width)
+            PW_HIP_TRY(hipMemcpyAsync(v + (size_t)p->width * H, p->pre_vals.as<uint32_t>() + (size_t)p->width * H, (size_t)p->pre_width * H * 4,
+                                      hipMemcpyDeviceToDevice, stream()));
+        TRY(row_layout_columns(v, H, (int)log_h, w1, p->d_next_cols, (uint32_t)p->h_next_cols.size(), 1, (p->row_flags & kRowsSelector) != 0, true));
+        d_trace = v;
+    } else if (p->pre_width) {  // operands >= width read the fixed matrix: the trace goes in front of it
         PW_HIP_TRY(hipMemcpyAsync(p->pre_vals.as<uint32_t>(), d_trace, (size_t)p->width * H * 4, hipMemcpyDeviceToDevice, stream()));
         d_trace = p->pre_vals.as<uint32_t>();
     }

@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct PwProver;  // prover_state.hpp (include/powdr_prover.h: the opaque handle)
+
 namespace pw {
 
 namespace field {
@@ -93,6 +95,10 @@ inline size_t merkle_level_offset(size_t n_leaves, int level) {  // in words
     return off;
 }
 
+// ---- prover.hip ------------------------------------------------------------------------
+// a prover made with preprocessed columns or by pw_prover_create_transition: segment proofs only (pw_prove_airs refuses it)
+bool prover_segment_only(const ::PwProver* p);
+
 // ---- stark_kernels.hip -----------------------------------------------------------------
 struct ConstraintProgram {
     const uint32_t* d_bytecode;  // PUSH_COL operands = column index (reference post-fix encoding) or xbc code
@@ -111,6 +117,11 @@ int quotient_eval(const uint32_t* lde, size_t N, const ConstraintProgram& prog, 
 // q = (sum of n_chunks partial sums) * zinv, partial sums as quotient_eval leaves them in `part`
 int quotient_combine(const uint32_t* part, uint32_t n_chunks, size_t N, uint32_t zinv_even, uint32_t zinv_odd, uint32_t* q);
 int check_constraints(const uint32_t* trace, size_t H, const ConstraintProgram& prog, unsigned long long* d_first_and_count);
+// The row layout's values behind the W1 columns of an n-row matrix m (column stride n): column W1 + i = column
+// next_cols[i] shifted up by `step` rows (cyclic; the LDE: 2, the trace: 1), then, when `selectors`, is_first_row, is_last_row and
+// is_transition at x_j — on the LDE coset (trace_domain = false) or their exact values on the trace domain g^j (true)
+int row_layout_columns(uint32_t* m, size_t n, int log_n, uint32_t w1, const uint32_t* d_next_cols, uint32_t n_next, uint32_t step,
+                       bool selectors, bool trace_domain);
 // chunk coefficients from the unscaled DIF-iNTT of q over N = 2H points:
 // out[(4*ch + k)*H + q'] = cbr[k*N + 2q' + ch] * s^-(bitrev(q') + ch*H) / 2   (H-scaled bit-reversed coefficients)
 int quotient_split(const uint32_t* cbr, size_t H, int log_h, uint32_t* out);
@@ -179,6 +190,11 @@ int quotient_eval_logup(const uint32_t* lde, const uint32_t* plde, size_t N, int
                         uint32_t zval_even, uint32_t zval_odd, uint32_t* q, bool main_only = false);
 int deep_quotient_logup(const uint32_t* lde, uint32_t W, const uint32_t* plde, uint32_t Wp, const uint32_t* qlde, size_t N, int logN,
                         const bb::Ext* d_gpow, bb::Ext sum1, bb::Ext sum2, bb::Ext zeta, bb::Ext gzeta, bb::Ext* v);
+// the same for a two-point AIR: its W main + preprocessed columns are also opened at g zeta, with the gamma powers
+// gK * gpow[k] (gK = gamma^(W + 2 Wp + 8)); the row combination of the W columns is formed once and used at both points. Wp = 0: a
+// constraints-only segment (plde unused)
+int deep_quotient_two_point(const uint32_t* lde, uint32_t W, const uint32_t* plde, uint32_t Wp, const uint32_t* qlde, size_t N, int logN,
+                            const bb::Ext* d_gpow, bb::Ext gK, bb::Ext sum1, bb::Ext sum2, bb::Ext zeta, bb::Ext gzeta, bb::Ext* v);
 
 // ---- stream_kernels.hip (the streamed proof path) ---------------------------------------------------------------------
 // out[k * N + r + (i << b)] = sum_c part[(c * 4 + k) * m + i]: the partial quotient sums of sub-coset r into their rows of the N-row vector

@@ -15,6 +15,7 @@ constexpr uint32_t kMagic = 0x31535750u;   // "PWS1"
 constexpr uint32_t kMagic2 = 0x32535750u;  // "PWS2": with the LogUp extension
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3": one proof per segment (segment_prover.hip)
 constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": a segment proof in which at least one AIR has preprocessed columns
+constexpr uint32_t kMagic5 = 0x35535750u;  // "PWS5": a segment proof in which at least one AIR is row-aware
 
 // ---- duplex-sponge challenger on Montgomery words (spec: oracle/stark_oracle.cpp Challenger) ----
 struct Challenger {
@@ -119,6 +120,17 @@ struct PwProver {
     uint32_t pre_width = 0, pre_log_h = 0;
     uint32_t pre_root[8] = {0};  // canonical: the verifying key's part
     pw::DeviceBuf pre_vals, pre_lde, pre_tree;
+    // the row layout (pw_prover_create_transition; segment proofs only). `transition`: made by that entry. row_flags:
+    // pw::kRowsNext | pw::kRowsSelector over the constraint programs, 0 = not row-aware (the prover then acts as a plain one). The
+    // device programs of a row-aware AIR are remapped onto a compact layout of the values they read,
+    //     [main | preprocessed | next_cols[0] .. next_cols[n-1] on the next row | is_first_row is_last_row is_transition (if read)]
+    // — `row_cols` columns behind the W1 = width + pre_width ones — which the segment prover writes behind the AIR's LDE (rows j + 2)
+    // and the mock prover into `row_vals` (rows j + 1, the selectors' values on the trace domain)
+    bool transition = false;
+    uint32_t row_flags = 0, row_cols = 0;
+    std::vector<uint32_t> h_next_cols;
+    uint32_t* d_next_cols = nullptr;
+    pw::DeviceBuf row_vals;
     // host copies of the plan-compiled (xbc) programs: the source of the run-time specialised kernels (jit_codegen.hpp)
     std::vector<uint32_t> h_xcode, h_xspans, h_icode, h_ixspans, h_gstarts;
     std::vector<pw::LogupInteraction> h_inter;

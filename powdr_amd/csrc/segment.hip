@@ -106,8 +106,8 @@ extern "C" int pw_prove_airs(const PwSegmentAir* airs, size_t n_airs, int shared
     if (!airs || !proofs || !n_words) return (int)hipErrorInvalidValue;
     for (size_t i = 0; i < n_airs; ++i)
         if (!airs[i].prover || !airs[i].d_trace) return (int)hipErrorInvalidValue;
-    for (size_t i = 0; i < n_airs; ++i)
-        if (pw_prover_preprocessed_width(airs[i].prover)) return -1;  // preprocessed columns are a segment-proof (pw_prove_segment) feature
+    for (size_t i = 0; i < n_airs; ++i)  // preprocessed columns and the row layout are segment-proof (pw_prove_segment) features
+        if (pw::prover_segment_only(airs[i].prover)) return -1;
     if (n_workers == 0) n_workers = 4;
     if (n_workers > n_airs) n_workers = (unsigned)n_airs;
     // largest (by cells) first: the tail of the schedule is filled with the small proofs

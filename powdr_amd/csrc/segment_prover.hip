@@ -75,6 +75,9 @@ thread_local SegCtx g_ctx;  // one per host thread (= per launch stream)
 struct Shape {
     uint32_t W, nc, n_int, n_g, Wp, M, K, log_h;
     uint32_t Wf, W1;  // preprocessed columns, W1 = W + Wf: the columns the programs and the ζ openings see
+    // the row layout: rf = kRowsNext | kRowsSelector (0: not row-aware), Wr = the values behind the W1 columns of the
+    // LDE (next rows, selectors), Wg = the columns opened at g zeta besides the permutation matrix (W1 for a two-point AIR, else 0)
+    uint32_t rf, Wr, Wg;
     size_t H, N, koff;
     int logN;
 };
@@ -89,7 +92,7 @@ AirPlan plan_air(const PwProver* p, const Shape& s, bool logup) {
     AirPlan B;
     B.panel_cols = lde_panel_cols(s.H, logup ? std::max<size_t>(s.W, s.Wp) : s.W);
     B.coef = B.panel_cols * s.H * 4;
-    B.lde = (size_t)s.W1 * s.N * 4;  // the fixed matrix's LDE rides behind the main columns
+    B.lde = ((size_t)s.W1 + s.Wr) * s.N * 4;  // the fixed matrix's LDE rides behind the main columns, the row layout's values behind both
     if (logup) {  // + the uncommitted per-row-sum columns of the specialised path
         B.perm = (size_t)(s.Wp + kJitExtraPermCols) * s.H * 4;
         B.plde = (size_t)(s.Wp + kJitExtraPermCols) * s.N * 4;
@@ -251,7 +254,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         s.n_int = lg ? p->n_inter : 0; s.n_g = lg ? p->n_groups : 0; s.Wp = lg ? 4 * (s.n_g + 1) : 0;
         s.M = s.nc + (lg ? s.n_g + 3 : 0);
         s.Wf = p->pre_width; s.W1 = s.W + s.Wf;
-        s.K = s.W1 + 2 * s.Wp + 8;
+        s.rf = p->row_flags; s.Wr = p->row_cols; s.Wg = (s.rf & kRowsNext) ? s.W1 : 0;
+        s.K = s.W1 + 2 * s.Wp + 8 + s.Wg;
         s.H = (size_t)1 << s.log_h; s.N = 2 * s.H; s.logN = (int)s.log_h + 1;
         s.koff = K_total;
         K_total += s.K;
@@ -312,8 +316,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     cx.last_plan[0] = cx.last_plan[1] = cx.last_plan[2] = 0;
     cx.plan_resident.clear(); cx.plan_streamed.clear(); cx.plan_b_max.clear();
     {
-        // (AIRs that share a height: their level is hashed run by run); an AIR with preprocessed columns is always resident
-        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3 && !sh[a].Wf; };
+        // (AIRs that share a height: their level is hashed run by run); an AIR with preprocessed columns or the row layout is always resident
+        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3 && !sh[a].Wf && !sh[a].rf; };
         auto b_max = [&](size_t a) { return std::min((int)sh[a].log_h - 1, 5); };
         if (!by_air.empty()) {  // forced per AIR (tests: mixed levels)
             for (size_t a = 0; a < A; ++a) if (may_stream(a) && by_air[a] > 0) sbv[a] = std::min(by_air[a], b_max(a));
@@ -365,9 +369,10 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     auto put = [&](uint32_t canonical) { pf.push_back(canonical); };
     auto put_monty = [&](const uint32_t* w, size_t n) { for (size_t i = 0; i < n; ++i) pf.push_back(bb::from_monty(w[i])); };
     Challenger ch;
-    bool any_pre = false;
-    for (size_t a = 0; a < A; ++a) any_pre = any_pre || sh[a].Wf;
-    for (uint32_t x : {any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg.num_queries, cfg.pow_bits}) { ch.observe_canonical(x % bb::P); put(x); }
+    bool any_pre = false, any_rows = false;
+    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; }
+    const uint32_t magic = any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3;
+    for (uint32_t x : {magic, (uint32_t)A, lg ? 1u : 0u, cfg.num_queries, cfg.pow_bits}) { ch.observe_canonical(x % bb::P); put(x); }
     for (size_t a = 0; a < A; ++a)
         for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) { ch.observe_canonical(x % bb::P); put(x); }
     // the verifying key's preprocessed commitments: observed, not written
@@ -376,6 +381,12 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         ch.observe_canonical((uint32_t)a % bb::P);
         ch.observe_canonical(sh[a].Wf % bb::P);
         for (int k = 0; k < 8; ++k) ch.observe_canonical(airs[a].prover->pre_root[k]);
+    }
+    // which AIRs are row-aware, and how: derived from the programs, observed, not written
+    for (size_t a = 0; a < A; ++a) {
+        if (!sh[a].rf) continue;
+        ch.observe_canonical((uint32_t)a % bb::P);
+        ch.observe_canonical(sh[a].rf);
     }
 
     // mixed commitment of one matrix per AIR: matrix(a) = (device pointer, width); heights are the AIRs' LDE heights
@@ -459,6 +470,10 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                                           hipMemcpyDeviceToDevice, stream()));
             }
             TRY(lde_matrix(p, Lc[a], sh[a].log_h, airs[a].d_trace, sh[a].W, p->lde.as<uint32_t>()));
+            // the row layout: next rows (LDE row j + 2 = the point g x_j) and the selectors at x_j behind the W1 columns
+            if (sh[a].rf)
+                TRY(row_layout_columns(p->lde.as<uint32_t>(), sh[a].N, sh[a].logN, sh[a].W1, p->d_next_cols, (uint32_t)p->h_next_cols.size(), 2,
+                                       (sh[a].rf & kRowsSelector) != 0, false));
         }
     }
     TRY(join());
@@ -583,7 +598,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     put_monty(root, 8);
     ch.observe_words(root, 8);
 
-    // ---- 4. openings: per AIR main | preprocessed | perm at zeta | quotient | perm at g zeta ---------------------
+    // ---- 4. openings: per AIR main | preprocessed | perm at zeta | quotient | perm at g zeta [| main | preprocessed at g zeta] ----
     const bb::Ext zeta = ch.sample_ext();
     std::vector<bb::Ext> gzeta(A);
     TRY(fork());
@@ -596,13 +611,17 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         bb::Ext* w2 = w1 + s.H;
         gzeta[a] = bb::ext_scale(zeta, field::root_of_unity((int)s.log_h));
         // trace columns: barycentric evaluation straight from the caller's trace (with preprocessed columns: the (trace | fixed) copy,
-        // both in one pass); quotient chunks from their coefficients
+        // both in one pass; a two-point AIR: at zeta and at g zeta in that pass); quotient chunks from their coefficients
         if (!eat[a]) {
             TRY(barycentric_weights(zeta, (int)s.log_h, w1));
-            TRY(ext_dot_columns(values_of(a), s.H, s.W1, s.H, w1, o, scratch_of(a)));
+            if (s.Wg) {
+                TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
+                TRY(ext_dot_columns2(values_of(a), s.H, s.W1, s.H, w1, w2, o, o + s.W1 + 2 * s.Wp + 8, scratch_of(a)));
+            } else
+                TRY(ext_dot_columns(values_of(a), s.H, s.W1, s.H, w1, o, scratch_of(a)));
         }
         if (lg && !sbv[a]) {  // the permutation matrix at zeta and at g zeta: one pass over its columns
-            TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
+            if (!s.Wg) TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
             TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W1, o + s.W1 + s.Wp + 8, scratch_of(a)));
         }
         TRY(zeta_weights(zeta, (int)s.log_h, w1));
@@ -642,6 +661,9 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
             if (sbv[a])
                 TRY(streamed::deep_from_coefficients(sctx(a), lg, tcoef_of(a), p->perm.as<uint32_t>(), p->qlde.as<uint32_t>(), s.logN,
                                                      d_gpow + s.koff, [] {}, sum1, sum2, zeta, gzeta[a], out));
+            else if (s.Wg)  // two-point: the W1 columns at both points from one read of their LDE
+                TRY(deep_quotient_two_point(p->lde.as<uint32_t>(), s.W1, lg ? p->plde.as<uint32_t>() : nullptr, s.Wp, p->qlde.as<uint32_t>(), s.N,
+                                            s.logN, d_gpow + s.koff, bb::ext_pow(gamma, K1 + s.Wp), sum1, sum2, zeta, gzeta[a], out));
             else if (s.log_h >= kDeepComboMinLogHeight && !s.Wf && !getenv("POWDR_DEEP_DIRECT") && !((uintptr_t)airs[a].d_trace & 7)) {
                 // resident and tall: the numerator is combined on the evaluations over <g_n> — the caller's trace, the permutation
                 // matrix: half the bytes their LDE holds — and extended as 4 (+ 4) columns, like the one-AIR prover does

@@ -108,6 +108,28 @@ __global__ __launch_bounds__(kBlock) void check_constraints_kernel(const uint32_
     }
 }
 
+// ---- the row layout --------------------------------------------------------------
+// blockIdx.y = i < n_next: m[(w1 + i) n + j] = m[next_cols[i] n + (j + step) mod n]; blockIdx.y = n_next + s: selector s at x_j
+// (x = shift w^j; trace_domain: shift = 1, the exact values of Z_H(x) / (x - 1) and Z_H(x) / (x - g^-1) at the roots, H and H g)
+__global__ __launch_bounds__(kBlock) void row_layout_kernel(uint32_t* __restrict__ m, size_t n, uint32_t w1, const uint32_t* __restrict__ next_cols,
+                                                             uint32_t n_next, uint32_t step, uint32_t shift, uint32_t wn, uint32_t ginv,
+                                                             uint32_t zv_even, uint32_t zv_odd, uint32_t h_m, uint32_t hg_m, int trace_domain) {
+    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t y = blockIdx.y;  // wave-uniform: which column this block writes
+    if (y < n_next) {
+        m[(size_t)(w1 + y) * n + j] = m[(size_t)next_cols[y] * n + ((j + step) & (n - 1))];
+        return;
+    }
+    const uint32_t s = y - n_next;
+    const uint32_t x = bb::mul(shift, bb::pow_u32(wn, (uint32_t)j));
+    uint32_t v;
+    if (s == 2) v = bb::sub(x, ginv);
+    else if (trace_domain) v = s == 0 ? (j == 0 ? h_m : 0u) : (j == n - 1 ? hg_m : 0u);
+    else v = bb::mul((j & 1) ? zv_odd : zv_even, bb::inv(bb::sub(x, s == 0 ? bb::R_MOD_P : ginv)));
+    m[(size_t)(w1 + n_next + s) * n + j] = v;
+}
+
 // out[(4*ch + k)*H + q'] = cbr[k*N + 2q' + ch] * s^-(bitrev(q') + ch*H) / 2
 __global__ __launch_bounds__(kBlock) void quotient_split_kernel(const uint32_t* __restrict__ cbr, size_t H, int log_h,
                                                                  uint32_t sinv, uint32_t half_m, uint32_t* __restrict__ out) {
@@ -473,6 +495,26 @@ int gather_rows_multi(const GatherRowsJob* d_jobs, uint32_t n_jobs, uint32_t max
     ScopedKernelTimer t("gather_rows_kernel");
     const uint32_t gx = std::min<uint32_t>(div_up(max_width, kBlock), 8u);
     hipLaunchKernelGGL(gather_rows_multi_kernel, dim3(gx, n_idx, n_jobs), dim3(kBlock), 0, stream(), d_jobs, d_indices, out);
+    return (int)hipGetLastError();
+}
+
+int row_layout_columns(uint32_t* m, size_t n, int log_n, uint32_t w1, const uint32_t* d_next_cols, uint32_t n_next, uint32_t step,
+                       bool selectors, bool trace_domain) {
+    const uint32_t n_cols = n_next + (selectors ? 3u : 0u);
+    if (!n_cols) return 0;
+    if (n_cols > 65535u || n < 2 || (n & (n - 1))) return (int)hipErrorInvalidValue;
+    // the LDE: x_j = s w_N^j, g = w_N^2, Z_H(x_j) = s^H (-1)^j - 1; the trace: x_j = g^j
+    const uint32_t wn = field::root_of_unity(log_n);
+    const uint32_t shift = trace_domain ? bb::R_MOD_P : bb::to_monty(field::kCosetShift);
+    const uint32_t ginv = bb::inv(trace_domain ? wn : bb::sqr(wn));
+    const size_t H = trace_domain ? n : n / 2;
+    uint32_t sH = shift;
+    for (size_t h = 1; h < H; h <<= 1) sH = bb::sqr(sH);
+    const uint32_t zv_even = bb::sub(sH, bb::R_MOD_P), zv_odd = bb::sub(bb::neg(sH), bb::R_MOD_P);
+    const uint32_t h_m = bb::to_monty((uint32_t)(H % bb::P)), hg_m = bb::mul(h_m, trace_domain ? wn : bb::sqr(wn));
+    ScopedKernelTimer t("row_layout_kernel");
+    hipLaunchKernelGGL(row_layout_kernel, dim3(div_up(n, kBlock), n_cols), dim3(kBlock), 0, stream(), m, n, w1, d_next_cols, n_next, step, shift,
+                       wn, ginv, zv_even, zv_odd, h_m, hg_m, trace_domain ? 1 : 0);
     return (int)hipGetLastError();
 }
 

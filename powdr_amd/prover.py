@@ -20,7 +20,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
                   "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables",
-                  "pw_prover_create_preprocessed", "pw_prover_preprocessed_root", "pw_prover_preprocessed_width", "pw_verify_segment_preprocessed"]
+                  "pw_prover_create_preprocessed", "pw_prover_preprocessed_root", "pw_prover_preprocessed_width", "pw_verify_segment_preprocessed",
+                  "pw_prover_create_transition", "pw_prover_row_flags", "pw_verify_segment_transition"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -35,6 +36,10 @@ lib.pw_prover_preprocessed_root.restype = C.c_int
 lib.pw_prover_preprocessed_root.argtypes = [C.c_void_p, C.c_void_p]
 lib.pw_prover_preprocessed_width.restype = C.c_uint32
 lib.pw_prover_preprocessed_width.argtypes = [C.c_void_p]
+lib.pw_prover_create_transition.restype = C.c_void_p
+lib.pw_prover_create_transition.argtypes = lib.pw_prover_create_preprocessed.argtypes
+lib.pw_prover_row_flags.restype = C.c_uint32
+lib.pw_prover_row_flags.argtypes = [C.c_void_p]
 lib.pw_prover_prove.restype = C.c_int
 lib.pw_prover_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
 lib.pw_prover_check_constraints.restype = C.c_int
@@ -151,6 +156,8 @@ class PwAirPreprocessed(C.Structure):
 lib.pw_verify_segment_preprocessed.restype = C.c_int
 lib.pw_verify_segment_preprocessed.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.POINTER(PwAirPreprocessed), C.c_size_t, C.c_int,
                                                C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+lib.pw_verify_segment_transition.restype = C.c_int
+lib.pw_verify_segment_transition.argtypes = lib.pw_verify_segment_preprocessed.argtypes
 lib.pw_verify_airs.restype = C.c_int
 lib.pw_verify_airs.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.c_size_t, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p]
@@ -160,6 +167,26 @@ lib.pw_commitment_digest.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
 
 lib.pw_logup_group_starts.restype = C.c_size_t
 lib.pw_logup_group_starts.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+
+
+class RowOperands:
+    """The operand layout of constraint programs with next-row reads and row selectors (pw_prover_create_transition):
+    W1 = width + pre_width; c < W1 the current row, next(c) = W1 + c the next row, then is_first_row, is_last_row, is_transition."""
+
+    def __init__(self, width: int, pre_width: int = 0):
+        self.width, self.pre_width = int(width), int(pre_width)
+        self.w1 = self.width + self.pre_width
+        self.is_first_row, self.is_last_row, self.is_transition = 2 * self.w1, 2 * self.w1 + 1, 2 * self.w1 + 2
+        self.bound = 2 * self.w1 + 3  # constraint operands below this; interaction operands below w1
+
+    def next(self, c: int) -> int:
+        if not 0 <= c < self.w1:
+            raise ValueError(f"column {c}: the current row has {self.w1} columns")
+        return self.w1 + c
+
+
+def row_operands(width: int, pre_width: int = 0) -> RowOperands:
+    return RowOperands(width, pre_width)
 
 
 def logup_group_starts(interactions) -> np.ndarray:
@@ -301,16 +328,21 @@ def set_device_budget(n_bytes: int) -> None:
 
 
 def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logup: bool = False, check_balance: bool = False,
-                   preprocessed=None):
+                   preprocessed=None, transition: bool = False):
     """Host verification of a segment proof. descs: [(width, log_height, cons_bytecode, cons_spans, interactions-or-None)]
     -> (code, sum of the AIRs' cumulative bus sums). 0 = valid; ((i+1) << 8) | 2 = constraint identity of AIR i;
     14 = the bus sums do not cancel (check_balance); 16 = a preprocessed row does not open against its root.
     preprocessed: None (pw_verify_segment) or, per AIR, None | (width, root8) — the verifying key's preprocessed commitments
-    (pw_verify_segment_preprocessed)."""
+    (pw_verify_segment_preprocessed). transition: constraint operands over the row layout (RowOperands; pw_verify_segment_transition,
+    which also takes `preprocessed`)."""
     recs, keep = _air_descriptions(descs)
     pr = np.ascontiguousarray(proof, dtype=np.uint32)
     cfg = PwStarkConfig(num_queries, pow_bits)
     total = np.zeros(4, np.uint32)
+    if transition and preprocessed is None:
+        rc = int(lib.pw_verify_segment_transition(C.byref(cfg), recs, None, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr),
+                                                  int(check_balance), total.ctypes.data_as(C.c_void_p)))
+        return rc, total
     if preprocessed is None:
         rc = int(lib.pw_verify_segment(C.byref(cfg), recs, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr), int(check_balance),
                                        total.ctypes.data_as(C.c_void_p)))
@@ -323,8 +355,9 @@ def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logu
             pre[i].width = int(w)
             for k, x in enumerate(np.asarray(root, dtype=np.uint32).reshape(8)):
                 pre[i].root8[k] = int(x)
-    rc = int(lib.pw_verify_segment_preprocessed(C.byref(cfg), recs, pre, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr),
-                                                int(check_balance), total.ctypes.data_as(C.c_void_p)))
+    fn = lib.pw_verify_segment_transition if transition else lib.pw_verify_segment_preprocessed
+    rc = int(fn(C.byref(cfg), recs, pre, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr), int(check_balance),
+                total.ctypes.data_as(C.c_void_p)))
     return rc, total
 
 
@@ -498,16 +531,34 @@ class Prover:
     host.compile_bus(apc, 1) — switches the prover to "pw-stark v0 + LogUp" (proof magic PWS2).
 
     preprocessed = (device tensor of the fixed matrix (column-major, Montgomery), pre_width, log_height): operands width ..
-    width + pre_width - 1 of the programs are those columns (pw_prover_create_preprocessed; segment proofs only, at that height)."""
+    width + pre_width - 1 of the programs are those columns (pw_prover_create_preprocessed; segment proofs only, at that height).
+
+    transition = True: the constraint programs may read the next row and the row selectors (RowOperands, DESIGN.md §5h;
+    pw_prover_create_transition, with or without `preprocessed`; segment proofs only)."""
 
     def __init__(self, width: int, cons_bytecode, cons_spans, num_queries: int = 100, pow_bits: int = 0, interactions=None,
-                 preprocessed=None):
+                 preprocessed=None, transition: bool = False):
         bc = np.ascontiguousarray(cons_bytecode, dtype=np.uint32)
         sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
         cfg = PwStarkConfig(num_queries, pow_bits)
         self.width = width
         self.pre_width = 0
-        if preprocessed is not None:
+        if transition:
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            if interactions is None:
+                tables = (None, 0, None, 0, None, 0)
+            else:
+                it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
+                isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
+                ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
+                tables = (vp(it), len(it), vp(isp), len(isp), vp(ibc), len(ibc))
+            t, pw_, lh = preprocessed if preprocessed is not None else (None, 0, 0)
+            if t is not None:
+                assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
+            self._h = lib.pw_prover_create_transition(C.byref(cfg), width, pw_, lh, t.data_ptr() if t is not None else None, vp(bc), len(bc),
+                                                      vp(sp), len(sp), *tables)
+            self.pre_width = pw_
+        elif preprocessed is not None:
             t, pw_, lh = preprocessed
             assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
             vp = lambda a: a.ctypes.data_as(C.c_void_p)
@@ -532,6 +583,11 @@ class Prover:
                                                  isp.ctypes.data_as(C.c_void_p), len(isp), ibc.ctypes.data_as(C.c_void_p), len(ibc))
         if not self._h:
             raise RuntimeError("pw_prover_create failed")
+
+    @property
+    def row_flags(self) -> int:
+        """pw_prover_row_flags: bit 0 the constraints read a next-row operand, bit 1 a row selector (0: not row-aware)."""
+        return int(lib.pw_prover_row_flags(self._h))
 
     def preprocessed_root(self) -> np.ndarray:
         """pw_prover_preprocessed_root: the commitment to the fixed matrix (8 canonical words; the verifying key's part)."""

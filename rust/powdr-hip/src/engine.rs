@@ -61,15 +61,28 @@ impl HipEngine {
         let provers = programs
             .iter()
             .map(|p| {
+                // an AIR whose constraints read the next row or a row selector (`main.row_slice(1)`, `when_first_row()`,
+                // `when_transition()`) takes the row layout; the others keep the plain entry and its words
+                let rows = p.reads_rows();
                 let handle = unsafe {
-                    ffi::pw_prover_create_logup(
-                        &config, p.width, p.cons_bytecode.as_ptr(), p.cons_bytecode.len(), p.cons_spans.as_ptr(),
-                        p.cons_spans.len() / 2, p.interactions.as_ptr(), p.interactions.len() / 3, p.inter_spans.as_ptr(),
-                        p.inter_spans.len() / 2, p.inter_bytecode.as_ptr(), p.inter_bytecode.len(),
-                    )
+                    if rows {
+                        ffi::pw_prover_create_transition(
+                            &config, p.width, 0, 0, core::ptr::null(), p.cons_bytecode.as_ptr(), p.cons_bytecode.len(),
+                            p.cons_spans.as_ptr(), p.cons_spans.len() / 2, p.interactions.as_ptr(), p.interactions.len() / 3,
+                            p.inter_spans.as_ptr(), p.inter_spans.len() / 2, p.inter_bytecode.as_ptr(), p.inter_bytecode.len(),
+                        )
+                    } else {
+                        ffi::pw_prover_create_logup(
+                            &config, p.width, p.cons_bytecode.as_ptr(), p.cons_bytecode.len(), p.cons_spans.as_ptr(),
+                            p.cons_spans.len() / 2, p.interactions.as_ptr(), p.interactions.len() / 3, p.inter_spans.as_ptr(),
+                            p.inter_spans.len() / 2, p.inter_bytecode.as_ptr(), p.inter_bytecode.len(),
+                        )
+                    }
                 };
-                assert!(!handle.is_null(), "pw_prover_create_logup failed");
-                // the reference's degree bound 2 * DEFAULT_APP_LOG_BLOWUP + 1 = 3 (lib.rs:97-101)
+                // (the row-layout entry also refuses a constraint above degree 3 by Plonky3's rule: next-row columns and the
+                // first / last row selectors count 1, is_transition 0)
+                assert!(!handle.is_null(), "pw_prover_create_logup / _transition failed");
+                // the reference's degree bound 2 * DEFAULT_APP_LOG_BLOWUP + 1 = 3 (lib.rs:97-101), by that rule
                 assert!(unsafe { ffi::pw_prover_max_constraint_degree(handle) } <= 3, "constraint degree above the blow-up-2 bound");
                 HipAirProver { handle, width: p.width }
             })
@@ -142,8 +155,10 @@ impl HipEngine {
             })
             .collect();
         let mut total = [0u32; 4];
+        // (the row-layout verifier: exactly pw_verify_segment for segments without a row-aware AIR)
         let rc = unsafe {
-            ffi::pw_verify_segment(&self.config, descs.as_ptr(), descs.len(), 1, proof.words.as_ptr(), proof.words.len(), 1, total.as_mut_ptr())
+            ffi::pw_verify_segment_transition(&self.config, descs.as_ptr(), core::ptr::null(), descs.len(), 1, proof.words.as_ptr(),
+                                              proof.words.len(), 1, total.as_mut_ptr())
         };
         if rc == 0 { Ok(()) } else { Err(rc) }
     }
@@ -157,6 +172,28 @@ pub struct AirProgram {
     pub interactions: Vec<u32>,   // {bus, n_args, first span} triples
     pub inter_spans: Vec<u32>,    // {off, len} pairs, [mult, arg0, ...] per interaction
     pub inter_bytecode: Vec<u32>,
+}
+
+impl AirProgram {
+    /// a constraint operand at or beyond `width`: a next-row column or a row selector
+    pub fn reads_rows(&self) -> bool {
+        self.cons_spans.chunks(2).any(|sp| {
+            let code = &self.cons_bytecode[sp[0] as usize..(sp[0] + sp[1]) as usize];
+            let mut ip = 0;
+            while ip < code.len() {
+                let op = code[ip];
+                ip += 1;
+                if op == 0 || op == 1 {
+                    // PUSH_APC / PUSH_CONST and their operand
+                    if op == 0 && ip < code.len() && code[ip] >= self.width {
+                        return true;
+                    }
+                    ip += 1;
+                }
+            }
+            false
+        })
+    }
 }
 
 impl StarkEngine for HipEngine {

@@ -303,6 +303,14 @@ extern "C" {
                                          inter_bytecode: *const u32, inter_bytecode_len: usize) -> *mut PwProver;
     pub fn pw_prover_preprocessed_root(p: *const PwProver, root8: *mut u32) -> c_int;
     pub fn pw_prover_preprocessed_width(p: *const PwProver) -> u32;
+    /// next-row operands and row selectors in the constraints: operands W1..2W1 = the next row, 2W1..2W1+3 =
+    /// is_first_row / is_last_row / is_transition (W1 = width + pre_width); pre_width = 0: no fixed matrix; segment proofs only
+    pub fn pw_prover_create_transition(cfg: *const PwStarkConfig, width: u32, pre_width: u32, log_height: u32, d_pre: *const u32,
+                                       cons_bytecode: *const u32, bytecode_len: usize, cons_spans: *const u32, n_constraints: usize,
+                                       interactions: *const u32, n_interactions: usize, inter_spans: *const u32, n_inter_spans: usize,
+                                       inter_bytecode: *const u32, inter_bytecode_len: usize) -> *mut PwProver;
+    /// bit 0: reads a next-row operand, bit 1: reads a selector (0: not row-aware)
+    pub fn pw_prover_row_flags(p: *const PwProver) -> u32;
     pub fn pw_prover_prove(p: *mut PwProver, d_trace: *const u32, log_height: u32, proof_words: *mut *const u32,
                            n_words: *mut usize) -> c_int;
     /// The trace is handed over (the engine owns `common_main`): a streamed proof leaves the coefficient arrays in its place.
@@ -344,6 +352,9 @@ extern "C" {
     pub fn pw_verify_segment_preprocessed(cfg: *const PwStarkConfig, airs: *const PwAirDescription, pre: *const PwAirPreprocessed,
                                           n_airs: usize, logup: c_int, proof_words: *const u32, n_words: usize, check_balance: c_int,
                                           total_sum4: *mut u32) -> c_int;
+    pub fn pw_verify_segment_transition(cfg: *const PwStarkConfig, airs: *const PwAirDescription, pre: *const PwAirPreprocessed,
+                                        n_airs: usize, logup: c_int, proof_words: *const u32, n_words: usize, check_balance: c_int,
+                                        total_sum4: *mut u32) -> c_int;
     pub fn pw_prove_airs(airs: *const PwSegmentAir, n_airs: usize, shared_bus_seed: c_int, n_workers: c_uint,
                          proofs: *mut *const u32, n_words: *mut usize, bus_seed8: *mut u32) -> c_int;
     pub fn pw_verify_airs(cfg: *const PwStarkConfig, airs: *const PwAirDescription, n_airs: usize,
