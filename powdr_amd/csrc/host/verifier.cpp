@@ -94,6 +94,65 @@ struct Interactions {
     size_t bc_len;
 };
 
+// sum_k X^k * o[k]: the coordinates of an opened extension-valued column are the basis coefficients
+Ext combine(const Ext* o) {
+    Ext r = bb::ext_zero();
+    for (int k = 0; k < 4; ++k) {
+        Ext basis = bb::ext_zero();
+        basis.c[k] = bb::R_MOD_P;
+        r = bb::ext_add(r, bb::ext_mul(basis, o[k]));
+    }
+    return r;
+}
+
+// The LogUp terms of one AIR's constraint identity, folded into acc with alpha: per group q_g * prod d_i = sum_i m_i prod_{j != i} d_j
+// on every row (i.e. q_g = sum_i m_i / d_i); phi is the running sum of sum_g q_g and ends at S. vals: the `width` opened values the
+// interaction programs read; perm / perm_next: the permutation matrix opened at zeta / at g zeta. false: a malformed program.
+bool logup_identity(const Interactions& lg, const std::vector<uint32_t>& gstarts, uint32_t max_args, const Ext* vals, uint32_t width, const Ext* perm,
+                    const Ext* perm_next, Ext al, Ext bl, Ext alpha, Ext zeta, Ext zh, uint32_t g_inv, Ext S, Ext& acc) {
+    const size_t n_g = gstarts.size() - 1;
+    std::vector<Ext> blpow(max_args + 2);
+    { Ext b = bb::ext_one(); for (auto& x : blpow) { x = b; b = bb::ext_mul(b, bl); } }
+    Ext sumq = bb::ext_zero(), sumq_next = bb::ext_zero();
+    for (size_t g = 0; g < n_g; ++g) {
+        Ext num = bb::ext_zero(), den = bb::ext_one();
+        for (size_t i = gstarts[g]; i < gstarts[g + 1]; ++i) {
+            const uint32_t bus = lg.inter[3 * i], na = lg.inter[3 * i + 1];
+            const uint32_t* sp = lg.spans + 2 * (size_t)lg.inter[3 * i + 2];
+            Ext d = bb::ext_add(al, bb::ext_from_base(bb::to_monty(bus % bb::P))), m, a;
+            for (uint32_t j = 0; j < na; ++j) {
+                if (!eval_ext(lg.bc + sp[2 + 2 * j], sp[3 + 2 * j], vals, width, a)) return false;
+                d = bb::ext_add(d, bb::ext_mul(blpow[j + 1], a));
+            }
+            if (!eval_ext(lg.bc + sp[0], sp[1], vals, width, m)) return false;
+            num = bb::ext_add(bb::ext_mul(num, d), bb::ext_mul(den, m));
+            den = bb::ext_mul(den, d);
+        }
+        const Ext qi = combine(perm + 4 * g), qn = combine(perm_next + 4 * g);
+        sumq = bb::ext_add(sumq, qi);
+        sumq_next = bb::ext_add(sumq_next, qn);
+        acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_sub(bb::ext_mul(qi, den), num));
+    }
+    const Ext phi = combine(perm + 4 * n_g), phin = combine(perm_next + 4 * n_g);
+    const Ext is_trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
+    const Ext is_first = bb::ext_mul(zh, bb::ext_inv(bb::ext_sub(zeta, bb::ext_one())));
+    const Ext is_last = bb::ext_mul(zh, bb::ext_inv(is_trans));
+    acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_first, bb::ext_sub(phi, sumq)));
+    acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_trans, bb::ext_sub(bb::ext_sub(phin, phi), sumq_next)));
+    acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_last, bb::ext_sub(phi, S)));
+    return true;
+}
+
+// a Merkle path of `depth` siblings read from the proof (get_digest), from `leaf` at index idx up to `root`
+template <class GetDigest>
+bool check_path(GetDigest& get_digest, Digest leaf, size_t idx, int depth, const Digest& root) {
+    for (int l = 0; l < depth; ++l) {
+        const Digest sib = get_digest();
+        leaf = ((idx >> l) & 1) ? compress(sib, leaf) : compress(leaf, sib);
+    }
+    return same(leaf, root);
+}
+
 // Returns 0 if the proof is valid, a positive code naming the first failed check otherwise:
 // 1 header, 2 constraint identity at zeta, 3 proof of work, 4 query index, 5/6 trace/quotient opening,
 // 7 FRI layer opening, 8 final polynomial, 9 trailing words, 10 truncated / malformed, 11 permutation opening, 12 bus seed.
@@ -105,13 +164,7 @@ int verify_impl(const PwStarkConfig* cfg, uint32_t width, uint32_t log_h, const 
     uint32_t max_args = 0;
     std::vector<uint32_t> gstarts{0};
     if (lg) {
-        for (size_t i = 0; i < lg->n; ++i) {
-            const uint32_t na = lg->inter[3 * i + 1], first = lg->inter[3 * i + 2];
-            if ((size_t)first + 1 + na > lg->n_spans) return 10;
-            for (uint32_t k = 0; k <= na; ++k)
-                if ((size_t)lg->spans[2 * (first + k)] + lg->spans[2 * (first + k) + 1] > lg->bc_len) return 10;
-            if (na > max_args) max_args = na;
-        }
+        if (!pw::interaction_table_ok(lg->inter, lg->n, lg->spans, lg->n_spans, lg->bc_len, &max_args)) return 10;
         gstarts = pw::logup_group_starts(lg->inter, lg->n, lg->spans, lg->bc);
     }
     const size_t n_g = gstarts.size() - 1;
@@ -185,50 +238,9 @@ int verify_impl(const PwStarkConfig* cfg, uint32_t width, uint32_t log_h, const 
     }
     const Ext zH = bb::ext_pow(zeta, H);
     const Ext zh = bb::ext_sub(zH, bb::ext_one());
-    // sum_k X^k * o_k: the coordinates of an opened extension-valued column are the basis coefficients
-    auto combine = [&](size_t base) {
-        Ext r = bb::ext_zero();
-        for (int k = 0; k < 4; ++k) {
-            Ext basis = bb::ext_zero();
-            basis.c[k] = bb::R_MOD_P;
-            r = bb::ext_add(r, bb::ext_mul(basis, opened[base + k]));
-        }
-        return r;
-    };
-    if (lg) {
-        // LogUp: per group q_g * prod d_i = sum_i m_i prod_{j != i} d_j on every row (i.e. q_g = sum_i m_i / d_i);
-        // phi is the running sum of sum_g q_g and ends at S
-        std::vector<Ext> blpow(max_args + 2);
-        { Ext b = bb::ext_one(); for (auto& x : blpow) { x = b; b = bb::ext_mul(b, bl); } }
-        Ext sumq = bb::ext_zero(), sumq_next = bb::ext_zero();
-        for (size_t g = 0; g < n_g; ++g) {
-            Ext num = bb::ext_zero(), den = bb::ext_one();
-            for (size_t i = gstarts[g]; i < gstarts[g + 1]; ++i) {
-                const uint32_t bus = lg->inter[3 * i], na = lg->inter[3 * i + 1];
-                const uint32_t* sp = lg->spans + 2 * (size_t)lg->inter[3 * i + 2];
-                Ext d = bb::ext_add(al, bb::ext_from_base(bb::to_monty(bus % bb::P))), m, a;
-                for (uint32_t j = 0; j < na; ++j) {
-                    if (!eval_ext(lg->bc + sp[2 + 2 * j], sp[3 + 2 * j], opened.data(), width, a)) return 10;
-                    d = bb::ext_add(d, bb::ext_mul(blpow[j + 1], a));
-                }
-                if (!eval_ext(lg->bc + sp[0], sp[1], opened.data(), width, m)) return 10;
-                num = bb::ext_add(bb::ext_mul(num, d), bb::ext_mul(den, m));
-                den = bb::ext_mul(den, d);
-            }
-            const Ext qi = combine(width + 4 * g), qn = combine(K1 + 4 * g);
-            sumq = bb::ext_add(sumq, qi);
-            sumq_next = bb::ext_add(sumq_next, qn);
-            acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_sub(bb::ext_mul(qi, den), num));
-        }
-        const Ext phi = combine(width + 4 * n_g), phin = combine(K1 + 4 * n_g);
-        const Ext is_trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
-        const Ext is_first = bb::ext_mul(zh, bb::ext_inv(bb::ext_sub(zeta, bb::ext_one())));
-        const Ext is_last = bb::ext_mul(zh, bb::ext_inv(is_trans));
-        acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_first, bb::ext_sub(phi, sumq)));
-        acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_trans, bb::ext_sub(bb::ext_sub(phin, phi), sumq_next)));
-        acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_last, bb::ext_sub(phi, S)));
-    }
-    const Ext qlo = combine(width + Wp), qhi = combine(width + Wp + 4);
+    if (lg && !logup_identity(*lg, gstarts, max_args, opened.data(), width, &opened[width], &opened[K1], al, bl, alpha, zeta, zh, g_inv, S, acc))
+        return 10;
+    const Ext qlo = combine(&opened[width + Wp]), qhi = combine(&opened[width + Wp + 4]);
     if (!bb::ext_eq(acc, bb::ext_mul(zh, bb::ext_add(qlo, bb::ext_mul(zH, qhi))))) return 2;
 
     const Ext gamma = ch.sample_ext();
@@ -254,13 +266,6 @@ int verify_impl(const PwStarkConfig* cfg, uint32_t width, uint32_t log_h, const 
     ch.observe(bb::to_monty(witness % bb::P));
     if (cfg->pow_bits && ch.sample_bits((int)cfg->pow_bits) != 0) return 3;
 
-    auto check_path = [&](Digest leaf, size_t idx, int depth, const Digest& root) {
-        for (int l = 0; l < depth; ++l) {
-            Digest sib = get_digest();
-            leaf = ((idx >> l) & 1) ? compress(sib, leaf) : compress(leaf, sib);
-        }
-        return same(leaf, root);
-    };
     const uint32_t shift0 = bb::to_monty(pw::field::kCosetShift);
     const uint32_t inv2 = bb::inv(bb::to_monty(2));
     std::vector<uint32_t> trow(width), prow(Wp), qrow(8);
@@ -269,13 +274,13 @@ int verify_impl(const PwStarkConfig* cfg, uint32_t width, uint32_t log_h, const 
         if (get() != idx) return short_read ? 10 : 4;
         for (auto& w : trow) w = get_m();
         if (short_read) return 10;
-        if (!check_path(hash_row(trow.data(), width), idx, logN, t_root)) return short_read ? 10 : 5;
+        if (!check_path(get_digest, hash_row(trow.data(), width), idx, logN, t_root)) return short_read ? 10 : 5;
         if (lg) {
             for (auto& w : prow) w = get_m();
-            if (!check_path(hash_row(prow.data(), Wp), idx, logN, p_root)) return short_read ? 10 : 11;
+            if (!check_path(get_digest, hash_row(prow.data(), Wp), idx, logN, p_root)) return short_read ? 10 : 11;
         }
         for (auto& w : qrow) w = get_m();
-        if (!check_path(hash_row(qrow.data(), 8), idx, logN, q_root)) return short_read ? 10 : 6;
+        if (!check_path(get_digest, hash_row(qrow.data(), 8), idx, logN, q_root)) return short_read ? 10 : 6;
         const uint32_t x = bb::mul(shift0, bb::pow_u32(pw::field::root_of_unity(logN), (uint32_t)idx));
         Ext a = bb::ext_zero(), a2 = bb::ext_zero();
         for (size_t k = 0; k < width; ++k) a = bb::ext_add(a, bb::ext_scale(gpow[k], trow[k]));
@@ -294,7 +299,7 @@ int verify_impl(const PwStarkConfig* cfg, uint32_t width, uint32_t log_h, const 
             uint32_t row[8];
             memcpy(row, lo.c, 16);
             memcpy(row + 4, hi.c, 16);
-            if (!check_path(hash_row(row, 8), p & (half - 1), logN - 1 - (int)l, fri_roots[l])) return short_read ? 10 : 7;
+            if (!check_path(get_digest, hash_row(row, 8), p & (half - 1), logN - 1 - (int)l, fri_roots[l])) return short_read ? 10 : 7;
             const uint32_t xi = bb::mul(shift, bb::pow_u32(pw::field::root_of_unity(logN - (int)l), (uint32_t)(p & (half - 1))));
             const Ext s = bb::ext_scale(bb::ext_add(lo, hi), inv2);
             const Ext d = bb::ext_scale(bb::ext_sub(lo, hi), bb::mul(inv2, bb::inv(xi)));
@@ -378,13 +383,7 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         }
         s.Wg = (s.rf & pw::kRowsNext) ? s.W1 : 0;
         if (lg) {
-            for (size_t i = 0; i < d.n_interactions; ++i) {
-                const uint32_t na = d.interactions[3 * i + 1], first = d.interactions[3 * i + 2];
-                if ((size_t)first + 1 + na > d.n_inter_spans) return 15;
-                for (uint32_t k = 0; k <= na; ++k)
-                    if ((size_t)d.inter_spans[2 * (first + k)] + d.inter_spans[2 * (first + k) + 1] > d.inter_bytecode_len) return 15;
-                if (na > s.max_args) s.max_args = na;
-            }
+            if (!pw::interaction_table_ok(d.interactions, d.n_interactions, d.inter_spans, d.n_inter_spans, d.inter_bytecode_len, &s.max_args)) return 15;
             s.gstarts = pw::logup_group_starts(d.interactions, d.n_interactions, d.inter_spans, d.inter_bytecode);
             if (s.gstarts.empty()) s.gstarts.push_back(0);
             s.n_g = s.gstarts.size() - 1;
@@ -455,15 +454,6 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         const size_t K1 = (size_t)s.W1 + s.Wp + 8;
         const uint32_t g_h = pw::field::root_of_unity((int)s.log_h), g_inv = bb::inv(g_h);
         gzeta[a] = bb::ext_scale(zeta, g_h);
-        auto combine = [&](size_t base) {
-            Ext r = bb::ext_zero();
-            for (int k = 0; k < 4; ++k) {
-                Ext basis = bb::ext_zero();
-                basis.c[k] = bb::R_MOD_P;
-                r = bb::ext_add(r, bb::ext_mul(basis, o[base + k]));
-            }
-            return r;
-        };
         const Ext zH = bb::ext_pow(zeta, s.H);
         const Ext zh = bb::ext_sub(zH, bb::ext_one());
         // the values the constraint operands name: the W1 openings at zeta; with the row layout also those at g zeta (zero when not
@@ -489,37 +479,10 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             acc = bb::ext_add(bb::ext_mul(acc, alpha), v);
         }
         if (lg) {
-            std::vector<Ext> blpow(s.max_args + 2);
-            { Ext b = bb::ext_one(); for (auto& x : blpow) { x = b; b = bb::ext_mul(b, bl); } }
-            Ext sumq = bb::ext_zero(), sumq_next = bb::ext_zero();
-            for (size_t g = 0; g < s.n_g; ++g) {
-                Ext num = bb::ext_zero(), den = bb::ext_one();
-                for (size_t i = s.gstarts[g]; i < s.gstarts[g + 1]; ++i) {
-                    const uint32_t bus = d.interactions[3 * i], na = d.interactions[3 * i + 1];
-                    const uint32_t* sp = d.inter_spans + 2 * (size_t)d.interactions[3 * i + 2];
-                    Ext dd = bb::ext_add(al, bb::ext_from_base(bb::to_monty(bus % bb::P))), m, arg;
-                    for (uint32_t j = 0; j < na; ++j) {
-                        if (!eval_ext(d.inter_bytecode + sp[2 + 2 * j], sp[3 + 2 * j], o, s.W1, arg)) return 15;
-                        dd = bb::ext_add(dd, bb::ext_mul(blpow[j + 1], arg));
-                    }
-                    if (!eval_ext(d.inter_bytecode + sp[0], sp[1], o, s.W1, m)) return 15;
-                    num = bb::ext_add(bb::ext_mul(num, dd), bb::ext_mul(den, m));
-                    den = bb::ext_mul(den, dd);
-                }
-                const Ext qi = combine(s.W1 + 4 * g), qn = combine(K1 + 4 * g);
-                sumq = bb::ext_add(sumq, qi);
-                sumq_next = bb::ext_add(sumq_next, qn);
-                acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_sub(bb::ext_mul(qi, den), num));
-            }
-            const Ext phi = combine(s.W1 + 4 * s.n_g), phin = combine(K1 + 4 * s.n_g);
-            const Ext is_trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
-            const Ext is_first = bb::ext_mul(zh, bb::ext_inv(bb::ext_sub(zeta, bb::ext_one())));
-            const Ext is_last = bb::ext_mul(zh, bb::ext_inv(is_trans));
-            acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_first, bb::ext_sub(phi, sumq)));
-            acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_trans, bb::ext_sub(bb::ext_sub(phin, phi), sumq_next)));
-            acc = bb::ext_add(bb::ext_mul(acc, alpha), bb::ext_mul(is_last, bb::ext_sub(phi, S[a])));
+            const Interactions it{d.interactions, d.n_interactions, d.inter_spans, d.n_inter_spans, d.inter_bytecode, d.inter_bytecode_len};
+            if (!logup_identity(it, s.gstarts, s.max_args, o, s.W1, o + s.W1, o + K1, al, bl, alpha, zeta, zh, g_inv, S[a], acc)) return 15;
         }
-        const Ext qlo = combine(s.W1 + s.Wp), qhi = combine(s.W1 + s.Wp + 4);
+        const Ext qlo = combine(o + s.W1 + s.Wp), qhi = combine(o + s.W1 + s.Wp + 4);
         if (!bb::ext_eq(acc, bb::ext_mul(zh, bb::ext_add(qlo, bb::ext_mul(zH, qhi))))) return (int)((a + 1) << 8) | 2;
     }
 
@@ -566,13 +529,6 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             if (any) cur = compress(cur, inj);
         }
         return same(cur, root);
-    };
-    auto check_path = [&](Digest leaf, size_t idx, int depth, const Digest& root) {
-        for (int l = 0; l < depth; ++l) {
-            const Digest sib = get_digest();
-            leaf = ((idx >> l) & 1) ? compress(sib, leaf) : compress(leaf, sib);
-        }
-        return same(leaf, root);
     };
     const uint32_t shift0 = bb::to_monty(pw::field::kCosetShift);
     const uint32_t inv2 = bb::inv(bb::to_monty(2));
@@ -640,7 +596,7 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             uint32_t row[8];
             memcpy(row, lo.c, 16);
             memcpy(row + 4, hi.c, 16);
-            if (!check_path(hash_row(row, 8), p & (half - 1), L - 1 - l, fri_roots[l])) return short_read ? 10 : 7;
+            if (!check_path(get_digest, hash_row(row, 8), p & (half - 1), L - 1 - l, fri_roots[l])) return short_read ? 10 : 7;
             // unshifted subgroup: x_i = w_l^i
             const uint32_t xi = bb::pow_u32(pw::field::root_of_unity(L - l), (uint32_t)(p & (half - 1)));
             const Ext s2 = bb::ext_scale(bb::ext_add(lo, hi), inv2);
@@ -685,12 +641,7 @@ extern "C" int pw_verify_segment_transition(const PwStarkConfig* cfg, const PwAi
 extern "C" size_t pw_logup_group_starts(const uint32_t* interactions, size_t n_interactions, const uint32_t* inter_spans,
                                         size_t n_inter_spans, const uint32_t* inter_bytecode, size_t inter_bytecode_len,
                                         uint32_t* out, size_t cap) {
-    for (size_t i = 0; i < n_interactions; ++i) {
-        const uint32_t na = interactions[3 * i + 1], first = interactions[3 * i + 2];
-        if ((size_t)first + 1 + na > n_inter_spans) return 0;
-        for (uint32_t k = 0; k <= na; ++k)
-            if ((size_t)inter_spans[2 * (first + k)] + inter_spans[2 * (first + k) + 1] > inter_bytecode_len) return 0;
-    }
+    if (!pw::interaction_table_ok(interactions, n_interactions, inter_spans, n_inter_spans, inter_bytecode_len)) return 0;
     const std::vector<uint32_t> g = pw::logup_group_starts(interactions, n_interactions, inter_spans, inter_bytecode);
     for (size_t i = 0; i < g.size() && i < cap; ++i) out[i] = g[i];
     return g.size();

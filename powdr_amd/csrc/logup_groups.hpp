@@ -78,6 +78,19 @@ inline uint32_t postfix_row_flags(const uint32_t* bc, uint32_t len, uint32_t w1)
     return f;
 }
 
+// An interaction table as it arrives from outside — `inter` = n x {bus, n_args, first span}, spans {off, len} laid out [mult, arg0, ...] —
+// stays inside its span list and its bytecode; *max_args (if asked for) = the most arguments of one interaction
+inline bool interaction_table_ok(const uint32_t* inter, size_t n, const uint32_t* spans, size_t n_spans, size_t bc_len, uint32_t* max_args = nullptr) {
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t na = inter[3 * i + 1], first = inter[3 * i + 2];
+        if ((size_t)first + 1 + na > n_spans) return false;
+        for (uint32_t k = 0; k <= na; ++k)
+            if ((size_t)spans[2 * (first + k)] + spans[2 * (first + k) + 1] > bc_len) return false;
+        if (max_args && na > *max_args) *max_args = na;
+    }
+    return true;
+}
+
 // Group boundaries, n_groups + 1 entries ({0} for no interactions). An interaction joins the current group while the
 // group's constraint  q * prod d_i - sum_i m_i prod_{j != i} d_j  keeps degree <= 3 (what a blow-up-2 quotient carries):
 //   1 + sum deg d_j <= 3  and  deg m_j + sum_{k != j} deg d_k <= 3 for every member.

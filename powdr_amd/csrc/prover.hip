@@ -6,8 +6,7 @@
 // 32-byte roots, the W+8 opened values and the query answers (a few hundred KB), which is
 // what it needs to run the transcript.
 #include "prover_state.hpp"
-#include "prover_stream.hpp"
-#include "logup_groups.hpp"
+#include "prover_stages.hpp"
 #include "xbc_compile.hpp"
 
 #include <atomic>
@@ -165,15 +164,13 @@ static PwProver* create_prover_logup(const PwStarkConfig* cfg, uint32_t width, c
     std::vector<pw::SmallForm> forms;  // one per span; the few that are no small forms (sums of many flags, ...) stay with the interpreter
     size_t not_small = 0;
     xbc::Compiler cc;
-    bool ok = true;
+    bool ok = pw::interaction_table_ok(inter, n_inter, ispans, n_ispans, ibc_len);
     for (size_t i = 0; i < n_inter && ok; ++i) {
         const uint32_t bus = inter[3 * i], na = inter[3 * i + 1], first = inter[3 * i + 2];
-        if ((size_t)first + 1 + na > n_ispans) { ok = false; break; }
         li[i] = {bb::to_monty(bus % bb::P), na, (uint32_t)(xspans.size() / 2)};
         if (na > p->max_args) p->max_args = na;
         for (uint32_t k = 0; k <= na && ok; ++k) {
             const uint32_t off = ispans[2 * (first + k)], len = ispans[2 * (first + k) + 1];
-            if ((size_t)off + len > ibc_len) { ok = false; break; }
             if (pw::postfix_degree(ibc + off, len) == pw::kBadDegree || !pw::postfix_columns_below(ibc + off, len, width)) { ok = false; break; }
             const uint32_t o = (uint32_t)(code.size() / 2);
             if (!cc.compile(ibc + off, len, code)) { ok = false; break; }
@@ -393,81 +390,26 @@ namespace {
 // The DEEP numerator sum_k gamma^k P_k is a polynomial: from 2^16 rows on it is combined on the UN-extended matrices (half the bytes
 // the LDE holds) and extended as 4 + 4 columns instead of being accumulated over the LDE of every column (deep_kernel); shorter traces
 // keep the one-kernel form (the extra launches cost more than the bytes they save).
-// (kDeepComboMinLogHeight: prover_state.hpp — the segment prover follows the same rule)
-
-struct BufferPlan {
-    size_t coef = 0, lde = 0, digests = 0, perm = 0, plde = 0, q = 0, qpart = 0, qcoef = 0, qlde = 0, ext_arena = 0, misc = 0,
-           tcoef = 0, fscale = 0, gbuf = 0;
-    size_t commit_total() const { return coef + lde + digests + tcoef + fscale; }
-    size_t total() const { return commit_total() + perm + plde + q + qpart + qcoef + qlde + ext_arena + misc + gbuf; }
-};
+// (kDeepComboMinLogHeight: prover_state.hpp; the dispatch is prover_stages.hpp deep_stage, the segment prover's as well)
 
 // consume: the caller hands its trace over (pw_prover_prove_consuming) — a streamed proof then keeps the trace's coefficient arrays IN
-// the caller's buffer (no tcoef); with LogUp the permutation matrix is computed into `lde` first (its evaluations are only needed until
-// its coefficients exist), while `perm` lends its room to the trace's coefficients until the trace itself is dead.
+// the caller's buffer (no tcoef; what that does to `perm` and `lde`: plan_stage_buffers). To the stage buffers of the AIR the one-AIR
+// proof adds its own trees, the trace's coefficient arrays, and in ext_arena / misc everything the proof keeps.
 void plan_buffers(const PwProver* p, uint32_t log_h, int b, CommitLayout& L, BufferPlan& B, bool consume = false) {
-    L.H = (size_t)1 << log_h;
-    L.N = 2 * L.H;
-    L.b = b;
-    L.m = L.N >> b;
-    L.tree_words = merkle_words(L.N);
-    L.fri_words = 0;
-    for (uint32_t l = 0; l < log_h; ++l) L.fri_words += merkle_words((L.N >> l) / 2);
-    L.n_trees = p->logup ? 3 : 2;  // trace | quotient | (perm) | FRI
-    const size_t H = L.H, N = L.N;
-    const int logN = (int)log_h + 1;
+    const AirShape s = air_shape(p, log_h, p->logup);
     const bool lg = p->logup;
-    const uint32_t W = p->width, nc = p->n_constraints;
-    const uint32_t n_g = lg ? p->n_groups : 0;
-    const uint32_t Wp = lg ? 4 * (n_g + 1) : 0;
-    const uint32_t K = W + 2 * Wp + 8;
-    const uint32_t M = nc + (lg ? n_g + 3 : 0);
-    // coefficients exist only per column panel (1 GB by default; larger panels = fewer, larger launches): iNTT -> panel ->
-    // coset NTT into the resident LDE. Streamed: the panel serves the eight phi / row-sum columns only.
-    const size_t widest = b ? 8 : (lg ? std::max<size_t>(W, Wp) : W);
-    L.panel_cols = lde_panel_cols(H, widest);
-    B.coef = L.panel_cols * H * 4;
-    // streamed: `lde` holds one sub-coset. The commitments and the query rows take the two matrices one after the other (max(W, Wp)
-    // columns); the quotient needs main AND permutation columns of the same rows — all of them for the interpreter, but a unit of the
-    // specialised LogUp kernels reads only the columns of its own groups: the main block + one unit's panel. That is what lets
-    // configs[2] run with 4 sub-cosets instead of 8 (half the coefficient re-reads, the transforms' first stage group is bound by them).
-    L.perm_panels = b && lg && p->jit.state == 1 && !getenv("POWDR_STREAM_NO_PANELS");
-    if (!b) B.lde = (size_t)W * N * 4;
-    else if (L.perm_panels) B.lde = std::max<size_t>(std::max(W, Wp), (size_t)W + quotient_max_unit_perm_cols(p)) * L.m * 4;
-    else B.lde = (size_t)(W + Wp) * L.m * 4;
+    plan_stage_buffers(p, s, AirMode{b, b && consume}, L, B);
+    L.tree_words = merkle_words(s.N);
+    L.fri_words = FriLayout(s.logN).fri_words;
+    L.n_trees = lg ? 3 : 2;  // trace | quotient | (perm) | FRI
     B.digests = (L.n_trees * L.tree_words + L.fri_words) * 4;
-    if (b) { B.tcoef = (size_t)W * H * 4; B.fscale = (size_t)1 << 15; }
-    if (b || log_h >= kDeepComboMinLogHeight) B.gbuf = (size_t)24 * H * 4;
-    if (lg) {  // + the uncommitted per-row-sum columns (kJitExtraPermCols; the streamed path keeps them on every path)
-        B.perm = (size_t)(Wp + kJitExtraPermCols) * H * 4;
-        B.plde = b ? (size_t)8 * N * 4 : (size_t)(Wp + kJitExtraPermCols) * N * 4;
-    }
-    B.q = 4 * N * 4;
-    const size_t q_rows = b ? L.m : N;
-    if (!lg) {
-        const uint32_t chunks = quotient_chunks(q_rows, nc);
-        if (chunks > 1) B.qpart = (size_t)chunks * 4 * q_rows * 4;
-    }
-    if (b) B.qpart += 4 * L.m * 4;  // the interpreter kernels' unscaled sums of one sub-coset
-    B.qpart = std::max(B.qpart, jit_part_bytes(p, H, q_rows));
-    if (b && consume) {
-        B.tcoef = 0;
-        if (lg) {
-            B.perm = std::max(B.perm, (size_t)W * H * 4);
-            B.lde = std::max(B.lde, (size_t)(Wp + kJitExtraPermCols) * H * 4);
-        }
-    }
-    B.qcoef = 8 * H * 4;
-    B.qlde = 8 * N * 4;
+    if (b) { B.tcoef = consume ? 0 : (size_t)s.W * s.H * 4; B.fscale = (size_t)1 << 15; }
     // ext arena: FRI layer vectors v_0 (N) .. v_log_h (2): 2N ext; weights (H); LogUp: second weights, row sums
-    B.ext_arena = (2 * N + (lg ? 3 : 1) * H + H / 4096 + 32) * sizeof(bb::Ext);
-    const uint32_t n_chunks = div_up(H, 8192);
-    const uint32_t dot_cols = std::max({W, Wp, 8u});
-    const size_t misc_ext = 2 * (size_t)dot_cols * n_chunks + K + K + M + p->max_args + 64;  // ext_dot_columns2 keeps two sets of partial sums
+    B.ext_arena = (2 * s.N + (lg ? 3 : 1) * s.H + s.H / 4096 + 32) * sizeof(bb::Ext);
+    const size_t misc_ext = dot_scratch_words(s) + 2 * (size_t)s.K + s.M + p->max_args + 64;  // scratch | opened | gamma powers | alpha, beta powers
     const uint32_t nq = p->cfg.num_queries;
-    const size_t path_records = (size_t)nq * (L.n_trees * (size_t)logN + (size_t)log_h * logN) + 16;
-    B.misc = misc_ext * sizeof(bb::Ext) + (size_t)nq * 8 + (size_t)nq * (W + Wp + 8) * 4 + path_records * (8 + 32) +
-             (size_t)nq * log_h * (8 + 16) + 4096;
+    const size_t path_records = (size_t)nq * (L.n_trees * (size_t)s.logN + (size_t)log_h * s.logN) + 16;
+    B.misc = misc_ext * sizeof(bb::Ext) + (size_t)nq * 8 + (size_t)nq * s.K1 * 4 + path_records * (8 + 32) + (size_t)nq * log_h * (8 + 16) + 4096;
 }
 
 }  // namespace
@@ -525,32 +467,22 @@ int stream_log_blocks(const PwProver* p, uint32_t log_h, bool consume = false) {
     return -1;
 }
 
-int apply_commit_buffers(PwProver* p, const BufferPlan& B) {
+int apply_buffers(PwProver* p, const BufferPlan& B) {
     // release before growing: stream_log_blocks counted a held tcoef as available (a consuming proof after a plain streamed one)
     if (!B.tcoef) p->tcoef.release();
-    TRY(p->coef.ensure(B.coef));
-    TRY(p->lde.ensure(B.lde));
-    TRY(p->digests.ensure(B.digests));
-    if (B.tcoef) TRY(p->tcoef.ensure(B.tcoef));
-    if (B.fscale) TRY(p->fscale.ensure(B.fscale));
-    return 0;
+    return apply_plan(p, B);
 }
 
 // Buffers of the trace commitment, sized as pw_prover_prove needs them (so that a later prove does not reallocate)
 int ensure_commit_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L) {
     BufferPlan B;
     plan_buffers(p, log_h, b, L, B);
-    return apply_commit_buffers(p, B);
-}
-
-streamed::Ctx stream_ctx(PwProver* p, const CommitLayout& L, uint32_t log_h) {
-    const uint32_t Wp = p->logup ? 4 * (p->n_groups + 1) : 0;
-    return streamed::Ctx{p, log_h, L.b, L.perm_panels, L.H, L.N, L.m, p->width, Wp};
+    return apply_buffers(p, B.commit_part());
 }
 
 // streamed commitment of a matrix given by its coefficient arrays: every sub-coset's rows are hashed into their leaves
 int commit_coefficients(PwProver* p, const CommitLayout& L, uint32_t log_h, const uint32_t* coef, uint32_t cols, uint32_t* d_tree) {
-    TRY(streamed::leaf_hashes(stream_ctx(p, L, log_h), coef, cols, d_tree));
+    TRY(streamed::leaf_hashes(stream_ctx(p, air_shape(p, log_h, p->logup), L), coef, cols, d_tree));
     return merkle_build_levels(d_tree, L.N);
 }
 
@@ -577,16 +509,7 @@ int commit_trace(PwProver* p, const CommitLayout& L, const uint32_t* d_trace, ui
 int ensure_prove_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bool consume = false) {
     BufferPlan B;
     plan_buffers(p, log_h, b, L, B, consume);
-    TRY(apply_commit_buffers(p, B));
-    if (B.perm) { TRY(p->perm.ensure(B.perm)); TRY(p->plde.ensure(B.plde)); }
-    TRY(p->q.ensure(B.q));
-    if (B.qpart) TRY(p->qpart.ensure(B.qpart));
-    TRY(p->qcoef.ensure(B.qcoef));
-    TRY(p->qlde.ensure(B.qlde));
-    TRY(p->ext_arena.ensure(B.ext_arena));
-    TRY(p->misc.ensure(B.misc));
-    if (B.gbuf) TRY(p->gbuf.ensure(B.gbuf));
-    return 0;
+    return apply_buffers(p, B);
 }
 }  // namespace
 
@@ -709,20 +632,14 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     // a handed-over trace becomes a coefficient array that is read 2 / 4 words at a time (fold loads, the DEEP combination)
     if (consume && ((uintptr_t)d_trace & 15)) return (int)hipErrorInvalidValue;
     (void)hipGetLastError();
-    const uint32_t W = p->width, nc = p->n_constraints;
-    const size_t H = (size_t)1 << log_h, N = 2 * H;
-    const int logN = (int)log_h + 1;
+    const AirShape s = air_shape(p, log_h, p->logup);
+    const uint32_t W = s.W, nc = s.nc, n_int = s.n_int, Wp = s.Wp, K1 = s.K1, K = s.K, M = s.M;
+    const size_t H = s.H, N = s.N;
+    const int logN = s.logN;
     const bool lg = p->logup;
-    const uint32_t n_int = lg ? p->n_inter : 0;
-    const uint32_t n_g = lg ? p->n_groups : 0;
-    const uint32_t Wp = lg ? 4 * (n_g + 1) : 0;     // permutation matrix: q_g coordinates per group, then phi
-    const uint32_t K1 = W + Wp + 8;                  // polynomials opened at zeta: main | perm | quotient
-    const uint32_t K = K1 + Wp;                      // + perm opened at g*zeta
-    const uint32_t M = nc + (lg ? n_g + 3 : 0);      // folded constraints
     hipStream_t st = stream();
     TRY(poseidon2_upload_params());
     (void)specialise_provers(&p, 1, &log_h, false);  // run-time specialised expression kernels, compiled once per prover (prover_jit.hip)
-    const bool jit = specialised(p);
 
     // ---- buffers --------------------------------------------------------------------------
     // digest arena: trace tree | quotient tree | (perm tree) | FRI trees
@@ -745,12 +662,11 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         rc_buf = ensure_prove_buffers(p, log_h, sb, L, false);
     }
     if (rc_buf) return rc_buf;
-    const bool eat = consume && sb > 0;  // the trace is overwritten by its coefficient arrays
+    const AirMode mode{sb, consume && sb > 0};
+    const bool eat = mode.eat;  // the trace is overwritten by its coefficient arrays
     const size_t tree_words = L.tree_words, n_trees = L.n_trees;
     // streamed: the trace's coefficient arrays — in tcoef, or (eat) in the caller's buffer, from the moment nothing reads the trace any more
     uint32_t* d_tcoef = eat ? const_cast<uint32_t*>(d_trace) : p->tcoef.as<uint32_t>();
-    const uint32_t n_chunks = div_up(H, 8192);
-    const uint32_t dot_cols = std::max({W, Wp, 8u});  // widest matrix ext_dot_columns sees (the quotient has 8 columns)
     const uint32_t nq = p->cfg.num_queries;
 
     uint32_t* d_lde = p->lde.as<uint32_t>();
@@ -760,19 +676,17 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     uint32_t* d_fdig = d_dig + n_trees * tree_words;
     uint32_t* d_perm = p->perm.as<uint32_t>();
     uint32_t* d_plde = p->plde.as<uint32_t>();
-    uint32_t* d_q = p->q.as<uint32_t>();
-    uint32_t* d_qcoef = p->qcoef.as<uint32_t>();
     uint32_t* d_qlde = p->qlde.as<uint32_t>();
     bb::Ext* d_v = p->ext_arena.as<bb::Ext>();          // FRI layers, consecutive
     bb::Ext* d_weights = d_v + 2 * N;
-    bb::Ext* d_weights2 = d_weights + H;                   // LogUp: weights at g*zeta
-    bb::Ext* d_rowsum = d_weights2 + H;                    // LogUp: per-row sums, then block totals
-    bb::Ext* d_scratch = p->misc.as<bb::Ext>();            // dot_cols * n_chunks
-    bb::Ext* d_opened = d_scratch + 2 * (size_t)dot_cols * n_chunks;  // K
+    bb::Ext* d_scratch = p->misc.as<bb::Ext>();
+    bb::Ext* d_opened = d_scratch + dot_scratch_words(s);  // K
     bb::Ext* d_gpow = d_opened + K;                        // K
     bb::Ext* d_apow = d_gpow + K;                          // M
     bb::Ext* d_blpow = d_apow + M + 4;                     // max_args + 2
     uint8_t* d_tail = reinterpret_cast<uint8_t*>(d_blpow + p->max_args + 8);
+    // trace values | coefficient arrays | alpha, beta powers | weights at zeta, at g zeta (LogUp) | per-row sums, block totals (LogUp) | scratch
+    const AirBufs bufs{d_trace, d_trace, d_tcoef, d_apow, d_blpow, d_weights, d_weights + H, d_weights + 2 * H, d_scratch};
 
     std::vector<uint32_t>& pf = p->proof;
     pf.clear();
@@ -805,7 +719,6 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
 
     // ---- 1b. LogUp: permutation trace, its LDE and commitment ---------------------------------------
     bb::Ext al = bb::ext_zero(), S = bb::ext_zero();
-    LogupProgram lp{p->d_inter, n_int, p->d_ixspans, p->d_icode, p->d_gstarts, n_g, p->d_iforms};
     if (lg) {
         // the bus challenges come from a transcript that saw only the bus seed (shared by all AIRs of a segment;
         // a lone AIR uses its own trace root), see oracle/stark_oracle.cpp bus_challenges
@@ -822,33 +735,13 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         { bb::Ext b = bb::ext_one(); for (auto& x : blpow) { x = b; b = bb::ext_mul(b, bl); } }
         PW_HIP_TRY(hipMemcpyAsync(d_blpow, blpow.data(), blpow.size() * sizeof(bb::Ext), hipMemcpyHostToDevice, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
-        // eat: the matrix's VALUES live in the sub-coset buffer (idle between two passes) until its coefficient arrays exist
-        uint32_t* d_pval = eat ? d_lde : d_perm;
-        if (jit) TRY(logup_perm_trace_jit(p, d_trace, H, al, d_blpow, d_pval, d_rowsum, d_rowsum + H));
-        else TRY(logup_perm_trace(d_trace, H, lp, al, d_blpow, d_pval, d_rowsum, d_rowsum + H));
-        if (!sb) {
-            TRY(lde_matrix(p, L, log_h, d_perm, Wp + (jit ? kJitExtraPermCols : 0u), d_plde));
-            TRY(merkle_commit_matrix(d_plde, N, Wp, N, d_pdig));
-        } else {
-            // streamed: only phi and the per-row sums (the boundary terms read them at rows j and j + 2) are extended for good
-            if (!jit) TRY(ext_to_cols(d_rowsum, H, d_pval + (size_t)(4 * n_g + 4) * H));
-            TRY(lde_matrix(p, L, log_h, d_pval + (size_t)(4 * n_g) * H, 8, d_plde));
-        }
+        const uint32_t* s_words[4];  // S = phi(last row)
+        TRY(logup_stage(p, s, mode, L, bufs, al, s_words));
+        if (sb) TRY(commit_coefficients(p, L, log_h, d_perm, Wp, d_pdig));  // the matrix is its coefficient arrays: sub-coset by sub-coset
+        else TRY(merkle_commit_matrix(d_plde, N, Wp, N, d_pdig));
         uint32_t sw[4];
         PW_HIP_TRY(hipMemcpyAsync(root, d_pdig + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
-        for (int k = 0; k < 4; ++k)  // S = phi(last row)
-            PW_HIP_TRY(hipMemcpyAsync(&sw[k], d_pval + ((size_t)(4 * n_g + k) * H + (H - 1)), 4, hipMemcpyDeviceToHost, st));
-        if (sb) {
-            // (S is read from the matrix first:) the permutation matrix becomes its coefficient arrays in place, committed sub-coset by sub-coset
-            PW_HIP_TRY(hipStreamSynchronize(st));
-            if (eat) {
-                // the trace's values are dead now: its coefficient arrays move into its place, the permutation buffer takes the matrix's
-                PW_HIP_TRY(hipMemcpyAsync(d_tcoef, d_coef_tmp, (size_t)W * H * 4, hipMemcpyDeviceToDevice, st));
-                TRY(intt_dif(d_pval, d_perm, H, H, Wp, (int)log_h));
-            } else TRY(intt_dif(d_perm, d_perm, H, H, Wp, (int)log_h));
-            TRY(commit_coefficients(p, L, log_h, d_perm, Wp, d_pdig));
-            PW_HIP_TRY(hipMemcpyAsync(root, d_pdig + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
-        }
+        for (int k = 0; k < 4; ++k) PW_HIP_TRY(hipMemcpyAsync(&sw[k], s_words[k], 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
         put_monty(root, 8);
         ch.observe_words(root, 8);
@@ -866,32 +759,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         if (M) PW_HIP_TRY(hipMemcpyAsync(d_apow, apow.data(), M * sizeof(bb::Ext), hipMemcpyHostToDevice, st));
         PW_HIP_TRY(hipStreamSynchronize(st));  // apow is a stack-local vector
     }
-    const uint32_t s_m = bb::to_monty(field::kCosetShift);
-    uint32_t sH = s_m;
-    for (uint32_t i = 0; i < log_h; ++i) sH = bb::sqr(sH);
-    const uint32_t one = bb::R_MOD_P;
-    const uint32_t zinv_even = bb::inv(bb::sub(sH, one));
-    const uint32_t zinv_odd = bb::inv(bb::sub(bb::neg(sH), one));
-    ConstraintProgram prog{p->d_bytecode, p->d_spans, nc, p->is_xbc};
-    if (sb) {
-        // streamed: the terms that read the current row only, sub-coset by sub-coset (unscaled sums scattered to their rows of d_q), then
-        // the boundary terms / the division by Z_H over all rows
-        TRY(streamed::quotient_sums(stream_ctx(p, L, log_h), jit, lg, nc, prog, lp, d_tcoef, d_perm, d_apow, al, d_blpow, S, logN, d_q));
-        if (lg)
-            TRY(quotient_logup_tail(d_q, 1, d_plde, d_plde + 4 * N, N, logN, d_apow + nc + n_g, S, bb::sub(sH, one), bb::sub(bb::neg(sH), one), d_q));
-        else
-            TRY(quotient_combine(d_q, 1, N, zinv_even, zinv_odd, d_q));
-    } else if (lg && jit)
-        TRY(quotient_eval_logup_jit(p, d_lde, d_plde, N, logN, d_apow, al, d_blpow, S, bb::sub(sH, one), bb::sub(bb::neg(sH), one), d_q));
-    else if (lg)
-        TRY(quotient_eval_logup(d_lde, d_plde, N, logN, prog, lp, d_apow, al, d_blpow, S, bb::sub(sH, one), bb::sub(bb::neg(sH), one), d_q));
-    else if (jit && nc)
-        TRY(quotient_eval_jit(p, d_lde, N, d_apow, zinv_even, zinv_odd, d_q));
-    else
-        TRY(quotient_eval(d_lde, N, prog, d_apow, zinv_even, zinv_odd, d_q, p->qpart.as<uint32_t>(), quotient_chunks(N, nc)));
-    TRY(intt_dif(d_q, d_q, N, N, 4, logN));
-    TRY(quotient_split(d_q, H, (int)log_h, d_qcoef));
-    TRY(coset_lde_from_coeffs(d_qcoef, d_qlde, H, N, 8, (int)log_h));
+    TRY(quotient_stage(p, s, mode, L, bufs, al, S));
     TRY(merkle_commit_matrix(d_qlde, N, 8, N, d_qdig));
     PW_HIP_TRY(hipMemcpyAsync(root, d_qdig + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
     PW_HIP_TRY(hipStreamSynchronize(st));
@@ -918,34 +786,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     const uint32_t n_slices = (mb && Wp >= 1024) ? 4u : 1u;
     uint32_t slice_at[5];
     for (uint32_t i = 0; i <= n_slices; ++i) slice_at[i] = i == n_slices ? Wp : (uint32_t)((uint64_t)Wp * i / n_slices) & ~7u;
-    auto open_perm = [&]() -> int {  // at zeta and at g zeta: one pass over the columns of a slice
-        for (uint32_t i = 0; i < n_slices; ++i) {
-            const uint32_t c0 = slice_at[i], c1 = slice_at[i + 1];
-            if (c1 > c0) TRY(ext_dot_columns2(d_perm + (size_t)c0 * H, H, c1 - c0, H, d_weights, d_weights2, d_open + W + c0, d_open + K1 + c0, d_scratch));
-            TRY(mark());
-        }
-        return 0;
-    };
-    if (!eat) {
-        TRY(barycentric_weights(zeta, (int)log_h, d_weights));
-        TRY(ext_dot_columns(d_trace, H, W, H, d_weights, d_open, d_scratch));
-        TRY(mark());
-    }
-    if (lg && !sb) {
-        TRY(barycentric_weights(gzeta, (int)log_h, d_weights2));
-        TRY(open_perm());
-    }
-    TRY(zeta_weights(zeta, (int)log_h, d_weights));
-    if (eat) {  // the trace is its coefficient arrays by now: opened like the permutation matrix below
-        TRY(ext_dot_columns(d_tcoef, H, W, H, d_weights, d_open, d_scratch));
-        TRY(mark());
-    }
-    if (lg && sb) {  // streamed: d_perm holds the matrix's coefficient arrays
-        TRY(zeta_weights(gzeta, (int)log_h, d_weights2));
-        TRY(open_perm());
-    }
-    TRY(ext_dot_columns(d_qcoef, H, 8, H, d_weights, d_open + W + Wp, d_scratch));
-    TRY(mark());
+    TRY(open_stage(p, s, mode, bufs, zeta, gzeta, d_open, slice_at, n_slices, mark));
     std::vector<bb::Ext> opened_copy;
     const bb::Ext* opened = mb ? mb->host : nullptr;
     if (!mb) {
@@ -986,47 +827,16 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         for (uint32_t k = K; k-- > K1;) opened_sum2 = bb::ext_add(bb::ext_mul(opened_sum2, gamma), opened[k]);
         opened_sum2 = bb::ext_mul(opened_sum2, bb::ext_pow(gamma, K1));
     };
-    if (sb) {
-        // streamed: sum_k gamma^k P_k is a POLYNOMIAL — combined on the coefficient arrays (one pass over them) and extended as 4 (+ 4 for
-        // the second opening point) columns; the eight quotient columns join from their resident LDE
-        TRY(streamed::deep_from_coefficients(stream_ctx(p, L, log_h), lg, d_tcoef, d_perm, d_qlde, logN, d_gpow, opened_sums, opened_sum, opened_sum2, zeta,
-                                             gzeta, d_v));
-    } else if (log_h >= kDeepComboMinLogHeight && !getenv("POWDR_DEEP_DIRECT") && !((uintptr_t)d_trace & 7)) {  // (the combination reads 8-byte pairs)
-        // resident: the same combination on the evaluations over <g_n> (the caller's trace, the permutation matrix), extended like any column
-        uint32_t* d_gev = p->gbuf.as<uint32_t>();
-        uint32_t* d_glde = d_gev + 8 * H;
-        const uint32_t gc = lg ? 8u : 4u;
-        TRY(ext_lincomb(d_trace, W, d_perm, Wp, H, d_gpow, lg ? K1 : 0u, d_gev));
-        TRY(lde_matrix(p, L, log_h, d_gev, gc, d_glde));
-        opened_sums();  // (the device is busy with the two launches above)
-        TRY(deep_from_combo(d_glde, d_qlde, N, logN, d_gpow + W + Wp, opened_sum, opened_sum2, zeta, gzeta, lg ? 1 : 0, d_v));
-    } else if (lg) {
-        opened_sums();
-        TRY(deep_quotient_logup(d_lde, W, d_plde, Wp, d_qlde, N, logN, d_gpow, opened_sum, opened_sum2, zeta, gzeta, d_v));
-    } else {
-        opened_sums();
-        TRY(deep_quotient(d_lde, W, d_qlde, 8, N, logN, d_gpow, opened_sum, zeta, d_v));
-    }
+    TRY(deep_stage(p, s, mode, L, bufs, d_gpow, gamma, opened_sums, opened_sum, opened_sum2, zeta, gzeta, d_v));
 
     // ---- 5. FRI commit phase --------------------------------------------------------------------
-    std::vector<size_t> layer_off(log_h + 1), tree_off(log_h);  // offsets in Ext / in words
-    {
-        size_t o = 0, t = 0;
-        for (uint32_t l = 0; l <= log_h; ++l) { layer_off[l] = o; o += N >> l; }
-        for (uint32_t l = 0; l < log_h; ++l) { tree_off[l] = t; t += merkle_words((N >> l) / 2); }
-    }
-    uint32_t shift = s_m;
+    const FriLayout fri(logN);
+    const std::vector<size_t>& layer_off = fri.layer_off;
+    uint32_t shift = bb::to_monty(field::kCosetShift);
     for (uint32_t l = 0; l < log_h; ++l) {
         const size_t half = (N >> l) / 2;
         bb::Ext* v = d_v + layer_off[l];
-        uint32_t* dg = d_fdig + tree_off[l];
-        // the tree's tail kernel writes the root into host-mapped memory: no copy dispatch between the layers
-        uint32_t* d_mail = nullptr;
-        uint32_t* h_mail = merkle_root_mailbox(&d_mail);
-        TRY(merkle_commit_ext_pairs(v, half, dg, h_mail ? d_mail : nullptr));
-        if (!h_mail) PW_HIP_TRY(hipMemcpyAsync(root, dg + merkle_words(half) - 8, 32, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-        if (h_mail) memcpy(root, h_mail, 32);
+        TRY(fri_commit_round(v, half, d_fdig + fri.tree_off[l], root));
         put_monty(root, 8);
         ch.observe_words(root, 8);
         const bb::Ext beta = ch.sample_ext();
@@ -1041,17 +851,8 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
 
     // ---- 6. proof of work ------------------------------------------------------------------------
     uint32_t witness = 0;
-    if (p->cfg.pow_bits) {
-        uint32_t* d_state = reinterpret_cast<uint32_t*>(d_tail);
-        uint32_t pending[8] = {0};
-        for (size_t i = 0; i < ch.in.size(); ++i) pending[i] = ch.in[i];
-        PW_HIP_TRY(hipMemcpyAsync(d_state, ch.st, 64, hipMemcpyHostToDevice, st));
-        PW_HIP_TRY(hipMemcpyAsync(d_state + 16, pending, 32, hipMemcpyHostToDevice, st));
-        TRY(pow_grind(d_state, d_state + 16, (uint32_t)ch.in.size(), p->cfg.pow_bits, d_state + 24, &witness));
-    }
+    TRY(grind(ch, p->cfg.pow_bits, reinterpret_cast<uint32_t*>(d_tail), &witness));
     put(witness);
-    ch.observe_canonical(witness);
-    if (p->cfg.pow_bits) (void)ch.sample_bits((int)p->cfg.pow_bits);
 
     // ---- 7. queries --------------------------------------------------------------------------------
     if (nq) {
@@ -1063,7 +864,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         uint32_t* d_trows = d_loc + nq;
         uint32_t* d_prows = d_trows + (size_t)nq * W;
         uint32_t* d_qrows = d_prows + (size_t)nq * Wp;
-        uint64_t* d_offs = reinterpret_cast<uint64_t*>(d_qrows + (size_t)nq * 8 + (((size_t)nq * (W + Wp + 10)) & 1));
+        uint64_t* d_offs = reinterpret_cast<uint64_t*>(d_qrows + (size_t)nq * 8 + (((size_t)nq * (K1 + 2)) & 1));
         // digest records (8 words) then FRI sibling records (4 words)
         std::vector<uint64_t> dig_offs, ext_offs;
         for (uint32_t qi = 0; qi < nq; ++qi) {
@@ -1075,13 +876,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
                 for (int l = 0; l < logN; ++l)
                     dig_offs.push_back(base + merkle_level_offset(N, l) + (((i >> l) ^ 1) * 8));
             }
-            for (uint32_t l = 0; l < log_h; ++l) {
-                const size_t Nl = N >> l, half = Nl / 2, pp = i & (Nl - 1);
-                ext_offs.push_back((layer_off[l] + (pp ^ half)) * 4);
-                const size_t leaf = pp & (half - 1);
-                for (int lv = 0; lv < logN - 1 - (int)l; ++lv)
-                    dig_offs.push_back(n_trees * tree_words + tree_off[l] + merkle_level_offset(half, lv) + (((leaf >> lv) ^ 1) * 8));
-            }
+            fri_query_offsets(i, logN, fri, n_trees * tree_words, ext_offs, dig_offs);
         }
         const size_t n_dig = dig_offs.size(), n_ext = ext_offs.size();
         uint64_t* d_dig_offs = d_offs;
@@ -1097,7 +892,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         } else {
             // streamed: one more pass over the sub-cosets that hold a queried row (prover_stream.hpp query_rows); d_loc and the first nq
             // words of d_qrows (filled afterwards) are its index scratch
-            const streamed::Ctx sc = stream_ctx(p, L, log_h);
+            const streamed::Ctx sc = stream_ctx(p, s, L);
             TRY(streamed::query_rows(sc, d_tcoef, W, idx.data(), nq, d_loc, d_qrows, d_trows));
             if (lg) TRY(streamed::query_rows(sc, d_perm, Wp, idx.data(), nq, d_loc, d_qrows, d_prows));
         }
@@ -1105,7 +900,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         TRY(gather_records(d_dig, d_dig_offs, 8u, (uint32_t)n_dig, d_dig_out));
         TRY(gather_records(reinterpret_cast<const uint32_t*>(d_v), d_ext_offs, 4u, (uint32_t)n_ext, d_ext_out));
         // the answers leave the device as canonical words (d_trows .. d_qrows are contiguous)
-        TRY(canonicalize_words(d_trows, (size_t)nq * (W + Wp + 8)));
+        TRY(canonicalize_words(d_trows, (size_t)nq * K1));
         TRY(canonicalize_words(d_dig_out, n_dig * 8));
         TRY(canonicalize_words(d_ext_out, n_ext * 4));
         std::vector<uint32_t> trows((size_t)nq * W), prows((size_t)nq * Wp + 1), qrows((size_t)nq * 8), dig(n_dig * 8), ext(n_ext * 4 + 1);

@@ -1,5 +1,6 @@
 // State shared by the prover's translation units (prover.hip: one AIR = one proof; segment_prover.hip: one proof per
-// segment): the per-AIR prover object, the host transcript, a growable device buffer. Not part of the C ABI.
+// segment): the per-AIR prover object, the host transcript, a growable device buffer. What both provers do to one AIR between two
+// commitments — and the plan of the buffers it needs — is prover_stages.hpp (streamed arms: prover_stream.hpp). Not part of the C ABI.
 #pragma once
 #include "prover_internal.hpp"
 #include "jit_codegen.hpp"

@@ -4,7 +4,9 @@
 // per_trace})` (/root/reference/openvm/src/trace_generation.rs:136-139, openvm-riscv/src/lib.rs:327-332). Protocol
 // definition: oracle/stark_segment.inc (header comment); the words produced here must equal the oracle's.
 //
-//   phase 1   LDE of every main trace (per-AIR kernels of prover.hip), ONE mixed-height Poseidon2 tree over all of them:
+// The per-AIR stages between the commitments (permutation matrix, quotient, openings, DEEP numerator, a FRI commit round, proof of
+// work) are prover_stages.hpp's, shared with the one-AIR prover; this file keeps the protocol: trees, transcript, FRI fold, queries.
+//   phase 1   LDE of every main trace (lde_matrix, prover.hip), ONE mixed-height Poseidon2 tree over all of them:
 //             the leaf hash runs over a column-pointer table, so all AIRs of one height are hashed by one launch — a
 //             2^12-row AIR no longer gets a launch (and a quarter-empty GPU) of its own
 //   phase 2   LogUp permutation matrices (shared challenges straight from the segment transcript), one mixed tree
@@ -19,8 +21,7 @@
 // prover_stream.hpp. A level's row digest is a sponge over the CONCATENATED rows of all matrices of that height: a level that holds a
 // streamed matrix is absorbed run by run with the rows' sponge states parked in between (merkle.hip leaf_absorb_kernel).
 #include "prover_state.hpp"
-#include "prover_stream.hpp"
-#include "logup_groups.hpp"
+#include "prover_stages.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -72,63 +73,18 @@ struct SegCtx {
 };
 thread_local SegCtx g_ctx;  // one per host thread (= per launch stream)
 
-struct Shape {
-    uint32_t W, nc, n_int, n_g, Wp, M, K, log_h;
-    uint32_t Wf, W1;  // preprocessed columns, W1 = W + Wf: the columns the programs and the ζ openings see
-    // the row layout: rf = kRowsNext | kRowsSelector (0: not row-aware), Wr = the values behind the W1 columns of the
-    // LDE (next rows, selectors), Wg = the columns opened at g zeta besides the permutation matrix (W1 for a two-point AIR, else 0)
-    uint32_t rf, Wr, Wg;
-    size_t H, N, koff;
-    int logN;
-};
-
 // device buffers of one RESIDENT AIR in the segment flow (the per-AIR prover object owns them; nothing here is freed per segment):
-// the sizes first — the streaming decision below adds up exactly what ensure_air would allocate — then the allocation
-struct AirPlan {
-    size_t panel_cols = 0, coef = 0, lde = 0, perm = 0, plde = 0, q = 0, qpart = 0, qcoef = 0, qlde = 0, ext_arena = 0, misc = 0, gbuf = 0;
-    size_t total() const { return coef + lde + perm + plde + q + qpart + qcoef + qlde + ext_arena + misc + gbuf; }
-};
-AirPlan plan_air(const PwProver* p, const Shape& s, bool logup) {
-    AirPlan B;
-    B.panel_cols = lde_panel_cols(s.H, logup ? std::max<size_t>(s.W, s.Wp) : s.W);
-    B.coef = B.panel_cols * s.H * 4;
-    B.lde = ((size_t)s.W1 + s.Wr) * s.N * 4;  // the fixed matrix's LDE rides behind the main columns, the row layout's values behind both
-    if (logup) {  // + the uncommitted per-row-sum columns of the specialised path
-        B.perm = (size_t)(s.Wp + kJitExtraPermCols) * s.H * 4;
-        B.plde = (size_t)(s.Wp + kJitExtraPermCols) * s.N * 4;
-    }
-    B.q = 4 * s.N * 4;
-    if (!logup) {
-        const uint32_t chunks = quotient_chunks(s.N, s.nc);
-        if (chunks > 1) B.qpart = (size_t)chunks * 4 * s.N * 4;
-    }
-    // the specialised kernels' partial sums (not lazily in the middle of the proof, while other AIRs' side streams run)
-    if (specialised(p)) B.qpart = std::max(B.qpart, jit_part_bytes(p, s.H, s.N));
-    B.qcoef = 8 * s.H * 4;
-    B.qlde = 8 * s.N * 4;
+// the sizes first — the streaming decision below adds up exactly what ensure_air would allocate — then the allocation.
+// To the stage buffers the AIR adds only its own vectors: trees, FRI layers, openings, gamma powers and the query tail are the segment's.
+BufferPlan plan_air(const PwProver* p, const AirShape& s, CommitLayout& Lc) {
+    BufferPlan B;
+    plan_stage_buffers(p, s, AirMode{0, false}, Lc, B);
+    Lc.tree_words = 0; Lc.fri_words = 0; Lc.n_trees = 0;
     B.ext_arena = (3 * s.H + s.H / 4096 + 32) * sizeof(bb::Ext);  // weights | weights at g zeta | row sums + block totals
-    const uint32_t n_chunks = div_up(s.H, 8192);
-    const uint32_t dot_cols = std::max({s.W1, s.Wp, 8u});
-    B.misc = (2 * (size_t)dot_cols * n_chunks + s.M + p->max_args + 64) * sizeof(bb::Ext) + 4096;  // ext_dot_columns2: two sets of partial sums
-    if (s.log_h >= kDeepComboMinLogHeight) B.gbuf = (size_t)24 * s.H * 4;  // the DEEP combinations and their LDE
+    B.misc = (dot_scratch_words(s) + s.M + p->max_args + 64) * sizeof(bb::Ext) + 4096;  // scratch | alpha, beta powers
     return B;
 }
-int ensure_air(PwProver* p, const Shape& s, bool logup, CommitLayout& Lc) {
-    const AirPlan B = plan_air(p, s, logup);
-    Lc.H = s.H; Lc.N = s.N; Lc.tree_words = 0; Lc.fri_words = 0; Lc.n_trees = 0;
-    Lc.panel_cols = B.panel_cols;
-    TRY(p->coef.ensure(B.coef));
-    TRY(p->lde.ensure(B.lde));
-    if (B.perm) { TRY(p->perm.ensure(B.perm)); TRY(p->plde.ensure(B.plde)); }
-    TRY(p->q.ensure(B.q));
-    if (B.qpart > p->qpart.bytes) TRY(p->qpart.ensure(B.qpart));
-    TRY(p->qcoef.ensure(B.qcoef));
-    TRY(p->qlde.ensure(B.qlde));
-    TRY(p->ext_arena.ensure(B.ext_arena));
-    TRY(p->misc.ensure(B.misc));
-    if (B.gbuf) TRY(p->gbuf.ensure(B.gbuf));
-    return 0;
-}
+int ensure_air(PwProver* p, const AirShape& s, CommitLayout& Lc) { return apply_plan(p, plan_air(p, s, Lc)); }
 
 }  // namespace
 
@@ -244,31 +200,23 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     const uint32_t nq = cfg.num_queries;
 
     // ---- shapes -----------------------------------------------------------------------------------------------
-    std::vector<Shape> sh(A);
+    std::vector<AirShape> sh(A);
+    std::vector<size_t> koff(A);  // where the AIR's openings and gamma powers start among the segment's
     size_t K_total = 0;
     int L = 0;
     for (size_t a = 0; a < A; ++a) {
-        const PwProver* p = airs[a].prover;
-        Shape& s = sh[a];
-        s.W = p->width; s.nc = p->n_constraints; s.log_h = airs[a].log_height;
-        s.n_int = lg ? p->n_inter : 0; s.n_g = lg ? p->n_groups : 0; s.Wp = lg ? 4 * (s.n_g + 1) : 0;
-        s.M = s.nc + (lg ? s.n_g + 3 : 0);
-        s.Wf = p->pre_width; s.W1 = s.W + s.Wf;
-        s.rf = p->row_flags; s.Wr = p->row_cols; s.Wg = (s.rf & kRowsNext) ? s.W1 : 0;
-        s.K = s.W1 + 2 * s.Wp + 8 + s.Wg;
-        s.H = (size_t)1 << s.log_h; s.N = 2 * s.H; s.logN = (int)s.log_h + 1;
-        s.koff = K_total;
-        K_total += s.K;
-        if (s.logN > L) L = s.logN;
+        sh[a] = air_shape(airs[a].prover, airs[a].log_height, lg);
+        koff[a] = K_total;
+        K_total += sh[a].K;
+        if (sh[a].logN > L) L = sh[a].logN;
     }
     const size_t Nmax = (size_t)1 << L;
     const size_t tree_words = merkle_words(Nmax);
     const int n_trees = lg ? 3 : 2;
     const int rounds = L - 1;
-    std::vector<size_t> layer_off(rounds + 1), ftree_off(rounds);
-    size_t fri_words = 0;
-    { size_t o = 0; for (int l = 0; l <= rounds; ++l) { layer_off[l] = o; o += Nmax >> l; } }
-    for (int l = 0; l < rounds; ++l) { ftree_off[l] = fri_words; fri_words += merkle_words((Nmax >> l) / 2); }
+    const FriLayout fri(L);
+    const std::vector<size_t>& layer_off = fri.layer_off;
+    const size_t fri_words = fri.fri_words;
     // reduced-opening vectors of the smaller heights, in the ext arena after the FRI layers
     std::vector<size_t> ro_off(L + 1, 0);
     std::vector<char> has_height(L + 1, 0);
@@ -287,7 +235,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     size_t row_words = 0;  // query answers: rows of every tree
     size_t n_pre_dig = 0;  // the preprocessed trees' siblings (each AIR's own tree)
     for (size_t a = 0; a < A; ++a) {
-        row_words += (size_t)nq * (sh[a].W1 + sh[a].Wp + 8);
+        row_words += (size_t)nq * sh[a].K1;
         if (sh[a].Wf) n_pre_dig += (size_t)nq * sh[a].logN;
     }
     const size_t n_dig = (size_t)nq * ((size_t)n_trees * L + (size_t)rounds * L) + n_pre_dig + 16;  // upper bound of digest records
@@ -313,6 +261,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
 
     // ---- which AIRs are streamed (sbv[a] = log2 of the number of sub-cosets, 0 = LDE resident) ------------------------------
     std::vector<int> sbv(A, 0);
+    std::vector<CommitLayout> Lc(A);
     cx.last_plan[0] = cx.last_plan[1] = cx.last_plan[2] = 0;
     cx.plan_resident.clear(); cx.plan_streamed.clear(); cx.plan_b_max.clear();
     {
@@ -338,7 +287,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                 resident.assign(A, 0); streamed.assign(A * 5, 0); bm.assign(A, 0);
                 size_t need = own;
                 for (size_t a = 0; a < A; ++a) {
-                    resident[a] = plan_air(airs[a].prover, sh[a], lg).total();
+                    resident[a] = plan_air(airs[a].prover, sh[a], Lc[a]).total();
                     need += resident[a];
                     if (!may_stream(a) || sh[a].log_h < stream_min_log_height()) continue;
                     bm[a] = b_max(a);
@@ -355,14 +304,11 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     for (size_t a = 0; a < A; ++a) eat[a] = handed[a] && sbv[a] > 0;
     cx.last_modes.assign(A, 0);
     for (size_t a = 0; a < A; ++a) cx.last_modes[a] = (uint32_t)sbv[a] | (eat[a] ? 0x100u : 0u);
-    std::vector<CommitLayout> Lc(A);
     for (size_t a = 0; a < A; ++a) {
         if (sbv[a]) TRY(ensure_proof_buffers(airs[a].prover, sh[a].log_h, sbv[a], Lc[a], eat[a] != 0));
-        else TRY(ensure_air(airs[a].prover, sh[a], lg, Lc[a]));
+        else TRY(ensure_air(airs[a].prover, sh[a], Lc[a]));
     }
-    auto sctx = [&](size_t a) {
-        return streamed::Ctx{airs[a].prover, sh[a].log_h, sbv[a], Lc[a].perm_panels, sh[a].H, sh[a].N, Lc[a].m, sh[a].W, sh[a].Wp};
-    };
+    auto sctx = [&](size_t a) { return stream_ctx(airs[a].prover, sh[a], Lc[a]); };
 
     std::vector<uint32_t>& pf = cx.proof;
     pf.clear();
@@ -485,15 +431,15 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     put_monty(root, 8);
     ch.observe_words(root, 8);
 
-    // per-AIR scratch pointers
-    auto weights_of = [&](size_t a) { return airs[a].prover->ext_arena.as<bb::Ext>(); };
-    auto scratch_of = [&](size_t a) { return airs[a].prover->misc.as<bb::Ext>(); };
-    auto apow_of = [&](size_t a) { return scratch_of(a) + 2 * (size_t)std::max({sh[a].W1, sh[a].Wp, 8u}) * div_up(sh[a].H, 8192); };
-    auto blpow_of = [&](size_t a) { return apow_of(a) + sh[a].M + 4; };
-    auto logup_program = [&](size_t a) {
-        const PwProver* p = airs[a].prover;
-        return LogupProgram{p->d_inter, sh[a].n_int, p->d_ixspans, p->d_icode, p->d_gstarts, sh[a].n_g, p->d_iforms};
+    // what the stages of AIR a read and write outside its prover's stage buffers: its vectors live in the prover's ext_arena
+    // (weights | weights at g zeta | row sums + block totals) and misc (dot-product scratch | alpha powers | beta powers)
+    auto bufs_of = [&](size_t a) {
+        bb::Ext* w = airs[a].prover->ext_arena.as<bb::Ext>();
+        bb::Ext* scratch = airs[a].prover->misc.as<bb::Ext>();
+        bb::Ext* apow = scratch + dot_scratch_words(sh[a]);
+        return AirBufs{airs[a].d_trace, values_of(a), tcoef_of(a), apow, apow + sh[a].M + 4, w, w + sh[a].H, w + 2 * sh[a].H, scratch};
     };
+    auto mode_of = [&](size_t a) { return AirMode{sbv[a], eat[a] != 0}; };
 
     // ---- 2. LogUp ---------------------------------------------------------------------------------------------
     bb::Ext al = bb::ext_zero(), bl = bb::ext_zero();
@@ -506,32 +452,11 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         for (size_t a = 0; a < A; ++a) {
             PwProver* p = airs[a].prover;
             on_air(a);
-            TRY(ext_powers(bl, p->max_args + 2, false, false, blpow_of(a)));  // beta^0 .. (computed where they are used: no upload per AIR)
-            bb::Ext* rowsum = weights_of(a) + 2 * sh[a].H;
-            // eat: the matrix's VALUES live in the sub-coset buffer (idle between two passes) until its coefficient arrays exist
-            uint32_t* d_pval = eat[a] ? p->lde.as<uint32_t>() : p->perm.as<uint32_t>();
-            if (specialised(p)) TRY(logup_perm_trace_jit(p, values_of(a), sh[a].H, al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
-            else TRY(logup_perm_trace(values_of(a), sh[a].H, logup_program(a), al, blpow_of(a), d_pval, rowsum, rowsum + sh[a].H));
-            if (sbv[a]) {
-                // streamed: only phi and the per-row sums are extended for good (the boundary terms read them at rows j and j + 2); S is
-                // saved before the matrix becomes its coefficient arrays in place
-                uint32_t* d_perm_a = p->perm.as<uint32_t>();
-                if (!specialised(p)) TRY(ext_to_cols(rowsum, sh[a].H, d_pval + (size_t)(4 * sh[a].n_g + 4) * sh[a].H));
-                TRY(lde_matrix(p, Lc[a], sh[a].log_h, d_pval + (size_t)(4 * sh[a].n_g) * sh[a].H, 8, p->plde.as<uint32_t>()));
-                uint32_t* d_save = p->gbuf.as<uint32_t>();
-                for (int k = 0; k < 4; ++k) {
-                    PW_HIP_TRY(hipMemcpyAsync(d_save + k, d_pval + ((size_t)(4 * sh[a].n_g + k) * sh[a].H + (sh[a].H - 1)), 4, hipMemcpyDeviceToDevice, stream()));
-                    sp.push_back(d_save + k);
-                }
-                if (eat[a]) {
-                    // the trace's values are dead now: its coefficient arrays move into its place, the permutation buffer takes the matrix's
-                    PW_HIP_TRY(hipMemcpyAsync(tcoef_of(a), d_perm_a, (size_t)sh[a].W * sh[a].H * 4, hipMemcpyDeviceToDevice, stream()));
-                    TRY(intt_dif(d_pval, d_perm_a, sh[a].H, sh[a].H, sh[a].Wp, (int)sh[a].log_h));
-                } else TRY(intt_dif(d_perm_a, d_perm_a, sh[a].H, sh[a].H, sh[a].Wp, (int)sh[a].log_h));
-                continue;
-            }
-            TRY(lde_matrix(p, Lc[a], sh[a].log_h, p->perm.as<uint32_t>(), sh[a].Wp + (specialised(p) ? kJitExtraPermCols : 0u), p->plde.as<uint32_t>()));
-            for (int k = 0; k < 4; ++k) sp.push_back(p->perm.as<uint32_t>() + ((size_t)(4 * sh[a].n_g + k) * sh[a].H + (sh[a].H - 1)));  // S = phi(last row)
+            const AirBufs B = bufs_of(a);
+            TRY(ext_powers(bl, p->max_args + 2, false, false, B.blpow));  // beta^0 .. (computed where they are used: no upload per AIR)
+            const uint32_t* s_words[4];  // S = phi(last row); a streamed AIR's is parked in its gbuf (free until the DEEP stage)
+            TRY(logup_stage(p, sh[a], mode_of(a), Lc[a], B, al, s_words));
+            sp.insert(sp.end(), s_words, s_words + 4);
         }
         TRY(join());
         TRY(commit_mixed([&](size_t a, const uint32_t*& m, uint32_t& w) {
@@ -555,41 +480,12 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     // ---- 3. quotients -----------------------------------------------------------------------------------------
     const bb::Ext alpha = ch.sample_ext();
     {
-        const uint32_t s_m = bb::to_monty(field::kCosetShift), one = bb::R_MOD_P;
         TRY(fork());
         for (size_t a = 0; a < A; ++a) {
-            PwProver* p = airs[a].prover;
-            const Shape& s = sh[a];
             on_air(a);
-            TRY(ext_powers(alpha, s.M, true, false, apow_of(a)));  // alpha^(M - 1) .. alpha^0
-            uint32_t sH = s_m;
-            for (uint32_t i = 0; i < s.log_h; ++i) sH = bb::sqr(sH);
-            const uint32_t zv_even = bb::sub(sH, one), zv_odd = bb::sub(bb::neg(sH), one);
-            ConstraintProgram prog{p->d_bytecode, p->d_spans, s.nc, p->is_xbc};
-            uint32_t* d_q = p->q.as<uint32_t>();
-            if (sbv[a]) {
-                // streamed: the current-row terms sub-coset by sub-coset, then the boundary terms / the division by Z_H over all rows
-                TRY(streamed::quotient_sums(sctx(a), specialised(p), lg, s.nc, prog, lg ? logup_program(a) : LogupProgram{}, tcoef_of(a),
-                                            p->perm.as<uint32_t>(), apow_of(a), al, blpow_of(a), S[a], s.logN, d_q));
-                if (lg)
-                    TRY(quotient_logup_tail(d_q, 1, p->plde.as<uint32_t>(), p->plde.as<uint32_t>() + 4 * s.N, s.N, s.logN, apow_of(a) + s.nc + s.n_g, S[a],
-                                            zv_even, zv_odd, d_q));
-                else
-                    TRY(quotient_combine(d_q, 1, s.N, bb::inv(zv_even), bb::inv(zv_odd), d_q));
-            } else if (lg && specialised(p))
-                TRY(quotient_eval_logup_jit(p, p->lde.as<uint32_t>(), p->plde.as<uint32_t>(), s.N, s.logN, apow_of(a), al, blpow_of(a), S[a], zv_even,
-                                            zv_odd, d_q));
-            else if (lg)
-                TRY(quotient_eval_logup(p->lde.as<uint32_t>(), p->plde.as<uint32_t>(), s.N, s.logN, prog, logup_program(a), apow_of(a), al,
-                                        blpow_of(a), S[a], zv_even, zv_odd, d_q));
-            else if (specialised(p) && s.nc)
-                TRY(quotient_eval_jit(p, p->lde.as<uint32_t>(), s.N, apow_of(a), bb::inv(zv_even), bb::inv(zv_odd), d_q));
-            else
-                TRY(quotient_eval(p->lde.as<uint32_t>(), s.N, prog, apow_of(a), bb::inv(zv_even), bb::inv(zv_odd), d_q, p->qpart.as<uint32_t>(),
-                                  quotient_chunks(s.N, s.nc)));
-            TRY(intt_dif(d_q, d_q, s.N, s.N, 4, s.logN));
-            TRY(quotient_split(d_q, s.H, (int)s.log_h, p->qcoef.as<uint32_t>()));
-            TRY(coset_lde_from_coeffs(p->qcoef.as<uint32_t>(), p->qlde.as<uint32_t>(), s.H, s.N, 8, (int)s.log_h));
+            const AirBufs B = bufs_of(a);
+            TRY(ext_powers(alpha, sh[a].M, true, false, B.apow));  // alpha^(M - 1) .. alpha^0
+            TRY(quotient_stage(airs[a].prover, sh[a], mode_of(a), Lc[a], B, al, S[a]));
         }
         TRY(join());
         TRY(commit_mixed([&](size_t a, const uint32_t*& m, uint32_t& w) { m = airs[a].prover->qlde.as<uint32_t>(); w = 8; }, 1, root));
@@ -603,34 +499,10 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     std::vector<bb::Ext> gzeta(A);
     TRY(fork());
     for (size_t a = 0; a < A; ++a) {
-        PwProver* p = airs[a].prover;
-        const Shape& s = sh[a];
         on_air(a);
-        bb::Ext* o = d_opened + s.koff;
-        bb::Ext* w1 = weights_of(a);
-        bb::Ext* w2 = w1 + s.H;
-        gzeta[a] = bb::ext_scale(zeta, field::root_of_unity((int)s.log_h));
-        // trace columns: barycentric evaluation straight from the caller's trace (with preprocessed columns: the (trace | fixed) copy,
-        // both in one pass; a two-point AIR: at zeta and at g zeta in that pass); quotient chunks from their coefficients
-        if (!eat[a]) {
-            TRY(barycentric_weights(zeta, (int)s.log_h, w1));
-            if (s.Wg) {
-                TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
-                TRY(ext_dot_columns2(values_of(a), s.H, s.W1, s.H, w1, w2, o, o + s.W1 + 2 * s.Wp + 8, scratch_of(a)));
-            } else
-                TRY(ext_dot_columns(values_of(a), s.H, s.W1, s.H, w1, o, scratch_of(a)));
-        }
-        if (lg && !sbv[a]) {  // the permutation matrix at zeta and at g zeta: one pass over its columns
-            if (!s.Wg) TRY(barycentric_weights(gzeta[a], (int)s.log_h, w2));
-            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W1, o + s.W1 + s.Wp + 8, scratch_of(a)));
-        }
-        TRY(zeta_weights(zeta, (int)s.log_h, w1));
-        if (eat[a]) TRY(ext_dot_columns(tcoef_of(a), s.H, s.W, s.H, w1, o, scratch_of(a)));  // the trace is its coefficient arrays by now
-        if (lg && sbv[a]) {  // streamed: p->perm holds the matrix's coefficient arrays
-            TRY(zeta_weights(gzeta[a], (int)s.log_h, w2));
-            TRY(ext_dot_columns2(p->perm.as<uint32_t>(), s.H, s.Wp, s.H, w1, w2, o + s.W1, o + s.W1 + s.Wp + 8, scratch_of(a)));
-        }
-        TRY(ext_dot_columns(p->qcoef.as<uint32_t>(), s.H, 8, s.H, w1, o + s.W1 + s.Wp, scratch_of(a)));
+        gzeta[a] = bb::ext_scale(zeta, field::root_of_unity((int)sh[a].log_h));
+        const uint32_t whole[2] = {0, sh[a].Wp};  // the permutation matrix in one piece: the values are fetched after the join
+        TRY(open_stage(airs[a].prover, sh[a], mode_of(a), bufs_of(a), zeta, gzeta[a], d_opened + koff[a], whole, 1, [] { return 0; }));
     }
     TRY(join());
     std::vector<bb::Ext> opened(K_total);
@@ -650,33 +522,15 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     {
         std::vector<char> started(L + 1, 0);
         for (size_t a = 0; a < A; ++a) {
-            PwProver* p = airs[a].prover;
-            const Shape& s = sh[a];
-            const size_t K1 = (size_t)s.W1 + s.Wp + 8;
+            const AirShape& s = sh[a];
             bb::Ext sum1 = bb::ext_zero(), sum2 = bb::ext_zero();
-            for (size_t k = 0; k < K1; ++k) sum1 = bb::ext_add(sum1, bb::ext_mul(gpow[s.koff + k], opened[s.koff + k]));
-            for (size_t k = K1; k < s.K; ++k) sum2 = bb::ext_add(sum2, bb::ext_mul(gpow[s.koff + k], opened[s.koff + k]));
+            auto sums = [&]() {
+                for (size_t k = 0; k < s.K1; ++k) sum1 = bb::ext_add(sum1, bb::ext_mul(gpow[koff[a] + k], opened[koff[a] + k]));
+                for (size_t k = s.K1; k < s.K; ++k) sum2 = bb::ext_add(sum2, bb::ext_mul(gpow[koff[a] + k], opened[koff[a] + k]));
+            };
             bb::Ext* target = s.logN == L ? d_v : d_v + ro_off[s.logN];
             bb::Ext* out = started[s.logN] ? d_v + tmp_off : target;
-            if (sbv[a])
-                TRY(streamed::deep_from_coefficients(sctx(a), lg, tcoef_of(a), p->perm.as<uint32_t>(), p->qlde.as<uint32_t>(), s.logN,
-                                                     d_gpow + s.koff, [] {}, sum1, sum2, zeta, gzeta[a], out));
-            else if (s.Wg)  // two-point: the W1 columns at both points from one read of their LDE
-                TRY(deep_quotient_two_point(p->lde.as<uint32_t>(), s.W1, lg ? p->plde.as<uint32_t>() : nullptr, s.Wp, p->qlde.as<uint32_t>(), s.N,
-                                            s.logN, d_gpow + s.koff, bb::ext_pow(gamma, K1 + s.Wp), sum1, sum2, zeta, gzeta[a], out));
-            else if (s.log_h >= kDeepComboMinLogHeight && !s.Wf && !getenv("POWDR_DEEP_DIRECT") && !((uintptr_t)airs[a].d_trace & 7)) {
-                // resident and tall: the numerator is combined on the evaluations over <g_n> — the caller's trace, the permutation
-                // matrix: half the bytes their LDE holds — and extended as 4 (+ 4) columns, like the one-AIR prover does
-                uint32_t* d_gev = p->gbuf.as<uint32_t>();
-                uint32_t* d_glde = d_gev + 8 * s.H;
-                TRY(ext_lincomb(airs[a].d_trace, s.W, p->perm.as<uint32_t>(), s.Wp, s.H, d_gpow + s.koff, lg ? (uint32_t)K1 : 0u, d_gev));
-                TRY(lde_matrix(p, Lc[a], s.log_h, d_gev, lg ? 8u : 4u, d_glde));
-                TRY(deep_from_combo(d_glde, p->qlde.as<uint32_t>(), s.N, s.logN, d_gpow + s.koff + s.W + s.Wp, sum1, sum2, zeta, gzeta[a], lg ? 1 : 0, out));
-            } else if (lg)
-                TRY(deep_quotient_logup(p->lde.as<uint32_t>(), s.W1, p->plde.as<uint32_t>(), s.Wp, p->qlde.as<uint32_t>(), s.N, s.logN,
-                                        d_gpow + s.koff, sum1, sum2, zeta, gzeta[a], out));
-            else
-                TRY(deep_quotient(p->lde.as<uint32_t>(), s.W1, p->qlde.as<uint32_t>(), 8, s.N, s.logN, d_gpow + s.koff, sum1, zeta, out));
+            TRY(deep_stage(airs[a].prover, s, mode_of(a), Lc[a], bufs_of(a), d_gpow + koff[a], gamma, sums, sum1, sum2, zeta, gzeta[a], out));
             if (started[s.logN]) TRY(ext_axpy(target, nullptr, out, s.N));
             started[s.logN] = 1;
         }
@@ -687,14 +541,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     for (int l = 0; l < rounds; ++l) {
         const size_t half = (Nmax >> l) / 2;
         bb::Ext* v = d_v + layer_off[l];
-        uint32_t* dg = d_fdig + ftree_off[l];
-        // the tree's tail kernel writes the root into host-mapped memory: no copy dispatch between the layers
-        uint32_t* d_mail = nullptr;
-        uint32_t* h_mail = merkle_root_mailbox(&d_mail);
-        TRY(merkle_commit_ext_pairs(v, half, dg, h_mail ? d_mail : nullptr));
-        if (!h_mail) PW_HIP_TRY(hipMemcpyAsync(root, dg + merkle_words(half) - 8, 32, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-        if (h_mail) memcpy(root, h_mail, 32);
+        TRY(fri_commit_round(v, half, d_fdig + fri.tree_off[l], root));
         put_monty(root, 8);
         ch.observe_words(root, 8);
         const bb::Ext beta = ch.sample_ext();
@@ -714,17 +561,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
 
     // ---- 7. proof of work ----------------------------------------------------------------------------------------
     uint32_t witness = 0;
-    if (cfg.pow_bits) {
-        uint32_t* d_state = d_small;
-        uint32_t pending[8] = {0};
-        for (size_t i = 0; i < ch.in.size(); ++i) pending[i] = ch.in[i];
-        PW_HIP_TRY(hipMemcpyAsync(d_state, ch.st, 64, hipMemcpyHostToDevice, st));
-        PW_HIP_TRY(hipMemcpyAsync(d_state + 16, pending, 32, hipMemcpyHostToDevice, st));
-        TRY(pow_grind(d_state, d_state + 16, (uint32_t)ch.in.size(), cfg.pow_bits, d_state + 24, &witness));
-    }
+    TRY(grind(ch, cfg.pow_bits, d_small, &witness));
     put(witness);
-    ch.observe_canonical(witness);
-    if (cfg.pow_bits) (void)ch.sample_bits((int)cfg.pow_bits);
 
     // ---- 8. queries ------------------------------------------------------------------------------------------------
     if (nq) {
@@ -793,13 +631,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
                     dig_offs.push_back(base + merkle_level_offset(Nmax, l) + (((p + size / 2) & (size - 1)) * 8));
                 }
             }
-            for (int l = 0; l < rounds; ++l) {
-                const size_t Nl = Nmax >> l, half = Nl / 2, pp = q & (Nl - 1);
-                ext_offs.push_back((layer_off[l] + (pp ^ half)) * 4);
-                const size_t leaf = pp & (half - 1);
-                for (int lv = 0; lv < L - 1 - l; ++lv)
-                    dig_offs.push_back((size_t)n_trees * tree_words + ftree_off[l] + merkle_level_offset(half, lv) + (((leaf >> lv) ^ 1) * 8));
-            }
+            fri_query_offsets(q, L, fri, (size_t)n_trees * tree_words, ext_offs, dig_offs);
         }
         const size_t nd = dig_offs.size(), ne = ext_offs.size(), npd = pre_offs.size();
         if (nd + npd > n_dig) return (int)hipErrorInvalidValue;

@@ -75,6 +75,21 @@ lib.pw_merkle_commit.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
 lib.pw_poseidon2_permute_host.argtypes = [C.c_void_p]
 
 
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _interaction_tables(interactions):
+    """interactions = (inter[n x 3] = {bus, n_args, first span}, spans[m x 2], bytecode) or None -> the six (pointer, length) arguments
+    the C entry points take for them, and the arrays those pointers point into."""
+    if interactions is None:
+        return (None, 0, None, 0, None, 0), []
+    it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
+    isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
+    ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
+    return (_vp(it), len(it), _vp(isp), len(isp), _vp(ibc), len(ibc)), [it, isp, ibc]
+
+
 lib.pw_verify.restype = C.c_int
 lib.pw_verify.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                           C.c_void_p, C.c_size_t]
@@ -110,15 +125,13 @@ def verify_logup(proof, width: int, log_height: int, cons_bytecode, cons_spans, 
     pr = np.ascontiguousarray(proof, dtype=np.uint32)
     bc = np.ascontiguousarray(cons_bytecode, dtype=np.uint32)
     sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
-    it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
-    isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
-    ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
+    tables, _ = _interaction_tables(interactions)
     cfg = PwStarkConfig(num_queries, pow_bits)
     s, root = np.zeros(4, np.uint32), np.zeros(8, np.uint32)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    p = _vp
     seed = None if bus_seed is None else np.ascontiguousarray(bus_seed, dtype=np.uint32)
-    rc = int(lib.pw_verify_logup(C.byref(cfg), width, log_height, p(bc), len(bc), p(sp), len(sp), p(it), len(it), p(isp), len(isp),
-                                 p(ibc), len(ibc), None if seed is None else p(seed), p(pr), len(pr), p(s), p(root)))
+    rc = int(lib.pw_verify_logup(C.byref(cfg), width, log_height, p(bc), len(bc), p(sp), len(sp), *tables,
+                                 None if seed is None else p(seed), p(pr), len(pr), p(s), p(root)))
     if with_root:
         return rc, (s if rc == 0 else None), (root if rc == 0 else None)
     return rc, (s if rc == 0 else None)
@@ -191,12 +204,9 @@ def row_operands(width: int, pre_width: int = 0) -> RowOperands:
 
 def logup_group_starts(interactions) -> np.ndarray:
     """Boundaries of the LogUp groups (one committed extension column each) for an interaction table."""
-    it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
-    isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
-    ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
-    out = np.zeros(len(it) + 2, np.uint32)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    k = lib.pw_logup_group_starts(p(it), len(it), p(isp), len(isp), p(ibc), len(ibc), p(out), len(out))
+    tables, _ = _interaction_tables(interactions)
+    out = np.zeros(tables[1] + 2, np.uint32)
+    k = lib.pw_logup_group_starts(*tables, _vp(out), len(out))
     if k == 0:
         raise ValueError("malformed interaction table")
     return out[:k].copy()
@@ -233,19 +243,12 @@ def prove_airs(airs, shared_bus_seed: bool = False, n_workers: int = 0, copy: bo
 def _air_descriptions(descs):
     n = len(descs)
     keep, recs = [], (PwAirDescription * max(n, 1))()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     for i, (w, lh, bc, sp, it) in enumerate(descs):
         bc = np.ascontiguousarray(bc, dtype=np.uint32)
         sp = np.ascontiguousarray(sp, dtype=np.uint32).reshape(-1, 2)
-        keep += [bc, sp]
-        if it is None:
-            recs[i] = PwAirDescription(w, lh, 0, vp(bc), len(bc), vp(sp), len(sp), None, 0, None, 0, None, 0)
-        else:
-            a = np.ascontiguousarray(it[0], dtype=np.uint32).reshape(-1, 3)
-            b = np.ascontiguousarray(it[1], dtype=np.uint32).reshape(-1, 2)
-            c = np.ascontiguousarray(it[2], dtype=np.uint32)
-            keep += [a, b, c]
-            recs[i] = PwAirDescription(w, lh, 1, vp(bc), len(bc), vp(sp), len(sp), vp(a), len(a), vp(b), len(b), vp(c), len(c))
+        tables, arrays = _interaction_tables(it)
+        keep += [bc, sp] + arrays  # (the record's pointer fields hold plain addresses)
+        recs[i] = PwAirDescription(w, lh, 0 if it is None else 1, _vp(bc), len(bc), _vp(sp), len(sp), *tables)
     return recs, keep
 
 
@@ -365,26 +368,13 @@ def verify_airs(descs, proofs, num_queries: int = 100, pow_bits: int = 0, shared
     """descs: [(width, log_height, cons_bytecode, cons_spans, interactions-or-None)] -> (code, total bus sum).
     code 0 = every proof valid (and balanced if asked); ((i+1) << 8) | c = proof i failed check c; 14 = unbalanced."""
     n = len(descs)
-    keep, recs = [], (PwAirDescription * max(n, 1))()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    for i, (w, lh, bc, sp, it) in enumerate(descs):
-        bc = np.ascontiguousarray(bc, dtype=np.uint32)
-        sp = np.ascontiguousarray(sp, dtype=np.uint32).reshape(-1, 2)
-        keep += [bc, sp]
-        if it is None:
-            recs[i] = PwAirDescription(w, lh, 0, vp(bc), len(bc), vp(sp), len(sp), None, 0, None, 0, None, 0)
-        else:
-            a = np.ascontiguousarray(it[0], dtype=np.uint32).reshape(-1, 3)
-            b = np.ascontiguousarray(it[1], dtype=np.uint32).reshape(-1, 2)
-            c = np.ascontiguousarray(it[2], dtype=np.uint32)
-            keep += [a, b, c]
-            recs[i] = PwAirDescription(w, lh, 1, vp(bc), len(bc), vp(sp), len(sp), vp(a), len(a), vp(b), len(b), vp(c), len(c))
+    recs, keep = _air_descriptions(descs)
     prs = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
     ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in prs])
     lens = (C.c_size_t * max(n, 1))(*[len(p) for p in prs])
     cfg = PwStarkConfig(num_queries, pow_bits)
     total = np.zeros(4, np.uint32)
-    rc = int(lib.pw_verify_airs(C.byref(cfg), recs, n, ptrs, lens, int(shared_bus_seed), int(check_balance), vp(total)))
+    rc = int(lib.pw_verify_airs(C.byref(cfg), recs, n, ptrs, lens, int(shared_bus_seed), int(check_balance), _vp(total)))
     return rc, total
 
 
@@ -411,12 +401,8 @@ def jit_compile_check(width: int, cons_bytecode, cons_spans, interactions=None) 
     f.restype = C.c_int
     f.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
-    if interactions is not None:
-        it, isp, ibc = (np.ascontiguousarray(a, dtype=np.uint32) for a in interactions)
-        isp = isp.reshape(-1, 2)
-        rc = f(width, vp(bc), len(bc), vp(sp), len(sp), vp(it), len(it.reshape(-1, 3)), vp(isp), len(isp), vp(ibc), len(ibc), C.byref(k), C.byref(b), C.byref(c), err, 4096)
-    else:
-        rc = f(width, vp(bc), len(bc), vp(sp), len(sp), None, 0, None, 0, None, 0, C.byref(k), C.byref(b), C.byref(c), err, 4096)
+    tables, _ = _interaction_tables(interactions)
+    rc = f(width, vp(bc), len(bc), vp(sp), len(sp), *tables, C.byref(k), C.byref(b), C.byref(c), err, 4096)
     return dict(rc=int(rc), kernels=k.value, code_bytes=b.value, chunks=c.value, error=err.value.decode(errors="replace"))
 
 
@@ -431,11 +417,7 @@ def jit_generated_sources(width: int, cons_bytecode, cons_spans, interactions=No
     f.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                   C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32),
                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if interactions is not None:
-        it, isp, ibc = (np.ascontiguousarray(a, dtype=np.uint32) for a in interactions)
-        tables = (vp(it), len(it.reshape(-1, 3)), vp(isp), len(isp.reshape(-1, 2)), vp(ibc), len(ibc))
-    else:
-        tables = (None, 0, None, 0, None, 0)
+    tables, _ = _interaction_tables(interactions)
     units, total = [], C.c_uint32()
     while True:
         first, n, name = C.c_uint32(), C.c_uint32(), C.create_string_buffer(64)
@@ -543,44 +525,18 @@ class Prover:
         cfg = PwStarkConfig(num_queries, pow_bits)
         self.width = width
         self.pre_width = 0
-        if transition:
-            vp = lambda a: a.ctypes.data_as(C.c_void_p)
-            if interactions is None:
-                tables = (None, 0, None, 0, None, 0)
-            else:
-                it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
-                isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
-                ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
-                tables = (vp(it), len(it), vp(isp), len(isp), vp(ibc), len(ibc))
+        tables, _ = _interaction_tables(interactions)
+        if transition or preprocessed is not None:
             t, pw_, lh = preprocessed if preprocessed is not None else (None, 0, 0)
             if t is not None:
                 assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
-            self._h = lib.pw_prover_create_transition(C.byref(cfg), width, pw_, lh, t.data_ptr() if t is not None else None, vp(bc), len(bc),
-                                                      vp(sp), len(sp), *tables)
-            self.pre_width = pw_
-        elif preprocessed is not None:
-            t, pw_, lh = preprocessed
-            assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
-            vp = lambda a: a.ctypes.data_as(C.c_void_p)
-            if interactions is None:
-                tables = (None, 0, None, 0, None, 0)
-            else:
-                it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
-                isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
-                ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
-                tables = (vp(it), len(it), vp(isp), len(isp), vp(ibc), len(ibc))
-            self._h = lib.pw_prover_create_preprocessed(C.byref(cfg), width, pw_, lh, t.data_ptr(), vp(bc), len(bc), vp(sp), len(sp), *tables)
+            create = lib.pw_prover_create_transition if transition else lib.pw_prover_create_preprocessed
+            self._h = create(C.byref(cfg), width, pw_, lh, t.data_ptr() if t is not None else None, _vp(bc), len(bc), _vp(sp), len(sp), *tables)
             self.pre_width = pw_
         elif interactions is None:
-            self._h = lib.pw_prover_create(C.byref(cfg), width, bc.ctypes.data_as(C.c_void_p), len(bc),
-                                           sp.ctypes.data_as(C.c_void_p), len(sp))
+            self._h = lib.pw_prover_create(C.byref(cfg), width, _vp(bc), len(bc), _vp(sp), len(sp))
         else:
-            it = np.ascontiguousarray(interactions[0], dtype=np.uint32).reshape(-1, 3)
-            isp = np.ascontiguousarray(interactions[1], dtype=np.uint32).reshape(-1, 2)
-            ibc = np.ascontiguousarray(interactions[2], dtype=np.uint32)
-            self._h = lib.pw_prover_create_logup(C.byref(cfg), width, bc.ctypes.data_as(C.c_void_p), len(bc),
-                                                 sp.ctypes.data_as(C.c_void_p), len(sp), it.ctypes.data_as(C.c_void_p), len(it),
-                                                 isp.ctypes.data_as(C.c_void_p), len(isp), ibc.ctypes.data_as(C.c_void_p), len(ibc))
+            self._h = lib.pw_prover_create_logup(C.byref(cfg), width, _vp(bc), len(bc), _vp(sp), len(sp), *tables)
         if not self._h:
             raise RuntimeError("pw_prover_create failed")
 
