@@ -524,6 +524,130 @@ __global__ __launch_bounds__(kBlock) void lde_fused2_kernel(const uint32_t* __re
     lde_fused_body<2>(tile2, in, out, in_stride, out_stride, ga, gd, tw_inv, tw_fwd, scale_br);
 }
 
+// The fused kernel specialised for its one geometry from 2^12 rows up (ka = 12: a 4 096-coefficient tile, 8 192 results, three radix-16
+// rounds each way, one passive bit on the forward side), every window, slot count, LDS offset and table offset a constant:
+//   A  DIF window 8-11: HBM -> registers -> LDS            (twiddles: per-lane table loads)
+//   B  DIF window 4-7:  LDS -> LDS                         (per-lane table loads, requested during A)
+//   C  DIF window 0-3:  LDS -> registers, times 1 / H      (15 wave-uniform twiddles)
+//   D  DIT window 1-4, both duplicates: registers -> LDS   (2 x 15 wave-uniform twiddles)
+//   E  DIT window 5-8:  LDS -> LDS, two slots              (ONE set of per-lane twiddles for both slots, requested during C)
+//   F  DIT window 9-12: LDS -> HBM, two slots              (per-lane table loads, requested during E)
+// No scale-and-duplicate pass: lane t ends C holding coefficients 16 t .. 16 t + 15 of the tile, and the two slots of D whose inputs
+// are their duplicates — positions 32 t + 2 rho + b of the doubled tile, b = the passive bit — are the slots 2 t and 2 t + 1, so the
+// lane runs both from its registers (one set of inputs, two sets of twiddles). The coset factor s^k is in the forward twiddles (stage
+// s of the size-2^(n+1) transform carries s^(2^(n-s)): the table is built per height, fused12_twiddles, and the strided DIT groups
+// multiply their round bases by GroupParams::cst); 1 / H is one product per coefficient at the end of C.
+// Per tile: 5 barriers (the generic kernel: 7), 24 576 LDS words written and 24 576 read (36 864 each).
+// Barrier 3 (between C and D): positions 32 t .. 32 t + 31 of the doubled tile are other lanes' coefficients 16 t .. 16 t + 15 of
+// the single one, so every lane must have read its C slot before any lane writes a D result.
+// LDS layout: lds_phys (one pad word per 32), 32-bit accesses, every one conflict-free per half-wave (32 banks): A / E / F move 32
+// consecutive words; B two runs of 16 words 528 = 16 (mod 32) words apart (see there); C reads with a lane stride of 16.5 words (banks
+// 16 (t & 1) + (t >> 1)) and D writes with one of 33 words. (The generic kernel's window 4-7 round is 2-way conflicting: measured.)
+constexpr uint32_t kF12A0 = 0, kF12A1 = 15u * 256u, kF12A2 = kF12A1 + 15u * 16u;   // DIF tables: windows 8-11, 4-7, 0-3
+constexpr uint32_t kF12D0 = 4096, kF12D1 = kF12D0 + 15u * 2u, kF12D2 = kF12D1 + 15u * 32u;  // DIT tables: windows 1-4, 5-8, 9-12
+constexpr uint32_t kF12Words = kF12D2 + 15u * 512u;
+
+template <int RB>
+__device__ constexpr uint32_t f12_off(int rho) {
+    return ((uint32_t)rho << RB) + (RB >= 5 ? ((uint32_t)rho << (RB >= 5 ? RB - 5 : 0)) : ((uint32_t)rho >> (RB >= 5 ? 0 : 5 - RB)));
+}
+
+template <bool CANON>
+__global__ __launch_bounds__(kBlock) void lde_fused12_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
+                                                             size_t out_stride, const uint32_t* __restrict__ tw, uint32_t hinv) {
+    __shared__ uint32_t tile[(1 << 13) + ((1 << 13) >> 5)];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t* src = in + (size_t)blockIdx.y * in_stride + ((size_t)blockIdx.x << 12);
+    uint32_t* dst = out + (size_t)blockIdx.y * out_stride + ((size_t)blockIdx.x << 13);
+    uint32_t x[16], tt[16], tn[16];
+    // ---- A ----
+#pragma unroll
+    for (int rho = 0; rho < 16; ++rho) x[rho] = src[tid + 256u * rho];
+#pragma unroll
+    for (int j = 0; j < 15; ++j) tt[j] = tw[kF12A0 + 256u * j + tid];
+#pragma unroll
+    for (int j = 0; j < 15; ++j) tn[j] = tw[kF12A1 + 16u * j + (tid & 15u)];
+    slot_butterflies<true, 4, true>(x, 0u, tt);
+    {
+        const uint32_t p0 = lds_phys(tid);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) tile[p0 + f12_off<8>(rho)] = x[rho];
+    }
+    __syncthreads();
+    // ---- B ----
+    {
+        // slot = (k, low), elements 256 k + 16 rho + low; low = lane bits 0-3, and k takes lane bits 4 and 5 SWAPPED: a half-wave
+        // then holds k0 and k0 + 2, whose runs of 16 words lie 528 = 16 (mod 32) words apart (k0, k0 + 1: 264 = 8, a 2-way conflict)
+        const uint32_t k = ((tid >> 5) & 1u) | (((tid >> 4) & 1u) << 1) | ((tid >> 6) << 2);
+        const uint32_t p0 = lds_phys((k << 8) | (tid & 15u));
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + f12_off<4>(rho)];
+        slot_butterflies<true, 4, true>(x, 0u, tn);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) tile[p0 + f12_off<4>(rho)] = x[rho];
+    }
+    __syncthreads();
+    // ---- C ----
+    {
+        const uint32_t p0 = lds_phys(tid << 4);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + (uint32_t)rho];
+#pragma unroll
+        for (int j = 0; j < 15; ++j) tn[j] = tw[kF12D1 + 32u * j + (tid & 31u)];  // for E
+#pragma unroll
+        for (int j = 0; j < 15; ++j) tt[j] = tw[kF12A2 + j];
+        slot_butterflies<true, 4, true>(x, 0u, tt);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[rho] = bb::mul(x[rho], hinv);
+    }
+    __syncthreads();
+    // ---- D ----
+    {
+        const uint32_t p0 = lds_phys(tid << 5);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            uint32_t y[16];
+#pragma unroll
+            for (int rho = 0; rho < 16; ++rho) y[rho] = x[rho];
+#pragma unroll
+            for (int j = 0; j < 15; ++j) tt[j] = tw[kF12D0 + 2u * j + b];
+            slot_butterflies<false, 4, true>(y, 0u, tt);
+#pragma unroll
+            for (int rho = 0; rho < 16; ++rho) tile[p0 + 2u * rho + b] = y[rho];
+        }
+    }
+    __syncthreads();
+    // ---- E ----
+    uint32_t tf[2][16];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+#pragma unroll
+        for (int j = 0; j < 15; ++j) tf[m][j] = tw[kF12D2 + 512u * j + tid + 256u * m];  // for F
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const uint32_t sigma = tid + 256u * m;
+        const uint32_t p0 = lds_phys(((sigma >> 5) << 9) | (sigma & 31u));
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + f12_off<5>(rho)];
+        slot_butterflies<false, 4, true>(x, 0u, tn);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) tile[p0 + f12_off<5>(rho)] = x[rho];
+    }
+    __syncthreads();
+    // ---- F ----
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const uint32_t sigma = tid + 256u * m;
+        const uint32_t p0 = lds_phys(sigma);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + f12_off<9>(rho)];
+        slot_butterflies<false, 4, true>(x, 0u, tf[m]);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) dst[sigma + 512u * rho] = CANON ? bb::reduce_2p(x[rho]) : x[rho];
+    }
+}
+
 struct Tables {
     uint32_t* tw_fwd = nullptr;    // g_n^j, j < 2^(n-1)
     uint32_t* tw_inv = nullptr;    // g_n^-j
@@ -797,10 +921,15 @@ __global__ void expand_small_kernel(const uint32_t* in, uint32_t* out, size_t in
 
 template <bool DIF>
 void launch_groups(std::vector<GroupParams>& groups, int logt, const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride,
-                   uint32_t cols, int n, const uint32_t* tw, const char* name) {
+                   uint32_t cols, int n, const uint32_t* tw, const char* name, const uint32_t* coset_pw = nullptr) {
     const uint32_t* src = in;
     size_t src_stride = in_stride;
     for (auto& g : groups) {
+        // coset_pw (the LDE behind lde_fused12_kernel): pw[e] = s^(2^e); the twiddles of stage s carry s^(2^(n-1-s)) (GroupParams::cst)
+        if (coset_pw) {
+            g.coset = 1;
+            for (int r = 0; r < g.n_rounds; ++r) g.cst[r] = coset_pw[n - 1 - (g.s0 + g.rb[r] + g.logr[r] - 1 - g.c)];
+        }
         const size_t tiles = (size_t)1 << (n - g.B);
         const size_t per_wg = (size_t)1 << (logt - g.B);  // (balanced plans: every group on the plan's tile size)
         const unsigned wgs = (unsigned)((tiles + per_wg - 1) / per_wg);
@@ -862,10 +991,46 @@ const FusedTwiddles* fused_twiddles(int ka, const GroupParams& ga, const GroupPa
     return &g_fused_tw.emplace(std::make_pair(device, ka), ft).first->second;
 }
 
+// The specialised kernel's table for height 2^n (lde_fused12_kernel): the two groups' tables at fixed offsets, the forward ones
+// with the coset constant of their stage folded in — stage s of the size-2^(n+1) transform carries s^(2^(n-s)), so unlike
+// FusedTwiddles this table depends on the height. pw[e] = s^(2^e), e <= n.
+std::map<std::pair<int, int>, uint32_t*> g_fused12_tw;  // (device, n)
+
+const uint32_t* fused12_twiddles(int n, const GroupParams& ga, const GroupParams& gd, const uint32_t* pw) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return nullptr;
+    auto it = g_fused12_tw.find({device, n});
+    if (it != g_fused12_tw.end()) return it->second;
+    std::vector<uint32_t> h;
+    unsigned dif_off[4] = {0, 0, 0, 0}, dit_off[4] = {0, 0, 0, 0};
+    append_group_table(h, ga, true, dif_off, 0);
+    if (h.size() > kF12D0) return nullptr;
+    h.resize(kF12D0, 0u);
+    append_group_table(h, gd, false, dit_off, kF12D0);
+    if (dif_off[0] != kF12A0 || dif_off[1] != kF12A1 || dif_off[2] != kF12A2 || dit_off[0] != 0 || kF12D0 + dit_off[1] != kF12D1 ||
+        kF12D0 + dit_off[2] != kF12D2 || h.size() != kF12Words)
+        return nullptr;  // the kernel's constants and the planner disagree
+    for (int r = 0; r < gd.n_rounds; ++r) {
+        const size_t G = (size_t)1 << gd.rb[r];
+        uint32_t* tab = h.data() + kF12D0 + dit_off[r];
+        for (int q = 0; q < gd.logr[r]; ++q) {
+            const uint32_t cq = pw[n - (gd.s0 + gd.rb[r] - gd.c + q)];
+            for (size_t i = (((size_t)1 << q) - 1) * G; i < (((size_t)2 << q) - 1) * G; ++i) tab[i] = bb::mul(tab[i], cq);
+        }
+    }
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, h.size() * 4) != hipSuccess) return nullptr;
+    if (hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;  // synchronous: published complete
+    g_fused12_tw.emplace(std::make_pair(device, n), d);
+    return d;
+}
+
 // The whole LDE of `cols` columns: natural-order evaluations on <g_n> (in) -> natural-order evaluations on the coset
 // s <g_(n+1)> (out), through the fused middle kernel: strided DIF groups (stages 0 .. n-13, into `tmp`, which needs
-// cols x 2^n words and is untouched when n <= 12), lde_fused_kernel (the 12 contiguous DIF stages, scaling, duplication,
-// 12 contiguous DIT stages), strided DIT groups in place on `out`. Same values as intt_dif + coset_lde_from_coeffs.
+// cols x 2^n words and is untouched when n <= 12), the fused kernel (the 12 contiguous DIF stages, scaling, duplication,
+// 12 contiguous DIT stages: lde_fused12_kernel from 2^12 rows up, the generic lde_fused_kernel below), strided DIT groups in
+// place on `out`. Same values as intt_dif + coset_lde_from_coeffs.
 int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride, size_t tmp_stride, size_t out_stride, uint32_t cols, int n) {
     if (n == 0) {
         int rc = intt_dif(in, tmp, in_stride, tmp_stride, cols, n);
@@ -875,6 +1040,9 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
     const Tables* t1 = tables(n + 1);
     if (!tn || !t1) return (int)hipErrorOutOfMemory;
     const int ka = n < 12 ? n : 12;
+    const char* force_generic = getenv("POWDR_LDE_FUSED_GENERIC");
+    const bool spec12 = ka == 12 && !(force_generic && atoi(force_generic) != 0);
+    const uint32_t hinv = bb::inv(bb::to_monty((uint32_t)(((uint64_t)1 << n) % bb::P)));
     const uint32_t* src = in;
     size_t src_stride = in_stride;
     if (n > ka) {
@@ -887,10 +1055,27 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
     GroupParams ga = contiguous_group(true, n, n - ka, ka, 0);
     GroupParams gd = contiguous_group(false, n + 1, 1, ka, 1);
     gd.canonical_out = ka == n ? 1 : 0;
-    const FusedTwiddles* ft = fused_twiddles(ka, ga, gd);
-    if (!ft) return (int)hipErrorOutOfMemory;
-    for (int r = 0; r < 4; ++r) { ga.twt_off[r] = ft->dif_off[r]; gd.twt_off[r] = ft->dit_off[r]; }
-    {
+    // from 2^12 rows up the kernel specialised for the 12 + 12 geometry, which takes the coset scaling in its (and the strided DIT
+    // groups') twiddles; POWDR_LDE_FUSED_GENERIC=1 keeps the generic kernel at every height
+    uint32_t coset_pw[33];
+    if (spec12) {
+        coset_pw[0] = bb::to_monty(field::kCosetShift);
+        for (int e = 1; e <= n; ++e) coset_pw[e] = bb::sqr(coset_pw[e - 1]);
+        const uint32_t* tw12 = fused12_twiddles(n, ga, gd, coset_pw);
+        if (!tw12) return (int)hipErrorOutOfMemory;
+        const unsigned wgs = 1u << (n - 12);
+        for (uint32_t c0 = 0; c0 < cols; c0 += 65535u) {
+            const uint32_t cc = cols - c0 < 65535u ? cols - c0 : 65535u;
+            ScopedKernelTimer t("lde_fused_kernel");
+            const uint32_t* s_ = src + (size_t)c0 * src_stride;
+            uint32_t* d_ = out + (size_t)c0 * out_stride;
+            if (n == 12) hipLaunchKernelGGL(lde_fused12_kernel<true>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
+            else hipLaunchKernelGGL(lde_fused12_kernel<false>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
+        }
+    } else {
+        const FusedTwiddles* ft = fused_twiddles(ka, ga, gd);
+        if (!ft) return (int)hipErrorOutOfMemory;
+        for (int r = 0; r < 4; ++r) { ga.twt_off[r] = ft->dif_off[r]; gd.twt_off[r] = ft->dit_off[r]; }
         const size_t tiles = (size_t)1 << (n - ka);
         const size_t per_wg = (size_t)1 << (12 - ka);
         const unsigned wgs = (unsigned)((tiles + per_wg - 1) / per_wg);
@@ -930,7 +1115,8 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
         int logt = 12;
         auto groups = plan_groups(false, n + 1, ka + 1, logt, n + 1, true);
         if (!groups.empty()) groups.back().canonical_out = 1;
-        launch_groups<false>(groups, logt, out, out, out_stride, out_stride, cols, n + 1, t1->tw_fwd, "ntt_group_kernel<dit>");
+        launch_groups<false>(groups, logt, out, out, out_stride, out_stride, cols, n + 1, t1->tw_fwd, "ntt_group_kernel<dit>",
+                             spec12 ? coset_pw : nullptr);
     }
     return (int)hipGetLastError();
 }
