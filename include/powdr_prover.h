@@ -148,6 +148,71 @@ int pw_trace_from_coefficients(uint32_t* d_coeffs, uint32_t width, uint32_t log_
 int pw_prover_check_constraints(PwProver* p, const uint32_t* d_trace, uint32_t log_height, uint64_t* n_violations,
                                 uint64_t* first_row, uint32_t* first_constraint);
 
+/* The other half of the mock prover: are the BUSES of a segment balanced, tuple by tuple — what `debug_proving_ctx`
+ * checks besides the constraints — evaluated on the raw traces, nothing committed, and if not, WHICH tuples are left over.
+ * A TUPLE is (bus, n_args, args...): two tuples are equal only when the bus, the number of arguments and every argument are equal,
+ * the reference's rule (it compares the field vectors of the interactions). That is deliberately STRICTER than the LogUp sum of a
+ * proof, in which (a, b) and (a, b, 0) have the same denominator: a sender of (a, b) and a receiver of (a, b, 0) verify with
+ * check_balance and are reported here as two unbalanced tuples. A bus is balanced when for every tuple the multiplicities — over all
+ * AIRs, interactions and rows, padding rows included; sends + m, receives - m as everywhere in this header — sum to 0 mod p.
+ * Interactions are evaluated exactly as the prover evaluates them: current-row operands below width + pre_width, operands >= width
+ * from the prover's fixed matrix (as pw_prover_check_constraints arranges it). A prover made without interaction tables contributes
+ * nothing. Bus ids are compared mod p (as the provers hold them).
+ *   airs / n_airs     as for pw_prove_segment (flags ignored; nothing is handed over; at most 2^18 AIRs of at most 2^20 interactions,
+ *                     2^26 rows). A preprocessed prover at another height than its own, or one that occurs twice in the list: -1.
+ *   buses / n_buses   the bus ids to check (duplicates count once); n_buses == 0: every bus id that occurs in the provers' tables.
+ *   seed              the two challenges of pass A and of the fingerprints are derived from it. NOTHING reported depends on it.
+ *   table_bytes       the most device bytes the tally table of ONE bus may take (40 per slot, a power of two of slots); 0: half of
+ *                     what pw_get_device_budget / the free memory allow. A bus starts with 2^16 slots (2.6 MB) and is tallied again
+ *                     into a table four times as large while it overflows, up to this bound (never beyond twice its active triples).
+ *                     A table holds 7/8 of its slots in tuples (so that probing stays short): give a bus you know 8/7 of its
+ *                     distinct tuples, rounded up to a power of two.
+ *   flags             PW_BUS_CHECK_TALLY_ALL: run the tuple tally for the buses pass A found balanced too.
+ *   summaries         one per checked bus, ordered by bus id; summary_cap smaller than their number: -1 (n_buses == 0: as many
+ *                     as there are distinct ids; otherwise as many as distinct entries of `buses`). NULL with summary_cap 0: skipped.
+ *   tuples            the unbalanced tuples ordered by (bus, n_args, args lexicographically on canonical words), truncated at
+ *                     tuple_cap (n_unbalanced of the summaries keeps the full count). NULL with tuple_cap 0: skipped.
+ * Pass A (always): per bus sum m / (alpha + sum_j beta^(j+1) a_j + beta^(n+1) n) over everything, in the extension field; zero
+ * <=> balanced up to the soundness of LogUp itself (below 2^-90 for a bus of 2^26 tuples and a seed chosen independently of the traces:
+ * DESIGN.md §5i). Pass B (unbalanced buses, or all): an exact tally per tuple in a device hash table keyed by the 124-bit fingerprint;
+ * a bound too small for a bus — or a table the device cannot allocate — gives that bus status 2: never an error, never a wrong
+ * answer, and (allocation failures apart) the same status every time for the same table_bytes. Where pass B
+ * ran without overflowing, its verdict is the one reported. The sum of a tuple's centred multiplicities is kept in 64 bits: exact
+ * for fewer than 2^33 contributions per tuple.
+ * Nothing the caller or the provers own is modified (a preprocessed prover's staging copy of the trace is rewritten, as by a proof).
+ * Stream contract as pw_prove_segment: the calling thread's launch stream; the call synchronises before it returns. Malformed
+ * arguments return -1 before any GPU call. Scratch is per host thread: the table and the tuple lists are released before the call
+ * returns, also when it returns an error; some twenty kilobytes of tables stay (pw_bus_check_scratch_bytes: held now; pw_bus_check_peak_bytes: the most the thread's last
+ * call held at once), and every prover keeps 4 bytes per interaction (counted by pw_prover_device_bytes) from its first check on. */
+#define PW_BUS_MAX_ARGS 16u
+#define PW_BUS_CHECK_TALLY_ALL 1u   /* flags: run the tuple tally for balanced buses too (tests, statistics) */
+
+typedef struct PwBusSummary {
+    uint32_t bus;
+    uint32_t status;         /* 0 balanced; 1 unbalanced, tuples listed; 2 unbalanced, tally table too small: not localised */
+    uint64_t n_active;       /* (air, interaction, row) triples with a non-zero multiplicity on this bus */
+    uint64_t n_unbalanced;   /* distinct tuples whose multiplicities do not sum to 0 mod p (0 when status is 0 or 2) */
+} PwBusSummary;
+
+typedef struct PwBusTuple {
+    uint32_t bus, n_args;
+    uint32_t args[PW_BUS_MAX_ARGS];  /* canonical words; the first 16 of a longer tuple (n_args keeps the real length) */
+    uint32_t net_multiplicity;       /* canonical, non-zero: the sum of all multiplicities that carried this tuple */
+    uint32_t air, interaction;       /* a witness: the lexicographically smallest (air, interaction, row) that contributed */
+    uint64_t row;
+    uint64_t n_contributions;
+} PwBusTuple;
+
+struct PwSegmentAir; /* below: "one segment = many AIRs" */
+int pw_check_segment_buses(const struct PwSegmentAir* airs, size_t n_airs,
+                           const uint32_t* buses, size_t n_buses,   /* n_buses == 0: every bus id that occurs */
+                           uint64_t seed, size_t table_bytes,       /* 0: a default bounded by pw_get_device_budget / free memory */
+                           uint32_t flags,
+                           PwBusSummary* summaries, size_t summary_cap, size_t* n_summaries,
+                           PwBusTuple* tuples, size_t tuple_cap, size_t* n_tuples);
+size_t pw_bus_check_scratch_bytes(void);
+size_t pw_bus_check_peak_bytes(void);
+
 /* Verify a proof on the host (no GPU): the counterpart of the reference's CPU verification step
  * `verify_app_proof::<BabyBearPoseidon2CpuEngine>` (openvm-riscv/src/lib.rs:337-341). Constraint
  * programs as for pw_prover_create (post-fix, column-index operands, no INV_OR_ZERO).

@@ -5,12 +5,13 @@
 #include "xbc.hpp"
 #include "expr_eval.hpp"
 #include "jit_device.hpp"
+#include "logup_eval.hpp"
 
 namespace pw {
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kLogupBlock;
 using bb::Ext;
 
 // d_i = al + bus_i + sum_j bl^(j+1) a_ij on row r of matrix `m` (column stride `stride`).
@@ -20,21 +21,7 @@ using bb::Ext;
 // below p^2 / 2 and two of them fit the reduction's domain (1.209 p^2) on top of what is already there (<= 0.134 p^2);
 // after two products the accumulator is reduced and re-enters as r * (R mod p). Per coordinate and argument ~3.5
 // instructions where a Montgomery product and a modular addition took 8.
-// One multiplicity / argument on row r. FAST: the span's small form (k0 + k1 A + k2 B + k3 A B, fixed code, both loads issued at
-// once, ~10 scalar instructions); else the xbc interpreter (a scalar decode of ~15 instructions per xbc instruction on the
-// CU's one scalar unit, which is what bounds these kernels when it runs: PMC profiles/r02_pmc_logup_kernels.txt).
-template <bool FAST>
-__device__ __forceinline__ uint32_t eval_span(const LogupProgram& lp, uint32_t span, const uint32_t* __restrict__ m, size_t stride,
-                                              size_t r, uint32_t* stk) {
-    if (FAST && !(lp.d_forms[span].flags & SmallForm::NOT_SMALL)) {
-        const SmallForm f = lp.d_forms[span];
-        const uint32_t ta = (f.flags & SmallForm::USES_A) ? m[(size_t)f.a * stride + r] : 0u;
-        const uint32_t tb = (f.flags & SmallForm::USES_B) ? m[(size_t)f.b * stride + r] : 0u;
-        return f.eval(ta, tb);
-    }
-    const uint32_t off = lp.d_xspans[2 * span], len = lp.d_xspans[2 * span + 1];
-    return xbc::eval<kBlock, true>(lp.d_code + 2 * (size_t)off, len, m, r, stk, stride);
-}
+// (one multiplicity / argument on row r: eval_span, logup_eval.hpp)
 
 using pwj::DenominatorSeeds;
 using pwj::denominator_seeds;

@@ -585,7 +585,7 @@ static PwProver::OpenedMailbox* opened_mailbox(PwProver* p, size_t K) {
 extern "C" void pw_prover_destroy(PwProver* p) {
     if (!p) return;
     for (DeviceBuf* b : {&p->coef, &p->lde, &p->digests, &p->q, &p->qcoef, &p->qlde, &p->ext_arena, &p->misc, &p->perm, &p->plde, &p->qpart, &p->tcoef,
-                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree, &p->row_vals})
+                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree, &p->row_vals, &p->bus_order})
         b->release();
     if (p->d_next_cols) (void)hipFree(p->d_next_cols);
     for (void* q : {(void*)p->d_inter, (void*)p->d_ixspans, (void*)p->d_icode, (void*)p->d_gstarts, (void*)p->d_iforms}) if (q) (void)hipFree(q);
@@ -620,7 +620,7 @@ extern "C" int pw_prover_stream_log_blocks(const PwProver* p, uint32_t log_h) {
 extern "C" size_t pw_prover_device_bytes(const PwProver* p) {
     return p->coef.bytes + p->lde.bytes + p->digests.bytes + p->q.bytes + p->qcoef.bytes + p->qlde.bytes +
            p->ext_arena.bytes + p->misc.bytes + p->perm.bytes + p->plde.bytes + p->qpart.bytes + p->tcoef.bytes + p->fscale.bytes + p->gbuf.bytes +
-           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes + p->row_vals.bytes;
+           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes + p->row_vals.bytes + p->bus_order.bytes;
 }
 
 

@@ -86,6 +86,10 @@ struct PwProver {
     uint32_t* d_icode = nullptr;
     pw::SmallForm* d_iforms = nullptr;  // all spans as small forms, when every one of them is one (else nullptr)
     pw::DeviceBuf perm, plde;
+    // the bus mock prover (bus_check.hip), made at its first use of this prover: the interaction indices ordered by
+    // (bus id, index) on the device, and per distinct bus id (ascending) where its run starts in that order (+ the end)
+    pw::DeviceBuf bus_order;
+    std::vector<uint32_t> h_bus_order, h_bus_ids, h_bus_starts;
     bool has_bus_seed = false;
     uint32_t bus_seed[8] = {0};  // Montgomery
     // pw_prover_trace_root leaves the trace's LDE and Merkle tree in `lde` / `digests`; a pw_prover_prove of the

@@ -21,7 +21,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
                   "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables",
                   "pw_prover_create_preprocessed", "pw_prover_preprocessed_root", "pw_prover_preprocessed_width", "pw_verify_segment_preprocessed",
-                  "pw_prover_create_transition", "pw_prover_row_flags", "pw_verify_segment_transition"]
+                  "pw_prover_create_transition", "pw_prover_row_flags", "pw_verify_segment_transition",
+                  "pw_check_segment_buses", "pw_bus_check_scratch_bytes", "pw_bus_check_peak_bytes", "pw_bus_check_last_stats"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -270,6 +271,79 @@ def prove_segment(airs, logup: bool = False, copy: bool = True, hand_over=None) 
         abi.check(lib.pw_prove_segment_consuming(recs, n, int(logup), C.byref(words), C.byref(nw)), "pw_prove_segment_consuming")
     a = np.ctypeslib.as_array(words, shape=(nw.value,))
     return a.copy() if copy else a
+
+
+PW_BUS_MAX_ARGS = 16
+PW_BUS_CHECK_TALLY_ALL = 1
+
+
+class PwBusSummary(C.Structure):
+    _fields_ = [("bus", C.c_uint32), ("status", C.c_uint32), ("n_active", C.c_uint64), ("n_unbalanced", C.c_uint64)]
+
+
+class PwBusTuple(C.Structure):
+    _fields_ = [("bus", C.c_uint32), ("n_args", C.c_uint32), ("args", C.c_uint32 * PW_BUS_MAX_ARGS), ("net_multiplicity", C.c_uint32),
+                ("air", C.c_uint32), ("interaction", C.c_uint32), ("row", C.c_uint64), ("n_contributions", C.c_uint64)]
+
+
+lib.pw_check_segment_buses.restype = C.c_int
+lib.pw_check_segment_buses.argtypes = [C.POINTER(PwSegmentAir), C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint32,
+                                       C.POINTER(PwBusSummary), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(PwBusTuple), C.c_size_t,
+                                       C.POINTER(C.c_size_t)]
+lib.pw_bus_check_scratch_bytes.restype = C.c_size_t
+lib.pw_bus_check_scratch_bytes.argtypes = []
+lib.pw_bus_check_peak_bytes.restype = C.c_size_t
+lib.pw_bus_check_peak_bytes.argtypes = []
+lib.pw_bus_check_last_stats.restype = None
+lib.pw_bus_check_last_stats.argtypes = [C.POINTER(C.c_uint64)] * 4  # (a diagnostic of the library for tools/bench_bus_check.py, not in the header)
+
+
+def check_segment_buses(airs, buses=None, seed: int = 0, table_bytes: int = 0, tally_all: bool = False, tuple_cap: int = 1024):
+    """pw_check_segment_buses, the bus half of the mock prover: airs = [(Prover, device trace pointer, log_height)] as
+    for prove_segment; buses = the bus ids to check (None: every id that occurs). Returns (summaries, tuples):
+    summaries, by bus id: dict(bus, status, n_active, n_unbalanced) — status 0 balanced, 1 unbalanced with its tuples listed,
+    2 unbalanced but the tally table (table_bytes: the most one bus's table may take; it grows to that from 2.6 MB) was too small to
+    name them;
+    tuples, by (bus, n_args, args): dict(bus, n_args, args (canonical, the first 16), net_multiplicity, air, interaction, row,
+    n_contributions) — at most tuple_cap of them, the first in that order. A tuple is (bus, n_args, args): (a, b) is not (a, b, 0)."""
+    n = len(airs)
+    recs = (PwSegmentAir * max(n, 1))()
+    for i, (pr, ptr, lh) in enumerate(airs):
+        recs[i] = PwSegmentAir(pr._h, ptr, lh, 0)
+    ids = None if buses is None else np.ascontiguousarray(sorted(set(int(b) for b in buses)), dtype=np.uint32)
+    if ids is not None and len(ids) == 0:
+        return [], []
+    cap = len(ids) if ids is not None else 4096  # (more distinct bus ids than that: -1)
+    sums = (PwBusSummary * cap)()
+    tups = (PwBusTuple * max(tuple_cap, 1))()
+    ns, nt = C.c_size_t(), C.c_size_t()
+    rc = lib.pw_check_segment_buses(recs, n, None if ids is None else _vp(ids), 0 if ids is None else len(ids), int(seed) & (2**64 - 1),
+                                    int(table_bytes), PW_BUS_CHECK_TALLY_ALL if tally_all else 0, sums, cap, C.byref(ns),
+                                    tups if tuple_cap else None, tuple_cap, C.byref(nt))
+    abi.check(rc, "pw_check_segment_buses")
+    summaries = [dict(bus=int(s.bus), status=int(s.status), n_active=int(s.n_active), n_unbalanced=int(s.n_unbalanced)) for s in sums[:ns.value]]
+    tuples = [dict(bus=int(t.bus), n_args=int(t.n_args), args=[int(x) for x in t.args[:min(t.n_args, PW_BUS_MAX_ARGS)]],
+                   net_multiplicity=int(t.net_multiplicity), air=int(t.air), interaction=int(t.interaction), row=int(t.row),
+                   n_contributions=int(t.n_contributions)) for t in tups[:nt.value]]
+    return summaries, tuples
+
+
+def bus_check_scratch_bytes() -> int:
+    """device bytes this thread's bus-check scratch holds now (the tally table and the tuple lists are released after every call)"""
+    return int(lib.pw_bus_check_scratch_bytes())
+
+
+def bus_check_peak_bytes() -> int:
+    """the most device bytes this thread's last check_segment_buses held at once (both passes)"""
+    return int(lib.pw_bus_check_peak_bytes())
+
+
+def bus_check_last_stats() -> dict:
+    """of this thread's last check_segment_buses: slots of the largest tally table, most slots occupied in one, triples inserted,
+    tables tallied into (the attempts that overflowed included)"""
+    a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.pw_bus_check_last_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return dict(table_slots=a.value, occupied_slots=b.value, inserted=c.value, tables=d.value)
 
 
 def segment_last_modes():

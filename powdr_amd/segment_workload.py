@@ -501,6 +501,13 @@ class HonestSegment:
         """the device's mock prover on the current traces: violated (row, constraint) pairs over all AIRs"""
         return sum(a["prover"].check_constraints(a["trace"].data_ptr(), a["log_h"])[0] for a in self.airs if len(a["cons"][1]))
 
+    def check_buses(self, buses=LOOKUP_BUSES, **kw):
+        """The bus half of the mock prover on the current traces (prover.check_segment_buses): per bus whether every
+        tuple's multiplicities cancel and, where not, which tuples are left over and where one of them was sent. buses=None: every bus
+        (memory, execution bridge and pc lookup have only senders here: unbalanced by construction). The segment's own provers serve;
+        the provers need their interaction tables (logup=True)."""
+        return prover.check_segment_buses(self.seg, buses=buses, **kw)
+
     def balance_witness(self):
         """The lookup buses (3 var-range, 6 bitwise, 7 tuple) have their senders AND receivers in this segment: the same traces,
         every AIR restricted to those buses, proven and verified with check_balance — the senders' LogUp sums and the periphery AIRs'

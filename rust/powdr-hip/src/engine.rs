@@ -136,6 +136,33 @@ impl HipEngine {
         Ok(HipSegmentProof { air_ids, log_heights, words })
     }
 
+    /// The bus half of `debug_proving_ctx` (`prove_mock`, openvm-riscv/src/lib.rs:288-294) on the device: every bus of the segment
+    /// balanced tuple by tuple, or the tuples that are not, each with the (air, interaction, row) of one contribution. Nothing is
+    /// committed; `bus_ids` empty = every bus the AIRs mention. `air` of a tuple indexes the AIRs of `ctx` with a non-empty trace.
+    pub fn debug_segment_buses(&self, ctx: &ProvingContext<HipBackend>, bus_ids: &[u32], tuple_cap: usize)
+                               -> Result<(Vec<ffi::PwBusSummary>, Vec<ffi::PwBusTuple>), HipError> {
+        let airs: Vec<ffi::PwSegmentAir> = ctx.per_trace.iter().filter(|(_, c)| c.common_main.height() != 0).map(|(air_id, c)| {
+            let m: &DeviceMatrix<BabyBear> = &c.common_main;
+            ffi::PwSegmentAir {
+                prover: self.provers[*air_id].handle,
+                d_trace: m.buffer().as_ptr() as *const u32,
+                log_height: m.height().trailing_zeros(),
+                flags: 0,
+            }
+        }).collect();
+        let mut summaries = vec![ffi::PwBusSummary::default(); if bus_ids.is_empty() { 4096 } else { bus_ids.len() }];
+        let mut tuples = vec![ffi::PwBusTuple::default(); tuple_cap];
+        let (mut n_summaries, mut n_tuples) = (0usize, 0usize);
+        HipError::from_result(unsafe {
+            ffi::pw_check_segment_buses(airs.as_ptr(), airs.len(), bus_ids.as_ptr(), bus_ids.len(), 0, 0, 0, summaries.as_mut_ptr(),
+                                        summaries.len(), &mut n_summaries,
+                                        if tuple_cap == 0 { core::ptr::null_mut() } else { tuples.as_mut_ptr() }, tuple_cap, &mut n_tuples)
+        })?;
+        summaries.truncate(n_summaries);
+        tuples.truncate(n_tuples);
+        Ok((summaries, tuples))
+    }
+
     /// The CPU verification step (`verify_app_proof::<BabyBearPoseidon2CpuEngine>`, openvm-riscv/src/lib.rs:337-341)
     pub fn verify_segment(&self, programs: &[AirProgram], proof: &HipSegmentProof) -> Result<(), i32> {
         let descs: Vec<ffi::PwAirDescription> = proof

@@ -261,6 +261,31 @@ pub struct PwSegmentAir {
 }
 /// `PwSegmentAir::flags`: the trace is the engine's to overwrite
 pub const PW_AIR_HAND_OVER: u32 = 1;
+/// `PwBusTuple::args` holds the first 16 words of a tuple
+pub const PW_BUS_MAX_ARGS: usize = 16;
+/// `pw_check_segment_buses` flags: run the tuple tally for balanced buses too
+pub const PW_BUS_CHECK_TALLY_ALL: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwBusSummary {
+    pub bus: u32,
+    /// 0 balanced; 1 unbalanced, tuples listed; 2 unbalanced, tally table too small: not localised
+    pub status: u32,
+    pub n_active: u64,
+    pub n_unbalanced: u64,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwBusTuple {
+    pub bus: u32,
+    pub n_args: u32,
+    pub args: [u32; PW_BUS_MAX_ARGS],
+    pub net_multiplicity: u32,
+    pub air: u32,
+    pub interaction: u32,
+    pub row: u64,
+    pub n_contributions: u64,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct PwAirDescription {
@@ -320,6 +345,12 @@ extern "C" {
     pub fn pw_trace_from_coefficients(d_coeffs: *mut u32, width: u32, log_height: u32, d_scratch: *mut u32) -> c_int;
     pub fn pw_prover_check_constraints(p: *mut PwProver, d_trace: *const u32, log_height: u32, n_violations: *mut u64,
                                        first_row: *mut u64, first_constraint: *mut u32) -> c_int;
+    /// the bus half of the mock prover (`debug_proving_ctx`): per bus balanced or not, and the unbalanced tuples with a witness each
+    pub fn pw_check_segment_buses(airs: *const PwSegmentAir, n_airs: usize, buses: *const u32, n_buses: usize, seed: u64,
+                                  table_bytes: usize, flags: u32, summaries: *mut PwBusSummary, summary_cap: usize,
+                                  n_summaries: *mut usize, tuples: *mut PwBusTuple, tuple_cap: usize, n_tuples: *mut usize) -> c_int;
+    pub fn pw_bus_check_scratch_bytes() -> usize;
+    pub fn pw_bus_check_peak_bytes() -> usize;
     pub fn pw_verify(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32, bytecode_len: usize,
                      cons_spans: *const u32, n_constraints: usize, proof_words: *const u32, n_words: usize) -> c_int;
     pub fn pw_verify_logup(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32,
