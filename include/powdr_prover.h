@@ -283,6 +283,57 @@ void pw_segment_last_plan(size_t* resident_bytes, size_t* planned_bytes, size_t*
  * planned bytes of pw_segment_last_plan. */
 size_t pw_segment_context_bytes(void);
 
+/* ---- closing a segment's buses: the traces of the program and memory boundary AIRs ------------------------------
+ * The receivers of the PC lookup and of the memory bus are AIRs like any other (powdr_amd/system_airs.py gives their programs);
+ * their traces depend on everything the other AIRs send, and these two routines make them on the device from the other AIRs' raw
+ * traces. Both take the AIR list of pw_check_segment_buses (same refusals: -1 before any GPU call), read the interactions on ONE bus
+ * through the provers' own programs exactly as that check does (operands >= width from the prover's fixed matrix; a preprocessed
+ * prover's staging copy of the trace is rewritten), modify nothing else of the caller's, run on the calling thread's launch stream
+ * and synchronise before they return. Scratch is per host thread and released before the call returns, on every path, but for a
+ * few kilobytes (pw_system_traces_scratch_bytes: held now; pw_system_traces_peak_bytes: the most the thread's last call held).
+ *
+ * pw_program_frequencies: d_freq_out[k] (2^log_h words, Montgomery) = the sum mod p of the multiplicities of all tuples on `bus`
+ * that equal row k of the program table d_program (9 x 2^log_h, column-major, Montgomery: pc, opcode, a .. g), where
+ * k = (pc - pc_base) / pc_step — the main column of the program AIR, which receives each row `freq` times. A tuple is FOREIGN when
+ * its pc is below pc_base, not a multiple of pc_step away from it, past the table, when it has not nine arguments or differs from
+ * its row in any word: foreign tuples are never dropped silently — *n_foreign counts them and *first_foreign (may be NULL) is the
+ * one with the smallest (air, interaction, row), with its own multiplicity in net_multiplicity — and never counted in d_freq_out.
+ * The sums are integer additions (64 bits: exact below 2^32 contributions per row), so the output does not depend on their order.
+ *
+ * pw_memory_boundary_trace: the trace of the memory boundary AIR — one row per touched location (as, ptr), sorted, 18 columns
+ * [is_valid, as, ptr, p_lo, p_hi, init0..3, init_ts, fin0..3, fin_ts, same_as, d_lo, d_hi], column-major, 2^*log_height rows,
+ * Montgomery, padding rows zero — from the tuples (as, ptr, four data words, timestamp) on `bus`: a location's initial words and
+ * timestamp are those of the receive (multiplicity -1) with the smallest timestamp, its final ones those of the send (+1) with the
+ * largest; ties go to the smallest (air, interaction, row), so the output does not depend on the order of arrival. An interaction
+ * on `bus` that has not seven arguments: -1. d_trace_out holds 18 x 2^cap_log_height words; *log_height = ceil(log2 *n_locations),
+ * at least 1. table_bytes bounds the address table (40 bytes per slot, grown from 2^16 slots by 4 while it overflows, full at 7/8,
+ * as the tally table of pw_check_segment_buses; 0: half of what the device budget allows). *status: 0 = written; 1 = cap_log_height
+ * too small (*n_locations and *log_height say what is needed); 2 = the table bound too small; 3 = a multiplicity on the bus that is
+ * not +1 or -1; 4 = a location with only receives or only sends. With a status other than 0 nothing is written and 0 is returned.
+ * The routine does NOT prove that memory was consistent — a read that returns what nobody wrote still gets its first receive and last
+ * send paired up: run pw_check_segment_buses on the bus with the boundary AIR in the list afterwards (pass A is the cheap verdict,
+ * pass B names the two tuples of a broken link). */
+int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_t pc_base, uint32_t pc_step,
+                           const uint32_t* d_program, uint32_t log_h, uint32_t* d_freq_out, uint64_t* n_foreign,
+                           PwBusTuple* first_foreign);
+int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, size_t table_bytes, uint32_t* d_trace_out,
+                             uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_locations, uint32_t* status);
+size_t pw_system_traces_scratch_bytes(void);
+size_t pw_system_traces_peak_bytes(void);
+/* What the calling thread's last calls did. Of its last pw_memory_boundary_trace: the slots of the address table kept, the slots
+ * occupied in it (= locations), the tables walked into (overflowed attempts included). Of its last call of either routine: rows x
+ * interactions walked (an upper bound of the active triples). Of its last pw_program_frequencies: the additions asked for (active
+ * triples), and the LDS and global atomics the kernel issued for them after merging. */
+typedef struct PwSystemTraceStats {
+    uint64_t table_slots, occupied_slots, tables, walked;
+    uint64_t additions, lds_atomics, global_atomics;
+} PwSystemTraceStats;
+void pw_system_traces_last_stats(PwSystemTraceStats* out);
+/* The first address table of the calling thread's later pw_memory_boundary_trace calls has 2^log_slots slots (6 .. 30; 0 = back to the
+ * default, 2^16): a caller that knows its segment touches few locations starts small, one that knows it touches millions skips the
+ * first growth steps. The result does not depend on it. -1: out of range. */
+int pw_memory_boundary_set_start_slots(uint32_t log_slots);
+
 /* Device memory ONE proof call may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
  * POWDR_DEVICE_BUDGET_BYTES read once). It is applied per call, to what that call's provers and (segments) the calling thread's
  * segment context hold: a proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove; segments:

@@ -6,36 +6,17 @@
 //                              non-zero mod p; bus_args_kernel re-evaluates the tuple words at the slots' witness rows. The table
 //                              starts small and is quadrupled (and the bus tallied again) until it holds the bus or reaches its bound
 // One lane per row, interactions evaluated by eval_span / DenominatorAcc exactly as logup_perm_kernel evaluates them.
-#include "prover_state.hpp"
-#include "logup_eval.hpp"
-
-#include <algorithm>
-#include <vector>
+#include "bus_shared.hpp"
 
 namespace pw {
 
 namespace {
 
-constexpr int kBlock = kLogupBlock;
-constexpr int kWaves = kBlock / 64;
+using namespace bus;
 using bb::Ext;
 using pwj::DenominatorSeeds;
 using pwj::denominator_seeds;
-typedef unsigned long long u64;
 
-constexpr u64 kEmpty = ~0ull;          // a key half no fingerprint can be (its words are below 2^31)
-constexpr uint32_t kRowBits = 26, kInterBits = 20, kAirBits = 18;  // the packed witness (air | interaction | row)
-constexpr size_t kSlotBytes = 40;      // key 2 x 8, sum 8, witness 8, count 8
-constexpr u64 kStartSlots = 1ull << 16;  // the first table of a bus (2.6 MB); quadrupled on overflow up to the bound
-// A table counts as full at 7/8 of its slots, so that linear probing stays short however the bound was chosen: the slots fall into
-// up to 64 classes (slot index mod the class count, at least 4096 slots each), every class counts the slots claimed in it (counters
-// 256 bytes apart: one atomic per DISTINCT tuple, spread over the memory channels) and the bus overflows when a class passes 7/8.
-constexpr u64 kMaxClasses = 64, kMinClassSlots = 4096, kLoadStride = 32;
-
-// the interactions order[begin .. end) of an AIR are those on selected bus number `slot`
-struct BusSeg { uint32_t begin, end, slot, pad; };
-// what bus_args_kernel needs of an AIR
-struct AirDev { const uint32_t* m; u64 H; LogupProgram lp; };
 struct Unbalanced { u64 witness, count; uint32_t net, pad; };
 
 // al + bus + sum_j bl^(j+1) a_j + bl^(n+1) n: the denominator of the interaction's tuple on row r with its ARITY folded in, so that
@@ -47,12 +28,6 @@ __device__ __forceinline__ Ext tuple_denominator(const LogupInteraction& it, con
     for (uint32_t j = 0; j < it.n_args; ++j) acc.add(eval_span<FAST>(lp, it.first_span + 1 + j, m, stride, r, stk), blpow[j + 1]);
     acc.add(bb::to_monty(it.n_args), blpow[it.n_args + 1]);
     return acc.result();
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // ---- pass A ---------------------------------------------------------------------------------------------------------------------
@@ -117,13 +92,6 @@ __global__ __launch_bounds__(kBlock) void bus_sum_kernel(const uint32_t* __restr
 // ---- pass B ---------------------------------------------------------------------------------------------------------------------
 struct Table { u64 *k0, *k1, *wit, *sum, *cnt; u64 mask; u64* load; u64 class_mask, class_cap; };
 
-__device__ __forceinline__ u64 slot_hash(u64 a, u64 b) {
-    u64 h = a * 0x9E3779B97F4A7C15ull ^ (b + 0x632BE59BD9B4E019ull) * 0xC2B2AE3D27D4EB4Full;
-    h ^= h >> 29;
-    h *= 0xBF58476D1CE4E5B9ull;
-    return h ^ (h >> 32);
-}
-
 // Every active (interaction, row) of ONE bus in one AIR: the slot of its tuple's fingerprint (the four words of the denominator: two
 // 64-bit key halves, each claimed by a compare-and-swap; a slot whose first half matches and whose second does not belongs to another
 // tuple: keep probing) gets the centred multiplicity added, the packed witness min-ed in and its count bumped. Keys never change once
@@ -148,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void bus_tally_kernel(const uint32_t* __res
         if (mu == 0u) continue;
         const Ext d = tuple_denominator<FAST>(it, lp, m, H, r, stk, sd, blpow);
         const u64 a = (u64)d.c[0] | ((u64)d.c[1] << 32), b = (u64)d.c[2] | ((u64)d.c[3] << 32);
-        const u64 witness = ((u64)air << (kRowBits + kInterBits)) | ((u64)idx << kRowBits) | (u64)r;
+        const u64 witness = pack_witness(air, idx, r);
         const long long cm = (long long)bb::centred(bb::from_monty(mu));
         const u64 h = slot_hash(a, b);
         bool done = false;
@@ -235,8 +203,6 @@ struct Released {
     ~Released() { cx.table.release(); cx.list.release(); cx.args.release(); }
 };
 
-#define TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)
-
 uint64_t splitmix(uint64_t& s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -247,41 +213,6 @@ Ext challenge(uint64_t& s) {
     Ext e;
     for (int k = 0; k < 4; ++k) e.c[k] = bb::to_monty((uint32_t)(splitmix(s) % bb::P));
     return e;
-}
-
-// the prover's interactions ordered by (bus id, index), once per prover
-int ensure_bus_order(PwProver* p) {
-    if (!p->h_bus_starts.empty() || !p->n_inter) return 0;
-    std::vector<uint32_t> order(p->n_inter);
-    for (uint32_t i = 0; i < p->n_inter; ++i) order[i] = i;
-    auto bus_of = [&](uint32_t i) { return bb::from_monty(p->h_inter[i].bus_monty); };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return bus_of(x) < bus_of(y); });
-    std::vector<uint32_t> ids, starts;
-    for (uint32_t k = 0; k < p->n_inter; ++k)
-        if (!k || bus_of(order[k]) != bus_of(order[k - 1])) { ids.push_back(bus_of(order[k])); starts.push_back(k); }
-    starts.push_back(p->n_inter);
-    TRY(p->bus_order.ensure(order.size() * 4));
-    PW_HIP_TRY(hipMemcpy(p->bus_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
-    p->h_bus_order = std::move(order);
-    p->h_bus_ids = std::move(ids);
-    p->h_bus_starts = std::move(starts);
-    return 0;
-}
-
-LogupProgram program_of(const PwProver* p) {
-    return LogupProgram{p->d_inter, p->n_inter, p->d_ixspans, p->d_icode, p->d_gstarts, p->n_groups, p->d_iforms};
-}
-
-// what the interaction programs of AIR a read: the trace, or with preprocessed columns the prover's (trace | fixed) staging matrix
-// (one copy per call: the argument check refuses a preprocessed prover that occurs twice, whose two traces would share the matrix)
-int stage_values(const PwSegmentAir& a, const uint32_t** out) {
-    PwProver* p = a.prover;
-    *out = a.d_trace;
-    if (!p->pre_width) return 0;
-    const size_t H = (size_t)1 << a.log_height;
-    PW_HIP_TRY(hipMemcpyAsync(p->pre_vals.as<uint32_t>(), a.d_trace, (size_t)p->width * H * 4, hipMemcpyDeviceToDevice, stream()));
-    *out = p->pre_vals.as<uint32_t>();
-    return 0;
 }
 
 }  // namespace
@@ -309,20 +240,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     if ((!airs && n_airs) || (!buses && n_buses) || (flags & ~PW_BUS_CHECK_TALLY_ALL)) return -1;
     if ((summaries != nullptr) != (summary_cap != 0) || (summaries && !n_summaries)) return -1;
     if ((!tuples && tuple_cap) || (tuples && !n_tuples)) return -1;
-    if (n_airs >= ((size_t)1 << kAirBits)) return -1;
-    for (size_t a = 0; a < n_airs; ++a) {
-        const PwProver* p = airs[a].prover;
-        if (!p || !airs[a].d_trace || airs[a].log_height > kRowBits) return -1;
-        if (p->pre_width && airs[a].log_height != p->pre_log_h) return -1;
-        if (p->logup && p->n_inter >= (1u << kInterBits)) return -1;
-    }
-    {
-        std::vector<const PwProver*> pre;
-        for (size_t a = 0; a < n_airs; ++a)
-            if (airs[a].prover->pre_width) pre.push_back(airs[a].prover);
-        std::sort(pre.begin(), pre.end());
-        if (std::adjacent_find(pre.begin(), pre.end()) != pre.end()) return -1;  // one staging matrix cannot hold two traces
-    }
+    if (!airs_well_formed(airs, n_airs)) return -1;
     std::vector<uint32_t> sel;
     if (n_buses) {
         for (size_t i = 0; i < n_buses; ++i) sel.push_back(buses[i] % bb::P);
@@ -351,7 +269,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     for (size_t a = 0; a < n_airs; ++a) {
         PwProver* p = airs[a].prover;
         if (!p->logup || !p->n_inter) continue;
-        TRY(ensure_bus_order(p));
+        PW_TRY(ensure_bus_order(p));
         Part part{a, {}, all_segs.size(), nullptr};
         for (size_t k = 0; k < p->h_bus_ids.size(); ++k) {
             const auto at = std::lower_bound(sel.begin(), sel.end(), p->h_bus_ids[k]);
@@ -374,7 +292,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     const size_t off_cnt = n_sel * 5 * 8, off_ovf = off_cnt + 32, off_load = off_ovf + 16, off_pow = off_load + load_bytes, off_seg = off_pow + blpow.size() * sizeof(Ext),
                  off_air = (off_seg + all_segs.size() * sizeof(BusSeg) + 15) & ~(size_t)15, small_bytes = off_air + n_airs * sizeof(AirDev);
     const Released released{cx};
-    TRY(cx.small.ensure(small_bytes));
+    PW_TRY(cx.small.ensure(small_bytes));
     cx.note();
     char* base = cx.small.as<char>();
     u64* d_acc = (u64*)base;
@@ -392,7 +310,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     std::vector<AirDev> air_tab(n_airs, AirDev{nullptr, 0, LogupProgram{}});
     for (Part& part : parts) {
         const PwSegmentAir& A = airs[part.air];
-        TRY(stage_values(A, &part.vals));
+        PW_TRY(stage_values(A, &part.vals));
         air_tab[part.air] = AirDev{part.vals, (u64)1 << A.log_height, program_of(A.prover)};
     }
     PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
@@ -521,8 +439,8 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
         sums[b].n_unbalanced = n_unb;
         if (!n_unb || !tuples || n_out >= tuple_cap) continue;
         // the unbalanced slots, their tuple words at the witness rows, sorted on the host
-        TRY(cx.list.ensure(n_unb * sizeof(Unbalanced)));
-        TRY(cx.args.ensure(n_unb * stride * 4));
+        PW_TRY(cx.list.ensure(n_unb * sizeof(Unbalanced)));
+        PW_TRY(cx.args.ensure(n_unb * stride * 4));
         cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.args.p, 0, n_unb * stride * 4, st));
         hipLaunchKernelGGL(bus_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.list.as<Unbalanced>(), n_unb, d_counts);

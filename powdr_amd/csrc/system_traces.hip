@@ -1,0 +1,609 @@
+// Device-side generation of the traces of the system AIRs that close a segment's buses (include/powdr_prover.h
+// pw_program_frequencies / pw_memory_boundary_trace; the AIRs themselves: powdr_amd/system_airs.py).
+//   program     program_freq_kernel   every active (air, interaction on the PC-lookup bus, row) is matched word for word against the
+//                                     row (pc - pc_base) / pc_step of the program table and adds its centred multiplicity to that
+//                                     row's sum — merged per wave, then per workgroup in LDS (the first kFreqLdsBins rows) — or is
+//                                     counted as foreign; program_freq_finish_kernel reduces the sums mod p
+//   boundary    boundary_walk_kernel  pass 1: (as, ptr) of every active triple of the memory bus into an open-addressing table keyed
+//                                     by ADDRESS (the bus check's hashing and load rule), atomicMin of the timestamp over the receives,
+//                                     atomicMax over the sends; pass 2: atomicMin of the packed witness over the triples that carry
+//                                     those extremes; boundary_compact_kernel + a radix sort of the keys; boundary_rows_kernel: one
+//                                     lane per row re-evaluates the data words at the two witnesses and writes the 18 columns
+// One lane per row, interactions evaluated by eval_span exactly as the prover and the bus check evaluate them.
+#include "bus_shared.hpp"
+
+#include <rocprim/rocprim.hpp>
+
+namespace pw {
+
+namespace {
+
+using namespace bus;
+
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kFreqLdsBins = 4096;    // 32 KB of 64-bit sums next to the interpreter's 16 KB stack
+constexpr int kFreqMergeRounds = 4;        // distinct table rows a wave merges before its lanes fall back to one atomic each
+constexpr uint32_t kProgramArgs = 9;       // pc, opcode, a .. g
+constexpr uint32_t kMemoryArgs = 7;        // as, ptr, four data words, timestamp
+constexpr uint32_t kBoundaryWidth = 18;
+constexpr uint32_t kLimbBits = 17;
+// what a walk found wrong with the multiplicities (boundary_walk_kernel)
+constexpr uint32_t kFlagMagnitude = 1u;
+
+__device__ __forceinline__ u64 wave_min(u64 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// ---- the program AIR's multiplicities ----------------------------------------------------------------------------------------------
+// sums[row] += the centred multiplicities of the tuples that equal program row `row` (two's complement in 64 bits: exact below 2^32
+// contributions per row); foreign[0] += tuples that equal no row, foreign[1] = min of their packed witnesses, foreign[2 .. 4] statistics. A lane walks
+// rows_per_lane rows (row = first + k * kBlock: coalesced). The loops are wave-uniform (a lane past the end carries no tuple), so that
+// the lanes of a wave can merge: the rows of an instruction AIR repeat a block's few instructions, a wave of 64 consecutive rows holds
+// a handful of distinct table rows, and each of them costs ONE atomic per wave — into LDS for the first kFreqLdsBins table rows (a loop
+// body lies there when pc_base is its first pc), one global atomic per (workgroup, row) at the end.
+template <bool FAST>
+__global__ __launch_bounds__(kBlock) void program_freq_kernel(const uint32_t* __restrict__ m, size_t H, uint32_t rows_per_lane, LogupProgram lp,
+                                                               const uint32_t* __restrict__ order, uint32_t begin, uint32_t end, uint32_t air,
+                                                               uint32_t pc_base, uint32_t pc_step, const uint32_t* __restrict__ program, uint32_t table_rows,
+                                                               u64* __restrict__ sums, u64* __restrict__ foreign) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    __shared__ u64 bins[kFreqLdsBins];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    for (uint32_t b = threadIdx.x; b < kFreqLdsBins; b += kBlock) bins[b] = 0;
+    __syncthreads();
+    const size_t first = (size_t)blockIdx.x * kBlock * rows_per_lane + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    u64 n_foreign = 0, w_foreign = kEmpty, n_active = 0, n_lds = 0, n_global = 0;
+    for (uint32_t k = 0; k < rows_per_lane; ++k) {
+        const size_t r = first + (size_t)k * kBlock;
+        for (uint32_t i = begin; i < end; ++i) {
+            const uint32_t idx = order[i];
+            const LogupInteraction it = lp.d_inter[idx];
+            uint32_t bin = kNone;
+            long long cm = 0;
+            const uint32_t mu = r < H ? eval_span<FAST>(lp, it.first_span, m, H, r, stk) : 0u;
+            if (mu != 0u) {
+                ++n_active;
+                cm = (long long)bb::centred(bb::from_monty(mu));
+                bool ok = it.n_args == kProgramArgs;
+                if (ok) {
+                    const uint32_t pc = bb::from_monty(eval_span<FAST>(lp, it.first_span + 1, m, H, r, stk));
+                    ok = pc >= pc_base && (pc - pc_base) % pc_step == 0u && (pc - pc_base) / pc_step < table_rows;
+                    if (ok) {
+                        const uint32_t row = (pc - pc_base) / pc_step;
+                        ok = bb::from_monty(program[row]) == pc;
+                        for (uint32_t j = 1; ok && j < kProgramArgs; ++j)
+                            ok = bb::from_monty(eval_span<FAST>(lp, it.first_span + 1 + j, m, H, r, stk)) == bb::from_monty(program[(size_t)j * table_rows + row]);
+                        if (ok) bin = row;
+                    }
+                }
+                if (!ok) {
+                    ++n_foreign;
+                    const u64 w = pack_witness(air, idx, r);
+                    w_foreign = w < w_foreign ? w : w_foreign;
+                }
+            }
+            u64 todo = __builtin_amdgcn_ballot_w64(bin != kNone);
+            for (int round = 0; round < kFreqMergeRounds && todo; ++round) {
+                const int leader = __builtin_ctzll(todo);
+                const uint32_t key = (uint32_t)__shfl((int)bin, leader, 64);
+                const bool mine = bin == key;
+                const u64 s = wave_sum(mine ? (u64)cm : 0ull);
+                if (lane == (unsigned)leader) {
+                    if (key < kFreqLdsBins) { atomicAdd(&bins[key], s); ++n_lds; }
+                    else { atomicAdd(sums + key, s); ++n_global; }
+                }
+                todo &= ~__builtin_amdgcn_ballot_w64(mine);
+            }
+            if ((todo >> lane) & 1ull) {  // (a wave with many distinct rows: straight-line code)
+                if (bin < kFreqLdsBins) { atomicAdd(&bins[bin], (u64)cm); ++n_lds; }
+                else { atomicAdd(sums + bin, (u64)cm); ++n_global; }
+            }
+        }
+    }
+    n_foreign = wave_sum(n_foreign);
+    w_foreign = wave_min(w_foreign);
+    if (lane == 0 && n_foreign) {
+        atomicAdd(foreign, n_foreign);
+        atomicMin(foreign + 1, w_foreign);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kFreqLdsBins && b < table_rows; b += kBlock)
+        if (bins[b]) { atomicAdd(sums + b, bins[b]); ++n_global; }
+    // what the call did, for pw_system_traces_last_stats: additions asked for, LDS and global atomics issued (three atomics per wave)
+    n_active = wave_sum(n_active);
+    n_lds = wave_sum(n_lds);
+    n_global = wave_sum(n_global);
+    if (lane == 0) {
+        if (n_active) atomicAdd(foreign + 2, n_active);
+        if (n_lds) atomicAdd(foreign + 3, n_lds);
+        if (n_global) atomicAdd(foreign + 4, n_global);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void program_freq_finish_kernel(const u64* __restrict__ sums, uint32_t table_rows, uint32_t* __restrict__ freq) {
+    const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= table_rows) return;
+    long long v = (long long)sums[r] % (long long)bb::P;
+    if (v < 0) v += (long long)bb::P;
+    freq[r] = bb::to_monty((uint32_t)v);
+}
+
+// args[e * stride + j] = argument j (canonical) of the interaction and row that witness e names, mult[e] its multiplicity; one wave
+// per entry (as bus_args_kernel: the lists are short)
+__global__ __launch_bounds__(kBlock) void witness_args_kernel(const u64* __restrict__ list, u64 n, const AirDev* __restrict__ airs, uint32_t stride,
+                                                               uint32_t* __restrict__ args, uint32_t* __restrict__ mult) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    const u64 e = (u64)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (e >= n) return;
+    const u64 w = list[e];
+    const AirDev a = airs[w >> (kRowBits + kInterBits)];
+    const uint32_t idx = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
+    const size_t r = (size_t)(w & ((1ull << kRowBits) - 1ull));
+    const LogupInteraction it = a.lp.d_inter[idx];
+    for (uint32_t j = 0; j <= it.n_args && j <= stride; ++j) {
+        const uint32_t v = a.lp.d_forms ? eval_span<true>(a.lp, it.first_span + j, a.m, (size_t)a.H, r, stk)
+                                        : eval_span<false>(a.lp, it.first_span + j, a.m, (size_t)a.H, r, stk);
+        if ((threadIdx.x & 63) == 0) {
+            if (j == 0) mult[e] = bb::from_monty(v);
+            else args[e * stride + j - 1] = bb::from_monty(v);
+        }
+    }
+}
+
+// ---- the memory boundary AIR's trace -----------------------------------------------------------------------------------------------
+// one slot per touched location: the key (as << 32 | ptr), the smallest timestamp a receive carried (what the location held before
+// its first access: kEmpty = no receive), the largest a send carried + 1 (what it holds after its last: 0 = no send), and the smallest
+// packed witness among the triples that carry each extreme
+struct AddrTable { u64 *key, *tmin, *wmin, *wmax, *tmax; u64 mask; u64* load; u64 class_mask, class_cap; };
+
+__device__ __forceinline__ u64 address_key(uint32_t as, uint32_t ptr) { return ((u64)as << 32) | (u64)ptr; }
+
+// the slot that holds `key`, or kEmpty (every key the rows kernel asks for was inserted)
+__device__ __forceinline__ u64 find_slot(const AddrTable& t, u64 key) {
+    const u64 h = slot_hash(key >> 32, key & 0xffffffffull);
+    for (u64 n = 0; n <= t.mask; ++n) {
+        const u64 s = (h + n) & t.mask;
+        const u64 k = __atomic_load_n(t.key + s, __ATOMIC_RELAXED);
+        if (k == key) return s;
+        if (k == kEmpty) break;
+    }
+    return kEmpty;
+}
+
+// PASS 1: claim the slot of every active triple's address (keys never change once set; the lane that claims a fresh slot counts it
+// in the slot's class, a class past its cap sets *overflow — the rule of bus_tally_kernel, so whether a table overflows is a function
+// of the traces and its size alone) and fold the timestamp in. PASS 2: the same walk; a triple whose timestamp is its slot's extreme
+// offers its witness. A multiplicity that is not +1 or -1 sets kFlagMagnitude and is left out.
+template <bool FAST, int PASS>
+__global__ __launch_bounds__(kBlock) void boundary_walk_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
+                                                                uint32_t begin, uint32_t end, uint32_t air, AddrTable t, uint32_t* __restrict__ overflow,
+                                                                uint32_t* __restrict__ flags) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= H || __atomic_load_n(overflow, __ATOMIC_RELAXED)) return;
+    for (uint32_t i = begin; i < end; ++i) {
+        const uint32_t idx = order[i];
+        const LogupInteraction it = lp.d_inter[idx];
+        const uint32_t mu = eval_span<FAST>(lp, it.first_span, m, H, r, stk);
+        if (mu == 0u) continue;
+        const int32_t cm = bb::centred(bb::from_monty(mu));
+        if (cm != 1 && cm != -1) {
+            if (PASS == 1) atomicOr(flags, kFlagMagnitude);
+            continue;
+        }
+        const uint32_t as = bb::from_monty(eval_span<FAST>(lp, it.first_span + 1, m, H, r, stk));
+        const uint32_t ptr = bb::from_monty(eval_span<FAST>(lp, it.first_span + 2, m, H, r, stk));
+        const u64 ts = bb::from_monty(eval_span<FAST>(lp, it.first_span + it.n_args, m, H, r, stk));
+        const u64 key = address_key(as, ptr);
+        if (PASS == 2) {
+            const u64 s = find_slot(t, key);
+            if (s == kEmpty) continue;
+            const u64 w = pack_witness(air, idx, r);
+            if (cm < 0) {
+                if (t.tmin[s] == ts) atomicMin(t.wmin + s, w);
+            } else if (t.tmax[s] == ts + 1) {
+                atomicMin(t.wmax + s, w);
+            }
+            continue;
+        }
+        const u64 h = slot_hash(as, ptr);
+        bool done = false;
+        for (u64 n = 0; n <= t.mask; ++n) {
+            const u64 s = (h + n) & t.mask;
+            u64 k = __atomic_load_n(t.key + s, __ATOMIC_RELAXED);
+            if (k == kEmpty) {
+                k = atomicCAS(t.key + s, kEmpty, key);
+                if (k == kEmpty) {
+                    k = key;
+                    if (atomicAdd(t.load + (s & t.class_mask) * kLoadStride, 1ull) >= t.class_cap) atomicOr(overflow, 1u);
+                }
+            }
+            if (k == key) {
+                // (a register is touched by every call: most triples lose against what the slot already holds and cost a load)
+                if (cm < 0) {
+                    if (__atomic_load_n(t.tmin + s, __ATOMIC_RELAXED) > ts) atomicMin(t.tmin + s, ts);
+                } else if (__atomic_load_n(t.tmax + s, __ATOMIC_RELAXED) < ts + 1) {
+                    atomicMax(t.tmax + s, ts + 1);
+                }
+                done = true;
+                break;
+            }
+            if ((n & 63) == 63 && __atomic_load_n(overflow, __ATOMIC_RELAXED)) break;
+        }
+        if (!done) {
+            atomicOr(overflow, 1u);
+            return;
+        }
+    }
+}
+
+// counts[0] = occupied slots, counts[1] = those with only receives or only sends; with `keys`: the occupied slots' keys, in arrival
+// order (sorted afterwards), counts[2] = written
+__global__ __launch_bounds__(kBlock) void boundary_compact_kernel(AddrTable t, u64* __restrict__ keys, u64 cap, u64* __restrict__ counts) {
+    const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
+    if (s > t.mask || t.key[s] == kEmpty) return;
+    if (!keys) {
+        atomicAdd(counts, 1ull);
+        if (t.tmin[s] == kEmpty || t.tmax[s] == 0ull) atomicAdd(counts + 1, 1ull);
+        return;
+    }
+    const u64 at = atomicAdd(counts + 2, 1ull);
+    if (at < cap) keys[at] = t.key[s];
+}
+
+__device__ __forceinline__ uint32_t witness_arg(const AirDev* __restrict__ airs, u64 w, uint32_t j, uint32_t* stk) {
+    const AirDev a = airs[w >> (kRowBits + kInterBits)];
+    const uint32_t idx = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
+    const size_t r = (size_t)(w & ((1ull << kRowBits) - 1ull));
+    const uint32_t span = a.lp.d_inter[idx].first_span + 1 + j;
+    return a.lp.d_forms ? eval_span<true>(a.lp, span, a.m, (size_t)a.H, r, stk) : eval_span<false>(a.lp, span, a.m, (size_t)a.H, r, stk);
+}
+
+// Row r of the boundary trace (column-major, H_out rows, Montgomery) from the r-th smallest address: [is_valid, as, ptr, p_lo, p_hi,
+// init0..3, init_ts, fin0..3, fin_ts, same_as, d_lo, d_hi]; the gap to the next address and same_as from the sorted neighbour, the
+// data words re-evaluated at the two witness rows (lanes of a wave may run different programs: correct, and the rows are few next to
+// the walks). Rows from n on are zero.
+__global__ __launch_bounds__(kBlock) void boundary_rows_kernel(const u64* __restrict__ sorted, u64 n, AddrTable t, const AirDev* __restrict__ airs,
+                                                                size_t H_out, uint32_t* __restrict__ out) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= H_out) return;
+    uint32_t v[kBoundaryWidth];
+#pragma unroll
+    for (uint32_t c = 0; c < kBoundaryWidth; ++c) v[c] = 0u;
+    if (r < n) {
+        const u64 key = sorted[r];
+        const uint32_t as = (uint32_t)(key >> 32), ptr = (uint32_t)key;
+        const u64 s = find_slot(t, key);
+        v[0] = bb::to_monty(1u);
+        v[1] = bb::to_monty(as);
+        v[2] = bb::to_monty(ptr);
+        v[3] = bb::to_monty(ptr & ((1u << kLimbBits) - 1u));
+        v[4] = bb::to_monty(ptr >> kLimbBits);
+        if (s != kEmpty) {
+            const u64 wmin = t.wmin[s], wmax = t.wmax[s];
+            for (uint32_t j = 0; j < 4 && wmin != kEmpty && wmax != kEmpty; ++j) {  // (both exist: the host has refused status 4)
+                v[5 + j] = witness_arg(airs, wmin, 2 + j, stk);
+                v[10 + j] = witness_arg(airs, wmax, 2 + j, stk);
+            }
+            v[9] = bb::to_monty((uint32_t)t.tmin[s]);
+            v[14] = bb::to_monty((uint32_t)(t.tmax[s] - 1));
+        }
+        if (r + 1 < n) {
+            const u64 next = sorted[r + 1];
+            if ((uint32_t)(next >> 32) == as) {
+                const uint32_t d = (uint32_t)next - ptr - 1u;
+                v[15] = bb::to_monty(1u);
+                v[16] = bb::to_monty(d & ((1u << kLimbBits) - 1u));
+                v[17] = bb::to_monty(d >> kLimbBits);
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < kBoundaryWidth; ++c) out[(size_t)c * H_out + r] = v[c];
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------------
+struct SysCtx {
+    DeviceBuf small;                      // counters | class loads | AIR table | one witness's arguments: stays
+    DeviceBuf sums, table, keys, sorted, temp;  // released before a call returns, on every path (SysReleased below)
+    size_t peak = 0;
+    uint64_t stat_slots = 0, stat_occupied = 0, stat_tables = 0, stat_triples = 0, stat_additions = 0, stat_lds_atomics = 0, stat_global_atomics = 0;
+    uint32_t start_log_slots = 0;  // 0: kStartSlots (pw_memory_boundary_set_start_slots)
+    size_t held() const { return small.bytes + sums.bytes + table.bytes + keys.bytes + sorted.bytes + temp.bytes; }
+    void note() { peak = std::max(peak, held()); }
+};
+thread_local SysCtx g_sys;
+struct SysReleased {
+    SysCtx& cx;
+    ~SysReleased() { cx.sums.release(); cx.table.release(); cx.keys.release(); cx.sorted.release(); cx.temp.release(); }
+};
+
+// the AIRs that have interactions on `bus`, with their run in the prover's bus order and the values their programs read
+struct Part { size_t air; uint32_t begin, end; const uint32_t* vals; };
+
+// before any GPU call: false when an interaction on `bus` has not `n_args` arguments
+bool bus_arity_is(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_t n_args) {
+    for (size_t a = 0; a < n_airs; ++a) {
+        const PwProver* p = airs[a].prover;
+        if (!p->logup) continue;
+        for (const LogupInteraction& it : p->h_inter)
+            if (bb::from_monty(it.bus_monty) == bus && it.n_args != n_args) return false;
+    }
+    return true;
+}
+
+int collect_parts(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, std::vector<Part>& parts, std::vector<AirDev>& air_tab) {
+    air_tab.assign(n_airs, AirDev{nullptr, 0, LogupProgram{}});
+    for (size_t a = 0; a < n_airs; ++a) {
+        PwProver* p = airs[a].prover;
+        if (!p->logup || !p->n_inter) continue;
+        PW_TRY(ensure_bus_order(p));
+        const auto at = std::lower_bound(p->h_bus_ids.begin(), p->h_bus_ids.end(), bus);
+        if (at == p->h_bus_ids.end() || *at != bus) continue;
+        const size_t k = at - p->h_bus_ids.begin();
+        Part part{a, p->h_bus_starts[k], p->h_bus_starts[k + 1], nullptr};
+        PW_TRY(stage_values(airs[a], &part.vals));
+        air_tab[a] = AirDev{part.vals, (u64)1 << airs[a].log_height, program_of(p)};
+        parts.push_back(part);
+    }
+    return 0;
+}
+
+}  // namespace
+
+}  // namespace pw
+
+using namespace pw;
+
+extern "C" size_t pw_system_traces_scratch_bytes(void) { return g_sys.held(); }
+extern "C" size_t pw_system_traces_peak_bytes(void) { return g_sys.peak; }
+extern "C" void pw_system_traces_last_stats(PwSystemTraceStats* out) {
+    if (!out) return;
+    *out = PwSystemTraceStats{g_sys.stat_slots, g_sys.stat_occupied, g_sys.stat_tables, g_sys.stat_triples, g_sys.stat_additions, g_sys.stat_lds_atomics,
+                              g_sys.stat_global_atomics};
+}
+extern "C" int pw_memory_boundary_set_start_slots(uint32_t log_slots) {
+    if (log_slots && (log_slots < 6 || log_slots > 30)) return -1;
+    g_sys.start_log_slots = log_slots;
+    return 0;
+}
+
+extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_t pc_base, uint32_t pc_step, const uint32_t* d_program,
+                                      uint32_t log_h, uint32_t* d_freq_out, uint64_t* n_foreign, PwBusTuple* first_foreign) {
+    if (!airs_well_formed(airs, n_airs) || !d_program || !d_freq_out || !n_foreign || !pc_step || log_h > kRowBits || bus >= bb::P) return -1;
+    SysCtx& cx = g_sys;
+    cx.peak = 0;
+    cx.stat_triples = 0;
+    *n_foreign = 0;
+    (void)hipGetLastError();
+    const SysReleased released{cx};
+    const uint32_t table_rows = 1u << log_h;
+    std::vector<Part> parts;
+    std::vector<AirDev> air_tab;
+    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
+    // small: foreign count, foreign witness, three statistics | AIR table | the witness's multiplicity, arguments
+    const size_t off_air = 48, off_args = off_air + n_airs * sizeof(AirDev), small_bytes = off_args + (1 + PW_BUS_MAX_ARGS) * 4;
+    PW_TRY(cx.small.ensure(small_bytes));
+    PW_TRY(cx.sums.ensure((size_t)table_rows * 8));
+    cx.note();
+    char* base = cx.small.as<char>();
+    u64* d_foreign = (u64*)base;
+    AirDev* d_airs = (AirDev*)(base + off_air);
+    uint32_t* d_args = (uint32_t*)(base + off_args);
+    hipStream_t st = stream();
+    const u64 foreign0[5] = {0, kEmpty, 0, 0, 0};
+    PW_HIP_TRY(hipMemcpyAsync(d_foreign, foreign0, sizeof foreign0, hipMemcpyHostToDevice, st));
+    PW_HIP_TRY(hipMemsetAsync(cx.sums.p, 0, (size_t)table_rows * 8, st));
+    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
+    {
+        ScopedKernelTimer timer("program_freq_kernel");
+        for (const Part& part : parts) {
+            const PwSegmentAir& A = airs[part.air];
+            const PwProver* p = A.prover;
+            const size_t H = (size_t)1 << A.log_height;
+            const uint32_t rows = A.log_height >= 16 ? 4u : 1u;
+            const LogupProgram lp = program_of(p);
+            const dim3 grid(div_up(H, (size_t)kBlock * rows));
+            cx.stat_triples += (uint64_t)H * (part.end - part.begin);
+            if (lp.d_forms)
+                hipLaunchKernelGGL(program_freq_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, rows, lp, (const uint32_t*)p->bus_order.p, part.begin, part.end,
+                                   (uint32_t)part.air, pc_base, pc_step, d_program, table_rows, cx.sums.as<u64>(), d_foreign);
+            else
+                hipLaunchKernelGGL(program_freq_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, rows, lp, (const uint32_t*)p->bus_order.p, part.begin, part.end,
+                                   (uint32_t)part.air, pc_base, pc_step, d_program, table_rows, cx.sums.as<u64>(), d_foreign);
+        }
+    }
+    hipLaunchKernelGGL(program_freq_finish_kernel, dim3(div_up(table_rows, kBlock)), dim3(kBlock), 0, st, cx.sums.as<u64>(), table_rows, d_freq_out);
+    PW_HIP_TRY(hipGetLastError());
+    u64 foreign[5];
+    PW_HIP_TRY(hipMemcpyAsync(foreign, d_foreign, sizeof foreign, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    *n_foreign = foreign[0];
+    cx.stat_additions = foreign[2];
+    cx.stat_lds_atomics = foreign[3];
+    cx.stat_global_atomics = foreign[4];
+    if (foreign[0] && first_foreign) {
+        // the tuple at the smallest foreign witness: its own multiplicity, one contribution
+        PW_HIP_TRY(hipMemsetAsync(d_args, 0, (1 + PW_BUS_MAX_ARGS) * 4, st));
+        hipLaunchKernelGGL(witness_args_kernel, dim3(1), dim3(kBlock), 0, st, (const u64*)(d_foreign + 1), (u64)1, (const AirDev*)d_airs, (uint32_t)PW_BUS_MAX_ARGS,
+                           d_args + 1, d_args);
+        PW_HIP_TRY(hipGetLastError());
+        uint32_t words[1 + PW_BUS_MAX_ARGS];
+        PW_HIP_TRY(hipMemcpyAsync(words, d_args, sizeof words, hipMemcpyDeviceToHost, st));
+        PW_HIP_TRY(hipStreamSynchronize(st));
+        const u64 w = foreign[1];
+        PwBusTuple& t = *first_foreign;
+        memset(&t, 0, sizeof t);
+        t.bus = bus;
+        t.air = (uint32_t)(w >> (kRowBits + kInterBits));
+        t.interaction = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
+        t.row = w & ((1ull << kRowBits) - 1ull);
+        t.n_args = airs[t.air].prover->h_inter[t.interaction].n_args;
+        for (uint32_t j = 0; j < t.n_args && j < PW_BUS_MAX_ARGS; ++j) t.args[j] = words[1 + j];
+        t.net_multiplicity = words[0];
+        t.n_contributions = 1;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, size_t table_bytes, uint32_t* d_trace_out,
+                                        uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_locations, uint32_t* status) {
+    if (!airs_well_formed(airs, n_airs) || !d_trace_out || !log_height || !n_locations || !status || cap_log_height < 1 || cap_log_height > kRowBits ||
+        bus >= bb::P)
+        return -1;
+    if (!bus_arity_is(airs, n_airs, bus, kMemoryArgs)) return -1;
+    SysCtx& cx = g_sys;
+    cx.peak = 0;
+    cx.stat_slots = cx.stat_occupied = cx.stat_tables = cx.stat_triples = 0;
+    *log_height = 0;
+    *n_locations = 0;
+    *status = 0;
+    (void)hipGetLastError();
+    const SysReleased released{cx};
+    std::vector<Part> parts;
+    std::vector<AirDev> air_tab;
+    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
+    u64 triples = 0;
+    for (const Part& part : parts) triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
+    cx.stat_triples = triples;
+    // small: counters (4 u64: occupied | incomplete | written | unused) | overflow word, flags (+ padding: 16 bytes) | class loads | AIR table
+    const size_t load_bytes = kMaxClasses * kLoadStride * 8;
+    const size_t off_ovf = 32, off_load = off_ovf + 16, off_air = off_load + load_bytes, small_bytes = off_air + n_airs * sizeof(AirDev);
+    PW_TRY(cx.small.ensure(small_bytes));
+    cx.note();
+    char* base = cx.small.as<char>();
+    u64* d_counts = (u64*)base;
+    uint32_t* d_ovf = (uint32_t*)(base + off_ovf);
+    uint32_t* d_flags = d_ovf + 1;
+    u64* d_load = (u64*)(base + off_load);
+    AirDev* d_airs = (AirDev*)(base + off_air);
+    hipStream_t st = stream();
+    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
+
+    // the largest table: a power of two of slots, at most twice the triples walked (no segment touches more locations), within the
+    // caller's bound, or by default half of the device's room
+    u64 max_slots = 1024;
+    while (max_slots < 2 * triples) max_slots <<= 1;
+    size_t bound = table_bytes;
+    if (!bound) {
+        size_t avail = 0;
+        bound = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
+    }
+    while (max_slots && max_slots * kSlotBytes > bound) max_slots >>= 1;
+    if (!max_slots) {
+        *status = 2;
+        return 0;
+    }
+    auto walk = [&](int pass, const AddrTable& T) {
+        for (const Part& part : parts) {
+            const PwSegmentAir& A = airs[part.air];
+            const PwProver* p = A.prover;
+            const size_t H = (size_t)1 << A.log_height;
+            const LogupProgram lp = program_of(p);
+            const dim3 grid(div_up(H, kBlock));
+            const uint32_t* order = (const uint32_t*)p->bus_order.p;
+            if (lp.d_forms && pass == 1)
+                hipLaunchKernelGGL((boundary_walk_kernel<true, 1>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
+            else if (lp.d_forms)
+                hipLaunchKernelGGL((boundary_walk_kernel<true, 2>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
+            else if (pass == 1)
+                hipLaunchKernelGGL((boundary_walk_kernel<false, 1>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
+            else
+                hipLaunchKernelGGL((boundary_walk_kernel<false, 2>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
+        }
+    };
+    // pass 1 into a small table first and into one four times as large while it overflows (the bus check's rule: what comes out depends
+    // on the last table alone)
+    u64 slots = std::min(max_slots, cx.start_log_slots ? (u64)1 << cx.start_log_slots : kStartSlots);
+    u64 counts[6] = {0, 0, 0, 0, 1, 0};  // occupied | incomplete | written | unused | overflow word, flags
+    AddrTable T{};
+    for (;;) {
+        int erc;
+        while ((erc = cx.table.ensure(slots * kSlotBytes)) != 0) {
+            (void)hipGetLastError();
+            if (erc != (int)hipErrorOutOfMemory) return erc;
+            if (slots <= 1) break;
+            max_slots = slots >>= 1;
+        }
+        if (!cx.table.p) break;
+        cx.note();
+        u64* tb = cx.table.as<u64>();
+        const u64 classes = std::min<u64>(kMaxClasses, std::max<u64>(1, slots / kMinClassSlots)), per_class = slots / classes;
+        T = AddrTable{tb, tb + slots, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots, slots - 1, d_load, classes - 1, per_class - per_class / 8};
+        {
+            ScopedKernelTimer timer("boundary_table_clear");
+            PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 4 * slots * 8, st));
+            PW_HIP_TRY(hipMemsetAsync(tb + 4 * slots, 0, slots * 8, st));
+            PW_HIP_TRY(hipMemsetAsync(d_counts, 0, off_air, st));  // counters, the overflow word, the flags, the class loads
+        }
+        {
+            ScopedKernelTimer timer("boundary_walk_kernel");
+            walk(1, T);
+        }
+        hipLaunchKernelGGL(boundary_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64)0, d_counts);
+        PW_HIP_TRY(hipGetLastError());
+        PW_HIP_TRY(hipMemcpyAsync(counts, d_counts, 48, hipMemcpyDeviceToHost, st));
+        PW_HIP_TRY(hipStreamSynchronize(st));
+        ++cx.stat_tables;
+        if (!(uint32_t)counts[4] || slots >= max_slots) break;
+        slots = std::min(max_slots, slots * 4);
+    }
+    if (!cx.table.p || (uint32_t)counts[4]) {
+        *status = 2;
+        return (int)hipGetLastError();
+    }
+    const u64 n = counts[0];
+    cx.stat_slots = slots;
+    cx.stat_occupied = n;
+    *n_locations = n;
+    uint32_t lh = 1;
+    while (((u64)1 << lh) < n) ++lh;
+    *log_height = lh;
+    if ((uint32_t)(counts[4] >> 32) & kFlagMagnitude) {
+        *status = 3;
+        return (int)hipGetLastError();
+    }
+    if (counts[1]) {
+        *status = 4;
+        return (int)hipGetLastError();
+    }
+    if (lh > cap_log_height) {
+        *status = 1;
+        return (int)hipGetLastError();
+    }
+    {
+        ScopedKernelTimer timer("boundary_witness_kernel");
+        walk(2, T);
+    }
+    const size_t H_out = (size_t)1 << lh;
+    if (n) {
+        PW_TRY(cx.keys.ensure(n * 8));
+        PW_TRY(cx.sorted.ensure(n * 8));
+        cx.note();
+        hipLaunchKernelGGL(boundary_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.keys.as<u64>(), n, d_counts);
+        PW_HIP_TRY(hipGetLastError());
+        ScopedKernelTimer timer("boundary_sort");
+        size_t temp_bytes = 0;
+        PW_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), (size_t)n, 0u, 64u, st));
+        PW_TRY(cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
+        cx.note();
+        PW_HIP_TRY(rocprim::radix_sort_keys(cx.temp.p, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), (size_t)n, 0u, 64u, st));
+    }
+    {
+        ScopedKernelTimer timer("boundary_rows_kernel");
+        hipLaunchKernelGGL(boundary_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, n, T, (const AirDev*)d_airs, H_out, d_trace_out);
+    }
+    PW_HIP_TRY(hipGetLastError());
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    return (int)hipGetLastError();
+}

@@ -222,7 +222,7 @@ def _offset_operands(ibc: np.ndarray, ispans: np.ndarray, height: int) -> np.nda
     return out
 
 
-class _BusReplay:
+class BusReplay:
     """_apc_apply_bus on an arbitrary trace with an interaction table kept on the device (uploaded once)."""
 
     def __init__(self, interactions, height: int):
@@ -240,6 +240,9 @@ class _BusReplay:
                                     p.tuple_bus, p.tuple_hist.data_ptr(), p.tuple_sizes[0], p.tuple_sizes[1],
                                     p.bitwise_bus, p.bitwise_hist.data_ptr())
         abi.check(rc, "_apc_apply_bus")
+
+
+_BusReplay = BusReplay  # (the name it had while only this module used it)
 
 
 def draw_segment_shape(seed: int, u: int, n_segments: int, apc_max_calls, instr_max_calls: int) -> dict:
@@ -302,7 +305,7 @@ class HonestSegment:
             self.instr_bufs[k] = (t.data_ptr(), heights[k])
             bc, sp, it = synth.reference_air_programs(n)
             self.airs.append(dict(name=n, role="instruction", width=oc.WIDTHS[k], log_h=heights[k].bit_length() - 1, cons=(bc, sp), inter=it, trace=t))
-            self.replays.append((_BusReplay(it, heights[k]), t))
+            self.replays.append((BusReplay(it, heights[k]), t))
         # ---- periphery AIRs (no constraints: lookup tables with multiplicity columns; the chips are external). Layout "main": the
         # tables in main columns (ours); "preprocessed": the chips' own — the tables fixed by the key, the multiplicities in the main trace
         empty = (np.zeros(0, np.uint32), np.zeros((0, 2), np.uint32))
@@ -402,7 +405,7 @@ class HonestSegment:
                 self.instr_bufs[k] = (t.data_ptr(), h)
                 a["log_h"] = h.bit_length() - 1
                 if (k, h) not in self._replay_cache:
-                    self._replay_cache[(k, h)] = _BusReplay(a["inter"], h)
+                    self._replay_cache[(k, h)] = BusReplay(a["inter"], h)
                 self.replays.append((self._replay_cache[(k, h)], t))
         self.shape = shape
         self._refresh()
@@ -504,7 +507,9 @@ class HonestSegment:
     def check_buses(self, buses=LOOKUP_BUSES, **kw):
         """The bus half of the mock prover on the current traces (prover.check_segment_buses): per bus whether every
         tuple's multiplicities cancel and, where not, which tuples are left over and where one of them was sent. buses=None: every bus
-        (memory, execution bridge and pc lookup have only senders here: unbalanced by construction). The segment's own provers serve;
+        (memory, execution bridge and pc lookup have only senders here and stay unbalanced: this segment's call records are random
+        per call and do not chain, so the receivers of system_airs.py — DESIGN.md §5j — have nothing consistent to receive). The
+        segment's own provers serve;
         the provers need their interaction tables (logup=True)."""
         return prover.check_segment_buses(self.seg, buses=buses, **kw)
 

@@ -1,0 +1,268 @@
+"""The receive side of the execution bridge, the memory bus and the PC lookup: the three system AIRs that close a segment's buses
+ — their constraint and interaction programs in the formats `prover.Prover` takes (the pattern of periphery.py; sends
++m, receives -m) — and the callers of the routines that make their traces on the device from the other AIRs' raw traces
+(include/powdr_prover.h `pw_program_frequencies`, `pw_memory_boundary_trace`).
+
+  program     preprocessed [pc, opcode, a .. g] (the bus-2 tuple of openvm_constraints.txt), main [freq]: row k is received freq times
+  connector   2 rows, preprocessed [is_end] = (0, 1), main [pc, timestamp]: row 0 sends the initial state, row 1 receives the final one
+  boundary    one row per touched location, sorted by (as, ptr): sends what the location held before its first access, receives what
+              it holds after its last; `init*` / `fin*` are witness columns (from SOME initial memory to SOME final memory)
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import abi, air_text, prover
+from .periphery import OP_PUSH_APC, OP_PUSH_CONST, _col, _neg_col, _tables
+
+lib = abi.lib
+lib.pw_program_frequencies.restype = C.c_int
+lib.pw_program_frequencies.argtypes = [C.POINTER(prover.PwSegmentAir), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(prover.PwBusTuple)]
+lib.pw_memory_boundary_trace.restype = C.c_int
+lib.pw_memory_boundary_trace.argtypes = [C.POINTER(prover.PwSegmentAir), C.c_size_t, C.c_uint32, C.c_size_t, C.c_void_p, C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+lib.pw_system_traces_scratch_bytes.restype = C.c_size_t
+lib.pw_system_traces_scratch_bytes.argtypes = []
+lib.pw_system_traces_peak_bytes.restype = C.c_size_t
+lib.pw_system_traces_peak_bytes.argtypes = []
+
+
+class PwSystemTraceStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("table_slots", "occupied_slots", "tables", "walked", "additions", "lds_atomics", "global_atomics")]
+
+
+lib.pw_system_traces_last_stats.restype = None
+lib.pw_system_traces_last_stats.argtypes = [C.POINTER(PwSystemTraceStats)]
+lib.pw_memory_boundary_set_start_slots.restype = C.c_int
+lib.pw_memory_boundary_set_start_slots.argtypes = [C.c_uint32]
+
+P = 0x78000001
+BUS_EXEC, BUS_MEMORY, BUS_PC, BUS_VAR_RANGE, BUS_BITWISE = 0, 1, 2, 3, 6
+OP_SUB, OP_MUL = 3, 4
+LIMB_BITS = (17, 12)  # a pointer or a gap below 2^29 = a 17-bit and a 12-bit limb, both within the variable range checker's 17 bits
+PROGRAM_COLUMNS = ["pc", "opcode", "a", "b", "c", "d", "e", "f", "g"]
+BOUNDARY_COLUMNS = (["is_valid", "as", "ptr", "p_lo", "p_hi"] + [f"init{i}" for i in range(4)] + ["init_ts"] + [f"fin{i}" for i in range(4)]
+                    + ["fin_ts", "same_as", "d_lo", "d_hi"])
+BOUNDARY_WIDTH = len(BOUNDARY_COLUMNS)  # 18
+BOUNDARY_CONSTRAINTS = [
+    ("is_valid boolean", "is_valid * (is_valid - 1)"),
+    ("same_as boolean", "same_as * (same_as - 1)"),
+    ("valid rows first", "is_transition * is_valid' * (1 - is_valid)"),
+    ("address space 1 or 2", "is_valid * (as - 1) * (as - 2)"),
+    ("pointer limbs", "ptr - p_lo - 131072 * p_hi"),
+    ("same address space", "is_transition * is_valid' * same_as * (as' - as)"),
+    ("next address space", "is_transition * is_valid' * (1 - same_as) * (as' - as - 1)"),
+    ("pointer gap", "is_transition * is_valid' * same_as * (ptr' - ptr - 1 - d_lo - 131072 * d_hi)"),
+]
+NO_CONS = (np.zeros(0, np.uint32), np.zeros((0, 2), np.uint32))
+STATUS = {0: "written", 1: "cap_log_height too small", 2: "address table bound too small", 3: "a multiplicity that is not +1 or -1",
+          4: "a location with only receives or only sends"}
+
+
+@dataclass
+class SystemAir:
+    """What `prover.Prover` and `prover.verify_segment` need of one system AIR. fixed: the preprocessed matrix (canonical,
+    [pre_width, rows]) or None; log_h: the height the fixed matrix gives the AIR (None: any)."""
+    name: str
+    width: int
+    cons: tuple
+    inter: tuple
+    columns: list
+    pre_width: int = 0
+    fixed: np.ndarray | None = None
+    transition: bool = False
+    log_h: int | None = None
+    _table: torch.Tensor | None = field(default=None, repr=False)
+
+    def fixed_table(self, device="cuda") -> torch.Tensor:
+        """the fixed matrix on the device (column-major, Montgomery), uploaded once"""
+        if self._table is None:
+            self._table = _to_device(self.fixed, device)
+        return self._table
+
+    def make_prover(self, num_queries: int = 100, pow_bits: int = 0) -> prover.Prover:
+        pre = None
+        if self.pre_width:
+            pre = (self.fixed_table(), self.pre_width, self.log_h)
+            torch.cuda.synchronize()  # the table exists before the prover copies it (on the library's stream)
+        return prover.Prover(self.width, self.cons[0], self.cons[1], num_queries=num_queries, pow_bits=pow_bits, interactions=self.inter,
+                             preprocessed=pre, transition=self.transition)
+
+    def description(self, log_h: int | None = None):
+        """(width, log_height, cons_bytecode, cons_spans, interactions): an entry of verify_segment's `descs` (transition=True)"""
+        return (self.width, self.log_h if log_h is None else log_h, self.cons[0], self.cons[1], self.inter)
+
+
+def _to_monty(canonical) -> np.ndarray:
+    a = np.ascontiguousarray(canonical, dtype=np.uint64).reshape(-1)
+    return ((a << np.uint64(32)) % np.uint64(P)).astype(np.uint32)
+
+
+def _to_device(canonical, device="cuda") -> torch.Tensor:
+    return torch.from_numpy(_to_monty(canonical).view(np.int32)).to(device)
+
+
+def _from_device(t: torch.Tensor) -> np.ndarray:
+    r_inv = pow(1 << 32, P - 2, P)
+    return ((t.cpu().numpy().view(np.uint32).astype(np.uint64) * np.uint64(r_inv)) % np.uint64(P)).astype(np.uint32)
+
+
+def program_air(table, bus: int = BUS_PC) -> SystemAir:
+    """table: the program as canonical words [9, 2^k] (rows pc, opcode, a .. g; a power of two of instructions, padded with rows no
+    execution reaches). Main [freq] | preprocessed the nine columns; no constraints; every row is received `freq` times on `bus`."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    rows = table.shape[1]
+    assert table.shape[0] == len(PROGRAM_COLUMNS) and rows >= 2 and rows & (rows - 1) == 0, "the program table is 9 x 2^k words, k >= 1"
+    inter = _tables(bus, [(_neg_col(0), [_col(1 + j) for j in range(len(PROGRAM_COLUMNS))])])
+    return SystemAir("program", 1, NO_CONS, inter, ["freq"], pre_width=len(PROGRAM_COLUMNS), fixed=table, log_h=rows.bit_length() - 1)
+
+
+def connector_air(bus: int = BUS_EXEC) -> SystemAir:
+    """Main [pc, timestamp] | preprocessed [is_end] = (0, 1): one interaction with multiplicity 1 - 2 is_end."""
+    mult = [OP_PUSH_CONST, 1, OP_PUSH_CONST, 2, OP_PUSH_APC, 2, OP_MUL, OP_SUB]
+    return SystemAir("connector", 2, NO_CONS, _tables(bus, [(mult, [_col(0), _col(1)])]), ["pc", "timestamp"], pre_width=1,
+                     fixed=np.array([[0, 1]], np.uint32), log_h=1)
+
+
+def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANGE, bitwise_bus: int = BUS_BITWISE) -> SystemAir:
+    """The memory boundary AIR (row-aware: transition=True). Constraints BOUNDARY_CONSTRAINTS; interactions, all on the current row:
+    send (as, ptr, init0..3, init_ts), receive (as, ptr, fin0..3, fin_ts), range checks of the four limbs, byte checks of the initial
+    words (the final ones are whatever the last access sent, whose chip checked them)."""
+    col = {n: i for i, n in enumerate(BOUNDARY_COLUMNS)}
+    rows = prover.row_operands(BOUNDARY_WIDTH)
+    bc, spans = [], []
+    for _, text in BOUNDARY_CONSTRAINTS:
+        code = air_text.compile_expr(text, col, rows)
+        spans.append((len(bc), len(code)))
+        bc += code
+    c = lambda n: _col(col[n])
+    const = lambda v: [OP_PUSH_CONST, v]
+    valid = c("is_valid")
+    by_bus = [
+        (memory_bus, [(valid, [c("as"), c("ptr")] + [c(f"init{i}") for i in range(4)] + [c("init_ts")]),
+                      (_neg_col(col["is_valid"]), [c("as"), c("ptr")] + [c(f"fin{i}") for i in range(4)] + [c("fin_ts")])]),
+        (var_range_bus, [(valid, [c("p_lo"), const(LIMB_BITS[0])]), (valid, [c("p_hi"), const(LIMB_BITS[1])]),
+                         (valid, [c("d_lo"), const(LIMB_BITS[0])]), (valid, [c("d_hi"), const(LIMB_BITS[1])])]),
+        (bitwise_bus, [(valid, [c("init0"), c("init1"), const(0), const(0)]), (valid, [c("init2"), c("init3"), const(0), const(0)])]),
+    ]
+    inter, ispans, ibc = [], [], []
+    for bus, rows_ in by_bus:  # one table over the three buses: spans and bytecode concatenated
+        it, sp, code = _tables(bus, rows_)
+        it = it.copy()
+        it[:, 2] += len(ispans)
+        sp = sp.copy()
+        sp[:, 0] += len(ibc)
+        inter += it.tolist()
+        ispans += sp.tolist()
+        ibc += code.tolist()
+    interactions = (np.array(inter, np.uint32).reshape(-1, 3), np.array(ispans, np.uint32).reshape(-1, 2), np.array(ibc, np.uint32))
+    return SystemAir("boundary", BOUNDARY_WIDTH, (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2)), interactions,
+                     list(BOUNDARY_COLUMNS), transition=True)
+
+
+# ---- traces -------------------------------------------------------------------------------------------------------------------------
+def _records(airs):
+    n = len(airs)
+    recs = (prover.PwSegmentAir * max(n, 1))()
+    for i, (pr, ptr, lh) in enumerate(airs):
+        recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
+    return recs, n
+
+
+def _tuple_dict(t) -> dict:
+    return dict(bus=int(t.bus), n_args=int(t.n_args), args=[int(x) for x in t.args[:min(t.n_args, prover.PW_BUS_MAX_ARGS)]],
+                net_multiplicity=int(t.net_multiplicity), air=int(t.air), interaction=int(t.interaction), row=int(t.row),
+                n_contributions=int(t.n_contributions))
+
+
+def program_frequencies(airs, table: torch.Tensor, log_h: int, pc_base: int, pc_step: int = 4, bus: int = BUS_PC, out: torch.Tensor | None = None):
+    """pw_program_frequencies: airs = [(Prover, device trace pointer, log_height)] as for check_segment_buses (the senders); table = the
+    program AIR's fixed matrix on the device (SystemAir.fixed_table()). -> (freq: the AIR's main trace, 2^log_h Montgomery words;
+    number of foreign tuples; the first of them as a dict, or None). Foreign tuples are in nobody's freq: the caller decides."""
+    assert table.numel() == len(PROGRAM_COLUMNS) << log_h
+    if out is None:
+        out = torch.empty(1 << log_h, dtype=torch.int32, device=table.device)
+    assert out.numel() >= 1 << log_h
+    recs, n = _records(airs)
+    n_foreign, first = C.c_uint64(), prover.PwBusTuple()
+    abi.check(lib.pw_program_frequencies(recs, n, bus, pc_base, pc_step, table.data_ptr(), log_h, out.data_ptr(), C.byref(n_foreign), C.byref(first)),
+              "pw_program_frequencies")
+    return out, int(n_foreign.value), (_tuple_dict(first) if n_foreign.value else None)
+
+
+def memory_boundary_trace(airs, cap_log_height: int, table_bytes: int = 0, bus: int = BUS_MEMORY, out: torch.Tensor | None = None):
+    """pw_memory_boundary_trace -> (trace: 18 x 2^log_height Montgomery words, column-major — None unless status is 0; log_height;
+    touched locations; status: a key of STATUS). Status 1: call again with cap_log_height = the log_height returned. The trace pairs
+    every location's first receive with its last send and proves nothing: check_segment_buses([... , boundary], buses=[bus]) does."""
+    if out is None:
+        out = torch.empty(BOUNDARY_WIDTH << cap_log_height, dtype=torch.int32, device="cuda")
+    assert out.numel() >= BOUNDARY_WIDTH << cap_log_height
+    recs, n = _records(airs)
+    lh, locations, status = C.c_uint32(), C.c_uint64(), C.c_uint32()
+    abi.check(lib.pw_memory_boundary_trace(recs, n, bus, int(table_bytes), out.data_ptr(), cap_log_height, C.byref(lh), C.byref(locations), C.byref(status)),
+              "pw_memory_boundary_trace")
+    trace = out[:BOUNDARY_WIDTH << lh.value] if status.value == 0 else None
+    return trace, int(lh.value), int(locations.value), int(status.value)
+
+
+def connector_trace(airs, bus: int = BUS_EXEC) -> torch.Tensor:
+    """The connector's 2 x 2 main trace [pc0, pc1, ts0, ts1] (Montgomery) from what check_segment_buses leaves over on the execution
+    bridge: exactly the initial state (received once and never sent) and the final one (sent once and never received)."""
+    _, tuples = prover.check_segment_buses(airs, buses=[bus], tuple_cap=8)
+    start = [t for t in tuples if t["net_multiplicity"] == P - 1 and t["n_args"] == 2]
+    end = [t for t in tuples if t["net_multiplicity"] == 1 and t["n_args"] == 2]
+    if len(tuples) != 2 or len(start) != 1 or len(end) != 1:
+        raise ValueError(f"the execution bridge (bus {bus}) does not leave one initial and one final state: {tuples}")
+    (pc0, ts0), (pc1, ts1) = start[0]["args"], end[0]["args"]
+    return _to_device([pc0, pc1, ts0, ts1])
+
+
+def last_stats() -> dict:
+    """pw_system_traces_last_stats of this thread (include/powdr_prover.h PwSystemTraceStats) as a dict, with the scratch bytes held now
+    and the most the last call held at once"""
+    st = PwSystemTraceStats()
+    lib.pw_system_traces_last_stats(C.byref(st))
+    out = {n: int(getattr(st, n)) for n, _ in PwSystemTraceStats._fields_}
+    out.update(peak_bytes=int(lib.pw_system_traces_peak_bytes()), scratch_bytes=int(lib.pw_system_traces_scratch_bytes()))
+    return out
+
+
+def set_boundary_start_slots(log_slots: int) -> None:
+    """pw_memory_boundary_set_start_slots: 2^log_slots slots (6 .. 30) in the first address table of this thread's later
+    memory_boundary_trace calls; 0: the default (2^16)"""
+    abi.check(lib.pw_memory_boundary_set_start_slots(int(log_slots)), "pw_memory_boundary_set_start_slots")
+
+
+def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int = 100, pow_bits: int = 0, pc_step: int = 4, table_bytes: int = 0,
+                  cap_log_height: int = 16):
+    """airs: [dict(prover, trace (device tensor), log_h, ...)] — every AIR that sends on the execution bridge, the memory bus and the
+    PC lookup, traces made. Appends the program, connector and boundary AIRs as dicts of the same shape (name, role "system", air =
+    the SystemAir, width, log_h, cons, inter, trace, prover, pre) and returns the list. periphery (tracegen.Periphery): its histograms
+    receive the boundary AIR's range and byte lookups (_apc_apply_bus on its trace) — call this BEFORE the periphery traces are made
+    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). Raises on foreign instructions, on a boundary status other than 0 and on an execution bridge that is not a chain."""
+    from .segment_workload import BusReplay
+
+    seg = [(a["prover"], a["trace"].data_ptr(), a["log_h"]) for a in airs]
+    bnd = boundary_air()
+    trace, lh, locations, status = memory_boundary_trace(seg, cap_log_height, table_bytes)
+    if status == 1:
+        trace, lh, locations, status = memory_boundary_trace(seg, lh, table_bytes)
+    if status:
+        raise ValueError(f"memory boundary: {STATUS[status]} ({locations} locations)")
+    BusReplay(bnd.inter, 1 << lh)(trace.data_ptr(), periphery)
+    prog = program_air(program_table)
+    freq, n_foreign, first = program_frequencies(seg, prog.fixed_table(), prog.log_h, pc_base, pc_step)
+    if n_foreign:
+        raise ValueError(f"{n_foreign} executed instructions are not in the program, the first: {first}")
+    con = connector_air()
+    out = list(airs)
+    for air, t, h in ((prog, freq, prog.log_h), (con, connector_trace(seg), 1), (bnd, trace, lh)):
+        p = air.make_prover(num_queries, pow_bits)
+        out.append(dict(name=air.name, role="system", air=air, width=air.width, log_h=h, cons=air.cons, inter=air.inter, trace=t, prover=p,
+                        pre=(air.fixed_table(), air.pre_width, air.log_h) if air.pre_width else None))
+    return out

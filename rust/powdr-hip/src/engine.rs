@@ -136,12 +136,9 @@ impl HipEngine {
         Ok(HipSegmentProof { air_ids, log_heights, words })
     }
 
-    /// The bus half of `debug_proving_ctx` (`prove_mock`, openvm-riscv/src/lib.rs:288-294) on the device: every bus of the segment
-    /// balanced tuple by tuple, or the tuples that are not, each with the (air, interaction, row) of one contribution. Nothing is
-    /// committed; `bus_ids` empty = every bus the AIRs mention. `air` of a tuple indexes the AIRs of `ctx` with a non-empty trace.
-    pub fn debug_segment_buses(&self, ctx: &ProvingContext<HipBackend>, bus_ids: &[u32], tuple_cap: usize)
-                               -> Result<(Vec<ffi::PwBusSummary>, Vec<ffi::PwBusTuple>), HipError> {
-        let airs: Vec<ffi::PwSegmentAir> = ctx.per_trace.iter().filter(|(_, c)| c.common_main.height() != 0).map(|(air_id, c)| {
+    /// The `PwSegmentAir` list of a context: its AIRs with a non-empty trace, in order, nothing handed over.
+    fn segment_airs(&self, ctx: &ProvingContext<HipBackend>) -> Vec<ffi::PwSegmentAir> {
+        ctx.per_trace.iter().filter(|(_, c)| c.common_main.height() != 0).map(|(air_id, c)| {
             let m: &DeviceMatrix<BabyBear> = &c.common_main;
             ffi::PwSegmentAir {
                 prover: self.provers[*air_id].handle,
@@ -149,7 +146,15 @@ impl HipEngine {
                 log_height: m.height().trailing_zeros(),
                 flags: 0,
             }
-        }).collect();
+        }).collect()
+    }
+
+    /// The bus half of `debug_proving_ctx` (`prove_mock`, openvm-riscv/src/lib.rs:288-294) on the device: every bus of the segment
+    /// balanced tuple by tuple, or the tuples that are not, each with the (air, interaction, row) of one contribution. Nothing is
+    /// committed; `bus_ids` empty = every bus the AIRs mention. `air` of a tuple indexes the AIRs of `ctx` with a non-empty trace.
+    pub fn debug_segment_buses(&self, ctx: &ProvingContext<HipBackend>, bus_ids: &[u32], tuple_cap: usize)
+                               -> Result<(Vec<ffi::PwBusSummary>, Vec<ffi::PwBusTuple>), HipError> {
+        let airs = self.segment_airs(ctx);
         let mut summaries = vec![ffi::PwBusSummary::default(); if bus_ids.is_empty() { 4096 } else { bus_ids.len() }];
         let mut tuples = vec![ffi::PwBusTuple::default(); tuple_cap];
         let (mut n_summaries, mut n_tuples) = (0usize, 0usize);
@@ -161,6 +166,20 @@ impl HipEngine {
         summaries.truncate(n_summaries);
         tuples.truncate(n_tuples);
         Ok((summaries, tuples))
+    }
+
+    /// The memory boundary AIR's trace from what the AIRs of `ctx` put on the memory bus, into `d_trace_out`
+    /// (18 x 2^cap_log_height words on the device): `(status, log_height, touched locations)`, status 0 = written. The caller adds
+    /// the AIR to the context and runs `debug_segment_buses` on the bus: this call pairs first and last accesses, it proves nothing.
+    pub fn memory_boundary_trace(&self, ctx: &ProvingContext<HipBackend>, memory_bus: u32, d_trace_out: *mut u32, cap_log_height: u32)
+                                 -> Result<(u32, u32, u64), HipError> {
+        let airs = self.segment_airs(ctx);
+        let (mut log_height, mut status, mut n_locations) = (0u32, 0u32, 0u64);
+        HipError::from_result(unsafe {
+            ffi::pw_memory_boundary_trace(airs.as_ptr(), airs.len(), memory_bus, 0, d_trace_out, cap_log_height, &mut log_height, &mut n_locations,
+                                          &mut status)
+        })?;
+        Ok((status, log_height, n_locations))
     }
 
     /// The CPU verification step (`verify_app_proof::<BabyBearPoseidon2CpuEngine>`, openvm-riscv/src/lib.rs:337-341)

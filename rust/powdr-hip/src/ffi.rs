@@ -287,6 +287,17 @@ pub struct PwBusTuple {
     pub n_contributions: u64,
 }
 #[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwSystemTraceStats {
+    pub table_slots: u64,
+    pub occupied_slots: u64,
+    pub tables: u64,
+    pub walked: u64,
+    pub additions: u64,
+    pub lds_atomics: u64,
+    pub global_atomics: u64,
+}
+#[repr(C)]
 #[derive(Clone, Copy)]
 pub struct PwAirDescription {
     pub width: u32,
@@ -351,6 +362,17 @@ extern "C" {
                                   n_summaries: *mut usize, tuples: *mut PwBusTuple, tuple_cap: usize, n_tuples: *mut usize) -> c_int;
     pub fn pw_bus_check_scratch_bytes() -> usize;
     pub fn pw_bus_check_peak_bytes() -> usize;
+    /// The program AIR's multiplicity column from what the other AIRs send on the PC-lookup bus; tuples that equal no table row are counted.
+    pub fn pw_program_frequencies(airs: *const PwSegmentAir, n_airs: usize, bus: u32, pc_base: u32, pc_step: u32, d_program: *const u32,
+                                  log_h: u32, d_freq_out: *mut u32, n_foreign: *mut u64, first_foreign: *mut PwBusTuple) -> c_int;
+    /// The memory boundary AIR's trace (18 columns, one row per touched location, sorted) from the memory bus; `status` 0 = written.
+    pub fn pw_memory_boundary_trace(airs: *const PwSegmentAir, n_airs: usize, bus: u32, table_bytes: usize, d_trace_out: *mut u32,
+                                    cap_log_height: u32, log_height: *mut u32, n_locations: *mut u64, status: *mut u32) -> c_int;
+    pub fn pw_system_traces_scratch_bytes() -> usize;
+    pub fn pw_system_traces_peak_bytes() -> usize;
+    pub fn pw_system_traces_last_stats(out: *mut PwSystemTraceStats);
+    /// 2^log_slots slots in the first address table of this thread's later `pw_memory_boundary_trace` calls (0 = default)
+    pub fn pw_memory_boundary_set_start_slots(log_slots: u32) -> c_int;
     pub fn pw_verify(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32, bytecode_len: usize,
                      cons_spans: *const u32, n_constraints: usize, proof_words: *const u32, n_words: usize) -> c_int;
     pub fn pw_verify_logup(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32,
