@@ -8,7 +8,7 @@
  *               /root/reference/openvm-riscv/src/lib.rs:327-341 (sdk.app_prover(exe).prove + verify_app_proof)
  *   engines     /root/reference/openvm/src/lib.rs:69-95 (BabyBearPoseidon2CpuEngine / ...GpuEngine)
  *   the AIR     /root/reference/openvm/src/powdr_extension/chip.rs:94-130 (PowdrAir::eval: current-row
- *               constraints `assert_zero(expr)`, no public values, no cached/preprocessed trace; the periphery
+ *               constraints `assert_zero(expr)`, no public values of its own (system AIRs have them: pw_prover_create_public below), no cached/preprocessed trace; the periphery
  *               chips that receive its lookups DO keep their tables in preprocessed columns — segment proofs take
  *               those through pw_prover_create_preprocessed, "pw-stark v1 + preprocessed" below)
  * The trait's method list lives in the un-vendored `openvm-stark-backend` crate, so this
@@ -118,6 +118,32 @@ PwProver* pw_prover_create_transition(const PwStarkConfig* cfg, uint32_t width, 
                                       size_t n_interactions, const uint32_t* inter_spans, size_t n_inter_spans,
                                       const uint32_t* inter_bytecode, size_t inter_bytecode_len);
 uint32_t pw_prover_row_flags(const PwProver* p);
+
+/* ---- public values: "pw-stark v1 + public values"  --------------------------------------------------------------
+ * An AIR with PUBLIC VALUES (Plonky3's `builder.public_values()`, OpenVM's `AirProvingContext.public_values`): field elements that are
+ * part of the statement, known to prover and verifier, fixed per proof and not when the prover is made. With W1 = width + pre_width, in a
+ * CONSTRAINT program operand 2 W1 + 3 + k, k < n_public <= 256, is public value k (behind the row layout of pw_prover_create_transition,
+ * whether or not the AIR is row-aware); its degree is 0, like is_transition, and the bound of 3 stays. INTERACTION operands stay below W1.
+ * NULL for an operand at or above 2 W1 + 3 + n_public, n_public > 256, a constraint of degree > 3, a malformed program. Every other
+ * argument as pw_prover_create_transition; with n_public = 0 the prover IS a pw_prover_create_transition prover (same proof words).
+ * pw_prover_row_flags is derived as there, from the operands in [W1, 2 W1 + 3): an AIR may have public values with row flags 0.
+ * The values are not columns: they live in a small device array that every expression kernel receives as an argument and reads at the
+ * (wave-uniform) index the program carries; the programs, the generated kernels and their on-disk cache key never depend on them.
+ * pw_prover_set_public_values: `values` = n host words, canonical; -1 when n != n_public or a word is >= p. The prover keeps a host
+ * copy, so one prover serves segment after segment. A segment proof snapshots the values when the call begins and uploads the snapshot
+ * on the calling thread's launch stream: setting new values after the call has returned never races with it.
+ * A prover with n_public > 0 proves in segments only (pw_prover_prove, _prove_consuming, _trace_root, pw_prove_airs: -1), is never
+ * streamed (pw_segment_last_modes reports 0; the memory plan counts it resident, as a row-aware AIR) and makes pw_prove_segment return
+ * -1, before any GPU work, while its values have never been set — it does not prove with zeros in their place.
+ * pw_prover_check_constraints reads public operands from the values set (-1: none set). The proof of a segment with at least one such
+ * AIR carries magic PWS6 and, right after the header words, the values of every such AIR in AIR order (canonical words). */
+PwProver* pw_prover_create_public(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                  const uint32_t* d_pre, uint32_t n_public, const uint32_t* cons_bytecode, size_t bytecode_len,
+                                  const uint32_t* cons_spans, size_t n_constraints, const uint32_t* interactions,
+                                  size_t n_interactions, const uint32_t* inter_spans, size_t n_inter_spans,
+                                  const uint32_t* inter_bytecode, size_t inter_bytecode_len);
+uint32_t pw_prover_n_public(const PwProver* p);
+int pw_prover_set_public_values(PwProver* p, const uint32_t* values, size_t n);
 
 /* Prove one trace (column-major, width x 2^log_height, Montgomery words, device).
  * *proof_words points at host memory owned by the prover, valid until the next call. */
@@ -393,6 +419,48 @@ int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const PwAirDescript
  * another proof against descriptions with one, returns 1. Without a row-aware AIR: exactly pw_verify_segment_preprocessed. */
 int pw_verify_segment_transition(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
                                  int logup, const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
+
+/* The public values of one AIR as the verifier is told them (one entry per AIR of a segment): n = how many the AIR has
+ * (0: none; it comes from the description, never from the proof), expected = what they must be (canonical), NULL = accept what the proof
+ * carries (pw_segment_proof_public_values reads them out). */
+typedef struct PwAirPublic {
+    uint32_t n;
+    const uint32_t* expected;
+} PwAirPublic;
+
+/* pw_verify_segment_transition for segments whose AIRs may have public values (pub == NULL or every n == 0: exactly that function).
+ * Constraint operands below 2 (width + pre[i].width) + 3 + pub[i].n are valid; an AIR with public values is held to what its prover entry
+ * checks (a constraint of degree > 3, an interaction operand at or above width + pre[i].width, n > 256: 15). The values enter the
+ * transcript and the constraint identity at zeta. Additional code 17 = the proof's public values of some AIR differ from `expected`;
+ * a PWS6 proof against descriptions without public values, or another proof against descriptions with some, returns 1. */
+int pw_verify_segment_public(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, const PwAirPublic* pub,
+                             size_t n_airs, int logup, const uint32_t* proof_words, size_t n_words, int check_balance, uint32_t* total_sum4);
+/* AIR `air`'s public values as a proof carries them: up to `cap` canonical words to `out` (may be NULL), returns their number
+ * (pub[air].n). (size_t)-1: the proof's header does not match the descriptions (nothing else of the proof is looked at: verify it). */
+size_t pw_segment_proof_public_values(const PwAirDescription* airs, const PwAirPublic* pub, size_t n_airs, const uint32_t* proof_words,
+                                      size_t n_words, size_t air, uint32_t* out, size_t cap);
+
+/* N segment proofs are CONSECUTIVE pieces of one execution: every segment verifies (pw_verify_segment_public) and every link holds from
+ * each segment to the next — link {air_from, index_from, air_to, index_to}: public value index_from of AIR air_from in segment s equals
+ * public value index_to of AIR air_to in segment s + 1, for every s < n_segments - 1 (the connector's final state = the next connector's
+ * initial state). Returns 0; the segment verifier's code of the first failing segment with *where = its index; 18 = a link does not hold
+ * (or names a value the descriptions do not have), *where = s * n_links + link. Host only. `where` may be NULL.
+ * NOT checked: that all segments ran the same program — compare the `pre` root of the program AIR across the segments; that is the caller's. */
+typedef struct PwChainSegment {
+    const PwAirDescription* airs;
+    const PwAirPreprocessed* pre;   /* may be NULL */
+    const PwAirPublic* pub;         /* may be NULL */
+    size_t n_airs;
+    int logup;
+    const uint32_t* proof;
+    size_t n_words;
+    int check_balance;
+} PwChainSegment;
+typedef struct PwChainLink {
+    uint32_t air_from, index_from, air_to, index_to;
+} PwChainLink;
+int pw_verify_segment_chain(const PwStarkConfig* cfg, const PwChainSegment* segments, size_t n_segments, const PwChainLink* links,
+                            size_t n_links, size_t* where);
 
 /* Host verification of pw_prove_airs' proofs. With shared_bus_seed the seed is recomputed from the trace roots inside the
  * proofs and every proof must have used it. Returns 0; ((air index + 1) << 8) | code of the first failing proof

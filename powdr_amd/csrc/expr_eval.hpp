@@ -34,10 +34,13 @@ constexpr int kStackCap = POWDR_EXPR_STACK_CAPACITY;
 // COLUMN_OPERANDS = false: PUSH_APC operand is an element offset (reference encoding);
 //                   true:  operand is a column index, cell = trace[operand * col_stride + r]
 //                          (used by the quotient kernel, whose matrices exceed 2^32 elements).
-template <int STRIDE, bool COLUMN_OPERANDS = false>
+// PUB (constraint programs of an AIR with public values): a PUSH_APC operand at or above pub_base is word
+//                          operand - pub_base of `pub` (Montgomery) — a wave-uniform address, hence a scalar load.
+template <int STRIDE, bool COLUMN_OPERANDS = false, bool PUB = false>
 __device__ __forceinline__ uint32_t eval_expr(const uint32_t* __restrict__ bc, uint32_t len,
                                               const uint32_t* __restrict__ trace, size_t r,
-                                              uint32_t* __restrict__ stk, size_t col_stride = 1) {
+                                              uint32_t* __restrict__ stk, size_t col_stride = 1,
+                                              const uint32_t* __restrict__ pub = nullptr, uint32_t pub_base = 0xffffffffu) {
     uint32_t top = 0;  // cached top of stack (valid when sp > 0)
     int sp = 0;        // number of live entries, including `top`
     for (uint32_t ip = 0; ip < len;) {
@@ -46,7 +49,9 @@ __device__ __forceinline__ uint32_t eval_expr(const uint32_t* __restrict__ bc, u
             const uint32_t operand = bc[ip++];
             if (sp > 0 && sp < kStackCap) stk[(sp - 1) * STRIDE] = top;
             sp = sp < kStackCap ? sp + 1 : sp;
-            if (op == POWDR_OP_PUSH_APC)
+            if (PUB && op == POWDR_OP_PUSH_APC && operand >= pub_base)
+                top = pub[operand - pub_base];
+            else if (op == POWDR_OP_PUSH_APC)
                 top = COLUMN_OPERANDS ? trace[(size_t)operand * col_stride + r] : trace[(size_t)operand + r];
             else
                 top = bb::to_monty(operand);

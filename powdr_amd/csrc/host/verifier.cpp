@@ -338,10 +338,12 @@ namespace {
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3"
 constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": at least one AIR has preprocessed columns
 constexpr uint32_t kMagic5 = 0x35535750u;  // "PWS5": at least one AIR is row-aware
+constexpr uint32_t kMagic6 = 0x36535750u;  // "PWS6": at least one AIR has public values
 
 struct SegShapeV {
     uint32_t W, nc, n_int, log_h;
     uint32_t Wf, W1;  // preprocessed columns, W + Wf
+    uint32_t np;      // public values: constraint operands 2 W1 + 3 + k, k < np
     uint32_t rf, Wg;  // the row layout: kRowsNext | kRowsSelector of the constraint programs; W1 if two-point, else 0
     Digest pre_root;  // Montgomery
     size_t H, N, n_g, Wp, K, koff;
@@ -350,9 +352,12 @@ struct SegShapeV {
     uint32_t max_args;
 };
 
-// pre: NULL = no AIR has preprocessed columns (pw_verify_segment); rows: constraint operands over the row layout
+// pre: NULL = no AIR has preprocessed columns (pw_verify_segment); rows: constraint operands over the row layout;
+// pub: NULL = no AIR has public values, else one entry per AIR (only with rows). pub_out (may be NULL): the proof's public
+// values, canonical, AIR after AIR.
 int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs, int logup_flag,
-                        const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4, bool rows = false) {
+                        const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4, bool rows = false,
+                        const PwAirPublic* pub = nullptr, std::vector<uint32_t>* pub_out = nullptr) {
     if (!cfg || !airs || !n_airs || !proof) return 15;
     const bool lg = logup_flag != 0;
     const size_t A = n_airs;
@@ -365,7 +370,9 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         if (d.log_height < 1 || d.log_height > 26 || !d.width) return 15;
         s.W = d.width; s.nc = (uint32_t)d.n_constraints; s.log_h = d.log_height; s.n_int = lg ? (uint32_t)d.n_interactions : 0;
         s.Wf = pre ? pre[a].width : 0;
-        if ((uint64_t)s.W + s.Wf > (rows ? 0x7ffffff0ull : 0xffffffffull)) return 15;
+        s.np = pub ? pub[a].n : 0;
+        if (s.np > pw::kMaxPublicValues) return 15;
+        if ((uint64_t)s.W + s.Wf > (!rows ? 0xffffffffull : s.np ? 0x7fffff00ull : 0x7ffffff0ull)) return 15;
         s.W1 = s.W + s.Wf;
         for (int k = 0; k < 8; ++k) {
             if (s.Wf && pre[a].root8[k] >= bb::P) return 15;
@@ -378,12 +385,18 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             if ((size_t)d.cons_spans[2 * k] + d.cons_spans[2 * k + 1] > d.bytecode_len) return 15;
             if (!rows) continue;
             const uint32_t* c = d.cons_bytecode + d.cons_spans[2 * k];
-            if (!pw::postfix_columns_below(c, d.cons_spans[2 * k + 1], 2 * s.W1 + 3)) return 15;  // (before the flags pick the magic)
+            if (!pw::postfix_columns_below(c, d.cons_spans[2 * k + 1], 2 * s.W1 + 3 + s.np)) return 15;  // (before the flags pick the magic)
             s.rf |= pw::postfix_row_flags(c, d.cons_spans[2 * k + 1], s.W1);
+            // an AIR with public values is checked as its prover entry checks it: well-formed programs of degree at most 3
+            if (s.np && pw::postfix_degree(c, d.cons_spans[2 * k + 1], 2 * s.W1 + 2, 2 * s.W1 + 3) > 3) return 15;
         }
         s.Wg = (s.rf & pw::kRowsNext) ? s.W1 : 0;
         if (lg) {
             if (!pw::interaction_table_ok(d.interactions, d.n_interactions, d.inter_spans, d.n_inter_spans, d.inter_bytecode_len, &s.max_args)) return 15;
+            for (size_t k = 0; s.np && k < d.n_inter_spans; ++k)  // (interaction operands stay below W1: current-row columns only)
+                if ((size_t)d.inter_spans[2 * k] + d.inter_spans[2 * k + 1] > d.inter_bytecode_len ||
+                    !pw::postfix_columns_below(d.inter_bytecode + d.inter_spans[2 * k], d.inter_spans[2 * k + 1], s.W1))
+                    return 15;
             s.gstarts = pw::logup_group_starts(d.interactions, d.n_interactions, d.inter_spans, d.inter_bytecode);
             if (s.gstarts.empty()) s.gstarts.push_back(0);
             s.n_g = s.gstarts.size() - 1;
@@ -402,12 +415,27 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
     auto get_digest = [&]() { Digest d; for (auto& w : d.w) w = get_m(); return d; };
     auto get_ext = [&]() { Ext e; for (auto& w : e.c) w = get_m(); return e; };
 
-    bool any_pre = false, any_rows = false;
-    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; }
-    std::vector<uint32_t> hdr = {any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries, cfg->pow_bits};
+    bool any_pre = false, any_rows = false, any_pub = false;
+    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; any_pub = any_pub || sh[a].np; }
+    std::vector<uint32_t> hdr = {any_pub ? kMagic6 : any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3, (uint32_t)A, lg ? 1u : 0u, cfg->num_queries,
+                                 cfg->pow_bits};
     for (size_t a = 0; a < A; ++a) for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) hdr.push_back(x);
     for (uint32_t h : hdr) if (get() != h) return 1;
     for (size_t i = 0; i < len; ++i) if (proof[i] >= bb::P) return 13;
+    // the public values, right after the header (their number comes from the descriptions): canonical here, compared with what the
+    // caller expects; Montgomery for the transcript and the constraint identity
+    std::vector<std::vector<uint32_t>> pubv(A);
+    for (size_t a = 0; a < A; ++a) {
+        for (uint32_t k = 0; k < sh[a].np; ++k) {
+            const uint32_t w = get();
+            if (pub_out) pub_out->push_back(w);
+            pubv[a].push_back(bb::to_monty(w));
+        }
+    }
+    if (short_read) return 10;
+    for (size_t a = 0; a < A; ++a)
+        for (uint32_t k = 0; k < sh[a].np && pub[a].expected; ++k)
+            if (pub[a].expected[k] != bb::from_monty(pubv[a][k])) return 17;
     Transcript ch;
     for (uint32_t h : hdr) ch.observe(bb::to_monty(h % bb::P));
     // the verifying key's preprocessed commitments (not in the proof)
@@ -422,6 +450,13 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         if (!sh[a].rf) continue;
         ch.observe(bb::to_monty((uint32_t)a % bb::P));
         ch.observe(bb::to_monty(sh[a].rf));
+    }
+    // the AIRs with public values: index, count, values
+    for (size_t a = 0; a < A; ++a) {
+        if (!sh[a].np) continue;
+        ch.observe(bb::to_monty((uint32_t)a % bb::P));
+        ch.observe(bb::to_monty(sh[a].np));
+        ch.observe_n(pubv[a].data(), sh[a].np);
     }
 
     const Digest t_root = get_digest();
@@ -462,7 +497,8 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
         uint32_t cw = s.W1;
         std::vector<Ext> rv;
         if (rows) {
-            rv.assign(2 * (size_t)s.W1 + 3, bb::ext_zero());
+            rv.assign(2 * (size_t)s.W1 + 3 + s.np, bb::ext_zero());
+            for (size_t k = 0; k < s.np; ++k) rv[2 * (size_t)s.W1 + 3 + k] = bb::ext_from_base(pubv[a][k]);
             for (size_t k = 0; k < s.W1; ++k) rv[k] = o[k];
             for (size_t k = 0; k < s.Wg; ++k) rv[s.W1 + k] = o[K1 + s.Wp + k];
             const Ext trans = bb::ext_sub(zeta, bb::ext_from_base(g_inv));
@@ -470,7 +506,7 @@ int verify_segment_impl(const PwStarkConfig* cfg, const PwAirDescription* airs, 
             rv[2 * (size_t)s.W1 + 1] = bb::ext_mul(zh, bb::ext_inv(trans));
             rv[2 * (size_t)s.W1 + 2] = trans;
             cv = rv.data();
-            cw = 2 * s.W1 + 3;
+            cw = 2 * s.W1 + 3 + s.np;
         }
         Ext acc = bb::ext_zero();
         for (size_t k = 0; k < d.n_constraints; ++k) {
@@ -634,6 +670,64 @@ extern "C" int pw_verify_segment_preprocessed(const PwStarkConfig* cfg, const Pw
 extern "C" int pw_verify_segment_transition(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, size_t n_airs,
                                             int logup_flag, const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
     return verify_segment_impl(cfg, airs, pre, n_airs, logup_flag, proof, len, check_balance, total_sum4, true);
+}
+
+// "pw-stark v1 + public values" (DESIGN.md §5k): pub[a] = how many public values AIR a has and, if the caller knows what they must be,
+// those; pub == NULL or every n == 0: exactly pw_verify_segment_transition.
+extern "C" int pw_verify_segment_public(const PwStarkConfig* cfg, const PwAirDescription* airs, const PwAirPreprocessed* pre, const PwAirPublic* pub,
+                                        size_t n_airs, int logup_flag, const uint32_t* proof, size_t len, int check_balance, uint32_t* total_sum4) {
+    return verify_segment_impl(cfg, airs, pre, n_airs, logup_flag, proof, len, check_balance, total_sum4, true, pub);
+}
+
+// the public values AIR `air` carries in a proof whose header matches the descriptions (nothing else of the proof is checked)
+extern "C" size_t pw_segment_proof_public_values(const PwAirDescription* airs, const PwAirPublic* pub, size_t n_airs, const uint32_t* proof,
+                                                 size_t len, size_t air, uint32_t* out, size_t cap) {
+    if (!airs || !pub || !proof || !n_airs || air >= n_airs || len < 5 + 4 * n_airs) return (size_t)-1;
+    size_t total = 0, off = 0;
+    for (size_t a = 0; a < n_airs; ++a) {
+        if (pub[a].n > pw::kMaxPublicValues) return (size_t)-1;
+        if (a < air) off += pub[a].n;
+        total += pub[a].n;
+    }
+    const bool lg = proof[2] != 0;
+    if (proof[0] != kMagic6 || !total || proof[1] != n_airs || proof[2] > 1) return (size_t)-1;
+    for (size_t a = 0; a < n_airs; ++a) {
+        const uint32_t want[4] = {airs[a].log_height, airs[a].width, (uint32_t)airs[a].n_constraints, lg ? (uint32_t)airs[a].n_interactions : 0u};
+        if (memcmp(proof + 5 + 4 * a, want, sizeof want)) return (size_t)-1;
+    }
+    const uint32_t* v = proof + 5 + 4 * n_airs;
+    if (len < 5 + 4 * n_airs + total) return (size_t)-1;
+    for (size_t k = 0; out && k < pub[air].n && k < cap; ++k) out[k] = v[off + k];
+    return pub[air].n;
+}
+
+// N segment proofs are consecutive pieces of one execution: every one verifies and every link holds from each segment to the next
+extern "C" int pw_verify_segment_chain(const PwStarkConfig* cfg, const PwChainSegment* segments, size_t n_segments, const PwChainLink* links,
+                                       size_t n_links, size_t* where) {
+    if (!cfg || !segments || !n_segments || (n_links && !links)) return 15;
+    std::vector<std::vector<uint32_t>> values(n_segments);
+    for (size_t s = 0; s < n_segments; ++s) {
+        const PwChainSegment& g = segments[s];
+        const int rc = verify_segment_impl(cfg, g.airs, g.pre, g.n_airs, g.logup, g.proof, g.n_words, g.check_balance, nullptr, true, g.pub, &values[s]);
+        if (rc) { if (where) *where = s; return rc; }
+    }
+    // where public value `index` of AIR `air` sits among a segment's values; false: no such value
+    auto locate = [&](const PwChainSegment& g, uint32_t air, uint32_t index, size_t& off) {
+        if (!g.pub || air >= g.n_airs || index >= g.pub[air].n) return false;
+        off = index;
+        for (uint32_t a = 0; a < air; ++a) off += g.pub[a].n;
+        return true;
+    };
+    for (size_t s = 0; s + 1 < n_segments; ++s)
+        for (size_t l = 0; l < n_links; ++l) {
+            size_t from = 0, to = 0;
+            if (!locate(segments[s], links[l].air_from, links[l].index_from, from) || !locate(segments[s + 1], links[l].air_to, links[l].index_to, to) ||
+                values[s][from] != values[s + 1][to]) {
+                if (where) *where = s * n_links + l;
+                return 18;
+            }
+        }
+    return 0;
 }
 
 // Boundaries of the LogUp groups the prover and the verifier derive from an interaction table (logup_groups.hpp):

@@ -38,10 +38,13 @@ struct Generated {
     std::vector<Unit> units;
     uint32_t n_chunks = 0;
     size_t est_instructions = 0;
+    bool has_pub = false;  // the kernels take the array of public values as one more (last) argument
 };
 
 // Quotient numerator on the extended domain. Kernel signature (all units):
 //   (const uint32_t* lde, const uint32_t* plde, uint64_t N, const Ext* apow, Ext al, const Ext* blpow, uint32_t* part)
+// and, when a constraint program holds a public form (xbc *_PUB; Generated::has_pub), one more: const uint32_t* pub — the values are read
+// from it at literal indices (scalar loads), so the source depends on the programs and never on the values.
 // part[(chunk * 4 + k) * N + j] = coordinate k of the chunk's share of
 //   sum_c apow[c] C_c(row j) + sum_g apow[nc + g] (q_g prod_i d_i - sum_i m_i prod_{l != i} d_l)      (lg == nullptr: first sum only)
 Generated gen_quotient(const XbcView& cons, const LogupView* lg, uint32_t chunk_cost, uint32_t chunks_per_unit);

@@ -13,9 +13,10 @@
 namespace pw {
 
 // Degree in the trace columns of a post-fix program; kBadDegree if malformed. Column operand `deg0` (none by default) has degree 0:
-// is_transition = x - g^-1 of the row layout, Plonky3's degree_multiple.
+// is_transition = x - g^-1 of the row layout, Plonky3's degree_multiple; so have the operands from `deg0_from` on: the
+// public values behind the row layout.
 constexpr int kBadDegree = 99;
-inline int postfix_degree(const uint32_t* bc, uint32_t len, uint32_t deg0 = 0xffffffffu) {
+inline int postfix_degree(const uint32_t* bc, uint32_t len, uint32_t deg0 = 0xffffffffu, uint32_t deg0_from = 0xffffffffu) {
     int st[POWDR_EXPR_STACK_CAPACITY];
     int sp = 0;
     for (uint32_t ip = 0; ip < len;) {
@@ -24,7 +25,7 @@ inline int postfix_degree(const uint32_t* bc, uint32_t len, uint32_t deg0 = 0xff
             case POWDR_OP_PUSH_APC:
             case POWDR_OP_PUSH_CONST:
                 if (sp >= POWDR_EXPR_STACK_CAPACITY || ip >= len) return kBadDegree;
-                st[sp++] = op == POWDR_OP_PUSH_APC && bc[ip] != deg0 ? 1 : 0;
+                st[sp++] = op == POWDR_OP_PUSH_APC && bc[ip] != deg0 && bc[ip] < deg0_from ? 1 : 0;
                 ++ip;
                 break;
             case POWDR_OP_ADD:
@@ -64,14 +65,16 @@ inline bool postfix_columns_below(const uint32_t* bc, uint32_t len, uint32_t wid
 
 // The row layout of the constraint programs, W1 = main + preprocessed columns: operand c < W1 is column c on the
 // current row, W1 <= c < 2 W1 column c - W1 on the next row, 2 W1 / 2 W1 + 1 / 2 W1 + 2 are is_first_row / is_last_row / is_transition.
-// The bits a (well-formed) program's operands set: kRowsNext (it reads a next-row operand), kRowsSelector (it reads a selector).
+// The bits a (well-formed) program's operands set: kRowsNext (it reads a next-row operand), kRowsSelector (it reads a selector);
+// operands from 2 W1 + 3 on (public values) set none.
+constexpr uint32_t kMaxPublicValues = 256u;
 constexpr uint32_t kRowsNext = 1u, kRowsSelector = 2u;
 inline uint32_t postfix_row_flags(const uint32_t* bc, uint32_t len, uint32_t w1) {
     uint32_t f = 0;
     for (uint32_t ip = 0; ip + 1 < len;) {
         const uint32_t op = bc[ip++];
         if (op == POWDR_OP_PUSH_APC || op == POWDR_OP_PUSH_CONST) {
-            if (op == POWDR_OP_PUSH_APC && bc[ip] >= w1) f |= bc[ip] < 2 * (uint64_t)w1 ? kRowsNext : kRowsSelector;
+            if (op == POWDR_OP_PUSH_APC && bc[ip] >= w1 && bc[ip] < 2 * (uint64_t)w1 + 3) f |= bc[ip] < 2 * (uint64_t)w1 ? kRowsNext : kRowsSelector;
             ++ip;
         }
     }

@@ -138,13 +138,15 @@ __global__ __launch_bounds__(kBlock) void scan_write_kernel(const Ext* __restric
 // acc = sum_k apow[k] C_k + sum_g apow[nc+g] (q_g den_g - num_g) + apow[nc+G] is_first (phi - sum q)
 //       + apow[nc+G+1] is_trans (phi' - phi - sum q') + apow[nc+G+2] is_last (phi - S);  q = acc / Z_H
 // with den_g = prod_{i in g} d_i, num_g = sum_{i in g} m_i prod_{j != i} d_j, G = number of groups
-template <bool XBC, bool FAST>
+// PUB: the CONSTRAINT programs may read public values from `pub` (interactions never do)
+template <bool XBC, bool FAST, bool PUB>
 __global__ __launch_bounds__(kBlock) void quotient_logup_kernel(const uint32_t* __restrict__ lde, const uint32_t* __restrict__ plde,
                                                                  size_t N, const uint32_t* __restrict__ bytecode,
                                                                  const uint32_t* __restrict__ spans, uint32_t nc, LogupProgram lp,
                                                                  const Ext* __restrict__ apow, Ext al, const Ext* __restrict__ blpow,
                                                                  Ext S, uint32_t zval_even, uint32_t zval_odd, uint32_t shift,
-                                                                 uint32_t wN, uint32_t ginv, uint32_t* __restrict__ q, int main_only) {
+                                                                 uint32_t wN, uint32_t ginv, uint32_t* __restrict__ q, int main_only,
+                                                                 const uint32_t* __restrict__ pub, uint32_t pub_base) {
     __shared__ uint32_t stack_lds[kStackCap * kBlock];
     uint32_t* stk = stack_lds + threadIdx.x;
     const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
@@ -155,8 +157,8 @@ __global__ __launch_bounds__(kBlock) void quotient_logup_kernel(const uint32_t* 
     bb::ExtProductAcc wide;
     for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t off = spans[2 * c], len = spans[2 * c + 1];
-        const uint32_t v = XBC ? xbc::eval<kBlock, true>(bytecode + 2 * (size_t)off, len, lde, j, stk, N)
-                               : eval_expr<kBlock, true>(bytecode + off, len, lde, j, stk, N);
+        const uint32_t v = XBC ? xbc::eval<kBlock, true, PUB>(bytecode + 2 * (size_t)off, len, lde, j, stk, N, pub)
+                               : eval_expr<kBlock, true, PUB>(bytecode + off, len, lde, j, stk, N, pub, pub_base);
         wide.fma_base(apow[c], v);
     }
     Ext sumq = bb::ext_zero(), sumq_next = bb::ext_zero();
@@ -369,10 +371,13 @@ int quotient_eval_logup(const uint32_t* lde, const uint32_t* plde, size_t N, int
     const int mo = main_only ? 1 : 0;
     ScopedKernelTimer t("quotient_logup_kernel");
     call_stats()[kStatInterpreterKernelLaunches] += 1;
-#define PW_LAUNCH_QL(X, F) hipLaunchKernelGGL((quotient_logup_kernel<X, F>), dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), lde, plde, N, \
-                                            prog.d_bytecode, prog.d_spans, prog.n_constraints, lp, d_apow, al, d_blpow, S, zval_even, zval_odd, shift, wN, ginv, q, mo)
+#define PW_LAUNCH_QL2(X, F, P) hipLaunchKernelGGL((quotient_logup_kernel<X, F, P>), dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), lde, plde, N, \
+                                                prog.d_bytecode, prog.d_spans, prog.n_constraints, lp, d_apow, al, d_blpow, S, zval_even, zval_odd, shift, wN, \
+                                                ginv, q, mo, prog.d_pub, prog.pub_base)
+#define PW_LAUNCH_QL(X, F) do { if (prog.d_pub) PW_LAUNCH_QL2(X, F, true); else PW_LAUNCH_QL2(X, F, false); } while (0)
     if (prog.is_xbc) { if (lp.d_forms) PW_LAUNCH_QL(true, true); else PW_LAUNCH_QL(true, false); }
     else { if (lp.d_forms) PW_LAUNCH_QL(false, true); else PW_LAUNCH_QL(false, false); }
+#undef PW_LAUNCH_QL2
 #undef PW_LAUNCH_QL
     return (int)hipGetLastError();
 }

@@ -48,6 +48,8 @@ extern "C" int pw_prover_specialised(const PwProver* p, size_t* n_kernels, size_
 
 // The row layout: the constraint programs of a row-aware AIR rewritten onto the compact device layout (prover_state.hpp
 // PwProver::row_flags), one program after the other; fills next_cols, *row_cols and new spans. Operands are in bounds (checked before).
+// Public values (operands 2 W1 + 3 + k) follow the compact columns: value k becomes operand W1 + *row_cols + k, so the
+// device programs tell them from every column by one bound (PwProver::pub_base) whether or not the AIR is row-aware.
 static std::vector<uint32_t> remap_row_programs(const uint32_t* bc, const uint32_t* spans, size_t n_constraints, uint32_t w1, uint32_t flags,
                                                 std::vector<uint32_t>& next_cols, uint32_t* row_cols, std::vector<uint32_t>& new_spans) {
     // the next-row columns read, ascending (a sorted list, not a table of W1 entries: W1 comes from the caller)
@@ -74,7 +76,8 @@ static std::vector<uint32_t> remap_row_programs(const uint32_t* bc, const uint32
             out.push_back(op);
             if (op != POWDR_OP_PUSH_APC && op != POWDR_OP_PUSH_CONST) continue;
             uint32_t a = bc[ip++];
-            if (op == POWDR_OP_PUSH_APC && a >= w1) a = a < 2 * w1 ? w1 + slot(a - w1) : w1 + n_next + (a - 2 * w1);
+            if (op == POWDR_OP_PUSH_APC && a >= 2 * w1 + 3) a = w1 + *row_cols + (a - (2 * w1 + 3));
+            else if (op == POWDR_OP_PUSH_APC && a >= w1) a = a < 2 * w1 ? w1 + slot(a - w1) : w1 + n_next + (a - 2 * w1);
             out.push_back(a);
         }
     }
@@ -82,19 +85,22 @@ static std::vector<uint32_t> remap_row_programs(const uint32_t* bc, const uint32
 }
 
 // `device` = false: host tables only (pw_jit_compile_check: code generation + hiprtc need no GPU). rows_w1 != 0: the row layout over
-// rows_w1 (= width) columns — constraint operands below 2 rows_w1 + 3, is_transition of degree 0
+// rows_w1 (= width) columns — constraint operands below 2 rows_w1 + 3, is_transition of degree 0 — and behind them
+// n_public public values of degree 0 (only with rows_w1)
 static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const uint32_t* bc, size_t bc_len,
-                               const uint32_t* spans, size_t n_constraints, bool device, uint32_t rows_w1 = 0) {
-    if (!cfg || !width) return nullptr;
+                               const uint32_t* spans, size_t n_constraints, bool device, uint32_t rows_w1 = 0, uint32_t n_public = 0) {
+    if (!cfg || !width || (n_public && !rows_w1)) return nullptr;
     PwProver* p = new PwProver();
     p->cfg = *cfg;
     p->width = width;
     p->n_constraints = (uint32_t)n_constraints;
     p->h_spans.assign(spans, spans + 2 * n_constraints);
-    const uint32_t bound = rows_w1 ? 2 * rows_w1 + 3 : width, deg0 = rows_w1 ? 2 * rows_w1 + 2 : 0xffffffffu;
+    const uint32_t bound = rows_w1 ? 2 * rows_w1 + 3 + n_public : width, deg0 = rows_w1 ? 2 * rows_w1 + 2 : 0xffffffffu;
+    const uint32_t deg0_from = n_public ? 2 * rows_w1 + 3 : 0xffffffffu;
+    p->n_public = n_public;
     for (size_t k = 0; k < n_constraints; ++k) {
         const uint32_t off = spans[2 * k], len = spans[2 * k + 1];
-        const int d = (size_t)off + len <= bc_len ? pw::postfix_degree(bc + off, len, deg0) : pw::kBadDegree;
+        const int d = (size_t)off + len <= bc_len ? pw::postfix_degree(bc + off, len, deg0, deg0_from) : pw::kBadDegree;
         // a span past the bytecode, an unknown opcode, an unbalanced or too deep stack, a column the trace does not have: no prover — the
         // post-fix fallback below is for well-formed programs the xbc compiler declines, not for these (they would index past the
         // bytecode or the trace on the device)
@@ -104,11 +110,12 @@ static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const u
     }
     // a row-aware AIR's programs go to the device (and to the xbc compiler) rewritten onto the compact layout of its values
     std::vector<uint32_t> row_bc, row_spans;
-    if (p->row_flags) {
+    if (p->row_flags || n_public) {
         row_bc = remap_row_programs(bc, spans, n_constraints, rows_w1, p->row_flags, p->h_next_cols, &p->row_cols, row_spans);
         bc = row_bc.data();
         bc_len = row_bc.size();
         spans = row_spans.data();
+        if (n_public) p->pub_base = rows_w1 + p->row_cols;
     }
     // compile the post-fix constraint programs to xbc (xbc.hpp); fall back to the post-fix interpreter if
     // any program is malformed or too deep
@@ -116,6 +123,7 @@ static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const u
     bool ok = getenv("POWDR_QUOTIENT_XBC") ? atoi(getenv("POWDR_QUOTIENT_XBC")) != 0 : true;
     {
         xbc::Compiler cc;
+        cc.pub_base = p->pub_base;
         for (size_t k = 0; k < n_constraints && ok; ++k) {
             const uint32_t off = spans[2 * k], len = spans[2 * k + 1];
             if ((size_t)off + len > bc_len) { ok = false; break; }
@@ -143,6 +151,10 @@ static PwProver* create_prover(const PwStarkConfig* cfg, uint32_t width, const u
         pw_prover_destroy(p);
         return nullptr;
     }
+    if (n_public && hipMalloc(&p->d_pub, (size_t)n_public * 4) != hipSuccess) {
+        pw_prover_destroy(p);
+        return nullptr;
+    }
     return p;
 }
 
@@ -155,8 +167,8 @@ extern "C" PwProver* pw_prover_create(const PwStarkConfig* cfg, uint32_t width, 
 static PwProver* create_prover_logup(const PwStarkConfig* cfg, uint32_t width, const uint32_t* bc, size_t bc_len,
                                      const uint32_t* spans, size_t n_constraints, const uint32_t* inter, size_t n_inter,
                                      const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len, bool device,
-                                     uint32_t rows_w1 = 0) {
-    PwProver* p = create_prover(cfg, width, bc, bc_len, spans, n_constraints, device, rows_w1);
+                                     uint32_t rows_w1 = 0, uint32_t n_public = 0) {
+    PwProver* p = create_prover(cfg, width, bc, bc_len, spans, n_constraints, device, rows_w1, n_public);
     if (!p) return nullptr;
     // interactions: {bus, n_args, first span}; spans [mult, arg0, ...] into ibc (post-fix, column operands)
     std::vector<pw::LogupInteraction> li(n_inter);
@@ -264,25 +276,81 @@ extern "C" PwProver* pw_prover_create_preprocessed(const PwStarkConfig* cfg, uin
 // Next-row operands and row selectors: constraint operands over the row layout of W1 = width + pre_width columns,
 // interaction operands below W1, constraint degrees by Plonky3's rule at most 3. pre_width = 0: no fixed matrix (log_height and d_pre
 // unused; any height >= 2 rows). A prover whose constraints read only current-row columns acts exactly as the plain (or preprocessed) one.
+// device = false: host tables only, no fixed matrix attached (the program checks and the code generation of pw_public_programs_check)
+static PwProver* create_row_prover(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height, const uint32_t* d_pre,
+                                   uint32_t n_public, const uint32_t* bc, size_t bc_len, const uint32_t* spans, size_t n_constraints,
+                                   const uint32_t* inter, size_t n_inter, const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc,
+                                   size_t ibc_len, bool device) {
+    // (2 W1 + 3 + n_public operands fit in 32 bits)
+    if (!cfg || !width || n_public > pw::kMaxPublicValues || (uint64_t)width + pre_width > (n_public ? 0x7fffff00ull : 0x7ffffff0ull)) return nullptr;
+    if (device && pre_width && (!d_pre || log_height < 1 || log_height > 26)) return nullptr;
+    const uint32_t w1 = width + pre_width;
+    PwProver* p = inter ? create_prover_logup(cfg, w1, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, device, w1, n_public)
+                        : create_prover(cfg, w1, bc, bc_len, spans, n_constraints, device, w1, n_public);
+    if (!p) return nullptr;
+    if (p->max_degree > 3) { pw_prover_destroy(p); return nullptr; }  // a blow-up-2 quotient carries degree 3
+    p->transition = true;
+    if (!pre_width || !device) { p->width = width; return p; }
+    return attach_preprocessed(p, width, pre_width, log_height, d_pre);
+}
+
 extern "C" PwProver* pw_prover_create_transition(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
                                                  const uint32_t* d_pre, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
                                                  size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
                                                  size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
-    if (!cfg || !width || (uint64_t)width + pre_width > 0x7ffffff0ull) return nullptr;  // (2 W1 + 3 operands fit in 32 bits)
-    if (pre_width && (!d_pre || log_height < 1 || log_height > 26)) return nullptr;
-    const uint32_t w1 = width + pre_width;
-    PwProver* p = inter ? create_prover_logup(cfg, w1, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc, ibc_len, true, w1)
-                        : create_prover(cfg, w1, bc, bc_len, spans, n_constraints, true, w1);
-    if (!p) return nullptr;
-    if (p->max_degree > 3) { pw_prover_destroy(p); return nullptr; }  // a blow-up-2 quotient carries degree 3
-    p->transition = true;
-    if (!pre_width) { p->width = width; return p; }
-    return attach_preprocessed(p, width, pre_width, log_height, d_pre);
+    return create_row_prover(cfg, width, pre_width, log_height, d_pre, 0, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans, ibc,
+                             ibc_len, true);
+}
+
+// Public values: constraint operands 2 W1 + 3 + k, k < n_public <= 256, of degree 0, behind the row layout. n_public = 0:
+// exactly pw_prover_create_transition. The values are set per segment (pw_prover_set_public_values) and never part of the programs.
+extern "C" PwProver* pw_prover_create_public(const PwStarkConfig* cfg, uint32_t width, uint32_t pre_width, uint32_t log_height,
+                                             const uint32_t* d_pre, uint32_t n_public, const uint32_t* bc, size_t bc_len, const uint32_t* spans,
+                                             size_t n_constraints, const uint32_t* inter, size_t n_inter, const uint32_t* ispans,
+                                             size_t n_ispans, const uint32_t* ibc, size_t ibc_len) {
+    return create_row_prover(cfg, width, pre_width, log_height, d_pre, n_public, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans,
+                             ibc, ibc_len, true);
+}
+
+extern "C" uint32_t pw_prover_n_public(const PwProver* p) { return p ? p->n_public : 0; }
+
+// host copy only: a segment proof (and the mock prover) uploads what is set when it begins, on its own launch stream
+extern "C" int pw_prover_set_public_values(PwProver* p, const uint32_t* values, size_t n) {
+    if (!p || n != p->n_public || (n && !values)) return -1;
+    for (size_t k = 0; k < n; ++k) if (values[k] >= bb::P) return -1;
+    p->h_pub.resize(n);
+    for (size_t k = 0; k < n; ++k) p->h_pub[k] = bb::to_monty(values[k]);
+    p->pub_set = true;
+    return 0;
+}
+
+// Test hook (not declared in include/): what pw_prover_create_public checks and compiles, WITHOUT a GPU — 0 and the highest constraint
+// degree, the row flags, the xbc code of the constraints (0 words: the post-fix fallback) and the generated HIP source of all units of
+// the specialised quotient kernels, one after the other; -2: the entry would return NULL.
+extern "C" int pw_public_programs_check(uint32_t width, uint32_t pre_width, uint32_t n_public, const uint32_t* bc, size_t bc_len,
+                                        const uint32_t* spans, size_t n_constraints, const uint32_t* inter, size_t n_inter,
+                                        const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len, int* max_degree,
+                                        uint32_t* row_flags, uint32_t* xbc_out, size_t xbc_cap, size_t* xbc_len, char* src, size_t src_cap,
+                                        size_t* src_len) {
+    const PwStarkConfig cfg{1, 0};
+    PwProver* p = create_row_prover(&cfg, width, pre_width, 0, nullptr, n_public, bc, bc_len, spans, n_constraints, inter, n_inter, ispans, n_ispans,
+                                    ibc, ibc_len, false);
+    if (!p) return -2;
+    if (max_degree) *max_degree = p->max_degree;
+    if (row_flags) *row_flags = p->row_flags;
+    if (xbc_len) *xbc_len = p->h_xcode.size();
+    for (size_t i = 0; xbc_out && i < p->h_xcode.size() && i < xbc_cap; ++i) xbc_out[i] = p->h_xcode[i];
+    std::string all;
+    for (const pw::jit::Unit& u : pw::generate_sources(p, 0, 8000, 8).units) all += u.source;
+    if (src_len) *src_len = all.size();
+    if (src && src_cap) { strncpy(src, all.c_str(), src_cap - 1); src[src_cap - 1] = 0; }
+    pw_prover_destroy(p);
+    return 0;
 }
 
 extern "C" uint32_t pw_prover_row_flags(const PwProver* p) { return p ? p->row_flags : 0; }
 namespace pw {
-bool prover_segment_only(const PwProver* p) { return p && (p->pre_width || p->transition); }
+bool prover_segment_only(const PwProver* p) { return p && (p->pre_width || p->transition || p->n_public); }
 }  // namespace pw
 
 extern "C" int pw_prover_preprocessed_root(const PwProver* p, uint32_t* root8) {
@@ -528,7 +596,7 @@ int ensure_proof_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bo
 // Trace commitment only (LDE + Merkle root): what a segment's AIRs exchange before the bus seed can be formed.
 extern "C" int pw_prover_trace_root(PwProver* p, const uint32_t* d_trace, uint32_t log_h, uint32_t* root8) {
     if (!p || !d_trace || !root8 || log_h < 1 || log_h > 26) return (int)hipErrorInvalidValue;
-    if (p->pre_width || p->transition) return -1;  // preprocessed columns and the row layout are segment-proof features
+    if (p->pre_width || p->transition || p->n_public) return -1;  // preprocessed columns, the row layout, public values: segment proofs
     (void)hipGetLastError();
     TRY(poseidon2_upload_params());
     CommitLayout L;
@@ -588,6 +656,7 @@ extern "C" void pw_prover_destroy(PwProver* p) {
                          &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree, &p->row_vals, &p->bus_order})
         b->release();
     if (p->d_next_cols) (void)hipFree(p->d_next_cols);
+    if (p->d_pub) (void)hipFree(p->d_pub);
     for (void* q : {(void*)p->d_inter, (void*)p->d_ixspans, (void*)p->d_icode, (void*)p->d_gstarts, (void*)p->d_iforms}) if (q) (void)hipFree(q);
     if (p->d_bytecode) (void)hipFree(p->d_bytecode);
     if (p->d_spans) (void)hipFree(p->d_spans);
@@ -628,7 +697,7 @@ namespace {
 // consume: pw_prover_prove_consuming — d_trace is the caller's to give away. Only a STREAMED proof uses that: the coefficient arrays
 // of the trace end up in d_trace itself (no tcoef buffer: 62.6 GB at configs[2], which is what lets it run on 2 sub-cosets instead of 4).
 int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint32_t** proof_words, size_t* n_words, bool consume) {
-    if (!p || !d_trace || log_h < 1 || log_h > 26 || p->pre_width || p->transition) return -1;  // (preprocessed columns, rows: segment proofs only)
+    if (!p || !d_trace || log_h < 1 || log_h > 26 || p->pre_width || p->transition || p->n_public) return -1;  // (preprocessed columns, rows: segment proofs only)
     // a handed-over trace becomes a coefficient array that is read 2 / 4 words at a time (fold loads, the DEEP combination)
     if (consume && ((uintptr_t)d_trace & 15)) return (int)hipErrorInvalidValue;
     (void)hipGetLastError();
@@ -966,7 +1035,9 @@ extern "C" int pw_trace_from_coefficients(uint32_t* d_coeffs, uint32_t width, ui
 extern "C" int pw_prover_check_constraints(PwProver* p, const uint32_t* d_trace, uint32_t log_h, uint64_t* n_violations,
                                            uint64_t* first_row, uint32_t* first_constraint) {
     if (!p || !d_trace || log_h > 40 || (p->pre_width && log_h != p->pre_log_h)) return -1;
+    if (p->n_public && !p->pub_set) return -1;  // never with zeros in their place
     (void)hipGetLastError();
+    if (p->n_public) PW_HIP_TRY(hipMemcpyAsync(p->d_pub, p->h_pub.data(), (size_t)p->n_public * 4, hipMemcpyHostToDevice, stream()));
     const size_t H = (size_t)1 << log_h;
     if (p->row_flags) {
         // the row layout on the trace domain: (trace | fixed) and behind it the next rows (j + 1 mod H) and the
@@ -990,7 +1061,7 @@ extern "C" int pw_prover_check_constraints(PwProver* p, const uint32_t* d_trace,
     unsigned long long* d = p->misc.as<unsigned long long>();
     unsigned long long init[2] = {~0ull, 0ull}, res[2];
     PW_HIP_TRY(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, stream()));
-    ConstraintProgram prog{p->d_bytecode, p->d_spans, p->n_constraints, p->is_xbc};
+    const ConstraintProgram prog = constraint_program(p, p->n_constraints);
     if (p->n_constraints) TRY(check_constraints(d_trace, H, prog, d));
     PW_HIP_TRY(hipMemcpyAsync(res, d, sizeof res, hipMemcpyDeviceToHost, stream()));
     PW_HIP_TRY(hipStreamSynchronize(stream()));

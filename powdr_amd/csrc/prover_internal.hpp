@@ -105,6 +105,10 @@ struct ConstraintProgram {
     const uint32_t* d_spans;     // {off, len} pairs (u32 words, or xbc instructions when is_xbc)
     uint32_t n_constraints;
     bool is_xbc;
+    // an AIR with public values: the prover's array of them (Montgomery; nullptr: the AIR has none and the kernels
+    // without the public forms run) and, for post-fix programs, the first operand that names one
+    const uint32_t* d_pub = nullptr;
+    uint32_t pub_base = 0xffffffffu;
 };
 // q[k*N + j] (k < 4) = coordinate k of  sum_c alpha_pow[c] * C_c(lde row j) * zinv[j & 1]
 // Short traces with many constraints: the constraint list is split over `n_chunks` (quotient_chunks) workgroup rows,

@@ -146,7 +146,8 @@ int quotient_parts_jit(PwProver* p, const uint32_t* T, const uint32_t* Pm, size_
                        uint32_t* part, uint32_t* n_chunks) {
     const jit::Generated& g = p->jit.quotient;
     uint64_t n64 = rows;
-    void* args[] = {(void*)&T, (void*)&Pm, (void*)&n64, (void*)&d_apow, (void*)&al, (void*)&d_blpow, (void*)&part};
+    const uint32_t* pub = p->d_pub;  // the last argument of kernels generated with has_pub, not a parameter of the others
+    void* args[] = {(void*)&T, (void*)&Pm, (void*)&n64, (void*)&d_apow, (void*)&al, (void*)&d_blpow, (void*)&part, (void*)&pub};
     ScopedKernelTimer t(Pm ? "quotient_logup_jit_kernel" : "quotient_jit_kernel");
     const int rc = launch_units(g, p->jit.quotient_prog, rows, args);
     if (n_chunks) *n_chunks = g.n_chunks;
@@ -169,7 +170,8 @@ int quotient_unit_jit(PwProver* p, uint32_t u, const uint32_t* T, const uint32_t
     // (a chunk stores to part + <its program-wide chunk id> * 4 * rows — the id is a literal in the generated code — so every unit
     // takes the same base pointer)
     uint64_t n64 = rows;
-    void* args[] = {(void*)&T, (void*)&Pm, (void*)&n64, (void*)&d_apow, (void*)&al, (void*)&d_blpow, (void*)&part};
+    const uint32_t* pub = p->d_pub;
+    void* args[] = {(void*)&T, (void*)&Pm, (void*)&n64, (void*)&d_apow, (void*)&al, (void*)&d_blpow, (void*)&part, (void*)&pub};
     ScopedKernelTimer t(Pm ? "quotient_logup_jit_kernel" : "quotient_jit_kernel");
     return launch_unit(g, p->jit.quotient_prog, u, rows, args);
 }

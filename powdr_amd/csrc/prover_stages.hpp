@@ -59,6 +59,13 @@ inline streamed::Ctx stream_ctx(PwProver* p, const AirShape& s, const CommitLayo
     return streamed::Ctx{p, s.log_h, L.b, L.perm_panels, s.H, s.N, L.m, s.W, s.Wp};
 }
 
+// the constraint programs as the interpreter kernels take them (an AIR with public values: with the array of them)
+inline ConstraintProgram constraint_program(const PwProver* p, uint32_t nc) {
+    ConstraintProgram c{p->d_bytecode, p->d_spans, nc, p->is_xbc};
+    if (p->n_public) { c.d_pub = p->d_pub; c.pub_base = p->pub_base; }
+    return c;
+}
+
 inline LogupProgram logup_program(const PwProver* p, const AirShape& s) {
     return s.Wp ? LogupProgram{p->d_inter, s.n_int, p->d_ixspans, p->d_icode, p->d_gstarts, s.n_g, p->d_iforms} : LogupProgram{};
 }
@@ -187,7 +194,7 @@ inline int quotient_stage(PwProver* p, const AirShape& s, AirMode m, const Commi
     uint32_t sH = bb::to_monty(field::kCosetShift);
     for (uint32_t i = 0; i < s.log_h; ++i) sH = bb::sqr(sH);
     const uint32_t zv_even = bb::sub(sH, one), zv_odd = bb::sub(bb::neg(sH), one);  // Z_H on the even / odd rows of the coset
-    const ConstraintProgram prog{p->d_bytecode, p->d_spans, s.nc, p->is_xbc};
+    const ConstraintProgram prog = constraint_program(p, s.nc);
     uint32_t* d_lde = p->lde.as<uint32_t>();
     uint32_t* d_plde = p->plde.as<uint32_t>();
     uint32_t* d_q = p->q.as<uint32_t>();

@@ -17,6 +17,7 @@ constexpr uint32_t kMagic2 = 0x32535750u;  // "PWS2": with the LogUp extension
 constexpr uint32_t kMagic3 = 0x33535750u;  // "PWS3": one proof per segment (segment_prover.hip)
 constexpr uint32_t kMagic4 = 0x34535750u;  // "PWS4": a segment proof in which at least one AIR has preprocessed columns
 constexpr uint32_t kMagic5 = 0x35535750u;  // "PWS5": a segment proof in which at least one AIR is row-aware
+constexpr uint32_t kMagic6 = 0x36535750u;  // "PWS6": a segment proof in which at least one AIR has public values
 
 // ---- duplex-sponge challenger on Montgomery words (spec: oracle/stark_oracle.cpp Challenger) ----
 struct Challenger {
@@ -136,6 +137,14 @@ struct PwProver {
     std::vector<uint32_t> h_next_cols;
     uint32_t* d_next_cols = nullptr;
     pw::DeviceBuf row_vals;
+    // public values (pw_prover_create_public; segment proofs only): constraint operands 2 W1 + 3 + k, k < n_public. On the
+    // device the programs name value k as operand pub_base + k (pub_base = W1 + row_cols, right behind the compact row layout; xbc: the
+    // *_PUB forms with index k) and every expression kernel gets `d_pub`, n_public Montgomery words, as an argument. h_pub: the values
+    // last set (Montgomery); a segment proof snapshots them when it begins and uploads the snapshot on its launch stream.
+    uint32_t n_public = 0, pub_base = 0xffffffffu;
+    bool pub_set = false;
+    std::vector<uint32_t> h_pub;
+    uint32_t* d_pub = nullptr;
     // host copies of the plan-compiled (xbc) programs: the source of the run-time specialised kernels (jit_codegen.hpp)
     std::vector<uint32_t> h_xcode, h_xspans, h_icode, h_ixspans, h_gstarts;
     std::vector<pw::LogupInteraction> h_inter;

@@ -47,6 +47,9 @@ struct SegCtx {
     // the byte tables the last call's memory policy planned with (pw::plan_segment_streams; tests: pw_segment_last_plan_tables)
     std::vector<size_t> plan_resident, plan_streamed;
     std::vector<int> plan_b_max;
+    // the public values of the call's AIRs as they were set when it began: uploaded from here, so a caller that sets
+    // new values after the call returns never races with a copy still in flight
+    std::vector<std::vector<uint32_t>> pub_snapshot;
     // side streams for the per-AIR stages of a segment with many AIRs (fork from / join into the caller's stream by events)
     hipStream_t side[kMaxSide] = {};
     hipEvent_t fork_ev = nullptr, done_ev[kMaxSide] = {};
@@ -138,6 +141,7 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         // prover cannot serve two AIRs of the same segment; one FRI / query phase means one configuration for all of them
         if (airs[a].prover->cfg.num_queries != airs[0].prover->cfg.num_queries || airs[a].prover->cfg.pow_bits != airs[0].prover->cfg.pow_bits)
             return (int)hipErrorInvalidValue;
+        if (airs[a].prover->n_public && !airs[a].prover->pub_set) return -1;  // public values never set: not proven with zeros in their place
     }
     {
         std::vector<const PwProver*> seen(A);
@@ -169,6 +173,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         (void)specialise_provers(ps.data(), A, lhs.data(), false);
     }
     SegCtx& cx = g_ctx;
+    cx.pub_snapshot.assign(A, {});
+    for (size_t a = 0; a < A; ++a) cx.pub_snapshot[a] = airs[a].prover->h_pub;
     // The per-AIR stages (LDE, permutation trace, quotient, openings, query rows) of different AIRs are independent chains of
     // small launches; on one stream a segment of 60 AIRs pays ~10 us of dispatch latency between 1 400 dependent kernels
     // (profiles/r02_segment_gaps.txt: 15 of 176 ms). With K side streams the chains of different AIRs overlap:
@@ -266,7 +272,8 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     cx.plan_resident.clear(); cx.plan_streamed.clear(); cx.plan_b_max.clear();
     {
         // (AIRs that share a height: their level is hashed run by run); an AIR with preprocessed columns or the row layout is always resident
-        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3 && !sh[a].Wf && !sh[a].rf; };
+        // (and so is one with public values)
+        auto may_stream = [&](size_t a) { return sh[a].log_h >= 3 && !sh[a].Wf && !sh[a].rf && !airs[a].prover->n_public; };
         auto b_max = [&](size_t a) { return std::min((int)sh[a].log_h - 1, 5); };
         if (!by_air.empty()) {  // forced per AIR (tests: mixed levels)
             for (size_t a = 0; a < A; ++a) if (may_stream(a) && by_air[a] > 0) sbv[a] = std::min(by_air[a], b_max(a));
@@ -315,9 +322,9 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
     auto put = [&](uint32_t canonical) { pf.push_back(canonical); };
     auto put_monty = [&](const uint32_t* w, size_t n) { for (size_t i = 0; i < n; ++i) pf.push_back(bb::from_monty(w[i])); };
     Challenger ch;
-    bool any_pre = false, any_rows = false;
-    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; }
-    const uint32_t magic = any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3;
+    bool any_pre = false, any_rows = false, any_pub = false;
+    for (size_t a = 0; a < A; ++a) { any_pre = any_pre || sh[a].Wf; any_rows = any_rows || sh[a].rf; any_pub = any_pub || airs[a].prover->n_public; }
+    const uint32_t magic = any_pub ? kMagic6 : any_rows ? kMagic5 : any_pre ? kMagic4 : kMagic3;
     for (uint32_t x : {magic, (uint32_t)A, lg ? 1u : 0u, cfg.num_queries, cfg.pow_bits}) { ch.observe_canonical(x % bb::P); put(x); }
     for (size_t a = 0; a < A; ++a)
         for (uint32_t x : {sh[a].log_h, sh[a].W, sh[a].nc, sh[a].n_int}) { ch.observe_canonical(x % bb::P); put(x); }
@@ -333,6 +340,18 @@ static int prove_segment_impl(const PwSegmentAir* airs, size_t n_airs, int logup
         if (!sh[a].rf) continue;
         ch.observe_canonical((uint32_t)a % bb::P);
         ch.observe_canonical(sh[a].rf);
+    }
+    // the public values: written right after the header, observed here, and on their way to the device on the launch
+    // stream — every kernel that reads them is enqueued behind this copy (the side streams fork from it)
+    for (size_t a = 0; a < A; ++a) {
+        const uint32_t np = airs[a].prover->n_public;
+        if (!np) continue;
+        const std::vector<uint32_t>& pv = cx.pub_snapshot[a];
+        ch.observe_canonical((uint32_t)a % bb::P);
+        ch.observe_canonical(np);
+        ch.observe_words(pv.data(), np);
+        put_monty(pv.data(), np);
+        PW_HIP_TRY(hipMemcpyAsync(airs[a].prover->d_pub, pv.data(), (size_t)np * 4, hipMemcpyHostToDevice, st));
     }
 
     // mixed commitment of one matrix per AIR: matrix(a) = (device pointer, width); heights are the AIRs' LDE heights

@@ -22,12 +22,15 @@ __device__ __forceinline__ bb::Ext load_ext_uniform(const bb::Ext* p) { return *
 // kQRows LDE rows per lane (rows t, t + kBlock, ... of a kQRows * kBlock-row block): the constraint interpreter is
 // bound by its scalar work, which is shared by the rows of a lane (xbc::eval_rows).
 constexpr int kQRows = 2;
-template <bool XBC>
+// PUB: the AIR has public values — `pub` is the prover's array of them, read at the wave-uniform index an instruction
+// carries (scalar loads); the instantiations without it take the two arguments and ignore them.
+template <bool XBC, bool PUB>
 __global__ __launch_bounds__(kBlock) void quotient_kernel(const uint32_t* __restrict__ lde, size_t N,
                                                            const uint32_t* __restrict__ bytecode,
                                                            const uint32_t* __restrict__ spans, uint32_t n_constraints,
                                                            const bb::Ext* __restrict__ alpha_pows, uint32_t zinv_even,
-                                                           uint32_t zinv_odd, uint32_t* __restrict__ q, uint32_t per_chunk) {
+                                                           uint32_t zinv_odd, uint32_t* __restrict__ q, uint32_t per_chunk,
+                                                           const uint32_t* __restrict__ pub, uint32_t pub_base) {
     __shared__ uint32_t stack_lds[kStackCap * kQRows * kBlock];
     uint32_t* stk = stack_lds + threadIdx.x;
     size_t rows[kQRows];
@@ -48,10 +51,10 @@ __global__ __launch_bounds__(kBlock) void quotient_kernel(const uint32_t* __rest
         const uint32_t off = spans[2 * c], len = spans[2 * c + 1];
         uint32_t v[kQRows];
         if (XBC) {
-            xbc::eval_rows<kBlock, true, kQRows>(bytecode + 2 * (size_t)off, len, lde, rows, stk, N, v);
+            xbc::eval_rows<kBlock, true, kQRows, PUB>(bytecode + 2 * (size_t)off, len, lde, rows, stk, N, v, pub);
         } else {
 #pragma unroll
-            for (int n = 0; n < kQRows; ++n) v[n] = eval_expr<kBlock, true>(bytecode + off, len, lde, rows[n], stk, N);
+            for (int n = 0; n < kQRows; ++n) v[n] = eval_expr<kBlock, true, PUB>(bytecode + off, len, lde, rows[n], stk, N, pub, pub_base);
         }
         const bb::Ext a = alpha_pows[c];
 #pragma unroll
@@ -87,20 +90,21 @@ __global__ __launch_bounds__(kBlock) void quotient_combine_kernel(const uint32_t
 }
 
 // "mock prover": evaluate every constraint on every TRACE row; first[0] <- min over violations of row * nc + c
-template <bool XBC>
+template <bool XBC, bool PUB>
 __global__ __launch_bounds__(kBlock) void check_constraints_kernel(const uint32_t* __restrict__ trace, size_t H,
                                                                     const uint32_t* __restrict__ bytecode,
                                                                     const uint32_t* __restrict__ spans, uint32_t n_constraints,
                                                                     unsigned long long* __restrict__ first,
-                                                                    unsigned long long* __restrict__ count) {
+                                                                    unsigned long long* __restrict__ count,
+                                                                    const uint32_t* __restrict__ pub, uint32_t pub_base) {
     __shared__ uint32_t stack_lds[kStackCap * kBlock];
     uint32_t* stk = stack_lds + threadIdx.x;
     const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= H) return;
     for (uint32_t c = 0; c < n_constraints; ++c) {
         const uint32_t off = spans[2 * c], len = spans[2 * c + 1];
-        const uint32_t v = XBC ? xbc::eval<kBlock, true>(bytecode + 2 * (size_t)off, len, trace, j, stk, H)
-                               : eval_expr<kBlock, true>(bytecode + off, len, trace, j, stk, H);
+        const uint32_t v = XBC ? xbc::eval<kBlock, true, PUB>(bytecode + 2 * (size_t)off, len, trace, j, stk, H, pub)
+                               : eval_expr<kBlock, true, PUB>(bytecode + off, len, trace, j, stk, H, pub, pub_base);
         if (v != 0u) {
             atomicMin(first, (unsigned long long)j * n_constraints + c);
             atomicAdd(count, 1ull);
@@ -393,12 +397,11 @@ int quotient_eval(const uint32_t* lde, size_t N, const ConstraintProgram& prog, 
     if (n_chunks > 1) n_chunks = (prog.n_constraints + per_chunk - 1) / per_chunk;
     uint32_t* out = n_chunks > 1 ? part : q;
     const dim3 grid(div_up(N, kBlock * kQRows), n_chunks);
-    if (prog.is_xbc)
-        hipLaunchKernelGGL(quotient_kernel<true>, grid, dim3(kBlock), 0, stream(), lde, N, prog.d_bytecode, prog.d_spans,
-                           prog.n_constraints, d_alpha_pows, zinv_even, zinv_odd, out, per_chunk);
-    else
-        hipLaunchKernelGGL(quotient_kernel<false>, grid, dim3(kBlock), 0, stream(), lde, N, prog.d_bytecode, prog.d_spans,
-                           prog.n_constraints, d_alpha_pows, zinv_even, zinv_odd, out, per_chunk);
+#define PW_LAUNCH_Q(X, P) hipLaunchKernelGGL((quotient_kernel<X, P>), grid, dim3(kBlock), 0, stream(), lde, N, prog.d_bytecode, prog.d_spans, \
+                                           prog.n_constraints, d_alpha_pows, zinv_even, zinv_odd, out, per_chunk, prog.d_pub, prog.pub_base)
+    if (prog.is_xbc) { if (prog.d_pub) PW_LAUNCH_Q(true, true); else PW_LAUNCH_Q(true, false); }
+    else { if (prog.d_pub) PW_LAUNCH_Q(false, true); else PW_LAUNCH_Q(false, false); }
+#undef PW_LAUNCH_Q
     if (n_chunks > 1)
         hipLaunchKernelGGL(quotient_combine_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, stream(), part, n_chunks, N, zinv_even,
                            zinv_odd, q);
@@ -413,12 +416,11 @@ int quotient_combine(const uint32_t* part, uint32_t n_chunks, size_t N, uint32_t
 
 int check_constraints(const uint32_t* trace, size_t H, const ConstraintProgram& prog, unsigned long long* d_first_and_count) {
     ScopedKernelTimer t("check_constraints_kernel");
-    if (prog.is_xbc)
-        hipLaunchKernelGGL(check_constraints_kernel<true>, dim3(div_up(H, kBlock)), dim3(kBlock), 0, stream(), trace, H,
-                           prog.d_bytecode, prog.d_spans, prog.n_constraints, d_first_and_count, d_first_and_count + 1);
-    else
-        hipLaunchKernelGGL(check_constraints_kernel<false>, dim3(div_up(H, kBlock)), dim3(kBlock), 0, stream(), trace, H,
-                           prog.d_bytecode, prog.d_spans, prog.n_constraints, d_first_and_count, d_first_and_count + 1);
+#define PW_LAUNCH_CC(X, P) hipLaunchKernelGGL((check_constraints_kernel<X, P>), dim3(div_up(H, kBlock)), dim3(kBlock), 0, stream(), trace, H, \
+                                            prog.d_bytecode, prog.d_spans, prog.n_constraints, d_first_and_count, d_first_and_count + 1, prog.d_pub, prog.pub_base)
+    if (prog.is_xbc) { if (prog.d_pub) PW_LAUNCH_CC(true, true); else PW_LAUNCH_CC(true, false); }
+    else { if (prog.d_pub) PW_LAUNCH_CC(false, true); else PW_LAUNCH_CC(false, false); }
+#undef PW_LAUNCH_CC
     return (int)hipGetLastError();
 }
 

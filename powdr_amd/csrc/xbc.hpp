@@ -7,6 +7,9 @@
 // into a tree, simplified (constant folding, x+0, x*1, x*0, --x) and re-emitted with the deeper
 // subtree first so that operators take a LEAF operand directly:
 //     top = top (+|-|*) T[a]      top = T[a] - top      top = top (+|*) const      top = const - top
+// A PUBLIC VALUE is a third kind of leaf: a constant that is not known when the program is compiled. It is not
+// folded and comes in the fused forms of the constants with an INDEX into the prover's array of values in place of the immediate
+// (plus SUB_PUB: top - const is ADD_CONST of the negated immediate, which an index cannot express).
 // Constants are converted to Montgomery form on the host. Field arithmetic is exact, so the value of
 // every expression is unchanged; the stack (LDS, one column per lane) is only used when both operands
 // of an operator are compound.
@@ -37,6 +40,14 @@ enum Op : uint32_t {
     MUL = 14,        // top = pop * top
     NEG = 15,
     INV = 16,        // top = top == 0 ? 0 : top^-1
+    // public values: P[a] = word a of the array the kernel was handed (Montgomery). The index is part of the wave-uniform
+    // instruction, so P[a] is a scalar load. Only evaluators instantiated with PUB execute them.
+    SET_PUB = 17,    // top = P[a]
+    PUSH_PUB = 18,   // push top; top = P[a]
+    ADD_PUB = 19,    // top = top + P[a]
+    SUB_PUB = 20,    // top = top - P[a]
+    RSUB_PUB = 21,   // top = P[a] - top
+    MUL_PUB = 22,    // top = top * P[a]
 };
 
 #if defined(__HIPCC__)
@@ -44,9 +55,11 @@ enum Op : uint32_t {
 // decode, dispatch — one scalar unit serves a CU's four SIMDs) is shared. Pays for long programs (the quotient's
 // constraints); for the 1-3-instruction programs of the bus replay it does not (profiles/r01_pipeline_experiments.txt).
 // `stk`: slot k of row n at stk[(k * NR + n) * STRIDE].
-template <int STRIDE, bool COLUMN_OPERANDS, int NR>
+// PUB: the program may hold the *_PUB forms, read from `pub` (evaluators without it are the code they were before those existed).
+template <int STRIDE, bool COLUMN_OPERANDS, int NR, bool PUB = false>
 __device__ __forceinline__ void eval_rows(const uint32_t* __restrict__ code, uint32_t n_instr, const uint32_t* __restrict__ trace,
-                                          const size_t (&r)[NR], uint32_t* __restrict__ stk, size_t col_stride, uint32_t (&top)[NR]) {
+                                          const size_t (&r)[NR], uint32_t* __restrict__ stk, size_t col_stride, uint32_t (&top)[NR],
+                                          const uint32_t* __restrict__ pub = nullptr) {
 #pragma unroll
     for (int n = 0; n < NR; ++n) top[n] = 0u;
     int sp = 0;
@@ -101,19 +114,34 @@ __device__ __forceinline__ void eval_rows(const uint32_t* __restrict__ code, uin
         } else if (op == NEG) {
 #pragma unroll
             for (int n = 0; n < NR; ++n) top[n] = bb::neg(top[n]);
-        } else {
+        } else if (!PUB || op == INV) {
 #pragma unroll
             for (int n = 0; n < NR; ++n) top[n] = bb::inv_or_zero(top[n]);
+        } else {
+            const uint32_t pv = pub[a];  // wave-uniform address: one scalar load for all rows and lanes
+            if (op == PUSH_PUB) {
+#pragma unroll
+                for (int n = 0; n < NR; ++n) stk[(sp * NR + n) * STRIDE] = top[n];
+                ++sp;
+            }
+#pragma unroll
+            for (int n = 0; n < NR; ++n) {
+                if (op <= PUSH_PUB) top[n] = pv;
+                else if (op == ADD_PUB) top[n] = bb::add(top[n], pv);
+                else if (op == SUB_PUB) top[n] = bb::sub(top[n], pv);
+                else if (op == RSUB_PUB) top[n] = bb::sub(pv, top[n]);
+                else top[n] = bb::mul(top[n], pv);
+            }
         }
     }
 }
 
 // `stk` = this thread's LDS column (slot k at stk[k * STRIDE]). COLUMN_OPERANDS: operand is a column
 // index, T[a] = trace[a * col_stride + r]; otherwise an element offset, T[a] = trace[a + r].
-template <int STRIDE, bool COLUMN_OPERANDS>
+template <int STRIDE, bool COLUMN_OPERANDS, bool PUB = false>
 __device__ __forceinline__ uint32_t eval(const uint32_t* __restrict__ code, uint32_t n_instr,
                                          const uint32_t* __restrict__ trace, size_t r, uint32_t* __restrict__ stk,
-                                         size_t col_stride = 1) {
+                                         size_t col_stride = 1, const uint32_t* __restrict__ pub = nullptr) {
     uint32_t top = 0u;
     int sp = 0;
     const uint2* ins = reinterpret_cast<const uint2*>(code);
@@ -145,8 +173,16 @@ __device__ __forceinline__ uint32_t eval(const uint32_t* __restrict__ code, uint
             else top = bb::mul(s, top);
         } else if (op == NEG) {
             top = bb::neg(top);
-        } else {
+        } else if (!PUB || op == INV) {
             top = bb::inv_or_zero(top);
+        } else {
+            const uint32_t pv = pub[a];
+            if (op == PUSH_PUB) { stk[sp * STRIDE] = top; ++sp; }
+            if (op <= PUSH_PUB) top = pv;
+            else if (op == ADD_PUB) top = bb::add(top, pv);
+            else if (op == SUB_PUB) top = bb::sub(top, pv);
+            else if (op == RSUB_PUB) top = bb::sub(pv, top);
+            else top = bb::mul(top, pv);
         }
     }
     return top;

@@ -8,14 +8,17 @@
 namespace xbc {
 
 struct Node {
-    enum Kind : uint8_t { COL, CONST, ADD, SUB, MUL, NEG, INV } kind;
-    uint32_t a;  // COL: operand; CONST: canonical value; unary: child; binary: left
+    enum Kind : uint8_t { COL, CONST, ADD, SUB, MUL, NEG, INV, PUB } kind;
+    uint32_t a;  // COL: operand; CONST: canonical value; PUB: index of the public value; unary: child; binary: left
     uint32_t b;  // binary: right
     uint8_t need;
 };
 
 class Compiler {
 public:
+    // A column operand at or above pub_base is public value (operand - pub_base): a PUB leaf — a constant the compiler does not know,
+    // so never folded — emitted in the fused forms of the constants with the index as the operand. The default: no such operand.
+    uint32_t pub_base = 0xffffffffu;
     // Compile one post-fix expression. Returns false if the code is malformed (stack underflow, leftovers,
     // unknown opcode, truncated operand) or needs more than `max_depth` stack slots.
     bool compile(const uint32_t* bc, uint32_t len, std::vector<uint32_t>& out, int max_depth = POWDR_EXPR_STACK_CAPACITY - 1) {
@@ -27,8 +30,9 @@ public:
                 case POWDR_OP_PUSH_APC:
                 case POWDR_OP_PUSH_CONST:
                     if (ip >= len) return false;
-                    st.push_back(leaf(op == POWDR_OP_PUSH_APC ? Node::COL : Node::CONST,
-                                      op == POWDR_OP_PUSH_CONST ? bc[ip] % bb::P : bc[ip]));
+                    if (op == POWDR_OP_PUSH_APC && bc[ip] >= pub_base) st.push_back(leaf(Node::PUB, bc[ip] - pub_base));
+                    else st.push_back(leaf(op == POWDR_OP_PUSH_APC ? Node::COL : Node::CONST,
+                                           op == POWDR_OP_PUSH_CONST ? bc[ip] % bb::P : bc[ip]));
                     ++ip;
                     break;
                 case POWDR_OP_ADD: case POWDR_OP_SUB: case POWDR_OP_MUL: {
@@ -68,7 +72,7 @@ private:
         return r;
     }
     bool is_const(uint32_t n, uint32_t v) const { return nodes_[n].kind == Node::CONST && nodes_[n].a == v; }
-    bool is_leaf(uint32_t n) const { return nodes_[n].kind == Node::COL || nodes_[n].kind == Node::CONST; }
+    bool is_leaf(uint32_t n) const { return nodes_[n].kind == Node::COL || nodes_[n].kind == Node::CONST || nodes_[n].kind == Node::PUB; }
     uint32_t leaf(Node::Kind k, uint32_t a) { nodes_.push_back({k, a, 0, 1}); return (uint32_t)nodes_.size() - 1; }
     uint32_t unary(Node::Kind k, uint32_t x) {
         const Node& c = nodes_[x];
@@ -100,6 +104,7 @@ private:
     static void emit(std::vector<uint32_t>& out, uint32_t op, uint32_t a) { out.push_back(op); out.push_back(a); }
     void emit_leaf(const Node& n, std::vector<uint32_t>& out, bool first) {
         if (n.kind == Node::COL) emit(out, first ? SET_COL : PUSH_COL, n.a);
+        else if (n.kind == Node::PUB) emit(out, first ? SET_PUB : PUSH_PUB, n.a);
         else emit(out, first ? SET_CONST : PUSH_CONST, bb::to_monty(n.a));
     }
     // `first`: the value stack is empty when this subtree starts (its first leaf uses SET instead of PUSH).
@@ -114,7 +119,7 @@ private:
             Frame f = st.back();
             st.pop_back();
             const Node nd = nodes_[f.n];
-            if (nd.kind == Node::COL || nd.kind == Node::CONST) { emit_leaf(nd, out, f.first); continue; }
+            if (nd.kind == Node::COL || nd.kind == Node::CONST || nd.kind == Node::PUB) { emit_leaf(nd, out, f.first); continue; }
             if (nd.kind == Node::NEG || nd.kind == Node::INV) {
                 if (f.state == 0) { st.push_back({f.n, f.first, 1}); st.push_back({nd.a, f.first, 0}); }
                 else emit(out, nd.kind == Node::NEG ? NEG : INV, 0);
@@ -134,12 +139,14 @@ private:
             if (lr_leaf) {
                 const Node& R = nodes_[r];
                 if (R.kind == Node::COL) emit(out, nd.kind == Node::ADD ? ADD_COL : nd.kind == Node::SUB ? SUB_COL : MUL_COL, R.a);
+                else if (R.kind == Node::PUB) emit(out, nd.kind == Node::ADD ? ADD_PUB : nd.kind == Node::SUB ? SUB_PUB : MUL_PUB, R.a);
                 else if (nd.kind == Node::ADD) emit(out, ADD_CONST, bb::to_monty(R.a));
                 else if (nd.kind == Node::SUB) emit(out, ADD_CONST, bb::to_monty(fsub(0, R.a)));
                 else emit(out, MUL_CONST, bb::to_monty(R.a));
             } else if (ll_leaf) {
                 const Node& L = nodes_[l];
                 if (L.kind == Node::COL) emit(out, nd.kind == Node::ADD ? ADD_COL : nd.kind == Node::SUB ? RSUB_COL : MUL_COL, L.a);
+                else if (L.kind == Node::PUB) emit(out, nd.kind == Node::ADD ? ADD_PUB : nd.kind == Node::SUB ? RSUB_PUB : MUL_PUB, L.a);
                 else if (nd.kind == Node::ADD) emit(out, ADD_CONST, bb::to_monty(L.a));
                 else if (nd.kind == Node::SUB) emit(out, RSUB_CONST, bb::to_monty(L.a));
                 else emit(out, MUL_CONST, bb::to_monty(L.a));

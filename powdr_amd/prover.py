@@ -22,6 +22,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_segment_context_bytes", "pw_segment_stream_plan", "pw_segment_last_plan_tables",
                   "pw_prover_create_preprocessed", "pw_prover_preprocessed_root", "pw_prover_preprocessed_width", "pw_verify_segment_preprocessed",
                   "pw_prover_create_transition", "pw_prover_row_flags", "pw_verify_segment_transition",
+                  "pw_prover_create_public", "pw_prover_n_public", "pw_prover_set_public_values", "pw_verify_segment_public",
+                  "pw_segment_proof_public_values", "pw_verify_segment_chain", "pw_public_programs_check",
                   "pw_check_segment_buses", "pw_bus_check_scratch_bytes", "pw_bus_check_peak_bytes", "pw_bus_check_last_stats"]
 
 lib.pw_prover_create.restype = C.c_void_p
@@ -41,6 +43,12 @@ lib.pw_prover_create_transition.restype = C.c_void_p
 lib.pw_prover_create_transition.argtypes = lib.pw_prover_create_preprocessed.argtypes
 lib.pw_prover_row_flags.restype = C.c_uint32
 lib.pw_prover_row_flags.argtypes = [C.c_void_p]
+lib.pw_prover_create_public.restype = C.c_void_p
+lib.pw_prover_create_public.argtypes = lib.pw_prover_create_preprocessed.argtypes[:5] + [C.c_uint32] + lib.pw_prover_create_preprocessed.argtypes[5:]
+lib.pw_prover_n_public.restype = C.c_uint32
+lib.pw_prover_n_public.argtypes = [C.c_void_p]
+lib.pw_prover_set_public_values.restype = C.c_int
+lib.pw_prover_set_public_values.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 lib.pw_prover_prove.restype = C.c_int
 lib.pw_prover_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
 lib.pw_prover_check_constraints.restype = C.c_int
@@ -172,6 +180,34 @@ lib.pw_verify_segment_preprocessed.argtypes = [C.POINTER(PwStarkConfig), C.POINT
                                                C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
 lib.pw_verify_segment_transition.restype = C.c_int
 lib.pw_verify_segment_transition.argtypes = lib.pw_verify_segment_preprocessed.argtypes
+
+
+class PwAirPublic(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("expected", C.c_void_p)]
+
+
+class PwChainSegment(C.Structure):
+    _fields_ = [("airs", C.POINTER(PwAirDescription)), ("pre", C.POINTER(PwAirPreprocessed)), ("pub", C.POINTER(PwAirPublic)), ("n_airs", C.c_size_t),
+                ("logup", C.c_int), ("proof", C.c_void_p), ("n_words", C.c_size_t), ("check_balance", C.c_int)]
+
+
+class PwChainLink(C.Structure):
+    _fields_ = [("air_from", C.c_uint32), ("index_from", C.c_uint32), ("air_to", C.c_uint32), ("index_to", C.c_uint32)]
+
+
+lib.pw_verify_segment_public.restype = C.c_int
+lib.pw_verify_segment_public.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.POINTER(PwAirPreprocessed), C.POINTER(PwAirPublic),
+                                         C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+lib.pw_segment_proof_public_values.restype = C.c_size_t
+lib.pw_segment_proof_public_values.argtypes = [C.POINTER(PwAirDescription), C.POINTER(PwAirPublic), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                               C.c_void_p, C.c_size_t]
+lib.pw_verify_segment_chain.restype = C.c_int
+lib.pw_verify_segment_chain.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwChainSegment), C.c_size_t, C.POINTER(PwChainLink), C.c_size_t,
+                                        C.POINTER(C.c_size_t)]
+lib.pw_public_programs_check.restype = C.c_int
+lib.pw_public_programs_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
 lib.pw_verify_airs.restype = C.c_int
 lib.pw_verify_airs.argtypes = [C.POINTER(PwStarkConfig), C.POINTER(PwAirDescription), C.c_size_t, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p]
@@ -191,7 +227,13 @@ class RowOperands:
         self.width, self.pre_width = int(width), int(pre_width)
         self.w1 = self.width + self.pre_width
         self.is_first_row, self.is_last_row, self.is_transition = 2 * self.w1, 2 * self.w1 + 1, 2 * self.w1 + 2
-        self.bound = 2 * self.w1 + 3  # constraint operands below this; interaction operands below w1
+        self.bound = 2 * self.w1 + 3  # constraint operands below this (+ n_public: public(k)); interaction operands below w1
+
+    def public(self, k: int) -> int:
+        """public value k of the AIR (Prover(..., n_public=)): a constraint operand of degree 0"""
+        if not 0 <= k < 256:
+            raise ValueError(f"public value {k}: an AIR has at most 256")
+        return self.bound + k
 
     def next(self, c: int) -> int:
         if not 0 <= c < self.w1:
@@ -405,17 +447,24 @@ def set_device_budget(n_bytes: int) -> None:
 
 
 def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logup: bool = False, check_balance: bool = False,
-                   preprocessed=None, transition: bool = False):
+                   preprocessed=None, transition: bool = False, public=None):
     """Host verification of a segment proof. descs: [(width, log_height, cons_bytecode, cons_spans, interactions-or-None)]
     -> (code, sum of the AIRs' cumulative bus sums). 0 = valid; ((i+1) << 8) | 2 = constraint identity of AIR i;
     14 = the bus sums do not cancel (check_balance); 16 = a preprocessed row does not open against its root.
     preprocessed: None (pw_verify_segment) or, per AIR, None | (width, root8) — the verifying key's preprocessed commitments
     (pw_verify_segment_preprocessed). transition: constraint operands over the row layout (RowOperands; pw_verify_segment_transition,
-    which also takes `preprocessed`)."""
+    which also takes `preprocessed`). public: None, or per AIR None (no public values) | an int (so many, accept what the proof
+    carries) | the expected values (pw_verify_segment_public, DESIGN.md §5k: operands RowOperands.public(k); 17 = the proof's
+    values differ from the expected ones)."""
     recs, keep = _air_descriptions(descs)
     pr = np.ascontiguousarray(proof, dtype=np.uint32)
     cfg = PwStarkConfig(num_queries, pow_bits)
     total = np.zeros(4, np.uint32)
+    if public is not None:
+        pre = _preprocessed_records(preprocessed, len(descs))
+        pub, keep_pub = _public_records(public, len(descs))
+        rc = int(lib.pw_verify_segment_public(C.byref(cfg), recs, pre, pub, len(descs), int(logup), _vp(pr), len(pr), int(check_balance), _vp(total)))
+        return rc, total
     if transition and preprocessed is None:
         rc = int(lib.pw_verify_segment_transition(C.byref(cfg), recs, None, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr),
                                                   int(check_balance), total.ctypes.data_as(C.c_void_p)))
@@ -436,6 +485,87 @@ def verify_segment(descs, proof, num_queries: int = 100, pow_bits: int = 0, logu
     rc = int(fn(C.byref(cfg), recs, pre, len(descs), int(logup), pr.ctypes.data_as(C.c_void_p), len(pr), int(check_balance),
                 total.ctypes.data_as(C.c_void_p)))
     return rc, total
+
+
+def _preprocessed_records(preprocessed, n: int):
+    """per AIR None | (width, root8) -> PwAirPreprocessed[n], or None"""
+    if preprocessed is None:
+        return None
+    assert len(preprocessed) == n
+    pre = (PwAirPreprocessed * max(n, 1))()
+    for i, e in enumerate(preprocessed):
+        if e is not None:
+            w, root = e
+            pre[i].width = int(w)
+            for k, x in enumerate(np.asarray(root, dtype=np.uint32).reshape(8)):
+                pre[i].root8[k] = int(x)
+    return pre
+
+
+def _public_records(public, n: int):
+    """per AIR None | count | expected values -> (PwAirPublic[n], the arrays its pointers point into)"""
+    assert len(public) == n
+    pub, keep = (PwAirPublic * max(n, 1))(), []
+    for i, e in enumerate(public):
+        if e is None:
+            continue
+        if isinstance(e, (int, np.integer)):
+            pub[i].n = int(e)
+            continue
+        v = np.ascontiguousarray(e, dtype=np.uint32).reshape(-1)
+        keep.append(v)
+        pub[i].n, pub[i].expected = len(v), v.ctypes.data
+    return pub, keep
+
+
+def segment_public_values(descs, proof, public, air: int) -> np.ndarray:
+    """pw_segment_proof_public_values: the public values AIR `air` carries in `proof` (canonical words). descs / public as for
+    verify_segment (only the counts of `public` matter). Raises when the proof's header does not match; nothing else is checked."""
+    recs, keep = _air_descriptions(descs)
+    pub, keep_pub = _public_records(public, len(descs))
+    pr = np.ascontiguousarray(proof, dtype=np.uint32)
+    out = np.zeros(max(int(pub[air].n), 1), np.uint32)
+    n = lib.pw_segment_proof_public_values(recs, pub, len(descs), _vp(pr), len(pr), air, _vp(out), len(out))
+    if n == C.c_size_t(-1).value:
+        raise ValueError("the proof's header does not match the descriptions")
+    return out[:n].copy()
+
+
+def verify_segment_chain(segments, links, num_queries: int = 100, pow_bits: int = 0):
+    """pw_verify_segment_chain (host only): segments = [dict(descs, proof, public, preprocessed=None, logup=False, check_balance=False)]
+    with the fields verify_segment takes; links = [(air_from, index_from, air_to, index_to)]: that public value of segment s equals this
+    one of segment s + 1 (system_airs.connector_links). -> (code, where): 0; a segment's verifier code and its index; 18 and
+    s * len(links) + link. That every segment ran the same program (the program AIR's preprocessed root) is the caller's to check."""
+    n = len(segments)
+    segs, keep = (PwChainSegment * max(n, 1))(), []
+    for i, g in enumerate(segments):
+        recs, k1 = _air_descriptions(g["descs"])
+        pre = _preprocessed_records(g.get("preprocessed"), len(g["descs"]))
+        pub, k2 = _public_records(g["public"], len(g["descs"])) if g.get("public") is not None else (None, [])
+        pr = np.ascontiguousarray(g["proof"], dtype=np.uint32)
+        keep += [recs, k1, pre, pub, k2, pr]
+        segs[i] = PwChainSegment(recs, pre, pub, len(g["descs"]), int(g.get("logup", False)), pr.ctypes.data, len(pr), int(g.get("check_balance", False)))
+    lk = (PwChainLink * max(len(links), 1))(*[PwChainLink(*[int(x) for x in l]) for l in links])
+    cfg = PwStarkConfig(num_queries, pow_bits)
+    where = C.c_size_t(0)
+    rc = int(lib.pw_verify_segment_chain(C.byref(cfg), segs, n, lk, len(links), C.byref(where)))
+    return rc, int(where.value)
+
+
+def public_programs_check(width: int, cons_bytecode, cons_spans, n_public: int, interactions=None, pre_width: int = 0):
+    """What Prover(..., n_public=) checks and compiles, without a GPU (test hook pw_public_programs_check): None when the entry would
+    refuse the AIR, else dict(max_degree, row_flags, xbc: the constraints' xbc code, source: the generated HIP of the specialised
+    quotient kernels — a function of the programs alone)."""
+    bc = np.ascontiguousarray(cons_bytecode, dtype=np.uint32)
+    sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
+    tables, _ = _interaction_tables(interactions)
+    deg, rf, nx, ns = C.c_int(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+    args = (width, pre_width, n_public, _vp(bc), len(bc), _vp(sp), len(sp), *tables, C.byref(deg), C.byref(rf))
+    if lib.pw_public_programs_check(*args, None, 0, C.byref(nx), None, 0, C.byref(ns)) != 0:
+        return None
+    xbc, src = np.zeros(max(nx.value, 1), np.uint32), C.create_string_buffer(ns.value + 1)
+    lib.pw_public_programs_check(*args, _vp(xbc), nx.value, C.byref(nx), src, ns.value + 1, C.byref(ns))
+    return dict(max_degree=deg.value, row_flags=rf.value, xbc=xbc[:nx.value].copy(), source=src.value.decode())
 
 
 def verify_airs(descs, proofs, num_queries: int = 100, pow_bits: int = 0, shared_bus_seed: bool = False, check_balance: bool = False):
@@ -590,17 +720,28 @@ class Prover:
     width + pre_width - 1 of the programs are those columns (pw_prover_create_preprocessed; segment proofs only, at that height).
 
     transition = True: the constraint programs may read the next row and the row selectors (RowOperands, DESIGN.md §5h;
-    pw_prover_create_transition, with or without `preprocessed`; segment proofs only)."""
+    pw_prover_create_transition, with or without `preprocessed`; segment proofs only).
+
+    n_public > 0: the AIR has that many public values (RowOperands.public(k); pw_prover_create_public, with or without
+    `preprocessed` and next-row reads; segment proofs only): set_public_values before every segment proof whose values differ."""
 
     def __init__(self, width: int, cons_bytecode, cons_spans, num_queries: int = 100, pow_bits: int = 0, interactions=None,
-                 preprocessed=None, transition: bool = False):
+                 preprocessed=None, transition: bool = False, n_public: int = 0):
         bc = np.ascontiguousarray(cons_bytecode, dtype=np.uint32)
         sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
         cfg = PwStarkConfig(num_queries, pow_bits)
         self.width = width
         self.pre_width = 0
+        self.n_public = int(n_public)
         tables, _ = _interaction_tables(interactions)
-        if transition or preprocessed is not None:
+        if n_public:
+            t, pw_, lh = preprocessed if preprocessed is not None else (None, 0, 0)
+            if t is not None:
+                assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
+            self._h = lib.pw_prover_create_public(C.byref(cfg), width, pw_, lh, t.data_ptr() if t is not None else None, int(n_public), _vp(bc), len(bc),
+                                                  _vp(sp), len(sp), *tables)
+            self.pre_width = pw_
+        elif transition or preprocessed is not None:
             t, pw_, lh = preprocessed if preprocessed is not None else (None, 0, 0)
             if t is not None:
                 assert t.numel() == pw_ << lh, "the fixed matrix must hold pre_width x 2^log_height words"
@@ -618,6 +759,12 @@ class Prover:
     def row_flags(self) -> int:
         """pw_prover_row_flags: bit 0 the constraints read a next-row operand, bit 1 a row selector (0: not row-aware)."""
         return int(lib.pw_prover_row_flags(self._h))
+
+    def set_public_values(self, values) -> None:
+        """pw_prover_set_public_values: n_public canonical words (the prover keeps a copy; a segment proof snapshots them when it begins)."""
+        v = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+        if lib.pw_prover_set_public_values(self._h, _vp(v), len(v)) != 0:
+            raise ValueError(f"{len(v)} public values for an AIR with {self.n_public}, or a word that is no canonical field element")
 
     def preprocessed_root(self) -> np.ndarray:
         """pw_prover_preprocessed_root: the commitment to the fixed matrix (8 canonical words; the verifying key's part)."""

@@ -49,6 +49,13 @@ PROGRAM_COLUMNS = ["pc", "opcode", "a", "b", "c", "d", "e", "f", "g"]
 BOUNDARY_COLUMNS = (["is_valid", "as", "ptr", "p_lo", "p_hi"] + [f"init{i}" for i in range(4)] + ["init_ts"] + [f"fin{i}" for i in range(4)]
                     + ["fin_ts", "same_as", "d_lo", "d_hi"])
 BOUNDARY_WIDTH = len(BOUNDARY_COLUMNS)  # 18
+CONNECTOR_PUBLIC = ["start_pc", "start_ts", "end_pc", "end_ts"]  # the public values of connector_air(public=True), in this order
+CONNECTOR_CONSTRAINTS = [  # pv0 .. pv3 = CONNECTOR_PUBLIC: row 0 is the state the segment starts from, row 1 the one it ends at
+    ("start pc", "(1 - is_end) * (pc - pv0)"),
+    ("start timestamp", "(1 - is_end) * (timestamp - pv1)"),
+    ("end pc", "is_end * (pc - pv2)"),
+    ("end timestamp", "is_end * (timestamp - pv3)"),
+]
 BOUNDARY_CONSTRAINTS = [
     ("is_valid boolean", "is_valid * (is_valid - 1)"),
     ("same_as boolean", "same_as * (same_as - 1)"),
@@ -77,6 +84,7 @@ class SystemAir:
     fixed: np.ndarray | None = None
     transition: bool = False
     log_h: int | None = None
+    n_public: int = 0
     _table: torch.Tensor | None = field(default=None, repr=False)
 
     def fixed_table(self, device="cuda") -> torch.Tensor:
@@ -91,7 +99,7 @@ class SystemAir:
             pre = (self.fixed_table(), self.pre_width, self.log_h)
             torch.cuda.synchronize()  # the table exists before the prover copies it (on the library's stream)
         return prover.Prover(self.width, self.cons[0], self.cons[1], num_queries=num_queries, pow_bits=pow_bits, interactions=self.inter,
-                             preprocessed=pre, transition=self.transition)
+                             preprocessed=pre, transition=self.transition, n_public=self.n_public)
 
     def description(self, log_h: int | None = None):
         """(width, log_height, cons_bytecode, cons_spans, interactions): an entry of verify_segment's `descs` (transition=True)"""
@@ -122,11 +130,31 @@ def program_air(table, bus: int = BUS_PC) -> SystemAir:
     return SystemAir("program", 1, NO_CONS, inter, ["freq"], pre_width=len(PROGRAM_COLUMNS), fixed=table, log_h=rows.bit_length() - 1)
 
 
-def connector_air(bus: int = BUS_EXEC) -> SystemAir:
-    """Main [pc, timestamp] | preprocessed [is_end] = (0, 1): one interaction with multiplicity 1 - 2 is_end."""
+def connector_air(bus: int = BUS_EXEC, public: bool = False) -> SystemAir:
+    """Main [pc, timestamp] | preprocessed [is_end] = (0, 1): one interaction with multiplicity 1 - 2 is_end. public: the AIR also has
+    the four public values CONNECTOR_PUBLIC and the four degree-2 constraints CONNECTOR_CONSTRAINTS that tie its two rows to them
+    (DESIGN.md §5k): the segment proof then SAYS where the execution started and ended (row flags 0: no next row, no selector)."""
     mult = [OP_PUSH_CONST, 1, OP_PUSH_CONST, 2, OP_PUSH_APC, 2, OP_MUL, OP_SUB]
-    return SystemAir("connector", 2, NO_CONS, _tables(bus, [(mult, [_col(0), _col(1)])]), ["pc", "timestamp"], pre_width=1,
-                     fixed=np.array([[0, 1]], np.uint32), log_h=1)
+    cons = NO_CONS
+    if public:
+        rows = prover.row_operands(2, 1)
+        # (named operands: the three columns and, as plain operand numbers, the public values)
+        col = {"pc": 0, "timestamp": 1, "is_end": 2, **{f"pv{k}": rows.public(k) for k in range(len(CONNECTOR_PUBLIC))}}
+        bc, spans = [], []
+        for _, text in CONNECTOR_CONSTRAINTS:
+            code = air_text.compile_expr(text, col, None)
+            spans.append((len(bc), len(code)))
+            bc += code
+        cons = (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2))
+    return SystemAir("connector", 2, cons, _tables(bus, [(mult, [_col(0), _col(1)])]), ["pc", "timestamp"], pre_width=1,
+                     fixed=np.array([[0, 1]], np.uint32), log_h=1, n_public=len(CONNECTOR_PUBLIC) if public else 0)
+
+
+def connector_links(connector_index: int):
+    """The links of prover.verify_segment_chain that make consecutive segments consecutive: the final (pc, timestamp) of one segment's
+    public connector (AIR `connector_index` of every segment) is the initial one of the next."""
+    i, k = int(connector_index), CONNECTOR_PUBLIC.index
+    return [(i, k("end_pc"), i, k("start_pc")), (i, k("end_ts"), i, k("start_ts"))]
 
 
 def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANGE, bitwise_bus: int = BUS_BITWISE) -> SystemAir:
@@ -210,16 +238,18 @@ def memory_boundary_trace(airs, cap_log_height: int, table_bytes: int = 0, bus: 
     return trace, int(lh.value), int(locations.value), int(status.value)
 
 
-def connector_trace(airs, bus: int = BUS_EXEC) -> torch.Tensor:
+def connector_trace(airs, bus: int = BUS_EXEC, with_states: bool = False):
     """The connector's 2 x 2 main trace [pc0, pc1, ts0, ts1] (Montgomery) from what check_segment_buses leaves over on the execution
-    bridge: exactly the initial state (received once and never sent) and the final one (sent once and never received)."""
+    bridge: exactly the initial state (received once and never sent) and the final one (sent once and never received).
+    with_states: (trace, (pc0, ts0), (pc1, ts1)) — the two tuples as canonical words."""
     _, tuples = prover.check_segment_buses(airs, buses=[bus], tuple_cap=8)
     start = [t for t in tuples if t["net_multiplicity"] == P - 1 and t["n_args"] == 2]
     end = [t for t in tuples if t["net_multiplicity"] == 1 and t["n_args"] == 2]
     if len(tuples) != 2 or len(start) != 1 or len(end) != 1:
         raise ValueError(f"the execution bridge (bus {bus}) does not leave one initial and one final state: {tuples}")
     (pc0, ts0), (pc1, ts1) = start[0]["args"], end[0]["args"]
-    return _to_device([pc0, pc1, ts0, ts1])
+    trace = _to_device([pc0, pc1, ts0, ts1])
+    return (trace, (pc0, ts0), (pc1, ts1)) if with_states else trace
 
 
 def last_stats() -> dict:
@@ -239,12 +269,12 @@ def set_boundary_start_slots(log_slots: int) -> None:
 
 
 def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int = 100, pow_bits: int = 0, pc_step: int = 4, table_bytes: int = 0,
-                  cap_log_height: int = 16):
+                  cap_log_height: int = 16, public_connector: bool = False):
     """airs: [dict(prover, trace (device tensor), log_h, ...)] — every AIR that sends on the execution bridge, the memory bus and the
     PC lookup, traces made. Appends the program, connector and boundary AIRs as dicts of the same shape (name, role "system", air =
     the SystemAir, width, log_h, cons, inter, trace, prover, pre) and returns the list. periphery (tracegen.Periphery): its histograms
     receive the boundary AIR's range and byte lookups (_apc_apply_bus on its trace) — call this BEFORE the periphery traces are made
-    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). Raises on foreign instructions, on a boundary status other than 0 and on an execution bridge that is not a chain."""
+    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). public_connector: the connector with its four public values (connector_air(public=True)), set from the two states connector_trace finds; its dict also has public = those values. Raises on foreign instructions, on a boundary status other than 0 and on an execution bridge that is not a chain."""
     from .segment_workload import BusReplay
 
     seg = [(a["prover"], a["trace"].data_ptr(), a["log_h"]) for a in airs]
@@ -259,10 +289,14 @@ def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int
     freq, n_foreign, first = program_frequencies(seg, prog.fixed_table(), prog.log_h, pc_base, pc_step)
     if n_foreign:
         raise ValueError(f"{n_foreign} executed instructions are not in the program, the first: {first}")
-    con = connector_air()
+    con = connector_air(public=public_connector)
+    con_trace, start, end = connector_trace(seg, with_states=True)
     out = list(airs)
-    for air, t, h in ((prog, freq, prog.log_h), (con, connector_trace(seg), 1), (bnd, trace, lh)):
+    for air, t, h in ((prog, freq, prog.log_h), (con, con_trace, 1), (bnd, trace, lh)):
         p = air.make_prover(num_queries, pow_bits)
         out.append(dict(name=air.name, role="system", air=air, width=air.width, log_h=h, cons=air.cons, inter=air.inter, trace=t, prover=p,
                         pre=(air.fixed_table(), air.pre_width, air.log_h) if air.pre_width else None))
+        if air.n_public:
+            out[-1]["public"] = np.array([*start, *end], np.uint32)
+            p.set_public_values(out[-1]["public"])
     return out

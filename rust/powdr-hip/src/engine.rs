@@ -16,6 +16,7 @@ use openvm_circuit::arch::{
 };
 use openvm_stark_backend::prover::{AirProvingContext, ProverBackend, ProvingContext};
 use openvm_stark_backend::{keygen::types::MultiStarkProvingKey, StarkEngine};
+use openvm_stark_backend::p3_field::PrimeField32; // (as_canonical_u32 of the public values)
 use openvm_stark_sdk::p3_baby_bear::BabyBear;
 use crate::isa_hip::OpenVmIsaHip;
 use powdr_openvm::isa::OpenVmISA;
@@ -65,7 +66,14 @@ impl HipEngine {
                 // `when_transition()`) takes the row layout; the others keep the plain entry and its words
                 let rows = p.reads_rows();
                 let handle = unsafe {
-                    if rows {
+                    if p.n_public > 0 {
+                        // public values (`builder.public_values()`): operands behind the row layout, set per segment
+                        ffi::pw_prover_create_public(
+                            &config, p.width, 0, 0, core::ptr::null(), p.n_public, p.cons_bytecode.as_ptr(), p.cons_bytecode.len(),
+                            p.cons_spans.as_ptr(), p.cons_spans.len() / 2, p.interactions.as_ptr(), p.interactions.len() / 3,
+                            p.inter_spans.as_ptr(), p.inter_spans.len() / 2, p.inter_bytecode.as_ptr(), p.inter_bytecode.len(),
+                        )
+                    } else if rows {
                         ffi::pw_prover_create_transition(
                             &config, p.width, 0, 0, core::ptr::null(), p.cons_bytecode.as_ptr(), p.cons_bytecode.len(),
                             p.cons_spans.as_ptr(), p.cons_spans.len() / 2, p.interactions.as_ptr(), p.interactions.len() / 3,
@@ -113,6 +121,12 @@ impl HipEngine {
             }
             assert!(m.height().is_power_of_two() && m.width() as u32 == self.provers[*air_id].width);
             let log_h = m.height().trailing_zeros();
+            // `AirProvingContext.public_values` (canonical words): the prover keeps a copy and the proof snapshots it when it begins
+            if unsafe { ffi::pw_prover_n_public(self.provers[*air_id].handle) } > 0 {
+                let pv: Vec<u32> = air_ctx.public_values.iter().map(|x| x.as_canonical_u32()).collect();
+                let rc = unsafe { ffi::pw_prover_set_public_values(self.provers[*air_id].handle, pv.as_ptr(), pv.len()) };
+                assert!(rc == 0, "AIR {air_id}: {} public values do not match the AIR's count", pv.len());
+            }
             airs.push(ffi::PwSegmentAir {
                 prover: self.provers[*air_id].handle,
                 d_trace: m.buffer().as_ptr() as *const u32,
@@ -201,10 +215,13 @@ impl HipEngine {
             })
             .collect();
         let mut total = [0u32; 4];
-        // (the row-layout verifier: exactly pw_verify_segment for segments without a row-aware AIR)
+        // (the public-values verifier: exactly pw_verify_segment for segments without a row-aware AIR or public values; the values the
+        // proof carries are accepted here — `pw_segment_proof_public_values` reads them, `pw_verify_segment_chain` links segments)
+        let publics: Vec<ffi::PwAirPublic> =
+            proof.air_ids.iter().map(|id| ffi::PwAirPublic { n: programs[*id].n_public, expected: core::ptr::null() }).collect();
         let rc = unsafe {
-            ffi::pw_verify_segment_transition(&self.config, descs.as_ptr(), core::ptr::null(), descs.len(), 1, proof.words.as_ptr(),
-                                              proof.words.len(), 1, total.as_mut_ptr())
+            ffi::pw_verify_segment_public(&self.config, descs.as_ptr(), core::ptr::null(), publics.as_ptr(), descs.len(), 1, proof.words.as_ptr(),
+                                          proof.words.len(), 1, total.as_mut_ptr())
         };
         if rc == 0 { Ok(()) } else { Err(rc) }
     }
@@ -218,6 +235,8 @@ pub struct AirProgram {
     pub interactions: Vec<u32>,   // {bus, n_args, first span} triples
     pub inter_spans: Vec<u32>,    // {off, len} pairs, [mult, arg0, ...] per interaction
     pub inter_bytecode: Vec<u32>,
+    /// `BaseAirWithPublicValues::num_public_values`: constraint operands 2 * width + 3 + k; 0 for `PowdrAir`
+    pub n_public: u32,
 }
 
 impl AirProgram {
@@ -231,7 +250,7 @@ impl AirProgram {
                 ip += 1;
                 if op == 0 || op == 1 {
                     // PUSH_APC / PUSH_CONST and their operand
-                    if op == 0 && ip < code.len() && code[ip] >= self.width {
+                    if op == 0 && ip < code.len() && code[ip] >= self.width && code[ip] < 2 * self.width + 3 {
                         return true;
                     }
                     ip += 1;

@@ -321,6 +321,35 @@ pub struct PwAirPreprocessed {
     pub width: u32,
     pub root8: [u32; 8],
 }
+/// The public values of one AIR as the verifier is told them: `n` of them, `expected` null = accept the proof's
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct PwAirPublic {
+    pub n: u32,
+    pub expected: *const u32,
+}
+/// One segment of `pw_verify_segment_chain`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct PwChainSegment {
+    pub airs: *const PwAirDescription,
+    pub pre: *const PwAirPreprocessed,
+    pub pub_: *const PwAirPublic,
+    pub n_airs: usize,
+    pub logup: c_int,
+    pub proof: *const u32,
+    pub n_words: usize,
+    pub check_balance: c_int,
+}
+/// public value `index_from` of AIR `air_from` in segment s = public value `index_to` of AIR `air_to` in segment s + 1
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwChainLink {
+    pub air_from: u32,
+    pub index_from: u32,
+    pub air_to: u32,
+    pub index_to: u32,
+}
 
 extern "C" {
     pub fn pw_prover_create(cfg: *const PwStarkConfig, width: u32, cons_bytecode: *const u32, bytecode_len: usize,
@@ -347,6 +376,15 @@ extern "C" {
                                        inter_bytecode: *const u32, inter_bytecode_len: usize) -> *mut PwProver;
     /// bit 0: reads a next-row operand, bit 1: reads a selector (0: not row-aware)
     pub fn pw_prover_row_flags(p: *const PwProver) -> u32;
+    /// public values: constraint operands 2 W1 + 3 + k, k < n_public <= 256, degree 0; n_public = 0: exactly
+    /// `pw_prover_create_transition`; segment proofs only, after `pw_prover_set_public_values`
+    pub fn pw_prover_create_public(cfg: *const PwStarkConfig, width: u32, pre_width: u32, log_height: u32, d_pre: *const u32, n_public: u32,
+                                   cons_bytecode: *const u32, bytecode_len: usize, cons_spans: *const u32, n_constraints: usize,
+                                   interactions: *const u32, n_interactions: usize, inter_spans: *const u32, n_inter_spans: usize,
+                                   inter_bytecode: *const u32, inter_bytecode_len: usize) -> *mut PwProver;
+    pub fn pw_prover_n_public(p: *const PwProver) -> u32;
+    /// `values`: n canonical host words (copied); -1: n != n_public or a word >= p
+    pub fn pw_prover_set_public_values(p: *mut PwProver, values: *const u32, n: usize) -> c_int;
     pub fn pw_prover_prove(p: *mut PwProver, d_trace: *const u32, log_height: u32, proof_words: *mut *const u32,
                            n_words: *mut usize) -> c_int;
     /// The trace is handed over (the engine owns `common_main`): a streamed proof leaves the coefficient arrays in its place.
@@ -408,6 +446,15 @@ extern "C" {
     pub fn pw_verify_segment_transition(cfg: *const PwStarkConfig, airs: *const PwAirDescription, pre: *const PwAirPreprocessed,
                                         n_airs: usize, logup: c_int, proof_words: *const u32, n_words: usize, check_balance: c_int,
                                         total_sum4: *mut u32) -> c_int;
+    /// 17 = the proof's public values differ from `expected`; pub null or every n 0: `pw_verify_segment_transition`
+    pub fn pw_verify_segment_public(cfg: *const PwStarkConfig, airs: *const PwAirDescription, pre: *const PwAirPreprocessed,
+                                    pub_: *const PwAirPublic, n_airs: usize, logup: c_int, proof_words: *const u32, n_words: usize,
+                                    check_balance: c_int, total_sum4: *mut u32) -> c_int;
+    pub fn pw_segment_proof_public_values(airs: *const PwAirDescription, pub_: *const PwAirPublic, n_airs: usize, proof_words: *const u32,
+                                          n_words: usize, air: usize, out: *mut u32, cap: usize) -> usize;
+    /// 0; a segment's verifier code with `where_` = its index; 18 = a link fails, `where_` = s * n_links + link
+    pub fn pw_verify_segment_chain(cfg: *const PwStarkConfig, segments: *const PwChainSegment, n_segments: usize, links: *const PwChainLink,
+                                   n_links: usize, where_: *mut usize) -> c_int;
     pub fn pw_prove_airs(airs: *const PwSegmentAir, n_airs: usize, shared_bus_seed: c_int, n_workers: c_uint,
                          proofs: *mut *const u32, n_words: *mut usize, bus_seed8: *mut u32) -> c_int;
     pub fn pw_verify_airs(cfg: *const PwStarkConfig, airs: *const PwAirDescription, n_airs: usize,
