@@ -6,15 +6,17 @@
 // consecutive butterfly stages on a tile of 2^(k+c) elements, so the data crosses HBM once per
 // group, not once per stage. A tile gathers the 2^k elements whose indices differ in the
 // group's k active bits, times 2^c neighbouring elements (c low index bits) so that every global
-// access of a strided group is a 64-byte contiguous segment.
+// access of a strided group is a contiguous segment of 64 bytes (128 for tall transforms: plan_groups).
 //
-// Inside a group a thread owns 16 (or 32) elements in VGPRs and runs up to 4 stages on them
-// without touching LDS ("round", a radix-16 butterfly network); rounds exchange data through a
-// padded LDS tile (one extra word per 32: conflict-free for every round's access pattern). The
+// Inside a group a "round" runs up to 4 stages without touching LDS: a thread holds a "slot", the
+// 2^logr <= 16 elements of a radix-16 butterfly network, in VGPRs, and takes the 16 (2^12-element
+// tile) or 32 (2^13) elements it owns per round one slot after the other; rounds exchange data
+// through a padded LDS tile (one extra word per 32: conflict-free for every round's access pattern). The
 // first round of a group loads straight from HBM into registers and the last round stores
 // straight from registers to HBM. Twiddles: the factor of a butterfly splits into a per-thread
-// base (one table lookup per round, squared from stage to stage) times a constant 16th/8th/4th
-// root of unity, so no per-butterfly table traffic exists.
+// base (one table lookup per slot, squared from stage to stage) times a constant 16th/8th/4th
+// root of unity, so no per-butterfly table traffic exists; groups whose factors do not depend on
+// the tile read all of a slot's twiddles from a small per-group table instead (group_twiddles).
 //
 //   inverse  = DIF (Gentleman-Sande), natural-order input -> bit-reversed output
 //   forward  = DIT (Cooley-Tukey),    bit-reversed input  -> natural-order output
@@ -30,11 +32,11 @@
 #include "common.hpp"
 #include "prover_internal.hpp"
 
-#include <atomic>
 #include <cstdlib>
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace pw {
@@ -42,9 +44,6 @@ namespace pw {
 namespace {
 
 constexpr int kBlock = 256;
-// 2^c neighbouring elements ride along in strided tiles: 64-byte segments (c = 4) up to 2^17 rows, 128-byte ones (c = 5) from
-// 2^18 rows on, where the strided passes run at 3.5 TB/s with 64-byte segments (profiles/r02_bench_ntt.txt); POWDR_NTT_C forces one
-
 __constant__ uint32_t c_roots16[2][8];  // [0]: w16^r forward, [1]: inverse (Montgomery), r < 8
 
 __global__ void fill_powers_kernel(uint32_t* out, uint32_t base, uint32_t scale, size_t n) {
@@ -70,12 +69,11 @@ struct GroupParams {
     int logr[4];  // window width per round
     unsigned long long n_tiles;  // tiles per column = 2^(n-B)
     int canonical_out;  // forward transform: the last group reduces its [0, 2p) values to [0, p) when it stores
-    unsigned twt_off[4];  // per round: offset of its twiddle table (contiguous groups of the fused LDE kernel, see FusedTwiddles)
+    unsigned twt_off[4];  // per round: offset of its twiddle table (tile-invariant groups: group_twiddles, FusedTwiddles)
     // sub-coset evaluation (subcoset_lde): FOLD loads — element g of the transform's input is the sum of 2^fold coefficients times the
     // wave-uniform constants foldk[] — and a COSET transform: the twiddles of stage s carry the constant c^(2^(n-1-s)). Tile-invariant
     // groups read them from a table derived for the sub-coset; the others multiply a round's top twiddle base by cst[round] (the lower
     // stages' constants follow from the squaring chain).
-    int logt;     // log2 of the LDS tile the group's kernel is instantiated for (0: the plan's common size)
     int fold;
     int coset;
     uint32_t foldk[16];
@@ -124,11 +122,11 @@ struct IndexMap {
 // The twiddle base of slot m of a round: w^(g << shift) for the slot's low global index bits g and the round's
 // smallest shift (the one of window bit logr-1). A table lookup with global-memory latency on the critical path
 // of the slot's butterflies, so callers fetch it one slot (or one round) ahead.
-template <bool DIF, int NT = kBlock>
+template <bool DIF>
 __device__ __forceinline__ uint32_t load_twiddle_base(const IndexMap& im, const GroupParams& gp, int round, int m, int tid,
                                                       const uint32_t* __restrict__ tw) {
     const int rb = gp.rb[round], logr = gp.logr[round];
-    const uint32_t sigma = (uint32_t)tid + (uint32_t)NT * m;
+    const uint32_t sigma = (uint32_t)tid + (uint32_t)kBlock * m;
     const uint32_t l0 = ((sigma >> rb) << (rb + logr)) | (sigma & ((1u << rb) - 1u));
     const size_t g = im.glow(l0, rb);
     const int sh_top = DIF ? gp.s0 + gp.k - 1 - (rb + (logr - 1) - gp.c)       // stage number s_q
@@ -206,16 +204,12 @@ __device__ __forceinline__ uint32_t fold_load(const uint32_t* __restrict__ src, 
 // EXPAND: `src` is the H-sized bit-reversed coefficient array (n = log2(2H)); element g of the
 // 2H-sized vector is src[g >> 1] * scale_br[g >> 1].
 // `tw_base` enters as the twiddle base of this round's slot 0 and leaves as the one of the next round's slot 0.
-// MODE: 0 = plain loads, 1 = EXPAND, 2 = FOLD (fold_load above).
-// NC (two-column experiment): a thread runs its slot for NC columns — column cc in tile0 + cc * tile_cs, src0 + cc * src_cs,
-// dst0 + cc * dst_cs — with ONE set of slot indices and twiddles (the table loads and the index arithmetic are shared).
-template <bool DIF, int LOGR, int EPT, int MODE, bool TWT = false, int NC = 1, int NT = kBlock>
-__device__ __forceinline__ void run_round(uint32_t* tile0, const IndexMap& im, const GroupParams& gp, int round,
-                                          const uint32_t* __restrict__ src0, uint32_t* __restrict__ dst0,
+// MODE: 0 = plain loads, 1 = EXPAND, 2 = FOLD (fold_load above). EPT: the elements a thread owns (tile size / kBlock).
+template <bool DIF, int LOGR, int EPT, int MODE, bool TWT = false>
+__device__ __forceinline__ void run_round(uint32_t* tile, const IndexMap& im, const GroupParams& gp, int round,
+                                          const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                           const uint32_t* __restrict__ tw, const uint32_t* __restrict__ scale_br, int tid,
-                                          uint32_t& tw_base, bool io_first = true, bool io_last = true, size_t src_cs = 0, size_t dst_cs = 0,
-                                          uint32_t tile_cs = 0) {
-    static_assert(NC == 1 || MODE == 0, "several columns per thread: plain loads only");
+                                          uint32_t& tw_base, bool io_first = true, bool io_last = true) {
     constexpr bool EXPAND = MODE == 1, FOLD = MODE == 2;
     const int rb = gp.rb[round];
     // io_first / io_last = false: the group's first round reads / its last round writes the LDS tile instead of HBM
@@ -234,7 +228,7 @@ __device__ __forceinline__ void run_round(uint32_t* tile0, const IndexMap& im, c
     };
 #pragma unroll 1
     for (int m = 0; m < SLOTS; ++m) {
-        const uint32_t sigma = (uint32_t)tid + (uint32_t)NT * m;
+        const uint32_t sigma = (uint32_t)tid + (uint32_t)kBlock * m;
         const uint32_t l0 = ((sigma >> rb) << (rb + LOGR)) | (sigma & ((1u << rb) - 1u));
         const uint32_t p0 = lds_phys(l0);
         // fetch the next slot's (or the next round's first) twiddle base while this slot computes
@@ -245,15 +239,10 @@ __device__ __forceinline__ void run_round(uint32_t* tile0, const IndexMap& im, c
 #pragma unroll
             for (int j = 0; j < R - 1; ++j) tt[j] = tab[(uint32_t)j << rb];
         } else {
-            if (m + 1 < SLOTS) tw_base = load_twiddle_base<DIF, NT>(im, gp, round, m + 1, tid, tw);
-            else if (!last_round) tw_base = load_twiddle_base<DIF, NT>(im, gp, round + 1, 0, tid, tw);
+            if (m + 1 < SLOTS) tw_base = load_twiddle_base<DIF>(im, gp, round, m + 1, tid, tw);
+            else if (!last_round) tw_base = load_twiddle_base<DIF>(im, gp, round + 1, 0, tid, tw);
         }
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) {
         uint32_t x[R];
-        uint32_t* tile = tile0 + (size_t)cc * tile_cs;
-        const uint32_t* src = src0 + (size_t)cc * src_cs;
-        uint32_t* dst = dst0 + (size_t)cc * dst_cs;
         // ---- load ----
         if (first) {
             if (FOLD) {
@@ -344,19 +333,16 @@ __device__ __forceinline__ void run_round(uint32_t* tile0, const IndexMap& im, c
 #pragma unroll
             for (int rho = 0; rho < R; ++rho) tile[p0 + lds_off(rho)] = x[rho];
         }
-      }
     }
 }
 
 // TWT: `tw` is the group's twiddle TABLE (tile-invariant groups, see group_twiddles) instead of the transform's root table
-// NT: threads per workgroup (256; 1 024 for the 2^14-element tiles of the two-pass plan: the same 16 elements per lane, 8 waves per SIMD)
-template <bool DIF, int LOGT, int MODE, bool TWT = false, int NT = kBlock>
-__global__ __launch_bounds__(NT) void ntt_group_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                       size_t in_stride, size_t out_stride, GroupParams gp,
-                                                       const uint32_t* __restrict__ tw,
-                                                       const uint32_t* __restrict__ scale_br) {
-    static_assert(NT == kBlock || MODE == 0, "wide workgroups: plain strided groups only");
-    constexpr int EPT = (1 << LOGT) / NT;
+template <bool DIF, int LOGT, int MODE, bool TWT = false>
+__global__ __launch_bounds__(kBlock) void ntt_group_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                           size_t in_stride, size_t out_stride, GroupParams gp,
+                                                           const uint32_t* __restrict__ tw,
+                                                           const uint32_t* __restrict__ scale_br) {
+    constexpr int EPT = (1 << LOGT) / kBlock;
     __shared__ uint32_t tile[(1 << LOGT) + ((1 << LOGT) >> 5)];
     const int tid = threadIdx.x;
     IndexMap im;
@@ -366,7 +352,7 @@ __global__ __launch_bounds__(NT) void ntt_group_kernel(const uint32_t* __restric
     im.n_tiles = (size_t)gp.n_tiles;
     const uint32_t* src = in + (size_t)blockIdx.y * in_stride;
     uint32_t* dst = out + (size_t)blockIdx.y * out_stride;
-    uint32_t tw_base = TWT ? 0u : load_twiddle_base<DIF, NT>(im, gp, 0, 0, tid, tw);
+    uint32_t tw_base = TWT ? 0u : load_twiddle_base<DIF>(im, gp, 0, 0, tid, tw);
     // FOLD (sub-coset evaluation): the folded inputs of the workgroup's tile(s) are staged through LDS first — lane = output, so a wave
     // reads 2^fold * 256 CONTIGUOUS bytes per instruction. (Loaded slot by slot like the other modes, a lane would read the 16 neighbouring
     // outputs of its slot: 64 lanes x 16 instructions walking 64 cache lines side by side, which L1 does not hold for a CU's worth of waves.)
@@ -416,10 +402,10 @@ __global__ __launch_bounds__(NT) void ntt_group_kernel(const uint32_t* __restric
     }
     for (int r = 0; r < gp.n_rounds; ++r) {
         switch (gp.logr[r]) {
-            case 1: run_round<DIF, 1, EPT, MODE, TWT, 1, NT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
-            case 2: run_round<DIF, 2, EPT, MODE, TWT, 1, NT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
-            case 3: run_round<DIF, 3, EPT, MODE, TWT, 1, NT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
-            default: run_round<DIF, 4, EPT, MODE, TWT, 1, NT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
+            case 1: run_round<DIF, 1, EPT, MODE, TWT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
+            case 2: run_round<DIF, 2, EPT, MODE, TWT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
+            case 3: run_round<DIF, 3, EPT, MODE, TWT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
+            default: run_round<DIF, 4, EPT, MODE, TWT>(tile, im, gp, r, src, dst, tw, scale_br, tid, tw_base, !kStageFold, !select); break;
         }
         if (r + 1 < gp.n_rounds) __syncthreads();  // the next round reads what this round wrote
     }
@@ -438,17 +424,16 @@ __global__ __launch_bounds__(NT) void ntt_group_kernel(const uint32_t* __restric
 }
 
 // all rounds of one stage group on the workgroup's tile(s). TWT: `tw` is the group's twiddle TABLE (FusedTwiddles).
-template <bool DIF, int EPT, bool TWT = false, int NC = 1>
+template <bool DIF, int EPT, bool TWT = false>
 __device__ __forceinline__ void run_group(uint32_t* tile, const IndexMap& im, const GroupParams& gp, const uint32_t* __restrict__ src,
-                                          uint32_t* __restrict__ dst, const uint32_t* __restrict__ tw, int tid, bool io_first, bool io_last,
-                                          size_t src_cs = 0, size_t dst_cs = 0, uint32_t tile_cs = 0) {
+                                          uint32_t* __restrict__ dst, const uint32_t* __restrict__ tw, int tid, bool io_first, bool io_last) {
     uint32_t tw_base = TWT ? 0u : load_twiddle_base<DIF>(im, gp, 0, 0, tid, tw);
     for (int r = 0; r < gp.n_rounds; ++r) {
         switch (gp.logr[r]) {
-            case 1: run_round<DIF, 1, EPT, 0, TWT, NC>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last, src_cs, dst_cs, tile_cs); break;
-            case 2: run_round<DIF, 2, EPT, 0, TWT, NC>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last, src_cs, dst_cs, tile_cs); break;
-            case 3: run_round<DIF, 3, EPT, 0, TWT, NC>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last, src_cs, dst_cs, tile_cs); break;
-            default: run_round<DIF, 4, EPT, 0, TWT, NC>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last, src_cs, dst_cs, tile_cs); break;
+            case 1: run_round<DIF, 1, EPT, 0, TWT>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last); break;
+            case 2: run_round<DIF, 2, EPT, 0, TWT>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last); break;
+            case 3: run_round<DIF, 3, EPT, 0, TWT>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last); break;
+            default: run_round<DIF, 4, EPT, 0, TWT>(tile, im, gp, r, src, dst, tw, nullptr, tid, tw_base, io_first, io_last); break;
         }
         if (r + 1 < gp.n_rounds) __syncthreads();
     }
@@ -460,42 +445,38 @@ __device__ __forceinline__ void run_group(uint32_t* tile, const IndexMap& im, co
 // rounds, expands through LDS and runs the DIT rounds on the 2^(ka+1) results: the H-sized coefficient array is neither
 // written nor re-read (8 of the 44 bytes the unfused schedule moves per trace cell). For H <= 2^12 the whole LDE of a
 // column is this one launch.
-template <int NC>
-__device__ __forceinline__ void lde_fused_body(uint32_t* tile, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
-                                               size_t out_stride, const GroupParams& ga, const GroupParams& gd, const uint32_t* __restrict__ tw_inv,
-                                               const uint32_t* __restrict__ tw_fwd, const uint32_t* __restrict__ scale_br) {
+__global__ __launch_bounds__(kBlock) void lde_fused_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
+                                                           size_t out_stride, GroupParams ga, GroupParams gd,
+                                                           const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ tw_fwd,
+                                                           const uint32_t* __restrict__ scale_br) {
     constexpr int LOGA = 12, LOGD = 13;
-    constexpr uint32_t kTileWords = (1u << LOGD) + ((1u << LOGD) >> 5);
+    __shared__ uint32_t tile[(1 << LOGD) + ((1 << LOGD) >> 5)];
     const int tid = threadIdx.x;
-    const uint32_t* src = in + (size_t)blockIdx.y * NC * in_stride;
-    uint32_t* dst = out + (size_t)blockIdx.y * NC * out_stride;
+    const uint32_t* src = in + (size_t)blockIdx.y * in_stride;
+    uint32_t* dst = out + (size_t)blockIdx.y * out_stride;
     IndexMap ia;
     ia.B = ga.B; ia.c = ga.c; ia.lowbits = ga.lowbits; ia.k = ga.k;
     ia.cmask = (1u << ga.c) - 1u;
     ia.tile0 = (size_t)blockIdx.x << (LOGA - ga.B);
     ia.n_tiles = (size_t)ga.n_tiles;
-    run_group<true, (1 << LOGA) / kBlock, true, NC>(tile, ia, ga, src, nullptr, tw_inv, tid, true, false, in_stride, 0, kTileWords);
+    run_group<true, (1 << LOGA) / kBlock, true>(tile, ia, ga, src, nullptr, tw_inv, tid, true, false);
     __syncthreads();
     // scale and duplicate: element l of the coefficient tile becomes elements 2l, 2l + 1 of the forward tile
-    uint32_t v[NC][(1 << LOGA) / kBlock];
+    uint32_t v[(1 << LOGA) / kBlock];
 #pragma unroll
     for (int m = 0; m < (1 << LOGA) / kBlock; ++m) {
         const uint32_t l = (uint32_t)tid + 256u * m;
         bool valid;
         const size_t q = ia.global(l, valid);
         const uint32_t sc = valid ? scale_br[q] : 0u;
-#pragma unroll
-        for (int cc = 0; cc < NC; ++cc) v[cc][m] = bb::mul(tile[cc * kTileWords + lds_phys(l)], sc);
+        v[m] = bb::mul(tile[lds_phys(l)], sc);
     }
     __syncthreads();
 #pragma unroll
     for (int m = 0; m < (1 << LOGA) / kBlock; ++m) {
         const uint32_t l = (uint32_t)tid + 256u * m;
-#pragma unroll
-        for (int cc = 0; cc < NC; ++cc) {
-            tile[cc * kTileWords + lds_phys(2 * l)] = v[cc][m];
-            tile[cc * kTileWords + lds_phys(2 * l + 1)] = v[cc][m];
-        }
+        tile[lds_phys(2 * l)] = v[m];
+        tile[lds_phys(2 * l + 1)] = v[m];
     }
     __syncthreads();
     IndexMap id;
@@ -503,25 +484,7 @@ __device__ __forceinline__ void lde_fused_body(uint32_t* tile, const uint32_t* _
     id.cmask = (1u << gd.c) - 1u;
     id.tile0 = (size_t)blockIdx.x << (LOGD - gd.B);
     id.n_tiles = (size_t)gd.n_tiles;
-    run_group<false, (1 << LOGD) / kBlock, true, NC>(tile, id, gd, nullptr, dst, tw_fwd, tid, false, true, 0, out_stride, kTileWords);
-}
-
-__global__ __launch_bounds__(kBlock) void lde_fused_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
-                                                           size_t out_stride, GroupParams ga, GroupParams gd,
-                                                           const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ tw_fwd,
-                                                           const uint32_t* __restrict__ scale_br) {
-    __shared__ uint32_t tile[(1 << 13) + ((1 << 13) >> 5)];
-    lde_fused_body<1>(tile, in, out, in_stride, out_stride, ga, gd, tw_inv, tw_fwd, scale_br);
-}
-
-// Two columns per workgroup (POWDR_NTT_TWO_COL=1; VERDICT r4 #5, measured in profiles/r05_ntt_two_column.txt): both columns' tiles in
-// LDS (67.6 KB, dynamic: two workgroups per CU instead of four), one set of twiddle-table loads and slot indices for the pair.
-__global__ __launch_bounds__(kBlock) void lde_fused2_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
-                                                            size_t out_stride, GroupParams ga, GroupParams gd,
-                                                            const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ tw_fwd,
-                                                            const uint32_t* __restrict__ scale_br) {
-    extern __shared__ uint32_t tile2[];
-    lde_fused_body<2>(tile2, in, out, in_stride, out_stride, ga, gd, tw_inv, tw_fwd, scale_br);
+    run_group<false, (1 << LOGD) / kBlock, true>(tile, id, gd, nullptr, dst, tw_fwd, tid, false, true);
 }
 
 // The fused kernel specialised for its one geometry from 2^12 rows up (ka = 12: a 4 096-coefficient tile, 8 192 results, three radix-16
@@ -698,11 +661,33 @@ const Tables* tables(int n) {
     return &g_tables.emplace(key, t).first->second;
 }
 
-// Split stages [first, n) into groups of at most `LOGT - c` stages and each group into rounds.
+// Stages [s, s + k) of a size-2^n transform as one group on tiles that carry c passive low bits, cut into rounds
+GroupParams make_group(bool dif, int n, int s, int k, int c) {
+    GroupParams g{};
+    g.n = n; g.s0 = s; g.k = k; g.c = c; g.lowbits = dif ? n - s - k : s; g.B = k + c;
+    g.n_tiles = 1ull << (n - g.B);
+    // rounds: ceil(k/4) windows of nearly equal width
+    int nr = (k + 3) / 4;
+    g.n_rounds = nr;
+    int widths[4];
+    for (int r = 0; r < nr; ++r) widths[r] = k / nr + (r < k % nr ? 1 : 0);
+    if (dif) {  // from the top active bit downwards
+        int top = c + k;
+        for (int r = 0; r < nr; ++r) { top -= widths[r]; g.rb[r] = top; g.logr[r] = widths[r]; }
+    } else {    // from the lowest active bit upwards
+        int bot = c;
+        for (int r = 0; r < nr; ++r) { g.rb[r] = bot; g.logr[r] = widths[r]; bot += widths[r]; }
+    }
+    return g;
+}
+
+// Split stages [first, n) into groups of at most `LOGT - c` stages, every group on tiles of 2^logt_out elements.
 // `end` < n: only the stages [first, end) (the fused LDE kernel takes the rest); `balance`: the groups get nearly equal numbers
 // of stages instead of greedy-full groups followed by a short one.
 std::vector<GroupParams> plan_groups(bool dif, int n, int first, int& logt_out, int end = -1, bool balance = false) {
     std::vector<GroupParams> out;
+    // 2^c neighbouring elements ride along in strided tiles: 64-byte segments (c = 4) up to 2^17 rows, 128-byte ones (c = 5) from
+    // 2^18 rows on, where the strided passes run at 3.5 TB/s with 64-byte segments (profiles/r02_bench_ntt.txt); POWDR_NTT_C forces one
     int kStridedC = (n - (dif ? 0 : 1)) >= 18 ? 5 : 4;  // n = log2 of the transform: the LDE's forward half has one bit more
     if (const char* e = getenv("POWDR_NTT_C")) { int v = atoi(e); if (v >= 0 && v <= 6) kStridedC = v; }
     if (end < 0) end = n;
@@ -724,24 +709,6 @@ std::vector<GroupParams> plan_groups(bool dif, int n, int first, int& logt_out, 
         n_groups = total > 0 ? passes(logt) : 0;
     }
     logt_out = logt;
-    auto make_group = [&](int s, int k, int c, int lt) {
-        GroupParams g{};
-        g.n = n; g.s0 = s; g.k = k; g.c = c; g.lowbits = dif ? n - s - k : s; g.B = k + c; g.logt = lt;
-        g.n_tiles = 1ull << (n - g.B);
-        // rounds: ceil(k/4) windows of nearly equal width
-        int nr = (k + 3) / 4;
-        g.n_rounds = nr;
-        int widths[4];
-        for (int r = 0; r < nr; ++r) widths[r] = k / nr + (r < k % nr ? 1 : 0);
-        if (dif) {  // from the top active bit downwards
-            int top = c + k;
-            for (int r = 0; r < nr; ++r) { top -= widths[r]; g.rb[r] = top; g.logr[r] = widths[r]; }
-        } else {    // from the lowest active bit upwards
-            int bot = c;
-            for (int r = 0; r < nr; ++r) { g.rb[r] = bot; g.logr[r] = widths[r]; bot += widths[r]; }
-        }
-        return g;
-    };
     int s = first;
     int groups_left = n_groups;
     while (s < end) {
@@ -750,20 +717,8 @@ std::vector<GroupParams> plan_groups(bool dif, int n, int first, int& logt_out, 
         --groups_left;
         int c = 0;
         for (; k >= 1; --k) { int lb = dif ? n - s - k : s; c = lb < kStridedC ? lb : kStridedC; if (k + c <= logt) break; }
-        out.push_back(make_group(s, k, c, logt));
+        out.push_back(make_group(dif, n, s, k, c));
         s += k;
-    }
-    // A tall transform whose greedy plan is three passes over HBM (2^22 points: 12 contiguous + 7 + 3 stages forward, 7 + 7 + 8 inverse)
-    // as TWO: the 12 contiguous stages on a 2^12 tile and ALL strided stages (at most 10) as one group on a 2^14-element tile with
-    // 64-byte segments (c = 4) — the strided groups run at the box's copy rate, so a pass less is the only way to make them faster
-    // (round 5; POWDR_NTT_TILE14=0 keeps the three-pass plan).
-    static const int tile14 = [] { const char* e = getenv("POWDR_NTT_TILE14"); return e ? atoi(e) : 0; }();
-    if (tile14 && !balance && out.size() == 3 && end == n && (dif || first == 0) && total - 12 >= 1 && total - 12 <= 10) {
-        const int ks = total - 12;
-        out.clear();
-        if (dif) { out.push_back(make_group(first, ks, 4, 14)); out.push_back(make_group(first + ks, 12, 0, 12)); }
-        else     { out.push_back(make_group(first, 12, 0, 12)); out.push_back(make_group(first + 12, ks, 4, 14)); }
-        logt_out = 12;
     }
     return out;
 }
@@ -795,24 +750,35 @@ void append_group_table(std::vector<uint32_t>& h, const GroupParams& gp, bool di
         }
     }
 }
-struct GroupTwiddles { uint32_t* d = nullptr; unsigned off[4] = {0, 0, 0, 0}; };
-std::map<std::tuple<int, int, int, int>, GroupTwiddles> g_group_tw;  // (device, dif, c, k)
-// nullptr: the group is not tile-invariant (or the table could not be built): the kernel derives its twiddles
-const GroupTwiddles* group_twiddles(const GroupParams& gp, bool dif) {
-    if (gp.lowbits != gp.c || getenv("POWDR_NTT_NO_TABLES")) return nullptr;
+
+// The twiddle caches below: cache[(device, key)], an Entry whose `d` is a device table that lives as long as the process. A missing
+// entry is built on the host (build(words, entry): false = no table), uploaded synchronously — it is published complete: other host
+// threads, on other streams, may use it at once — and kept. nullptr: no table (nothing is kept, and nothing stays allocated).
+template <class Key, class Entry, class Build>
+const Entry* cached_table(std::map<std::pair<int, Key>, Entry>& cache, const Key& key, Build&& build) {
     std::lock_guard<std::mutex> lk(g_mu);
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    const auto key = std::make_tuple(device, dif ? 1 : 0, gp.c, gp.k);
-    auto it = g_group_tw.find(key);
-    if (it != g_group_tw.end()) return &it->second;
-    GroupTwiddles gt;
+    const std::pair<int, Key> dk{device, key};
+    auto it = cache.find(dk);
+    if (it != cache.end()) return &it->second;
+    Entry e;
     std::vector<uint32_t> h;
-    append_group_table(h, gp, dif, gt.off, 0);
-    if (h.empty()) return nullptr;
-    if (hipMalloc(&gt.d, h.size() * 4) != hipSuccess) return nullptr;
-    if (hipMemcpy(gt.d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;  // synchronous: published complete
-    return &g_group_tw.emplace(key, gt).first->second;
+    if (!build(h, e) || h.empty()) return nullptr;
+    if (hipMalloc(&e.d, h.size() * 4) != hipSuccess) return nullptr;
+    if (hipMemcpy(e.d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(e.d); return nullptr; }
+    return &cache.emplace(dk, e).first->second;
+}
+
+struct GroupTwiddles { uint32_t* d = nullptr; unsigned off[4] = {0, 0, 0, 0}; };
+std::map<std::pair<int, std::tuple<int, int, int>>, GroupTwiddles> g_group_tw;  // (device, (dif, c, k))
+// nullptr: the group is not tile-invariant (or the table could not be built): the kernel derives its twiddles
+const GroupTwiddles* group_twiddles(const GroupParams& gp, bool dif) {
+    if (gp.lowbits != gp.c) return nullptr;
+    return cached_table(g_group_tw, std::make_tuple(dif ? 1 : 0, gp.c, gp.k), [&](std::vector<uint32_t>& h, GroupTwiddles& gt) {
+        append_group_table(h, gp, dif, gt.off, 0);
+        return true;
+    });
 }
 
 // A tile-invariant group's twiddle table with a sub-coset's constants folded in: entry (round r, stage q of the round) times cq[r][q]
@@ -841,28 +807,52 @@ struct CosetSpec {
     uint32_t* sel_part = nullptr;
 };
 
+// blockIdx.y is the column and a grid has at most 65 535 of them: launch(c0, cc) for the chunks [c0, c0 + cc) of `cols` columns
+template <class Launch>
+void for_column_chunks(uint32_t cols, Launch&& launch) {
+    for (uint32_t c0 = 0; c0 < cols; c0 += 65535u) launch(c0, cols - c0 < 65535u ? cols - c0 : 65535u);
+}
+
+// ntt_group_kernel<DIF, logt, mode, table != nullptr> (the twiddle argument: `table`, else the transform's roots `tw`). EXPAND and
+// FOLD loads exist in the forward direction only.
 template <bool DIF>
-void run_groups(const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride, uint32_t cols, int n,
-                int first_stage, const uint32_t* tw, const uint32_t* expand_scale_br, const char* name, const CosetSpec* cs = nullptr,
-                int max_groups = -1, int* stages_done = nullptr) {
-    int logt = 12;
-    auto groups = plan_groups(DIF, n, first_stage, logt);
-    // max_groups: only the first groups of the plan (subcoset_lde_first_group: the rest is evaluated for a few outputs only)
-    if (max_groups >= 0 && (size_t)max_groups < groups.size()) groups.resize((size_t)max_groups);
-    if (stages_done) { *stages_done = first_stage; for (auto& g : groups) *stages_done += g.k; }
-    const bool complete = !stages_done || *stages_done == n;
+void launch_group_kernel(int logt, int mode, dim3 grid, const uint32_t* src, uint32_t* dst, size_t src_stride, size_t dst_stride,
+                         const GroupParams& g, const uint32_t* table, const uint32_t* tw, const uint32_t* scale_br) {
+    auto launch = [&](auto lt, auto md) {
+        constexpr int LT = decltype(lt)::value, MD = decltype(md)::value;
+        if (table) hipLaunchKernelGGL((ntt_group_kernel<DIF, LT, MD, true>), grid, dim3(kBlock), 0, stream(), src, dst, src_stride, dst_stride, g, table, scale_br);
+        else hipLaunchKernelGGL((ntt_group_kernel<DIF, LT, MD, false>), grid, dim3(kBlock), 0, stream(), src, dst, src_stride, dst_stride, g, tw, scale_br);
+    };
+    auto with_mode = [&](auto lt) {
+        if constexpr (!DIF) {
+            if (mode == 2) return launch(lt, std::integral_constant<int, 2>{});
+            if (mode == 1) return launch(lt, std::integral_constant<int, 1>{});
+        }
+        launch(lt, std::integral_constant<int, 0>{});
+    };
+    if (logt == 13) with_mode(std::integral_constant<int, 13>{});
+    else with_mode(std::integral_constant<int, 12>{});
+}
+
+// The groups of a plan, one launch per group and column chunk, on tiles of 2^logt elements: the first from `in` with the loads of
+// `mode` (ntt_group_kernel: 1 = EXPAND with `expand_scale_br`, 2 = FOLD with cs), the others in place on `out` with plain loads.
+// Tile-invariant groups read their twiddles from a table. cs: a sub-coset transform (FOLD / SELECT, the coset's constants in every
+// group's twiddles). coset_pw (the LDE behind lde_fused12_kernel): pw[e] = s^(2^e); the twiddles of stage s carry s^(2^(n-1-s)).
+template <bool DIF>
+void launch_groups(std::vector<GroupParams>& groups, int logt, int mode, const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride,
+                   uint32_t cols, const uint32_t* tw, const uint32_t* expand_scale_br, const char* name, const CosetSpec* cs = nullptr,
+                   const uint32_t* coset_pw = nullptr) {
     const uint32_t* src = in;
     size_t src_stride = in_stride;
-    int mode = cs ? 2 : expand_scale_br != nullptr ? 1 : 0;
-    if (!groups.empty() && complete) groups.back().canonical_out = 1;
     for (auto& g : groups) {
-        const int glt = g.logt ? g.logt : logt;
-        const size_t tiles = (size_t)1 << (n - g.B);
-        const size_t per_wg = (size_t)1 << (glt - g.B);
-        const unsigned wgs = (unsigned)((tiles + per_wg - 1) / per_wg);
-        const GroupTwiddles* gt = group_twiddles(g, DIF);  // tile-invariant groups read their twiddles from a table
+        const unsigned wgs = (unsigned)div_up((size_t)g.n_tiles, (size_t)1 << (logt - g.B));
+        const GroupTwiddles* gt = group_twiddles(g, DIF);
         if (gt) for (int r = 0; r < 4; ++r) g.twt_off[r] = gt->off[r];
         const uint32_t* table = gt ? gt->d : nullptr;
+        if (coset_pw) {
+            g.coset = 1;
+            for (int r = 0; r < g.n_rounds; ++r) g.cst[r] = coset_pw[g.n - 1 - (g.s0 + g.rb[r] + g.logr[r] - 1 - g.c)];
+        }
         if (cs) {
             g.coset = 1;
             g.fold = mode == 2 ? cs->fold_log : 0;
@@ -882,25 +872,32 @@ void run_groups(const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_
                 table = cs->d_scratch;
             }
         }
-        for (uint32_t c0 = 0; c0 < cols; c0 += 65535u) {
-            uint32_t cc = cols - c0 < 65535u ? cols - c0 : 65535u;
+        for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
             // (the sub-coset transforms' first group — FOLD loads, the sub-coset's own twiddle table — has a timer of its own)
             ScopedKernelTimer t(mode == 2 ? "ntt_subcoset_first_group_kernel" : name);
-            const uint32_t* s_ = src + (size_t)c0 * src_stride;
-            uint32_t* d_ = out + (size_t)c0 * out_stride;
-            dim3 grid(wgs, cc), block(kBlock);
-#define PW_LAUNCH_NTT(LT, MD) do { if (gt) hipLaunchKernelGGL((ntt_group_kernel<DIF, LT, MD, true>), grid, block, 0, stream(), s_, d_, src_stride, out_stride, g, table, expand_scale_br); \
-                                   else hipLaunchKernelGGL((ntt_group_kernel<DIF, LT, MD, false>), grid, block, 0, stream(), s_, d_, src_stride, out_stride, g, tw, expand_scale_br); } while (0)
-            if (glt == 14) hipLaunchKernelGGL((ntt_group_kernel<DIF, 14, 0, false, 1024>), grid, dim3(1024), 0, stream(), s_, d_, src_stride, out_stride, g, tw, expand_scale_br);  // (a strided group: never the first of a coset / expanding transform)
-            else if (glt == 13) { if (mode == 2) PW_LAUNCH_NTT(13, 2); else if (mode == 1) PW_LAUNCH_NTT(13, 1); else PW_LAUNCH_NTT(13, 0); }
-            else            { if (mode == 2) PW_LAUNCH_NTT(12, 2); else if (mode == 1) PW_LAUNCH_NTT(12, 1); else PW_LAUNCH_NTT(12, 0); }
-#undef PW_LAUNCH_NTT
-        }
+            launch_group_kernel<DIF>(logt, mode, dim3(wgs, cc), src + (size_t)c0 * src_stride, out + (size_t)c0 * out_stride, src_stride, out_stride,
+                                     g, table, tw, expand_scale_br);
+        });
         src = out;
         src_stride = out_stride;
         mode = 0;
         expand_scale_br = nullptr;
     }
+}
+
+// A whole transform (or its stages from `first_stage`): plan and launch
+template <bool DIF>
+void run_groups(const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride, uint32_t cols, int n,
+                int first_stage, const uint32_t* tw, const uint32_t* expand_scale_br, const char* name, const CosetSpec* cs = nullptr,
+                int max_groups = -1, int* stages_done = nullptr) {
+    int logt = 12;
+    auto groups = plan_groups(DIF, n, first_stage, logt);
+    // max_groups: only the first groups of the plan (subcoset_lde_first_group: the rest is evaluated for a few outputs only)
+    if (max_groups >= 0 && (size_t)max_groups < groups.size()) groups.resize((size_t)max_groups);
+    if (stages_done) { *stages_done = first_stage; for (auto& g : groups) *stages_done += g.k; }
+    const bool complete = !stages_done || *stages_done == n;
+    if (!groups.empty() && complete) groups.back().canonical_out = 1;
+    launch_groups<DIF>(groups, logt, cs ? 2 : expand_scale_br != nullptr ? 1 : 0, in, out, in_stride, out_stride, cols, tw, expand_scale_br, name, cs);
     if (groups.empty() && in != out) {
         for (uint32_t c = 0; c < cols; ++c)
             (void)hipMemcpyAsync(out + (size_t)c * out_stride, in + (size_t)c * in_stride, (size_t)4 << n,
@@ -919,49 +916,6 @@ __global__ void expand_small_kernel(const uint32_t* in, uint32_t* out, size_t in
     out[(size_t)blockIdx.y * out_stride + 2 * q + 1] = v;
 }
 
-template <bool DIF>
-void launch_groups(std::vector<GroupParams>& groups, int logt, const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride,
-                   uint32_t cols, int n, const uint32_t* tw, const char* name, const uint32_t* coset_pw = nullptr) {
-    const uint32_t* src = in;
-    size_t src_stride = in_stride;
-    for (auto& g : groups) {
-        // coset_pw (the LDE behind lde_fused12_kernel): pw[e] = s^(2^e); the twiddles of stage s carry s^(2^(n-1-s)) (GroupParams::cst)
-        if (coset_pw) {
-            g.coset = 1;
-            for (int r = 0; r < g.n_rounds; ++r) g.cst[r] = coset_pw[n - 1 - (g.s0 + g.rb[r] + g.logr[r] - 1 - g.c)];
-        }
-        const size_t tiles = (size_t)1 << (n - g.B);
-        const size_t per_wg = (size_t)1 << (logt - g.B);  // (balanced plans: every group on the plan's tile size)
-        const unsigned wgs = (unsigned)((tiles + per_wg - 1) / per_wg);
-        for (uint32_t c0 = 0; c0 < cols; c0 += 65535u) {
-            const uint32_t cc = cols - c0 < 65535u ? cols - c0 : 65535u;
-            ScopedKernelTimer t(name);
-            const uint32_t* s_ = src + (size_t)c0 * src_stride;
-            uint32_t* d_ = out + (size_t)c0 * out_stride;
-            dim3 grid(wgs, cc), block(kBlock);
-            if (logt == 13) hipLaunchKernelGGL((ntt_group_kernel<DIF, 13, 0>), grid, block, 0, stream(), s_, d_, src_stride, out_stride, g, tw, (const uint32_t*)nullptr);
-            else hipLaunchKernelGGL((ntt_group_kernel<DIF, 12, 0>), grid, block, 0, stream(), s_, d_, src_stride, out_stride, g, tw, (const uint32_t*)nullptr);
-        }
-        src = out;
-        src_stride = out_stride;
-    }
-}
-
-GroupParams contiguous_group(bool dif, int n, int s0, int k, int c) {
-    GroupParams g{};
-    g.n = n; g.s0 = s0; g.k = k; g.c = c; g.lowbits = dif ? n - s0 - k : s0; g.B = k + c;
-    g.n_tiles = 1ull << (n - g.B);
-    const int nr = (k + 3) / 4;
-    g.n_rounds = nr;
-    int widths[4];
-    for (int r = 0; r < nr; ++r) widths[r] = k / nr + (r < k % nr ? 1 : 0);
-    if (dif) { int top = c + k; for (int r = 0; r < nr; ++r) { top -= widths[r]; g.rb[r] = top; g.logr[r] = widths[r]; } }
-    else { int bot = c; for (int r = 0; r < nr; ++r) { g.rb[r] = bot; g.logr[r] = widths[r]; bot += widths[r]; } }
-    return g;
-}
-
-}  // namespace
-
 // Twiddle tables of the fused kernel's two contiguous groups. In a contiguous group the twiddle of a butterfly depends on
 // the tile-local index only — the stages are the last ones of the inverse / the first ones of the forward transform, their
 // factors are the roots of order 2^(rb + logr) of a round with window [rb, rb + logr) whatever the transform size — so a
@@ -976,55 +930,44 @@ struct FusedTwiddles {
 std::map<std::pair<int, int>, FusedTwiddles> g_fused_tw;  // (device, ka)
 
 const FusedTwiddles* fused_twiddles(int ka, const GroupParams& ga, const GroupParams& gd) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    auto it = g_fused_tw.find({device, ka});
-    if (it != g_fused_tw.end()) return &it->second;
-    FusedTwiddles ft;
-    std::vector<uint32_t> h;
-    append_group_table(h, ga, true, ft.dif_off, 0);
-    ft.dit_base = h.size();
-    append_group_table(h, gd, false, ft.dit_off, ft.dit_base);
-    if (hipMalloc(&ft.d, h.size() * 4) != hipSuccess) return nullptr;
-    if (hipMemcpy(ft.d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;  // synchronous: published complete
-    return &g_fused_tw.emplace(std::make_pair(device, ka), ft).first->second;
+    return cached_table(g_fused_tw, ka, [&](std::vector<uint32_t>& h, FusedTwiddles& ft) {
+        append_group_table(h, ga, true, ft.dif_off, 0);
+        ft.dit_base = h.size();
+        append_group_table(h, gd, false, ft.dit_off, ft.dit_base);
+        return true;
+    });
 }
 
 // The specialised kernel's table for height 2^n (lde_fused12_kernel): the two groups' tables at fixed offsets, the forward ones
 // with the coset constant of their stage folded in — stage s of the size-2^(n+1) transform carries s^(2^(n-s)), so unlike
 // FusedTwiddles this table depends on the height. pw[e] = s^(2^e), e <= n.
-std::map<std::pair<int, int>, uint32_t*> g_fused12_tw;  // (device, n)
+struct Fused12Twiddles { uint32_t* d = nullptr; };
+std::map<std::pair<int, int>, Fused12Twiddles> g_fused12_tw;  // (device, n)
 
 const uint32_t* fused12_twiddles(int n, const GroupParams& ga, const GroupParams& gd, const uint32_t* pw) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    auto it = g_fused12_tw.find({device, n});
-    if (it != g_fused12_tw.end()) return it->second;
-    std::vector<uint32_t> h;
-    unsigned dif_off[4] = {0, 0, 0, 0}, dit_off[4] = {0, 0, 0, 0};
-    append_group_table(h, ga, true, dif_off, 0);
-    if (h.size() > kF12D0) return nullptr;
-    h.resize(kF12D0, 0u);
-    append_group_table(h, gd, false, dit_off, kF12D0);
-    if (dif_off[0] != kF12A0 || dif_off[1] != kF12A1 || dif_off[2] != kF12A2 || dit_off[0] != 0 || kF12D0 + dit_off[1] != kF12D1 ||
-        kF12D0 + dit_off[2] != kF12D2 || h.size() != kF12Words)
-        return nullptr;  // the kernel's constants and the planner disagree
-    for (int r = 0; r < gd.n_rounds; ++r) {
-        const size_t G = (size_t)1 << gd.rb[r];
-        uint32_t* tab = h.data() + kF12D0 + dit_off[r];
-        for (int q = 0; q < gd.logr[r]; ++q) {
-            const uint32_t cq = pw[n - (gd.s0 + gd.rb[r] - gd.c + q)];
-            for (size_t i = (((size_t)1 << q) - 1) * G; i < (((size_t)2 << q) - 1) * G; ++i) tab[i] = bb::mul(tab[i], cq);
+    const Fused12Twiddles* ft = cached_table(g_fused12_tw, n, [&](std::vector<uint32_t>& h, Fused12Twiddles&) {
+        unsigned dif_off[4] = {0, 0, 0, 0}, dit_off[4] = {0, 0, 0, 0};
+        append_group_table(h, ga, true, dif_off, 0);
+        if (h.size() > kF12D0) return false;
+        h.resize(kF12D0, 0u);
+        append_group_table(h, gd, false, dit_off, kF12D0);
+        if (dif_off[0] != kF12A0 || dif_off[1] != kF12A1 || dif_off[2] != kF12A2 || dit_off[0] != 0 || kF12D0 + dit_off[1] != kF12D1 ||
+            kF12D0 + dit_off[2] != kF12D2 || h.size() != kF12Words)
+            return false;  // the kernel's constants and the planner disagree
+        for (int r = 0; r < gd.n_rounds; ++r) {
+            const size_t G = (size_t)1 << gd.rb[r];
+            uint32_t* tab = h.data() + kF12D0 + dit_off[r];
+            for (int q = 0; q < gd.logr[r]; ++q) {
+                const uint32_t cq = pw[n - (gd.s0 + gd.rb[r] - gd.c + q)];
+                for (size_t i = (((size_t)1 << q) - 1) * G; i < (((size_t)2 << q) - 1) * G; ++i) tab[i] = bb::mul(tab[i], cq);
+            }
         }
-    }
-    uint32_t* d = nullptr;
-    if (hipMalloc(&d, h.size() * 4) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;  // synchronous: published complete
-    g_fused12_tw.emplace(std::make_pair(device, n), d);
-    return d;
+        return true;
+    });
+    return ft ? ft->d : nullptr;
 }
+
+}  // namespace
 
 // The whole LDE of `cols` columns: natural-order evaluations on <g_n> (in) -> natural-order evaluations on the coset
 // s <g_(n+1)> (out), through the fused middle kernel: strided DIF groups (stages 0 .. n-13, into `tmp`, which needs
@@ -1048,12 +991,12 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
     if (n > ka) {
         int logt = 12;
         auto groups = plan_groups(true, n, 0, logt, n - ka, true);
-        launch_groups<true>(groups, logt, in, tmp, in_stride, tmp_stride, cols, n, tn->tw_inv, "ntt_group_kernel<dif>");
+        launch_groups<true>(groups, logt, 0, in, tmp, in_stride, tmp_stride, cols, tn->tw_inv, nullptr, "ntt_group_kernel<dif>");
         src = tmp;
         src_stride = tmp_stride;
     }
-    GroupParams ga = contiguous_group(true, n, n - ka, ka, 0);
-    GroupParams gd = contiguous_group(false, n + 1, 1, ka, 1);
+    GroupParams ga = make_group(true, n, n - ka, ka, 0);
+    GroupParams gd = make_group(false, n + 1, 1, ka, 1);
     gd.canonical_out = ka == n ? 1 : 0;
     // from 2^12 rows up the kernel specialised for the 12 + 12 geometry, which takes the coset scaling in its (and the strided DIT
     // groups') twiddles; POWDR_LDE_FUSED_GENERIC=1 keeps the generic kernel at every height
@@ -1064,58 +1007,29 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
         const uint32_t* tw12 = fused12_twiddles(n, ga, gd, coset_pw);
         if (!tw12) return (int)hipErrorOutOfMemory;
         const unsigned wgs = 1u << (n - 12);
-        for (uint32_t c0 = 0; c0 < cols; c0 += 65535u) {
-            const uint32_t cc = cols - c0 < 65535u ? cols - c0 : 65535u;
+        for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
             ScopedKernelTimer t("lde_fused_kernel");
             const uint32_t* s_ = src + (size_t)c0 * src_stride;
             uint32_t* d_ = out + (size_t)c0 * out_stride;
             if (n == 12) hipLaunchKernelGGL(lde_fused12_kernel<true>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
             else hipLaunchKernelGGL(lde_fused12_kernel<false>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
-        }
+        });
     } else {
         const FusedTwiddles* ft = fused_twiddles(ka, ga, gd);
         if (!ft) return (int)hipErrorOutOfMemory;
         for (int r = 0; r < 4; ++r) { ga.twt_off[r] = ft->dif_off[r]; gd.twt_off[r] = ft->dit_off[r]; }
-        const size_t tiles = (size_t)1 << (n - ka);
-        const size_t per_wg = (size_t)1 << (12 - ka);
-        const unsigned wgs = (unsigned)((tiles + per_wg - 1) / per_wg);
-        uint32_t done = 0;
-        static const bool two_col = [] { const char* e = getenv("POWDR_NTT_TWO_COL"); return e && atoi(e) != 0; }();
-        if (two_col && cols >= 2) {
-            constexpr size_t kLds2 = 2 * ((1u << 13) + ((1u << 13) >> 5)) * sizeof(uint32_t);
-            // the attribute belongs to the current device's code object: set it once per device (worker threads of pw_prove_segments_multi)
-            static std::atomic<uint64_t> attr_ok{0}, attr_tried{0};
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            const uint64_t bit = 1ull << (dev & 63);
-            if (!(attr_tried.load() & bit)) {
-                if (hipFuncSetAttribute((const void*)lde_fused2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds2) == hipSuccess) attr_ok |= bit;
-                else (void)hipGetLastError();
-                attr_tried |= bit;
-            }
-            if (attr_ok.load() & bit) {
-                const uint32_t pairs = cols / 2;
-                for (uint32_t p0 = 0; p0 < pairs; p0 += 65535u) {
-                    const uint32_t pc = pairs - p0 < 65535u ? pairs - p0 : 65535u;
-                    ScopedKernelTimer t("lde_fused_kernel");
-                    hipLaunchKernelGGL(lde_fused2_kernel, dim3(wgs, pc), dim3(kBlock), kLds2, stream(), src + (size_t)(2 * p0) * src_stride,
-                                       out + (size_t)(2 * p0) * out_stride, src_stride, out_stride, ga, gd, ft->d, ft->d + ft->dit_base, tn->shift_br);
-                }
-                done = 2 * pairs;
-            }
-        }
-        for (uint32_t c0 = done; c0 < cols; c0 += 65535u) {
-            const uint32_t cc = cols - c0 < 65535u ? cols - c0 : 65535u;
+        const unsigned wgs = (unsigned)div_up((size_t)ga.n_tiles, (size_t)1 << (12 - ka));
+        for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
             ScopedKernelTimer t("lde_fused_kernel");
             hipLaunchKernelGGL(lde_fused_kernel, dim3(wgs, cc), dim3(kBlock), 0, stream(), src + (size_t)c0 * src_stride,
                                out + (size_t)c0 * out_stride, src_stride, out_stride, ga, gd, ft->d, ft->d + ft->dit_base, tn->shift_br);
-        }
+        });
     }
     if (n > ka) {
         int logt = 12;
         auto groups = plan_groups(false, n + 1, ka + 1, logt, n + 1, true);
         if (!groups.empty()) groups.back().canonical_out = 1;
-        launch_groups<false>(groups, logt, out, out, out_stride, out_stride, cols, n + 1, t1->tw_fwd, "ntt_group_kernel<dit>",
+        launch_groups<false>(groups, logt, 0, out, out, out_stride, out_stride, cols, t1->tw_fwd, nullptr, "ntt_group_kernel<dit>", nullptr,
                              spec12 ? coset_pw : nullptr);
     }
     return (int)hipGetLastError();
@@ -1253,7 +1167,7 @@ int subcoset_query_rows(const uint32_t* coeffs, size_t in_stride, uint32_t cols,
     if (!subcoset_spec(n, b, r, d_work, cs)) return (int)hipErrorInvalidValue;
     int logt = 12;
     auto groups = plan_groups(false, nm, 0, logt);
-    if (groups.size() < 2 || (groups[0].logt ? groups[0].logt : logt) != 12 || groups[0].B != 12 || groups[0].c != 0 || groups[0].lowbits != 0 || cs.fold_log > 1) return 1;
+    if (groups.size() < 2 || logt != 12 || groups[0].B != 12 || groups[0].c != 0 || groups[0].lowbits != 0 || cs.fold_log > 1) return 1;
     const int k1 = groups[0].k, k2 = nm - k1;
     const size_t n_tiles = (size_t)1 << k2;
     uint32_t* d_pos = d_work + (1u << 13);
@@ -1337,7 +1251,5 @@ int subcoset_rows(const uint32_t* part, size_t stride, uint32_t cols, int n, int
                        field::root_of_unity(nm), d_local_idx, d_slot, out);
     return (int)hipGetLastError();
 }
-
-const uint32_t* shift_table(int n) { const Tables* t = tables(n); return t ? t->shift : nullptr; }
 
 }  // namespace pw

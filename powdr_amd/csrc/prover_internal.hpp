@@ -30,7 +30,6 @@ int coset_lde_from_coeffs(const uint32_t* coeffs, uint32_t* out, size_t in_strid
 // intt_dif + coset_lde_from_coeffs in three (instead of four) passes over HBM: the contiguous stage groups of both transforms
 // run in one kernel (ntt.hip lde_fused_kernel). tmp: cols x 2^n words of scratch (unused for n <= 12).
 int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride, size_t tmp_stride, size_t out_stride, uint32_t cols, int n);
-const uint32_t* shift_table(int n);  // s^k / 2^n (Montgomery), k < 2^n, device
 // Sub-coset evaluation (the streamed prover): the rows j = r + 2^b i, i < 2^(n+1-b), of the LDE of `cols` polynomials given by their
 // coefficient arrays as intt_dif leaves them (2^n words each, bit-reversed, H-scaled): out[c * out_stride + i] = P_c(s g_(n+1)^j).
 // d_scratch: 2^13 words (the sub-coset's twiddle table). 1 <= b <= 5.
