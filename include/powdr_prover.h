@@ -360,6 +360,26 @@ void pw_system_traces_last_stats(PwSystemTraceStats* out);
  * first growth steps. The result does not depend on it. -1: out of range. */
 int pw_memory_boundary_set_start_slots(uint32_t log_slots);
 
+/* ---- the Poseidon2 compression chip's trace (the AIR: powdr_amd/system_airs.py poseidon2_air) ----------------------
+ * The contract of pw_memory_boundary_trace: `airs` is the AIR list of pw_check_segment_buses — the SENDERS on `bus`, not the chip —
+ * with the same refusals (-1 before any GPU call; also for an interaction on `bus` that has not 24 arguments left[8], right[8], out[8]),
+ * the call runs on the calling thread's launch stream and synchronises before it returns, scratch is released on every path.
+ * The key is the 16 input words: every active (air, interaction, row) on `bus` adds its centred multiplicity to its key's 64-bit sum
+ * in an open-addressing table (32 bytes per slot; keyed by a 124-bit fingerprint of the inputs as the tally of
+ * pw_check_segment_buses; 2^start_log_slots slots at first, 6 .. 30, 0 = 2^16; grown by 4 while it overflows, full at 7/8, bounded
+ * by table_bytes, 0 = half of what the device budget allows) and offers its packed witness to an atomic minimum. The `out` words of
+ * the senders are NOT read: the chip computes the digest, and a sender with a wrong one gets its row and an unbalanced bus.
+ * d_trace_out (307 x 2^cap_log_height words) receives 307 columns [mult | in[16] | cube, sbox[16] of full rounds 0..7 | pcube, psbox
+ * of partial rounds 0..12 | out[8]], column-major, 2^*log_height rows (*log_height = ceil(log2 *n_rows), at least 1), Montgomery:
+ * one row per distinct key, sorted by the key's smallest witness — every byte is independent of the order of arrival — with the
+ * intermediates of the installed permutation (pw_set_poseidon2_constants) and mult = the sum mod p (a key whose multiplicities
+ * cancel keeps its row with mult 0); padding rows are the row of the all-zero input with mult 0. *status: 0 = written; 1 =
+ * cap_log_height too small (*n_rows and *log_height say what is needed); 2 = the table bound too small. With a status other than 0
+ * nothing is written and 0 is returned. pw_system_traces_last_stats: table_slots, occupied_slots (= rows), tables, walked. */
+int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, size_t table_bytes, uint32_t start_log_slots,
+                                uint32_t* d_trace_out, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
+                                uint32_t* status);
+
 /* Device memory ONE proof call may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
  * POWDR_DEVICE_BUDGET_BYTES read once). It is applied per call, to what that call's provers and (segments) the calling thread's
  * segment context hold: a proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove; segments:

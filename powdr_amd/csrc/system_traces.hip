@@ -9,8 +9,14 @@
 //                                     atomicMax over the sends; pass 2: atomicMin of the packed witness over the triples that carry
 //                                     those extremes; boundary_compact_kernel + a radix sort of the keys; boundary_rows_kernel: one
 //                                     lane per row re-evaluates the data words at the two witnesses and writes the 18 columns
+//   poseidon2   compress_tally_kernel every active triple of the compression bus into an open-addressing table keyed by the fingerprint
+//                                     of its 16 INPUT words (the digest words are not read): 64-bit sum of the centred multiplicities,
+//                                     atomicMin of the packed witness; compress_compact_kernel + a radix sort of (witness, sum);
+//                                     compress_rows_kernel: one lane per row re-evaluates the inputs at the witness and runs a
+//                                     permutation that stores every committed intermediate
 // One lane per row, interactions evaluated by eval_span exactly as the prover and the bus check evaluate them.
 #include "bus_shared.hpp"
+#include "prover_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -312,20 +318,202 @@ __global__ __launch_bounds__(kBlock) void boundary_rows_kernel(const u64* __rest
     for (uint32_t c = 0; c < kBoundaryWidth; ++c) out[(size_t)c * H_out + r] = v[c];
 }
 
+// ---- the Poseidon2 compression chip's trace -----------------------------------------------------------------------------------------
+constexpr uint32_t kCompressArgs = 24, kCompressIn = 16;  // left[8], right[8], out[8]: the key is the 16 input words
+constexpr uint32_t kP2Width = 307;                         // mult | in[16] | 8 x (cube[16], sbox[16]) | 13 x (pcube, psbox) | out[8]
+constexpr uint32_t kP2In = 1, kP2Full = 17, kP2Partial = kP2Full + 8 * 32, kP2Out = kP2Partial + 2 * 13;
+constexpr size_t kP2SlotBytes = 32;                        // key 2 x 8, sum 8, witness 8
+static_assert(kP2Out + 8 == kP2Width, "the layout of powdr_amd/system_airs.py poseidon2_air");
+
+// the definition of the installed permutation (Montgomery words) and the challenges of the key's fingerprint: kernel arguments, so
+// the round constants arrive through scalar loads indexed by the wave-uniform round counter
+struct P2Def { uint32_t ext_rc[8][16]; uint32_t int_rc[13]; uint32_t diag[16]; };
+struct P2Key { bb::Ext al; bb::Ext blpow[kCompressIn + 1]; };
+struct P2Table { u64 *k0, *k1, *sum, *wit; u64 mask; u64* load; u64 class_mask, class_cap; };
+
+// bus_tally_kernel with the key cut down to the inputs: every active (interaction, row) of the compression bus in one AIR adds its
+// centred multiplicity to the slot of the fingerprint al + sum_j bl^(j+1) in_j (j < 16; 124 bits, two 64-bit halves claimed by
+// compare-and-swap) and offers its packed witness. Keys never change once set, sums are integer additions and the witness is a
+// minimum: what a slot ends with does not depend on the order of arrival; the load rule is the bus check's (bus_shared.hpp).
+template <bool FAST>
+__global__ __launch_bounds__(kBlock) void compress_tally_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
+                                                                 uint32_t begin, uint32_t end, uint32_t air, P2Key key, P2Table t,
+                                                                 uint32_t* __restrict__ overflow) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= H || __atomic_load_n(overflow, __ATOMIC_RELAXED)) return;
+    const pwj::DenominatorSeeds sd = pwj::denominator_seeds(key.al);
+    for (uint32_t i = begin; i < end; ++i) {
+        const uint32_t idx = order[i];
+        const LogupInteraction it = lp.d_inter[idx];
+        const uint32_t mu = eval_span<FAST>(lp, it.first_span, m, H, r, stk);
+        if (mu == 0u) continue;
+        pwj::DenominatorAcc acc(sd, 0u);
+        for (uint32_t j = 0; j < kCompressIn; ++j) acc.add(eval_span<FAST>(lp, it.first_span + 1 + j, m, H, r, stk), key.blpow[j + 1]);
+        const bb::Ext d = acc.result();
+        const u64 a = (u64)d.c[0] | ((u64)d.c[1] << 32), b = (u64)d.c[2] | ((u64)d.c[3] << 32);
+        const u64 witness = pack_witness(air, idx, r);
+        const long long cm = (long long)bb::centred(bb::from_monty(mu));
+        const u64 h = slot_hash(a, b);
+        bool done = false;
+        for (u64 n = 0; n <= t.mask; ++n) {
+            const u64 s = (h + n) & t.mask;
+            u64 ka = __atomic_load_n(t.k0 + s, __ATOMIC_RELAXED);
+            if (ka == kEmpty) {
+                ka = atomicCAS(t.k0 + s, kEmpty, a);
+                if (ka == kEmpty) {
+                    ka = a;
+                    if (atomicAdd(t.load + (s & t.class_mask) * kLoadStride, 1ull) >= t.class_cap) atomicOr(overflow, 1u);
+                }
+            }
+            if (ka == a) {
+                u64 kb = __atomic_load_n(t.k1 + s, __ATOMIC_RELAXED);
+                if (kb == kEmpty) {
+                    kb = atomicCAS(t.k1 + s, kEmpty, b);
+                    if (kb == kEmpty) kb = b;
+                }
+                if (kb == b) {
+                    atomicAdd(t.sum + s, (u64)cm);
+                    atomicMin(t.wit + s, witness);
+                    done = true;
+                    break;
+                }
+            }
+            if ((n & 63) == 63 && __atomic_load_n(overflow, __ATOMIC_RELAXED)) break;
+        }
+        if (!done) {
+            atomicOr(overflow, 1u);
+            return;
+        }
+    }
+}
+
+// counts[0] = occupied slots; with `wit`: their (witness, sum) pairs in arrival order (sorted afterwards), counts[2] = written. One
+// atomic per wave: the occupied lanes of a wave are counted by a ballot and take consecutive places behind the leader's.
+__global__ __launch_bounds__(kBlock) void compress_compact_kernel(P2Table t, u64* __restrict__ wit, u64* __restrict__ sum, u64 cap, u64* __restrict__ counts) {
+    const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const bool occupied = s <= t.mask && t.k0[s] != kEmpty;
+    const u64 lanes = __builtin_amdgcn_ballot_w64(occupied);
+    if (!lanes) return;
+    const unsigned lane = threadIdx.x & 63u;
+    const int leader = __builtin_ctzll(lanes);
+    u64 base = 0;
+    if ((int)lane == leader) base = atomicAdd(counts + (wit ? 2 : 0), (u64)__builtin_popcountll(lanes));
+    if (!wit || !occupied) return;
+    base = ((u64)(uint32_t)__shfl((int)(base >> 32), leader, 64) << 32) | (u64)(uint32_t)__shfl((int)base, leader, 64);
+    const u64 at = base + (u64)__builtin_popcountll(lanes & ((1ull << lane) - 1ull));
+    if (at < cap) {
+        wit[at] = t.wit[s];
+        sum[at] = t.sum[s];
+    }
+}
+
+// the external layer on canonical Montgomery words: M4 on each block of four through its shared partial sums (poseidon2.hpp
+// external_layer), then every word gets its column's sum over the four blocks
+__device__ __forceinline__ void p2_external_plain(uint32_t* s) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const uint32_t x0 = s[4 * b], x1 = s[4 * b + 1], x2 = s[4 * b + 2], x3 = s[4 * b + 3];
+        const uint32_t t01 = bb::add(x0, x1), t23 = bb::add(x2, x3), t = bb::add(t01, t23);
+        const uint32_t ta = bb::add(t, x1), tb = bb::add(t, x3);
+        s[4 * b] = bb::add(ta, t01);
+        s[4 * b + 1] = bb::add(ta, bb::double_(x2));
+        s[4 * b + 2] = bb::add(tb, t23);
+        s[4 * b + 3] = bb::add(tb, bb::double_(x0));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t col = bb::add(bb::add(s[i], s[4 + i]), bb::add(s[8 + i], s[12 + i]));
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s[4 * b + i] = bb::add(s[4 * b + i], col);
+    }
+}
+
+// x -> x^7 with x^3 and x^7 stored where the AIR commits them (x = the S-box input, its round constant added)
+__device__ __forceinline__ uint32_t p2_sbox_record(uint32_t x, uint32_t* __restrict__ cube_at, uint32_t* __restrict__ sbox_at) {
+    const uint32_t cube = bb::mul(bb::sqr(x), x), x7 = bb::mul(bb::sqr(cube), x);
+    *cube_at = cube;
+    *sbox_at = x7;
+    return x7;
+}
+
+// Row r of the chip's trace (column-major, H_out rows, Montgomery): the r-th smallest witness's 16 inputs re-evaluated, mult = its
+// sum mod p, and the RECORDING permutation — the definition (P2Def: ext_rc, int_rc, diag) in plain canonical Montgomery arithmetic, so
+// that every stored word is the Montgomery form of the value itself (p2::permute holds scaled representatives, which are not what
+// the constraints read). Rows from n on: the zero input, mult 0. The state lives in 16 registers; every store is one word per lane at
+// column c, row r: a wave writes 256 contiguous bytes. The round loops stay rolled (the column offset follows the round counter), as in
+// p2::permute.
+__global__ __launch_bounds__(kBlock) void compress_rows_kernel(const u64* __restrict__ wit, const u64* __restrict__ sum, u64 n, const AirDev* __restrict__ airs,
+                                                                P2Def C, size_t H_out, uint32_t* __restrict__ out) {
+    __shared__ uint32_t stack_lds[kStackCap * kBlock];
+    uint32_t* stk = stack_lds + threadIdx.x;
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= H_out) return;
+    uint32_t s[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = 0u;
+    uint32_t mult = 0u;
+    if (r < n) {
+        const u64 w = wit[r];
+        for (uint32_t j = 0; j < kCompressIn; ++j) {
+            const uint32_t v = witness_arg(airs, w, j, stk);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[i] = (uint32_t)i == j ? v : s[i];  // (registers: no run-time index into the state)
+        }
+        long long v = (long long)sum[r] % (long long)bb::P;
+        if (v < 0) v += (long long)bb::P;
+        mult = bb::to_monty((uint32_t)v);
+    }
+    uint32_t* __restrict__ o = out + r;
+    o[0] = mult;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[(size_t)(kP2In + i) * H_out] = s[i];
+    p2_external_plain(s);
+#pragma unroll 1
+    for (int rd = 0; rd < 4; ++rd) {
+        uint32_t* __restrict__ c = o + (size_t)(kP2Full + 32 * rd) * H_out;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = p2_sbox_record(bb::add(s[i], C.ext_rc[rd][i]), c + (size_t)i * H_out, c + (size_t)(16 + i) * H_out);
+        p2_external_plain(s);
+    }
+#pragma unroll 1
+    for (int k = 0; k < 13; ++k) {
+        uint32_t* __restrict__ c = o + (size_t)(kP2Partial + 2 * k) * H_out;
+        s[0] = p2_sbox_record(bb::add(s[0], C.int_rc[k]), c, c + H_out);
+        uint32_t total = s[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) total = bb::add(total, s[i]);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = bb::add(total, bb::mul(C.diag[i], s[i]));
+    }
+#pragma unroll 1
+    for (int rd = 4; rd < 8; ++rd) {
+        uint32_t* __restrict__ c = o + (size_t)(kP2Full + 32 * rd) * H_out;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = p2_sbox_record(bb::add(s[i], C.ext_rc[rd][i]), c + (size_t)i * H_out, c + (size_t)(16 + i) * H_out);
+        p2_external_plain(s);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[(size_t)(kP2Out + j) * H_out] = s[j];
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 struct SysCtx {
     DeviceBuf small;                      // counters | class loads | AIR table | one witness's arguments: stays
-    DeviceBuf sums, table, keys, sorted, temp;  // released before a call returns, on every path (SysReleased below)
+    DeviceBuf sums, table, keys, sorted, temp, vals, sorted_vals;  // released before a call returns, on every path (SysReleased below)
     size_t peak = 0;
     uint64_t stat_slots = 0, stat_occupied = 0, stat_tables = 0, stat_triples = 0, stat_additions = 0, stat_lds_atomics = 0, stat_global_atomics = 0;
     uint32_t start_log_slots = 0;  // 0: kStartSlots (pw_memory_boundary_set_start_slots)
-    size_t held() const { return small.bytes + sums.bytes + table.bytes + keys.bytes + sorted.bytes + temp.bytes; }
+    size_t held() const { return small.bytes + sums.bytes + table.bytes + keys.bytes + sorted.bytes + temp.bytes + vals.bytes + sorted_vals.bytes; }
     void note() { peak = std::max(peak, held()); }
 };
 thread_local SysCtx g_sys;
 struct SysReleased {
     SysCtx& cx;
-    ~SysReleased() { cx.sums.release(); cx.table.release(); cx.keys.release(); cx.sorted.release(); cx.temp.release(); }
+    ~SysReleased() {
+        cx.sums.release(); cx.table.release(); cx.keys.release(); cx.sorted.release(); cx.temp.release(); cx.vals.release(); cx.sorted_vals.release();
+    }
 };
 
 // the AIRs that have interactions on `bus`, with their run in the prover's bus order and the values their programs read
@@ -602,6 +790,170 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     {
         ScopedKernelTimer timer("boundary_rows_kernel");
         hipLaunchKernelGGL(boundary_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, n, T, (const AirDev*)d_airs, H_out, d_trace_out);
+    }
+    PW_HIP_TRY(hipGetLastError());
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    return (int)hipGetLastError();
+}
+
+extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, size_t table_bytes, uint32_t start_log_slots,
+                                           uint32_t* d_trace_out, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows, uint32_t* status) {
+    if (!airs_well_formed(airs, n_airs) || !d_trace_out || !log_height || !n_rows || !status || cap_log_height < 1 || cap_log_height > kRowBits ||
+        bus >= bb::P || (start_log_slots && (start_log_slots < 6 || start_log_slots > 30)))
+        return -1;
+    if (!bus_arity_is(airs, n_airs, bus, kCompressArgs)) return -1;
+    SysCtx& cx = g_sys;
+    cx.peak = 0;
+    cx.stat_slots = cx.stat_occupied = cx.stat_tables = cx.stat_triples = 0;
+    *log_height = 0;
+    *n_rows = 0;
+    *status = 0;
+    (void)hipGetLastError();
+    const SysReleased released{cx};
+    std::vector<Part> parts;
+    std::vector<AirDev> air_tab;
+    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
+    u64 triples = 0;
+    for (const Part& part : parts) triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
+    cx.stat_triples = triples;
+    // small: counters (4 u64: occupied | unused | written | unused) | overflow word (+ padding: 16 bytes) | class loads | AIR table
+    const size_t load_bytes = kMaxClasses * kLoadStride * 8;
+    const size_t off_ovf = 32, off_load = off_ovf + 16, off_air = off_load + load_bytes, small_bytes = off_air + n_airs * sizeof(AirDev);
+    PW_TRY(cx.small.ensure(small_bytes));
+    cx.note();
+    char* base = cx.small.as<char>();
+    u64* d_counts = (u64*)base;
+    uint32_t* d_ovf = (uint32_t*)(base + off_ovf);
+    u64* d_load = (u64*)(base + off_load);
+    AirDev* d_airs = (AirDev*)(base + off_air);
+    hipStream_t st = stream();
+    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
+
+    // the definition of the installed permutation, and the fingerprint's challenges: a fixed splitmix64 stream — nothing written
+    // depends on them short of a collision, which costs a key its row and leaves its tuple unbalanced on the bus
+    P2Def def;
+    {
+        const p2::Params& hp = poseidon2_params_host();
+        memcpy(def.ext_rc, hp.ext_rc, sizeof def.ext_rc);
+        memcpy(def.int_rc, hp.int_rc, sizeof def.int_rc);
+        memcpy(def.diag, hp.diag, sizeof def.diag);
+    }
+    P2Key key;
+    {
+        uint64_t sm = 0x70325f636f6d7072ull;
+        auto draw = [&]() {
+            bb::Ext e;
+            for (int k = 0; k < 4; ++k) {
+                uint64_t z = (sm += 0x9E3779B97F4A7C15ull);
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                e.c[k] = bb::to_monty((uint32_t)((z ^ (z >> 31)) % bb::P));
+            }
+            return e;
+        };
+        key.al = draw();
+        const bb::Ext bl = draw();
+        key.blpow[0] = bb::ext_one();
+        for (uint32_t j = 1; j <= kCompressIn; ++j) key.blpow[j] = bb::ext_mul(key.blpow[j - 1], bl);
+    }
+
+    // the largest table: a power of two of slots, at most twice the triples walked, within the caller's bound or by default half of
+    // the device's room (the rule of pw_memory_boundary_trace)
+    u64 max_slots = 1024;
+    while (max_slots < 2 * triples) max_slots <<= 1;
+    size_t bound = table_bytes;
+    if (!bound) {
+        size_t avail = 0;
+        bound = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
+    }
+    while (max_slots && max_slots * kP2SlotBytes > bound) max_slots >>= 1;
+    if (!max_slots) {
+        *status = 2;
+        return 0;
+    }
+    u64 slots = std::min(max_slots, start_log_slots ? (u64)1 << start_log_slots : kStartSlots);
+    u64 counts[5] = {0, 0, 0, 0, 1};  // occupied | unused | written | unused | overflow word
+    P2Table T{};
+    for (;;) {
+        int erc;
+        while ((erc = cx.table.ensure(slots * kP2SlotBytes)) != 0) {
+            (void)hipGetLastError();
+            if (erc != (int)hipErrorOutOfMemory) return erc;
+            if (slots <= 1) break;
+            max_slots = slots >>= 1;
+        }
+        if (!cx.table.p) break;
+        cx.note();
+        u64* tb = cx.table.as<u64>();
+        const u64 classes = std::min<u64>(kMaxClasses, std::max<u64>(1, slots / kMinClassSlots)), per_class = slots / classes;
+        T = P2Table{tb, tb + slots, tb + 2 * slots, tb + 3 * slots, slots - 1, d_load, classes - 1, per_class - per_class / 8};
+        {
+            ScopedKernelTimer timer("compress_table_clear");
+            PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 2 * slots * 8, st));
+            PW_HIP_TRY(hipMemsetAsync(tb + 2 * slots, 0, slots * 8, st));
+            PW_HIP_TRY(hipMemsetAsync(tb + 3 * slots, 0xFF, slots * 8, st));
+            PW_HIP_TRY(hipMemsetAsync(d_counts, 0, off_air, st));  // counters, the overflow word, the class loads
+        }
+        {
+            ScopedKernelTimer timer("compress_tally_kernel");
+            for (const Part& part : parts) {
+                const PwSegmentAir& A = airs[part.air];
+                const PwProver* p = A.prover;
+                const size_t H = (size_t)1 << A.log_height;
+                const LogupProgram lp = program_of(p);
+                const dim3 grid(div_up(H, kBlock));
+                const uint32_t* order = (const uint32_t*)p->bus_order.p;
+                if (lp.d_forms)
+                    hipLaunchKernelGGL(compress_tally_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, key, T, d_ovf);
+                else
+                    hipLaunchKernelGGL(compress_tally_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, key, T, d_ovf);
+            }
+        }
+        hipLaunchKernelGGL(compress_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64*)nullptr, (u64)0, d_counts);
+        PW_HIP_TRY(hipGetLastError());
+        PW_HIP_TRY(hipMemcpyAsync(counts, d_counts, 40, hipMemcpyDeviceToHost, st));
+        PW_HIP_TRY(hipStreamSynchronize(st));
+        ++cx.stat_tables;
+        if (!(uint32_t)counts[4] || slots >= max_slots) break;
+        slots = std::min(max_slots, slots * 4);
+    }
+    if (!cx.table.p || (uint32_t)counts[4]) {
+        *status = 2;
+        return (int)hipGetLastError();
+    }
+    const u64 n = counts[0];
+    cx.stat_slots = slots;
+    cx.stat_occupied = n;
+    *n_rows = n;
+    uint32_t lh = 1;
+    while (((u64)1 << lh) < n) ++lh;
+    *log_height = lh;
+    if (lh > cap_log_height) {
+        *status = 1;
+        return (int)hipGetLastError();
+    }
+    const size_t H_out = (size_t)1 << lh;
+    if (n) {
+        PW_TRY(cx.keys.ensure(n * 8));
+        PW_TRY(cx.vals.ensure(n * 8));
+        PW_TRY(cx.sorted.ensure(n * 8));
+        PW_TRY(cx.sorted_vals.ensure(n * 8));
+        cx.note();
+        hipLaunchKernelGGL(compress_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.keys.as<u64>(), cx.vals.as<u64>(), n, d_counts);
+        PW_HIP_TRY(hipGetLastError());
+        ScopedKernelTimer timer("compress_sort");
+        size_t temp_bytes = 0;
+        PW_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), cx.vals.as<u64>(), cx.sorted_vals.as<u64>(), (size_t)n, 0u,
+                                             64u, st));
+        PW_TRY(cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
+        cx.note();
+        PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), cx.vals.as<u64>(), cx.sorted_vals.as<u64>(), (size_t)n,
+                                             0u, 64u, st));
+    }
+    {
+        ScopedKernelTimer timer("compress_rows_kernel");
+        hipLaunchKernelGGL(compress_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, (const u64*)cx.sorted_vals.p, n,
+                           (const AirDev*)d_airs, def, H_out, d_trace_out);
     }
     PW_HIP_TRY(hipGetLastError());
     PW_HIP_TRY(hipStreamSynchronize(st));

@@ -24,7 +24,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_prover_create_transition", "pw_prover_row_flags", "pw_verify_segment_transition",
                   "pw_prover_create_public", "pw_prover_n_public", "pw_prover_set_public_values", "pw_verify_segment_public",
                   "pw_segment_proof_public_values", "pw_verify_segment_chain", "pw_public_programs_check",
-                  "pw_check_segment_buses", "pw_bus_check_scratch_bytes", "pw_bus_check_peak_bytes", "pw_bus_check_last_stats"]
+                  "pw_check_segment_buses", "pw_bus_check_scratch_bytes", "pw_bus_check_peak_bytes", "pw_bus_check_last_stats",
+                  "pw_poseidon2_compress_trace"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]

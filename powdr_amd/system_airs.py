@@ -7,6 +7,11 @@
   connector   2 rows, preprocessed [is_end] = (0, 1), main [pc, timestamp]: row 0 sends the initial state, row 1 receives the final one
   boundary    one row per touched location, sorted by (as, ptr): sends what the location held before its first access, receives what
               it holds after its last; `init*` / `fin*` are witness columns (from SOME initial memory to SOME final memory)
+
+and the Poseidon2 compression chip (`pw_poseidon2_compress_trace`), the receive side of every hash a later AIR states:
+
+  poseidon2   one permutation per row, 307 columns [mult, in[16], the cube and the seventh power of every S-box input, out[8]]:
+              receives (left[8], right[8], out[8]) `mult` times on BUS_COMPRESS
 """
 from __future__ import annotations
 
@@ -26,6 +31,9 @@ lib.pw_program_frequencies.argtypes = [C.POINTER(prover.PwSegmentAir), C.c_size_
 lib.pw_memory_boundary_trace.restype = C.c_int
 lib.pw_memory_boundary_trace.argtypes = [C.POINTER(prover.PwSegmentAir), C.c_size_t, C.c_uint32, C.c_size_t, C.c_void_p, C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+lib.pw_poseidon2_compress_trace.restype = C.c_int
+lib.pw_poseidon2_compress_trace.argtypes = [C.POINTER(prover.PwSegmentAir), C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 lib.pw_system_traces_scratch_bytes.restype = C.c_size_t
 lib.pw_system_traces_scratch_bytes.argtypes = []
 lib.pw_system_traces_peak_bytes.restype = C.c_size_t
@@ -43,7 +51,8 @@ lib.pw_memory_boundary_set_start_slots.argtypes = [C.c_uint32]
 
 P = 0x78000001
 BUS_EXEC, BUS_MEMORY, BUS_PC, BUS_VAR_RANGE, BUS_BITWISE = 0, 1, 2, 3, 6
-OP_SUB, OP_MUL = 3, 4
+BUS_COMPRESS = 5  # (left[8], right[8], out[8]): out = the first 8 words of Poseidon2(left | right); received by poseidon2_air
+OP_ADD, OP_SUB, OP_MUL = 2, 3, 4
 LIMB_BITS = (17, 12)  # a pointer or a gap below 2^29 = a 17-bit and a 12-bit limb, both within the variable range checker's 17 bits
 PROGRAM_COLUMNS = ["pc", "opcode", "a", "b", "c", "d", "e", "f", "g"]
 BOUNDARY_COLUMNS = (["is_valid", "as", "ptr", "p_lo", "p_hi"] + [f"init{i}" for i in range(4)] + ["init_ts"] + [f"fin{i}" for i in range(4)]
@@ -193,6 +202,86 @@ def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANG
                      list(BOUNDARY_COLUMNS), transition=True)
 
 
+# ---- the Poseidon2 compression chip ---------------------------------------------------------------------------------
+# [mult | in[16] | per full round r = 0..7: cube[r][16], sbox[r][16] | per partial round k = 0..12: pcube[k], psbox[k] | out[8]]
+P2_FULL_ROUNDS, P2_PARTIAL_ROUNDS, P2_HALF = 8, 13, 4
+P2_IN, P2_FULL, P2_PARTIAL, P2_OUT = 1, 17, 17 + 32 * P2_FULL_ROUNDS, 17 + 32 * P2_FULL_ROUNDS + 2 * P2_PARTIAL_ROUNDS
+POSEIDON2_WIDTH = P2_OUT + 8  # 307
+POSEIDON2_COLUMNS = (["mult"] + [f"in{i}" for i in range(16)]
+                     + [f"{n}{r}_{i}" for r in range(P2_FULL_ROUNDS) for n in ("cube", "sbox") for i in range(16)]
+                     + [f"{n}{k}" for k in range(P2_PARTIAL_ROUNDS) for n in ("pcube", "psbox")] + [f"out{j}" for j in range(8)])
+_M4 = np.array([[2, 3, 1, 1], [1, 2, 3, 1], [1, 1, 2, 3], [3, 1, 1, 2]], np.int64)
+# the external layer as one 16 x 16 matrix: M4 on every block of four words, then every word gets its column's sum over the blocks
+P2_EXTERNAL = np.kron(np.eye(4, dtype=np.int64), _M4) + np.kron(np.ones((4, 4), np.int64), _M4)
+
+
+def p2_cube(r: int, i: int) -> int:
+    return P2_FULL + 32 * r + i
+
+
+def p2_sbox(r: int, i: int) -> int:
+    return P2_FULL + 32 * r + 16 + i
+
+
+def _form_code(form, const: int = 0) -> list:
+    """one left-leaning sum c0 col0 + c1 col1 + ... + const of a coefficient vector over the columns (never deeper than 3 slots)"""
+    code = []
+    for c in np.nonzero(form)[0].tolist():
+        code += [OP_PUSH_APC, c] + ([OP_PUSH_CONST, int(form[c]), OP_MUL] if int(form[c]) != 1 else []) + ([OP_ADD] if code else [])
+    if const or not code:
+        code += [OP_PUSH_CONST, int(const)] + ([OP_ADD] if code else [])
+    return code
+
+
+def poseidon2_air(bus: int = BUS_COMPRESS) -> SystemAir:
+    """The Poseidon2 compression chip: one permutation per row, 307 main columns POSEIDON2_COLUMNS, no preprocessed columns, no row
+    flags, no public values; the tuple (in[0..16], out[0..8]) is received `mult` times on `bus`. The permutation is the library's
+    (pw_poseidon2_permute_host): width 16, x^7, an external layer, 4 full, 13 partial, 4 full rounds. Committed per S-box: cube = x^3
+    and sbox = cube^2 x, x the linear form that enters it with its round constant — 282 constraints of degree 3 — and out[j] = word j
+    of the last external layer (8 of degree 1). The linear layers are applied here, symbolically: a state word is a coefficient
+    vector over the committed columns (16 terms in the full rounds, 16 + k in partial round k, 29 entering round 4). A padding row
+    is the honest row of the zero input with mult = 0 (no is_valid column).
+    THE ROUND CONSTANTS ARE READ FROM prover.poseidon2_constants() NOW and are part of the constraint programs: an AIR made under one
+    table is a different AIR under another (its constraints do not hold on rows made under the other) — make it again after
+    prover.set_poseidon2_constants."""
+    ext_rc, int_rc, diag = (np.asarray(a).astype(np.int64) for a in prover.poseidon2_constants())
+    state = np.zeros((16, POSEIDON2_WIDTH), np.int64)  # state[i] = word i as a linear form over the columns
+    state[np.arange(16), P2_IN + np.arange(16)] = 1
+    bc, spans = [], []
+
+    def constrain(code):
+        spans.append((len(bc), len(code)))
+        bc.extend(code)
+
+    def sbox(x, cube, out):
+        constrain([OP_PUSH_APC, cube] + x + x + [OP_MUL] + x + [OP_MUL, OP_SUB])                       # cube - x^3
+        constrain([OP_PUSH_APC, out, OP_PUSH_APC, cube, OP_PUSH_APC, cube, OP_MUL] + x + [OP_MUL, OP_SUB])  # sbox - cube^2 x
+
+    def full_round(r):
+        nonlocal state
+        for i in range(16):
+            sbox(_form_code(state[i], ext_rc[r, i]), p2_cube(r, i), p2_sbox(r, i))
+        state = np.zeros((16, POSEIDON2_WIDTH), np.int64)
+        state[np.arange(16), [p2_sbox(r, i) for i in range(16)]] = 1
+        state = P2_EXTERNAL @ state % P
+
+    state = P2_EXTERNAL @ state % P
+    for r in range(P2_HALF):
+        full_round(r)
+    for k in range(P2_PARTIAL_ROUNDS):
+        sbox(_form_code(state[0], int_rc[k]), P2_PARTIAL + 2 * k, P2_PARTIAL + 2 * k + 1)
+        state[0] = 0
+        state[0, P2_PARTIAL + 2 * k + 1] = 1
+        state = (state.sum(axis=0) % P + diag[:, None] * state) % P  # 1 1^T + diag
+    for r in range(P2_HALF, P2_FULL_ROUNDS):
+        full_round(r)
+    for j in range(8):
+        constrain([OP_PUSH_APC, P2_OUT + j] + _form_code(state[j]) + [OP_SUB])
+    inter = _tables(bus, [(_neg_col(0), [_col(P2_IN + i) for i in range(16)] + [_col(P2_OUT + j) for j in range(8)])])
+    return SystemAir("poseidon2", POSEIDON2_WIDTH, (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2)), inter,
+                     list(POSEIDON2_COLUMNS))
+
+
 # ---- traces -------------------------------------------------------------------------------------------------------------------------
 def _records(airs):
     n = len(airs)
@@ -238,6 +327,29 @@ def memory_boundary_trace(airs, cap_log_height: int, table_bytes: int = 0, bus: 
     return trace, int(lh.value), int(locations.value), int(status.value)
 
 
+def poseidon2_compress_trace(airs, cap_log_height: int, table_bytes: int = 0, start_log_slots: int = 0, bus: int = BUS_COMPRESS,
+                             out: torch.Tensor | None = None):
+    """pw_poseidon2_compress_trace: airs = the SENDERS on `bus` as for check_segment_buses -> (trace: 307 x 2^log_height Montgomery
+    words, column-major — None unless status is 0; log_height; rows = distinct keys; status: 0 written, 1 cap_log_height too small, 2
+    table bound too small). Status 1 is retried once at the height the library asked for, in a buffer of that height — unless the
+    caller gave `out`, whose size is the caller's business: then status 1 is returned with the height to come back with.
+    The senders' digests are not read: check_segment_buses([..., chip], buses=[bus]) says whether they were right."""
+    recs, n = _records(airs)
+    own = out is None
+    for _ in range(2):
+        if own:
+            out = torch.empty(POSEIDON2_WIDTH << cap_log_height, dtype=torch.int32, device="cuda")
+        assert out.numel() >= POSEIDON2_WIDTH << cap_log_height
+        lh, rows, status = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        abi.check(lib.pw_poseidon2_compress_trace(recs, n, bus, int(table_bytes), int(start_log_slots), out.data_ptr(), cap_log_height, C.byref(lh),
+                                                  C.byref(rows), C.byref(status)), "pw_poseidon2_compress_trace")
+        if status.value != 1 or not own:
+            break
+        cap_log_height = int(lh.value)
+    trace = out[:POSEIDON2_WIDTH << lh.value] if status.value == 0 else None
+    return trace, int(lh.value), int(rows.value), int(status.value)
+
+
 def connector_trace(airs, bus: int = BUS_EXEC, with_states: bool = False):
     """The connector's 2 x 2 main trace [pc0, pc1, ts0, ts1] (Montgomery) from what check_segment_buses leaves over on the execution
     bridge: exactly the initial state (received once and never sent) and the final one (sent once and never received).
@@ -269,12 +381,12 @@ def set_boundary_start_slots(log_slots: int) -> None:
 
 
 def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int = 100, pow_bits: int = 0, pc_step: int = 4, table_bytes: int = 0,
-                  cap_log_height: int = 16, public_connector: bool = False):
+                  cap_log_height: int = 16, public_connector: bool = False, poseidon2: bool = False):
     """airs: [dict(prover, trace (device tensor), log_h, ...)] — every AIR that sends on the execution bridge, the memory bus and the
     PC lookup, traces made. Appends the program, connector and boundary AIRs as dicts of the same shape (name, role "system", air =
     the SystemAir, width, log_h, cons, inter, trace, prover, pre) and returns the list. periphery (tracegen.Periphery): its histograms
     receive the boundary AIR's range and byte lookups (_apc_apply_bus on its trace) — call this BEFORE the periphery traces are made
-    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). public_connector: the connector with its four public values (connector_air(public=True)), set from the two states connector_trace finds; its dict also has public = those values. Raises on foreign instructions, on a boundary status other than 0 and on an execution bridge that is not a chain."""
+    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). public_connector: the connector with its four public values (connector_air(public=True)), set from the two states connector_trace finds; its dict also has public = those values. poseidon2: when any AIR sends on BUS_COMPRESS, the Poseidon2 compression chip (poseidon2_air, made under the constants installed now) is appended after the three, its trace by poseidon2_compress_trace; False (the default): the bus is left alone. Raises on foreign instructions, on a boundary or chip status other than 0 and on an execution bridge that is not a chain."""
     from .segment_workload import BusReplay
 
     seg = [(a["prover"], a["trace"].data_ptr(), a["log_h"]) for a in airs]
@@ -291,8 +403,14 @@ def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int
         raise ValueError(f"{n_foreign} executed instructions are not in the program, the first: {first}")
     con = connector_air(public=public_connector)
     con_trace, start, end = connector_trace(seg, with_states=True)
+    system = [(prog, freq, prog.log_h), (con, con_trace, 1), (bnd, trace, lh)]
+    if poseidon2 and any(BUS_COMPRESS in np.asarray(a["inter"][0]).reshape(-1, 3)[:, 0] for a in airs if a.get("inter") is not None):
+        p2_trace, p2_lh, p2_rows, p2_status = poseidon2_compress_trace(seg, min(cap_log_height, 10), table_bytes)
+        if p2_status:
+            raise ValueError(f"poseidon2 chip: {STATUS[p2_status]} ({p2_rows} rows)")
+        system.append((poseidon2_air(), p2_trace, p2_lh))
     out = list(airs)
-    for air, t, h in ((prog, freq, prog.log_h), (con, con_trace, 1), (bnd, trace, lh)):
+    for air, t, h in system:
         p = air.make_prover(num_queries, pow_bits)
         out.append(dict(name=air.name, role="system", air=air, width=air.width, log_h=h, cons=air.cons, inter=air.inter, trace=t, prover=p,
                         pre=(air.fixed_table(), air.pre_width, air.log_h) if air.pre_width else None))

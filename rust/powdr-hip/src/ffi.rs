@@ -411,6 +411,10 @@ extern "C" {
     pub fn pw_system_traces_last_stats(out: *mut PwSystemTraceStats);
     /// 2^log_slots slots in the first address table of this thread's later `pw_memory_boundary_trace` calls (0 = default)
     pub fn pw_memory_boundary_set_start_slots(log_slots: u32) -> c_int;
+    /// the Poseidon2 compression chip's trace from the senders on `bus` (status 1: retry with `cap_log_height = *log_height`)
+    pub fn pw_poseidon2_compress_trace(airs: *const PwSegmentAir, n_airs: usize, bus: u32, table_bytes: usize, start_log_slots: u32,
+                                       d_trace_out: *mut u32, cap_log_height: u32, log_height: *mut u32, n_rows: *mut u64,
+                                       status: *mut u32) -> c_int;
     pub fn pw_verify(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32, bytecode_len: usize,
                      cons_spans: *const u32, n_constraints: usize, proof_words: *const u32, n_words: usize) -> c_int;
     pub fn pw_verify_logup(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32,
