@@ -380,6 +380,61 @@ int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_
                                 uint32_t* d_trace_out, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
                                 uint32_t* status);
 
+/* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
+ * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
+ * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —
+ * Z_0 = the digest of the zero payload, Z_(l+1) = compress(Z_l, Z_l): a subtree nobody has written hashes to Z_l and is not stored,
+ * an empty tree's root is Z_H. Per level the device holds the sorted indices and digests of the stored nodes (level 0: the payloads
+ * too), Montgomery words below p. The memory of §5j is H = 30 with the key (as - 1) * 2^29 + ptr.
+ *
+ * pw_memory_tree_create: NULL unless 1 <= height <= 40. Z_0 .. Z_H are computed on the host and device memory is allocated by the
+ * first call that needs it: creating a tree and asking an empty tree for its root need no GPU. The tree keeps a copy of the round
+ * constants installed when it is made (pw_get_poseidon2_constants); EVERY call below compares them with the installed table and
+ * returns -1 when they differ — a tree is as tied to its table as the Poseidon2 chip's AIR is.
+ * pw_memory_tree_root: out[8] = the root, canonical words on the host (no GPU call).
+ * pw_memory_tree_stats: stored leaves; stored nodes over all levels (the leaves included); device bytes held; and of the last
+ * pw_memory_tree_update that ended with status 0: permutations hashed, launches (the library's own kernels; a rocPRIM select or scan
+ * counts as one), the most scratch bytes held at once (all three zero after an update of n = 0 keys).
+ *
+ * pw_memory_tree_update: d_keys = n strictly increasing leaf indices below 2^H; d_init, d_fin = 8 words per key, row-major,
+ * Montgomery. In this order: (1) validation — *status 4: the keys are not strictly increasing or one is >= 2^H; 5: a payload word
+ * >= p; *info = the index of the first offending key; (2) continuity — for every key the stored payload (the zero payload for a leaf
+ * that is not stored) must equal its d_init words: *status 3, *info = the smallest mismatching KEY; (3) the record count — the touched
+ * node sets are T_0 = the keys, T_l = unique(T_(l-1) >> 1); *n_rows = 2 (n + sum_(l=1..H) |T_l|), *log_height = the smallest height
+ * >= 1 that holds them; with d_records != NULL and cap_log_height < *log_height: *status 1 and nothing is written; (4) the phase-0
+ * records from the tree as it stands, the new tree (the payloads become d_fin), the phase-1 records from the new tree.
+ * d_records (may be NULL: no records) = 25 columns [valid, left[8], right[8], out[8]], column-major with pitch 2^*log_height,
+ * Montgomery: valid = 1 on the *n_rows rows, all 25 words zero on the padding rows. Row order: phase (0 = before, 1 = after); inside
+ * a phase level 0 in key order, then the nodes of T_1, .., T_H, each by index. A level-0 row is (payload, 0^8, leaf digest), a
+ * level-l row (left child digest, right child digest, node digest) with the defaults Z_(l-1), Z_l where a node is not stored; the
+ * last row of each phase has the root as `out`. d_node_ids (optional, needs d_records): one uint64 per row, phase << 63 | level <<
+ * 56 | index. Every byte is independent of the order of arrival: the keys are sorted and unique and every output place is a rank.
+ * LOAD MODE: d_init == NULL skips continuity and records and just writes the payloads (an initial image); d_records and d_node_ids
+ * must then be NULL, log_height and n_rows may be.
+ * With any non-zero *status or return value the tree is exactly what it was (the new tree is built into fresh buffers and swapped in
+ * at the end). Malformed arguments (a NULL where a pointer is required, a tree whose buffers live on another device, changed round
+ * constants): -1 before any GPU call. The call runs on the calling thread's launch stream, synchronises before it returns and frees
+ * its scratch on every path (the contract of pw_memory_boundary_trace). A leaf written with the zero payload stays stored: its digest
+ * is Z_0, the root is the one of a tree without it.
+ *
+ * pw_memory_tree_boundary_leaves: the leaves of a memory boundary trace (pw_memory_boundary_trace: 18 columns, 2^log_height rows, the
+ * first n_locations valid, sorted by (as, ptr), hence by key): d_keys[r] = (as - 1) * 2^29 + ptr, d_init / d_fin[8 r ..] = (init0..3,
+ * 0, 0, 0, 0) / (fin0..3, 0, 0, 0, 0). -1: a NULL pointer, log_height outside 1 .. 40, more locations than rows. */
+typedef struct PwMemoryTree PwMemoryTree;
+typedef struct PwMemoryTreeStats {
+    uint64_t leaves, stored_nodes, device_bytes;
+    uint64_t last_permutations, last_launches, last_scratch_bytes;
+} PwMemoryTreeStats;
+PwMemoryTree* pw_memory_tree_create(uint32_t height);
+void pw_memory_tree_destroy(PwMemoryTree* tree);
+int pw_memory_tree_root(const PwMemoryTree* tree, uint32_t* out);
+int pw_memory_tree_stats(const PwMemoryTree* tree, PwMemoryTreeStats* out);
+int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys, const uint32_t* d_init, const uint32_t* d_fin, size_t n,
+                          uint32_t* d_records, uint64_t* d_node_ids, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
+                          uint32_t* status, uint64_t* info);
+int pw_memory_tree_boundary_leaves(const uint32_t* d_boundary_trace, uint32_t log_height, uint64_t n_locations, uint64_t* d_keys,
+                                   uint32_t* d_init, uint32_t* d_fin);
+
 /* Device memory ONE proof call may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
  * POWDR_DEVICE_BUDGET_BYTES read once). It is applied per call, to what that call's provers and (segments) the calling thread's
  * segment context hold: a proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove; segments:

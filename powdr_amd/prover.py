@@ -25,7 +25,9 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_prover_create_public", "pw_prover_n_public", "pw_prover_set_public_values", "pw_verify_segment_public",
                   "pw_segment_proof_public_values", "pw_verify_segment_chain", "pw_public_programs_check",
                   "pw_check_segment_buses", "pw_bus_check_scratch_bytes", "pw_bus_check_peak_bytes", "pw_bus_check_last_stats",
-                  "pw_poseidon2_compress_trace"]
+                  "pw_poseidon2_compress_trace",
+                  "pw_memory_tree_create", "pw_memory_tree_destroy", "pw_memory_tree_root", "pw_memory_tree_stats", "pw_memory_tree_update",
+                  "pw_memory_tree_boundary_leaves"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]

@@ -297,6 +297,21 @@ pub struct PwSystemTraceStats {
     pub lds_atomics: u64,
     pub global_atomics: u64,
 }
+/// the opaque handle of `pw_memory_tree_create`
+#[repr(C)]
+pub struct PwMemoryTree {
+    _private: [u8; 0],
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwMemoryTreeStats {
+    pub leaves: u64,
+    pub stored_nodes: u64,
+    pub device_bytes: u64,
+    pub last_permutations: u64,
+    pub last_launches: u64,
+    pub last_scratch_bytes: u64,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct PwAirDescription {
@@ -415,6 +430,20 @@ extern "C" {
     pub fn pw_poseidon2_compress_trace(airs: *const PwSegmentAir, n_airs: usize, bus: u32, table_bytes: usize, start_log_slots: u32,
                                        d_trace_out: *mut u32, cap_log_height: u32, log_height: *mut u32, n_rows: *mut u64,
                                        status: *mut u32) -> c_int;
+    /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
+    pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
+    pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
+    /// the root as 8 canonical words on the host
+    pub fn pw_memory_tree_root(tree: *const PwMemoryTree, out: *mut u32) -> c_int;
+    pub fn pw_memory_tree_stats(tree: *const PwMemoryTree, out: *mut PwMemoryTreeStats) -> c_int;
+    /// `status` 0 = the tree holds `d_fin`; 1 = `cap_log_height` too small; 3 = `d_init` is not what the tree holds (`info` = the key);
+    /// 4 / 5 = malformed keys / payloads (`info` = the index). `d_init` NULL: load mode, no records.
+    pub fn pw_memory_tree_update(tree: *mut PwMemoryTree, d_keys: *const u64, d_init: *const u32, d_fin: *const u32, n: usize,
+                                 d_records: *mut u32, d_node_ids: *mut u64, cap_log_height: u32, log_height: *mut u32, n_rows: *mut u64,
+                                 status: *mut u32, info: *mut u64) -> c_int;
+    /// keys and payloads of the rows of a memory boundary trace
+    pub fn pw_memory_tree_boundary_leaves(d_boundary_trace: *const u32, log_height: u32, n_locations: u64, d_keys: *mut u64,
+                                          d_init: *mut u32, d_fin: *mut u32) -> c_int;
     pub fn pw_verify(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32, bytecode_len: usize,
                      cons_spans: *const u32, n_constraints: usize, proof_words: *const u32, n_words: usize) -> c_int;
     pub fn pw_verify_logup(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32,
