@@ -417,6 +417,21 @@ int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_
  * its scratch on every path (the contract of pw_memory_boundary_trace). A leaf written with the zero payload stays stored: its digest
  * is Z_0, the root is the one of a tree without it.
  *
+ * pw_memory_tree_set_mode / pw_memory_tree_get_mode: how pw_memory_tree_update makes the levels above level 0. Nothing else depends on
+ * the mode: statuses and *info, *n_rows, *log_height, records, node ids, the root and every stored byte are the same in both, a
+ * non-zero status or return value leaves the tree as it was, and no byte depends on an order of arrival. The mode may be changed
+ * between any two updates of one tree; neither call touches the GPU, both work on a tree without device buffers. -1: a NULL pointer,
+ * an unknown mode, changed round constants.
+ *   PW_MEMORY_TREE_REBUILD (0, the default): level 0 is merged by ranks and only the update's leaves are hashed; every level above is
+ *   hashed again from the level below. last_permutations = n + sum_(l>=1) s_l (s_l = the stored nodes of level l afterwards).
+ *   PW_MEMORY_TREE_INCREMENTAL (1): with L = the number of levels l >= 1 whose level l - 1 holds more than 1024 nodes afterwards (the
+ *   levels the rebuild gives a launch of their own), the levels 1 .. L are rank merges too: the nodes of T_l are hashed, once each,
+ *   from their children in the new level l - 1, and every other stored node moves to its new rank with its index and digest, unhashed.
+ *   The levels above L are finished by the one workgroup that finishes them in the rebuild. last_permutations = n + sum_(l=1..L) |T_l|
+ *   + sum_(l>L) s_l; last_launches also counts the one read-back each of those L levels needs (the size of the new level), and
+ *   last_scratch_bytes the touched sets, which stay until the levels are merged. The new tree is built next to the old one as in the
+ *   rebuild (not in place). LOAD MODE is the full rebuild in both modes.
+ *
  * pw_memory_tree_boundary_leaves: the leaves of a memory boundary trace (pw_memory_boundary_trace: 18 columns, 2^log_height rows, the
  * first n_locations valid, sorted by (as, ptr), hence by key): d_keys[r] = (as - 1) * 2^29 + ptr, d_init / d_fin[8 r ..] = (init0..3,
  * 0, 0, 0, 0) / (fin0..3, 0, 0, 0, 0). -1: a NULL pointer, log_height outside 1 .. 40, more locations than rows. */
@@ -432,6 +447,10 @@ int pw_memory_tree_stats(const PwMemoryTree* tree, PwMemoryTreeStats* out);
 int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys, const uint32_t* d_init, const uint32_t* d_fin, size_t n,
                           uint32_t* d_records, uint64_t* d_node_ids, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
                           uint32_t* status, uint64_t* info);
+#define PW_MEMORY_TREE_REBUILD 0u
+#define PW_MEMORY_TREE_INCREMENTAL 1u
+int pw_memory_tree_set_mode(PwMemoryTree* tree, uint32_t mode);
+int pw_memory_tree_get_mode(const PwMemoryTree* tree, uint32_t* mode);
 int pw_memory_tree_boundary_leaves(const uint32_t* d_boundary_trace, uint32_t log_height, uint64_t n_locations, uint64_t* d_keys,
                                    uint32_t* d_init, uint32_t* d_fin);
 

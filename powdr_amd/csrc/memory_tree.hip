@@ -9,6 +9,9 @@
 //               (tail_kernel: the top of the tree is a chain of one or two nodes per level over most of its height).
 //   records     the touched node sets T_0 = keys, T_l = unique(T_(l-1) >> 1) by the same flag + select (tail_kernel<false> for the
 //               chain), records_kernel looks every touched node and its children up in the old tree (phase 0) and the new (phase 1).
+//   incremental (pw_memory_tree_set_mode, opt-in) the levels above the threshold are rank merges too, the way level 0 is: found + a scan
+//               rank T_l in the old level l, touched_parent_kernel hashes every node of T_l from its children in the new level l - 1,
+//               move_kernel streams every other stored node to its new rank, unhashed; the tail and load mode are the rebuild's.
 // The new tree is built into fresh buffers next to the old one and swapped in at the very end: any status or error leaves the tree
 // as it was. The permutation is p2::permute with the parameters as a kernel argument (scalar loads, as the __constant__ copy of
 // merkle.hip gives them).
@@ -56,6 +59,7 @@ struct PwMemoryTree {
         uint32_t root[8];
     } data;
     uint64_t last_permutations = 0, last_launches = 0, last_scratch = 0;
+    uint32_t mode = PW_MEMORY_TREE_REBUILD;
 };
 
 namespace pw {
@@ -191,6 +195,60 @@ __global__ __launch_bounds__(kBlock) void level_kernel(const u64* __restrict__ c
     store8(pdig + p * 8, st);
 }
 
+// Incremental mode, level l >= 1: the new level is the rank merge of the old level with the touched set T_l (sorted, unique), as level 0
+// is of the stored keys with the update's. Touched node j lands behind the old nodes below it and the touched nodes below it, the ones
+// that are both counted once (before[j] = how many of the touched nodes below j are stored in the old level), and is hashed from its
+// one or two children in the NEW level below: one lower_bound for 2t, the sibling adjacent, `z` for a missing side. A touched node has a
+// touched child, and every touched node of the level below is stored in the new tree: at least one side is found.
+__global__ __launch_bounds__(kBlock) void touched_parent_kernel(const u64* __restrict__ t, u64 m, const u64* __restrict__ before, LevelView old, LevelView ch,
+                                                                 const Digest z, const p2::Params P, u64* __restrict__ pidx, uint32_t* __restrict__ pdig) {
+    const u64 j = (u64)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const u64 node = t[j];
+    const u64 at = j + lower_bound(old.idx, old.n, node) - before[j];
+    u64 c = lower_bound(ch.idx, ch.n, 2 * node);
+    uint32_t st[16];
+    if (c < ch.n && ch.idx[c] == 2 * node) {
+        load8(ch.dig + c * 8, st);
+        ++c;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) st[k] = z.w[k];
+    }
+    if (c < ch.n && ch.idx[c] == 2 * node + 1) {
+        load8(ch.dig + c * 8, st + 8);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) st[8 + k] = z.w[k];
+    }
+    p2::permute(st, P);
+    pidx[at] = node;
+    store8(pdig + at * 8, st);
+}
+
+// The old nodes of that level that are not in T_l move to their new rank with index and digest, unhashed: 40 bytes per node. Two lanes
+// per node, each one 16-byte half of the digest, so a wave reads and writes runs of contiguous 16-byte words (the ranks of neighbours
+// differ only where a new node lands between them); the first lane of a pair moves the 8-byte index. The rank needs the node's place
+// in T_l: the workgroup's first and last nodes bound it (the same two searches in every lane), and between two touched nodes that
+// leaves nothing to search.
+constexpr int kMoveNodes = kBlock / 2;
+__global__ __launch_bounds__(kBlock) void move_kernel(LevelView old, const u64* __restrict__ t, u64 m, const u64* __restrict__ before, u64* __restrict__ idx,
+                                                       uint32_t* __restrict__ dig) {
+    const u64 first = (u64)blockIdx.x * kMoveNodes;
+    const u64 i = first + (threadIdx.x >> 1);
+    if (i >= old.n) return;
+    const u64 last = first + kMoveNodes <= old.n ? first + kMoveNodes - 1 : old.n - 1;
+    const u64 lo = lower_bound(t, m, old.idx[first]);
+    const u64 hi = lower_bound(t + lo, m - lo, old.idx[last]);  // the touched nodes below the last node, counted from lo
+    const u64 node = old.idx[i];
+    const u64 c = lo + lower_bound(t + lo, hi, node);
+    if (c < m && t[c] == node) return;  // hashed again by touched_parent_kernel
+    const u64 at = i + c - before[c];
+    const unsigned half = threadIdx.x & 1u;
+    reinterpret_cast<uint4*>(dig)[at * 2 + half] = reinterpret_cast<const uint4*>(old.dig)[i * 2 + half];
+    if (!half) idx[at] = node;
+}
+
 // The levels first .. last from the level below `first` (n0 <= kTail nodes), in one workgroup of kTail threads: thread i owns child
 // i, the heads are ranked by ballots and a prefix over the waves' totals, level l goes to slot l - first of idx_out / dig_out (kTail
 // nodes each) and its size to counts[l - first]. A level written by the workgroup is made visible to its other waves by
@@ -323,9 +381,16 @@ __global__ __launch_bounds__(kBlock) void boundary_leaves_kernel(const uint32_t*
 struct TreeCtx {
     DeviceBuf small;                                   // errors | a count | the tail's level sizes: stays (a few hundred bytes)
     DeviceBuf found, before, flags, head, ping, pong, temp, tail_t;  // released before a call returns, on every path
+    // incremental mode: the touched sets above the tail's stay until the levels are merged (tset[l] = T_l, wherever it lives)
+    std::vector<std::unique_ptr<DeviceBuf>> kept;
+    std::vector<const u64*> tset;
     size_t peak = 0;
     uint64_t launches = 0;
-    size_t held() const { return found.bytes + before.bytes + flags.bytes + head.bytes + ping.bytes + pong.bytes + temp.bytes + tail_t.bytes; }
+    size_t held() const {
+        size_t b = found.bytes + before.bytes + flags.bytes + head.bytes + ping.bytes + pong.bytes + temp.bytes + tail_t.bytes;
+        for (const auto& k : kept) b += k->bytes;
+        return b;
+    }
     void note() { peak = std::max(peak, held()); }
 };
 thread_local TreeCtx g_tree;
@@ -334,6 +399,8 @@ struct TreeReleased {
     ~TreeReleased() {
         cx.found.release(); cx.before.release(); cx.flags.release(); cx.head.release(); cx.ping.release(); cx.pong.release(); cx.temp.release();
         cx.tail_t.release();
+        cx.kept.clear();
+        cx.tset.clear();
     }
 };
 constexpr size_t kErr = 0, kCount = 4, kTailCounts = 8;  // u64 places in TreeCtx::small
@@ -365,8 +432,10 @@ int select_heads(TreeCtx& cx, const u64* idx, u64 n, u64* count) {
 }
 
 // The touched node sets T_0 = keys, T_l = unique(T_(l-1) >> 1). rec == nullptr: their sizes into sizes[0 .. H]. Otherwise the sizes are
-// given and every level's record rows are written as soon as its set exists (rec->lv[l].row set by the caller).
-int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64 n, std::vector<u64>& sizes, RecArgs* rec) {
+// given and every level's record rows are written as soon as its set exists (rec->lv[l].row set by the caller). keep (with the sizes
+// pass): every set stays, in a buffer of its own or in the tail's slots, and cx.tset[l] says where; a records pass that finds them
+// there only writes the rows.
+int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64 n, std::vector<u64>& sizes, RecArgs* rec, bool keep = false) {
     hipStream_t st = stream();
     const int H = (int)tree->height;
     const p2::Params& P = poseidon2_params_host();
@@ -383,15 +452,36 @@ int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64
     }
     const u64* cur = d_keys;
     int l = 1;
+    if (rec && !cx.tset.empty()) {  // the sets of the sizes pass are still there
+        for (; l <= H && sizes[l - 1] > kTail; ++l) {
+            rec->lv[l].t = cx.tset[l]; rec->lv[l].n = sizes[l];
+            emit(l, 1, sizes[l]);
+        }
+        if (l <= H) {
+            u64 widest = 0;
+            for (int k = l; k <= H; ++k) {
+                rec->lv[k].t = cx.tset[k]; rec->lv[k].n = sizes[k];
+                widest = std::max(widest, sizes[k]);
+            }
+            emit(l, H - l + 1, widest);
+        }
+        return (int)hipGetLastError();
+    }
+    if (keep) {
+        cx.tset.assign(H + 1, nullptr);
+        cx.tset[0] = d_keys;
+    }
     for (; l <= H && sizes[l - 1] > kTail; ++l) {
         const u64 m = sizes[l - 1];
-        DeviceBuf& out = (l & 1) ? cx.ping : cx.pong;
         PW_TRY(select_heads(cx, cur, m, rec ? nullptr : &sizes[l]));
-        PW_HIP_TRY((hipError_t)out.ensure(m * 8));
+        if (keep) cx.kept.emplace_back(new DeviceBuf);
+        DeviceBuf& out = keep ? *cx.kept.back() : (l & 1) ? cx.ping : cx.pong;
+        PW_HIP_TRY((hipError_t)out.ensure(keep ? sizes[l] * 8 : m * 8));
         cx.note();
         hipLaunchKernelGGL(gather_parent_kernel, dim3(div_up(sizes[l], kBlock)), dim3(kBlock), 0, st, cur, cx.head.as<u64>(), sizes[l], out.as<u64>());
         ++cx.launches;
         cur = out.as<u64>();
+        if (keep) cx.tset[l] = cur;
         if (rec) {
             rec->lv[l].t = cur; rec->lv[l].n = sizes[l];
             emit(l, 1, sizes[l]);
@@ -408,6 +498,8 @@ int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64
         if (!rec) {
             PW_HIP_TRY(hipMemcpyAsync(&sizes[l], d_counts, (size_t)levels * 8, hipMemcpyDeviceToHost, st));
             PW_HIP_TRY(hipStreamSynchronize(st));
+            if (keep)
+                for (int k = l; k <= H; ++k) cx.tset[k] = cx.tail_t.as<u64>() + (size_t)(k - l) * kTail;
         } else {
             u64 widest = 0;
             for (int k = l; k <= H; ++k) {
@@ -420,13 +512,61 @@ int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64
     return (int)hipGetLastError();
 }
 
-// The tree over the merged level 0 (already in `d`): every level above it, the root read back
-int build_levels(TreeCtx& cx, PwMemoryTree* tree, PwMemoryTree::Data& d, uint64_t* permutations) {
+// One level of the incremental mode: the rank merge of the old level l with T_l (cx.tset[l], m nodes) into a fresh buffer. found +
+// scan as for level 0, then ONE read-back — how many of T_l the old level stores, which gives the new level's size — counted among the
+// launches: it is the dependent step of the level.
+int merge_level(TreeCtx& cx, PwMemoryTree* tree, const PwMemoryTree::Data& old, PwMemoryTree::Data& d, int l, u64 m) {
+    hipStream_t st = stream();
+    const p2::Params& P = poseidon2_params_host();
+    const LevelView o = old.lv[l], c = d.lv[l - 1];
+    const u64* t = cx.tset[l];
+    hipLaunchKernelGGL(lookup_kernel, dim3(div_up(m + 1, kBlock)), dim3(kBlock), 0, st, t, (const uint32_t*)nullptr, m, o, (const uint32_t*)nullptr, cx.found.as<u64>(),
+                       cx.small.as<u64>() + kErr);
+    size_t temp_bytes = 0;
+    PW_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, m + 1, rocprim::plus<u64>(), st));
+    PW_HIP_TRY((hipError_t)cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
+    cx.note();
+    PW_HIP_TRY(rocprim::exclusive_scan(cx.temp.p, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, m + 1, rocprim::plus<u64>(), st));
+    u64 n_found = 0;
+    PW_HIP_TRY(hipMemcpyAsync(&n_found, cx.before.as<u64>() + m, 8, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    cx.launches += 3;
+    if (n_found > m || n_found > o.n) return -1;
+    const u64 parents = o.n + m - n_found;
+    d.bufs.emplace_back(new DeviceBuf);
+    DeviceBuf& b = *d.bufs.back();
+    PW_HIP_TRY((hipError_t)b.ensure((size_t)parents * 40));
+    uint32_t* dig = b.as<uint32_t>();
+    u64* idx = reinterpret_cast<u64*>(dig + (size_t)parents * 8);
+    Digest z;
+    memcpy(z.w, tree->zero[l - 1], sizeof z.w);
+    {
+        ScopedKernelTimer tm("memory_tree_touched_kernel");
+        hipLaunchKernelGGL(touched_parent_kernel, dim3(div_up(m, kBlock)), dim3(kBlock), 0, st, t, m, cx.before.as<u64>(), o, c, z, P, idx, dig);
+    }
+    ++cx.launches;
+    if (o.n) {
+        ScopedKernelTimer tm("memory_tree_move_kernel");
+        hipLaunchKernelGGL(move_kernel, dim3(div_up(o.n, kMoveNodes)), dim3(kBlock), 0, st, o, t, m, cx.before.as<u64>(), idx, dig);
+        ++cx.launches;
+    }
+    d.lv[l] = LevelView{idx, dig, parents};
+    return 0;
+}
+
+// The tree over the merged level 0 (already in `d`): every level above it, the root read back. sizes != nullptr (incremental mode; the
+// touched sets in cx.tset): the levels above the threshold are merged from `old`, only |T_l| nodes of each hashed.
+int build_levels(TreeCtx& cx, PwMemoryTree* tree, const PwMemoryTree::Data& old, PwMemoryTree::Data& d, const std::vector<u64>* sizes, uint64_t* permutations) {
     hipStream_t st = stream();
     const int H = (int)tree->height;
     const p2::Params& P = poseidon2_params_host();
     int l = 1;
     for (; l <= H && d.lv[l - 1].n > kTail; ++l) {
+        if (sizes) {
+            PW_TRY(merge_level(cx, tree, old, d, l, (*sizes)[l]));
+            *permutations += (*sizes)[l];
+            continue;
+        }
         const LevelView c = d.lv[l - 1];
         u64 parents = 0;
         PW_TRY(select_heads(cx, c.idx, c.n, &parents));
@@ -514,6 +654,18 @@ extern "C" int pw_memory_tree_stats(const PwMemoryTree* tree, PwMemoryTreeStats*
     return 0;
 }
 
+extern "C" int pw_memory_tree_set_mode(PwMemoryTree* tree, uint32_t mode) {
+    if (!tree || (mode != PW_MEMORY_TREE_REBUILD && mode != PW_MEMORY_TREE_INCREMENTAL) || !same_table(tree)) return -1;
+    tree->mode = mode;
+    return 0;
+}
+
+extern "C" int pw_memory_tree_get_mode(const PwMemoryTree* tree, uint32_t* mode) {
+    if (!tree || !mode || !same_table(tree)) return -1;
+    *mode = tree->mode;
+    return 0;
+}
+
 extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_, const uint32_t* d_init, const uint32_t* d_fin, size_t n,
                                      uint32_t* d_records, uint64_t* d_node_ids_, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
                                      uint32_t* status, uint64_t* info) {
@@ -583,8 +735,9 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
     // 3. the records: index work only
     std::vector<u64> sizes;
     u64 phase_rows = 0;
+    const bool incremental = d_init && tree->mode == PW_MEMORY_TREE_INCREMENTAL;  // load mode is the full rebuild in both modes
     if (d_init) {
-        PW_TRY(touched_levels(cx, tree, d_keys, n, sizes, nullptr));
+        PW_TRY(touched_levels(cx, tree, d_keys, n, sizes, nullptr, incremental));
         for (u64 s : sizes) phase_rows += s;
         *n_rows = 2 * phase_rows;
         *log_height = ceil_log2_at_least_1(2 * phase_rows);
@@ -615,7 +768,7 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
         fresh.lv[0] = LevelView{idx, dig, n0};
         fresh.payload = payload;
     }
-    PW_TRY(build_levels(cx, tree, fresh, &permutations));
+    PW_TRY(build_levels(cx, tree, old, fresh, incremental ? &sizes : nullptr, &permutations));
     // phase-0 rows from the tree as it stands, phase-1 rows from the new one
     if (d_init && d_records) {
         const u64 pitch = (u64)1 << *log_height;

@@ -3,6 +3,8 @@
 from the memory the last one left, and the opened paths as (left, right, out) rows the Poseidon2 chip receives on BUS_COMPRESS.
 
   MemoryTree(height=30)   load(keys, payloads) an initial image; update(keys, init, fin) one segment's touched leaves; root(); stats()
+                          incremental=True (or the `incremental` property, between any two updates): an update hashes only the touched
+                          paths and moves every other stored node, instead of hashing every level again — the same bytes either way
   boundary_leaves         keys and payloads of the rows of a memory boundary trace (key = (as - 1) * 2^29 + ptr)
   records_air             the sender of the records: 25 columns [valid, left[8], right[8], out[8]]
 
@@ -41,6 +43,12 @@ lib.pw_memory_tree_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_vo
 lib.pw_memory_tree_boundary_leaves.restype = C.c_int
 lib.pw_memory_tree_boundary_leaves.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 
+lib.pw_memory_tree_set_mode.restype = C.c_int
+lib.pw_memory_tree_set_mode.argtypes = [C.c_void_p, C.c_uint32]
+lib.pw_memory_tree_get_mode.restype = C.c_int
+lib.pw_memory_tree_get_mode.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+
+MODE_REBUILD, MODE_INCREMENTAL = 0, 1  # PW_MEMORY_TREE_REBUILD, PW_MEMORY_TREE_INCREMENTAL
 TAIL_NODES = 1024  # csrc/memory_tree.hip kMemoryTreeTailNodes: a level of at most this many nodes is finished by one workgroup
 RECORD_WIDTH = 25
 RECORD_COLUMNS = ["valid"] + [f"left{i}" for i in range(8)] + [f"right{i}" for i in range(8)] + [f"out{i}" for i in range(8)]
@@ -70,13 +78,26 @@ def _payloads(words, n: int) -> torch.Tensor:
 class MemoryTree:
     """pw_memory_tree_create .. pw_memory_tree_destroy. Keys: increasing leaf indices below 2^height (numpy / list, or a device int64
     tensor); payloads: [n, 8] canonical words (numpy / list), or a device int32 tensor of Montgomery words. The tree belongs to the
-    Poseidon2 table installed when it is made: under another table every call raises."""
+    Poseidon2 table installed when it is made: under another table every call raises. incremental: pw_memory_tree_set_mode — updates
+    hash only the touched paths (load() is the full rebuild either way); may be changed between any two updates."""
 
-    def __init__(self, height: int = 30):
+    def __init__(self, height: int = 30, incremental: bool = False):
         self._h = lib.pw_memory_tree_create(int(height))
         if not self._h:
             raise ValueError("the height of a memory tree is 1 .. 40")
         self.height = int(height)
+        if incremental:
+            self.incremental = True
+
+    @property
+    def incremental(self) -> bool:
+        mode = C.c_uint32()
+        abi.check(lib.pw_memory_tree_get_mode(self._h, C.byref(mode)), "pw_memory_tree_get_mode")
+        return mode.value == MODE_INCREMENTAL
+
+    @incremental.setter
+    def incremental(self, on: bool) -> None:
+        abi.check(lib.pw_memory_tree_set_mode(self._h, MODE_INCREMENTAL if on else MODE_REBUILD), "pw_memory_tree_set_mode")
 
     def close(self) -> None:
         if getattr(self, "_h", None) and lib is not None:

@@ -297,6 +297,10 @@ pub struct PwSystemTraceStats {
     pub lds_atomics: u64,
     pub global_atomics: u64,
 }
+/// `pw_memory_tree_set_mode`: every level above level 0 hashed again from the level below
+pub const PW_MEMORY_TREE_REBUILD: u32 = 0;
+/// `pw_memory_tree_set_mode`: only the touched paths hashed, every other stored node moved
+pub const PW_MEMORY_TREE_INCREMENTAL: u32 = 1;
 /// the opaque handle of `pw_memory_tree_create`
 #[repr(C)]
 pub struct PwMemoryTree {
@@ -441,6 +445,10 @@ extern "C" {
     pub fn pw_memory_tree_update(tree: *mut PwMemoryTree, d_keys: *const u64, d_init: *const u32, d_fin: *const u32, n: usize,
                                  d_records: *mut u32, d_node_ids: *mut u64, cap_log_height: u32, log_height: *mut u32, n_rows: *mut u64,
                                  status: *mut u32, info: *mut u64) -> c_int;
+    /// `PW_MEMORY_TREE_REBUILD` (the default) or `PW_MEMORY_TREE_INCREMENTAL`: how an update makes the levels above level 0; the
+    /// results are the same bytes. No GPU call; -1 for an unknown mode or changed round constants.
+    pub fn pw_memory_tree_set_mode(tree: *mut PwMemoryTree, mode: u32) -> c_int;
+    pub fn pw_memory_tree_get_mode(tree: *const PwMemoryTree, mode: *mut u32) -> c_int;
     /// keys and payloads of the rows of a memory boundary trace
     pub fn pw_memory_tree_boundary_leaves(d_boundary_trace: *const u32, log_height: u32, n_locations: u64, d_keys: *mut u64,
                                           d_init: *mut u32, d_fin: *mut u32) -> c_int;

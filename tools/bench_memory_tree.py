@@ -1,16 +1,22 @@
-"""The sparse memory Merkle tree (pw_memory_tree_*, powdr_amd/memory_tree.py). A new capability has no parent figure, so
-it is reported against two yardsticks of the same build. One process per section, the measurements alternating after a warm-up, host
-clock around calls that synchronise themselves; per-kernel times from the library's HIP events. Each section merges its object into
---out, so that a job can run every section under a time limit of its own:
+"""The sparse memory Merkle tree (pw_memory_tree_*, powdr_amd/memory_tree.py). One process per section, the measurements
+alternating after a warm-up, host clock around calls that synchronise themselves; per-kernel times from the library's HIP events. Each
+section merges its object into --out, so that a job can run every section under a time limit of its own. `sizes` and `segment` measure
+every mode of --modes (rebuild: every level hashed again; incremental: only the touched paths, pw_memory_tree_set_mode) on trees of their
+own, alternating; --parent names the file the PARENT commit's copy of this tool wrote in the same job (its only mode is the rebuild):
+its figures are put next to each cell, with parent's fastest step over this build's slowest.
   kernel    (a) permutations per second of memory_tree_level_kernel while 2^log_leaves dense leaves are loaded, against compress_kernel
             committing a matrix of as many rows (pw_merkle_commit), alternating
   sizes     trees of 2^20 and 2^24 stored leaves, dense keys and keys scattered over the whole 2^30 space (the worst case for stored
             nodes: bytes held), updates of 2^12, 2^16 and 2^20 stored leaves with and without records: ms, permutations hashed against
-            the permutations on the touched paths (what an incremental rebuild would hash), launches, peak scratch
+            the permutations on the touched paths, launches, host read-backs, peak scratch, per-kernel ms of one more update with
+            the library's events on; at the smallest update also move_kernel's bytes per second (read + written) against a
+            device-to-device copy of as many bytes
   segment   (b) the memory-log segment of tools/bench_system_airs.py: boundary trace -> boundary_leaves -> update, as a fraction of
             that segment's prove_segment
 
-  python tools/bench_memory_tree.py --section kernel|sizes|segment [--steps 3] [--warmup 1] [--out profiles/memory_tree.json]"""
+  python tools/bench_memory_tree.py --section kernel|sizes|segment [--steps 3] [--warmup 1] [--modes rebuild incremental]
+         [--parent parent.json] [--out profiles/memory_tree_incremental.json]
+profiles/memory_tree.json is the record of the commit that added the tree (rebuild only) and is not written any more."""
 from __future__ import annotations
 
 import argparse
@@ -36,7 +42,9 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--queries", type=int, default=100)
-    ap.add_argument("--out", default=str(Path(__file__).resolve().parents[1] / "profiles" / "memory_tree.json"))
+    ap.add_argument("--modes", nargs="*", default=["rebuild", "incremental"], choices=["rebuild", "incremental"])
+    ap.add_argument("--parent", default=None)
+    ap.add_argument("--out", default=str(Path(__file__).resolve().parents[1] / "profiles" / "memory_tree_incremental.json"))
     args = ap.parse_args()
 
     import numpy as np
@@ -79,7 +87,24 @@ def main():
             out.append(len(t))
         return out
 
-    result = dict(device=torch.cuda.get_device_name(0), steps=args.steps, warmup=args.warmup, tail_nodes=mt.TAIL_NODES)
+    def stored_level_sizes(keys):
+        """s_l of the tree over these sorted device keys, l = 0 .. H"""
+        out, t = [keys.numel()], keys
+        for _ in range(H):
+            t = torch.unique_consecutive(t >> 1)
+            out.append(t.numel())
+        return out
+
+    def over_parent(cell, parent_cell):
+        """the parent's figures next to this build's, and parent's fastest step over this build's slowest (and the medians')"""
+        for k in ("with_records", "without_records"):
+            cell["parent"][k] = parent_cell[k]
+            for mode in args.modes:
+                cell[mode][k + "_parent_min_over_max"] = round(parent_cell[k]["ms_min"] / cell[mode][k]["ms_max"], 3)
+                cell[mode][k + "_parent_median_over_median"] = round(parent_cell[k]["ms_median"] / cell[mode][k]["ms_median"], 3)
+
+    parent = json.loads(Path(args.parent).read_text()) if args.parent else None
+    result = dict(device=torch.cuda.get_device_name(0), steps=args.steps, warmup=args.warmup, tail_nodes=mt.TAIL_NODES, modes=args.modes)
     section = {}
 
     if args.section == "kernel":
@@ -130,13 +155,18 @@ def main():
                     host_keys = np.sort(rng.choice(host_keys, n, replace=False))
                 keys = torch.from_numpy(host_keys.view(np.int64)).cuda()
                 pay = words(n, 3)
-                tree = mt.MemoryTree(H)
-                ms_load, st = timed(lambda: tree.load(keys, pay))
-                assert st == (0, 0)
-                s0 = tree.stats()
-                entry = dict(load_ms=round(ms_load, 3), leaves=s0["leaves"], stored_nodes=s0["stored_nodes"], device_bytes=s0["device_bytes"],
+                trees, ms_load = {}, {}
+                for mode in args.modes:
+                    trees[mode] = mt.MemoryTree(H, incremental=mode == "incremental")
+                    ms_load[mode], st = timed(lambda: trees[mode].load(keys, pay))
+                    assert st == (0, 0)
+                s0 = trees[args.modes[0]].stats()
+                stored = stored_level_sizes(keys)
+                merged = sum(1 for l in range(1, H + 1) if stored[l - 1] > mt.TAIL_NODES)  # L: the levels with launches of their own
+                assert s0["stored_nodes"] == sum(stored)
+                entry = dict(load_ms={m: round(v, 3) for m, v in ms_load.items()}, leaves=s0["leaves"], stored_nodes=s0["stored_nodes"], device_bytes=s0["device_bytes"],
                              bytes_per_leaf=round(s0["device_bytes"] / n, 1), load_permutations=s0["last_permutations"], load_launches=s0["last_launches"],
-                             load_permutations_per_second=round(s0["last_permutations"] / (ms_load * 1e-3)), updates={})
+                             levels_above_the_tail_threshold=merged, updates={})
                 note(log_stored, layout, entry)
                 for log_touched in args.touched:
                     m = 1 << log_touched
@@ -144,29 +174,71 @@ def main():
                         continue
                     at = np.sort(rng.choice(n, m, replace=False))
                     tk = keys[torch.from_numpy(at).cuda()].contiguous()
-                    a, b = pay[torch.from_numpy(at).cuda()].contiguous(), words(m, 4 + log_touched)
-                    touched_perms = sum(level_sizes(host_keys[at]))
+                    words_a, words_b = pay[torch.from_numpy(at).cuda()].contiguous(), words(m, 4 + log_touched)
+                    touched = level_sizes(host_keys[at])
+                    touched_perms = sum(touched)
+                    touched_above = sum(1 for l in range(1, H + 1) if touched[l - 1] > mt.TAIL_NODES)
                     cap = max(1, (2 * touched_perms - 1).bit_length())
                     out = torch.empty(25 << cap, dtype=torch.int32, device="cuda")
-                    ts, plain, last = [], [], None
-                    for it in range(2 * (args.warmup + args.steps)):  # with records, without, alternating; the payloads go a -> b -> a
-                        rec = it % 2 == 0
-                        dt, r = timed(lambda: tree.update(tk, a, b, records=rec, cap_log_height=cap, out=out if rec else None))
+                    state = {mode: [words_a, words_b] for mode in args.modes}  # the payloads go a -> b -> a, per tree
+
+                    def update(mode, rec):
+                        a, b = state[mode]
+                        r = trees[mode].update(tk, a, b, records=rec, cap_log_height=cap, out=out if rec else None)
                         assert r[0] == 0, r[:2]
-                        a, b = b, a
-                        if it >= 2 * args.warmup:
-                            (ts if rec else plain).append(dt)
-                        if rec:
-                            last = r
-                    su = tree.stats()
-                    entry["updates"][f"2^{log_touched}"] = dict(
-                        with_records=stats(ts), without_records=stats(plain), n_rows=last[4], log_height=last[3], permutations_hashed=su["last_permutations"],
-                        permutations_on_touched_paths=touched_perms, hashed_over_touched=round(su["last_permutations"] / touched_perms, 2), launches=su["last_launches"],
-                        peak_scratch_bytes=su["last_scratch_bytes"], permutations_per_second=round(su["last_permutations"] / (statistics.median(plain) * 1e-3)))
-                    note(log_stored, layout, log_touched, entry["updates"][f"2^{log_touched}"])
+                        state[mode] = [b, a]
+                        return r
+
+                    ts = {mode: dict(with_records=[], without_records=[]) for mode in args.modes}
+                    last = None
+                    for it in range(2 * (args.warmup + args.steps)):  # with records, without, alternating; inside, the modes alternating
+                        rec = it % 2 == 0
+                        for mode in (args.modes if (it // 2) % 2 == 0 else args.modes[::-1]):
+                            dt, r = timed(lambda: update(mode, rec))
+                            if it >= 2 * args.warmup:
+                                ts[mode]["with_records" if rec else "without_records"].append(dt)
+                            if rec:
+                                last = r
+                    cell = dict(n_rows=last[4], log_height=last[3], permutations_on_touched_paths=touched_perms, parent={})
+                    for mode in args.modes:
+                        su = trees[mode].stats()
+                        want = m + sum(stored[1:]) if mode == "rebuild" else m + sum(touched[1:merged + 1]) + sum(stored[merged + 1:])
+                        assert su["last_permutations"] == want, (mode, su["last_permutations"], want)
+                        kern = event_timed(lambda: update(mode, False), ("memory_tree_",))
+                        update(mode, False)  # an even number of updates: the tree holds the image's payloads again
+                        assert state[mode][0] is words_a
+                        cell[mode] = dict(
+                            with_records=stats(ts[mode]["with_records"]), without_records=stats(ts[mode]["without_records"]), permutations_hashed=su["last_permutations"],
+                            hashed_over_touched=round(su["last_permutations"] / touched_perms, 2), launches=su["last_launches"],
+                            # validate, continuity, a count per touched set above the threshold and the tail's sets, a count per level above it and the tail
+                            host_read_backs=4 + touched_above + merged, peak_scratch_bytes=su["last_scratch_bytes"], kernels_without_records=kern)
+                    if "incremental" in args.modes and log_touched == min(args.touched):
+                        moved = sum(stored[l] - touched[l] for l in range(1, merged + 1))  # every key is stored: T_l is part of the old level
+                        ms_move = cell["incremental"]["kernels_without_records"]["memory_tree_move_kernel"]["ms"]
+                        src = torch.empty(moved * 40, dtype=torch.uint8, device="cuda")
+                        dst = torch.empty_like(src)
+                        copies = []
+                        for _ in range(args.warmup + args.steps):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            dst.copy_(src)
+                            e1.record()
+                            torch.cuda.synchronize()
+                            copies.append(e0.elapsed_time(e1))
+                        ms_copy = statistics.median(copies[args.warmup:])
+                        cell["move_kernel"] = dict(nodes_moved=moved, bytes_read_and_written=2 * 40 * moved, launches=merged, ms=ms_move,
+                                                   gb_per_second=round(2 * 40 * moved / ms_move / 1e6, 1), device_copy_ms=round(ms_copy, 4),
+                                                   device_copy_ms_all=[round(x, 4) for x in copies[args.warmup:]],
+                                                   device_copy_gb_per_second=round(2 * 40 * moved / ms_copy / 1e6, 1), over_device_copy=round(ms_copy / ms_move, 3))
+                        del src, dst
+                    if parent:
+                        over_parent(cell, parent["sizes"][f"2^{log_stored}_{layout}"]["updates"][f"2^{log_touched}"])
+                    entry["updates"][f"2^{log_touched}"] = cell
+                    note(log_stored, layout, log_touched, cell)
                     del out
                 section[f"2^{log_stored}_{layout}"] = entry
-                tree.close()
+                for t in trees.values():
+                    t.close()
                 del keys, pay
                 torch.cuda.empty_cache()
 
@@ -199,21 +271,25 @@ def main():
         trace, lh, locations, status = sa.memory_boundary_trace(seg, cap)
         assert status == 0
         keys, init, fin = mt.boundary_leaves(trace, lh, locations)
-        tree = mt.MemoryTree(H)
-        assert tree.load(keys, init) == (0, 0)
+        trees = {mode: mt.MemoryTree(H, incremental=mode == "incremental") for mode in args.modes}
+        for t in trees.values():
+            assert t.load(keys, init) == (0, 0)
         rec_cap = 27
         out = torch.empty(25 << rec_cap, dtype=torch.int32, device="cuda")
-        state = dict(a=init, b=fin)
+        state = {mode: [init, fin] for mode in args.modes}
 
-        def update(records):
-            r = tree.update(keys, state["a"], state["b"], records=records, cap_log_height=rec_cap, out=out if records else None)
+        def update(mode, records):
+            a, b = state[mode]
+            r = trees[mode].update(keys, a, b, records=records, cap_log_height=rec_cap, out=out if records else None)
             assert r[0] == 0, r[:2]
-            state["a"], state["b"] = state["b"], state["a"]
+            state[mode] = [b, a]
             return r
 
-        runs = {"boundary_leaves": lambda: mt.boundary_leaves(trace, lh, locations), "update_with_records": lambda: update(True),
-                "update_without_records": lambda: update(False), "memory_boundary_trace": lambda: sa.memory_boundary_trace(seg, cap),
-                "prove_segment": lambda: prover.prove_segment(seg, logup=True, copy=False)}
+        runs = {"boundary_leaves": lambda: mt.boundary_leaves(trace, lh, locations)}
+        for mode in args.modes:
+            runs[f"update_with_records_{mode}"] = lambda mode=mode: update(mode, True)
+            runs[f"update_without_records_{mode}"] = lambda mode=mode: update(mode, False)
+        runs.update({"memory_boundary_trace": lambda: sa.memory_boundary_trace(seg, cap), "prove_segment": lambda: prover.prove_segment(seg, logup=True, copy=False)})
         times, last = {k: [] for k in runs}, {}
         for it in range(args.warmup + args.steps):
             for k in (list(runs) if it % 2 == 0 else list(runs)[::-1]):
@@ -221,13 +297,21 @@ def main():
                 if it >= args.warmup:
                     times[k].append(dt)
                 note(it, k, round(dt, 2), "ms")
-        su = tree.stats()
-        section.update(log_rows=args.log_rows, locations=locations, runs={k: stats(v) for k, v in times.items()}, n_rows=last["update_with_records"][4],
-                       record_log_height=last["update_with_records"][3], tree=su)
+        first = args.modes[0]
+        section.update(log_rows=args.log_rows, locations=locations, runs={k: stats(v) for k, v in times.items()}, n_rows=last[f"update_with_records_{first}"][4],
+                       record_log_height=last[f"update_with_records_{first}"][3], tree={mode: t.stats() for mode, t in trees.items()})
+        section["kernels_without_records"] = {mode: event_timed(lambda: update(mode, False), ("memory_tree_",)) for mode in args.modes}
         prove = section["runs"]["prove_segment"]["ms_median"]
-        section["fraction_of_prove_segment"] = {k: round(section["runs"][k]["ms_median"] / prove, 4)
-                                                for k in ("boundary_leaves", "update_with_records", "update_without_records", "memory_boundary_trace")}
-        tree.close()
+        section["fraction_of_prove_segment"] = {k: round(v["ms_median"] / prove, 4) for k, v in section["runs"].items() if k != "prove_segment"}
+        if parent:
+            section["parent"] = {k: parent["segment"]["runs"][k] for k in ("update_with_records", "update_without_records", "prove_segment")}
+            for mode in args.modes:
+                for k in ("update_with_records", "update_without_records"):
+                    mine, theirs = section["runs"][f"{k}_{mode}"], section["parent"][k]
+                    section[f"{k}_{mode}_parent_min_over_max"] = round(theirs["ms_min"] / mine["ms_max"], 3)
+                    section[f"{k}_{mode}_parent_median_over_median"] = round(theirs["ms_median"] / mine["ms_median"], 3)
+        for t in trees.values():
+            t.close()
         for p in provers:
             p.close()
 
@@ -235,7 +319,7 @@ def main():
     if out.exists():
         result = {**json.loads(out.read_text()), **result}
     result[args.section] = section
-    result["not_measured"] = ["an incremental rebuild (none was built: hashed_over_touched says what it would save in permutations, not in time)",
+    result["not_measured"] = ["an in-place incremental update (the new levels are built next to the old ones, as in the rebuild)",
                               "trees of other heights than 30", "more than one update in flight, other streams, multi-GPU",
                               "the tree under a device budget (pw_set_device_budget does not account for it)",
                               "the chained VM's segments (a few thousand locations: launch-bound, see the launches per update)"]
