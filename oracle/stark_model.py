@@ -25,6 +25,21 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+_REFUSED = C.c_size_t(-1).value  # or_prove*: a malformed program (oracle/stark_oracle.cpp, `validation`); nothing was evaluated
+
+
+def _proof_words(call, cap):
+    """call(buffer, cap) -> words written or needed; the proof, with a second call if the first buffer was too small"""
+    while True:
+        buf = np.zeros(cap, np.uint32)
+        n = call(buf, cap)
+        if n == _REFUSED:
+            raise ValueError("malformed program: the oracle proves well-formed post-fix programs over the AIR's columns only")
+        if n <= cap:
+            return buf[:n].copy()
+        cap = int(n)
+
+
 def poseidon2(state) -> np.ndarray:
     s = np.ascontiguousarray(state, dtype=np.uint32).copy()
     assert s.shape == (16,)
@@ -123,23 +138,18 @@ def prove(trace_cm, width, log_h, cons_bc, cons_spans, num_queries=8, pow_bits=0
     lib = _lib()
     t = np.ascontiguousarray(trace_cm, dtype=np.uint32)
     bc = np.ascontiguousarray(cons_bc, dtype=np.uint32)
-    sp = np.ascontiguousarray(cons_spans, dtype=np.uint32)
-    args = (C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(t), C.c_uint32(width), C.c_uint32(log_h), _p(bc), _p(sp), C.c_size_t(len(sp)))
-    cap = max(1 << 16, _proof_cap(num_queries, [(width, 0, log_h)]))
-    while True:
-        buf = np.zeros(cap, np.uint32)
-        n = lib.or_prove(*args, _p(buf), C.c_size_t(cap))
-        if n <= cap:
-            return buf[:n].copy()
-        cap = int(n)
+    sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
+    args = (C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(t), C.c_uint32(width), C.c_uint32(log_h), _p(bc), C.c_size_t(len(bc)), _p(sp),
+            C.c_size_t(len(sp)))
+    return _proof_words(lambda buf, cap: lib.or_prove(*args, _p(buf), C.c_size_t(cap)), max(1 << 16, _proof_cap(num_queries, [(width, 0, log_h)])))
 
 
 def verify(proof, width, log_h, cons_bc, cons_spans, num_queries=8, pow_bits=0) -> int:
     pr = np.ascontiguousarray(proof, dtype=np.uint32)
     bc = np.ascontiguousarray(cons_bc, dtype=np.uint32)
-    sp = np.ascontiguousarray(cons_spans, dtype=np.uint32)
+    sp = np.ascontiguousarray(cons_spans, dtype=np.uint32).reshape(-1, 2)
     return int(_lib().or_verify(C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(pr), C.c_size_t(len(pr)), C.c_uint32(width),
-                                C.c_uint32(log_h), _p(bc), _p(sp), C.c_size_t(len(sp))))
+                                C.c_uint32(log_h), _p(bc), C.c_size_t(len(bc)), _p(sp), C.c_size_t(len(sp))))
 
 
 def compile_interactions(apc: om.Apc, idx: dict):
@@ -154,7 +164,10 @@ def group_starts(inter, ispans, ibc) -> np.ndarray:
     out = np.zeros(n + 2, np.uint32)
     lib = _lib()
     lib.or_group_starts.restype = C.c_size_t
-    k = lib.or_group_starts(_p(it), C.c_size_t(n), _p(isp), _p(ib), _p(out), C.c_size_t(len(out)))
+    k = lib.or_group_starts(_p(it), C.c_size_t(n), _p(isp), C.c_size_t(len(isp.reshape(-1, 2))), _p(ib), C.c_size_t(len(ib)), _p(out),
+                            C.c_size_t(len(out)))
+    if k == 0:
+        raise ValueError("malformed interaction table")
     return out[:k].copy()
 
 
@@ -172,15 +185,11 @@ def prove_logup(trace_cm, width, log_h, cons_bc, cons_spans, inter, ispans, ibc,
     keep, seed_p = _seed(bus_seed)
     arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (trace_cm, cons_bc, cons_spans, inter, ispans, ibc)]
     t, bc, sp, it, isp, ib = arrs
-    args = (C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(t), C.c_uint32(width), C.c_uint32(log_h), _p(bc), _p(sp),
-            C.c_size_t(len(sp.reshape(-1, 2))), _p(it), C.c_size_t(len(it.reshape(-1, 3))), _p(isp), _p(ib), seed_p)
+    args = (C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(t), C.c_uint32(width), C.c_uint32(log_h), _p(bc), C.c_size_t(len(bc)), _p(sp),
+            C.c_size_t(len(sp.reshape(-1, 2))), _p(it), C.c_size_t(len(it.reshape(-1, 3))), _p(isp), C.c_size_t(len(isp.reshape(-1, 2))), _p(ib),
+            C.c_size_t(len(ib)), seed_p)
     cap = max(1 << 18, _proof_cap(num_queries, [(width, 4 * (len(it.reshape(-1, 3)) + 1), log_h)]))
-    while True:
-        buf = np.zeros(cap, np.uint32)
-        n = lib.or_prove_logup(*args, _p(buf), C.c_size_t(cap))
-        if n <= cap:
-            return buf[:n].copy()
-        cap = int(n)
+    return _proof_words(lambda buf, cap: lib.or_prove_logup(*args, _p(buf), C.c_size_t(cap)), cap)
 
 
 def verify_logup(proof, width, log_h, cons_bc, cons_spans, inter, ispans, ibc, num_queries=8, pow_bits=0, bus_seed=None) -> int:
@@ -188,8 +197,9 @@ def verify_logup(proof, width, log_h, cons_bc, cons_spans, inter, ispans, ibc, n
     arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (proof, cons_bc, cons_spans, inter, ispans, ibc)]
     pr, bc, sp, it, isp, ib = arrs
     return int(_lib().or_verify_logup(C.c_uint32(num_queries), C.c_uint32(pow_bits), _p(pr), C.c_size_t(len(pr)), C.c_uint32(width),
-                                      C.c_uint32(log_h), _p(bc), _p(sp), C.c_size_t(len(sp.reshape(-1, 2))), _p(it),
-                                      C.c_size_t(len(it.reshape(-1, 3))), _p(isp), _p(ib), seed_p))
+                                      C.c_uint32(log_h), _p(bc), C.c_size_t(len(bc)), _p(sp), C.c_size_t(len(sp.reshape(-1, 2))), _p(it),
+                                      C.c_size_t(len(it.reshape(-1, 3))), _p(isp), C.c_size_t(len(isp.reshape(-1, 2))), _p(ib),
+                                      C.c_size_t(len(ib)), seed_p))
 
 
 def commitment_digest(roots) -> np.ndarray:
@@ -210,7 +220,8 @@ def commitment_digest(roots) -> np.ndarray:
 # ---- pw-stark v1: one proof per segment (oracle/stark_segment.inc) ----------------------------------------------------
 class OrSegAir(C.Structure):
     _fields_ = [("trace", C.c_void_p), ("width", C.c_uint32), ("log_h", C.c_uint32), ("cons_bc", C.c_void_p), ("cons_spans", C.c_void_p),
-                ("n_constraints", C.c_size_t), ("inter", C.c_void_p), ("n_inter", C.c_size_t), ("ispans", C.c_void_p), ("ibc", C.c_void_p)]
+                ("n_constraints", C.c_size_t), ("inter", C.c_void_p), ("n_inter", C.c_size_t), ("ispans", C.c_void_p), ("ibc", C.c_void_p),
+                ("cons_bc_len", C.c_size_t), ("n_ispans", C.c_size_t), ("ibc_len", C.c_size_t)]
 
 
 def _seg_airs(airs, with_traces=True):
@@ -228,7 +239,7 @@ def _seg_airs(airs, with_traces=True):
             c = np.ascontiguousarray(it[2], dtype=np.uint32)
         keep += [bc, sp, tt, a, b, c]
         recs[i] = OrSegAir(None if tt is None else tt.ctypes.data, w, lh, bc.ctypes.data, sp.ctypes.data, len(sp), a.ctypes.data, len(a),
-                           b.ctypes.data, c.ctypes.data)
+                           b.ctypes.data, c.ctypes.data, len(bc), len(b), len(c))
     return recs, keep
 
 
@@ -239,12 +250,8 @@ def prove_segment(airs, num_queries=8, pow_bits=0, logup=False) -> np.ndarray:
     recs, keep = _seg_airs(airs)
     cap = max(1 << 18, _proof_cap(num_queries, [(w, 4 * ((0 if it is None else len(np.asarray(it[0]).reshape(-1, 3))) + 1) if logup else 0, lh)
                                                   for (_, w, lh, _, _, it) in airs]))
-    while True:
-        buf = np.zeros(cap, np.uint32)
-        n = lib.or_prove_segment(C.c_uint32(num_queries), C.c_uint32(pow_bits), C.c_int(int(logup)), recs, C.c_size_t(len(airs)), _p(buf), C.c_size_t(cap))
-        if n <= cap:
-            return buf[:n].copy()
-        cap = int(n)
+    return _proof_words(lambda buf, cap: lib.or_prove_segment(C.c_uint32(num_queries), C.c_uint32(pow_bits), C.c_int(int(logup)), recs,
+                                                              C.c_size_t(len(airs)), _p(buf), C.c_size_t(cap)), cap)
 
 
 def verify_segment(proof, airs, num_queries=8, pow_bits=0, logup=False, check_balance=False):

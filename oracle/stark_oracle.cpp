@@ -291,7 +291,7 @@ void lde_column(const u32* col, int log_n, u32* out) {
 /* post-fix programs over the current row; PUSH operand = column index (same opcodes as the
  * trace-generation bytecode, openvm/src/cuda_abi.rs:137-147, minus INV_OR_ZERO) */
 enum { OP_PUSH_COL = 0, OP_PUSH_CONST = 1, OP_ADD = 2, OP_SUB = 3, OP_MUL = 4, OP_NEG = 5 };
-struct Program { const u32* bc; const u32* spans; size_t n; };
+struct Program { const u32* bc; const u32* spans; size_t n; size_t bc_len; };  /* spans = n x {off, len} into bc[bc_len] */
 
 u32 eval_base(const u32* bc, u32 len, const u32* m, size_t stride, size_t row) {
     u32 st[16]; int sp = 0;
@@ -611,7 +611,7 @@ int verify(const Config& cfg, const u32* proof, size_t len, u32 width, u32 log_h
  */
 constexpr u32 MAGIC2 = 0x32535750u; /* "PWS2" */
 
-struct Interactions { const u32* inter; size_t n; const u32* spans; const u32* bc; };  /* inter = n x {bus, n_args, span index} */
+struct Interactions { const u32* inter; size_t n; const u32* spans; const u32* bc; size_t n_spans, bc_len; };  /* inter = n x {bus, n_args, span index} */
 
 struct LogupRow {  /* per-row evaluation shared by prover (base values) and verifier (ext values) */
     static Ext denom_base(const Interactions& I, size_t i, const u32* m, size_t stride, size_t row, const Ext& al, const Ext* blpow) {
@@ -672,6 +672,45 @@ std::vector<u32> group_starts(const Interactions& I) {
     if (I.n) starts.push_back((u32)I.n);
     return starts;
 }
+
+/* ---- validation: what every entry point asks of the programs it is handed BEFORE anything evaluates them.
+ * eval_base / eval_ext (and LogupRow, group_starts) check nothing: their 16-entry stacks, the operand fetches and the
+ * column reads rely on this pass. A span is accepted when it lies inside its bytecode and holds a well-formed post-fix
+ * program (expr_degree: known opcodes only - INV_OR_ZERO is not polynomial -, every PUSH with its operand inside the
+ * span, no underflow, at most 16 values on the stack, exactly one left) whose column operands are below `width`; an
+ * interaction table when every {mult, arg0, ...} run lies inside the span list. The product refuses the same programs
+ * (pw::postfix_degree, postfix_columns_below, interaction_table_ok). */
+bool span_ok(const u32* bc, size_t bc_len, const u32* span, u32 width) {
+    if ((size_t)span[0] + span[1] > bc_len) return false;
+    const u32* c = bc + span[0];
+    if (expr_degree(c, span[1]) == 99) return false;
+    for (u32 ip = 0; ip < span[1]; ip += 1 + (c[ip] == OP_PUSH_COL || c[ip] == OP_PUSH_CONST))
+        if (c[ip] == OP_PUSH_COL && c[ip + 1] >= width) return false;  /* (well-formed: the operand is inside the span) */
+    return true;
+}
+bool constraints_ok(const Program& p, u32 width) {
+    if (p.n && (!p.bc || !p.spans)) return false;
+    for (size_t k = 0; k < p.n; ++k) if (!span_ok(p.bc, p.bc_len, p.spans + 2 * k, width)) return false;
+    return true;
+}
+bool interaction_table_ok(const Interactions& I) {
+    if (I.n && (!I.inter || !I.spans)) return false;
+    for (size_t i = 0; i < I.n; ++i) {
+        const u32 na = I.inter[3 * i + 1], first = I.inter[3 * i + 2];
+        if ((size_t)first + 1 + na > I.n_spans) return false;
+        for (u32 k = 0; k <= na; ++k) if ((size_t)I.spans[2 * (first + k)] + I.spans[2 * (first + k) + 1] > I.bc_len) return false;
+    }
+    return true;
+}
+bool interactions_ok(const Interactions& I, u32 width) {
+    if (!interaction_table_ok(I)) return false;
+    for (size_t i = 0; i < I.n; ++i)
+        for (u32 k = 0; k <= I.inter[3 * i + 1]; ++k)
+            if (!span_ok(I.bc, I.bc_len, I.spans + 2 * ((size_t)I.inter[3 * i + 2] + k), width)) return false;
+    return true;
+}
+constexpr int MALFORMED_PROGRAM = 10;           /* the verifiers' code, as pw_verify* answers */
+constexpr size_t PROVE_REFUSED = (size_t)-1;    /* or_prove*: no proof was made */
 
 void observe_instance2(Challenger& ch, u32 log_h, u32 width, u32 nc, u32 n_int, const Config& cfg) {
     ch.observe(MAGIC2 % P); ch.observe(log_h); ch.observe(width); ch.observe(nc); ch.observe(n_int);
@@ -1122,19 +1161,22 @@ void or_merkle_commit(const uint32_t* m, size_t height, size_t width, uint32_t* 
         for (auto& l : t.layers) { memcpy(digests_out + o, l.data(), l.size() * 32); o += l.size() * 8; }
     }
 }
-/* prove: returns the number of u32 words written (or needed if cap is too small) */
+/* prove: returns the number of u32 words written (or needed if cap is too small); (size_t)-1 = a malformed program, nothing
+ * was evaluated. The verifiers answer 10 (or_verify_segment: 15, a malformed description) for the same programs. */
 size_t or_prove(uint32_t num_queries, uint32_t pow_bits, const uint32_t* trace, uint32_t width, uint32_t log_h,
-                const uint32_t* cons_bc, const uint32_t* cons_spans, size_t n_constraints, uint32_t* proof, size_t cap) {
+                const uint32_t* cons_bc, size_t cons_bc_len, const uint32_t* cons_spans, size_t n_constraints, uint32_t* proof, size_t cap) {
     Config cfg{num_queries, pow_bits};
-    Program pr{cons_bc, cons_spans, n_constraints};
+    Program pr{cons_bc, cons_spans, n_constraints, cons_bc_len};
+    if (!constraints_ok(pr, width)) return PROVE_REFUSED;
     std::vector<u32> w = prove(cfg, trace, width, log_h, pr);
     if (w.size() <= cap) memcpy(proof, w.data(), w.size() * 4);
     return w.size();
 }
 int or_verify(uint32_t num_queries, uint32_t pow_bits, const uint32_t* proof, size_t len, uint32_t width, uint32_t log_h,
-              const uint32_t* cons_bc, const uint32_t* cons_spans, size_t n_constraints) {
+              const uint32_t* cons_bc, size_t cons_bc_len, const uint32_t* cons_spans, size_t n_constraints) {
     Config cfg{num_queries, pow_bits};
-    Program pr{cons_bc, cons_spans, n_constraints};
+    Program pr{cons_bc, cons_spans, n_constraints, cons_bc_len};
+    if (!constraints_ok(pr, width)) return MALFORMED_PROGRAM;
     return verify(cfg, proof, len, width, log_h, pr);
 }
 
@@ -1142,29 +1184,35 @@ int or_verify(uint32_t num_queries, uint32_t pow_bits, const uint32_t* proof, si
 /* ---- pw-stark v0 + LogUp: interactions = n x {bus id, n_args, first span index}; spans = {off,len} pairs laid out
  * [mult, arg0, arg1, ...] per interaction; bytecode with column-index operands (compile_bus with height 1). */
 size_t or_prove_logup(uint32_t num_queries, uint32_t pow_bits, const uint32_t* trace, uint32_t width, uint32_t log_h,
-                      const uint32_t* cons_bc, const uint32_t* cons_spans, size_t n_constraints, const uint32_t* inter,
-                      size_t n_inter, const uint32_t* ispans, const uint32_t* ibc, const uint32_t* bus_seed /* 8 words or NULL */,
-                      uint32_t* proof, size_t cap) {
+                      const uint32_t* cons_bc, size_t cons_bc_len, const uint32_t* cons_spans, size_t n_constraints, const uint32_t* inter,
+                      size_t n_inter, const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len,
+                      const uint32_t* bus_seed /* 8 words or NULL */, uint32_t* proof, size_t cap) {
     Config cfg{num_queries, pow_bits};
-    Program pr{cons_bc, cons_spans, n_constraints};
-    Interactions I{inter, n_inter, ispans, ibc};
+    Program pr{cons_bc, cons_spans, n_constraints, cons_bc_len};
+    Interactions I{inter, n_inter, ispans, ibc, n_ispans, ibc_len};
+    if (!constraints_ok(pr, width) || !interactions_ok(I, width)) return PROVE_REFUSED;
     std::vector<u32> w = prove_logup(cfg, trace, width, log_h, pr, I, bus_seed);
     if (w.size() <= cap) memcpy(proof, w.data(), w.size() * 4);
     return w.size();
 }
-/* group boundaries of the LogUp packing: writes up to cap entries, returns the number of entries (n_groups + 1) */
-size_t or_group_starts(const uint32_t* inter, size_t n_inter, const uint32_t* ispans, const uint32_t* ibc, uint32_t* out, size_t cap) {
-    Interactions I{inter, n_inter, ispans, ibc};
+/* group boundaries of the LogUp packing: writes up to cap entries, returns the number of entries (n_groups + 1); 0 = the table
+ * leaves its span list or its bytecode (a malformed PROGRAM inside it is no error here: it has the degree 99 and packs alone) */
+size_t or_group_starts(const uint32_t* inter, size_t n_inter, const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len,
+                       uint32_t* out, size_t cap) {
+    Interactions I{inter, n_inter, ispans, ibc, n_ispans, ibc_len};
+    if (!interaction_table_ok(I)) return 0;
     std::vector<u32> g = group_starts(I);
     for (size_t i = 0; i < g.size() && i < cap; ++i) out[i] = g[i];
     return g.size();
 }
 int or_verify_logup(uint32_t num_queries, uint32_t pow_bits, const uint32_t* proof, size_t len, uint32_t width, uint32_t log_h,
-                    const uint32_t* cons_bc, const uint32_t* cons_spans, size_t n_constraints, const uint32_t* inter,
-                    size_t n_inter, const uint32_t* ispans, const uint32_t* ibc, const uint32_t* expected_seed /* or NULL */) {
+                    const uint32_t* cons_bc, size_t cons_bc_len, const uint32_t* cons_spans, size_t n_constraints, const uint32_t* inter,
+                    size_t n_inter, const uint32_t* ispans, size_t n_ispans, const uint32_t* ibc, size_t ibc_len,
+                    const uint32_t* expected_seed /* or NULL */) {
     Config cfg{num_queries, pow_bits};
-    Program pr{cons_bc, cons_spans, n_constraints};
-    Interactions I{inter, n_inter, ispans, ibc};
+    Program pr{cons_bc, cons_spans, n_constraints, cons_bc_len};
+    Interactions I{inter, n_inter, ispans, ibc, n_ispans, ibc_len};
+    if (!constraints_ok(pr, width) || !interactions_ok(I, width)) return MALFORMED_PROGRAM;
     return verify_logup(cfg, proof, len, width, log_h, pr, I, expected_seed);
 }
 
@@ -1175,25 +1223,35 @@ typedef struct {
     uint32_t width, log_h;
     const uint32_t* cons_bc; const uint32_t* cons_spans; size_t n_constraints;
     const uint32_t* inter; size_t n_inter; const uint32_t* ispans; const uint32_t* ibc;
+    size_t cons_bc_len, n_ispans, ibc_len;
 } OrSegAir;
 
 static std::vector<SegAir> seg_airs(const OrSegAir* airs, size_t n) {
     std::vector<SegAir> v(n);
     for (size_t i = 0; i < n; ++i)
-        v[i] = SegAir{airs[i].trace, airs[i].width, airs[i].log_h, Program{airs[i].cons_bc, airs[i].cons_spans, airs[i].n_constraints},
-                      Interactions{airs[i].inter, airs[i].n_inter, airs[i].ispans, airs[i].ibc}};
+        v[i] = SegAir{airs[i].trace, airs[i].width, airs[i].log_h, Program{airs[i].cons_bc, airs[i].cons_spans, airs[i].n_constraints, airs[i].cons_bc_len},
+                      Interactions{airs[i].inter, airs[i].n_inter, airs[i].ispans, airs[i].ibc, airs[i].n_ispans, airs[i].ibc_len}};
     return v;
+}
+/* the interaction tables of a segment count only with logup, as in pw_verify_segment */
+static bool seg_programs_ok(const std::vector<SegAir>& v, bool logup) {
+    for (const auto& a : v) if (!constraints_ok(a.prog, a.width) || (logup && !interactions_ok(a.I, a.width))) return false;
+    return true;
 }
 size_t or_prove_segment(uint32_t num_queries, uint32_t pow_bits, int logup, const OrSegAir* airs, size_t n_airs, uint32_t* proof, size_t cap) {
     Config cfg{num_queries, pow_bits};
-    std::vector<u32> w = prove_segment(cfg, seg_airs(airs, n_airs), logup != 0);
+    const std::vector<SegAir> v = seg_airs(airs, n_airs);
+    if (!seg_programs_ok(v, logup != 0)) return PROVE_REFUSED;
+    std::vector<u32> w = prove_segment(cfg, v, logup != 0);
     if (w.size() <= cap) memcpy(proof, w.data(), w.size() * 4);
     return w.size();
 }
 int or_verify_segment(uint32_t num_queries, uint32_t pow_bits, int logup, const OrSegAir* airs, size_t n_airs, const uint32_t* proof,
                       size_t len, int check_balance, uint32_t* total_sum4) {
     Config cfg{num_queries, pow_bits};
-    return verify_segment(cfg, proof, len, seg_airs(airs, n_airs), logup != 0, check_balance != 0, total_sum4);
+    const std::vector<SegAir> v = seg_airs(airs, n_airs);
+    if (!seg_programs_ok(v, logup != 0)) return 15;  /* a malformed segment description */
+    return verify_segment(cfg, proof, len, v, logup != 0, check_balance != 0, total_sum4);
 }
 
 }  // extern "C"

@@ -378,7 +378,8 @@ std::vector<u32> prove_segment(const Config& cfg, const std::vector<SegAir>& air
 }
 
 /* 0 = valid; codes as verify()/verify_logup() plus 14 = the cumulative bus sums do not cancel (check_balance),
- * 15 = malformed segment description. total_sum4 (may be NULL) receives sum_a S_a. */
+ * 15 = malformed segment description (or_verify_segment also answers it for a malformed PROGRAM of an AIR, before this is called:
+ * `validation` in stark_oracle.cpp). total_sum4 (may be NULL) receives sum_a S_a. */
 int verify_segment(const Config& cfg, const u32* proof, size_t len, const std::vector<SegAir>& airs, bool logup, bool check_balance,
                    u32* total_sum4) {
     const size_t A = airs.size();
