@@ -454,6 +454,28 @@ int pw_memory_tree_get_mode(const PwMemoryTree* tree, uint32_t* mode);
 int pw_memory_tree_boundary_leaves(const uint32_t* d_boundary_trace, uint32_t log_height, uint64_t n_locations, uint64_t* d_keys,
                                    uint32_t* d_init, uint32_t* d_fin);
 
+/* ---- the memory Merkle AIR's trace (the AIR: powdr_amd/memory_tree.py merkle_air) ------------------------------------
+ * d_records (25 columns, column-major with pitch 2^records_log_height, Montgomery) and d_node_ids are what ONE pw_memory_tree_update
+ * of a tree of `height` H wrote: n_rows rows (even), the first half phase 0 and the second half phase 1, both halves in the same node
+ * order, the ids strictly increasing inside a half. d_trace_out (55 x 2^cap_log_height words) receives ONE row per touched node:
+ *   [valid, is_root, is_leaf, left_touched, right_touched, level, index, left0[8], right0[8], out0[8], left1[8], right1[8], out1[8]]
+ * column-major with pitch 2^*log_height, Montgomery; *n_nodes = n_rows / 2, *log_height = the smallest height >= 1 that holds them.
+ * Row r is node *n_nodes - 1 - r of the records order, so the root is row 0 and the leaves come last; left0 / right0 / out0 are the
+ * node's phase-0 record, left1 / right1 / out1 its phase-1 record; level and index come from the id; is_root on the node (H, 0),
+ * is_leaf on level 0; left_touched / right_touched say whether the child (level - 1, 2 index) / (level - 1, 2 index + 1) has a row of
+ * its own. Rows past *n_nodes are all zero. No byte depends on an order of arrival.
+ * *status: 0 = written; 1 = cap_log_height too small (*log_height says what is needed, nothing is written); 2 = n_rows == 0 — a
+ * segment that touches no memory has no root row: the AIR has no trace for it, and proving such a segment's memory continuity is out
+ * of scope here (nothing is written); 3 = the ids are not a records set: the phase-1 id of some node is not its phase-0 id with bit
+ * 63 set, a level is above H or an index does not fit its level, or the last id is not (H, 0) — checked on the device and read back
+ * with the call's one synchronisation; the buffer then holds nothing the caller can rely on.
+ * -1 before any GPU call: a NULL pointer, an odd n_rows, H outside 1 .. 30 (an index below 2^30 is a field element; the tree itself
+ * allows up to 40), a log height outside 1 .. 38 (one lane per row: what a launch holds), more rows than 2^records_log_height. The call runs on the calling thread's launch
+ * stream, synchronises once before it returns and frees its scratch on every path (the contract of pw_memory_boundary_trace). */
+int pw_memory_merkle_trace(const uint32_t* d_records, uint32_t records_log_height, const uint64_t* d_node_ids, uint64_t n_rows,
+                           uint32_t height, uint32_t* d_trace_out, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_nodes,
+                           uint32_t* status);
+
 /* Device memory ONE proof call may plan for (bytes; 0 = no limit beyond what the device has free — the default, or
  * POWDR_DEVICE_BUDGET_BYTES read once). It is applied per call, to what that call's provers and (segments) the calling thread's
  * segment context hold: a proof whose resident buffers would exceed it runs streamed (one-AIR proofs: pw_prover_prove; segments:

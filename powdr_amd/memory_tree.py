@@ -6,9 +6,15 @@ from the memory the last one left, and the opened paths as (left, right, out) ro
                           incremental=True (or the `incremental` property, between any two updates): an update hashes only the touched
                           paths and moves every other stored node, instead of hashing every level again — the same bytes either way
   boundary_leaves         keys and payloads of the rows of a memory boundary trace (key = (as - 1) * 2^29 + ptr)
-  records_air             the sender of the records: 25 columns [valid, left[8], right[8], out[8]]
+  records_air             the sender of the records: 25 columns [valid, left[8], right[8], out[8]] ("each is a compression", no more)
+  merkle_air              the memory Merkle AIR: one row per touched node, before and after the segment; the opened paths
+                          are paths of ONE tree before and ONE tree after, whose roots are its 16 public values MERKLE_PUBLIC
+  merkle_trace            pw_memory_merkle_trace: its 55-column trace on the device from the records and node ids of one update
+  memory_links            the links of prover.verify_segment_chain that make one segment's root_after the next one's root_before
 
-Nothing in a proof constrains the records yet beyond "each is a compression": the Merkle AIR and the persistent boundary AIR come next.
+system_airs.close_segment(..., memory_tree=tree) puts them into a segment. What remains open: the leaves are tied to the boundary AIR's
+init / fin words of THIS segment only through the leaf bus — access adapters, a user public-values chip and a segment that touches no
+memory at all (no root row) are not covered.
 """
 from __future__ import annotations
 
@@ -17,10 +23,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import abi
-from .periphery import _col, _tables
+from . import abi, air_text, prover
+from .periphery import _col, _join_tables, _neg_col, _tables
 from .periphery import OP_PUSH_APC, OP_PUSH_CONST
-from .system_airs import BUS_COMPRESS, OP_MUL, OP_SUB, SystemAir, _to_monty
+from .system_airs import BUS_COMPRESS, OP_ADD, OP_MUL, OP_SUB, SystemAir, _to_monty
 
 lib = abi.lib
 
@@ -47,6 +53,10 @@ lib.pw_memory_tree_set_mode.restype = C.c_int
 lib.pw_memory_tree_set_mode.argtypes = [C.c_void_p, C.c_uint32]
 lib.pw_memory_tree_get_mode.restype = C.c_int
 lib.pw_memory_tree_get_mode.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+
+lib.pw_memory_merkle_trace.restype = C.c_int
+lib.pw_memory_merkle_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 
 MODE_REBUILD, MODE_INCREMENTAL = 0, 1  # PW_MEMORY_TREE_REBUILD, PW_MEMORY_TREE_INCREMENTAL
 TAIL_NODES = 1024  # csrc/memory_tree.hip kMemoryTreeTailNodes: a level of at most this many nodes is finished by one workgroup
@@ -182,3 +192,98 @@ def records_air(bus: int = BUS_COMPRESS) -> SystemAir:
     cons = (np.array([OP_PUSH_APC, 0, OP_PUSH_APC, 0, OP_PUSH_CONST, 1, OP_SUB, OP_MUL], np.uint32), np.array([[0, 8]], np.uint32))
     inter = _tables(bus, [(_col(0), [_col(1 + j) for j in range(24)])])
     return SystemAir("memory_records", RECORD_WIDTH, cons, inter, list(RECORD_COLUMNS))
+
+
+# ---- the memory Merkle AIR (DESIGN.md §5n) -------------------------------------------------------------------------------------------
+BUS_MERKLE, BUS_LEAF = 8, 9  # (level, index, digest before[8], digest after[8]) | (key, init0..3, fin0..3): free next to buses 0-3, 5, 6, 7
+MERKLE_MAX_HEIGHT = 30       # an index below 2^30 is a field element
+_WORDS = ("left0", "right0", "out0", "left1", "right1", "out1")
+MERKLE_COLUMNS = ["valid", "is_root", "is_leaf", "left_touched", "right_touched", "level", "index"] + [f"{n}_{j}" for n in _WORDS for j in range(8)]
+MERKLE_WIDTH = len(MERKLE_COLUMNS)  # 55
+MERKLE_PUBLIC = [f"root_before{j}" for j in range(8)] + [f"root_after{j}" for j in range(8)]
+_FLAGS = ("is_root", "is_leaf", "left_touched", "right_touched")
+MERKLE_STATUS = {0: "written", 1: "cap_log_height too small", 2: "no touched node: a segment that touches no memory has no root row",
+                 3: "the ids are not a records set"}
+
+
+def merkle_constraints(height: int) -> list:
+    """[(name, text)] in the air_text style of system_airs.BOUNDARY_CONSTRAINTS; pv0 .. pv15 = MERKLE_PUBLIC; degree at most 3"""
+    w = range(8)
+    cons = [(f"{n} boolean", f"{n} * ({n} - 1)") for n in ("valid",) + _FLAGS]
+    cons += [(f"{n} only on valid rows", f"{n} * (1 - valid)") for n in _FLAGS]
+    cons += [("the first row is the root", "is_first_row * (1 - is_root)"), ("no root after the first row", "is_transition * is_root'"),
+             ("root level", f"is_root * (level - {int(height)})"), ("root index", "is_root * index")]
+    cons += [(f"root before {j}", f"is_root * (out0_{j} - pv{j})") for j in w]
+    cons += [(f"root after {j}", f"is_root * (out1_{j} - pv{8 + j})") for j in w]
+    cons += [("leaf level", "is_leaf * level"), ("leaf left untouched", "is_leaf * left_touched"), ("leaf right untouched", "is_leaf * right_touched")]
+    cons += [(f"leaf payload tail {n} {j}", f"is_leaf * {n}_{j}") for n in ("left0", "left1") for j in range(4, 8)]
+    cons += [(f"leaf capacity {n} {j}", f"is_leaf * {n}_{j}") for n in ("right0", "right1") for j in w]
+    cons += [(f"untouched left child {j}", f"(1 - is_leaf - left_touched) * (left0_{j} - left1_{j})") for j in w]
+    cons += [(f"untouched right child {j}", f"(1 - right_touched) * (right0_{j} - right1_{j})") for j in w]
+    return cons
+
+
+def merkle_air(height: int = 30, compress_bus: int = BUS_COMPRESS, merkle_bus: int = BUS_MERKLE, leaf_bus: int = BUS_LEAF) -> SystemAir:
+    """The memory Merkle AIR (row-aware: transition=True): ONE row per touched node, carrying the node before (left0, right0, out0) and
+    after (left1, right1, out1) the segment; 55 main columns MERKLE_COLUMNS, 16 public values MERKLE_PUBLIC, constraints
+    merkle_constraints(height). Interactions, every multiplicity and argument of degree at most 1, no public value in any:
+      compress_bus  +valid (left0, right0, out0) and +valid (left1, right1, out1): the Poseidon2 chip makes every out the compression
+      merkle_bus    +(valid - is_root) (level, index, out0, out1): every node but the root is somebody's child;
+                    -left_touched (level - 1, 2 index, left0, left1), -right_touched (level - 1, 2 index + 1, right0, right1)
+      leaf_bus      -is_leaf (index, left0[0..3], left1[0..3]): what boundary_air(leaf_bus=) sends, key and words
+    A padding row is all zeros. height: 1 .. 30 (the tree's own limit is 40: an index below 2^30 is a field element)."""
+    if not 1 <= int(height) <= MERKLE_MAX_HEIGHT:
+        raise ValueError(f"the height of the memory Merkle AIR is 1 .. {MERKLE_MAX_HEIGHT}")
+    if len({compress_bus, merkle_bus, leaf_bus}) != 3:
+        raise ValueError("the compression, Merkle and leaf buses are three buses")
+    col = {n: i for i, n in enumerate(MERKLE_COLUMNS)}
+    rows = prover.row_operands(MERKLE_WIDTH)
+    names = {**col, **{f"pv{k}": rows.public(k) for k in range(len(MERKLE_PUBLIC))}}
+    bc, spans = [], []
+    for _, text in merkle_constraints(height):
+        code = air_text.compile_expr(text, names, rows)
+        spans.append((len(bc), len(code)))
+        bc += code
+    c = lambda n: _col(col[n])
+    words = lambda n, k=8: [c(f"{n}_{j}") for j in range(k)]
+    child_level = c("level") + [OP_PUSH_CONST, 1, OP_SUB]
+    left_index = [OP_PUSH_CONST, 2] + c("index") + [OP_MUL]
+    by_bus = [
+        (compress_bus, [(c("valid"), words("left0") + words("right0") + words("out0")), (c("valid"), words("left1") + words("right1") + words("out1"))]),
+        (merkle_bus, [(c("valid") + c("is_root") + [OP_SUB], [c("level"), c("index")] + words("out0") + words("out1")),
+                      (_neg_col(col["left_touched"]), [child_level, left_index] + words("left0") + words("left1")),
+                      (_neg_col(col["right_touched"]), [child_level, left_index + [OP_PUSH_CONST, 1, OP_ADD]] + words("right0") + words("right1"))]),
+        (leaf_bus, [(_neg_col(col["is_leaf"]), [c("index")] + words("left0", 4) + words("left1", 4))]),
+    ]
+    return SystemAir("memory_merkle", MERKLE_WIDTH, (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2)), _join_tables(by_bus),
+                     list(MERKLE_COLUMNS), transition=True, n_public=len(MERKLE_PUBLIC))
+
+
+def memory_links(merkle_index: int):
+    """The links of prover.verify_segment_chain that make the memory of consecutive segments one memory: root_after[j] of one segment's
+    Merkle AIR (AIR `merkle_index` of every segment) is root_before[j] of the next."""
+    i = int(merkle_index)
+    return [(i, 8 + j, i, j) for j in range(8)]
+
+
+def merkle_trace(records: torch.Tensor, ids: torch.Tensor, log_h: int, n_rows: int, height: int, cap_log_height: int = 10, out: torch.Tensor | None = None):
+    """pw_memory_merkle_trace: records, ids, log_h, n_rows = what MemoryTree.update(..., node_ids=True) returned for a tree of `height`
+    -> (trace: 55 x 2^log_height Montgomery words, column-major (MERKLE_COLUMNS), the root on row 0 — None unless status is 0;
+    log_height; n_nodes = n_rows / 2; status: a key of MERKLE_STATUS). Status 1 is retried once at the height the library asked for, in
+    a buffer of that height — unless the caller gave `out`, whose size is the caller's business (the rule of poseidon2_compress_trace)."""
+    assert records.dtype == torch.int32 and records.is_cuda and records.numel() >= RECORD_WIDTH << log_h
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.numel() >= n_rows
+    torch.cuda.synchronize()
+    own = out is None
+    for _ in range(2):
+        if own:
+            out = torch.empty(MERKLE_WIDTH << cap_log_height, dtype=torch.int32, device="cuda")
+        assert out.numel() >= MERKLE_WIDTH << cap_log_height
+        lh, nodes, status = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        abi.check(lib.pw_memory_merkle_trace(records.data_ptr(), int(log_h), ids.data_ptr(), int(n_rows), int(height), out.data_ptr(), cap_log_height,
+                                             C.byref(lh), C.byref(nodes), C.byref(status)), "pw_memory_merkle_trace")
+        if status.value != 1 or not own:
+            break
+        cap_log_height = int(lh.value)
+    trace = out[:MERKLE_WIDTH << lh.value] if status.value == 0 else None
+    return trace, int(lh.value), int(nodes.value), int(status.value)

@@ -102,6 +102,21 @@ def _tables(bus: int, rows):
     return np.array(inter, np.uint32).reshape(-1, 3), np.array(spans, np.uint32).reshape(-1, 2), np.array(bc, np.uint32)
 
 
+def _join_tables(by_bus):
+    """[(bus, rows of _tables)] -> one interaction table over the buses: spans and bytecode concatenated"""
+    inter, ispans, ibc = [], [], []
+    for bus, rows_ in by_bus:
+        it, sp, code = _tables(bus, rows_)
+        it = it.copy()
+        it[:, 2] += len(ispans)
+        sp = sp.copy()
+        sp[:, 0] += len(ibc)
+        inter += it.tolist()
+        ispans += sp.tolist()
+        ibc += code.tolist()
+    return np.array(inter, np.uint32).reshape(-1, 3), np.array(ispans, np.uint32).reshape(-1, 2), np.array(ibc, np.uint32)
+
+
 def _col(c):
     return [OP_PUSH_APC, c]
 

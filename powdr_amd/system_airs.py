@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import abi, air_text, prover
-from .periphery import OP_PUSH_APC, OP_PUSH_CONST, _col, _neg_col, _tables
+from .periphery import OP_PUSH_APC, OP_PUSH_CONST, _col, _join_tables, _neg_col, _tables
 
 lib = abi.lib
 lib.pw_program_frequencies.restype = C.c_int
@@ -166,10 +166,12 @@ def connector_links(connector_index: int):
     return [(i, k("end_pc"), i, k("start_pc")), (i, k("end_ts"), i, k("start_ts"))]
 
 
-def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANGE, bitwise_bus: int = BUS_BITWISE) -> SystemAir:
+def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANGE, bitwise_bus: int = BUS_BITWISE, leaf_bus: int | None = None) -> SystemAir:
     """The memory boundary AIR (row-aware: transition=True). Constraints BOUNDARY_CONSTRAINTS; interactions, all on the current row:
     send (as, ptr, init0..3, init_ts), receive (as, ptr, fin0..3, fin_ts), range checks of the four limbs, byte checks of the initial
-    words (the final ones are whatever the last access sent, whose chip checked them)."""
+    words (the final ones are whatever the last access sent, whose chip checked them). leaf_bus (None, the default: the AIR as it
+    always was): one more interaction, the send of ((as - 1) * 2^29 + ptr, init0..3, fin0..3) with multiplicity is_valid — the key
+    and the four payload words of pw_memory_tree_boundary_leaves, received by the memory Merkle AIR's leaf rows."""
     col = {n: i for i, n in enumerate(BOUNDARY_COLUMNS)}
     rows = prover.row_operands(BOUNDARY_WIDTH)
     bc, spans = [], []
@@ -187,18 +189,10 @@ def boundary_air(memory_bus: int = BUS_MEMORY, var_range_bus: int = BUS_VAR_RANG
                          (valid, [c("d_lo"), const(LIMB_BITS[0])]), (valid, [c("d_hi"), const(LIMB_BITS[1])])]),
         (bitwise_bus, [(valid, [c("init0"), c("init1"), const(0), const(0)]), (valid, [c("init2"), c("init3"), const(0), const(0)])]),
     ]
-    inter, ispans, ibc = [], [], []
-    for bus, rows_ in by_bus:  # one table over the three buses: spans and bytecode concatenated
-        it, sp, code = _tables(bus, rows_)
-        it = it.copy()
-        it[:, 2] += len(ispans)
-        sp = sp.copy()
-        sp[:, 0] += len(ibc)
-        inter += it.tolist()
-        ispans += sp.tolist()
-        ibc += code.tolist()
-    interactions = (np.array(inter, np.uint32).reshape(-1, 3), np.array(ispans, np.uint32).reshape(-1, 2), np.array(ibc, np.uint32))
-    return SystemAir("boundary", BOUNDARY_WIDTH, (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2)), interactions,
+    if leaf_bus is not None:
+        key = c("as") + const(1) + [OP_SUB] + const(1 << 29) + [OP_MUL] + c("ptr") + [OP_ADD]
+        by_bus.append((leaf_bus, [(valid, [key] + [c(f"init{i}") for i in range(4)] + [c(f"fin{i}") for i in range(4)])]))
+    return SystemAir("boundary", BOUNDARY_WIDTH, (np.array(bc, np.uint32), np.array(spans, np.uint32).reshape(-1, 2)), _join_tables(by_bus),
                      list(BOUNDARY_COLUMNS), transition=True)
 
 
@@ -381,16 +375,33 @@ def set_boundary_start_slots(log_slots: int) -> None:
 
 
 def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int = 100, pow_bits: int = 0, pc_step: int = 4, table_bytes: int = 0,
-                  cap_log_height: int = 16, public_connector: bool = False, poseidon2: bool = False):
+                  cap_log_height: int = 16, public_connector: bool = False, poseidon2: bool = False, memory_tree=None):
     """airs: [dict(prover, trace (device tensor), log_h, ...)] — every AIR that sends on the execution bridge, the memory bus and the
     PC lookup, traces made. Appends the program, connector and boundary AIRs as dicts of the same shape (name, role "system", air =
     the SystemAir, width, log_h, cons, inter, trace, prover, pre) and returns the list. periphery (tracegen.Periphery): its histograms
     receive the boundary AIR's range and byte lookups (_apc_apply_bus on its trace) — call this BEFORE the periphery traces are made
-    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). public_connector: the connector with its four public values (connector_air(public=True)), set from the two states connector_trace finds; its dict also has public = those values. poseidon2: when any AIR sends on BUS_COMPRESS, the Poseidon2 compression chip (poseidon2_air, made under the constants installed now) is appended after the three, its trace by poseidon2_compress_trace; False (the default): the bus is left alone. Raises on foreign instructions, on a boundary or chip status other than 0 and on an execution bridge that is not a chain."""
+    from them. cap_log_height: the boundary buffer first tried (a taller trace is retried once at its own height). public_connector: the connector with its four public values (connector_air(public=True)), set from the two states connector_trace finds; its dict also has public = those values. poseidon2: when any AIR sends on BUS_COMPRESS, the Poseidon2 compression chip (poseidon2_air, made under the constants installed now) is appended after the three, its trace by poseidon2_compress_trace; False (the default): the bus is left alone. Raises on foreign instructions, on a boundary or chip status other than 0 and on an execution bridge that is not a chain.
+    memory_tree (a memory_tree.MemoryTree holding the memory the segment starts from; None, the default: the function as it always
+    was): the boundary AIR is made with its leaf send (boundary_air(leaf_bus=BUS_LEAF)), its rows' leaves go through the tree's update
+    (node ids on) — any status of the update raises, status 3 with the key that does not hold its initial words, and the tree is then
+    what it was — and the memory Merkle AIR (memory_tree.merkle_air) is appended after the boundary with its trace
+    (memory_tree.merkle_trace) and public = the tree's root before the update | its root after, read from the tree, not from the
+    trace. The Merkle AIR is among the senders the Poseidon2 chip's trace is made from, and the chip is appended after it:
+    memory_tree needs poseidon2=True (ValueError otherwise, before anything is made — the Merkle AIR's sends on BUS_COMPRESS would
+    have no receiver). A segment without a memory location raises before the update (the Merkle AIR has no trace without a root
+    row). THE TREE MOVES WITH THE UPDATE: an error raised after it — a Merkle trace or chip status — leaves the tree at the
+    segment's final memory, with no segment returned; only the update's own statuses leave it where it was."""
     from .segment_workload import BusReplay
 
     seg = [(a["prover"], a["trace"].data_ptr(), a["log_h"]) for a in airs]
-    bnd = boundary_air()
+    if memory_tree is not None:
+        from . import memory_tree as mt  # (it imports this module)
+
+        if not poseidon2:
+            raise ValueError("memory_tree needs poseidon2=True: the memory Merkle AIR sends on the compression bus, which the chip receives")
+        bnd = boundary_air(leaf_bus=mt.BUS_LEAF)
+    else:
+        bnd = boundary_air()
     trace, lh, locations, status = memory_boundary_trace(seg, cap_log_height, table_bytes)
     if status == 1:
         trace, lh, locations, status = memory_boundary_trace(seg, lh, table_bytes)
@@ -404,17 +415,36 @@ def close_segment(airs, program_table, pc_base: int, periphery, num_queries: int
     con = connector_air(public=public_connector)
     con_trace, start, end = connector_trace(seg, with_states=True)
     system = [(prog, freq, prog.log_h), (con, con_trace, 1), (bnd, trace, lh)]
-    if poseidon2 and any(BUS_COMPRESS in np.asarray(a["inter"][0]).reshape(-1, 3)[:, 0] for a in airs if a.get("inter") is not None):
+    public, made = {con.name: np.array([*start, *end], np.uint32)}, {}
+    hashers = any(BUS_COMPRESS in np.asarray(a["inter"][0]).reshape(-1, 3)[:, 0] for a in airs if a.get("inter") is not None)
+    if memory_tree is not None:
+        if not locations:
+            raise ValueError(f"memory Merkle trace: {mt.MERKLE_STATUS[2]}")
+        mk = mt.merkle_air(memory_tree.height)
+        root_before = memory_tree.root()
+        keys, init, fin = mt.boundary_leaves(trace, lh, locations)
+        t_status, info, records, rec_lh, rec_rows = memory_tree.update(keys, init, fin, node_ids=True)
+        if t_status:
+            raise ValueError(f"memory tree: status {t_status}, {mt.STATUS[t_status]}" + (f" (key {info})" if t_status == 3 else f" ({info})"))
+        mk_trace, mk_lh, nodes, mk_status = mt.merkle_trace(*records, rec_lh, rec_rows, memory_tree.height)
+        if mk_status:
+            raise ValueError(f"memory Merkle trace: {mt.MERKLE_STATUS[mk_status]} ({nodes} nodes)")
+        public[mk.name] = np.concatenate([root_before, memory_tree.root()]).astype(np.uint32)
+        made[mk.name] = mk.make_prover(num_queries, pow_bits)
+        system.append((mk, mk_trace, mk_lh))
+        seg = seg + [(made[mk.name], mk_trace.data_ptr(), mk_lh)]  # the chip's senders
+        hashers = True
+    if poseidon2 and hashers:
         p2_trace, p2_lh, p2_rows, p2_status = poseidon2_compress_trace(seg, min(cap_log_height, 10), table_bytes)
         if p2_status:
             raise ValueError(f"poseidon2 chip: {STATUS[p2_status]} ({p2_rows} rows)")
         system.append((poseidon2_air(), p2_trace, p2_lh))
     out = list(airs)
     for air, t, h in system:
-        p = air.make_prover(num_queries, pow_bits)
+        p = made.get(air.name) or air.make_prover(num_queries, pow_bits)
         out.append(dict(name=air.name, role="system", air=air, width=air.width, log_h=h, cons=air.cons, inter=air.inter, trace=t, prover=p,
                         pre=(air.fixed_table(), air.pre_width, air.log_h) if air.pre_width else None))
         if air.n_public:
-            out[-1]["public"] = np.array([*start, *end], np.uint32)
+            out[-1]["public"] = public[air.name]
             p.set_public_values(out[-1]["public"])
     return out

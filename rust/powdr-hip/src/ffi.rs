@@ -452,6 +452,11 @@ extern "C" {
     /// keys and payloads of the rows of a memory boundary trace
     pub fn pw_memory_tree_boundary_leaves(d_boundary_trace: *const u32, log_height: u32, n_locations: u64, d_keys: *mut u64,
                                           d_init: *mut u32, d_fin: *mut u32) -> c_int;
+    /// the memory Merkle AIR's trace (55 columns, one row per touched node, the root first) from the records and node ids of one
+    /// `pw_memory_tree_update`; `status` 0 = written, 1 = `cap_log_height` too small, 2 = no rows, 3 = the ids are not a records set
+    pub fn pw_memory_merkle_trace(d_records: *const u32, records_log_height: u32, d_node_ids: *const u64, n_rows: u64, height: u32,
+                                  d_trace_out: *mut u32, cap_log_height: u32, log_height: *mut u32, n_nodes: *mut u64,
+                                  status: *mut u32) -> c_int;
     pub fn pw_verify(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32, bytecode_len: usize,
                      cons_spans: *const u32, n_constraints: usize, proof_words: *const u32, n_words: usize) -> c_int;
     pub fn pw_verify_logup(cfg: *const PwStarkConfig, width: u32, log_height: u32, cons_bytecode: *const u32,
