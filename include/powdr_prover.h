@@ -434,7 +434,30 @@ int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_
  *
  * pw_memory_tree_boundary_leaves: the leaves of a memory boundary trace (pw_memory_boundary_trace: 18 columns, 2^log_height rows, the
  * first n_locations valid, sorted by (as, ptr), hence by key): d_keys[r] = (as - 1) * 2^29 + ptr, d_init / d_fin[8 r ..] = (init0..3,
- * 0, 0, 0, 0) / (fin0..3, 0, 0, 0, 0). -1: a NULL pointer, log_height outside 1 .. 40, more locations than rows. */
+ * 0, 0, 0, 0) / (fin0..3, 0, 0, 0, 0). -1: a NULL pointer, log_height outside 1 .. 40, more locations than rows.
+ *
+ * pw_memory_tree_open: the multi-opening of n leaves, read-only — the tree is unchanged in every stored byte, its
+ * root, its stats and its mode, in both modes. d_keys = n strictly increasing leaf indices below 2^H (what pw_memory_tree_update
+ * takes). d_payloads (n x 8 words, row-major, Montgomery): row j = the payload stored for key j, 8 zeros where the key is not stored
+ * (so an opening proves non-membership too). d_siblings (cap_siblings x 8 words, Montgomery): with T_0 = the keys and T_(l+1) =
+ * unique(T_l >> 1), for l = 0 .. H - 1 in ascending level and inside a level in ascending index, for every node t of T_l whose
+ * sibling t ^ 1 is NOT in T_l the digest of node (l, t ^ 1), Z_l where that node is not stored — the standard multiproof; *n_siblings
+ * = their number (one key: H; the keys {0, 1}: H - 1; every leaf of a tree: 0; never above n H). Three launches whatever H is: one
+ * lane per (level, key) flags the nodes whose sibling is carried, one scan ranks them, the flagged lanes look the sibling up in its
+ * level and write it at its rank; nothing is hashed and no byte depends on an order of arrival. *status: 0 = written; 4 = the keys
+ * are not strictly increasing or one is >= 2^H, *info = the index of the first offender (the rule of the update); 1 = cap_siblings <
+ * *n_siblings (which is set). With a non-zero *status neither output buffer is touched and 0 is returned. -1 before any GPU call: a
+ * NULL pointer, n == 0 (or above 2^40), changed round constants, a tree whose buffers live on another device. An empty tree may get
+ * its Z_0 .. Z_H buffer allocated by this call (every sibling is a Z_l, every payload zero). The stream contract is the update's:
+ * the calling thread's launch stream, a synchronisation before the return, the scratch (9 n H bytes and the scan's) freed on every
+ * path. WHAT IT PROVES: that the tree with this root holds these payloads at these keys — a statement about a root. That the root is
+ * the memory an execution ended with is what pw_verify_segment_chain says about the last segment's root_after.
+ * pw_memory_opening_verify (host, no GPU call; the installed table): recomputes the root bottom-up from keys, payloads and siblings
+ * — all canonical words, the siblings consumed in the order above — leaf = compress(payload | 0^8), node = compress(left | right).
+ * 0 = the root is `root`; 20 = it is not; 19 = malformed: height outside 1 .. 40, n == 0 or a NULL pointer, the keys not strictly
+ * increasing or >= 2^height (*where = the first such key's index), a word >= p (*where = its index in its array, looked for in
+ * root, payloads, siblings in this order), m not the number the keys imply (*where = that number: m is derived, never trusted).
+ * where may be NULL. (10 .. 18 are the proof verifiers' codes.) */
 typedef struct PwMemoryTree PwMemoryTree;
 typedef struct PwMemoryTreeStats {
     uint64_t leaves, stored_nodes, device_bytes;
@@ -453,6 +476,10 @@ int pw_memory_tree_set_mode(PwMemoryTree* tree, uint32_t mode);
 int pw_memory_tree_get_mode(const PwMemoryTree* tree, uint32_t* mode);
 int pw_memory_tree_boundary_leaves(const uint32_t* d_boundary_trace, uint32_t log_height, uint64_t n_locations, uint64_t* d_keys,
                                    uint32_t* d_init, uint32_t* d_fin);
+int pw_memory_tree_open(const PwMemoryTree* tree, const uint64_t* d_keys, size_t n, uint32_t* d_payloads, uint32_t* d_siblings,
+                        uint64_t cap_siblings, uint64_t* n_siblings, uint32_t* status, uint64_t* info);
+int pw_memory_opening_verify(uint32_t height, const uint32_t* root, const uint64_t* keys, const uint32_t* payloads, size_t n,
+                             const uint32_t* siblings, size_t m, size_t* where);
 
 /* ---- the memory Merkle AIR's trace (the AIR: powdr_amd/memory_tree.py merkle_air) ------------------------------------
  * d_records (25 columns, column-major with pitch 2^records_log_height, Montgomery) and d_node_ids are what ONE pw_memory_tree_update

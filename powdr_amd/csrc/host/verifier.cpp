@@ -730,6 +730,69 @@ extern "C" int pw_verify_segment_chain(const PwStarkConfig* cfg, const PwChainSe
     return 0;
 }
 
+// A multi-opening of the sparse memory Merkle tree (pw_memory_tree_open) against a root: no GPU call. The touched sets
+// T_0 = keys, T_(l+1) = unique(T_l >> 1) are walked twice — first the indices alone, which gives the number of siblings the keys imply
+// (`m` is compared with it, never trusted), then the digests: a node of T_l whose sibling is in T_l is hashed with it, any other with
+// the next sibling of the proof, on the side its index says. 19: malformed; 20: another root.
+extern "C" int pw_memory_opening_verify(uint32_t height, const uint32_t* root, const uint64_t* keys, const uint32_t* payloads, size_t n,
+                                        const uint32_t* siblings, size_t m, size_t* where) {
+    size_t unused = 0;
+    size_t& at = where ? *where : unused;
+    at = 0;
+    if (height < 1 || height > 40 || !n || !root || !keys || !payloads || (m && !siblings)) return 19;
+    for (size_t j = 0; j < n; ++j)
+        if ((keys[j] >> height) != 0 || (j > 0 && keys[j - 1] >= keys[j])) { at = j; return 19; }
+    for (size_t i = 0; i < 8; ++i)
+        if (root[i] >= bb::P) { at = i; return 19; }
+    for (size_t i = 0; i < 8 * n; ++i)
+        if (payloads[i] >= bb::P) { at = i; return 19; }
+    for (size_t i = 0; i < 8 * m; ++i)
+        if (siblings[i] >= bb::P) { at = i; return 19; }
+    std::vector<uint64_t> idx(keys, keys + n);
+    size_t expected = 0;
+    for (uint32_t l = 0; l < height; ++l) {
+        size_t out = 0;
+        for (size_t i = 0; i < idx.size();) {
+            const uint64_t t = idx[i];
+            const bool pair = !(t & 1) && i + 1 < idx.size() && idx[i + 1] == t + 1;
+            if (!pair) ++expected;
+            idx[out++] = t >> 1;
+            i += pair ? 2 : 1;
+        }
+        idx.resize(out);
+    }
+    if (expected != m) { at = expected; return 19; }
+    idx.assign(keys, keys + n);
+    std::vector<Digest> dig(n);
+    const Digest zero8{};
+    for (size_t j = 0; j < n; ++j) {
+        Digest w;
+        for (int i = 0; i < 8; ++i) w.w[i] = bb::to_monty(payloads[8 * j + i]);
+        dig[j] = compress(w, zero8);
+    }
+    size_t next = 0;
+    for (uint32_t l = 0; l < height; ++l) {
+        size_t out = 0;
+        for (size_t i = 0; i < idx.size();) {
+            const uint64_t t = idx[i];
+            const bool pair = !(t & 1) && i + 1 < idx.size() && idx[i + 1] == t + 1;
+            Digest sib{};
+            if (!pair) {
+                for (int q = 0; q < 8; ++q) sib.w[q] = bb::to_monty(siblings[8 * next + q]);
+                ++next;
+            }
+            const Digest parent = pair ? compress(dig[i], dig[i + 1]) : (t & 1) ? compress(sib, dig[i]) : compress(dig[i], sib);
+            idx[out] = t >> 1;
+            dig[out++] = parent;
+            i += pair ? 2 : 1;
+        }
+        idx.resize(out);
+    }
+    for (int i = 0; i < 8; ++i)
+        if (dig[0].w[i] != bb::to_monty(root[i])) return 20;
+    return 0;
+}
+
 // Boundaries of the LogUp groups the prover and the verifier derive from an interaction table (logup_groups.hpp):
 // writes up to `cap` entries, returns the number of entries (n_groups + 1), 0 if the table is malformed.
 extern "C" size_t pw_logup_group_starts(const uint32_t* interactions, size_t n_interactions, const uint32_t* inter_spans,

@@ -12,6 +12,10 @@
 //   incremental (pw_memory_tree_set_mode, opt-in) the levels above the threshold are rank merges too, the way level 0 is: found + a scan
 //               rank T_l in the old level l, touched_parent_kernel hashes every node of T_l from its children in the new level l - 1,
 //               move_kernel streams every other stored node to its new rank, unhashed; the tail and load mode are the rebuild's.
+//   open        (pw_memory_tree_open; read-only) the multiproof of n keys in three launches whatever H is: open_flag_kernel,
+//               one lane per (level, key), says which lanes own a node of T_l whose sibling is not in T_l; one scan ranks them;
+//               open_gather_kernel looks the sibling up in its level and writes its digest (Z_l: not stored) at the rank, the level-0
+//               lanes the payloads. No hashing, no tree buffers, nothing that depends on an order of arrival.
 // The new tree is built into fresh buffers next to the old one and swapped in at the very end: any status or error leaves the tree
 // as it was. The permutation is p2::permute with the parameters as a kernel argument (scalar loads, as the __constant__ copy of
 // merkle.hip gives them).
@@ -355,6 +359,75 @@ __global__ __launch_bounds__(kBlock) void records_kernel(const RecArgs a) {
 #pragma unroll
     for (int k = 0; k < 24; ++k) out[(size_t)(1 + k) * a.pitch] = w[k];
     if (a.ids) a.ids[row] = ((u64)ph << 63) | ((u64)l << 56) | t;
+}
+
+// ---- the multi-opening (pw_memory_tree_open) ------------------------------------------------------------------------------------------
+// Lane (l, j) = (blockIdx.y, blockIdx.x * kBlock + threadIdx.x) stands for the node t = key_j >> l of T_l and owns it when key_(j-1)
+// is not below it too. Its sibling t ^ 1 is in T_l iff, t odd: key_(j-1) >> l == t - 1 (the keys are sorted: the key before the first
+// one below t); t even: the first key at or past (t + 1) << l — searched among the keys behind j only — is below t + 2 as well.
+// flags[l * n + j] = the lane owns a node whose sibling the proof has to carry. The level-0 lanes apply validate_kernel's rule to the
+// keys on the way (err[0]); with malformed keys the flags mean nothing, and every read stays inside keys[0 .. n).
+__global__ __launch_bounds__(kBlock) void open_flag_kernel(const u64* __restrict__ keys, u64 n, uint32_t H, uint8_t* __restrict__ flags, u64* __restrict__ err) {
+    const u64 j = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t l = blockIdx.y;
+    if (j == 0 && l == 0) flags[n * H] = 0;  // (the scan's last place: the total)
+    if (j >= n) return;
+    const u64 k = keys[j];
+    const u64 before = j > 0 ? keys[j - 1] : 0;
+    if (l == 0 && ((k >> H) != 0 || (j > 0 && before >= k))) atomicMin(err, j);
+    const u64 t = k >> l;
+    bool carry = j == 0 || (before >> l) != t;
+    if (carry) {
+        if (t & 1ull) {
+            carry = j == 0 || (before >> l) != t - 1;
+        } else {
+            // the keys below t end a run that starts at j: short on the low levels, where most lanes own a node — gallop, then search
+            const u64 first = (t + 1) << l;
+            u64 lo = j + 1, hi = j + 1;
+            for (u64 step = 1; hi < n && keys[hi] < first; step <<= 1) { lo = hi + 1; hi += step; }
+            hi = hi < n ? hi : n;
+            const u64 c = lo + lower_bound(keys + lo, hi - lo, first);
+            carry = c >= n || (keys[c] >> l) != t + 1;
+        }
+    }
+    flags[(u64)l * n + j] = carry ? 1 : 0;
+}
+
+// The flagged lanes: one lower_bound for t ^ 1 in level l's sorted indices, the digest (Z_l where it is not stored) as two 16-byte
+// loads and two 16-byte stores at the lane's rank. The level-0 lanes look their key up as well and write its payload row.
+struct FlagToCount {
+    __host__ __device__ u64 operator()(uint8_t f) const { return f; }
+};
+struct OpenArgs {
+    LevelView lv[kMaxHeight];  // levels 0 .. H - 1: the root has no sibling
+    const uint32_t* payload;
+    const uint32_t* zero;
+};
+__global__ __launch_bounds__(kBlock) void open_gather_kernel(const OpenArgs a, const u64* __restrict__ keys, u64 n, const uint8_t* __restrict__ flags,
+                                                              const u64* __restrict__ rank, uint32_t* __restrict__ payloads, uint32_t* __restrict__ siblings) {
+    const u64 j = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t l = blockIdx.y;
+    if (j >= n) return;
+    const u64 i = (u64)l * n + j;
+    const bool carry = flags[i] != 0;
+    if (!carry && l != 0) return;
+    const u64 k = keys[j];
+    const LevelView me = a.lv[l];
+    uint32_t w[8];
+    if (l == 0) {
+        const u64 at = lower_bound(me.idx, me.n, k);
+        if (at < me.n && me.idx[at] == k) load8(a.payload + at * 8, w);
+        else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) w[q] = 0u;
+        }
+        store8(payloads + j * 8, w);
+        if (!carry) return;
+    }
+    const u64 s = (k >> l) ^ 1ull;
+    const u64 at = lower_bound(me.idx, me.n, s);
+    if (at < me.n && me.idx[at] == s) load8(me.dig + at * 8, w); else load8(a.zero + (size_t)l * 8, w);
+    store8(siblings + rank[i] * 8, w);
 }
 
 // One lane per row of the memory boundary AIR's trace. THE COLUMN POSITIONS ARE THOSE OF BOUNDARY_COLUMNS (powdr_amd/system_airs.py;
@@ -792,6 +865,76 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
     tree->last_launches = cx.launches;
     tree->last_scratch = cx.peak;
     return 0;
+}
+
+extern "C" int pw_memory_tree_open(const PwMemoryTree* tree_, const uint64_t* d_keys_, size_t n, uint32_t* d_payloads, uint32_t* d_siblings, uint64_t cap_siblings,
+                                   uint64_t* n_siblings, uint32_t* status, uint64_t* info) {
+    if (!tree_ || !d_keys_ || !n || !d_payloads || !d_siblings || !n_siblings || !status || !info || !same_table(tree_)) return -1;
+    const int H = (int)tree_->height;
+    const u64 lanes = (u64)n * (u64)H;
+    if (n > ((u64)1 << 40) || div_up(n, kBlock) > 0x7fffffffu) return -1;  // more keys than leaves, or than one launch holds
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (tree_->device >= 0 && tree_->device != dev) return -1;
+    (void)hipGetLastError();
+    PwMemoryTree* tree = const_cast<PwMemoryTree*>(tree_);  // (Z_0 .. Z_H go to the device with the first call that needs them, as in the update)
+    const u64* d_keys = reinterpret_cast<const u64*>(d_keys_);
+    *status = 0;
+    *info = 0;
+    *n_siblings = 0;
+    hipStream_t st = stream();
+    TreeCtx& cx = g_tree;
+    PW_HIP_TRY((hipError_t)cx.small.ensure(kSmallWords * 8));
+    if (!tree->zbuf.p) {
+        PW_HIP_TRY((hipError_t)tree->zbuf.ensure((size_t)(H + 1) * 32));
+        PW_HIP_TRY(hipMemcpyAsync(tree->zbuf.p, tree->zero, (size_t)(H + 1) * 32, hipMemcpyHostToDevice, st));
+        tree->device = dev;
+    }
+    // one scratch buffer, freed on every path: the scan's temporary storage | the ranks | the flags (the first two at 256-byte offsets,
+    // the alignment of an allocation: rocPRIM lays its look-back state out from the start of what it is given)
+    const FlagToCount to_u64{};
+    DeviceBuf scratch;
+    size_t temp_bytes = 0;
+    const size_t rank_bytes = (size_t)(lanes + 1) * 8;
+    {
+        const auto none = rocprim::make_transform_iterator((const uint8_t*)nullptr, to_u64);
+        PW_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, none, (u64*)nullptr, 0ull, (size_t)(lanes + 1), rocprim::plus<u64>(), st));
+    }
+    const size_t temp_room = (std::max<size_t>(temp_bytes, 16) + 255) & ~(size_t)255;
+    PW_HIP_TRY((hipError_t)scratch.ensure(temp_room + rank_bytes + (size_t)(lanes + 1)));
+    void* d_temp = scratch.p;
+    u64* d_rank = reinterpret_cast<u64*>(scratch.as<uint8_t>() + temp_room);
+    uint8_t* d_flags = scratch.as<uint8_t>() + temp_room + rank_bytes;
+    u64* d_err = cx.small.as<u64>() + kErr;
+    u64 err = kNoIndex, total = 0;
+    const dim3 grid(div_up(n, kBlock), H);
+    PW_HIP_TRY(hipMemcpyAsync(d_err, &err, 8, hipMemcpyHostToDevice, st));
+    {
+        ScopedKernelTimer t("memory_tree_open_flag_kernel");
+        hipLaunchKernelGGL(open_flag_kernel, grid, dim3(kBlock), 0, st, d_keys, (u64)n, (uint32_t)H, d_flags, d_err);
+    }
+    {
+        ScopedKernelTimer t("memory_tree_open_scan");
+        PW_HIP_TRY(rocprim::exclusive_scan(d_temp, temp_bytes, rocprim::make_transform_iterator((const uint8_t*)d_flags, to_u64), d_rank, 0ull, (size_t)(lanes + 1),
+                                           rocprim::plus<u64>(), st));
+    }
+    PW_HIP_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipMemcpyAsync(&total, d_rank + lanes, 8, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    if (err != kNoIndex) { *status = 4; *info = err; return 0; }
+    if (total > lanes) return -1;
+    *n_siblings = total;
+    if (total > cap_siblings) { *status = 1; return 0; }
+    OpenArgs a{};
+    for (int l = 0; l < H; ++l) a.lv[l] = tree->data.lv[l];
+    a.payload = tree->data.payload;
+    a.zero = tree->zbuf.as<uint32_t>();
+    {
+        ScopedKernelTimer t("memory_tree_open_gather_kernel");
+        hipLaunchKernelGGL(open_gather_kernel, grid, dim3(kBlock), 0, st, a, d_keys, (u64)n, (const uint8_t*)d_flags, (const u64*)d_rank, d_payloads, d_siblings);
+    }
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    return (int)hipGetLastError();
 }
 
 extern "C" int pw_memory_tree_boundary_leaves(const uint32_t* d_boundary_trace, uint32_t log_height, uint64_t n_locations, uint64_t* d_keys, uint32_t* d_init,

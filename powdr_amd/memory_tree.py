@@ -11,10 +11,17 @@ from the memory the last one left, and the opened paths as (left, right, out) ro
                           are paths of ONE tree before and ONE tree after, whose roots are its 16 public values MERKLE_PUBLIC
   merkle_trace            pw_memory_merkle_trace: its 55-column trace on the device from the records and node ids of one update
   memory_links            the links of prover.verify_segment_chain that make one segment's root_after the next one's root_before
+  MemoryTree.open         pw_memory_tree_open: the payloads of a set of keys (zero: not stored) and the minimal sibling
+                          digests that tie them to the root, read-only
+  verify_opening          pw_memory_opening_verify: such an opening against a root, on the host
 
-system_airs.close_segment(..., memory_tree=tree) puts them into a segment. What remains open: the leaves are tied to the boundary AIR's
-init / fin words of THIS segment only through the leaf bus — access adapters, a user public-values chip and a segment that touches no
-memory at all (no root row) are not covered.
+system_airs.close_segment(..., memory_tree=tree) puts them into a segment. The program's outputs are read out of a chain's statement by
+an opening: open the output keys on the tree after the last segment and verify them against root_after as the LAST segment proof
+states it (prover.segment_public_values); the initial image is spot-checked the same way against the first root_before. That is what
+stands where a user public-values chip would: an opening is a statement about a root, and that the root is the execution's final
+memory comes from the chain verifier. Access adapters are moot here (every memory-bus tuple is one 4-word block, a leaf one such block
+padded to 8 words). What remains open: a segment that touches no memory at all (no root row), public values inside interaction
+programs, and which tree mode to make the default.
 """
 from __future__ import annotations
 
@@ -49,6 +56,12 @@ lib.pw_memory_tree_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_vo
 lib.pw_memory_tree_boundary_leaves.restype = C.c_int
 lib.pw_memory_tree_boundary_leaves.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 
+lib.pw_memory_tree_open.restype = C.c_int
+lib.pw_memory_tree_open.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint64)]
+lib.pw_memory_opening_verify.restype = C.c_int
+lib.pw_memory_opening_verify.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+
 lib.pw_memory_tree_set_mode.restype = C.c_int
 lib.pw_memory_tree_set_mode.argtypes = [C.c_void_p, C.c_uint32]
 lib.pw_memory_tree_get_mode.restype = C.c_int
@@ -64,6 +77,13 @@ RECORD_WIDTH = 25
 RECORD_COLUMNS = ["valid"] + [f"left{i}" for i in range(8)] + [f"right{i}" for i in range(8)] + [f"out{i}" for i in range(8)]
 STATUS = {0: "updated", 1: "cap_log_height too small", 3: "init is not what the tree holds", 4: "keys not strictly increasing or out of range",
           5: "a payload word that is no field element"}
+OPEN_STATUS = {0: "opened", 1: "cap_siblings too small", 4: "keys not strictly increasing or out of range"}
+OPENING_CODES = {0: "the opening hashes to the root", 19: "malformed opening", 20: "the opening hashes to another root"}
+_R_INV = pow(1 << 32, -1, 0x78000001)
+
+
+def _from_monty(words: np.ndarray) -> np.ndarray:
+    return ((words.astype(np.uint64) * np.uint64(_R_INV)) % np.uint64(0x78000001)).astype(np.uint32)
 
 
 def _keys(keys) -> torch.Tensor:
@@ -171,6 +191,52 @@ class MemoryTree:
             if node_ids:
                 trace = (trace, ids[:int(rows.value)])
         return int(status.value), int(info.value), trace, int(lh.value), int(rows.value)
+
+
+    def open(self, keys, cap_siblings: int | None = None, device: bool = False):
+        """pw_memory_tree_open, read-only: the multi-opening of `keys` -> (status, info, payloads, siblings): status a key of OPEN_STATUS,
+        info the first offending index (4); payloads [n, 8] = what the tree holds for every key (zeros: not stored) and siblings [m, 8] =
+        the digests verify_opening consumes, by level and inside a level by index — canonical numpy uint32, None with a non-zero
+        status. Status 1 is retried once with the count the library asked for (the rule of update). device=True: the two arrays stay on
+        the device as int32 tensors of Montgomery words (siblings a view of the first m rows of the buffer)."""
+        k = _keys(keys)
+        n = k.numel()
+        cap = int(cap_siblings) if cap_siblings is not None else min(n * self.height, max(1024, 4 * n))
+        payloads = torch.empty((max(n, 1), 8), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        for _ in range(2):
+            siblings = torch.empty((max(cap, 1), 8), dtype=torch.int32, device="cuda")
+            m, status, info = C.c_uint64(), C.c_uint32(), C.c_uint64()
+            abi.check(lib.pw_memory_tree_open(self._h, k.data_ptr(), n, payloads.data_ptr(), siblings.data_ptr(), cap, C.byref(m), C.byref(status), C.byref(info)),
+                      "pw_memory_tree_open")
+            if status.value != 1 or cap_siblings is not None:
+                break
+            cap = int(m.value)
+        if status.value != 0:
+            return int(status.value), int(info.value), None, None
+        siblings = siblings[:int(m.value)]
+        if device:
+            return 0, 0, payloads, siblings
+        host = lambda t: _from_monty(t.cpu().numpy().view(np.uint32))
+        return 0, 0, host(payloads), host(siblings)
+
+
+def verify_opening(height: int, root, keys, payloads, siblings):
+    """pw_memory_opening_verify (host only, the installed Poseidon2 table): does the opening — keys, their [n, 8] payloads and the [m, 8]
+    siblings of MemoryTree.open, canonical words — hash to `root` (8 canonical words) in a tree of `height`? -> (code, where): code a
+    key of OPENING_CODES; where: with 19 the index of the first bad key, or of the first word >= p in its array (root, payloads,
+    siblings in this order), or — none of those — the number of siblings the keys imply. It proves what the tree with this root holds
+    at these keys (the zero payload: nothing), not where the root comes from: that is prover.verify_segment_chain's statement."""
+    r = np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    p = np.ascontiguousarray(payloads, dtype=np.uint32).reshape(-1)
+    s = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(-1)
+    if r.size != 8 or p.size != 8 * k.size or s.size % 8:
+        raise ValueError("an opening is 8 root words, n keys, n x 8 payload words and m x 8 sibling words")
+    where = C.c_size_t()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    code = lib.pw_memory_opening_verify(int(height), ptr(r), ptr(k), ptr(p), k.size, ptr(s), s.size // 8, C.byref(where))
+    return int(code), int(where.value)
 
 
 def boundary_leaves(trace: torch.Tensor, log_h: int, n_locations: int):

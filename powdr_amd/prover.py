@@ -28,7 +28,7 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_poseidon2_compress_trace",
                   "pw_memory_tree_create", "pw_memory_tree_destroy", "pw_memory_tree_root", "pw_memory_tree_stats", "pw_memory_tree_update",
                   "pw_memory_tree_boundary_leaves", "pw_memory_tree_set_mode", "pw_memory_tree_get_mode",
-                  "pw_memory_merkle_trace"]
+                  "pw_memory_merkle_trace", "pw_memory_tree_open", "pw_memory_opening_verify"]
 
 lib.pw_prover_create.restype = C.c_void_p
 lib.pw_prover_create.argtypes = [C.POINTER(PwStarkConfig), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]

@@ -452,6 +452,13 @@ extern "C" {
     /// keys and payloads of the rows of a memory boundary trace
     pub fn pw_memory_tree_boundary_leaves(d_boundary_trace: *const u32, log_height: u32, n_locations: u64, d_keys: *mut u64,
                                           d_init: *mut u32, d_fin: *mut u32) -> c_int;
+    /// the multi-opening of `n` leaves, read-only: payloads (`n` x 8, zero where a key is not stored) and the minimal sibling digests, by
+    /// level and index; `status` 0 = written, 1 = `cap_siblings` too small (`n_siblings` is set), 4 = malformed keys (`info` = the index)
+    pub fn pw_memory_tree_open(tree: *const PwMemoryTree, d_keys: *const u64, n: usize, d_payloads: *mut u32, d_siblings: *mut u32,
+                               cap_siblings: u64, n_siblings: *mut u64, status: *mut u32, info: *mut u64) -> c_int;
+    /// host only: 0 = the opening (canonical words) hashes to `root`, 19 = malformed (`where_`: the first bad key or word), 20 = another root
+    pub fn pw_memory_opening_verify(height: u32, root: *const u32, keys: *const u64, payloads: *const u32, n: usize, siblings: *const u32,
+                                    m: usize, where_: *mut usize) -> c_int;
     /// the memory Merkle AIR's trace (55 columns, one row per touched node, the root first) from the records and node ids of one
     /// `pw_memory_tree_update`; `status` 0 = written, 1 = `cap_log_height` too small, 2 = no rows, 3 = the ids are not a records set
     pub fn pw_memory_merkle_trace(d_records: *const u32, records_log_height: u32, d_node_ids: *const u64, n_rows: u64, height: u32,
