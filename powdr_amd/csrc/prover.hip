@@ -572,13 +572,6 @@ int commit_trace(PwProver* p, const CommitLayout& L, const uint32_t* d_trace, ui
 }
 
 
-// Every device buffer a proof of a 2^log_h-row trace needs (grown on demand; pw_prover_reserve calls this at set-up
-// time so that the first proof does not pay for tens of gigabytes of hipMalloc).
-int ensure_prove_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bool consume = false) {
-    BufferPlan B;
-    plan_buffers(p, log_h, b, L, B, consume);
-    return apply_buffers(p, B);
-}
 }  // namespace
 
 namespace pw {
@@ -588,8 +581,12 @@ size_t proof_plan_bytes(const PwProver* p, uint32_t log_h, int b, bool consume) 
     plan_buffers(p, log_h, b, L, B, consume && b > 0);
     return B.total();
 }
+// Every device buffer a proof of a 2^log_h-row trace needs (grown on demand; pw_prover_reserve calls this at set-up
+// time so that the first proof does not pay for tens of gigabytes of hipMalloc).
 int ensure_proof_buffers(PwProver* p, uint32_t log_h, int b, CommitLayout& L, bool consume) {
-    return ensure_prove_buffers(p, log_h, b, L, consume && b > 0);
+    BufferPlan B;
+    plan_buffers(p, log_h, b, L, B, consume && b > 0);
+    return apply_buffers(p, B);
 }
 }  // namespace pw
 
@@ -652,9 +649,7 @@ static PwProver::OpenedMailbox* opened_mailbox(PwProver* p, size_t K) {
 
 extern "C" void pw_prover_destroy(PwProver* p) {
     if (!p) return;
-    for (DeviceBuf* b : {&p->coef, &p->lde, &p->digests, &p->q, &p->qcoef, &p->qlde, &p->ext_arena, &p->misc, &p->perm, &p->plde, &p->qpart, &p->tcoef,
-                         &p->fscale, &p->gbuf, &p->pre_vals, &p->pre_lde, &p->pre_tree, &p->row_vals, &p->bus_order})
-        b->release();
+    for_each_buffer(p, [](DeviceBuf& b) { b.release(); });
     if (p->d_next_cols) (void)hipFree(p->d_next_cols);
     if (p->d_pub) (void)hipFree(p->d_pub);
     for (void* q : {(void*)p->d_inter, (void*)p->d_ixspans, (void*)p->d_icode, (void*)p->d_gstarts, (void*)p->d_iforms}) if (q) (void)hipFree(q);
@@ -676,7 +671,7 @@ extern "C" int pw_prover_reserve(PwProver* p, uint32_t log_h) {
     (void)specialise_provers(&p, 1, &log_h, false);
     const int sb = stream_log_blocks(p, log_h);
     if (sb < 0) return (int)hipErrorOutOfMemory;
-    return ensure_prove_buffers(p, log_h, sb, L);
+    return ensure_proof_buffers(p, log_h, sb, L);
 }
 
 // 0: the last reservation / proof of a 2^log_height-row trace would keep the LDE resident; b >= 1: it is streamed over 2^b sub-cosets
@@ -687,9 +682,9 @@ extern "C" int pw_prover_stream_log_blocks(const PwProver* p, uint32_t log_h) {
 }
 
 extern "C" size_t pw_prover_device_bytes(const PwProver* p) {
-    return p->coef.bytes + p->lde.bytes + p->digests.bytes + p->q.bytes + p->qcoef.bytes + p->qlde.bytes +
-           p->ext_arena.bytes + p->misc.bytes + p->perm.bytes + p->plde.bytes + p->qpart.bytes + p->tcoef.bytes + p->fscale.bytes + p->gbuf.bytes +
-           p->pre_vals.bytes + p->pre_lde.bytes + p->pre_tree.bytes + p->row_vals.bytes + p->bus_order.bytes;
+    size_t held = 0;
+    for_each_buffer(p, [&](const DeviceBuf& b) { held += b.bytes; });
+    return held;
 }
 
 
@@ -719,7 +714,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     int sb = have_commitment ? p->committed_b : stream_log_blocks(p, log_h, consume);
     if (sb < 0) return (int)hipErrorOutOfMemory;
     CommitLayout L;
-    int rc_buf = ensure_prove_buffers(p, log_h, sb, L, consume && sb > 0);
+    int rc_buf = ensure_proof_buffers(p, log_h, sb, L, consume);
     if (rc_buf == (int)hipErrorOutOfMemory && have_commitment && sb == 0) {
         // pw_prove_airs commits every AIR first: several of them may each have chosen "resident" against the same free memory
         // (ADVICE r4). The commitment is dropped and made again in the streamed mode that fits NOW — same root, same words.
@@ -728,7 +723,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         have_commitment = false;
         sb = stream_log_blocks(p, log_h, false);
         if (sb <= 0) return (int)hipErrorOutOfMemory;
-        rc_buf = ensure_prove_buffers(p, log_h, sb, L, false);
+        rc_buf = ensure_proof_buffers(p, log_h, sb, L, false);
     }
     if (rc_buf) return rc_buf;
     const AirMode mode{sb, consume && sb > 0};
@@ -757,19 +752,11 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     // trace values | coefficient arrays | alpha, beta powers | weights at zeta, at g zeta (LogUp) | per-row sums, block totals (LogUp) | scratch
     const AirBufs bufs{d_trace, d_trace, d_tcoef, d_apow, d_blpow, d_weights, d_weights + H, d_weights + 2 * H, d_scratch};
 
-    std::vector<uint32_t>& pf = p->proof;
-    pf.clear();
-    auto put = [&](uint32_t canonical) { pf.push_back(canonical); };
-    auto put_monty = [&](const uint32_t* w, size_t n) { for (size_t i = 0; i < n; ++i) pf.push_back(bb::from_monty(w[i])); };
-
-    Challenger ch;
-    if (lg) {
-        for (uint32_t x : {kMagic2 % bb::P, log_h, W, nc, n_int, p->cfg.num_queries, p->cfg.pow_bits}) ch.observe_canonical(x);
-        for (uint32_t x : {kMagic2, log_h, W, nc, n_int, p->cfg.num_queries, p->cfg.pow_bits}) put(x);
-    } else {
-        for (uint32_t x : {kMagic % bb::P, log_h, W, nc, p->cfg.num_queries, p->cfg.pow_bits}) ch.observe_canonical(x);
-        for (uint32_t x : {kMagic, log_h, W, nc, p->cfg.num_queries, p->cfg.pow_bits}) put(x);
-    }
+    ProofSink pf(p->proof);
+    Challenger& ch = pf.ch;
+    for (uint32_t x : {lg ? kMagic2 : kMagic, log_h, W, nc}) pf.word(x);
+    if (lg) pf.word(n_int);
+    for (uint32_t x : {p->cfg.num_queries, p->cfg.pow_bits}) pf.word(x);
 
     // ---- 1. trace: coefficients, LDE, commitment ---------------------------------------------
     uint32_t root[8];
@@ -783,8 +770,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         PW_HIP_TRY(hipMemcpyAsync(root, p->digests.as<uint32_t>() + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
     } else TRY(commit_trace(p, L, d_trace, log_h, root));
-    put_monty(root, 8);
-    ch.observe_words(root, 8);
+    pf.root(root);
 
     // ---- 1b. LogUp: permutation trace, its LDE and commitment ---------------------------------------
     bb::Ext al = bb::ext_zero(), S = bb::ext_zero();
@@ -793,8 +779,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         // a lone AIR uses its own trace root), see oracle/stark_oracle.cpp bus_challenges
         uint32_t seed[8];
         memcpy(seed, p->has_bus_seed ? p->bus_seed : root, 32);
-        put_monty(seed, 8);
-        ch.observe_words(seed, 8);
+        pf.root(seed);
         Challenger cb;
         cb.observe_canonical(kMagic2 % bb::P);
         cb.observe_words(seed, 8);
@@ -812,11 +797,9 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
         PW_HIP_TRY(hipMemcpyAsync(root, d_pdig + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
         for (int k = 0; k < 4; ++k) PW_HIP_TRY(hipMemcpyAsync(&sw[k], s_words[k], 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
-        put_monty(root, 8);
-        ch.observe_words(root, 8);
+        pf.root(root);
         for (int k = 0; k < 4; ++k) S.c[k] = sw[k];
-        put_monty(S.c, 4);
-        ch.observe_ext(S);
+        pf.ext(S);
     }
 
     // ---- 2. quotient ---------------------------------------------------------------------------
@@ -832,8 +815,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
     TRY(merkle_commit_matrix(d_qlde, N, 8, N, d_qdig));
     PW_HIP_TRY(hipMemcpyAsync(root, d_qdig + tree_words - 8, 32, hipMemcpyDeviceToHost, st));
     PW_HIP_TRY(hipStreamSynchronize(st));
-    put_monty(root, 8);
-    ch.observe_words(root, 8);
+    pf.root(root);
 
     // ---- 3. openings at zeta -------------------------------------------------------------------
     const bb::Ext zeta = ch.sample_ext();
@@ -872,7 +854,7 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
             ++waited;
             return 0;
         };
-        auto emit = [&](size_t a, size_t b) { for (size_t k = a; k < b; ++k) { put_monty(opened[k].c, 4); ch.observe_ext(opened[k]); } };
+        auto emit = [&](size_t a, size_t b) { for (size_t k = a; k < b; ++k) pf.ext(opened[k]); };
         TRY(wait());
         emit(0, W);
         if (lg)
@@ -900,28 +882,12 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
 
     // ---- 5. FRI commit phase --------------------------------------------------------------------
     const FriLayout fri(logN);
-    const std::vector<size_t>& layer_off = fri.layer_off;
-    uint32_t shift = bb::to_monty(field::kCosetShift);
-    for (uint32_t l = 0; l < log_h; ++l) {
-        const size_t half = (N >> l) / 2;
-        bb::Ext* v = d_v + layer_off[l];
-        TRY(fri_commit_round(v, half, d_fdig + fri.tree_off[l], root));
-        put_monty(root, 8);
-        ch.observe_words(root, 8);
-        const bb::Ext beta = ch.sample_ext();
-        TRY(fri_fold(v, half, logN - (int)l, shift, beta, d_v + layer_off[l + 1]));
-        shift = bb::sqr(shift);
-    }
-    bb::Ext final_poly;
-    PW_HIP_TRY(hipMemcpyAsync(&final_poly, d_v + layer_off[log_h], sizeof(bb::Ext), hipMemcpyDeviceToHost, st));
-    PW_HIP_TRY(hipStreamSynchronize(st));
-    put_monty(final_poly.c, 4);
-    ch.observe_ext(final_poly);
+    TRY(fri_commit_phase(pf, fri, logN, d_v, d_fdig, bb::to_monty(field::kCosetShift), no_roll_in));  // the coset's shift, squared from round to round
 
     // ---- 6. proof of work ------------------------------------------------------------------------
     uint32_t witness = 0;
     TRY(grind(ch, p->cfg.pow_bits, reinterpret_cast<uint32_t*>(d_tail), &witness));
-    put(witness);
+    pf.put(witness);
 
     // ---- 7. queries --------------------------------------------------------------------------------
     if (nq) {
@@ -948,13 +914,9 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
             fri_query_offsets(i, logN, fri, n_trees * tree_words, ext_offs, dig_offs);
         }
         const size_t n_dig = dig_offs.size(), n_ext = ext_offs.size();
-        uint64_t* d_dig_offs = d_offs;
-        uint64_t* d_ext_offs = d_offs + n_dig;
-        uint32_t* d_dig_out = reinterpret_cast<uint32_t*>(d_ext_offs + n_ext);
+        uint32_t* d_dig_out = reinterpret_cast<uint32_t*>(d_offs + n_dig + n_ext);  // behind the offsets themselves
         uint32_t* d_ext_out = d_dig_out + n_dig * 8;
         PW_HIP_TRY(hipMemcpyAsync(d_idx, idx.data(), nq * 4, hipMemcpyHostToDevice, st));
-        PW_HIP_TRY(hipMemcpyAsync(d_dig_offs, dig_offs.data(), n_dig * 8, hipMemcpyHostToDevice, st));
-        if (n_ext) PW_HIP_TRY(hipMemcpyAsync(d_ext_offs, ext_offs.data(), n_ext * 8, hipMemcpyHostToDevice, st));
         if (!sb) {
             TRY(gather_rows(d_lde, N, W, d_idx, nq, d_trows));
             if (lg) TRY(gather_rows(d_plde, N, Wp, d_idx, nq, d_prows));
@@ -966,41 +928,30 @@ int prove_impl(PwProver* p, const uint32_t* d_trace, uint32_t log_h, const uint3
             if (lg) TRY(streamed::query_rows(sc, d_perm, Wp, idx.data(), nq, d_loc, d_qrows, d_prows));
         }
         TRY(gather_rows(d_qlde, N, 8, d_idx, nq, d_qrows));
-        TRY(gather_records(d_dig, d_dig_offs, 8u, (uint32_t)n_dig, d_dig_out));
-        TRY(gather_records(reinterpret_cast<const uint32_t*>(d_v), d_ext_offs, 4u, (uint32_t)n_ext, d_ext_out));
-        // the answers leave the device as canonical words (d_trows .. d_qrows are contiguous)
+        // the answers leave the device as canonical words (d_trows .. d_qrows are contiguous); the rows' copies end with the digests'
         TRY(canonicalize_words(d_trows, (size_t)nq * K1));
-        TRY(canonicalize_words(d_dig_out, n_dig * 8));
-        TRY(canonicalize_words(d_ext_out, n_ext * 4));
-        std::vector<uint32_t> trows((size_t)nq * W), prows((size_t)nq * Wp + 1), qrows((size_t)nq * 8), dig(n_dig * 8), ext(n_ext * 4 + 1);
+        std::vector<uint32_t> trows((size_t)nq * W), prows((size_t)nq * Wp + 1), qrows((size_t)nq * 8), dig, ext;
         PW_HIP_TRY(hipMemcpyAsync(trows.data(), d_trows, trows.size() * 4, hipMemcpyDeviceToHost, st));
         if (lg) PW_HIP_TRY(hipMemcpyAsync(prows.data(), d_prows, (size_t)nq * Wp * 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipMemcpyAsync(qrows.data(), d_qrows, qrows.size() * 4, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipMemcpyAsync(dig.data(), d_dig_out, n_dig * 32, hipMemcpyDeviceToHost, st));
-        if (n_ext) PW_HIP_TRY(hipMemcpyAsync(ext.data(), d_ext_out, n_ext * 16, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-        auto put_raw = [&](const uint32_t* w, size_t n) { pf.insert(pf.end(), w, w + n); };
-        pf.reserve(pf.size() + nq + trows.size() + prows.size() + qrows.size() + dig.size() + ext.size());
+        TRY(fetch_query_answers(d_dig, d_v, dig_offs, ext_offs, d_offs, d_dig_out, d_ext_out, 0, [] { return 0; }, dig, ext));
+        pf.words.reserve(pf.words.size() + nq + trows.size() + prows.size() + qrows.size() + dig.size() + ext.size());
         size_t dpos = 0, epos = 0;
         for (uint32_t qi = 0; qi < nq; ++qi) {
-            put(idx[qi]);
-            put_raw(&trows[(size_t)qi * W], W);
-            put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
+            pf.put(idx[qi]);
+            pf.put_raw(&trows[(size_t)qi * W], W);
+            pf.put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
             if (lg) {
-                put_raw(&prows[(size_t)qi * Wp], Wp);
-                put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
+                pf.put_raw(&prows[(size_t)qi * Wp], Wp);
+                pf.put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
             }
-            put_raw(&qrows[(size_t)qi * 8], 8);
-            put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
-            for (uint32_t l = 0; l < log_h; ++l) {
-                put_raw(&ext[epos * 4], 4); epos += 1;
-                const size_t depth = (size_t)logN - 1 - l;
-                put_raw(&dig[dpos * 8], depth * 8); dpos += depth;
-            }
+            pf.put_raw(&qrows[(size_t)qi * 8], 8);
+            pf.put_raw(&dig[dpos * 8], (size_t)logN * 8); dpos += logN;
+            put_fri_answer(pf, logN, dig, ext, dpos, epos);
         }
     }
-    *proof_words = pf.data();
-    *n_words = pf.size();
+    *proof_words = pf.words.data();
+    *n_words = pf.words.size();
     return (int)hipGetLastError();
 }
 }  // namespace

@@ -177,7 +177,7 @@ int quotient_unit_jit(PwProver* p, uint32_t u, const uint32_t* T, const uint32_t
 }
 
 int quotient_eval_jit(PwProver* p, const uint32_t* lde, size_t N, const bb::Ext* d_apow, uint32_t zinv_even, uint32_t zinv_odd, uint32_t* q) {
-    PW_TRY_INT(p->qpart.ensure(jit_part_bytes(p, N / 2, N)));  // (reserved by ensure_prove_buffers; a no-op then)
+    PW_TRY_INT(p->qpart.ensure(jit_part_bytes(p, N / 2, N)));  // (reserved by ensure_proof_buffers; a no-op then)
     uint32_t* part = p->qpart.as<uint32_t>();
     uint32_t n_chunks = 0;
     PW_TRY_INT(quotient_parts_jit(p, lde, nullptr, N, d_apow, bb::ext_zero(), nullptr, part, &n_chunks));
@@ -199,7 +199,7 @@ int logup_perm_trace_jit(PwProver* p, const uint32_t* trace, size_t H, bb::Ext a
                          bb::Ext* d_block_totals) {
     const jit::Generated& g = p->jit.perm;
     const uint32_t G = p->n_groups;
-    PW_TRY_INT(p->qpart.ensure((size_t)(g.n_chunks ? g.n_chunks : 1) * 4 * H * 4));  // (a no-op after ensure_prove_buffers / ensure_air)
+    PW_TRY_INT(p->qpart.ensure((size_t)(g.n_chunks ? g.n_chunks : 1) * 4 * H * 4));  // (a no-op after ensure_proof_buffers / ensure_air)
     uint32_t* part = p->qpart.as<uint32_t>();
     uint64_t h64 = H;
     void* args[] = {(void*)&trace, (void*)&h64, (void*)&al, (void*)&d_blpow, (void*)&perm, (void*)&part};

@@ -1,11 +1,13 @@
 // What is done to ONE AIR between two commitments, shared by the one-AIR prover (prover.hip: pw-stark v0) and the segment prover
 // (segment_prover.hip: v1): the shape numbers, the plan of the per-AIR stage buffers, and the stages themselves — LogUp permutation
-// matrix, quotient, openings, DEEP numerator, one FRI commit round, proof of work, the FRI part of a query answer. The two protocols
-// differ in how commitments, the transcript, the FRI fold and the query answers are laid out: that stays with the callers. What they
+// matrix, quotient, openings, DEEP numerator, proof of work — and what the two protocols do alike around them: the proof sink (words +
+// transcript), the FRI commit phase, fetching the query answers and emitting their FRI part. The protocols differ in the header, in how
+// commitments and the trees' query answers are laid out, and in what FRI folds (a shifted coset; unshifted subgroups with the smaller
+// heights rolled in): that stays with the callers. What they
 // place differently (trace values, coefficient arrays, power tables, weights, scratch, outputs) comes in as pointers; the stage
 // buffers proper are the prover object's (perm, plde, q, qpart, qcoef, qlde, gbuf; lde for the resident LDE or one sub-coset).
 // Every stage enqueues on pw::stream() as it is at the time of the call (the segment prover moves it from AIR to AIR) and none
-// synchronises with the host. The streamed arms are prover_stream.hpp's. Not part of the C ABI.
+// synchronises with the host (the FRI commit phase and fetch_query_answers do, and say so). The streamed arms are prover_stream.hpp's. Not part of the C ABI.
 #pragma once
 #include "prover_stream.hpp"
 #include "logup_groups.hpp"
@@ -127,16 +129,43 @@ inline void plan_stage_buffers(const PwProver* p, const AirShape& s, AirMode m, 
     B.qlde = 8 * N * 4;
 }
 
+// Every device buffer of a prover object, listed ONCE: the planned ones with their entry of the plan, then those made outside a
+// proof's plan (preprocessed columns, the mock provers' row values and bus order). apply_plan, pw_prover_destroy and
+// pw_prover_device_bytes all walk these two tables.
+constexpr struct { DeviceBuf PwProver::*buf; size_t BufferPlan::*bytes; } kPlannedBuffers[] = {
+    {&PwProver::coef, &BufferPlan::coef}, {&PwProver::lde, &BufferPlan::lde}, {&PwProver::digests, &BufferPlan::digests},
+    {&PwProver::tcoef, &BufferPlan::tcoef}, {&PwProver::fscale, &BufferPlan::fscale}, {&PwProver::perm, &BufferPlan::perm},
+    {&PwProver::plde, &BufferPlan::plde}, {&PwProver::q, &BufferPlan::q}, {&PwProver::qpart, &BufferPlan::qpart},
+    {&PwProver::qcoef, &BufferPlan::qcoef}, {&PwProver::qlde, &BufferPlan::qlde}, {&PwProver::ext_arena, &BufferPlan::ext_arena},
+    {&PwProver::misc, &BufferPlan::misc}, {&PwProver::gbuf, &BufferPlan::gbuf}};
+constexpr DeviceBuf PwProver::*kUnplannedBuffers[] = {&PwProver::pre_vals, &PwProver::pre_lde, &PwProver::pre_tree, &PwProver::row_vals,
+                                                      &PwProver::bus_order};
+template <class P, class F>
+inline void for_each_buffer(P* p, F&& f) {
+    for (const auto& e : kPlannedBuffers) f(p->*e.buf);
+    for (const auto m : kUnplannedBuffers) f(p->*m);
+}
+
 // grows the prover's buffers to a plan (nothing shrinks; a zero entry is a buffer the plan does not use)
 inline int apply_plan(PwProver* p, const BufferPlan& B) {
-    const struct { DeviceBuf* buf; size_t bytes; } all[] = {
-        {&p->coef, B.coef}, {&p->lde, B.lde}, {&p->digests, B.digests}, {&p->tcoef, B.tcoef}, {&p->fscale, B.fscale}, {&p->perm, B.perm},
-        {&p->plde, B.plde}, {&p->q, B.q}, {&p->qpart, B.qpart}, {&p->qcoef, B.qcoef}, {&p->qlde, B.qlde}, {&p->ext_arena, B.ext_arena},
-        {&p->misc, B.misc}, {&p->gbuf, B.gbuf}};
-    for (const auto& e : all)
-        if (e.bytes) PW_STRY(e.buf->ensure(e.bytes));
+    for (const auto& e : kPlannedBuffers)
+        if (B.*e.bytes) PW_STRY((p->*e.buf).ensure(B.*e.bytes));
     return 0;
 }
+
+// ---- the proof sink ------------------------------------------------------------------------------------------------------------
+// The proof's words and the transcript that sees them, together: what a proof writes is observed in the same call.
+struct ProofSink {
+    std::vector<uint32_t>& words;
+    Challenger ch;
+    explicit ProofSink(std::vector<uint32_t>& w) : words(w) { words.clear(); }
+    void put(uint32_t canonical) { words.push_back(canonical); }  // written, not observed (the witness, a query index)
+    void put_monty(const uint32_t* w, size_t n) { for (size_t i = 0; i < n; ++i) words.push_back(bb::from_monty(w[i])); }
+    void put_raw(const uint32_t* w, size_t n) { words.insert(words.end(), w, w + n); }  // answers: canonical already
+    void word(uint32_t x) { ch.observe_canonical(x % bb::P); put(x); }  // a header word
+    void root(const uint32_t* r8) { put_monty(r8, 8); ch.observe_words(r8, 8); }  // a Merkle root (Montgomery)
+    void ext(const bb::Ext& e) { put_monty(e.c, 4); ch.observe_ext(e); }
+};
 
 // ---- the stages --------------------------------------------------------------------------------------------------------------
 // What the two provers place differently. Unused entries may be null (tcoef when resident, blpow / weights2 / rowsum without LogUp).
@@ -349,6 +378,67 @@ inline void fri_query_offsets(size_t q, int logN, const FriLayout& F, size_t fri
         const size_t leaf = pp & (half - 1);
         for (int lv = 0; lv < logN - 1 - l; ++lv)
             dig_offs.push_back(fri_base + F.tree_off[l] + merkle_level_offset(half, lv) + (((leaf >> lv) ^ 1) * 8));
+    }
+}
+
+// The FRI commit phase over the layers at d_v (F's offsets), trees into d_fdig: per round the tree of the layer, its root into the
+// proof, the challenge, the fold — with `shift` squared from round to round (R_MOD_P: the unshifted subgroups, which stay so) —
+// and roll_in(l, beta, next layer, its length) for what the caller adds to the folded layer; then the final polynomial.
+template <class RollIn>
+inline int fri_commit_phase(ProofSink& pf, const FriLayout& F, int logN, bb::Ext* d_v, uint32_t* d_fdig, uint32_t shift, RollIn&& roll_in) {
+    const size_t N = (size_t)1 << logN;
+    uint32_t root[8];
+    for (int l = 0; l + 1 < logN; ++l) {
+        const size_t half = (N >> l) / 2;
+        bb::Ext* v = d_v + F.layer_off[l];
+        bb::Ext* nv = d_v + F.layer_off[l + 1];
+        PW_STRY(fri_commit_round(v, half, d_fdig + F.tree_off[l], root));
+        pf.root(root);
+        const bb::Ext beta = pf.ch.sample_ext();
+        PW_STRY(fri_fold(v, half, logN - l, shift, beta, nv));
+        PW_STRY(roll_in(l, beta, nv, half));
+        shift = bb::sqr(shift);
+    }
+    bb::Ext final_poly;
+    PW_HIP_TRY(hipMemcpyAsync(&final_poly, d_v + F.layer_off[logN - 1], sizeof(bb::Ext), hipMemcpyDeviceToHost, stream()));
+    PW_HIP_TRY(hipStreamSynchronize(stream()));
+    pf.ext(final_poly);
+    return 0;
+}
+inline int no_roll_in(int, const bb::Ext&, bb::Ext*, size_t) { return 0; }
+
+// The query answers that are digests and FRI siblings, to the host as canonical words: the offsets go up to d_offs (digest offsets,
+// then ext offsets), the records are gathered from the digest arena and the layer arena into d_dig_out / d_ext_out; more_digests()
+// may gather n_more further digest records behind those; ONE synchronisation, which also ends whatever the caller enqueued before.
+template <class MoreDigests>
+inline int fetch_query_answers(const uint32_t* d_dig, const bb::Ext* d_v, const std::vector<uint64_t>& dig_offs, const std::vector<uint64_t>& ext_offs,
+                               uint64_t* d_offs, uint32_t* d_dig_out, uint32_t* d_ext_out, size_t n_more, MoreDigests&& more_digests,
+                               std::vector<uint32_t>& dig, std::vector<uint32_t>& ext) {
+    const size_t nd = dig_offs.size(), ne = ext_offs.size();
+    const hipStream_t st = stream();
+    PW_HIP_TRY(hipMemcpyAsync(d_offs, dig_offs.data(), nd * 8, hipMemcpyHostToDevice, st));
+    if (ne) PW_HIP_TRY(hipMemcpyAsync(d_offs + nd, ext_offs.data(), ne * 8, hipMemcpyHostToDevice, st));
+    PW_STRY(gather_records(d_dig, d_offs, 8u, (uint32_t)nd, d_dig_out));
+    PW_STRY(gather_records(reinterpret_cast<const uint32_t*>(d_v), d_offs + nd, 4u, (uint32_t)ne, d_ext_out));
+    PW_STRY(more_digests());
+    PW_STRY(canonicalize_words(d_dig_out, (nd + n_more) * 8));
+    PW_STRY(canonicalize_words(d_ext_out, ne * 4));
+    dig.resize((nd + n_more) * 8 + 1);
+    ext.resize(ne * 4 + 1);
+    PW_HIP_TRY(hipMemcpyAsync(dig.data(), d_dig_out, (nd + n_more) * 32, hipMemcpyDeviceToHost, st));
+    if (ne) PW_HIP_TRY(hipMemcpyAsync(ext.data(), d_ext_out, ne * 16, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the FRI part of one query's answer (fri_query_offsets' order): per round the sibling value, then the path's digests
+inline void put_fri_answer(ProofSink& pf, int logN, const std::vector<uint32_t>& dig, const std::vector<uint32_t>& ext, size_t& dpos, size_t& epos) {
+    for (int l = 0; l + 1 < logN; ++l) {
+        pf.put_raw(&ext[epos * 4], 4);
+        epos += 1;
+        const size_t depth = (size_t)logN - 1 - l;
+        pf.put_raw(&dig[dpos * 8], depth * 8);
+        dpos += depth;
     }
 }
 

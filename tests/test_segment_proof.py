@@ -372,7 +372,8 @@ def test_the_memory_policy_streams_the_largest_air_first_under_a_budget(gpu, mon
 @pytest.mark.gpu
 def test_what_a_segment_proof_holds_is_what_it_planned(gpu, monkeypatch):
     """After a segment proof on fresh provers in a fresh host thread, the device bytes its provers and the thread's segment context
-    hold are at most the planned bytes (and within the room the policy had, when the plan fits), under budgets that keep everything
+    hold are at most the planned bytes (exactly the all-resident plan when nothing is streamed; within the room the policy had, when
+    the plan fits), under budgets that keep everything
     resident, stream some AIRs or cannot be met. The device's free memory drops by at most the plan + an allowance (see below)."""
     import threading
 
@@ -424,6 +425,8 @@ def test_what_a_segment_proof_holds_is_what_it_planned(gpu, monkeypatch):
             assert (r["pf"] == want).all(), budget
             res_plan, planned, avail = r["plan"]
             assert r["held"] <= planned, (budget, r["held"], planned)
+            if not any(b for b, _ in r["modes"]):  # everything resident, fresh provers: plan and allocation are the same figures
+                assert r["held"] == res_plan, (budget, r["held"], res_plan)
             if planned <= avail:
                 assert r["held"] <= avail
             if budget:
