@@ -174,6 +174,14 @@ int powdr_field_selftest(uint64_t seed, uint32_t iterations);
 /* The same checks on the GPU (16 384 threads with different seeds; exercises the inline multiply-add instructions).
  * Returns a HIP error code; *failing_check receives 0 or the number of the first failing check. */
 int powdr_field_selftest_gpu(uint64_t seed, uint32_t iterations, int* failing_check);
+/* Both runs also check the Poseidon2 layers at the edges of their signed ranges and the whole permutation, under the table that
+ * pw_set_poseidon2_constants installed, against a plain restatement of its definition (checks 30 to 40).
+ *
+ * Read-only test hook, called by no product path: the derived tables of the installed Poseidon2 parameters (csrc/poseidon2.hpp,
+ * Params) as 64-bit integers, in this order: ext_fold 8 x 16, entry_c, part_kappa 2, part_rho 2, part_diag 2 x 16, int_fold 13,
+ * exit_fold 16 (ext_fold, entry_c and part_*: centred representatives; int_fold and exit_fold: centred representative times
+ * 2^32 mod p). Writes at most `cap` values and returns the total, 194. */
+size_t powdr_poseidon2_derived(int64_t* out, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -236,10 +236,11 @@ PW_HD int64_t swide_mul(int32_t x, int32_t k) {
     return (int64_t)x * k;
 #endif
 }
-// |y| < 64 p  ->  a representative of y mod p in (-0.017 p, 1.017 p) (for the |y| < 43 p of Poseidon2: (-0.011 p, 1.011 p)):  q = floor(floor(y / 2^7) * 273 / 2^32) with
-// 273 = floor(2^39 / p); y - q p = y (1 - 273 p / 2^39) + (rounding of the two floors, in [0, p + 273 p / 2^32)), and
-// 1 - 273 p / 2^39 = 0.000256. Three instructions: a funnel shift, a signed mul_hi and one multiply-add y + q (-p) of
-// which only the low word is kept.
+// |y| < 128 p (floor(y / 2^7) must fit an int32)  ->  a representative of y mod p in (-0.0313 p, 1.0313 p); Poseidon2's last layer
+// hands it [15.3 p, 84.7 p) and gets [0, 1.0207 p) (exact figures: p2::bounds in poseidon2.hpp, computed by tools/poseidon2_bounds.py):
+// q = floor(floor(y / 2^7) * 273 / 2^32) with 273 = floor(2^39 / p); y - q p = y (1 - 273 p / 2^39) + (rounding of the two floors,
+// in [0, p + 273 p / 2^32 + 1)), and 1 - 273 p / 2^39 = 0.000244. Three instructions: a funnel shift, a signed mul_hi and one
+// multiply-add y + q (-p) of which only the low word is kept.
 PW_HD int32_t sreduce_wide_loose(int64_t y) {
     const int32_t a = (int32_t)(y >> 7);
     const int32_t q = (int32_t)(((int64_t)a * 273) >> 32);

@@ -106,23 +106,33 @@ const char* powdr_gpu_version(void) { return "powdr_gpu-mi355x 0.1 (gfx950; Fp=B
 // ---- device run of the field self-test (field_selftest.hpp) ---------------------------------------------------
 #include "field_selftest.hpp"
 
+namespace pw { const p2::Params& poseidon2_params_host(); }  // merkle.hip: the installed table
+
 namespace {
-__global__ void field_selftest_kernel(uint64_t seed, uint32_t iterations, int* first_failure) {
+__global__ void field_selftest_kernel(uint64_t seed, uint32_t iterations, const p2::Params* params, int* first_failure) {
     const uint64_t s = seed + 0x1234567ull * (blockIdx.x * blockDim.x + threadIdx.x + 1);
-    const int rc = pw::field_selftest_checks(s, iterations);
+    const int rc = pw::field_selftest_checks(s, iterations, params);
     if (rc) atomicCAS(first_failure, 0, rc);
 }
 }  // namespace
 
 extern "C" int powdr_field_selftest_gpu(uint64_t seed, uint32_t iterations, int* failing_check) {
-    int* d = nullptr;
-    PW_HIP_TRY(hipMalloc(&d, sizeof(int)));
-    PW_HIP_TRY(hipMemsetAsync(d, 0, sizeof(int), pw::stream()));
-    hipLaunchKernelGGL(field_selftest_kernel, dim3(64), dim3(256), 0, pw::stream(), seed, iterations, d);
+    // one allocation: the failure word, then a copy of the installed Poseidon2 table (the whole-permutation checks run under it)
+    constexpr size_t kParamsOff = 64;
+    char* buf = nullptr;
+    PW_HIP_TRY(hipMalloc(&buf, kParamsOff + sizeof(p2::Params)));
+    int* d = reinterpret_cast<int*>(buf);
+    const p2::Params host_params = pw::poseidon2_params_host();
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(int), pw::stream());
+    if (e == hipSuccess) e = hipMemcpyAsync(buf + kParamsOff, &host_params, sizeof(p2::Params), hipMemcpyHostToDevice, pw::stream());
     int rc = 0;
-    hipError_t e = hipMemcpyAsync(&rc, d, sizeof(int), hipMemcpyDeviceToHost, pw::stream());
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(field_selftest_kernel, dim3(64), dim3(256), 0, pw::stream(), seed, iterations,
+                           reinterpret_cast<const p2::Params*>(buf + kParamsOff), d);
+        e = hipMemcpyAsync(&rc, d, sizeof(int), hipMemcpyDeviceToHost, pw::stream());
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(pw::stream());
-    (void)hipFree(d);
+    (void)hipFree(buf);
     if (e != hipSuccess) return (int)e;
     if (failing_check) *failing_check = rc;
     return (int)hipGetLastError();

@@ -67,5 +67,25 @@ extern "C" int powdr_small_form_eval_host(const uint32_t* postfix, uint32_t len,
     return 0;
 }
 
-// Host entry point of the field self-test (field_selftest.hpp).
-extern "C" int powdr_field_selftest(uint64_t seed, uint32_t iterations) { return pw::field_selftest_checks(seed, iterations); }
+namespace pw { const p2::Params& poseidon2_params_host(); }  // merkle.hip: the installed table
+
+// Host entry point of the field self-test (field_selftest.hpp): the whole-permutation checks run under the installed table.
+extern "C" int powdr_field_selftest(uint64_t seed, uint32_t iterations) {
+    return pw::field_selftest_checks(seed, iterations, &pw::poseidon2_params_host());
+}
+
+// Read-only test hook: the derived tables of the installed Poseidon2 parameters, in the order documented in powdr_host.h.
+extern "C" size_t powdr_poseidon2_derived(int64_t* out, size_t cap) {
+    const p2::Params& p = pw::poseidon2_params_host();
+    int64_t v[195];
+    size_t n = 0;
+    for (int r = 0; r < 8; ++r) for (int i = 0; i < 16; ++i) v[n++] = p.ext_fold[r][i];
+    v[n++] = p.entry_c;
+    for (int k = 0; k < 2; ++k) v[n++] = p.part_kappa[k];
+    for (int k = 0; k < 2; ++k) v[n++] = p.part_rho[k];
+    for (int k = 0; k < 2; ++k) for (int i = 0; i < 16; ++i) v[n++] = p.part_diag[k][i];
+    for (int r = 0; r < 13; ++r) v[n++] = p.int_fold[r];
+    for (int i = 0; i < 16; ++i) v[n++] = p.exit_fold[i];
+    for (size_t i = 0; i < n && i < cap; ++i) out[i] = v[i];
+    return n;
+}

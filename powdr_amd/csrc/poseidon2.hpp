@@ -29,6 +29,25 @@
 
 namespace p2 {
 
+// The ranges the permutation relies on, as exact integers (exclusive magnitudes unless an interval is named). They are
+// COMPUTED by tools/poseidon2_bounds.py, which reads this block and asserts every constant against its own figure; the
+// self-test (field_selftest.hpp) takes the edges it presents from here. p = 2013265921.
+namespace bounds {
+constexpr int64_t kSmontDomain = 4899916392431616000ll;  // 2^63 - 2^31 p = 1.209 p^2: bb::smont takes |t| < this
+constexpr int64_t kSreduceDomain = 257698037888ll;       // 128 p: bb::sreduce_wide_loose takes |y| < this
+constexpr int64_t kSreduceE = 134217455ll;               // 2^39 - 273 p: sreduce_wide_loose(y) = y E / 2^39 + [0, kSreduceRound)
+constexpr int64_t kSreduceRound = 2013266050ll;          // p + floor(273 p / 2^32) + 2
+constexpr int64_t kClosureWide = 191260262495ll;         // 95 p: the last layer's sum as the fixed-point closure takes it
+constexpr int32_t kLayerInTop = 2059960355;              // 1.0232 p: inputs of a layer fed by permutation inputs (what 95 p reduces to)
+constexpr int32_t kSboxOutTop = 1890224929;              // 0.9389 p: inputs of a layer fed by S-box outputs
+constexpr int64_t kExtWideTop = 87198106825ll;           // 43.3 p: a 64-bit output of a layer with constants
+constexpr int32_t kExtOutTop = 1006632981;               // 0.5000 p: its Montgomery reduction
+constexpr int32_t kLastInTop = 1419447163;               // 0.7050 p: inputs of the last layer (x^7 of a word below kExtOutTop)
+constexpr int64_t kLastWideLo = 30849986135ll;           // 40 p - 35 kLastInTop = 15.3 p: the last layer's biased sums lie in
+constexpr int64_t kLastWideHi = 170476605965ll;          // [kLastWideLo, kLastWideHi), kLastWideHi = 60 p + 35 kLastInTop = 84.7 p
+constexpr int32_t kInputTop = 2054886230;                // 1.0207 p: the last layer's outputs, and so permute's inputs, lie in [0, this)
+}  // namespace bounds
+
 struct Params {
     // the definition: canonical Montgomery words
     uint32_t ext_rc[8][16];
@@ -159,7 +178,7 @@ inline void generate_params(Params& p) {
     derive_params(p);
 }
 
-// x^7 on a signed representative, |x| < 1.09 p (the rounds deliver |x| < 1.024 p): x2 = x x, x3 = x2 x, x4 = x2 x2, x7 = x3 x4, each a signed Montgomery
+// x^7 on a signed representative, |x| < 1.09 p (the rounds deliver |x| < 1.0232 p, bounds::kLayerInTop): x2 = x x, x3 = x2 x, x4 = x2 x2, x7 = x3 x4, each a signed Montgomery
 // product (3 instructions) whose result is below p in magnitude — no conditional subtraction anywhere; |x^7| < 0.93 p.
 PW_HD int32_t sbox7(int32_t x) {
     const int32_t x2 = bb::smont(bb::smul(x, x));
@@ -174,11 +193,12 @@ PW_HD int32_t sbox7(int32_t x) {
 // multiply-add), with M4's shared partial sums: t01 = x0 + x1, t23 = x2 + x3, t = t01 + t23, ta = t + x1, tb = t + x3,
 // y0 = ta + t01, y1 = ta + 2 x2, y2 = tb + t23, y3 = tb + 2 x0 — 11 instructions per block, 13 with the constants
 // (Params::ext_fold) — then the column sums (12 + 16) and one reduction per output: a signed MONTGOMERY reduction (2
-// instructions; it divides the scale by R, see Params) in every layer but the last: 112 in all. Inputs |x| < 1.024 p: an output
-// is below 5 * (7 * 1.024 + 1.5) p = 43.3 p in magnitude and its reduction below 43 p / 2^32 + p / 2: S-box inputs.
-// BIAS (the last layer of the permutation, no constants, scale 1): the seeds are 4 p, which puts 40 p or 60 p on every
-// output — more than the sum can be negative — and the reduction is the Barrett-style sreduce_wide_loose (3 instructions,
-// keeps the scale): results in [0, 1.021 p), one conditional subtraction makes them canonical.
+// instructions; it divides the scale by R, see Params) in every layer but the last: 112 in all. Inputs |x| < 1.0232 p: an output
+// is below 5 * (7 * 1.0232 + 1.5) p = 43.3 p in magnitude and its reduction below 43.3 p / 2^32 + p / 2 = 0.5000 p: S-box inputs.
+// BIAS (the last layer of the permutation, no constants, scale 1, inputs |x| < 0.7050 p): the seeds are 4 p, which puts 40 p
+// or 60 p on every output — more than the sum (|sum| < 24.7 p) can be negative — so the biased sums lie in [15.3 p, 84.7 p),
+// inside the |y| < 128 p of the Barrett-style sreduce_wide_loose (3 instructions, keeps the scale): results in
+// [0, 1.0207 p), one conditional subtraction makes them canonical. (All figures: namespace bounds.)
 template <bool FOLD, bool BIAS>
 PW_HD void external_layer(int32_t* s, const int64_t* fold) {
     int64_t y[16];
@@ -231,9 +251,11 @@ PW_HD void internal_layer(int32_t* s, const int32_t* m, int32_t kappa, int32_t r
 // indexed by the (wave-uniform) round counter and arrive through scalar loads.
 // Round constants of the external rounds are added by the linear layer that PRECEDES the round (external_layer) or, for
 // round 4, by the last partial round.
-// Input: any representatives with -0.02 p < x < 1.021 p as int32 (canonical words qualify).
+// Input: any representatives in [0, 1.0207 p) (bounds::kInputTop) — canonical words and the words permute<true> leaves, which is
+// all a caller delivers. (The range analysis closes over the wider |x| < 1.0232 p, and the first layer is self-tested there on
+// both signs, but negative words are not part of this function's contract.)
 // SPONGE = false: canonical output. SPONGE = true: the permutation of an absorbing sponge whose output is not read — the
-// rate words are overwritten and the capacity words only enter the next permutation — leaves [0, 1.021 p).
+// rate words are overwritten and the capacity words only enter the next permutation — leaves [0, 1.0207 p).
 template <bool SPONGE = false>
 PW_HD void permute(uint32_t* words, const Params& P) {
     int32_t* s = reinterpret_cast<int32_t*>(words);

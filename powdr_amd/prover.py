@@ -714,6 +714,19 @@ def poseidon2_constants():
     return e, i, d
 
 
+lib.powdr_poseidon2_derived.restype = C.c_size_t
+lib.powdr_poseidon2_derived.argtypes = [C.c_void_p, C.c_size_t]
+
+
+def poseidon2_derived() -> dict:
+    """powdr_poseidon2_derived (a read-only test hook): the derived tables of the installed table as Python integers."""
+    v = np.zeros(194, np.int64)
+    assert lib.powdr_poseidon2_derived(v.ctypes.data_as(C.c_void_p), len(v)) == len(v)
+    v = [int(x) for x in v]
+    return dict(ext_fold=[v[16 * r:16 * r + 16] for r in range(8)], entry_c=v[128], part_kappa=v[129:131], part_rho=v[131:133],
+                part_diag=[v[133:149], v[149:165]], int_fold=v[165:178], exit_fold=v[178:194])
+
+
 class Prover:
     """One AIR = one prover (constraint programs fixed at construction).
 

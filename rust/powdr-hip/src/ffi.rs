@@ -234,6 +234,7 @@ extern "C" {
     pub fn powdr_small_form_eval_host(postfix: *const u32, len: u32, trace: *const u32, r: usize, result: *mut u32, flags: *mut u32) -> c_int;
     pub fn powdr_field_selftest(seed: u64, iterations: u32) -> c_int;
     pub fn powdr_field_selftest_gpu(seed: u64, iterations: u32, failing_check: *mut c_int) -> c_int;
+    pub fn powdr_poseidon2_derived(out: *mut i64, cap: usize) -> usize;
 }
 
 // ------------------------------------------------------------------------------------------- include/powdr_prover.h

@@ -37,8 +37,10 @@ def _edge_states(rng):
 
 
 def test_host_permutation_equals_oracle_under_any_constants():
-    """Random tables and the extreme ones (all 0, all p - 1, both neighbours of p / 2 — the largest centred magnitudes the
-    bounds of tools/poseidon2_bounds.py allow for an additive constant): signed host form == oracle."""
+    """Random raw tables and raw tables of equal words (all 0, all p - 1, both neighbours of p / 2, all 1): signed host form == oracle.
+    These are extreme as RAW words only: the rounds consume what derive_params folds them into, and equal raw words fold to small
+    multiples of c / 15. Tables whose FOLDED constants sit at +-(p - 1) / 2, the magnitudes tools/poseidon2_bounds.py allows for,
+    are installed by tests/test_poseidon2_edge_tables.py."""
     from powdr_amd import prover
 
     rng = np.random.default_rng(5)

@@ -83,6 +83,17 @@ def test_merkle_commit_matches_oracle(gpu, height, W):
     abi.check(prover.lib.pw_merkle_commit(d_m.data_ptr(), height, W, d_d.data_ptr()), "pw_merkle_commit")
     torch.cuda.synchronize()
     assert (from_dev(d_d) == dig).all()
+    # edge-valued words (all 0, all p - 1, both neighbours of p / 2, one-hot rows): tests/_poseidon2_tables.py
+    from tests._poseidon2_tables import edge_matrices
+
+    for kind, m in edge_matrices(height, W).items():
+        if kind == "random":
+            continue
+        root, dig = sm.merkle_commit(m, height, W, want_digests=True)
+        d_m = to_dev(torch, m)
+        abi.check(prover.lib.pw_merkle_commit(d_m.data_ptr(), height, W, d_d.data_ptr()), "pw_merkle_commit")
+        torch.cuda.synchronize()
+        assert (from_dev(d_d) == dig).all(), kind
 
 
 def _synthetic(shape, calls, seed):

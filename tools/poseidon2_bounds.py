@@ -1,27 +1,37 @@
 """Exact value ranges of the signed forms in powdr_amd/csrc/poseidon2.hpp (sbox7, external_layer, internal_layer, permute).
 Every 32-bit intermediate must fit an int32, every argument of the signed Montgomery reduction must satisfy
-|t| + 2^31 p < 2^63, every wide sum must stay inside sreduce_wide_loose's 64 p.  All bounds are magnitudes (exclusive)."""
+|t| + 2^31 p < 2^63, every wide sum must stay inside sreduce_wide_loose's domain |y| < 128 p (babybear.hpp; the permutation
+hands it [15.3 p, 84.7 p), the fixed-point closure below allows for 95 p).  All bounds are magnitudes (exclusive).
+The figures the self-test (csrc/field_selftest.hpp) works with are kept as exact integers in the block "p2::bounds" of
+poseidon2.hpp; this tool reads that block from the header text and asserts every constant against what it computes.
+The permutation's input domain is [0, INPUT_TOP) = [0, 1.0207 p): canonical words and the outputs of permute<true>."""
+import re
+from pathlib import Path
+
 p, R = 0x78000001, 1 << 32
 R_MOD_P = R % p
 I32 = 1 << 31
 HALF = (p - 1) // 2  # largest centred representative
+SMONT_DOMAIN = (1 << 63) - I32 * p  # smont takes |t| < this
+SREDUCE_DOMAIN = 128 * p            # sreduce_wide_loose takes |y| < this
+SREDUCE_E = (1 << 39) - 273 * p     # y - q p = y E / 2^39 + the rounding of the two floors
 
 
 def smont(tmax):
     """|t| <= tmax -> bound of |(t + m p) >> 32| for a signed m in [-2^31, 2^31)"""
-    assert tmax + I32 * p < 1 << 63, f"|t| = {tmax / p / p:.3f} p^2 leaves the domain of the signed reduction"
+    assert tmax < SMONT_DOMAIN, f"|t| = {tmax / p / p:.3f} p^2 leaves the domain of the signed reduction"
     out = (tmax + I32 * p) // R + 1
     assert out < I32
     return out
 
 
 def sreduce(ymax):
-    """|y| <= ymax -> (lowest, highest) value of y - q p, q = floor(floor(y / 128) * 273 / 2^32); exact extremes are hard,
-    so use the analytic envelope: y (1 - 273 p / 2^39) + [0, p + 273 p / 2^32 + 1)"""
-    assert ymax < 128 * p  # floor(y / 128) must fit an int32
-    eps = 1 - 273 * p / 2 ** 39
-    lo = -int(ymax * eps) - 1
-    hi = int(ymax * eps) + p + (273 * p >> 32) + 2
+    """|y| <= ymax -> exclusive (lowest, highest) bounds of y - q p, q = floor(floor(y / 128) * 273 / 2^32); exact extremes are
+    hard, so use the analytic envelope: y (1 - 273 p / 2^39) + [0, p + 273 p / 2^32 + 1), in integers (E = 2^39 - 273 p)"""
+    assert ymax < SREDUCE_DOMAIN  # floor(y / 128) must fit an int32
+    m = ymax * SREDUCE_E >> 39
+    lo = -m - 1
+    hi = m + p + (273 * p >> 32) + 2
     assert -I32 < lo and hi < I32
     return lo, hi
 
@@ -51,8 +61,10 @@ print(f"S-box input may be as large as {lo_ok / p:.3f} p")
 def ext_y(X, consts=True):
     return 5 * (7 * X + (3 * HALF if consts else 0))
 
-# closure of "permutation input -> layer -> S-box -> layer ...": inputs are canonical words or sponge outputs ([0, 1.011 p))
-lo_last, hi_last = sreduce(35 * p + 60 * p)  # the last layer's outputs (bias included, non-negative): what a sponge hands to the next permutation
+# closure of "permutation input -> layer -> S-box -> layer ...": inputs are canonical words or sponge outputs ([0, 1.0207 p), shown at
+# the end; the closure starts from the wider 95 p, so every layer is also good for |x| < 1.0232 p)
+CLOSURE_WIDE = 35 * p + 60 * p
+lo_last, hi_last = sreduce(CLOSURE_WIDE)  # the last layer's outputs (bias included, non-negative): what a sponge hands to the next permutation
 sb_in = hi_last
 for _ in range(8):
     y0 = ext_y(sb_in)                       # a layer fed by permutation inputs
@@ -104,3 +116,18 @@ x7l = x7m
 assert 35 * x7l < 40 * p and 35 * x7l + 60 * p < 128 * p
 lo_f, hi_f = sreduce(35 * x7l + 60 * p)
 print(f"last layer: |sum| < {35 * x7l / p:.1f} p, biased into [{(40 * p - 35 * x7l) / p:.1f} p, {(60 * p + 35 * x7l) / p:.1f} p): outputs in [0, {hi_f / p:.4f} p)")
+
+# ---- the same figures as exact integers in poseidon2.hpp (block p2::bounds): what the self-test's edges are taken from
+computed = {
+    "kSmontDomain": SMONT_DOMAIN, "kSreduceDomain": SREDUCE_DOMAIN, "kSreduceE": SREDUCE_E, "kSreduceRound": p + (273 * p >> 32) + 2,
+    "kClosureWide": CLOSURE_WIDE, "kLayerInTop": sb_in, "kSboxOutTop": x7, "kExtWideTop": max(y0, y1), "kExtOutTop": mid,
+    "kLastInTop": x7l, "kLastWideLo": 40 * p - 35 * x7l, "kLastWideHi": 60 * p + 35 * x7l, "kInputTop": hi_f,
+}
+header = (Path(__file__).resolve().parents[1] / "powdr_amd" / "csrc" / "poseidon2.hpp").read_text()
+block = re.search(r"namespace bounds \{(.*?)\}  // namespace bounds", header, flags=re.S)
+assert block, "poseidon2.hpp has no p2::bounds block"
+stated = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr int(?:32|64)_t (k\w+) = (-?\d+)(?:ll)?;", block.group(1))}
+assert set(stated) == set(computed), (sorted(set(stated) ^ set(computed)))
+for name, want in computed.items():
+    assert stated[name] == want, f"poseidon2.hpp states {name} = {stated[name]}, computed {want}"
+print(f"poseidon2.hpp p2::bounds: {len(stated)} constants agree")
