@@ -380,6 +380,55 @@ int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_airs, uint32_
                                 uint32_t* d_trace_out, uint32_t cap_log_height, uint32_t* log_height, uint64_t* n_rows,
                                 uint32_t* status);
 
+/* ---- empirical constraints: column ranges per pc and cell classes per basic block --------------------------------
+ * The data-parallel half of the reference's `detect_empirical_constraints` (openvm/src/empirical_constraints.rs), on the instruction
+ * AIRs' raw device traces. `airs` is the AIR list of pw_check_segment_buses; segment_of_air (n_airs words, NULL = all 0) says which
+ * segment an entry's trace belongs to. An AIR without an interaction on `bus` (the execution bridge) is ignored. Of every other AIR
+ * every row's interactions on `bus` are evaluated as the bus check evaluates them: all multiplicities 0 = padding, the row takes part
+ * in nothing; otherwise exactly one interaction has the centred multiplicity -1 (the receive: its two arguments are the row's pc and
+ * timestamp), every other non-zero one +1. Time key = segment << 32 | timestamp; cells = the canonical values of the AIR's `width`
+ * main columns. `blocks`: start pcs strictly increasing, start + pc_step * n_instructions <= the next start.
+ * Result (host side, canonical order: pcs and blocks ascending, a class's cells by (instruction, column), classes by first cell):
+ *   per executed pc its 64-bit row count, the index of the AIR that executed it, and per column (lo, hi) = the elements n / 100 and
+ *   n * 99 / 100 of the column's n values sorted as canonical integers (pw_empirical_percentile_indices);
+ *   per listed block that ran (a head row and the n_instructions - 1 rows that follow it in time order, at the pcs start + k pc_step)
+ *   the classes of at least two cells (instruction_idx, column_idx) that held equal values in EVERY instance the call saw.
+ * Classes are found by 128-bit fingerprints and then VERIFIED cell against first cell over all instances; on a mismatch the grouping
+ * is repeated under another seed, three times in all: the partition returned is exact, never probable.
+ * The contract of the system-trace routines: the call runs on the calling thread's launch stream and synchronises before it
+ * returns; scratch is per thread and released on every path. -1 before any GPU call: a NULL pointer, pc_step == 0, a block table that
+ * is unsorted, overlapping or has a zero count, an AIR whose interactions on `bus` have not two arguments, 2^32 rows or more.
+ * scratch_bytes bounds the scratch (0: half of what the device budget allows); the columns are walked in panels that fit.
+ * *status: 0 = *out is set (pw_empirical_destroy frees it); 2 = the bound is too small for the row index or one column, *info = bytes
+ * needed (before a row is read: as far as known then; a second status 2 is exact); 3 = not block-structured, *info = the smallest
+ * time key of a head whose instructions do not follow it or of an in-block row without its head; 4 = two rows with one time key,
+ * *info = the key; 5 = a pc executed by rows of two AIRs, *info = the pc; 6 = fingerprint collisions under every seed; 7 = a
+ * multiplicity on the bus other than 0, +1, -1 or not exactly one receive in an active row, *info = air << 32 | row, the smallest.
+ * Checked in the order 2 (the row index), 7, 4, 3, 5, 2 (one column), 6. With a non-zero status no result exists and 0 is
+ * returned. */
+typedef struct { uint32_t start_pc, n_instructions; } PwBasicBlock;
+typedef struct PwEmpirical PwEmpirical;
+int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bus, uint32_t pc_step,
+                        const PwBasicBlock* blocks, size_t n_blocks, size_t scratch_bytes, PwEmpirical** out, uint32_t* status,
+                        uint64_t* info);
+void pw_empirical_destroy(PwEmpirical* e);
+/* Read-outs into caller arrays (a NULL array is skipped). sizes[5] = pcs, ranges (= sum of the pcs' AIR widths), blocks that ran,
+ * classes, cells. pcs / counts / air_of_pc: one per pc; range_offsets: pcs + 1; lo_hi: 2 words per range; start_pcs: one per block;
+ * class_offsets: blocks + 1 (into the classes); cell_offsets: classes + 1 (into the cells); instruction_column: 2 words per cell. */
+void pw_empirical_sizes(const PwEmpirical* e, uint64_t* sizes);
+void pw_empirical_read_pcs(const PwEmpirical* e, uint32_t* pcs, uint64_t* counts, uint32_t* air_of_pc, uint64_t* range_offsets);
+void pw_empirical_read_ranges(const PwEmpirical* e, uint32_t* lo_hi);
+void pw_empirical_read_blocks(const PwEmpirical* e, uint32_t* start_pcs, uint64_t* class_offsets, uint64_t* cell_offsets);
+void pw_empirical_read_cells(const PwEmpirical* e, uint32_t* instruction_column);
+/* *lo = n / 100, *hi = n * 99 / 100 (the product in more than 64 bits). Host only, no GPU call. */
+void pw_empirical_percentile_indices(uint64_t n, uint64_t* lo, uint64_t* hi);
+/* A TEST HOOK: ANDed onto both 64-bit fingerprint halves of the calling thread's later pw_empirical_detect calls (0 = the full
+ * width), so that a test can make collisions happen. The result stays exact or the status is 6. */
+void pw_empirical_set_fingerprint_mask(uint64_t mask);
+/* Of the calling thread's last pw_empirical_detect, out[6]: column panels walked, seeds tried, active rows, cells verified, the most
+ * scratch bytes held at once, scratch bytes held now. */
+void pw_empirical_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -298,6 +298,18 @@ pub struct PwSystemTraceStats {
     pub lds_atomics: u64,
     pub global_atomics: u64,
 }
+/// a basic block of `pw_empirical_detect`: `n_instructions` instructions from `start_pc` on, `pc_step` apart
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwBasicBlock {
+    pub start_pc: u32,
+    pub n_instructions: u32,
+}
+/// the opaque host-side result of `pw_empirical_detect`
+#[repr(C)]
+pub struct PwEmpirical {
+    _private: [u8; 0],
+}
 /// `pw_memory_tree_set_mode`: every level above level 0 hashed again from the level below
 pub const PW_MEMORY_TREE_REBUILD: u32 = 0;
 /// `pw_memory_tree_set_mode`: only the touched paths hashed, every other stored node moved
@@ -435,6 +447,24 @@ extern "C" {
     pub fn pw_poseidon2_compress_trace(airs: *const PwSegmentAir, n_airs: usize, bus: u32, table_bytes: usize, start_log_slots: u32,
                                        d_trace_out: *mut u32, cap_log_height: u32, log_height: *mut u32, n_rows: *mut u64,
                                        status: *mut u32) -> c_int;
+    /// Empirical constraints: per pc the percentile range of every column, per listed block its classes of equal cells.
+    /// `status` 0 = `*out` is set (free it with `pw_empirical_destroy`); otherwise no result and `info` says where.
+    pub fn pw_empirical_detect(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bus: u32, pc_step: u32,
+                               blocks: *const PwBasicBlock, n_blocks: usize, scratch_bytes: usize, out: *mut *mut PwEmpirical,
+                               status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_empirical_destroy(e: *mut PwEmpirical);
+    /// sizes[5] = pcs, ranges, blocks that ran, classes, cells
+    pub fn pw_empirical_sizes(e: *const PwEmpirical, sizes: *mut u64);
+    pub fn pw_empirical_read_pcs(e: *const PwEmpirical, pcs: *mut u32, counts: *mut u64, air_of_pc: *mut u32, range_offsets: *mut u64);
+    pub fn pw_empirical_read_ranges(e: *const PwEmpirical, lo_hi: *mut u32);
+    pub fn pw_empirical_read_blocks(e: *const PwEmpirical, start_pcs: *mut u32, class_offsets: *mut u64, cell_offsets: *mut u64);
+    pub fn pw_empirical_read_cells(e: *const PwEmpirical, instruction_column: *mut u32);
+    /// n / 100 and n * 99 / 100: host only
+    pub fn pw_empirical_percentile_indices(n: u64, lo: *mut u64, hi: *mut u64);
+    /// a test hook: ANDed onto both fingerprint halves of this thread's later `pw_empirical_detect` calls (0 = full width)
+    pub fn pw_empirical_set_fingerprint_mask(mask: u64);
+    /// out[6]: panels, seeds, active rows, cells verified, peak scratch bytes, scratch bytes held
+    pub fn pw_empirical_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
