@@ -3,10 +3,12 @@
 //   pass A  bus_sum_kernel     per selected bus the LogUp sum over all AIRs, interactions and rows (the verdict), and n_active
 //   pass B  bus_tally_kernel   one bus at a time: every active (air, interaction, row) adds its centred multiplicity to the slot of
 //                              its tuple's fingerprint in an open-addressing table; bus_compact_kernel lists the slots whose sum is
-//                              non-zero mod p; bus_args_kernel re-evaluates the tuple words at the slots' witness rows. The table
-//                              starts small and is quadrupled (and the bus tallied again) until it holds the bus or reaches its bound
+//                              non-zero mod p; witness_args_kernel re-evaluates the tuple words at the slots' witness rows
+// The table itself — the claim loop, the load rule, the sizing and the growth from a small first table — is bus_shared.hpp's; what is
+// here is the table's payload (sum, witness, count).
 // One lane per row, interactions evaluated by eval_span / DenominatorAcc exactly as logup_perm_kernel evaluates them.
 #include "bus_shared.hpp"
+#include "bus_witness_args.hpp"
 
 namespace pw {
 
@@ -17,7 +19,7 @@ using bb::Ext;
 using pwj::DenominatorSeeds;
 using pwj::denominator_seeds;
 
-struct Unbalanced { u64 witness, count; uint32_t net, pad; };
+struct Unbalanced { u64 witness, count; uint32_t net, pad; };  // (the witness first: witness_args_kernel reads a list of these)
 
 // al + bus + sum_j bl^(j+1) a_j + bl^(n+1) n: the denominator of the interaction's tuple on row r with its ARITY folded in, so that
 // (a, b) and (a, b, 0) differ (the prover's own denominator, interaction_denominator of logup_kernels.hip, stops before the last term)
@@ -90,16 +92,11 @@ __global__ __launch_bounds__(kBlock) void bus_sum_kernel(const uint32_t* __restr
 }
 
 // ---- pass B ---------------------------------------------------------------------------------------------------------------------
-struct Table { u64 *k0, *k1, *wit, *sum, *cnt; u64 mask; u64* load; u64 class_mask, class_cap; };
+struct Table { TableView v; u64 *wit, *sum, *cnt; };
 
-// Every active (interaction, row) of ONE bus in one AIR: the slot of its tuple's fingerprint (the four words of the denominator: two
-// 64-bit key halves, each claimed by a compare-and-swap; a slot whose first half matches and whose second does not belongs to another
-// tuple: keep probing) gets the centred multiplicity added, the packed witness min-ed in and its count bumped. Keys never change once
-// set, so every contribution of a tuple ends in the same slot whatever the order of arrival. The lane that claims a fresh slot counts
-// it in the slot's class; a class past its cap sets *overflow (and so does a lane that has seen every slot taken by other tuples: only
-// tables of fewer than 8 slots get that far). With linear probing the SET of taken slots does not depend on the order of arrival and
-// only grows with the tuples inserted, so whether a class passes its cap — *overflow — is a function of the traces and the table size
-// alone. Every lane stops early once it is set: the host throws the table away.
+// Every active (interaction, row) of ONE bus in one AIR: the slot of its tuple's fingerprint (the four words of the denominator: the
+// two 64-bit key words of claim_slot, bus_shared.hpp) gets the centred multiplicity added, the packed witness min-ed in and its count
+// bumped. Every lane stops early once *overflow is set: the host throws the table away.
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void bus_tally_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
                                                             uint32_t begin, uint32_t end, uint32_t air, Ext al, const Ext* __restrict__ blpow, Table t,
@@ -118,38 +115,11 @@ __global__ __launch_bounds__(kBlock) void bus_tally_kernel(const uint32_t* __res
         const u64 a = (u64)d.c[0] | ((u64)d.c[1] << 32), b = (u64)d.c[2] | ((u64)d.c[3] << 32);
         const u64 witness = pack_witness(air, idx, r);
         const long long cm = (long long)bb::centred(bb::from_monty(mu));
-        const u64 h = slot_hash(a, b);
-        bool done = false;
-        for (u64 n = 0; n <= t.mask; ++n) {
-            const u64 s = (h + n) & t.mask;
-            u64 ka = __atomic_load_n(t.k0 + s, __ATOMIC_RELAXED);
-            if (ka == kEmpty) {
-                ka = atomicCAS(t.k0 + s, kEmpty, a);
-                if (ka == kEmpty) {
-                    ka = a;
-                    if (atomicAdd(t.load + (s & t.class_mask) * kLoadStride, 1ull) >= t.class_cap) atomicOr(overflow, 1u);
-                }
-            }
-            if (ka == a) {
-                u64 kb = __atomic_load_n(t.k1 + s, __ATOMIC_RELAXED);
-                if (kb == kEmpty) {
-                    kb = atomicCAS(t.k1 + s, kEmpty, b);
-                    if (kb == kEmpty) kb = b;
-                }
-                if (kb == b) {
-                    atomicAdd(t.sum + s, (u64)cm);
-                    atomicMin(t.wit + s, witness);
-                    atomicAdd(t.cnt + s, 1ull);
-                    done = true;
-                    break;
-                }
-            }
-            if ((n & 63) == 63 && __atomic_load_n(overflow, __ATOMIC_RELAXED)) break;
-        }
-        if (!done) {
-            atomicOr(overflow, 1u);
-            return;
-        }
+        const u64 s = claim_slot<2>(t.v, a, b, overflow);
+        if (s == kEmpty) return;
+        atomicAdd(t.sum + s, (u64)cm);
+        atomicMin(t.wit + s, witness);
+        atomicAdd(t.cnt + s, 1ull);
     }
 }
 
@@ -157,35 +127,13 @@ __global__ __launch_bounds__(kBlock) void bus_tally_kernel(const uint32_t* __res
 // sorts them by their tuples; cap = the count of a first, counting launch, so nothing is dropped)
 __global__ __launch_bounds__(kBlock) void bus_compact_kernel(Table t, Unbalanced* __restrict__ out, u64 cap, u64* __restrict__ counts) {
     const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
-    if (s > t.mask || t.k0[s] == kEmpty) return;
-    const long long sum = (long long)t.sum[s];
-    long long net = sum % (long long)bb::P;
-    if (net < 0) net += (long long)bb::P;
+    if (s > t.v.mask || t.v.k0[s] == kEmpty) return;
+    const uint32_t net = sum_residue(t.sum[s]);
     if (!out) atomicAdd(counts, 1ull);
     if (net == 0) return;
     if (!out) { atomicAdd(counts + 1, 1ull); return; }
     const u64 at = atomicAdd(counts + 2, 1ull);
-    if (at < cap) out[at] = Unbalanced{t.wit[s], t.cnt[s], (uint32_t)net, 0u};
-}
-
-// args[e * stride + j] = argument j (canonical) of the interaction and row entry e's witness names; one wave per entry, every lane
-// of it evaluating the same program on the same row (the interpreter wants wave-uniform code; the lists are short)
-__global__ __launch_bounds__(kBlock) void bus_args_kernel(const Unbalanced* __restrict__ list, u64 n, const AirDev* __restrict__ airs, uint32_t stride,
-                                                           uint32_t* __restrict__ args) {
-    __shared__ uint32_t stack_lds[kStackCap * kBlock];
-    uint32_t* stk = stack_lds + threadIdx.x;
-    const u64 e = (u64)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (e >= n) return;
-    const u64 w = list[e].witness;
-    const AirDev a = airs[w >> (kRowBits + kInterBits)];
-    const uint32_t idx = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
-    const size_t r = (size_t)(w & ((1ull << kRowBits) - 1ull));
-    const LogupInteraction it = a.lp.d_inter[idx];
-    for (uint32_t j = 0; j < it.n_args && j < stride; ++j) {
-        const uint32_t v = a.lp.d_forms ? eval_span<true>(a.lp, it.first_span + 1 + j, a.m, (size_t)a.H, r, stk)
-                                        : eval_span<false>(a.lp, it.first_span + 1 + j, a.m, (size_t)a.H, r, stk);
-        if ((threadIdx.x & 63) == 0) args[e * stride + j] = bb::from_monty(v);
-    }
+    if (at < cap) out[at] = Unbalanced{t.wit[s], t.cnt[s], net, 0u};
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
@@ -202,18 +150,6 @@ struct Released {
     BusCtx& cx;
     ~Released() { cx.table.release(); cx.list.release(); cx.args.release(); }
 };
-
-uint64_t splitmix(uint64_t& s) {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-Ext challenge(uint64_t& s) {
-    Ext e;
-    for (int k = 0; k < 4; ++k) e.c[k] = bb::to_monty((uint32_t)(splitmix(s) % bb::P));
-    return e;
-}
 
 }  // namespace
 
@@ -262,15 +198,15 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
 
     (void)hipGetLastError();
     // ---- the AIRs that take part, their bus runs, the challenge powers
-    struct Part { size_t air; std::vector<BusSeg> segs; size_t seg_off; const uint32_t* vals; };
-    std::vector<Part> parts;
+    struct BusPart { size_t air; std::vector<BusSeg> segs; size_t seg_off; const uint32_t* vals; };
+    std::vector<BusPart> parts;
     std::vector<BusSeg> all_segs;
     uint32_t max_args = 0;
     for (size_t a = 0; a < n_airs; ++a) {
         PwProver* p = airs[a].prover;
         if (!p->logup || !p->n_inter) continue;
         PW_TRY(ensure_bus_order(p));
-        Part part{a, {}, all_segs.size(), nullptr};
+        BusPart part{a, {}, all_segs.size(), nullptr};
         for (size_t k = 0; k < p->h_bus_ids.size(); ++k) {
             const auto at = std::lower_bound(sel.begin(), sel.end(), p->h_bus_ids[k]);
             if (at == sel.end() || *at != p->h_bus_ids[k]) continue;
@@ -287,18 +223,16 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     blpow[0] = bb::ext_one();
     for (size_t j = 1; j < blpow.size(); ++j) blpow[j] = bb::ext_mul(blpow[j - 1], bl);
 
-    // small: accumulators (5 u64 per bus) | counters (4 u64) | overflow (+ padding, 16 bytes) | class loads | powers | bus runs | AIR table
-    const size_t load_bytes = kMaxClasses * kLoadStride * 8;
-    const size_t off_cnt = n_sel * 5 * 8, off_ovf = off_cnt + 32, off_load = off_ovf + 16, off_pow = off_load + load_bytes, off_seg = off_pow + blpow.size() * sizeof(Ext),
+    // small: accumulators (5 u64 per bus) | the walker's head (counters: in use | unbalanced | written | unused) | powers | bus runs | AIR table
+    const size_t off_head = n_sel * 5 * 8, off_pow = off_head + sizeof(WalkHead), off_seg = off_pow + blpow.size() * sizeof(Ext),
                  off_air = (off_seg + all_segs.size() * sizeof(BusSeg) + 15) & ~(size_t)15, small_bytes = off_air + n_airs * sizeof(AirDev);
     const Released released{cx};
     PW_TRY(cx.small.ensure(small_bytes));
     cx.note();
     char* base = cx.small.as<char>();
     u64* d_acc = (u64*)base;
-    u64* d_counts = (u64*)(base + off_cnt);
-    uint32_t* d_ovf = (uint32_t*)(base + off_ovf);
-    u64* d_load = (u64*)(base + off_load);
+    WalkHead* d_head = (WalkHead*)(base + off_head);
+    u64* d_counts = d_head->c.counts;
     const Ext* d_blpow = (const Ext*)(base + off_pow);
     const BusSeg* d_segs = (const BusSeg*)(base + off_seg);
     AirDev* d_airs = (AirDev*)(base + off_air);
@@ -308,7 +242,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     if (!all_segs.empty()) PW_HIP_TRY(hipMemcpyAsync(base + off_seg, all_segs.data(), all_segs.size() * sizeof(BusSeg), hipMemcpyHostToDevice, st));
 
     std::vector<AirDev> air_tab(n_airs, AirDev{nullptr, 0, LogupProgram{}});
-    for (Part& part : parts) {
+    for (BusPart& part : parts) {
         const PwSegmentAir& A = airs[part.air];
         PW_TRY(stage_values(A, &part.vals));
         air_tab[part.air] = AirDev{part.vals, (u64)1 << A.log_height, program_of(A.prover)};
@@ -318,20 +252,13 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     // ---- pass A
     {
         ScopedKernelTimer timer("bus_sum_kernel");
-        for (const Part& part : parts) {
-            const PwSegmentAir& A = airs[part.air];
-            const PwProver* p = A.prover;
-            const size_t H = (size_t)1 << A.log_height;
-            const uint32_t* vals = part.vals;
-            const uint32_t rows = A.log_height >= 16 ? 4u : 1u;
-            const LogupProgram lp = program_of(p);
-            const dim3 grid(div_up(H, (size_t)kBlock * rows));
-            if (lp.d_forms)
-                hipLaunchKernelGGL(bus_sum_kernel<true>, grid, dim3(kBlock), 0, st, vals, H, rows, lp, (const uint32_t*)p->bus_order.p, d_segs + part.seg_off,
-                                   (uint32_t)part.segs.size(), al, d_blpow, d_acc);
-            else
-                hipLaunchKernelGGL(bus_sum_kernel<false>, grid, dim3(kBlock), 0, st, vals, H, rows, lp, (const uint32_t*)p->bus_order.p, d_segs + part.seg_off,
-                                   (uint32_t)part.segs.size(), al, d_blpow, d_acc);
+        for (const BusPart& part : parts) {
+            const Walked w = walked(airs[part.air]);
+            const uint32_t rows = airs[part.air].log_height >= 16 ? 4u : 1u;
+            with_fast(w.lp, [&](auto fast) {
+                hipLaunchKernelGGL(bus_sum_kernel<decltype(fast)::value>, dim3(div_up(w.H, (size_t)kBlock * rows)), dim3(kBlock), 0, st, part.vals, w.H, rows, w.lp,
+                                   w.order, d_segs + part.seg_off, (uint32_t)part.segs.size(), al, d_blpow, d_acc);
+            });
         }
     }
     PW_HIP_TRY(hipGetLastError());
@@ -353,88 +280,54 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     size_t n_out = 0;
     for (size_t b = 0; b < n_sel; ++b) {
         if ((zero_sum[b] && !(flags & PW_BUS_CHECK_TALLY_ALL)) || !sums[b].n_active) continue;
-        // the largest table this bus may get: a power of two of slots, at most twice the active triples (no bus needs more), within the
-        // caller's bound, or by default half of the device's room
-        u64 max_slots = 1024;
-        while (max_slots < 2 * sums[b].n_active) max_slots <<= 1;
-        size_t bound = table_bytes;
-        if (!bound) {
-            if (!room_known) {
-                size_t avail = 0;
-                room = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
-                room_known = true;
-            }
-            bound = room;
+        // the table's bound: the caller's, or by default half of the device's room (asked once per call)
+        if (!table_bytes && !room_known) {
+            room = default_bound(cx.held());
+            room_known = true;
         }
-        while (max_slots && max_slots * kSlotBytes > bound) max_slots >>= 1;
-        if (!max_slots) continue;  // (status 2 when the sum is not zero, balanced otherwise: as pass A left it)
         uint32_t stride = 1;
-        for (const Part& part : parts)
+        for (const BusPart& part : parts)
             for (const BusSeg& x : part.segs)
                 if (x.slot == b)
                     for (uint32_t i = x.begin; i < x.end; ++i)
                         stride = std::max(stride, airs[part.air].prover->h_inter[airs[part.air].prover->h_bus_order[i]].n_args);
-        // tally into a small table first and into one four times as large while the bus overflows it: lookup buses repeat a few hundred
-        // thousand tuples thousands of times, so the active count says little about the table a bus needs. What is reported depends on
-        // the LAST table alone. An overflowing tally stops early (every lane leaves once the overflow word is set), which should keep the
-        // attempts before the last one cheap; that has not been measured.
-        u64 slots = std::min(max_slots, kStartSlots);
-        u64 counts[6] = {0, 0, 0, 0, 1, 0};  // in use | unbalanced | written | (unused) | overflow word
+        // tally into tables that grow until one holds the bus (grow_table, bus_shared.hpp; that an overflowing tally is cheap has not been
+        // measured: DESIGN.md §5i)
         Table T{};
-        for (;;) {
-            // a table the device cannot give is a table too small: try half, never an error
-            int erc;
-            while ((erc = cx.table.ensure(slots * kSlotBytes)) != 0) {
-                (void)hipGetLastError();
-                if (erc != (int)hipErrorOutOfMemory) return erc;
-                if (slots <= 1) break;
-                max_slots = slots >>= 1;
-            }
-            if (!cx.table.p) break;
-            cx.note();
-            u64* tb = cx.table.as<u64>();
-            const u64 classes = std::min<u64>(kMaxClasses, std::max<u64>(1, slots / kMinClassSlots)), per_class = slots / classes;
-            T = Table{tb, tb + slots, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots, slots - 1, d_load, classes - 1, per_class - per_class / 8};
-            {
-                ScopedKernelTimer timer("bus_table_clear");
+        Grown g;
+        PW_TRY(grow_table(
+            cx.table, d_head, sums[b].n_active, kSlotBytes, table_bytes ? table_bytes : room, kStartSlots, "bus_table_clear",
+            [&](u64* tb, const TableRule& rule) -> int {
+                const u64 slots = rule.mask + 1;
+                cx.note();
+                T = Table{TableView{rule, tb, tb + slots}, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots};
                 PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 3 * slots * 8, st));
                 PW_HIP_TRY(hipMemsetAsync(tb + 3 * slots, 0, 2 * slots * 8, st));
-                PW_HIP_TRY(hipMemsetAsync(d_counts, 0, 48 + load_bytes, st));  // counters, the overflow word, the class loads
-            }
-            {
+                return 0;
+            },
+            [&] {
                 ScopedKernelTimer timer("bus_tally_kernel");
-                for (const Part& part : parts) {
+                for (const BusPart& part : parts) {
                     const BusSeg* sg = nullptr;
                     for (const BusSeg& x : part.segs)
                         if (x.slot == b) sg = &x;
                     if (!sg) continue;
-                    const PwSegmentAir& A = airs[part.air];
-                    const PwProver* p = A.prover;
-                    const size_t H = (size_t)1 << A.log_height;
-                    const LogupProgram lp = program_of(p);
-                    const dim3 grid(div_up(H, kBlock));
-                    if (lp.d_forms)
-                        hipLaunchKernelGGL(bus_tally_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, lp, (const uint32_t*)p->bus_order.p, sg->begin,
-                                           sg->end, (uint32_t)part.air, al, d_blpow, T, d_ovf);
-                    else
-                        hipLaunchKernelGGL(bus_tally_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, lp, (const uint32_t*)p->bus_order.p, sg->begin,
-                                           sg->end, (uint32_t)part.air, al, d_blpow, T, d_ovf);
+                    const Walked w = walked(airs[part.air]);
+                    with_fast(w.lp, [&](auto fast) {
+                        hipLaunchKernelGGL(bus_tally_kernel<decltype(fast)::value>, dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H, w.lp, w.order,
+                                           sg->begin, sg->end, (uint32_t)part.air, al, d_blpow, T, &d_head->c.overflow);
+                    });
                 }
-            }
-            hipLaunchKernelGGL(bus_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, (Unbalanced*)nullptr, (u64)0, d_counts);
-            PW_HIP_TRY(hipGetLastError());
-            PW_HIP_TRY(hipMemcpyAsync(counts, d_counts, 48, hipMemcpyDeviceToHost, st));
-            PW_HIP_TRY(hipStreamSynchronize(st));
-            ++cx.stat_tables;
-            if (!(uint32_t)counts[4] || slots >= max_slots) break;
-            slots = std::min(max_slots, slots * 4);
-        }
-        if (!cx.table.p) continue;  // no table at all: as pass A left it
+            },
+            [&] { hipLaunchKernelGGL(bus_compact_kernel, dim3(div_up(T.v.mask + 1, kBlock)), dim3(kBlock), 0, st, T, (Unbalanced*)nullptr, (u64)0, d_counts); }, &g));
+        cx.stat_tables += g.tables;
+        if (g.no_table) continue;  // (status 2 when the sum is not zero, balanced otherwise: as pass A left it)
+        const u64 slots = g.slots;
         cx.stat_slots = std::max<uint64_t>(cx.stat_slots, slots);
-        cx.stat_occupied = std::max<uint64_t>(cx.stat_occupied, counts[0]);
-        if ((uint32_t)counts[4]) continue;  // overflow: not localised
+        cx.stat_occupied = std::max<uint64_t>(cx.stat_occupied, g.c.counts[0]);
+        if (g.overflowed()) continue;  // not localised
         cx.stat_inserted += sums[b].n_active;
-        const u64 n_unb = counts[1];
+        const u64 n_unb = g.c.counts[1];
         sums[b].status = n_unb ? 1u : 0u;
         sums[b].n_unbalanced = n_unb;
         if (!n_unb || !tuples || n_out >= tuple_cap) continue;
@@ -444,8 +337,8 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
         cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.args.p, 0, n_unb * stride * 4, st));
         hipLaunchKernelGGL(bus_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.list.as<Unbalanced>(), n_unb, d_counts);
-        hipLaunchKernelGGL(bus_args_kernel, dim3(div_up(n_unb, kWaves)), dim3(kBlock), 0, st, cx.list.as<Unbalanced>(), n_unb, d_airs, stride,
-                           cx.args.as<uint32_t>());
+        hipLaunchKernelGGL(witness_args_kernel, dim3(div_up(n_unb, kWaves)), dim3(kBlock), 0, st, (const u64*)cx.list.p, (uint32_t)(sizeof(Unbalanced) / 8), n_unb,
+                           (const AirDev*)d_airs, stride, cx.args.as<uint32_t>(), (uint32_t*)nullptr);
         PW_HIP_TRY(hipGetLastError());
         std::vector<Unbalanced> list(n_unb);
         std::vector<uint32_t> args(n_unb * stride);
@@ -453,8 +346,8 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
         PW_HIP_TRY(hipMemcpyAsync(args.data(), cx.args.p, args.size() * 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
         auto n_args_of = [&](const Unbalanced& u) {
-            const PwProver* p = airs[u.witness >> (kRowBits + kInterBits)].prover;
-            return p->h_inter[(u.witness >> kRowBits) & ((1u << kInterBits) - 1u)].n_args;
+            const Witness w = unpack_witness(u.witness);
+            return airs[w.air].prover->h_inter[w.inter].n_args;
         };
         std::vector<size_t> idx(n_unb);
         for (size_t i = 0; i < n_unb; ++i) idx[i] = i;
@@ -475,9 +368,10 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
             t.n_args = n_args_of(u);
             for (uint32_t j = 0; j < t.n_args && j < PW_BUS_MAX_ARGS; ++j) t.args[j] = args[idx[k] * stride + j];
             t.net_multiplicity = u.net;
-            t.air = (uint32_t)(u.witness >> (kRowBits + kInterBits));
-            t.interaction = (uint32_t)(u.witness >> kRowBits) & ((1u << kInterBits) - 1u);
-            t.row = u.witness & ((1ull << kRowBits) - 1ull);
+            const Witness w = unpack_witness(u.witness);
+            t.air = w.air;
+            t.interaction = w.inter;
+            t.row = w.row;
             t.n_contributions = u.count;
         }
     }

@@ -38,6 +38,13 @@ inline int hip_status(hipError_t e) { return (int)e; }
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// the log height of the smallest trace of at least two rows that holds `rows`
+inline uint32_t ceil_log2_at_least_1(unsigned long long rows) {
+    uint32_t lh = 1;
+    while ((1ull << lh) < rows) ++lh;
+    return lh;
+}
+
 // Which code paths the calling thread's library calls took (powdr_gpu_call_stats): parity tests assert that a workload
 // really exercised the job forms / kernels it is meant to cover instead of inferring it from sizes.
 enum CallStat : int {

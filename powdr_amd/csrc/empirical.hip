@@ -18,6 +18,8 @@
 //              empirical_pick_kernel reads the two percentile elements
 //   classes    the host groups a block's cells by fingerprint (small), empirical_verify_kernel compares every member of a candidate
 //              class with the class's first cell over all instances; a mismatch repeats the fingerprints under another seed
+// No table here: of bus_shared.hpp this file takes the AIRs on the bridge bus (collect_parts), their launch (walked, with_fast) and
+// the default scratch bound.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
 
@@ -50,15 +52,6 @@ constexpr int kFpItems = 16;               // positions a lane of the fingerprin
 struct EAir { const uint32_t* trace; u64 H; uint32_t width, pad; };
 struct EPart { u64 g0; uint32_t air, pad; };
 struct VPair { uint32_t ra, ca, rf, cf; };
-
-__device__ __forceinline__ u64 wave_min64(u64 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 __host__ __device__ __forceinline__ u64 mix64(u64 z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void empirical_index_kernel(const uint32_t*
         pcs[g0 + r] = ok ? pc : kNoPc;
     }
     if (__builtin_amdgcn_ballot_w64(bad)) {  // (never on honest traces)
-        const u64 w = wave_min64(bad ? ((u64)air << 32) | (u64)r : kEmpty);
+        const u64 w = wave_min(bad ? ((u64)air << 32) | (u64)r : kEmpty);
         if ((threadIdx.x & 63u) == 0u) atomicMin(counters + 1, w);
     }
 }
@@ -327,8 +320,6 @@ struct EmpReleased {
     }
 };
 
-struct Part { size_t air; uint32_t begin, end; const uint32_t* vals; u64 g0; };
-
 size_t sort_pairs_temp(size_t n) {
     size_t bytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 64u, stream());
@@ -445,21 +436,13 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     std::vector<Part> parts;
     std::vector<EPart> h_parts;
     std::vector<EAir> h_airs(n_airs, EAir{nullptr, 0, 0, 0});
+    PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
+    for (size_t a = 0; a < n_airs; ++a) h_airs[a] = EAir{airs[a].d_trace, (u64)1 << airs[a].log_height, airs[a].prover->width, 0};
     {
-        u64 g0 = 0;
-        for (size_t a = 0; a < n_airs; ++a) {
-            PwProver* p = airs[a].prover;
-            h_airs[a] = EAir{airs[a].d_trace, (u64)1 << airs[a].log_height, p->width, 0};
-            if (!p->logup || !p->n_inter) continue;
-            PW_TRY(ensure_bus_order(p));
-            const auto at = std::lower_bound(p->h_bus_ids.begin(), p->h_bus_ids.end(), bus);
-            if (at == p->h_bus_ids.end() || *at != bus) continue;
-            const size_t k = at - p->h_bus_ids.begin();
-            Part part{a, p->h_bus_starts[k], p->h_bus_starts[k + 1], nullptr, g0};
-            PW_TRY(stage_values(airs[a], &part.vals));
-            parts.push_back(part);
-            h_parts.push_back(EPart{g0, (uint32_t)a, 0});
-            g0 += (u64)1 << airs[a].log_height;
+        u64 g0 = 0;  // the parts' rows numbered through
+        for (const Part& part : parts) {
+            h_parts.push_back(EPart{g0, (uint32_t)part.air, 0});
+            g0 += (u64)1 << airs[part.air].log_height;
         }
     }
 
@@ -477,11 +460,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     const PwBasicBlock* d_blocks = (const PwBasicBlock*)(base + off_blocks);
 
     // the bound: the caller's, or half of what the device has room for
-    size_t bound = scratch_bytes;
-    if (!bound) {
-        size_t avail = 0;
-        bound = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
-    }
+    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
     // the index stage holds 32 bytes per row and a sort's temporary storage; one column of a panel 16 bytes per active row (at most M)
     const size_t index_need = small_bytes + (size_t)M * 32 + sort_pairs_temp(M);
     auto panel_need = [&](u64 N, uint32_t C, u64 n_runs, u64 n_cells) {
@@ -511,20 +490,14 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     cx.note();
     {
         ScopedKernelTimer timer("empirical_index_kernel");
-        for (const Part& part : parts) {
-            const PwSegmentAir& A = airs[part.air];
-            const PwProver* p = A.prover;
-            const size_t H = (size_t)1 << A.log_height;
-            const LogupProgram lp = program_of(p);
-            const dim3 grid(div_up(H, kBlock));
-            const uint32_t* order = (const uint32_t*)p->bus_order.p;
+        for (size_t k = 0; k < parts.size(); ++k) {
+            const Part& part = parts[k];
+            const Walked w = walked(airs[part.air]);
             const uint32_t seg = segment_of_air ? segment_of_air[part.air] : 0u;
-            if (lp.d_forms)
-                hipLaunchKernelGGL(empirical_index_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, seg, part.g0,
-                                   cx.tkey.as<u64>(), cx.pcs.as<uint32_t>(), d_counters);
-            else
-                hipLaunchKernelGGL(empirical_index_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, seg, part.g0,
-                                   cx.tkey.as<u64>(), cx.pcs.as<uint32_t>(), d_counters);
+            with_fast(w.lp, [&](auto fast) {
+                hipLaunchKernelGGL(empirical_index_kernel<decltype(fast)::value>, dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H, w.lp, w.order, part.begin,
+                                   part.end, (uint32_t)part.air, seg, h_parts[k].g0, cx.tkey.as<u64>(), cx.pcs.as<uint32_t>(), d_counters);
+            });
         }
         hipLaunchKernelGGL(empirical_iota_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, cx.idx.as<uint32_t>(), M);
     }

@@ -680,12 +680,6 @@ int build_levels(TreeCtx& cx, PwMemoryTree* tree, const PwMemoryTree::Data& old,
     return (int)hipGetLastError();
 }
 
-uint32_t ceil_log2_at_least_1(u64 rows) {
-    uint32_t lh = 1;
-    while (((u64)1 << lh) < rows) ++lh;
-    return lh;
-}
-
 }  // namespace
 
 }  // namespace pw

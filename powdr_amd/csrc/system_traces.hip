@@ -5,17 +5,19 @@
 //                                     row's sum — merged per wave, then per workgroup in LDS (the first kFreqLdsBins rows) — or is
 //                                     counted as foreign; program_freq_finish_kernel reduces the sums mod p
 //   boundary    boundary_walk_kernel  pass 1: (as, ptr) of every active triple of the memory bus into an open-addressing table keyed
-//                                     by ADDRESS (the bus check's hashing and load rule), atomicMin of the timestamp over the receives,
-//                                     atomicMax over the sends; pass 2: atomicMin of the packed witness over the triples that carry
-//                                     those extremes; boundary_compact_kernel + a radix sort of the keys; boundary_rows_kernel: one
-//                                     lane per row re-evaluates the data words at the two witnesses and writes the 18 columns
+//                                     by ADDRESS, atomicMin of the timestamp over the receives, atomicMax over the sends; pass 2:
+//                                     atomicMin of the packed witness over the triples that carry those extremes;
+//                                     boundary_compact_kernel + a radix sort of the keys; boundary_rows_kernel: one lane per row
+//                                     re-evaluates the data words at the two witnesses and writes the 18 columns
 //   poseidon2   compress_tally_kernel every active triple of the compression bus into an open-addressing table keyed by the fingerprint
 //                                     of its 16 INPUT words (the digest words are not read): 64-bit sum of the centred multiplicities,
 //                                     atomicMin of the packed witness; compress_compact_kernel + a radix sort of (witness, sum);
 //                                     compress_rows_kernel: one lane per row re-evaluates the inputs at the witness and runs a
 //                                     permutation that stores every committed intermediate
-// One lane per row, interactions evaluated by eval_span exactly as the prover and the bus check evaluate them.
+// One lane per row, interactions evaluated by eval_span exactly as the prover and the bus check evaluate them. Both tables are the
+// bus check's (bus_shared.hpp: the claim loop, the load rule, the sizing and the growth), each with its own payload columns.
 #include "bus_shared.hpp"
+#include "bus_witness_args.hpp"
 #include "prover_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
@@ -35,15 +37,6 @@ constexpr uint32_t kBoundaryWidth = 18;
 constexpr uint32_t kLimbBits = 17;
 // what a walk found wrong with the multiplicities (boundary_walk_kernel)
 constexpr uint32_t kFlagMagnitude = 1u;
-
-__device__ __forceinline__ u64 wave_min(u64 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // ---- the program AIR's multiplicities ----------------------------------------------------------------------------------------------
 // sums[row] += the centred multiplicities of the tuples that equal program row `row` (two's complement in 64 bits: exact below 2^32
@@ -135,58 +128,20 @@ __global__ __launch_bounds__(kBlock) void program_freq_kernel(const uint32_t* __
 __global__ __launch_bounds__(kBlock) void program_freq_finish_kernel(const u64* __restrict__ sums, uint32_t table_rows, uint32_t* __restrict__ freq) {
     const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
     if (r >= table_rows) return;
-    long long v = (long long)sums[r] % (long long)bb::P;
-    if (v < 0) v += (long long)bb::P;
-    freq[r] = bb::to_monty((uint32_t)v);
-}
-
-// args[e * stride + j] = argument j (canonical) of the interaction and row that witness e names, mult[e] its multiplicity; one wave
-// per entry (as bus_args_kernel: the lists are short)
-__global__ __launch_bounds__(kBlock) void witness_args_kernel(const u64* __restrict__ list, u64 n, const AirDev* __restrict__ airs, uint32_t stride,
-                                                               uint32_t* __restrict__ args, uint32_t* __restrict__ mult) {
-    __shared__ uint32_t stack_lds[kStackCap * kBlock];
-    uint32_t* stk = stack_lds + threadIdx.x;
-    const u64 e = (u64)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (e >= n) return;
-    const u64 w = list[e];
-    const AirDev a = airs[w >> (kRowBits + kInterBits)];
-    const uint32_t idx = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
-    const size_t r = (size_t)(w & ((1ull << kRowBits) - 1ull));
-    const LogupInteraction it = a.lp.d_inter[idx];
-    for (uint32_t j = 0; j <= it.n_args && j <= stride; ++j) {
-        const uint32_t v = a.lp.d_forms ? eval_span<true>(a.lp, it.first_span + j, a.m, (size_t)a.H, r, stk)
-                                        : eval_span<false>(a.lp, it.first_span + j, a.m, (size_t)a.H, r, stk);
-        if ((threadIdx.x & 63) == 0) {
-            if (j == 0) mult[e] = bb::from_monty(v);
-            else args[e * stride + j - 1] = bb::from_monty(v);
-        }
-    }
+    freq[r] = bb::to_monty(sum_residue(sums[r]));
 }
 
 // ---- the memory boundary AIR's trace -----------------------------------------------------------------------------------------------
-// one slot per touched location: the key (as << 32 | ptr), the smallest timestamp a receive carried (what the location held before
-// its first access: kEmpty = no receive), the largest a send carried + 1 (what it holds after its last: 0 = no send), and the smallest
-// packed witness among the triples that carry each extreme
-struct AddrTable { u64 *key, *tmin, *wmin, *wmax, *tmax; u64 mask; u64* load; u64 class_mask, class_cap; };
+// one slot per touched location: the key (as << 32 | ptr: one key word, v.k1 unused), the smallest timestamp a receive carried (what
+// the location held before its first access: kEmpty = no receive), the largest a send carried + 1 (what it holds after its last: 0 =
+// no send), and the smallest packed witness among the triples that carry each extreme
+struct AddrTable { TableView v; u64 *tmin, *wmin, *wmax, *tmax; };
 
 __device__ __forceinline__ u64 address_key(uint32_t as, uint32_t ptr) { return ((u64)as << 32) | (u64)ptr; }
 
-// the slot that holds `key`, or kEmpty (every key the rows kernel asks for was inserted)
-__device__ __forceinline__ u64 find_slot(const AddrTable& t, u64 key) {
-    const u64 h = slot_hash(key >> 32, key & 0xffffffffull);
-    for (u64 n = 0; n <= t.mask; ++n) {
-        const u64 s = (h + n) & t.mask;
-        const u64 k = __atomic_load_n(t.key + s, __ATOMIC_RELAXED);
-        if (k == key) return s;
-        if (k == kEmpty) break;
-    }
-    return kEmpty;
-}
-
-// PASS 1: claim the slot of every active triple's address (keys never change once set; the lane that claims a fresh slot counts it
-// in the slot's class, a class past its cap sets *overflow — the rule of bus_tally_kernel, so whether a table overflows is a function
-// of the traces and its size alone) and fold the timestamp in. PASS 2: the same walk; a triple whose timestamp is its slot's extreme
-// offers its witness. A multiplicity that is not +1 or -1 sets kFlagMagnitude and is left out.
+// PASS 1: claim the slot of every active triple's address (claim_slot, bus_shared.hpp) and fold the timestamp in. PASS 2: the same
+// walk; a triple whose timestamp is its slot's extreme offers its witness (every key it asks for was inserted). A multiplicity that
+// is not +1 or -1 sets kFlagMagnitude and is left out.
 template <bool FAST, int PASS>
 __global__ __launch_bounds__(kBlock) void boundary_walk_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
                                                                 uint32_t begin, uint32_t end, uint32_t air, AddrTable t, uint32_t* __restrict__ overflow,
@@ -210,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void boundary_walk_kernel(const uint32_t* _
         const u64 ts = bb::from_monty(eval_span<FAST>(lp, it.first_span + it.n_args, m, H, r, stk));
         const u64 key = address_key(as, ptr);
         if (PASS == 2) {
-            const u64 s = find_slot(t, key);
+            const u64 s = find_slot(t.v, key);
             if (s == kEmpty) continue;
             const u64 w = pack_witness(air, idx, r);
             if (cm < 0) {
@@ -220,33 +175,13 @@ __global__ __launch_bounds__(kBlock) void boundary_walk_kernel(const uint32_t* _
             }
             continue;
         }
-        const u64 h = slot_hash(as, ptr);
-        bool done = false;
-        for (u64 n = 0; n <= t.mask; ++n) {
-            const u64 s = (h + n) & t.mask;
-            u64 k = __atomic_load_n(t.key + s, __ATOMIC_RELAXED);
-            if (k == kEmpty) {
-                k = atomicCAS(t.key + s, kEmpty, key);
-                if (k == kEmpty) {
-                    k = key;
-                    if (atomicAdd(t.load + (s & t.class_mask) * kLoadStride, 1ull) >= t.class_cap) atomicOr(overflow, 1u);
-                }
-            }
-            if (k == key) {
-                // (a register is touched by every call: most triples lose against what the slot already holds and cost a load)
-                if (cm < 0) {
-                    if (__atomic_load_n(t.tmin + s, __ATOMIC_RELAXED) > ts) atomicMin(t.tmin + s, ts);
-                } else if (__atomic_load_n(t.tmax + s, __ATOMIC_RELAXED) < ts + 1) {
-                    atomicMax(t.tmax + s, ts + 1);
-                }
-                done = true;
-                break;
-            }
-            if ((n & 63) == 63 && __atomic_load_n(overflow, __ATOMIC_RELAXED)) break;
-        }
-        if (!done) {
-            atomicOr(overflow, 1u);
-            return;
+        const u64 s = claim_slot<1>(t.v, key, 0, overflow);
+        if (s == kEmpty) return;
+        // (a register is touched by every call: most triples lose against what the slot already holds and cost a load)
+        if (cm < 0) {
+            if (__atomic_load_n(t.tmin + s, __ATOMIC_RELAXED) > ts) atomicMin(t.tmin + s, ts);
+        } else if (__atomic_load_n(t.tmax + s, __ATOMIC_RELAXED) < ts + 1) {
+            atomicMax(t.tmax + s, ts + 1);
         }
     }
 }
@@ -255,22 +190,20 @@ __global__ __launch_bounds__(kBlock) void boundary_walk_kernel(const uint32_t* _
 // order (sorted afterwards), counts[2] = written
 __global__ __launch_bounds__(kBlock) void boundary_compact_kernel(AddrTable t, u64* __restrict__ keys, u64 cap, u64* __restrict__ counts) {
     const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
-    if (s > t.mask || t.key[s] == kEmpty) return;
+    if (s > t.v.mask || t.v.k0[s] == kEmpty) return;
     if (!keys) {
         atomicAdd(counts, 1ull);
         if (t.tmin[s] == kEmpty || t.tmax[s] == 0ull) atomicAdd(counts + 1, 1ull);
         return;
     }
     const u64 at = atomicAdd(counts + 2, 1ull);
-    if (at < cap) keys[at] = t.key[s];
+    if (at < cap) keys[at] = t.v.k0[s];
 }
 
 __device__ __forceinline__ uint32_t witness_arg(const AirDev* __restrict__ airs, u64 w, uint32_t j, uint32_t* stk) {
-    const AirDev a = airs[w >> (kRowBits + kInterBits)];
-    const uint32_t idx = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
-    const size_t r = (size_t)(w & ((1ull << kRowBits) - 1ull));
-    const uint32_t span = a.lp.d_inter[idx].first_span + 1 + j;
-    return a.lp.d_forms ? eval_span<true>(a.lp, span, a.m, (size_t)a.H, r, stk) : eval_span<false>(a.lp, span, a.m, (size_t)a.H, r, stk);
+    const Witness at = unpack_witness(w);
+    const AirDev a = airs[at.air];
+    return eval_span_of(a, a.lp.d_inter[at.inter].first_span + 1 + j, at.row, stk);
 }
 
 // Row r of the boundary trace (column-major, H_out rows, Montgomery) from the r-th smallest address: [is_valid, as, ptr, p_lo, p_hi,
@@ -289,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void boundary_rows_kernel(const u64* __rest
     if (r < n) {
         const u64 key = sorted[r];
         const uint32_t as = (uint32_t)(key >> 32), ptr = (uint32_t)key;
-        const u64 s = find_slot(t, key);
+        const u64 s = find_slot(t.v, key);
         v[0] = bb::to_monty(1u);
         v[1] = bb::to_monty(as);
         v[2] = bb::to_monty(ptr);
@@ -329,12 +262,12 @@ static_assert(kP2Out + 8 == kP2Width, "the layout of powdr_amd/system_airs.py po
 // the round constants arrive through scalar loads indexed by the wave-uniform round counter
 struct P2Def { uint32_t ext_rc[8][16]; uint32_t int_rc[13]; uint32_t diag[16]; };
 struct P2Key { bb::Ext al; bb::Ext blpow[kCompressIn + 1]; };
-struct P2Table { u64 *k0, *k1, *sum, *wit; u64 mask; u64* load; u64 class_mask, class_cap; };
+struct P2Table { TableView v; u64 *sum, *wit; };
 
 // bus_tally_kernel with the key cut down to the inputs: every active (interaction, row) of the compression bus in one AIR adds its
-// centred multiplicity to the slot of the fingerprint al + sum_j bl^(j+1) in_j (j < 16; 124 bits, two 64-bit halves claimed by
-// compare-and-swap) and offers its packed witness. Keys never change once set, sums are integer additions and the witness is a
-// minimum: what a slot ends with does not depend on the order of arrival; the load rule is the bus check's (bus_shared.hpp).
+// centred multiplicity to the slot of the fingerprint al + sum_j bl^(j+1) in_j (j < 16; 124 bits, the two key words of claim_slot,
+// bus_shared.hpp) and offers its packed witness. Keys never change once set, sums are integer additions and the witness is a
+// minimum: what a slot ends with does not depend on the order of arrival.
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void compress_tally_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
                                                                  uint32_t begin, uint32_t end, uint32_t air, P2Key key, P2Table t,
@@ -355,37 +288,10 @@ __global__ __launch_bounds__(kBlock) void compress_tally_kernel(const uint32_t* 
         const u64 a = (u64)d.c[0] | ((u64)d.c[1] << 32), b = (u64)d.c[2] | ((u64)d.c[3] << 32);
         const u64 witness = pack_witness(air, idx, r);
         const long long cm = (long long)bb::centred(bb::from_monty(mu));
-        const u64 h = slot_hash(a, b);
-        bool done = false;
-        for (u64 n = 0; n <= t.mask; ++n) {
-            const u64 s = (h + n) & t.mask;
-            u64 ka = __atomic_load_n(t.k0 + s, __ATOMIC_RELAXED);
-            if (ka == kEmpty) {
-                ka = atomicCAS(t.k0 + s, kEmpty, a);
-                if (ka == kEmpty) {
-                    ka = a;
-                    if (atomicAdd(t.load + (s & t.class_mask) * kLoadStride, 1ull) >= t.class_cap) atomicOr(overflow, 1u);
-                }
-            }
-            if (ka == a) {
-                u64 kb = __atomic_load_n(t.k1 + s, __ATOMIC_RELAXED);
-                if (kb == kEmpty) {
-                    kb = atomicCAS(t.k1 + s, kEmpty, b);
-                    if (kb == kEmpty) kb = b;
-                }
-                if (kb == b) {
-                    atomicAdd(t.sum + s, (u64)cm);
-                    atomicMin(t.wit + s, witness);
-                    done = true;
-                    break;
-                }
-            }
-            if ((n & 63) == 63 && __atomic_load_n(overflow, __ATOMIC_RELAXED)) break;
-        }
-        if (!done) {
-            atomicOr(overflow, 1u);
-            return;
-        }
+        const u64 s = claim_slot<2>(t.v, a, b, overflow);
+        if (s == kEmpty) return;
+        atomicAdd(t.sum + s, (u64)cm);
+        atomicMin(t.wit + s, witness);
     }
 }
 
@@ -393,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void compress_tally_kernel(const uint32_t* 
 // atomic per wave: the occupied lanes of a wave are counted by a ballot and take consecutive places behind the leader's.
 __global__ __launch_bounds__(kBlock) void compress_compact_kernel(P2Table t, u64* __restrict__ wit, u64* __restrict__ sum, u64 cap, u64* __restrict__ counts) {
     const u64 s = (u64)blockIdx.x * kBlock + threadIdx.x;
-    const bool occupied = s <= t.mask && t.k0[s] != kEmpty;
+    const bool occupied = s <= t.v.mask && t.v.k0[s] != kEmpty;
     const u64 lanes = __builtin_amdgcn_ballot_w64(occupied);
     if (!lanes) return;
     const unsigned lane = threadIdx.x & 63u;
@@ -461,9 +367,7 @@ __global__ __launch_bounds__(kBlock) void compress_rows_kernel(const u64* __rest
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = (uint32_t)i == j ? v : s[i];  // (registers: no run-time index into the state)
         }
-        long long v = (long long)sum[r] % (long long)bb::P;
-        if (v < 0) v += (long long)bb::P;
-        mult = bb::to_monty((uint32_t)v);
+        mult = bb::to_monty(sum_residue(sum[r]));
     }
     uint32_t* __restrict__ o = out + r;
     o[0] = mult;
@@ -516,9 +420,6 @@ struct SysReleased {
     }
 };
 
-// the AIRs that have interactions on `bus`, with their run in the prover's bus order and the values their programs read
-struct Part { size_t air; uint32_t begin, end; const uint32_t* vals; };
-
 // before any GPU call: false when an interaction on `bus` has not `n_args` arguments
 bool bus_arity_is(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_t n_args) {
     for (size_t a = 0; a < n_airs; ++a) {
@@ -530,20 +431,18 @@ bool bus_arity_is(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_
     return true;
 }
 
-int collect_parts(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, std::vector<Part>& parts, std::vector<AirDev>& air_tab) {
-    air_tab.assign(n_airs, AirDev{nullptr, 0, LogupProgram{}});
-    for (size_t a = 0; a < n_airs; ++a) {
-        PwProver* p = airs[a].prover;
-        if (!p->logup || !p->n_inter) continue;
-        PW_TRY(ensure_bus_order(p));
-        const auto at = std::lower_bound(p->h_bus_ids.begin(), p->h_bus_ids.end(), bus);
-        if (at == p->h_bus_ids.end() || *at != bus) continue;
-        const size_t k = at - p->h_bus_ids.begin();
-        Part part{a, p->h_bus_starts[k], p->h_bus_starts[k + 1], nullptr};
-        PW_TRY(stage_values(airs[a], &part.vals));
-        air_tab[a] = AirDev{part.vals, (u64)1 << airs[a].log_height, program_of(p)};
-        parts.push_back(part);
-    }
+// what the two traces built through a table begin with: the parts of the bus and the triples they hold; small = the walker's head |
+// the AIR table, the latter copied (from air_tab: it lives as long as the call)
+struct TableWalk { std::vector<Part> parts; std::vector<AirDev> air_tab; u64 triples = 0; WalkHead* d_head = nullptr; AirDev* d_airs = nullptr; };
+int begin_table_walk(SysCtx& cx, const PwSegmentAir* airs, size_t n_airs, uint32_t bus, TableWalk* w) {
+    PW_TRY(collect_parts(airs, n_airs, bus, w->parts, &w->air_tab));
+    for (const Part& part : w->parts) w->triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
+    cx.stat_triples = w->triples;
+    PW_TRY(cx.small.ensure(sizeof(WalkHead) + n_airs * sizeof(AirDev)));
+    cx.note();
+    w->d_head = cx.small.as<WalkHead>();
+    w->d_airs = (AirDev*)(w->d_head + 1);
+    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(w->d_airs, w->air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, stream()));
     return 0;
 }
 
@@ -578,7 +477,7 @@ extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, u
     const uint32_t table_rows = 1u << log_h;
     std::vector<Part> parts;
     std::vector<AirDev> air_tab;
-    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
+    PW_TRY(collect_parts(airs, n_airs, bus, parts, &air_tab));
     // small: foreign count, foreign witness, three statistics | AIR table | the witness's multiplicity, arguments
     const size_t off_air = 48, off_args = off_air + n_airs * sizeof(AirDev), small_bytes = off_args + (1 + PW_BUS_MAX_ARGS) * 4;
     PW_TRY(cx.small.ensure(small_bytes));
@@ -596,19 +495,13 @@ extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, u
     {
         ScopedKernelTimer timer("program_freq_kernel");
         for (const Part& part : parts) {
-            const PwSegmentAir& A = airs[part.air];
-            const PwProver* p = A.prover;
-            const size_t H = (size_t)1 << A.log_height;
-            const uint32_t rows = A.log_height >= 16 ? 4u : 1u;
-            const LogupProgram lp = program_of(p);
-            const dim3 grid(div_up(H, (size_t)kBlock * rows));
-            cx.stat_triples += (uint64_t)H * (part.end - part.begin);
-            if (lp.d_forms)
-                hipLaunchKernelGGL(program_freq_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, rows, lp, (const uint32_t*)p->bus_order.p, part.begin, part.end,
-                                   (uint32_t)part.air, pc_base, pc_step, d_program, table_rows, cx.sums.as<u64>(), d_foreign);
-            else
-                hipLaunchKernelGGL(program_freq_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, rows, lp, (const uint32_t*)p->bus_order.p, part.begin, part.end,
-                                   (uint32_t)part.air, pc_base, pc_step, d_program, table_rows, cx.sums.as<u64>(), d_foreign);
+            const Walked w = walked(airs[part.air]);
+            const uint32_t rows = airs[part.air].log_height >= 16 ? 4u : 1u;
+            cx.stat_triples += (uint64_t)w.H * (part.end - part.begin);
+            with_fast(w.lp, [&](auto fast) {
+                hipLaunchKernelGGL(program_freq_kernel<decltype(fast)::value>, dim3(div_up(w.H, (size_t)kBlock * rows)), dim3(kBlock), 0, st, part.vals, w.H, rows, w.lp,
+                                   w.order, part.begin, part.end, (uint32_t)part.air, pc_base, pc_step, d_program, table_rows, cx.sums.as<u64>(), d_foreign);
+            });
         }
     }
     hipLaunchKernelGGL(program_freq_finish_kernel, dim3(div_up(table_rows, kBlock)), dim3(kBlock), 0, st, cx.sums.as<u64>(), table_rows, d_freq_out);
@@ -623,19 +516,19 @@ extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, u
     if (foreign[0] && first_foreign) {
         // the tuple at the smallest foreign witness: its own multiplicity, one contribution
         PW_HIP_TRY(hipMemsetAsync(d_args, 0, (1 + PW_BUS_MAX_ARGS) * 4, st));
-        hipLaunchKernelGGL(witness_args_kernel, dim3(1), dim3(kBlock), 0, st, (const u64*)(d_foreign + 1), (u64)1, (const AirDev*)d_airs, (uint32_t)PW_BUS_MAX_ARGS,
-                           d_args + 1, d_args);
+        hipLaunchKernelGGL(witness_args_kernel, dim3(1), dim3(kBlock), 0, st, (const u64*)(d_foreign + 1), 1u, (u64)1, (const AirDev*)d_airs,
+                           (uint32_t)PW_BUS_MAX_ARGS, d_args + 1, d_args);
         PW_HIP_TRY(hipGetLastError());
         uint32_t words[1 + PW_BUS_MAX_ARGS];
         PW_HIP_TRY(hipMemcpyAsync(words, d_args, sizeof words, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
-        const u64 w = foreign[1];
+        const Witness w = unpack_witness(foreign[1]);
         PwBusTuple& t = *first_foreign;
         memset(&t, 0, sizeof t);
         t.bus = bus;
-        t.air = (uint32_t)(w >> (kRowBits + kInterBits));
-        t.interaction = (uint32_t)(w >> kRowBits) & ((1u << kInterBits) - 1u);
-        t.row = w & ((1ull << kRowBits) - 1ull);
+        t.air = w.air;
+        t.interaction = w.inter;
+        t.row = w.row;
         t.n_args = airs[t.air].prover->h_inter[t.interaction].n_args;
         for (uint32_t j = 0; j < t.n_args && j < PW_BUS_MAX_ARGS; ++j) t.args[j] = words[1 + j];
         t.net_multiplicity = words[0];
@@ -658,110 +551,54 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     *status = 0;
     (void)hipGetLastError();
     const SysReleased released{cx};
-    std::vector<Part> parts;
-    std::vector<AirDev> air_tab;
-    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
-    u64 triples = 0;
-    for (const Part& part : parts) triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
-    cx.stat_triples = triples;
-    // small: counters (4 u64: occupied | incomplete | written | unused) | overflow word, flags (+ padding: 16 bytes) | class loads | AIR table
-    const size_t load_bytes = kMaxClasses * kLoadStride * 8;
-    const size_t off_ovf = 32, off_load = off_ovf + 16, off_air = off_load + load_bytes, small_bytes = off_air + n_airs * sizeof(AirDev);
-    PW_TRY(cx.small.ensure(small_bytes));
-    cx.note();
-    char* base = cx.small.as<char>();
-    u64* d_counts = (u64*)base;
-    uint32_t* d_ovf = (uint32_t*)(base + off_ovf);
-    uint32_t* d_flags = d_ovf + 1;
-    u64* d_load = (u64*)(base + off_load);
-    AirDev* d_airs = (AirDev*)(base + off_air);
+    TableWalk tw;
+    PW_TRY(begin_table_walk(cx, airs, n_airs, bus, &tw));
     hipStream_t st = stream();
-    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
-
-    // the largest table: a power of two of slots, at most twice the triples walked (no segment touches more locations), within the
-    // caller's bound, or by default half of the device's room
-    u64 max_slots = 1024;
-    while (max_slots < 2 * triples) max_slots <<= 1;
-    size_t bound = table_bytes;
-    if (!bound) {
-        size_t avail = 0;
-        bound = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
-    }
-    while (max_slots && max_slots * kSlotBytes > bound) max_slots >>= 1;
-    if (!max_slots) {
-        *status = 2;
-        return 0;
-    }
-    auto walk = [&](int pass, const AddrTable& T) {
-        for (const Part& part : parts) {
-            const PwSegmentAir& A = airs[part.air];
-            const PwProver* p = A.prover;
-            const size_t H = (size_t)1 << A.log_height;
-            const LogupProgram lp = program_of(p);
-            const dim3 grid(div_up(H, kBlock));
-            const uint32_t* order = (const uint32_t*)p->bus_order.p;
-            if (lp.d_forms && pass == 1)
-                hipLaunchKernelGGL((boundary_walk_kernel<true, 1>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
-            else if (lp.d_forms)
-                hipLaunchKernelGGL((boundary_walk_kernel<true, 2>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
-            else if (pass == 1)
-                hipLaunchKernelGGL((boundary_walk_kernel<false, 1>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
-            else
-                hipLaunchKernelGGL((boundary_walk_kernel<false, 2>), grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, T, d_ovf, d_flags);
+    u64* d_counts = tw.d_head->c.counts;  // occupied | incomplete | written | unused
+    AddrTable T{};
+    auto walk = [&](auto pass) {
+        for (const Part& part : tw.parts) {
+            const Walked w = walked(airs[part.air]);
+            with_fast(w.lp, [&](auto fast) {
+                hipLaunchKernelGGL((boundary_walk_kernel<decltype(fast)::value, decltype(pass)::value>), dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H,
+                                   w.lp, w.order, part.begin, part.end, (uint32_t)part.air, T, &tw.d_head->c.overflow, &tw.d_head->c.flags);
+            });
         }
     };
-    // pass 1 into a small table first and into one four times as large while it overflows (the bus check's rule: what comes out depends
-    // on the last table alone)
-    u64 slots = std::min(max_slots, cx.start_log_slots ? (u64)1 << cx.start_log_slots : kStartSlots);
-    u64 counts[6] = {0, 0, 0, 0, 1, 0};  // occupied | incomplete | written | unused | overflow word, flags
-    AddrTable T{};
-    for (;;) {
-        int erc;
-        while ((erc = cx.table.ensure(slots * kSlotBytes)) != 0) {
-            (void)hipGetLastError();
-            if (erc != (int)hipErrorOutOfMemory) return erc;
-            if (slots <= 1) break;
-            max_slots = slots >>= 1;
-        }
-        if (!cx.table.p) break;
-        cx.note();
-        u64* tb = cx.table.as<u64>();
-        const u64 classes = std::min<u64>(kMaxClasses, std::max<u64>(1, slots / kMinClassSlots)), per_class = slots / classes;
-        T = AddrTable{tb, tb + slots, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots, slots - 1, d_load, classes - 1, per_class - per_class / 8};
-        {
-            ScopedKernelTimer timer("boundary_table_clear");
+    // pass 1 into tables that grow until one holds the locations (no segment touches more than its triples)
+    Grown g;
+    PW_TRY(grow_table(
+        cx.table, tw.d_head, tw.triples, kSlotBytes, table_bytes ? table_bytes : default_bound(cx.held()),
+        cx.start_log_slots ? (u64)1 << cx.start_log_slots : kStartSlots, "boundary_table_clear",
+        [&](u64* tb, const TableRule& rule) -> int {
+            const u64 slots = rule.mask + 1;
+            cx.note();
+            T = AddrTable{TableView{rule, tb, nullptr}, tb + slots, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots};
             PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 4 * slots * 8, st));
             PW_HIP_TRY(hipMemsetAsync(tb + 4 * slots, 0, slots * 8, st));
-            PW_HIP_TRY(hipMemsetAsync(d_counts, 0, off_air, st));  // counters, the overflow word, the flags, the class loads
-        }
-        {
+            return 0;
+        },
+        [&] {
             ScopedKernelTimer timer("boundary_walk_kernel");
-            walk(1, T);
-        }
-        hipLaunchKernelGGL(boundary_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64)0, d_counts);
-        PW_HIP_TRY(hipGetLastError());
-        PW_HIP_TRY(hipMemcpyAsync(counts, d_counts, 48, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-        ++cx.stat_tables;
-        if (!(uint32_t)counts[4] || slots >= max_slots) break;
-        slots = std::min(max_slots, slots * 4);
-    }
-    if (!cx.table.p || (uint32_t)counts[4]) {
+            walk(std::integral_constant<int, 1>{});
+        },
+        [&] { hipLaunchKernelGGL(boundary_compact_kernel, dim3(div_up(T.v.mask + 1, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64)0, d_counts); }, &g));
+    cx.stat_tables = g.tables;
+    if (g.no_table || g.overflowed()) {
         *status = 2;
         return (int)hipGetLastError();
     }
-    const u64 n = counts[0];
+    const u64 n = g.c.counts[0], slots = g.slots;
     cx.stat_slots = slots;
     cx.stat_occupied = n;
     *n_locations = n;
-    uint32_t lh = 1;
-    while (((u64)1 << lh) < n) ++lh;
+    const uint32_t lh = ceil_log2_at_least_1(n);
     *log_height = lh;
-    if ((uint32_t)(counts[4] >> 32) & kFlagMagnitude) {
+    if (g.c.flags & kFlagMagnitude) {
         *status = 3;
         return (int)hipGetLastError();
     }
-    if (counts[1]) {
+    if (g.c.counts[1]) {
         *status = 4;
         return (int)hipGetLastError();
     }
@@ -771,7 +608,7 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     }
     {
         ScopedKernelTimer timer("boundary_witness_kernel");
-        walk(2, T);
+        walk(std::integral_constant<int, 2>{});
     }
     const size_t H_out = (size_t)1 << lh;
     if (n) {
@@ -789,7 +626,7 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     }
     {
         ScopedKernelTimer timer("boundary_rows_kernel");
-        hipLaunchKernelGGL(boundary_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, n, T, (const AirDev*)d_airs, H_out, d_trace_out);
+        hipLaunchKernelGGL(boundary_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, n, T, (const AirDev*)tw.d_airs, H_out, d_trace_out);
     }
     PW_HIP_TRY(hipGetLastError());
     PW_HIP_TRY(hipStreamSynchronize(st));
@@ -810,24 +647,10 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
     *status = 0;
     (void)hipGetLastError();
     const SysReleased released{cx};
-    std::vector<Part> parts;
-    std::vector<AirDev> air_tab;
-    PW_TRY(collect_parts(airs, n_airs, bus, parts, air_tab));
-    u64 triples = 0;
-    for (const Part& part : parts) triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
-    cx.stat_triples = triples;
-    // small: counters (4 u64: occupied | unused | written | unused) | overflow word (+ padding: 16 bytes) | class loads | AIR table
-    const size_t load_bytes = kMaxClasses * kLoadStride * 8;
-    const size_t off_ovf = 32, off_load = off_ovf + 16, off_air = off_load + load_bytes, small_bytes = off_air + n_airs * sizeof(AirDev);
-    PW_TRY(cx.small.ensure(small_bytes));
-    cx.note();
-    char* base = cx.small.as<char>();
-    u64* d_counts = (u64*)base;
-    uint32_t* d_ovf = (uint32_t*)(base + off_ovf);
-    u64* d_load = (u64*)(base + off_load);
-    AirDev* d_airs = (AirDev*)(base + off_air);
+    TableWalk tw;
+    PW_TRY(begin_table_walk(cx, airs, n_airs, bus, &tw));
     hipStream_t st = stream();
-    if (n_airs) PW_HIP_TRY(hipMemcpyAsync(d_airs, air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, st));
+    u64* d_counts = tw.d_head->c.counts;  // occupied | unused | written | unused
 
     // the definition of the installed permutation, and the fingerprint's challenges: a fixed splitmix64 stream — nothing written
     // depends on them short of a collision, which costs a key its row and leaves its tuple unbalanced on the bus
@@ -841,92 +664,50 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
     P2Key key;
     {
         uint64_t sm = 0x70325f636f6d7072ull;
-        auto draw = [&]() {
-            bb::Ext e;
-            for (int k = 0; k < 4; ++k) {
-                uint64_t z = (sm += 0x9E3779B97F4A7C15ull);
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                e.c[k] = bb::to_monty((uint32_t)((z ^ (z >> 31)) % bb::P));
-            }
-            return e;
-        };
-        key.al = draw();
-        const bb::Ext bl = draw();
+        key.al = challenge(sm);
+        const bb::Ext bl = challenge(sm);
         key.blpow[0] = bb::ext_one();
         for (uint32_t j = 1; j <= kCompressIn; ++j) key.blpow[j] = bb::ext_mul(key.blpow[j - 1], bl);
     }
 
-    // the largest table: a power of two of slots, at most twice the triples walked, within the caller's bound or by default half of
-    // the device's room (the rule of pw_memory_boundary_trace)
-    u64 max_slots = 1024;
-    while (max_slots < 2 * triples) max_slots <<= 1;
-    size_t bound = table_bytes;
-    if (!bound) {
-        size_t avail = 0;
-        bound = device_room(cx.held(), &avail) ? avail / 2 : (size_t)1 << 30;
-    }
-    while (max_slots && max_slots * kP2SlotBytes > bound) max_slots >>= 1;
-    if (!max_slots) {
-        *status = 2;
-        return 0;
-    }
-    u64 slots = std::min(max_slots, start_log_slots ? (u64)1 << start_log_slots : kStartSlots);
-    u64 counts[5] = {0, 0, 0, 0, 1};  // occupied | unused | written | unused | overflow word
     P2Table T{};
-    for (;;) {
-        int erc;
-        while ((erc = cx.table.ensure(slots * kP2SlotBytes)) != 0) {
-            (void)hipGetLastError();
-            if (erc != (int)hipErrorOutOfMemory) return erc;
-            if (slots <= 1) break;
-            max_slots = slots >>= 1;
-        }
-        if (!cx.table.p) break;
-        cx.note();
-        u64* tb = cx.table.as<u64>();
-        const u64 classes = std::min<u64>(kMaxClasses, std::max<u64>(1, slots / kMinClassSlots)), per_class = slots / classes;
-        T = P2Table{tb, tb + slots, tb + 2 * slots, tb + 3 * slots, slots - 1, d_load, classes - 1, per_class - per_class / 8};
-        {
-            ScopedKernelTimer timer("compress_table_clear");
+    Grown g;
+    PW_TRY(grow_table(
+        cx.table, tw.d_head, tw.triples, kP2SlotBytes, table_bytes ? table_bytes : default_bound(cx.held()),
+        start_log_slots ? (u64)1 << start_log_slots : kStartSlots, "compress_table_clear",
+        [&](u64* tb, const TableRule& rule) -> int {
+            const u64 slots = rule.mask + 1;
+            cx.note();
+            T = P2Table{TableView{rule, tb, tb + slots}, tb + 2 * slots, tb + 3 * slots};
             PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 2 * slots * 8, st));
             PW_HIP_TRY(hipMemsetAsync(tb + 2 * slots, 0, slots * 8, st));
             PW_HIP_TRY(hipMemsetAsync(tb + 3 * slots, 0xFF, slots * 8, st));
-            PW_HIP_TRY(hipMemsetAsync(d_counts, 0, off_air, st));  // counters, the overflow word, the class loads
-        }
-        {
+            return 0;
+        },
+        [&] {
             ScopedKernelTimer timer("compress_tally_kernel");
-            for (const Part& part : parts) {
-                const PwSegmentAir& A = airs[part.air];
-                const PwProver* p = A.prover;
-                const size_t H = (size_t)1 << A.log_height;
-                const LogupProgram lp = program_of(p);
-                const dim3 grid(div_up(H, kBlock));
-                const uint32_t* order = (const uint32_t*)p->bus_order.p;
-                if (lp.d_forms)
-                    hipLaunchKernelGGL(compress_tally_kernel<true>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, key, T, d_ovf);
-                else
-                    hipLaunchKernelGGL(compress_tally_kernel<false>, grid, dim3(kBlock), 0, st, part.vals, H, lp, order, part.begin, part.end, (uint32_t)part.air, key, T, d_ovf);
+            for (const Part& part : tw.parts) {
+                const Walked w = walked(airs[part.air]);
+                with_fast(w.lp, [&](auto fast) {
+                    hipLaunchKernelGGL(compress_tally_kernel<decltype(fast)::value>, dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H, w.lp, w.order,
+                                       part.begin, part.end, (uint32_t)part.air, key, T, &tw.d_head->c.overflow);
+                });
             }
-        }
-        hipLaunchKernelGGL(compress_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64*)nullptr, (u64)0, d_counts);
-        PW_HIP_TRY(hipGetLastError());
-        PW_HIP_TRY(hipMemcpyAsync(counts, d_counts, 40, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-        ++cx.stat_tables;
-        if (!(uint32_t)counts[4] || slots >= max_slots) break;
-        slots = std::min(max_slots, slots * 4);
-    }
-    if (!cx.table.p || (uint32_t)counts[4]) {
+        },
+        [&] {
+            hipLaunchKernelGGL(compress_compact_kernel, dim3(div_up(T.v.mask + 1, kBlock)), dim3(kBlock), 0, st, T, (u64*)nullptr, (u64*)nullptr, (u64)0, d_counts);
+        },
+        &g));
+    cx.stat_tables = g.tables;
+    if (g.no_table || g.overflowed()) {
         *status = 2;
         return (int)hipGetLastError();
     }
-    const u64 n = counts[0];
+    const u64 n = g.c.counts[0], slots = g.slots;
     cx.stat_slots = slots;
     cx.stat_occupied = n;
     *n_rows = n;
-    uint32_t lh = 1;
-    while (((u64)1 << lh) < n) ++lh;
+    const uint32_t lh = ceil_log2_at_least_1(n);
     *log_height = lh;
     if (lh > cap_log_height) {
         *status = 1;
@@ -953,7 +734,7 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
     {
         ScopedKernelTimer timer("compress_rows_kernel");
         hipLaunchKernelGGL(compress_rows_kernel, dim3(div_up(H_out, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.sorted.p, (const u64*)cx.sorted_vals.p, n,
-                           (const AirDev*)d_airs, def, H_out, d_trace_out);
+                           (const AirDev*)tw.d_airs, def, H_out, d_trace_out);
     }
     PW_HIP_TRY(hipGetLastError());
     PW_HIP_TRY(hipStreamSynchronize(st));
