@@ -91,7 +91,7 @@ def check(rc: int, what: str):
 
 CALL_STATS = ("gather_sparse_jobs", "gather_whole_jobs", "gather_chunk_jobs", "gather_calls", "bus_fast_interactions",
               "bus_interpreted_interactions", "bus_binned_windows", "bus_direct_calls", "bus_xbc_calls", "jit_launches",
-              "interpreter_launches")
+              "interpreter_launches", "ntt_strided_fixed_launches")
 
 
 def call_stats(reset: bool = False) -> dict:

@@ -50,7 +50,7 @@ inline uint32_t ceil_log2_at_least_1(unsigned long long rows) {
 enum CallStat : int {
     kStatGatherSparseJobs = 0, kStatGatherWholeJobs, kStatGatherChunkJobs, kStatGatherCalls,
     kStatBusFastInteractions, kStatBusInterpretedInteractions, kStatBusBinnedWindows, kStatBusDirectCalls,
-    kStatBusXbcCalls, kStatJitKernelLaunches, kStatInterpreterKernelLaunches, kStatCount = 16
+    kStatBusXbcCalls, kStatJitKernelLaunches, kStatInterpreterKernelLaunches, kStatNttStridedFixedLaunches, kStatCount = 16
 };
 uint64_t* call_stats();  // this thread's kStatCount counters
 

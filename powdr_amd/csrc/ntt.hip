@@ -611,6 +611,95 @@ __global__ __launch_bounds__(kBlock) void lde_fused12_kernel(const uint32_t* __r
     }
 }
 
+// The strided stage group of the fused schedule at 2^20 rows (K = 8 stages: stages 0-7 of the size-2^20 inverse transform into `tmp`,
+// stages 13-20 of the size-2^21 forward one in place on `out`) with its geometry as constants — what ntt_group_kernel<DIF, 13, 0> does
+// for the group make_group(DIF, DIF ? 20 : 21, DIF ? 0 : 13, 8, 5), word for word: a 2^13-element tile of 256 rows of 32 consecutive
+// words (c = 5: 128-byte segments), LB = log2 of the word distance between two rows (the group's `lowbits`), tile t of a column at
+// word 32 t. Two radix-16 rounds, two slots per lane and round:
+//   "hi", window 9-12: slot (tid, m) holds rows (tid >> 5) + 8 m + 16 rho, column tid & 31
+//   "lo", window 5-8:  slot (tid, m) holds rows 16 ((tid >> 5) + 8 m) + rho, column tid & 31
+// DIF runs hi then lo, DIT lo then hi; the first round loads from HBM, the second stores to it, LDS (lds_phys) in between.
+// Straight-line code: the tile and twiddle positions are wave-uniform bases (scalar registers) plus ONE 32-bit byte offset per lane
+// and round kind, the per-element strides constants on the scalar side; a lane issues all 32 loads of its two slots and its three
+// twiddle bases (one per hi slot; the lo slots of a lane share theirs: it depends on the column only) before the first butterfly.
+// cst_lo / cst_hi: the coset constants of the two rounds' top stages (GroupParams::cst; the Montgomery one without a coset: a product
+// that returns its canonical argument). The forward group reduces to [0, p) on its store (it is the transform's last).
+// A workgroup reads and writes its own tile's positions only, so the forward group is safe in place.
+template <int RB>
+__device__ __forceinline__ constexpr uint32_t strided8_words(int lb, int m, int rho) {  // slot m, element rho: words from the lane's base
+    return RB == 9 ? (((uint32_t)(8 * m) << lb) + ((uint32_t)rho << (lb + 4))) : (((uint32_t)m << (lb + 7)) + ((uint32_t)rho << lb));
+}
+// base + off4 bytes as the global access with a scalar base and a 32-bit lane offset (pwj::ld's form). `base` — wave-uniform, a constant
+// stride already added — passes through an empty asm statement that pins it to a scalar register pair: left to itself the compiler
+// moves the constant into a 64-bit lane addition per access (two VALU instructions each, 128 per wave).
+// (The pointers are named global ones: behind the asm statement the compiler no longer sees where they came from.)
+typedef __attribute__((address_space(1))) const char* GlobalBytesIn;
+typedef __attribute__((address_space(1))) char* GlobalBytesOut;
+__device__ __forceinline__ uint32_t ld_off4(const uint32_t* base, uint32_t off4) {
+    GlobalBytesIn b = (GlobalBytesIn)base;
+    asm("" : "+s"(b));
+    return *(__attribute__((address_space(1))) const uint32_t*)(b + off4);
+}
+__device__ __forceinline__ void st_off4(uint32_t* base, uint32_t off4, uint32_t v) {
+    GlobalBytesOut b = (GlobalBytesOut)base;
+    asm("" : "+s"(b));
+    *(__attribute__((address_space(1))) uint32_t*)(b + off4) = v;
+}
+
+template <bool DIF, int K>
+__global__ __launch_bounds__(kBlock) void ntt_strided_kernel(const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride,
+                                                             const uint32_t* __restrict__ tw, uint32_t cst_lo, uint32_t cst_hi) {
+    static_assert(K == 8, "the 2^20-row geometry; other heights take ntt_group_kernel");
+    constexpr int LB = DIF ? 12 : 13;
+    constexpr int RB0 = DIF ? 9 : 5, RB1 = DIF ? 5 : 9;  // the two rounds' windows, in execution order
+    __shared__ uint32_t tile[(1 << 13) + ((1 << 13) >> 5)];
+    const uint32_t tid = threadIdx.x, row = tid >> 5, col = tid & 31u;
+    const size_t t0 = (size_t)blockIdx.x << 5;
+    const uint32_t* src = in + (size_t)blockIdx.y * in_stride + t0;
+    uint32_t* dst = out + (size_t)blockIdx.y * out_stride + t0;
+    const uint32_t off_hi = 4u * ((row << LB) | col), off_lo = 4u * ((row << (LB + 4)) | col);  // byte offsets of the lane's slot 0
+    const uint32_t off0 = RB0 == 9 ? off_hi : off_lo, off1 = RB1 == 9 ? off_hi : off_lo;
+    // ---- every load of the tile, then the twiddle bases ----
+    uint32_t x[2][16];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) x[m][rho] = ld_off4(src + strided8_words<RB0>(LB, m, rho), off0);
+    }
+    // hi: w^g, g = the slot's row and column and the tile (its global index below the window); lo: w^(16 g), g = tile and column
+    uint32_t b_hi[2], b_lo;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) b_hi[m] = ld_off4(tw + t0 + ((uint32_t)(8 * m) << LB), off_hi);
+    b_lo = ld_off4(tw + (t0 << 4), col << 6);
+    if (!DIF) {
+        b_lo = bb::mul(b_lo, cst_lo);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) b_hi[m] = bb::mul(b_hi[m], cst_hi);
+    }
+    // padded LDS positions of the lane's slot 0; slot 1 lies 264 (hi) / 4 224 (lo) words further
+    const uint32_t p_hi = lds_phys(tid), p_lo = (row << 9) + (row << 4) + col;
+    const uint32_t p0 = RB0 == 9 ? p_hi : p_lo, p1 = RB1 == 9 ? p_hi : p_lo;
+    constexpr uint32_t kSlot0 = RB0 == 9 ? 264u : 4224u, kSlot1 = RB1 == 9 ? 264u : 4224u;
+    // ---- first round: registers -> LDS ----
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        slot_butterflies<DIF, 4>(x[m], RB0 == 9 ? b_hi[m] : b_lo);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) tile[p0 + kSlot0 * m + f12_off<RB0>(rho)] = x[m][rho];
+    }
+    __syncthreads();
+    // ---- second round: LDS -> HBM ----
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        uint32_t y[16];
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) y[rho] = tile[p1 + kSlot1 * m + f12_off<RB1>(rho)];
+        slot_butterflies<DIF, 4>(y, RB1 == 9 ? b_hi[m] : b_lo);
+#pragma unroll
+        for (int rho = 0; rho < 16; ++rho) st_off4(dst + strided8_words<RB1>(LB, m, rho), off1, DIF ? y[rho] : bb::reduce_2p(y[rho]));
+    }
+}
+
 struct Tables {
     uint32_t* tw_fwd = nullptr;    // g_n^j, j < 2^(n-1)
     uint32_t* tw_inv = nullptr;    // g_n^-j
@@ -834,6 +923,14 @@ void launch_group_kernel(int logt, int mode, dim3 grid, const uint32_t* src, uin
     else with_mode(std::integral_constant<int, 12>{});
 }
 
+// Is `g` on 2^logt tiles the group ntt_strided_kernel<DIF, 8> is written for? (The kernel's constants restate what make_group derives.)
+template <bool DIF>
+bool strided8_geometry(const GroupParams& g, int logt) {
+    return logt == 13 && g.n == (DIF ? 20 : 21) && g.s0 == (DIF ? 0 : 13) && g.k == 8 && g.c == 5 && g.lowbits == (DIF ? 12 : 13) && g.B == 13 &&
+           g.n_tiles == (DIF ? 128ull : 256ull) && g.n_rounds == 2 && g.logr[0] == 4 && g.logr[1] == 4 && g.rb[0] == (DIF ? 9 : 5) &&
+           g.rb[1] == (DIF ? 5 : 9) && (DIF || g.canonical_out) && !g.fold && !g.n_sel;
+}
+
 // The groups of a plan, one launch per group and column chunk, on tiles of 2^logt elements: the first from `in` with the loads of
 // `mode` (ntt_group_kernel: 1 = EXPAND with `expand_scale_br`, 2 = FOLD with cs), the others in place on `out` with plain loads.
 // Tile-invariant groups read their twiddles from a table. cs: a sub-coset transform (FOLD / SELECT, the coset's constants in every
@@ -841,7 +938,7 @@ void launch_group_kernel(int logt, int mode, dim3 grid, const uint32_t* src, uin
 template <bool DIF>
 void launch_groups(std::vector<GroupParams>& groups, int logt, int mode, const uint32_t* in, uint32_t* out, size_t in_stride, size_t out_stride,
                    uint32_t cols, const uint32_t* tw, const uint32_t* expand_scale_br, const char* name, const CosetSpec* cs = nullptr,
-                   const uint32_t* coset_pw = nullptr) {
+                   const uint32_t* coset_pw = nullptr, bool fused_schedule = false) {
     const uint32_t* src = in;
     size_t src_stride = in_stride;
     for (auto& g : groups) {
@@ -871,6 +968,21 @@ void launch_groups(std::vector<GroupParams>& groups, int logt, int mode, const u
                 hipLaunchKernelGGL(coset_table_kernel, dim3(div_up(a.total, 256)), dim3(256), 0, stream(), gt->d, cs->d_scratch, a);
                 table = cs->d_scratch;
             }
+        }
+        // the fused schedule's strided group at 2^20 rows: ntt_strided_kernel<DIF, 8> (lde_fused passes fused_schedule unless
+        // POWDR_NTT_STRIDED_GENERIC=1); the same timer name, so reports sum the group under one label whichever kernel ran
+        if (fused_schedule && mode == 0 && !table && !cs && strided8_geometry<DIF>(g, logt)) {
+            const uint32_t one = bb::R_MOD_P;
+            const uint32_t cst_lo = g.coset ? g.cst[DIF ? 1 : 0] : one, cst_hi = g.coset ? g.cst[DIF ? 0 : 1] : one;
+            for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
+                ScopedKernelTimer t(name);
+                call_stats()[kStatNttStridedFixedLaunches] += 1;
+                hipLaunchKernelGGL((ntt_strided_kernel<DIF, 8>), dim3((unsigned)g.n_tiles, cc), dim3(kBlock), 0, stream(), src + (size_t)c0 * src_stride,
+                                   out + (size_t)c0 * out_stride, src_stride, out_stride, tw, cst_lo, cst_hi);
+            });
+            src = out;
+            src_stride = out_stride;
+            continue;
         }
         for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
             // (the sub-coset transforms' first group — FOLD loads, the sub-coset's own twiddle table — has a timer of its own)
@@ -985,13 +1097,17 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
     const int ka = n < 12 ? n : 12;
     const char* force_generic = getenv("POWDR_LDE_FUSED_GENERIC");
     const bool spec12 = ka == 12 && !(force_generic && atoi(force_generic) != 0);
+    // POWDR_NTT_STRIDED_GENERIC=1 (read per call): the strided groups stay on ntt_group_kernel at every height
+    const char* strided_generic = getenv("POWDR_NTT_STRIDED_GENERIC");
+    const bool strided_fixed = !(strided_generic && atoi(strided_generic) != 0);
     const uint32_t hinv = bb::inv(bb::to_monty((uint32_t)(((uint64_t)1 << n) % bb::P)));
     const uint32_t* src = in;
     size_t src_stride = in_stride;
     if (n > ka) {
         int logt = 12;
         auto groups = plan_groups(true, n, 0, logt, n - ka, true);
-        launch_groups<true>(groups, logt, 0, in, tmp, in_stride, tmp_stride, cols, tn->tw_inv, nullptr, "ntt_group_kernel<dif>");
+        launch_groups<true>(groups, logt, 0, in, tmp, in_stride, tmp_stride, cols, tn->tw_inv, nullptr, "ntt_group_kernel<dif>", nullptr, nullptr,
+                            strided_fixed);
         src = tmp;
         src_stride = tmp_stride;
     }
@@ -1030,7 +1146,7 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
         auto groups = plan_groups(false, n + 1, ka + 1, logt, n + 1, true);
         if (!groups.empty()) groups.back().canonical_out = 1;
         launch_groups<false>(groups, logt, 0, out, out, out_stride, out_stride, cols, t1->tw_fwd, nullptr, "ntt_group_kernel<dit>", nullptr,
-                             spec12 ? coset_pw : nullptr);
+                             spec12 ? coset_pw : nullptr, strided_fixed);
     }
     return (int)hipGetLastError();
 }
