@@ -429,6 +429,56 @@ void pw_empirical_set_fingerprint_mask(uint64_t mask);
  * scratch bytes held at once, scratch bytes held now. */
 void pw_empirical_last_stats(uint64_t* out);
 
+/* ---- superblock detection: basic-block runs, window counts and pc counts of an execution -------------------------
+ * What the reference's `detect_superblocks` / `pc_count` (autoprecompiles/src/blocks/mod.rs, execution_profile.rs) compute from the
+ * pc trace of an execution, and the body of `count_and_update_execution` (pgo/cell/selection.rs) on a copy that stays on the device.
+ * Input: the N pcs in execution order (pw_execution_blocks_from_pcs: a device array, read on the calling thread's launch stream) or
+ * the instruction AIRs' traces exactly as pw_empirical_detect takes them (pw_execution_blocks_from_traces: the same bridge
+ * evaluation and time order, one copy of the code). `blocks` as for pw_empirical_detect; it must list EVERY block that runs,
+ * one-instruction blocks included. max_bb in 1 .. 255 = the reference's superblock_max_bb_count.
+ * Heads: position 0 is a head; a head at p of block (s, n) requires pc[p + k] = s + k pc_step for every k < n with p + k < N, and
+ * the next head is p + n (a last block cut off by the end of the list counts). Heads of one-instruction blocks cut the head
+ * sequence; the maximal stretches of multi-instruction heads between cuts are the runs.
+ * Result (host side; sequences of start pcs in lexicographic order, a prefix before its extensions — a BTreeMap<Vec<u64>, _>):
+ *   pc counts    per executed pc its number of occurrences, ascending;
+ *   runs         the distinct runs, each with the number of times it occurs;
+ *   superblocks  for every L in 1 .. max_bb every sequence of L start pcs that occurs as a window inside some run, with the sum over
+ *                ALL run instances of the leftmost-greedy non-overlapping occurrences (on a match advance by L, otherwise by 1:
+ *                [1,2,1] occurs once in [1,2,1,2,1]). Counts are 64-bit: the reference's u32 wrap is not reproduced.
+ * Equal runs are found by 128-bit fingerprints and then VERIFIED element by element against the first run of their group; on a
+ * mismatch the grouping is repeated under another seed, three in all. Windows are named exactly, level by level, by sorting.
+ * The contract of pw_empirical_detect: the call synchronises before it returns; scratch is per thread, bounded by scratch_bytes
+ * (0: half of what the device budget allows) and released on every path; the handle keeps 8 bytes per multi-instruction head on the
+ * device. -1 before any GPU call: a NULL pointer, pc_step == 0, a malformed block table, max_bb 0 or above 255, n >= 2^32 (2^32
+ * rows), and for the trace route what pw_empirical_detect refuses. An empty execution gives an empty result, status 0.
+ * *status: 0 = *out is set (pw_execution_blocks_destroy frees it); 2 = the bound is too small, *info = bytes needed (before an
+ * element is read: an upper bound that always suffices); 3 = not block-structured: a head pc that is no start_pc or an in-block pc
+ * that does not follow, *info = the smallest offending position (the reference panics on the first and mis-walks on the second) —
+ * on the trace route the time key of that row; 4 and 7 as for pw_empirical_detect (trace route); 6 = fingerprint collisions under
+ * every seed. Checked in the order 2, 7, 4, 3, 2, 6. With a non-zero status no result exists and 0 is returned. */
+typedef struct PwExecutionBlocks PwExecutionBlocks;
+int pw_execution_blocks_from_pcs(const uint32_t* d_pcs, uint64_t n, uint32_t pc_step, const PwBasicBlock* blocks, size_t n_blocks,
+                                 uint32_t max_bb, size_t scratch_bytes, PwExecutionBlocks** out, uint32_t* status, uint64_t* info);
+int pw_execution_blocks_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bus,
+                                    uint32_t pc_step, const PwBasicBlock* blocks, size_t n_blocks, uint32_t max_bb,
+                                    size_t scratch_bytes, PwExecutionBlocks** out, uint32_t* status, uint64_t* info);
+void pw_execution_blocks_destroy(PwExecutionBlocks* e);
+/* Read-outs into caller arrays (a NULL array is skipped). sizes[6] = pcs, distinct runs, start pcs of all runs, superblocks, start
+ * pcs of all superblocks, multi-instruction heads kept on the device. offsets: runs + 1 / superblocks + 1 (into the start pcs). */
+void pw_execution_blocks_sizes(const PwExecutionBlocks* e, uint64_t* sizes);
+void pw_execution_blocks_read_pc_counts(const PwExecutionBlocks* e, uint32_t* pcs, uint64_t* counts);
+void pw_execution_blocks_read_runs(const PwExecutionBlocks* e, uint64_t* offsets, uint32_t* start_pcs, uint64_t* counts);
+void pw_execution_blocks_read_superblocks(const PwExecutionBlocks* e, uint64_t* offsets, uint32_t* start_pcs, uint64_t* counts);
+/* *count = the leftmost-greedy non-overlapping occurrences of the needle (len start pcs, host memory) over the runs the handle
+ * holds now. remove != 0: the counted windows are taken out and what is left of each run becomes separate runs — no later window
+ * crosses a removed stretch. A needle with an unknown pc, or longer than every run, gives 0. -1: a NULL pointer or len == 0. */
+int pw_execution_blocks_count(PwExecutionBlocks* e, const uint32_t* needle_start_pcs, uint32_t len, int remove, uint64_t* count);
+/* A TEST HOOK, as pw_empirical_set_fingerprint_mask: ANDed onto both fingerprint halves of the calling thread's later calls. */
+void pw_execution_blocks_set_fingerprint_mask(uint64_t mask);
+/* Of the calling thread's last pw_execution_blocks_from_*, out[7]: levels run, clusters counted by pointer doubling, seeds tried,
+ * heads, runs, the most scratch bytes held at once (the handle's included), scratch bytes held now. */
+void pw_execution_blocks_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -1,12 +1,9 @@
 // Empirical constraints on the device (include/powdr_prover.h pw_empirical_detect): per executed pc the 1st and 99th
 // percentile of every main column, per listed basic block the partition of its cells into classes that held equal values in every
 // instance of the block — from the instruction AIRs' raw traces, read through the provers' own execution-bridge interactions.
-//   index      empirical_index_kernel     one lane per (AIR, row) evaluates the bridge exactly as the bus check does: an active row
-//                                         writes its time key (segment << 32 | timestamp) and pc at its GLOBAL row number, a padding
-//                                         row the key ~0 — no compaction, so nothing depends on an order of arrival; a radix sort of
-//                                         (time key, row number) puts the active rows first, in time order
-//   structure  empirical_time_kernel      neighbours with one key (status 4), the number of active rows, the pcs in time order;
-//              empirical_structure_kernel every row looks its pc up in the block table: a head checks the pcs of the rows behind it,
+//   index      time_index.hpp             the executed rows by time key and their pcs in time order (statuses 7 and 4): the stage shared
+//                                         with the superblock detector (execution_blocks.hip, §5q)
+//   structure  empirical_structure_kernel every row looks its pc up in the block table: a head checks the pcs of the rows behind it,
 //                                         any other in-block row that its head is where it must be (status 3)
 //   runs       a STABLE radix sort by pc keeps the time order inside a pc: one contiguous run per pc whose j-th row belongs to the
 //              j-th instance of the pc's block; run-length encoding gives the pcs and their counts; empirical_loc_kernel turns row
@@ -22,6 +19,7 @@
 // the default scratch bound.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
+#include "time_index.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -42,8 +40,8 @@ namespace pw {
 namespace {
 
 using namespace bus;
+using namespace time_index;
 
-constexpr uint32_t kNoPc = 0xffffffffu;
 constexpr int kMergeRounds = 4;            // distinct runs a wave merges before its lanes fall back to one atomic each
 constexpr uint32_t kVerifyChunk = 1024;    // instances a workgroup of the verification compares
 constexpr int kSeeds = 3;                  // groupings tried before status 6
@@ -57,80 +55,6 @@ __host__ __device__ __forceinline__ u64 mix64(u64 z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-// counters: [0] active rows | [1] smallest (air << 32 | row) with bad multiplicities | [2] smallest duplicate key | [3] smallest
-// offending head key | [4] smallest pc in two AIRs | [5] runs (32 bits)
-template <bool FAST>
-__global__ __launch_bounds__(kBlock) void empirical_index_kernel(const uint32_t* __restrict__ m, size_t H, LogupProgram lp, const uint32_t* __restrict__ order,
-                                                                  uint32_t begin, uint32_t end, uint32_t air, uint32_t segment, u64 g0,
-                                                                  u64* __restrict__ tkey, uint32_t* __restrict__ pcs, u64* __restrict__ counters) {
-    __shared__ uint32_t stack_lds[kStackCap * kBlock];
-    uint32_t* stk = stack_lds + threadIdx.x;
-    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    bool active = false, bad = false;
-    uint32_t n_recv = 0, pc = 0, ts = 0;
-    if (r < H) {
-        for (uint32_t i = begin; i < end; ++i) {
-            const uint32_t idx = order[i];
-            const LogupInteraction it = lp.d_inter[idx];
-            const uint32_t mu = eval_span<FAST>(lp, it.first_span, m, H, r, stk);
-            if (mu == 0u) continue;
-            active = true;
-            const int32_t cm = bb::centred(bb::from_monty(mu));
-            if (cm == -1) {
-                if (n_recv++ == 0u) {
-                    pc = bb::from_monty(eval_span<FAST>(lp, it.first_span + 1, m, H, r, stk));
-                    ts = bb::from_monty(eval_span<FAST>(lp, it.first_span + 2, m, H, r, stk));
-                }
-            } else if (cm != 1) {
-                bad = true;
-            }
-        }
-        bad = active && (bad || n_recv != 1u);
-        const bool ok = active && !bad;
-        tkey[g0 + r] = ok ? ((u64)segment << 32) | (u64)ts : kEmpty;
-        pcs[g0 + r] = ok ? pc : kNoPc;
-    }
-    if (__builtin_amdgcn_ballot_w64(bad)) {  // (never on honest traces)
-        const u64 w = wave_min(bad ? ((u64)air << 32) | (u64)r : kEmpty);
-        if ((threadIdx.x & 63u) == 0u) atomicMin(counters + 1, w);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void empirical_iota_kernel(uint32_t* __restrict__ out, u64 n) {
-    const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) out[i] = (uint32_t)i;
-}
-
-// over the rows in time order: the pcs in that order, the number of active rows (the padding keys sort last), a key held twice
-__global__ __launch_bounds__(kBlock) void empirical_time_kernel(const u64* __restrict__ tkey_s, const uint32_t* __restrict__ idx_s, const uint32_t* __restrict__ pcs,
-                                                                 u64 M, uint32_t* __restrict__ pc_t, u64* __restrict__ counters) {
-    const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= M) return;
-    const u64 k = tkey_s[i];
-    pc_t[i] = pcs[idx_s[i]];
-    if (k == kEmpty) return;
-    const u64 next = i + 1 < M ? tkey_s[i + 1] : kEmpty;
-    if (next == kEmpty) counters[0] = i + 1;
-    else if (next == k) atomicMin(counters + 2, k);
-}
-
-// the block that holds pc as one of its instructions: its index and the instruction's, or false
-__device__ __forceinline__ bool find_block(const PwBasicBlock* __restrict__ blocks, uint32_t n_blocks, uint32_t pc_step, uint32_t pc, uint32_t* b, uint32_t* k) {
-    uint32_t lo = 0, hi = n_blocks;  // the last block with start_pc <= pc
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (blocks[mid].start_pc <= pc) lo = mid + 1;
-        else hi = mid;
-    }
-    if (!lo) return false;
-    const PwBasicBlock B = blocks[lo - 1];
-    const uint32_t d = pc - B.start_pc;
-    if (d % pc_step != 0u || d / pc_step >= B.n_instructions) return false;
-    *b = lo - 1;
-    *k = d / pc_step;
-    return true;
 }
 
 // A head (instruction 0 of a listed block) checks the pcs of the n - 1 rows behind it; any other in-block row checks that the row k
@@ -320,11 +244,6 @@ struct EmpReleased {
     }
 };
 
-size_t sort_pairs_temp(size_t n) {
-    size_t bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 64u, stream());
-    return std::max<size_t>(bytes, 16);
-}
 size_t sort_keys_temp(size_t n, unsigned end_bit) {
     size_t bytes = 0;
     (void)rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, n, 0u, end_bit, stream());
@@ -395,25 +314,11 @@ extern "C" void pw_empirical_read_cells(const PwEmpirical* e, uint32_t* instruct
 
 extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bus, uint32_t pc_step, const PwBasicBlock* blocks,
                                    size_t n_blocks, size_t scratch_bytes, PwEmpirical** out, uint32_t* status, uint64_t* info) {
-    if (!out || !status || !info || !pc_step || (!blocks && n_blocks) || n_blocks >= ((size_t)1 << 31) || bus >= bb::P || !airs_well_formed(airs, n_airs)) return -1;
-    for (size_t b = 0; b < n_blocks; ++b) {
-        const u64 end = (u64)blocks[b].start_pc + (u64)pc_step * blocks[b].n_instructions;
-        if (!blocks[b].n_instructions || end > (b + 1 < n_blocks ? (u64)blocks[b + 1].start_pc : (u64)1 << 32)) return -1;
-    }
-    u64 M = 0;
-    for (size_t a = 0; a < n_airs; ++a) {
-        const PwProver* p = airs[a].prover;
-        if (!p->logup) continue;
-        bool on_bus = false;
-        for (const LogupInteraction& it : p->h_inter)
-            if (bb::from_monty(it.bus_monty) == bus) {
-                if (it.n_args != 2) return -1;
-                on_bus = true;
-            }
-        if (on_bus) {
-            M += (u64)1 << airs[a].log_height;
-        }
-    }
+    if (!out || !status || !info || !pc_step || bus >= bb::P || !airs_well_formed(airs, n_airs)) return -1;
+    if (!blocks_well_formed(blocks, n_blocks, pc_step)) return -1;
+    const long long rows = bridge_rows(airs, n_airs, bus);
+    if (rows < 0) return -1;
+    const u64 M = (u64)rows;
     if (M >= ((u64)1 << 32)) return -1;  // row numbers and run positions are 32-bit words
     EmpCtx& cx = g_emp;
     cx.peak = 0;
@@ -480,54 +385,14 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     PW_HIP_TRY(hipMemcpyAsync((void*)d_parts, h_parts.data(), h_parts.size() * sizeof(EPart), hipMemcpyHostToDevice, st));
     if (n_blocks) PW_HIP_TRY(hipMemcpyAsync((void*)d_blocks, blocks, n_blocks * sizeof(PwBasicBlock), hipMemcpyHostToDevice, st));
 
-    // ---- index ----
-    PW_TRY(cx.tkey.ensure(M * 8));
-    PW_TRY(cx.tkey_s.ensure(M * 8));
-    PW_TRY(cx.idx.ensure(M * 4));
-    PW_TRY(cx.idx_s.ensure(M * 4));
-    PW_TRY(cx.pcs.ensure(M * 4));
-    PW_TRY(cx.pc_t.ensure(M * 4));
-    cx.note();
-    {
-        ScopedKernelTimer timer("empirical_index_kernel");
-        for (size_t k = 0; k < parts.size(); ++k) {
-            const Part& part = parts[k];
-            const Walked w = walked(airs[part.air]);
-            const uint32_t seg = segment_of_air ? segment_of_air[part.air] : 0u;
-            with_fast(w.lp, [&](auto fast) {
-                hipLaunchKernelGGL(empirical_index_kernel<decltype(fast)::value>, dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H, w.lp, w.order, part.begin,
-                                   part.end, (uint32_t)part.air, seg, h_parts[k].g0, cx.tkey.as<u64>(), cx.pcs.as<uint32_t>(), d_counters);
-            });
-        }
-        hipLaunchKernelGGL(empirical_iota_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, cx.idx.as<uint32_t>(), M);
-    }
-    PW_HIP_TRY(hipGetLastError());
-    {
-        ScopedKernelTimer timer("empirical_sort_time");
-        size_t temp_bytes = sort_pairs_temp(M);
-        PW_TRY(cx.temp.ensure(temp_bytes));
-        cx.note();
-        PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.tkey.as<u64>(), cx.tkey_s.as<u64>(), cx.idx.as<uint32_t>(), cx.idx_s.as<uint32_t>(), (size_t)M, 0u,
-                                             64u, st));
-    }
+    // ---- index (time_index.hpp) ----
     u64 counters[8];
     {
-        ScopedKernelTimer timer("empirical_structure_kernel");
-        hipLaunchKernelGGL(empirical_time_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.tkey_s.p, (const uint32_t*)cx.idx_s.p,
-                           (const uint32_t*)cx.pcs.p, M, cx.pc_t.as<uint32_t>(), d_counters);
-        PW_HIP_TRY(hipGetLastError());
-        PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
-        PW_HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (counters[1] != kEmpty) {
-        *status = 7;
-        *info = counters[1];
-        return (int)hipGetLastError();
-    }
-    if (counters[2] != kEmpty) {
-        *status = 4;
-        *info = counters[2];
-        return (int)hipGetLastError();
+        std::vector<u64> g0;
+        for (const EPart& part : h_parts) g0.push_back(part.g0);
+        PW_TRY(rows_in_time_order(airs, segment_of_air, parts, g0, M, d_counters, Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
+                                  Names{"empirical_index_kernel", "empirical_sort_time", "empirical_structure_kernel"}, [&] { cx.note(); }, counters, status, info));
+        if (*status) return (int)hipGetLastError();
     }
     const u64 N = counters[0];
     cx.stat_rows = N;

@@ -310,6 +310,11 @@ pub struct PwBasicBlock {
 pub struct PwEmpirical {
     _private: [u8; 0],
 }
+/// the opaque result of `pw_execution_blocks_from_*`: host-side tables and the head sequence kept on the device
+#[repr(C)]
+pub struct PwExecutionBlocks {
+    _private: [u8; 0],
+}
 /// `pw_memory_tree_set_mode`: every level above level 0 hashed again from the level below
 pub const PW_MEMORY_TREE_REBUILD: u32 = 0;
 /// `pw_memory_tree_set_mode`: only the touched paths hashed, every other stored node moved
@@ -465,6 +470,26 @@ extern "C" {
     pub fn pw_empirical_set_fingerprint_mask(mask: u64);
     /// out[6]: panels, seeds, active rows, cells verified, peak scratch bytes, scratch bytes held
     pub fn pw_empirical_last_stats(out: *mut u64);
+    /// Superblock detection: pc counts, distinct basic-block runs and the greedy counts of every window of up to
+    /// `max_bb` blocks, from the execution's pcs on the device. `status` 0 = `*out` is set (free it with `pw_execution_blocks_destroy`).
+    pub fn pw_execution_blocks_from_pcs(d_pcs: *const u32, n: u64, pc_step: u32, blocks: *const PwBasicBlock, n_blocks: usize, max_bb: u32,
+                                        scratch_bytes: usize, out: *mut *mut PwExecutionBlocks, status: *mut u32, info: *mut u64) -> c_int;
+    /// the same from the instruction AIRs' traces, read as `pw_empirical_detect` reads them
+    pub fn pw_execution_blocks_from_traces(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bus: u32, pc_step: u32,
+                                           blocks: *const PwBasicBlock, n_blocks: usize, max_bb: u32, scratch_bytes: usize,
+                                           out: *mut *mut PwExecutionBlocks, status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_execution_blocks_destroy(e: *mut PwExecutionBlocks);
+    /// sizes[6] = pcs, runs, start pcs of all runs, superblocks, start pcs of all superblocks, heads kept on the device
+    pub fn pw_execution_blocks_sizes(e: *const PwExecutionBlocks, sizes: *mut u64);
+    pub fn pw_execution_blocks_read_pc_counts(e: *const PwExecutionBlocks, pcs: *mut u32, counts: *mut u64);
+    pub fn pw_execution_blocks_read_runs(e: *const PwExecutionBlocks, offsets: *mut u64, start_pcs: *mut u32, counts: *mut u64);
+    pub fn pw_execution_blocks_read_superblocks(e: *const PwExecutionBlocks, offsets: *mut u64, start_pcs: *mut u32, counts: *mut u64);
+    /// the greedy non-overlapping occurrences of a candidate over what is left of the execution; `remove` takes them out
+    pub fn pw_execution_blocks_count(e: *mut PwExecutionBlocks, needle_start_pcs: *const u32, len: u32, remove: c_int, count: *mut u64) -> c_int;
+    /// a test hook: ANDed onto both fingerprint halves of this thread's later `pw_execution_blocks_from_*` calls (0 = full width)
+    pub fn pw_execution_blocks_set_fingerprint_mask(mask: u64);
+    /// out[7]: levels, clusters counted by pointer doubling, seeds, heads, runs, peak scratch bytes, scratch bytes held
+    pub fn pw_execution_blocks_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
