@@ -831,6 +831,42 @@ int pw_lde_subcoset(const uint32_t* d_coeffs, uint32_t width, uint32_t log_heigh
  * leaves first, root last. */
 int pw_merkle_commit(const uint32_t* d_matrix, size_t height, uint32_t width, uint32_t* d_digests);
 
+/* The commitment kernels form by form. Every call validates its arguments first and launches nothing when it refuses: -1 for a
+ * malformed argument (a NULL pointer where one is needed, a zero height / width / n_cols, and what each call lists below),
+ * hipErrorInvalidValue for a digest or state pointer that is not 16-byte aligned (the kernels store 16 bytes at a time). Words on the
+ * device are Montgomery words, as everywhere.
+ *
+ * Row digests of a column-major matrix (any height >= 1, column c at d_matrix + c * col_stride, col_stride >= height): the digest of
+ * row j goes to the 8 words at slot j * digest_stride + digest_offset of d_digests (digest_offset < digest_stride), so a matrix that
+ * holds the rows r + 2^b i of a committed one fills its share of the leaves with (2^b, r). Other slots are not written. */
+int pw_merkle_leaf_hash(const uint32_t* d_matrix, size_t height, uint32_t width, size_t col_stride, uint32_t* d_digests,
+                        size_t digest_stride, size_t digest_offset);
+
+/* One RUN of the row digests of a level whose hashed row is the concatenation of several matrices' rows. The run's n_cols columns are
+ * those of a matrix (d_matrix, col_stride >= height) or of a device array of n_cols device column pointers (d_cols): exactly one of
+ * the two. Row j < height of the run is row j * row_stride + row_offset of the level (row_offset < row_stride). pos0 < 8 = the number
+ * of columns the level's earlier runs absorbed, mod 8. first: the sponge states start at zero (pos0 must be 0); otherwise they are
+ * read from d_state (16 words per row of the level). last: the digests are written to d_digests (8 words per row of the level);
+ * otherwise the states go back to d_state, as words that only a later run of the same level can read. Rows the run does not name are
+ * not touched. Same digests as one sponge over the whole row. */
+int pw_merkle_leaf_absorb(const uint32_t* d_matrix, size_t col_stride, const uint32_t* const* d_cols, uint32_t n_cols, uint32_t pos0,
+                          size_t height, size_t row_stride, size_t row_offset, uint32_t* d_state, uint32_t* d_digests, int first, int last);
+
+/* The mixed-height tree of a segment commitment over the levels of 2^L, ..., 1 rows. n_cols_by_log[k] and external_by_log[k], k = 0..L
+ * (host arrays): the number of columns of height 2^k, and whether the level's row digests are already in place (level L: the first
+ * 2^L * 8 words of d_digests; level k < L: d_inject + 2^k * 8) instead of being hashed here. d_cols: ONE device array of device column
+ * pointers, level L's n_cols_by_log[L] first, then level L - 1's, ..., level 0's last (an external level's entries are skipped, not
+ * read; NULL if every populated level is external). Level L must be populated or external; L <= 27. d_digests: (2^(L+1) - 1) * 8 words,
+ * the levels of 2^L, 2^(L-1), ..., 1 nodes back to back: node j of the level of n nodes = compress(child j, child j + n), then, where
+ * the level is populated or external, compress(node, digest of row j). d_inject: 2^L * 8 words of scratch (NULL if no level below L is
+ * populated or external). */
+int pw_merkle_commit_mixed(const uint32_t* const* d_cols, const uint32_t* n_cols_by_log, const uint32_t* external_by_log, uint32_t L,
+                           uint32_t* d_digests, uint32_t* d_inject);
+
+/* The tree of a FRI round: d_values = 2 * half extension elements (4 words each), leaf i = the first 8 words of
+ * Poseidon2(v[i] || v[i + half] || 0^8), then the binary tree; half a power of two; d_digests gets (2 * half - 1) * 8 words. */
+int pw_merkle_commit_ext_pairs(const uint32_t* d_values, size_t half, uint32_t* d_digests);
+
 /* Host-side Poseidon2 permutation used by the transcript (canonical words in/out). This is also the known-answer-test
  * hook: after pw_set_poseidon2_constants a maintainer feeds it the vector of the backend's own Poseidon2 test. */
 void pw_poseidon2_permute_host(uint32_t* state16);

@@ -1057,6 +1057,56 @@ extern "C" int pw_merkle_commit(const uint32_t* d_matrix, size_t height, uint32_
     return merkle_commit_matrix(d_matrix, height, width, height, d_digests);
 }
 
+// The commitment kernels form by form: each validates its arguments (no launch on a refusal) and forwards to the function of the same
+// name in prover_internal.hpp. -1: a malformed argument; hipErrorInvalidValue: a digest / state pointer the uint4 stores cannot take.
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+extern "C" int pw_merkle_leaf_hash(const uint32_t* d_matrix, size_t height, uint32_t width, size_t col_stride, uint32_t* d_digests,
+                                   size_t digest_stride, size_t digest_offset) {
+    (void)hipGetLastError();
+    if (!d_matrix || !d_digests || !height || !width || col_stride < height || digest_offset >= digest_stride) return -1;
+    if (misaligned16(d_digests)) return (int)hipErrorInvalidValue;
+    return merkle_leaf_hash(d_matrix, height, width, col_stride, d_digests, digest_stride, digest_offset);
+}
+
+extern "C" int pw_merkle_leaf_absorb(const uint32_t* d_matrix, size_t col_stride, const uint32_t* const* d_cols, uint32_t n_cols, uint32_t pos0,
+                                     size_t height, size_t row_stride, size_t row_offset, uint32_t* d_state, uint32_t* d_digests, int first,
+                                     int last) {
+    (void)hipGetLastError();
+    if ((d_matrix == nullptr) == (d_cols == nullptr) || !n_cols || pos0 >= 8 || (first && pos0) || !height) return -1;
+    if (d_matrix && col_stride < height) return -1;
+    if (!row_stride || row_offset >= row_stride) return -1;
+    if ((!d_state && !(first && last)) || (last && !d_digests)) return -1;  // the state is read unless `first`, written unless `last`
+    if (misaligned16(d_state) || misaligned16(d_digests)) return (int)hipErrorInvalidValue;
+    return merkle_leaf_absorb(d_matrix, col_stride, d_cols, n_cols, pos0, height, row_stride, row_offset, d_state, d_digests, first != 0, last != 0);
+}
+
+extern "C" int pw_merkle_commit_mixed(const uint32_t* const* d_cols, const uint32_t* n_cols_by_log, const uint32_t* external_by_log, uint32_t L,
+                                      uint32_t* d_digests, uint32_t* d_inject) {
+    (void)hipGetLastError();
+    if (!n_cols_by_log || !external_by_log || !d_digests || L > 27) return -1;
+    if (!n_cols_by_log[L] && !external_by_log[L]) return -1;
+    MixedLevelCols by_log[28];
+    size_t first = 0;
+    bool resident = false, below = false;
+    for (int k = (int)L; k >= 0; --k) {  // the table holds level k's n_cols_by_log[k] pointers whether the level is external or not
+        by_log[k] = MixedLevelCols{d_cols ? d_cols + first : nullptr, n_cols_by_log[k], external_by_log[k]};
+        first += n_cols_by_log[k];
+        resident = resident || (n_cols_by_log[k] && !external_by_log[k]);
+        below = below || (k < (int)L && (n_cols_by_log[k] || external_by_log[k]));
+    }
+    if ((resident && !d_cols) || (below && !d_inject)) return -1;
+    if (misaligned16(d_digests) || misaligned16(d_inject)) return (int)hipErrorInvalidValue;
+    return merkle_commit_mixed(by_log, (int)L, d_digests, d_inject);
+}
+
+extern "C" int pw_merkle_commit_ext_pairs(const uint32_t* d_values, size_t half, uint32_t* d_digests) {
+    (void)hipGetLastError();
+    if (!d_values || !d_digests || !half || (half & (half - 1))) return -1;
+    if (misaligned16(d_digests)) return (int)hipErrorInvalidValue;
+    return merkle_commit_ext_pairs(reinterpret_cast<const bb::Ext*>(d_values), half, d_digests);
+}
+
 extern "C" int pw_set_poseidon2_constants(const uint32_t* ext_rc, const uint32_t* int_rc) {
     return poseidon2_set_constants(ext_rc, int_rc);
 }

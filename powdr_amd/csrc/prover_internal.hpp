@@ -73,8 +73,7 @@ uint32_t* merkle_root_mailbox(uint32_t** device_ptr);
 // Mixed-height commitment of a segment (oracle/stark_segment.inc `MixedTree`): by_log[k] = the columns of all matrices of
 // height 2^k (device array of device column pointers, AIR order; n_cols = 0 if there is none), k = 0..L, by_log[L] non-empty.
 // digests: levels of 2^L, 2^(L-1), ..., 1 nodes concatenated ((2^(L+1) - 1) * 8 words), level of n nodes:
-// node j = compress(child j, child j + n) [then compress(node, H(rows j of the height-n matrices))]. d_inject: 2^(L-1) * 8 words
-// of scratch. NOTE the same scratch is reused level after level on the launch stream.
+// node j = compress(child j, child j + n) [then compress(node, H(rows j of the height-n matrices))].
 struct MixedLevelCols {
     const uint32_t* const* d_cols;
     uint32_t n_cols;

@@ -16,6 +16,7 @@ class PwStarkConfig(C.Structure):
 
 PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create", "pw_prover_create_logup", "pw_verify_logup", "pw_prover_trace_root", "pw_prover_set_bus_seed", "pw_prover_logup_path", "pw_prove_airs", "pw_verify_airs", "pw_prove_segment", "pw_verify_segment", "pw_commitment_digest", "pw_logup_group_starts", "pw_prover_width", "pw_prover_reserve", "pw_prover_stream_log_blocks", "pw_prover_max_constraint_degree", "pw_prover_destroy", "pw_prover_prove", "pw_prover_prove_consuming", "pw_prover_stream_log_blocks_consuming", "pw_trace_from_coefficients", "pw_prover_device_bytes",
                   "pw_lde_batch", "pw_lde_fused", "pw_lde_subcoset", "pw_merkle_commit", "pw_poseidon2_permute_host",
+                  "pw_merkle_leaf_hash", "pw_merkle_leaf_absorb", "pw_merkle_commit_mixed", "pw_merkle_commit_ext_pairs",
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
@@ -85,6 +86,15 @@ lib.pw_set_device_budget.argtypes = [C.c_size_t]
 lib.pw_get_device_budget.restype = C.c_size_t
 lib.pw_merkle_commit.restype = C.c_int
 lib.pw_merkle_commit.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+lib.pw_merkle_leaf_hash.restype = C.c_int
+lib.pw_merkle_leaf_hash.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t]
+lib.pw_merkle_leaf_absorb.restype = C.c_int
+lib.pw_merkle_leaf_absorb.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_int]
+lib.pw_merkle_commit_mixed.restype = C.c_int
+lib.pw_merkle_commit_mixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.pw_merkle_commit_ext_pairs.restype = C.c_int
+lib.pw_merkle_commit_ext_pairs.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
 lib.pw_poseidon2_permute_host.argtypes = [C.c_void_p]
 
 

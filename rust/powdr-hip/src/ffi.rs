@@ -580,6 +580,10 @@ extern "C" {
     pub fn pw_lde_fused(d_trace: *const u32, width: u32, log_height: u32, d_tmp: *mut u32, d_lde: *mut u32) -> c_int;
     pub fn pw_lde_subcoset(d_coeffs: *const u32, width: u32, log_height: u32, log_blocks: u32, r: u32, d_scale: *mut u32, d_out: *mut u32) -> c_int;
     pub fn pw_merkle_commit(d_matrix: *const u32, height: usize, width: u32, d_digests: *mut u32) -> c_int;
+    pub fn pw_merkle_leaf_hash(d_matrix: *const u32, height: usize, width: u32, col_stride: usize, d_digests: *mut u32, digest_stride: usize, digest_offset: usize) -> c_int;
+    pub fn pw_merkle_leaf_absorb(d_matrix: *const u32, col_stride: usize, d_cols: *const *const u32, n_cols: u32, pos0: u32, height: usize, row_stride: usize, row_offset: usize, d_state: *mut u32, d_digests: *mut u32, first: c_int, last: c_int) -> c_int;
+    pub fn pw_merkle_commit_mixed(d_cols: *const *const u32, n_cols_by_log: *const u32, external_by_log: *const u32, l: u32, d_digests: *mut u32, d_inject: *mut u32) -> c_int;
+    pub fn pw_merkle_commit_ext_pairs(d_values: *const u32, half: usize, d_digests: *mut u32) -> c_int;
     pub fn pw_prover_specialise(p: *mut PwProver) -> c_int;
     pub fn pw_prover_specialised(p: *const PwProver, n_kernels: *mut usize, code_bytes: *mut usize, n_chunks: *mut usize) -> c_int;
     pub fn pw_prove_segments_multi(devices: *const c_int, n_workers: usize, segment_cells: *const u64, n_segments: usize,
