@@ -479,6 +479,65 @@ void pw_execution_blocks_set_fingerprint_mask(uint64_t mask);
  * heads, runs, the most scratch bytes held at once (the handle's included), scratch bytes held now. */
 void pw_execution_blocks_last_stats(uint64_t* out);
 
+/* ---- selecting APC calls: optimistic constraints and overlapping candidates ----------------------------------------
+ * What the reference's `ApcCandidates` (autoprecompiles/src/execution/candidates.rs, with the evaluator of execution/evaluator.rs)
+ * decides while an execution runs, computed from the whole execution at once.
+ * The execution is n_states = N + 1 states: state i is the machine before instruction i, state N the machine after the last one;
+ * the clock of state i is i. d_pcs[i] is its pc, d_regs[r * n_states + i] register r (n_regs >= 0 registers of 32 bits; device
+ * arrays, read on the calling thread's launch stream). limb_bits in 1 .. 32.
+ * APC a (host array, any order, apc_id = the index) starts at start_pc, spans cycle_count >= 1 instructions and owns the constraints
+ * [first_constraint, first_constraint + n_constraints) of the flat host array. A constraint says left == right; an operand is
+ * kind 0 Number(value), kind 1 Pc(instr_idx) = the pc of state s + instr_idx, or kind 2 RegisterLimb(instr_idx, reg, limb) =
+ * (register reg of state s + instr_idx >> limb * limb_bits) & (2^limb_bits - 1), s being the candidate's first state. A constraint's
+ * step is the largest instr_idx among its literals, 0 without one.
+ * Semantics: for i = 0 .. N: check_conditions(state i); extract_calls(); try_insert(state i, a) for every APC with start_pc ==
+ * d_pcs[i], in ascending apc_id. After state N: abort_in_progress(), extract_calls(). So a candidate (a, s) is inserted iff every
+ * constraint of step 0 holds, fails at the first step k <= cycle_count with a false constraint (a constraint of a larger step is
+ * never checked), is done at state s + cycle_count with the range [s, s + cycle_count), and is aborted if s + cycle_count > N.
+ * extract_calls folds the done candidates in insertion order over all pairs (i < j): if neither is discarded and the ranges overlap,
+ * the lower rank is discarded, rank = (priority, length, earlier insertion). The fold is order-dependent — a candidate discards
+ * lower-ranked followers until it meets a higher-ranked one, and what it discarded stays discarded — and is reproduced exactly.
+ * Result (host side): the calls (apc_id, from, to) in insertion order; per APC seven 64-bit counters: pc matches, refused at
+ * insertion, failed later, aborted at the end, done, discarded by the fold, calls (matches = refused + failed + aborted + done,
+ * done = discarded + calls); the number of positions covered by calls.
+ * pw_apc_calls_from_traces takes the instruction AIRs' traces exactly as pw_execution_blocks_from_traces takes them (the same bridge
+ * evaluation and time order): the states are the pcs of the active rows in time order and final_pc, the pc after the last row (the
+ * bridge's receive does not carry it). Pcs only: there are no registers, so a RegisterLimb operand is refused. segment_of_air must
+ * name ONE segment (NULL = 0): the reference aborts candidates at a segment's end, so segments are selected one by one. The result
+ * also holds the time key (segment << 32 | timestamp) of every position.
+ * The contract of pw_empirical_detect: the call synchronises before it returns; scratch is per thread, bounded by scratch_bytes
+ * (0: half of what the device budget allows) and released on every path; the APC table and the constraints are copied to the device
+ * once per call. -1 before any GPU call: a NULL pointer, cycle_count == 0, a constraint span outside the array, an operand kind
+ * above 2, reg >= n_regs, limb_bits outside 1 .. 32, limb * limb_bits >= 32, n_states >= 2^32 or n_states times the largest number
+ * of APCs sharing a start pc >= 2^32, two segment numbers on the trace route, and there what pw_empirical_detect refuses.
+ * n_states == 0 gives an empty result, status 0.
+ * *status: 0 = *out is set (pw_apc_calls_destroy frees it); 2 = the bound is too small, *info = bytes that always suffice (decided
+ * before an element is read); 4 and 7 as for pw_empirical_detect (trace route). Checked in the order 2, 7, 4. With a non-zero
+ * status no result exists and 0 is returned. */
+typedef struct { uint32_t kind, instr_idx, reg, limb; uint64_t value; } PwApcOperand;
+typedef struct { PwApcOperand left, right; } PwApcConstraint;
+typedef struct { uint32_t start_pc, cycle_count; uint64_t priority, first_constraint, n_constraints; } PwApc;
+typedef struct PwApcCalls PwApcCalls;
+int pw_apc_calls_from_states(const uint32_t* d_pcs, const uint32_t* d_regs, uint64_t n_states, uint32_t n_regs, uint32_t limb_bits,
+                             const PwApc* apcs, size_t n_apcs, const PwApcConstraint* constraints, size_t n_constraints,
+                             size_t scratch_bytes, PwApcCalls** out, uint32_t* status, uint64_t* info);
+int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bus, uint32_t final_pc,
+                             const PwApc* apcs, size_t n_apcs, const PwApcConstraint* constraints, size_t n_constraints,
+                             size_t scratch_bytes, PwApcCalls** out, uint32_t* status, uint64_t* info);
+void pw_apc_calls_destroy(PwApcCalls* e);
+/* Read-outs into caller arrays (a NULL array is skipped). sizes[5] = calls, APCs, positions covered by calls, states, time keys
+ * (trace route: N, otherwise 0). apc_ids / from / to: one per call; counters: 7 per APC in the order above; keys: one per position. */
+void pw_apc_calls_sizes(const PwApcCalls* e, uint64_t* sizes);
+void pw_apc_calls_read_calls(const PwApcCalls* e, uint32_t* apc_ids, uint64_t* from, uint64_t* to);
+void pw_apc_calls_read_counters(const PwApcCalls* e, uint64_t* counters);
+void pw_apc_calls_read_time_keys(const PwApcCalls* e, uint64_t* keys);
+/* A TEST HOOK, in the style of pw_execution_blocks_set_fingerprint_mask: components of more than n candidates take the long path
+ * of the fold in the calling thread's later calls (0 = the default, 32), so that small inputs reach it. The result does not change. */
+void pw_apc_calls_set_long_threshold(uint64_t n);
+/* Of the calling thread's last pw_apc_calls_from_*, out[7]: candidates, valid (done) candidates, components, the longest component,
+ * components on the long path, the most scratch bytes held at once, scratch bytes held now. */
+void pw_apc_calls_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -315,6 +315,38 @@ pub struct PwEmpirical {
 pub struct PwExecutionBlocks {
     _private: [u8; 0],
 }
+/// an operand of an optimistic constraint: kind 0 `Number(value)`, 1 `Pc(instr_idx)`, 2 `RegisterLimb(instr_idx, reg, limb)`
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwApcOperand {
+    pub kind: u32,
+    pub instr_idx: u32,
+    pub reg: u32,
+    pub limb: u32,
+    pub value: u64,
+}
+/// an optimistic constraint `left == right`
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwApcConstraint {
+    pub left: PwApcOperand,
+    pub right: PwApcOperand,
+}
+/// an APC of `pw_apc_calls_from_*`: its constraints are `[first_constraint, first_constraint + n_constraints)` of the flat array
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct PwApc {
+    pub start_pc: u32,
+    pub cycle_count: u32,
+    pub priority: u64,
+    pub first_constraint: u64,
+    pub n_constraints: u64,
+}
+/// the opaque host-side result of `pw_apc_calls_from_*`
+#[repr(C)]
+pub struct PwApcCalls {
+    _private: [u8; 0],
+}
 /// `pw_memory_tree_set_mode`: every level above level 0 hashed again from the level below
 pub const PW_MEMORY_TREE_REBUILD: u32 = 0;
 /// `pw_memory_tree_set_mode`: only the touched paths hashed, every other stored node moved
@@ -490,6 +522,26 @@ extern "C" {
     pub fn pw_execution_blocks_set_fingerprint_mask(mask: u64);
     /// out[7]: levels, clusters counted by pointer doubling, seeds, heads, runs, peak scratch bytes, scratch bytes held
     pub fn pw_execution_blocks_last_stats(out: *mut u64);
+    /// APC call selection: the calls the reference's `ApcCandidates` extracts, from the execution's states on the
+    /// device. `status` 0 = `*out` is set (free it with `pw_apc_calls_destroy`).
+    pub fn pw_apc_calls_from_states(d_pcs: *const u32, d_regs: *const u32, n_states: u64, n_regs: u32, limb_bits: u32, apcs: *const PwApc, n_apcs: usize,
+                                    constraints: *const PwApcConstraint, n_constraints: usize, scratch_bytes: usize, out: *mut *mut PwApcCalls,
+                                    status: *mut u32, info: *mut u64) -> c_int;
+    /// the same from the instruction AIRs' traces of ONE segment (pcs only); `final_pc` = the pc after the last row
+    pub fn pw_apc_calls_from_traces(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bus: u32, final_pc: u32, apcs: *const PwApc,
+                                    n_apcs: usize, constraints: *const PwApcConstraint, n_constraints: usize, scratch_bytes: usize,
+                                    out: *mut *mut PwApcCalls, status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_apc_calls_destroy(e: *mut PwApcCalls);
+    /// sizes[5] = calls, APCs, positions covered by calls, states, time keys
+    pub fn pw_apc_calls_sizes(e: *const PwApcCalls, sizes: *mut u64);
+    pub fn pw_apc_calls_read_calls(e: *const PwApcCalls, apc_ids: *mut u32, from: *mut u64, to: *mut u64);
+    /// 7 per APC: matches, refused, failed, aborted, done, discarded, calls
+    pub fn pw_apc_calls_read_counters(e: *const PwApcCalls, counters: *mut u64);
+    pub fn pw_apc_calls_read_time_keys(e: *const PwApcCalls, keys: *mut u64);
+    /// a test hook: components of more than `n` candidates take the fold's long path in this thread's later calls (0 = the default)
+    pub fn pw_apc_calls_set_long_threshold(n: u64);
+    /// out[7]: candidates, valid, components, longest component, components on the long path, peak scratch bytes, scratch bytes held
+    pub fn pw_apc_calls_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
