@@ -236,6 +236,20 @@ PW_HD int64_t swide_mul(int32_t x, int32_t k) {
     return (int64_t)x * k;
 #endif
 }
+// The forward (Cooley-Tukey) butterfly on signed representatives: (a, b) -> (a + b w, a - b w) for a Montgomery twiddle w given as
+// its centred representative (|w| <= p / 2, from a table) and nw = -w. Both outputs are ONE signed reduction of a kappa + b (+-w)
+// with kappa = R mod p (Montgomery 1, 0.133 p: centred as it stands): the product a kappa, two multiply-adds, two 2-instruction
+// reductions — 7 instructions, no conditional anything. |a|, |b| < p keeps |t| <= (p - 1)^2 inside smont's domain and the outputs
+// below 0.969 p in magnitude, so a chain of butterflies needs no correction in between (exact figures: ntt::bounds in ntt.hip).
+PW_HD void dit_signed(int32_t& a, int32_t& b, int32_t w, int32_t nw, int32_t kappa = (int32_t)R_MOD_P) {
+    const int64_t ak = smul_uniform(a, kappa);
+    const int64_t tx = ak + (int64_t)b * w, ty = ak + (int64_t)b * nw;
+    a = smont(tx);
+    b = smont(ty);
+}
+// a signed representative in (-p, p) -> canonical: min(x, x + p) on the unsigned view (a negative x is huge as unsigned, and x + p wraps
+// into [0, p); a non-negative one is below x + p < 2^32)
+PW_HD uint32_t canonical_of_centred(int32_t x) { return umin((uint32_t)x, (uint32_t)x + P); }
 // |y| < 128 p (floor(y / 2^7) must fit an int32)  ->  a representative of y mod p in (-0.0313 p, 1.0313 p); Poseidon2's last layer
 // hands it [15.3 p, 84.7 p) and gets [0, 1.0207 p) (exact figures: p2::bounds in poseidon2.hpp, computed by tools/poseidon2_bounds.py):
 // q = floor(floor(y / 2^7) * 273 / 2^32) with 273 = floor(2^39 / p); y - q p = y (1 - 273 p / 2^39) + (rounding of the two floors,

@@ -491,15 +491,17 @@ __global__ __launch_bounds__(kBlock) void lde_fused_kernel(const uint32_t* __res
 // rounds each way, one passive bit on the forward side), every window, slot count, LDS offset and table offset a constant:
 //   A  DIF window 8-11: HBM -> registers -> LDS            (twiddles: per-lane table loads)
 //   B  DIF window 4-7:  LDS -> LDS                         (per-lane table loads, requested during A)
-//   C  DIF window 0-3:  LDS -> registers, times 1 / H      (15 wave-uniform twiddles)
-//   D  DIT window 1-4, both duplicates: registers -> LDS   (2 x 15 wave-uniform twiddles)
+//   C  DIF window 0-3:  LDS -> registers                   (15 wave-uniform twiddles)
+//   D  DIT window 1-4, both duplicates: registers -> LDS   (2 x 15 wave-uniform twiddles; its first stage multiplies by 1 / H)
 //   E  DIT window 5-8:  LDS -> LDS, two slots              (ONE set of per-lane twiddles for both slots, requested during C)
 //   F  DIT window 9-12: LDS -> HBM, two slots              (per-lane table loads, requested during E)
 // No scale-and-duplicate pass: lane t ends C holding coefficients 16 t .. 16 t + 15 of the tile, and the two slots of D whose inputs
 // are their duplicates — positions 32 t + 2 rho + b of the doubled tile, b = the passive bit — are the slots 2 t and 2 t + 1, so the
 // lane runs both from its registers (one set of inputs, two sets of twiddles). The coset factor s^k is in the forward twiddles (stage
 // s of the size-2^(n+1) transform carries s^(2^(n-s)): the table is built per height, fused12_twiddles, and the strided DIT groups
-// multiply their round bases by GroupParams::cst); 1 / H is one product per coefficient at the end of C.
+// multiply their round bases by GroupParams::cst); 1 / H is in the constants of D's first stage.
+// A, B, C run the unsigned butterflies of slot_butterflies on canonical words; D, E, F the signed ones below (ntt::bounds), and F's
+// store returns to canonical words.
 // Per tile: 5 barriers (the generic kernel: 7), 24 576 LDS words written and 24 576 read (36 864 each).
 // Barrier 3 (between C and D): positions 32 t .. 32 t + 31 of the doubled tile are other lanes' coefficients 16 t .. 16 t + 15 of
 // the single one, so every lane must have read its C slot before any lane writes a D result.
@@ -515,14 +517,57 @@ __device__ constexpr uint32_t f12_off(int rho) {
     return ((uint32_t)rho << RB) + (RB >= 5 ? ((uint32_t)rho << (RB >= 5 ? RB - 5 : 0)) : ((uint32_t)rho >> (RB >= 5 ? 0 : 5 - RB)));
 }
 
-template <bool CANON>
+// The forward rounds D, E, F run on SIGNED representatives (bb::dit_signed): the ranges they rely on, as exact integers. D's inputs are
+// the canonical words C leaves; the forward tables hold centred twiddles (fused12_twiddles) and kappa is R mod p or, in D's first stage,
+// the centred word of 1 / H; every butterfly
+// maps magnitudes below kInTop to magnitudes below kOutTop <= kInTop, so three rounds of four stages need no correction in between,
+// and F's store makes its words canonical with bb::canonical_of_centred. tests/test_ntt_signed_bounds.py recomputes every figure and
+// presents the edges to the host path of bb::dit_signed. p = 2013265921.
+namespace ntt {
+namespace bounds {
+constexpr int64_t kSmontDomain = 4899916392431616000ll;  // 2^63 - 2^31 p = 1.209 p^2: bb::smont takes |t| < this
+constexpr int64_t kInTop = 2013265921ll;                  // p (B = 1): |a|, |b| < this; canonical words are inside
+constexpr int64_t kTwiddleTop = 1006632960ll;             // (p - 1) / 2: |w|, |kappa| <= this
+constexpr int64_t kWideTop = 4053239664633446400ll;       // 2 (kInTop - 1) kTwiddleTop = (p - 1)^2 = 1.000 p^2: |a kappa + b w| <= this
+constexpr int64_t kOutTop = 1950351361ll;                 // floor((kWideTop + 2^31 p) / 2^32) + 1 = 0.96875 p: |output| < this
+static_assert(kSmontDomain == (int64_t)((1ull << 63) - ((uint64_t)bb::P << 31)), "smont's domain");
+static_assert(kInTop == (int64_t)bb::P && kTwiddleTop == (int64_t)(bb::P - 1) / 2, "B = 1, centred twiddles");
+static_assert(kWideTop == 2 * (kInTop - 1) * kTwiddleTop && kWideTop < kSmontDomain, "a kappa + b w stays inside smont's domain");
+static_assert(kOutTop == (int64_t)(((uint64_t)kWideTop + ((uint64_t)bb::P << 31)) >> 32) + 1, "the reduction adds at most 2^31 p");
+static_assert(kOutTop <= kInTop, "the range closes: outputs are inputs of the next stage");
+static_assert(kOutTop + (int64_t)bb::P <= (1ll << 32), "canonical_of_centred: x + p does not wrap for x >= 0");
+static_assert((int64_t)bb::R_MOD_P <= kTwiddleTop, "kappa = R mod p is centred as it stands");
+}  // namespace bounds
+}  // namespace ntt
+
+// One radix-16 slot of a forward round on signed representatives: `tt` as slot_butterflies' table form, centred; kappa0: the factor of
+// `a` in the slot's first stage (R mod p, or a constant the stage multiplies by: its twiddles then carry the same constant).
+// -w is one full-rate negation per twiddle, 15 per slot (E's two slots share theirs; D's twiddles are wave-uniform: none). Measured
+// against -b per butterfly (the compiler negates the 64-bit product instead: 2 instructions) and against a second, negated table
+// (15 more loads and registers per slot, 132 VGPRs): 1.35 against 1.39 and 1.40 ms at 256 x 2^20 (profiles/lde_fused_signed.txt).
+__device__ __forceinline__ void slot_dit_signed(int32_t* v, const int32_t* tt, int32_t kappa0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int lowp = u & ((1 << q) - 1);
+            const int i0 = ((u >> q) << (q + 1)) | lowp;
+            const int i1 = i0 | (1 << q);
+            const int32_t w = tt[(1 << q) - 1 + lowp];
+            bb::dit_signed(v[i0], v[i1], w, -w, q == 0 ? kappa0 : (int32_t)bb::R_MOD_P);
+        }
+    }
+}
+
+// hinv_c: the centred representative of the Montgomery word of 1 / H (D's first stage: see there)
 __global__ __launch_bounds__(kBlock) void lde_fused12_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t in_stride,
-                                                             size_t out_stride, const uint32_t* __restrict__ tw, uint32_t hinv) {
+                                                             size_t out_stride, const uint32_t* __restrict__ tw, int32_t hinv_c) {
     __shared__ uint32_t tile[(1 << 13) + ((1 << 13) >> 5)];
     const uint32_t tid = threadIdx.x;
     const uint32_t* src = in + (size_t)blockIdx.y * in_stride + ((size_t)blockIdx.x << 12);
     uint32_t* dst = out + (size_t)blockIdx.y * out_stride + ((size_t)blockIdx.x << 13);
     uint32_t x[16], tt[16], tn[16];
+    int32_t te[16];
     // ---- A ----
 #pragma unroll
     for (int rho = 0; rho < 16; ++rho) x[rho] = src[tid + 256u * rho];
@@ -556,58 +601,58 @@ __global__ __launch_bounds__(kBlock) void lde_fused12_kernel(const uint32_t* __r
 #pragma unroll
         for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + (uint32_t)rho];
 #pragma unroll
-        for (int j = 0; j < 15; ++j) tn[j] = tw[kF12D1 + 32u * j + (tid & 31u)];  // for E
+        for (int j = 0; j < 15; ++j) te[j] = (int32_t)tw[kF12D1 + 32u * j + (tid & 31u)];  // for E
 #pragma unroll
         for (int j = 0; j < 15; ++j) tt[j] = tw[kF12A2 + j];
         slot_butterflies<true, 4, true>(x, 0u, tt);
-#pragma unroll
-        for (int rho = 0; rho < 16; ++rho) x[rho] = bb::mul(x[rho], hinv);
     }
     __syncthreads();
-    // ---- D ----
+    // ---- D ---- (from here on signed representatives: ntt::bounds; the inputs are C's canonical words)
+    // 1 / H rides in the first stage: a kappa + b w with kappa = (1 / H) R and the stage's twiddles times 1 / H (fused12_twiddles)
+    // gives (a + b w) / H and (a - b w) / H — no product per coefficient.
     {
         const uint32_t p0 = lds_phys(tid << 5);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            uint32_t y[16];
+            int32_t y[16], ts[16];
 #pragma unroll
-            for (int rho = 0; rho < 16; ++rho) y[rho] = x[rho];
+            for (int rho = 0; rho < 16; ++rho) y[rho] = (int32_t)x[rho];
 #pragma unroll
-            for (int j = 0; j < 15; ++j) tt[j] = tw[kF12D0 + 2u * j + b];
-            slot_butterflies<false, 4, true>(y, 0u, tt);
+            for (int j = 0; j < 15; ++j) ts[j] = (int32_t)tw[kF12D0 + 2u * j + b];
+            slot_dit_signed(y, ts, hinv_c);
 #pragma unroll
-            for (int rho = 0; rho < 16; ++rho) tile[p0 + 2u * rho + b] = y[rho];
+            for (int rho = 0; rho < 16; ++rho) tile[p0 + 2u * rho + b] = (uint32_t)y[rho];
         }
     }
     __syncthreads();
     // ---- E ----
-    uint32_t tf[2][16];
+    int32_t tf[2][16], sx[16];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
 #pragma unroll
-        for (int j = 0; j < 15; ++j) tf[m][j] = tw[kF12D2 + 512u * j + tid + 256u * m];  // for F
+        for (int j = 0; j < 15; ++j) tf[m][j] = (int32_t)tw[kF12D2 + 512u * j + tid + 256u * m];  // for F
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const uint32_t sigma = tid + 256u * m;
         const uint32_t p0 = lds_phys(((sigma >> 5) << 9) | (sigma & 31u));
 #pragma unroll
-        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + f12_off<5>(rho)];
-        slot_butterflies<false, 4, true>(x, 0u, tn);
+        for (int rho = 0; rho < 16; ++rho) sx[rho] = (int32_t)tile[p0 + f12_off<5>(rho)];
+        slot_dit_signed(sx, te, (int32_t)bb::R_MOD_P);
 #pragma unroll
-        for (int rho = 0; rho < 16; ++rho) tile[p0 + f12_off<5>(rho)] = x[rho];
+        for (int rho = 0; rho < 16; ++rho) tile[p0 + f12_off<5>(rho)] = (uint32_t)sx[rho];
     }
     __syncthreads();
-    // ---- F ----
+    // ---- F ---- (its store makes the words canonical: the strided forward groups take [0, 2p), and at 2^12 rows it is the LDE's last)
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const uint32_t sigma = tid + 256u * m;
         const uint32_t p0 = lds_phys(sigma);
 #pragma unroll
-        for (int rho = 0; rho < 16; ++rho) x[rho] = tile[p0 + f12_off<9>(rho)];
-        slot_butterflies<false, 4, true>(x, 0u, tf[m]);
+        for (int rho = 0; rho < 16; ++rho) sx[rho] = (int32_t)tile[p0 + f12_off<9>(rho)];
+        slot_dit_signed(sx, tf[m], (int32_t)bb::R_MOD_P);
 #pragma unroll
-        for (int rho = 0; rho < 16; ++rho) dst[sigma + 512u * rho] = CANON ? bb::reduce_2p(x[rho]) : x[rho];
+        for (int rho = 0; rho < 16; ++rho) dst[sigma + 512u * rho] = bb::canonical_of_centred(sx[rho]);
     }
 }
 
@@ -1052,11 +1097,12 @@ const FusedTwiddles* fused_twiddles(int ka, const GroupParams& ga, const GroupPa
 
 // The specialised kernel's table for height 2^n (lde_fused12_kernel): the two groups' tables at fixed offsets, the forward ones
 // with the coset constant of their stage folded in — stage s of the size-2^(n+1) transform carries s^(2^(n-s)), so unlike
-// FusedTwiddles this table depends on the height. pw[e] = s^(2^e), e <= n.
+// FusedTwiddles this table depends on the height — the first forward stage times hinv = 1 / H as well, and every forward entry as
+// its centred representative (|w| <= p / 2, an int32's bits): the kernel's forward rounds are signed. pw[e] = s^(2^e), e <= n.
 struct Fused12Twiddles { uint32_t* d = nullptr; };
 std::map<std::pair<int, int>, Fused12Twiddles> g_fused12_tw;  // (device, n)
 
-const uint32_t* fused12_twiddles(int n, const GroupParams& ga, const GroupParams& gd, const uint32_t* pw) {
+const uint32_t* fused12_twiddles(int n, const GroupParams& ga, const GroupParams& gd, const uint32_t* pw, uint32_t hinv) {
     const Fused12Twiddles* ft = cached_table(g_fused12_tw, n, [&](std::vector<uint32_t>& h, Fused12Twiddles&) {
         unsigned dif_off[4] = {0, 0, 0, 0}, dit_off[4] = {0, 0, 0, 0};
         append_group_table(h, ga, true, dif_off, 0);
@@ -1070,8 +1116,10 @@ const uint32_t* fused12_twiddles(int n, const GroupParams& ga, const GroupParams
             const size_t G = (size_t)1 << gd.rb[r];
             uint32_t* tab = h.data() + kF12D0 + dit_off[r];
             for (int q = 0; q < gd.logr[r]; ++q) {
-                const uint32_t cq = pw[n - (gd.s0 + gd.rb[r] - gd.c + q)];
-                for (size_t i = (((size_t)1 << q) - 1) * G; i < (((size_t)2 << q) - 1) * G; ++i) tab[i] = bb::mul(tab[i], cq);
+                uint32_t cq = pw[n - (gd.s0 + gd.rb[r] - gd.c + q)];
+                if (r == 0 && q == 0) cq = bb::mul(cq, hinv);  // D's first stage multiplies by 1 / H (lde_fused12_kernel)
+                // centred (|w| <= p / 2), as the int32's bits: the forward rounds run bb::dit_signed
+                for (size_t i = (((size_t)1 << q) - 1) * G; i < (((size_t)2 << q) - 1) * G; ++i) tab[i] = (uint32_t)bb::centred(bb::mul(tab[i], cq));
             }
         }
         return true;
@@ -1120,15 +1168,14 @@ int lde_fused(const uint32_t* in, uint32_t* tmp, uint32_t* out, size_t in_stride
     if (spec12) {
         coset_pw[0] = bb::to_monty(field::kCosetShift);
         for (int e = 1; e <= n; ++e) coset_pw[e] = bb::sqr(coset_pw[e - 1]);
-        const uint32_t* tw12 = fused12_twiddles(n, ga, gd, coset_pw);
+        const uint32_t* tw12 = fused12_twiddles(n, ga, gd, coset_pw, hinv);
         if (!tw12) return (int)hipErrorOutOfMemory;
         const unsigned wgs = 1u << (n - 12);
         for_column_chunks(cols, [&](uint32_t c0, uint32_t cc) {
             ScopedKernelTimer t("lde_fused_kernel");
             const uint32_t* s_ = src + (size_t)c0 * src_stride;
             uint32_t* d_ = out + (size_t)c0 * out_stride;
-            if (n == 12) hipLaunchKernelGGL(lde_fused12_kernel<true>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
-            else hipLaunchKernelGGL(lde_fused12_kernel<false>, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, hinv);
+            hipLaunchKernelGGL(lde_fused12_kernel, dim3(wgs, cc), dim3(kBlock), 0, stream(), s_, d_, src_stride, out_stride, tw12, bb::centred(hinv));
         });
     } else {
         const FusedTwiddles* ft = fused_twiddles(ka, ga, gd);
