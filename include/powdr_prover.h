@@ -538,6 +538,60 @@ void pw_apc_calls_set_long_threshold(uint64_t n);
  * components on the long path, the most scratch bytes held at once, scratch bytes held now. */
 void pw_apc_calls_last_stats(uint64_t* out);
 
+/* ---- the states of an execution from its traces: pcs, registers, time keys -----------------------------------------
+ * What pw_apc_calls_from_states wants, built where the traces lie. Positions, time keys and pcs are those of
+ * pw_apc_calls_from_traces (bridge_bus = its bus): state i < N is the machine before the active row with the i-th smallest
+ * timestamp ts_i, state N the machine after the last row with pc final_pc. The registers are read off the memory bus: a register
+ * access is an active interaction on memory_bus (as, ptr, d0, d1, d2, d3, t) with as == reg_as; its register is ptr / reg_ptr_step
+ * (4 for RV32), its word d0 | d1 << 8 | d2 << 16 | d3 << 24. Interactions in other address spaces are skipped, and so are
+ * accesses to registers nobody asked for, once ptr is evaluated. A send (+1) with timestamp t is seen from state
+ * p = #{ j < N : ts_j <= t } on (it belongs to instruction p - 1, so 1 <= p <= N); of several sends to one register with one p the
+ * largest t wins. A receive (-1) carries (previous word, previous timestamp): per register the receive with the smallest previous
+ * timestamp holds the register's value at state 0. The value of a register at state i is the word of the last send with p <= i, or
+ * the value at state 0 without one. initial_regs (optional) is the machine at the segment's start: with it a register that is never
+ * received has that word at state 0, and a first receive that disagrees is status 10; without it a requested register that is
+ * never received is status 9. Whether every receive finds what the previous send left is pw_check_segment_buses' business, not
+ * this routine's. Only original-instruction AIRs are meant: one instruction per active row.
+ * pw_execution_states_from_traces: regs = n_regs distinct register numbers (host), row k of the table is register regs[k];
+ * initial_regs NULL or n_regs host words, one per row. The handle owns three device arrays: pcs[N + 1], regs[n_regs x (N + 1)]
+ * (row k at k * (N + 1): the layout pw_apc_calls_from_states reads) and the N time keys.
+ * pw_apc_calls_from_traces_registers: pw_apc_calls_from_traces with RegisterLimb operands. n_regs bounds the reg of a literal, as
+ * on the states route; initial_regs NULL or n_regs host words indexed by register. Only the distinct registers the constraints
+ * name become rows; the table never leaves the device. The result carries the time keys; without a register literal it equals
+ * pw_apc_calls_from_traces'.
+ * The contract of pw_apc_calls_from_traces: the call synchronises before it returns; scratch is per thread, bounded by scratch_bytes
+ * (0: half of what the device budget allows; the handle's own arrays count) and released on every path; one segment number per
+ * call. -1 before any GPU call: a NULL pointer, reg_ptr_step == 0, an entry of regs twice or with regs[k] * reg_ptr_step >= p, more
+ * than 65535 rows, a bus id >= p, two segment numbers, an interaction on memory_bus with an arity other than 7, and whatever
+ * pw_apc_calls_from_traces refuses.
+ * *status: 0 = *out is set; 2 = the bound is too small, *info = bytes that always suffice (decided before an element is read); 7
+ * and 4 as for pw_apc_calls_from_traces; 8 = a register tuple that is none, *info = the smallest packed witness
+ * (air << 46 | interaction << 26 | row) among: a multiplicity other than +-1, ptr no multiple of the step, a data word >= 256, two
+ * sends with one (register, timestamp), a send before ts_0; 9 = a requested register without a value, *info = the smallest such
+ * register; 10 = initial_regs contradicted by the first receive, *info = the smallest such register. Checked in the order 2, 7, 4,
+ * 8, 9, 10. With a non-zero status no result exists and 0 is returned. */
+typedef struct PwExecutionStates PwExecutionStates;
+int pw_execution_states_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                                    uint32_t memory_bus, uint32_t final_pc, uint32_t reg_as, uint32_t reg_ptr_step, const uint32_t* regs,
+                                    size_t n_regs, const uint32_t* initial_regs, size_t scratch_bytes, PwExecutionStates** out,
+                                    uint32_t* status, uint64_t* info);
+void pw_execution_states_destroy(PwExecutionStates* e);
+/* sizes[4] = states (N + 1), registers (rows), register sends read, device bytes the handle holds. */
+void pw_execution_states_sizes(const PwExecutionStates* e, uint64_t* sizes);
+/* The handle's device arrays (a NULL argument is skipped); they live until pw_execution_states_destroy. */
+void pw_execution_states_device(const PwExecutionStates* e, const uint32_t** d_pcs, const uint32_t** d_regs, const uint64_t** d_time_keys);
+/* Copies into host arrays of N + 1, n_regs x (N + 1) and N elements (a NULL array is skipped). -1: a NULL handle. */
+int pw_execution_states_read(const PwExecutionStates* e, uint32_t* pcs, uint32_t* regs, uint64_t* time_keys);
+/* Of the calling thread's last pw_execution_states_from_traces, out[5]: register sends read, sends kept after placing, the table
+ * words a workgroup of the fill writes (its tile), the most scratch bytes held at once (the handle's included), scratch bytes held
+ * now. */
+void pw_execution_states_last_stats(uint64_t* out);
+int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                                       uint32_t memory_bus, uint32_t final_pc, uint32_t reg_as, uint32_t reg_ptr_step, uint32_t n_regs,
+                                       uint32_t limb_bits, const uint32_t* initial_regs, const PwApc* apcs, size_t n_apcs,
+                                       const PwApcConstraint* constraints, size_t n_constraints, size_t scratch_bytes, PwApcCalls** out,
+                                       uint32_t* status, uint64_t* info);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

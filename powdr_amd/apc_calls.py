@@ -16,7 +16,8 @@ from .empirical import BUS_EXEC
 
 lib = abi.lib
 STATUS = {0: "selected", 2: "the scratch bound is too small", 4: "two rows with one time key",
-          7: "multiplicities on the bus that are no single receive with sends"}
+          7: "multiplicities on the bus that are no single receive with sends", 8: "a register tuple that is none",
+          9: "a requested register without a value", 10: "the initial registers contradicted by the first receive"}
 COUNTERS = ("matches", "refused", "failed", "aborted", "done", "discarded", "calls")
 KIND_NUMBER, KIND_PC, KIND_REGISTER_LIMB = 0, 1, 2
 
@@ -49,6 +50,8 @@ lib.pw_apc_calls_from_states.restype = C.c_int
 lib.pw_apc_calls_from_states.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32] + _tail
 lib.pw_apc_calls_from_traces.restype = C.c_int
 lib.pw_apc_calls_from_traces.argtypes = [C.POINTER(prover.PwSegmentAir), _u32p, C.c_size_t, C.c_uint32, C.c_uint32] + _tail
+lib.pw_apc_calls_from_traces_registers.restype = C.c_int
+lib.pw_apc_calls_from_traces_registers.argtypes = [C.POINTER(prover.PwSegmentAir), _u32p, C.c_size_t] + [C.c_uint32] * 7 + [_u32p] + _tail
 lib.pw_apc_calls_destroy.restype = None
 lib.pw_apc_calls_destroy.argtypes = [C.c_void_p]
 lib.pw_apc_calls_sizes.restype = None
@@ -165,8 +168,9 @@ class ApcCallsError(ValueError):
 
     def __init__(self, status: int, info: int):
         self.status, self.info = int(status), int(info)
-        what = {2: f"{self.info} bytes needed", 4: f"segment {self.info >> 32}, timestamp {self.info & 0xFFFFFFFF}",
-                7: f"air {self.info >> 32}, row {self.info & 0xFFFFFFFF}"}.get(self.status, "")
+        from .execution_states import describe
+
+        what = describe(self.status, self.info)
         super().__init__(f"pw_apc_calls: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
 
 
@@ -219,6 +223,14 @@ def from_traces_raw(recs, n_airs, segments, bus, final_pc, t_apcs, n_apcs, t_con
     return rc, int(status.value), int(info.value), out.value
 
 
+def from_traces_registers_raw(recs, n_airs, segments, bus, memory_bus, final_pc, reg_as, ptr_step, n_regs, limb_bits, initial_regs, t_apcs, n_apcs, t_cons, n_cons,
+                              scratch_bytes):
+    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
+    rc = lib.pw_apc_calls_from_traces_registers(recs, segments, n_airs, bus, memory_bus, final_pc, reg_as, ptr_step, n_regs, limb_bits, initial_regs, t_apcs, n_apcs,
+                                                t_cons, n_cons, scratch_bytes, C.byref(out), C.byref(status), C.byref(info))
+    return rc, int(status.value), int(info.value), out.value
+
+
 class ApcCalls:
     """`.calls` [ApcCall(apc_id, start, end)] in insertion order; `.counters` per APC {matches, refused, failed, aborted, done,
     discarded, calls}; `.covered` the positions inside calls; `.time_keys` (trace route) the time key of every position."""
@@ -267,11 +279,14 @@ def _device_words(x, what):
 
 
 def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_pc=None, segments=None, bus: int = BUS_EXEC,
-                 scratch_bytes: int = 0) -> ApcCalls:
+                 scratch_bytes: int = 0, registers=None) -> ApcCalls:
     """states_or_segment: the pcs of the execution's N + 1 states in order (a CUDA int32 / uint32 tensor read in place, or anything
     numpy turns into 32-bit words) with `regs` the register values, one row of N + 1 values per register (column-major on the device)
     — or the AIR list [(Prover, device trace pointer, log_height)] of `execution_blocks.detect` with `final_pc`, the pc after the last
-    row, and `segments` naming one segment. apcs: [Apc(start_pc, cycle_count, priority, constraints)], apc_id = the index.
+    row, and `segments` naming one segment. On that route `registers` = dict(n_regs=32, initial=None, reg_as=1, ptr_step=4, memory_bus=1)
+    (every key optional) reads the registers the constraints name off the memory bus (§5s): n_regs bounds a literal's register, initial
+    is None or n_regs words, the machine at the segment's start; without it a register literal is refused as before.
+    apcs: [Apc(start_pc, cycle_count, priority, constraints)], apc_id = the index.
     A non-zero status raises ApcCallsError."""
     t_apcs, n_apcs, t_cons, n_cons = tables(apcs)
     traces = isinstance(states_or_segment, (list, tuple)) and len(states_or_segment) > 0 and isinstance(states_or_segment[0], tuple) and hasattr(states_or_segment[0][0], "_h")
@@ -286,11 +301,26 @@ def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_p
         if segments is not None:
             assert len(segments) == n
             seg = (C.c_uint32 * n)(*[int(s) for s in segments])
-        rc, status, info, handle = from_traces_raw(recs, n, seg, int(bus), int(final_pc), t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
-        what = "pw_apc_calls_from_traces"
+        if registers is None:
+            rc, status, info, handle = from_traces_raw(recs, n, seg, int(bus), int(final_pc), t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
+            what = "pw_apc_calls_from_traces"
+        else:
+            unknown = set(registers) - {"n_regs", "initial", "reg_as", "ptr_step", "memory_bus"}
+            if unknown:
+                raise ValueError(f"registers: unknown keys {sorted(unknown)}")
+            n_regs, initial = int(registers.get("n_regs", 32)), registers.get("initial")
+            if initial is not None and len(initial) != n_regs:
+                raise ValueError("registers: initial holds one word per register")
+            t_init = None if initial is None else (C.c_uint32 * max(n_regs, 1))(*[int(w) for w in initial])
+            rc, status, info, handle = from_traces_registers_raw(recs, n, seg, int(bus), int(registers.get("memory_bus", 1)), int(final_pc),
+                                                                 int(registers.get("reg_as", 1)), int(registers.get("ptr_step", 4)), n_regs, int(limb_bits), t_init,
+                                                                 t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
+            what = "pw_apc_calls_from_traces_registers"
     else:
         import torch
 
+        if registers is not None:
+            raise ValueError("registers: on the trace route only")
         keep_pcs, n_states = _device_words(states_or_segment, "the pcs")
         keep_regs, n_regs = None, 0
         if regs is not None:

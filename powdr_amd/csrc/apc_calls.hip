@@ -21,6 +21,7 @@
 // Counters are added once per distinct key of a wave (a hot APC is one address, not one atomic per lane).
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
+#include "register_states.hpp"
 #include "time_index.hpp"
 
 #include <rocprim/rocprim.hpp>
@@ -298,14 +299,15 @@ __global__ __launch_bounds__(kBlock) void apc_calls_tally_kernel(const u64* __re
 }
 
 struct AcCtx {
-    DeviceBuf small, count, off, cand, item_off, fail, done, V, end, mx, cflag, cfirst, longs, disc, keep, calls, temp, states, icount, tkey, tkey_s, idx, idx_s, pcs, pc_t;
+    DeviceBuf small, count, off, cand, item_off, fail, done, V, end, mx, cflag, cfirst, longs, disc, keep, calls, temp, states, icount, tkey, tkey_s, idx, idx_s, pcs, pc_t, regtab, tkeys;
+    register_states::Ctx stage;  // of the trace route with registers (register_states.hpp)
     size_t peak = 0;
     uint64_t long_threshold = 0;  // 0: kLongDefault
     uint64_t stat_candidates = 0, stat_valid = 0, stat_components = 0, stat_longest = 0, stat_long = 0;
-    DeviceBuf* all[25] = {&small, &count, &off, &cand, &item_off, &fail, &done, &V, &end, &mx, &cflag, &cfirst, &longs, &disc, &keep, &calls, &temp, &states, &icount,
-                          &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t};
+    DeviceBuf* all[27] = {&small, &count, &off, &cand, &item_off, &fail, &done, &V, &end, &mx, &cflag, &cfirst, &longs, &disc, &keep, &calls, &temp, &states, &icount,
+                          &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &regtab, &tkeys};
     size_t held() const {
-        size_t s = 0;
+        size_t s = stage.held();
         for (DeviceBuf* b : all) s += b->bytes;
         return s;
     }
@@ -316,6 +318,7 @@ struct AcReleased {
     AcCtx& cx;
     ~AcReleased() {
         for (DeviceBuf* b : cx.all) b->release();
+        cx.stage.release();
     }
 };
 
@@ -720,6 +723,63 @@ extern "C" int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t
     PW_HIP_TRY(hipStreamSynchronize(st));
     for (DeviceBuf* b : {&cx.tkey, &cx.tkey_s, &cx.idx, &cx.idx_s, &cx.pcs, &cx.pc_t, &cx.temp, &cx.icount}) b->release();
     const int rc = select_calls(cx, (const uint32_t*)cx.states.p, nullptr, N + 1, 8, h, bound, 0, *result, status, info);
+    if (!rc && !*status) *out = result.release();
+    return rc;
+}
+
+// The trace route with registers: the states of register_states.hpp for the distinct registers the constraints name (row k of the
+// table = the k-th smallest of them), the constraints' registers renamed to rows, then select_calls on the table where it lies.
+extern "C" int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, uint32_t memory_bus,
+                                                  uint32_t final_pc, uint32_t reg_as, uint32_t reg_ptr_step, uint32_t n_regs, uint32_t limb_bits,
+                                                  const uint32_t* initial_regs, const PwApc* apcs, size_t n_apcs, const PwApcConstraint* constraints,
+                                                  size_t n_constraints, size_t scratch_bytes, PwApcCalls** out, uint32_t* status, uint64_t* info) {
+    namespace rs = register_states;
+    HostTables h;
+    const rs::Args a{airs, segment_of_air, n_airs, bridge_bus, memory_bus, final_pc, reg_as, reg_ptr_step};
+    u64 M = 0, slots = 0;
+    if (!out || !status || !info || !check_tables(apcs, n_apcs, constraints, n_constraints, n_regs, limb_bits, h) || !rs::args_ok(a, &M, &slots) ||
+        (M + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32))
+        return -1;
+    std::vector<uint32_t> regs;
+    for (const ConDev& q : h.cons)
+        for (const OpDev* o : {&q.l, &q.r})
+            if (o->kind == 2u) regs.push_back(o->reg);
+    std::sort(regs.begin(), regs.end());
+    regs.erase(std::unique(regs.begin(), regs.end()), regs.end());
+    if (!rs::registers_ok(regs.data(), regs.size(), reg_ptr_step)) return -1;
+    std::vector<uint32_t> initial;
+    for (uint32_t r : regs) {
+        if (initial_regs) initial.push_back(initial_regs[r]);
+    }
+    for (ConDev& q : h.cons)
+        for (OpDev* o : {&q.l, &q.r})
+            if (o->kind == 2u) o->reg = (uint32_t)(std::lower_bound(regs.begin(), regs.end(), o->reg) - regs.begin());
+    AcCtx& cx = g_ac;
+    reset_stats(cx);
+    *out = nullptr;
+    *status = 0;
+    *info = 0;
+    (void)hipGetLastError();
+    const AcReleased released{cx};
+    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    // the states, the table and the time keys stay through the selection
+    const size_t extra = 64 + (size_t)(M + 1) * 4 * (regs.size() + 1) + (size_t)M * 8;
+    {
+        const size_t need = std::max(rs::bytes_needed(M, slots, regs.size()), calls_need(M + 1, (M + 1) * h.max_share, h.bytes()) + extra);
+        if (bound < need) {
+            *status = 2;
+            *info = need;  // (what is known before a row is read: every row may be active, every interaction a send)
+            return 0;
+        }
+    }
+    u64 N = 0;
+    PW_TRY(rs::states_from_traces(a, regs, initial_regs ? initial.data() : nullptr, M, slots, cx.stage, cx.states, cx.regtab, cx.tkeys, [&] { cx.note(); }, &N, status, info));
+    if (*status) return (int)hipGetLastError();
+    auto result = empty_result(n_apcs, N + 1);
+    result->time_keys.resize(N);
+    if (N) PW_HIP_TRY(hipMemcpy(result->time_keys.data(), cx.tkeys.p, N * 8, hipMemcpyDeviceToHost));
+    cx.stage.release();
+    const int rc = select_calls(cx, (const uint32_t*)cx.states.p, regs.empty() ? nullptr : (const uint32_t*)cx.regtab.p, N + 1, limb_bits, h, bound, 0, *result, status, info);
     if (!rc && !*status) *out = result.release();
     return rc;
 }

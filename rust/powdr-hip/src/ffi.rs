@@ -347,6 +347,11 @@ pub struct PwApc {
 pub struct PwApcCalls {
     _private: [u8; 0],
 }
+/// the opaque result of `pw_execution_states_from_traces`: the states of a segment on the device
+#[repr(C)]
+pub struct PwExecutionStates {
+    _private: [u8; 0],
+}
 /// `pw_memory_tree_set_mode`: every level above level 0 hashed again from the level below
 pub const PW_MEMORY_TREE_REBUILD: u32 = 0;
 /// `pw_memory_tree_set_mode`: only the touched paths hashed, every other stored node moved
@@ -542,6 +547,24 @@ extern "C" {
     pub fn pw_apc_calls_set_long_threshold(n: u64);
     /// out[7]: candidates, valid, components, longest component, components on the long path, peak scratch bytes, scratch bytes held
     pub fn pw_apc_calls_last_stats(out: *mut u64);
+    /// the states of ONE segment from its traces: pcs, the registers `regs` read off the memory bus and the time
+    /// keys, kept on the device in the layout `pw_apc_calls_from_states` reads. `status` 0 = `*out` is set (free it with
+    /// `pw_execution_states_destroy`); 8 = a register tuple that is none, 9 = a register without a value, 10 = `initial_regs` contradicted
+    pub fn pw_execution_states_from_traces(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, memory_bus: u32,
+                                           final_pc: u32, reg_as: u32, reg_ptr_step: u32, regs: *const u32, n_regs: usize, initial_regs: *const u32,
+                                           scratch_bytes: usize, out: *mut *mut PwExecutionStates, status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_execution_states_destroy(e: *mut PwExecutionStates);
+    /// sizes[4] = states, registers, register sends read, device bytes held
+    pub fn pw_execution_states_sizes(e: *const PwExecutionStates, sizes: *mut u64);
+    pub fn pw_execution_states_device(e: *const PwExecutionStates, d_pcs: *mut *const u32, d_regs: *mut *const u32, d_time_keys: *mut *const u64);
+    pub fn pw_execution_states_read(e: *const PwExecutionStates, pcs: *mut u32, regs: *mut u32, time_keys: *mut u64) -> c_int;
+    /// out[5]: register sends read, sends kept, the fill's tile in table words, peak scratch bytes, scratch bytes held
+    pub fn pw_execution_states_last_stats(out: *mut u64);
+    /// `pw_apc_calls_from_traces` with `RegisterLimb` operands: the registers the constraints name come from the memory bus
+    pub fn pw_apc_calls_from_traces_registers(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, memory_bus: u32,
+                                              final_pc: u32, reg_as: u32, reg_ptr_step: u32, n_regs: u32, limb_bits: u32, initial_regs: *const u32,
+                                              apcs: *const PwApc, n_apcs: usize, constraints: *const PwApcConstraint, n_constraints: usize,
+                                              scratch_bytes: usize, out: *mut *mut PwApcCalls, status: *mut u32, info: *mut u64) -> c_int;
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
