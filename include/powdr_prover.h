@@ -592,6 +592,76 @@ int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, const uint32_t*
                                        const PwApcConstraint* constraints, size_t n_constraints, size_t scratch_bytes, PwApcCalls** out,
                                        uint32_t* status, uint64_t* info);
 
+/* ---- applying APC calls: per-APC source traces and residual chip traces -------------------------------------------
+ * pw_trace_gather_rows: the row gather on caller-owned device buffers, all jobs in ONE launch. Per job (a host record holding device
+ * pointers) out[c * h_out + i] = idx[i] < h_in ? in[c * h_in + idx[i]] : 0 for c < width, i < h_out: `in` is a column-major
+ * width x h_in matrix, `out` a column-major width x h_out matrix of which EVERY word is written, idx h_out row numbers; 0xFFFFFFFF
+ * means "zero row" (and so does any other index that is no row of `in`). Words are copied bit for bit. A lane owns 4 consecutive
+ * output rows and stores 16 bytes at once; 4 consecutive source rows at a 16-byte aligned address are one 16-byte load. h_out < 4, or
+ * an `out` / `idx` that is not 16-byte aligned, takes a word-by-word path. -1 before any GPU call: a NULL pointer in a job (or jobs
+ * NULL with n_jobs > 0), h_in or h_out no power of two, h_in > 2^31, h_out > 2^32, width == 0 or >= 2^32. The outputs of two jobs
+ * must not overlap. The call runs on the calling thread's launch stream and synchronises before it returns.
+ *
+ * pw_apc_sources_from_traces: positions, time keys and the map position -> (AIR, row) are pw_apc_calls_from_traces' (bridge_bus =
+ * its bus): position i < N is the active row with the i-th smallest time key. One instruction per active row: original-instruction
+ * AIRs only. An AIR without a two-argument interaction on bridge_bus takes no part and gets no output. APC a spans
+ * cycle_counts[a] >= 1 instructions; the calls are three host arrays (apc_id, from, to), strictly ascending in from, non-overlapping,
+ * to - from == cycle_counts[apc_id]: what pw_apc_calls_read_calls returns.
+ * Sources: for APC a with calls c_0 .. c_(n-1) in start order, air_a[k] = the AIR of position from_0 + k (the same for every call, or
+ * status 12), occ_a[k] = #{k' < k : air_a[k'] == air_a[k]}, rbs_a[A] = #{k : air_a[k] == A}. For every AIR A with rbs_a[A] > 0 the
+ * source matrix S is column-major, of A's width and height H = max(2^min_log_height, next power of two >= n * rbs_a[A]), with
+ * S[c * H + j * rbs + occ_a[k]] = trace_A[c * H_A + row(from_j + k)] for every k with air_a[k] == A and every other row zero: the
+ * OriginalAir {width, H, S, rbs} of include/powdr_gpu.h with Subst.row = occ_a[k].
+ * Residuals: for every AIR A that takes part, the active rows of A at no covered position in ascending row order, in a matrix of
+ * height max(2^min_log_height, next power of two >= their number) whose other rows are zero — the padding convention of
+ * powdr_original_airs_expand. An AIR whose idle row is not the zero row is outside this contract.
+ * Nothing in either output depends on an order of arrival. The handle owns the matrices; the originals are left as they are.
+ * The contract of pw_apc_calls_from_traces: the call synchronises before it returns; scratch is per thread, bounded by scratch_bytes
+ * (0: half of what the device budget allows; the handle's own matrices count) and released on every path; one segment number per
+ * call. -1 before any GPU call: a NULL pointer, apc_id >= n_apcs, cycle_count == 0, to - from != cycle_count, calls unsorted or
+ * overlapping, min_log_height > 31, two segment numbers, and whatever pw_apc_calls_from_traces refuses about the AIR list.
+ * *status: 0 = *out is set (pw_apc_sources_destroy frees it; the matrices live until then); 2 = the bound is too small, *info =
+ * bytes that always suffice (decided before an element is read); 7 and 4 as for pw_apc_calls_from_traces; 11 = a call with to > N,
+ * *info = the smallest such call index; 12 = two calls of one APC disagree on the AIR of an instruction, *info = the smallest
+ * position that disagrees with the APC's first call. Checked in the order 2, 7, 4, 11, 12. With a non-zero status no result exists
+ * and 0 is returned. */
+typedef struct PwGatherJob {
+    const uint32_t* in; /* device, column-major width x h_in */
+    uint64_t h_in;
+    uint64_t width;
+    const uint32_t* idx; /* device, h_out row numbers of `in`, 0xFFFFFFFF = zero row */
+    uint32_t* out;       /* device, column-major width x h_out */
+    uint64_t h_out;
+} PwGatherJob;
+int pw_trace_gather_rows(const PwGatherJob* jobs, size_t n_jobs);
+typedef struct PwApcSources PwApcSources;
+int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                               const uint32_t* cycle_counts, size_t n_apcs, const uint32_t* call_apc_ids, const uint64_t* call_from,
+                               const uint64_t* call_to, size_t n_calls, uint32_t min_log_height, size_t scratch_bytes, PwApcSources** out,
+                               uint32_t* status, uint64_t* info);
+void pw_apc_sources_destroy(PwApcSources* e);
+/* sizes[6] = APCs, AIRs, positions (N), covered positions, bytes of the source matrices, bytes of the residual matrices. */
+void pw_apc_sources_sizes(const PwApcSources* e, uint64_t* sizes);
+/* The layout of APC apc: *n_calls, and for an APC with calls air[k], occ[k] of its cycle_count instructions (NULL arguments are
+ * skipped). Returns the number of entries written per array (0 for an APC without calls: its layout is unknown), -1 for a NULL
+ * handle or apc >= n_apcs. */
+int64_t pw_apc_sources_layout(const PwApcSources* e, uint32_t apc, uint64_t* n_calls, uint32_t* air, uint32_t* occ);
+/* The source matrix of (apc, air): device pointer, width, height, row_block_size — height 0 (and a NULL pointer) where the APC does
+ * not use the AIR. -1: a NULL handle, apc >= n_apcs, air >= n_airs. */
+int pw_apc_sources_source(const PwApcSources* e, uint32_t apc, uint32_t air, const uint32_t** d_matrix, uint32_t* width, uint64_t* height,
+                          uint32_t* row_block_size);
+/* The residual of AIR air: device pointer, rows kept, log_height. Returns 1, 0 for an AIR that takes no part (no matrix), -1 for a
+ * NULL handle or air >= n_airs. */
+int pw_apc_sources_residual(const PwApcSources* e, uint32_t air, const uint32_t** d_matrix, uint64_t* rows, uint32_t* log_height);
+/* Copies of a whole matrix into a host array of width x height words (nothing is written where there is no matrix). -1: a NULL
+ * argument or an index out of range. */
+int pw_apc_sources_read_source(const PwApcSources* e, uint32_t apc, uint32_t air, uint32_t* words);
+int pw_apc_sources_read_residual(const PwApcSources* e, uint32_t air, uint32_t* words);
+/* Of the calling thread's last pw_apc_sources_from_traces or pw_trace_gather_rows, out[8]: covered positions, source bytes, residual
+ * bytes, gather jobs, gather tiles (1 024 rows x 16 columns) whose loads were all 16-byte loads, tiles with 4-byte loads, the most
+ * scratch bytes held at once (the handle's matrices included), scratch bytes held now. */
+void pw_apc_sources_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -54,6 +54,10 @@ def describe(status: int, info: int) -> str:
         return "air %d, interaction %d, row %d" % unpack_witness(info)
     if status in (9, 10):
         return f"register {info}"
+    if status == 11:
+        return f"call {info}"
+    if status == 12:
+        return f"position {info}"
     return ""
 
 

@@ -347,6 +347,22 @@ pub struct PwApc {
 pub struct PwApcCalls {
     _private: [u8; 0],
 }
+/// the opaque result of `pw_apc_sources_from_traces`: source and residual matrices on the device
+#[repr(C)]
+pub struct PwApcSources {
+    _private: [u8; 0],
+}
+/// a job of `pw_trace_gather_rows`: `out[c * h_out + i] = in[c * h_in + idx[i]]`, `idx[i] == !0` = a zero row (device pointers)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PwGatherJob {
+    pub r#in: *const u32,
+    pub h_in: u64,
+    pub width: u64,
+    pub idx: *const u32,
+    pub out: *mut u32,
+    pub h_out: u64,
+}
 /// the opaque result of `pw_execution_states_from_traces`: the states of a segment on the device
 #[repr(C)]
 pub struct PwExecutionStates {
@@ -565,6 +581,25 @@ extern "C" {
                                               final_pc: u32, reg_as: u32, reg_ptr_step: u32, n_regs: u32, limb_bits: u32, initial_regs: *const u32,
                                               apcs: *const PwApc, n_apcs: usize, constraints: *const PwApcConstraint, n_constraints: usize,
                                               scratch_bytes: usize, out: *mut *mut PwApcCalls, status: *mut u32, info: *mut u64) -> c_int;
+    /// the row gather of DESIGN.md §5t on caller-owned device buffers, all jobs in one launch
+    pub fn pw_trace_gather_rows(jobs: *const PwGatherJob, n_jobs: usize) -> c_int;
+    /// applying the calls of ONE segment: per (APC, AIR) the call-major source matrix `_apc_tracegen` reads, per AIR
+    /// the residual trace. `status` 0 = `*out` is set (free it with `pw_apc_sources_destroy`); 11 = a call beyond the execution,
+    /// 12 = two calls of one APC disagree on an instruction's AIR
+    pub fn pw_apc_sources_from_traces(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, cycle_counts: *const u32,
+                                      n_apcs: usize, call_apc_ids: *const u32, call_from: *const u64, call_to: *const u64, n_calls: usize,
+                                      min_log_height: u32, scratch_bytes: usize, out: *mut *mut PwApcSources, status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_apc_sources_destroy(e: *mut PwApcSources);
+    /// sizes[6] = APCs, AIRs, positions, covered positions, source bytes, residual bytes
+    pub fn pw_apc_sources_sizes(e: *const PwApcSources, sizes: *mut u64);
+    pub fn pw_apc_sources_layout(e: *const PwApcSources, apc: u32, n_calls: *mut u64, air: *mut u32, occ: *mut u32) -> i64;
+    pub fn pw_apc_sources_source(e: *const PwApcSources, apc: u32, air: u32, d_matrix: *mut *const u32, width: *mut u32, height: *mut u64,
+                                 row_block_size: *mut u32) -> c_int;
+    pub fn pw_apc_sources_residual(e: *const PwApcSources, air: u32, d_matrix: *mut *const u32, rows: *mut u64, log_height: *mut u32) -> c_int;
+    pub fn pw_apc_sources_read_source(e: *const PwApcSources, apc: u32, air: u32, words: *mut u32) -> c_int;
+    pub fn pw_apc_sources_read_residual(e: *const PwApcSources, air: u32, words: *mut u32) -> c_int;
+    /// out[8]: covered positions, source bytes, residual bytes, gather jobs, 16-byte-load tiles, 4-byte-load tiles, peak scratch, scratch held
+    pub fn pw_apc_sources_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
