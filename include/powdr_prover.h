@@ -662,6 +662,57 @@ int pw_apc_sources_read_residual(const PwApcSources* e, uint32_t air, uint32_t* 
  * scratch bytes held at once (the handle's matrices included), scratch bytes held now. */
 void pw_apc_sources_last_stats(uint64_t* out);
 
+/* ---- applying APC calls, direct mode: APC traces straight from the chips' traces ----------------------------------
+ * pw_apc_sources_from_traces_flags: flags == 0 is pw_apc_sources_from_traces, the same results and statuses. PW_APC_SOURCES_DIRECT
+ * builds NO source matrices: the handle keeps, in one device allocation of its own, the index lists the place stage makes — for every
+ * (APC a, AIR A) with rbs_a[A] > 0 the list L of n * rbs words with L[j * rbs + occ_a[k]] = row(from_j + k) for every k with
+ * air_a[k] == A — and remembers each participating AIR's trace pointer, height and width: THE CALLER'S TRACES MUST STAY ALIVE AND
+ * UNCHANGED UNTIL THE LAST pw_apc_sources_tracegen ON THE HANDLE. Layout, residuals, the statuses 7, 4, 11, 12 and their order are
+ * those of flags 0; the bound of status 2 counts the lists where flags 0 counts the source matrices. On a direct handle
+ * pw_apc_sources_source reports height 0 and a NULL pointer for every pair (width and row_block_size as with flags 0),
+ * pw_apc_sources_read_source writes nothing and sizes[4] is 0. Any other bit of flags: -1.
+ * pw_apc_sources_index_bytes: the bytes of the handle's index lists, 0 on a flags-0 handle (and for a NULL handle).
+ *
+ * pw_apc_sources_tracegen: for every job, every cell {instr, col, apc_col} of it and every r < out_height, with (A, occ) the layout
+ * entry of instr in APC job.apc, L that pair's list and H_A the height of A's trace:
+ *   d_out[apc_col * out_height + r] = r < n_calls(apc) ? trace_A[col * H_A + L[r * rbs + occ]] : 0
+ * — word for word what _apc_tracegen writes from the source matrices of flags 0 with Subst {A, col, occ, apc_col}. d_out is a
+ * column-major out_width x out_height matrix on the device; columns no cell names are NOT touched (derived columns are written
+ * later, by _apc_apply_derived_expr); one source cell may feed several APC columns; the cells are host arrays in any order. A job
+ * for an APC without calls writes zeros into the columns it names. ALL jobs of a call are ONE launch: a workgroup is (job,
+ * instruction, tile of 1 024 rows, group of up to 16 of the instruction's cells); a lane owns 4 consecutive rows, reads its 4 list
+ * entries once and stores 16 bytes per cell; 4 consecutive source rows at a 16-byte aligned address are one 16-byte load.
+ * out_height < 4, or a d_out off the 16-byte grid, goes word by word. A list entry that is no row of the AIR reads as zero.
+ * -1 before any GPU call: a NULL argument (the handle; jobs with n_jobs > 0; cells with n_cells > 0; d_out), a handle that is not
+ * direct, apc >= n_apcs, instr >= the APC's cycle count, col >= the AIR's width (for an APC with calls: without calls its AIRs are
+ * unknown), apc_col >= out_width, two cells of a job with one apc_col, out_height no power of two or > 2^32 or < n_calls(apc),
+ * out_width == 0, two jobs whose output matrices overlap. The call runs on the calling thread's launch stream and synchronises
+ * before it returns; its tables go through the per-thread scratch of pw_apc_sources_from_traces and are released on every path.
+ * pw_apc_sources_tracegen_last_stats: of the calling thread's last pw_apc_sources_tracegen, out[6]: jobs, work items (job,
+ * instruction, cell group), tiles whose loads were all 16-byte loads (or none: zero rows), tiles with 4-byte loads, bytes
+ * written, scratch bytes held now. */
+#define PW_APC_SOURCES_DIRECT 1u
+typedef struct PwApcCell {
+    uint32_t instr;   /* instruction of the APC: < its cycle count */
+    uint32_t col;     /* column of that instruction's AIR */
+    uint32_t apc_col; /* column of d_out */
+} PwApcCell;
+typedef struct PwApcTraceJob {
+    uint32_t apc;
+    const PwApcCell* cells; /* host */
+    size_t n_cells;
+    uint32_t* d_out; /* device, column-major out_width x out_height */
+    uint64_t out_height;
+    uint32_t out_width;
+} PwApcTraceJob;
+int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                                     const uint32_t* cycle_counts, size_t n_apcs, const uint32_t* call_apc_ids,
+                                     const uint64_t* call_from, const uint64_t* call_to, size_t n_calls, uint32_t min_log_height,
+                                     size_t scratch_bytes, uint32_t flags, PwApcSources** out, uint32_t* status, uint64_t* info);
+uint64_t pw_apc_sources_index_bytes(const PwApcSources* e);
+int pw_apc_sources_tracegen(const PwApcSources* e, const PwApcTraceJob* jobs, size_t n_jobs);
+void pw_apc_sources_tracegen_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -1,7 +1,11 @@
 """Applying APC calls (include/powdr_prover.h `pw_apc_sources_from_traces`, `pw_trace_gather_rows`): from a segment's
 instruction-AIR traces on the device and the calls `apc_calls.select_calls` chose, per (APC, AIR) the call-major source matrix the APC
 trace generator reads (`OriginalAir`, `Subst` of include/powdr_gpu.h) and per AIR the residual trace — the rows no call covers, which
-the original chip still has to prove. Nothing leaves the device."""
+the original chip still has to prove. Nothing leaves the device.
+
+Direct mode (`pw_apc_sources_from_traces_flags` with `PW_APC_SOURCES_DIRECT`, `pw_apc_sources_tracegen`): `apply_calls(...,
+direct=True)` builds no source matrices — the handle keeps the index lists and `ApcSources.apc_traces` writes the APC traces straight
+from the chips' traces, which must stay alive and unchanged until the last `apc_traces` call."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,6 +22,8 @@ lib = abi.lib
 STATUS = {0: "applied", 2: "the scratch bound is too small", 4: "two rows with one time key",
           7: "multiplicities on the bus that are no single receive with sends", 11: "a call that ends after the execution",
           12: "two calls of one APC disagree on the AIR of an instruction"}
+DIRECT = 1  # PW_APC_SOURCES_DIRECT
+TRACEGEN_STATS = ("jobs", "work_items", "tiles_16_byte_loads", "tiles_4_byte_loads", "bytes_written", "scratch_bytes")
 STATS = ("covered", "source_bytes", "residual_bytes", "gather_jobs", "tiles_16_byte_loads", "tiles_4_byte_loads", "peak_bytes", "scratch_bytes")
 
 Layout = namedtuple("Layout", "n_calls instructions")  # instructions: [(air, occ)], empty for an APC without calls
@@ -32,12 +38,32 @@ class PwGatherJob(C.Structure):
 
 assert C.sizeof(PwGatherJob) == 48
 
+
+class PwApcCell(C.Structure):
+    _fields_ = [("instr", C.c_uint32), ("col", C.c_uint32), ("apc_col", C.c_uint32)]
+
+
+class PwApcTraceJob(C.Structure):
+    _fields_ = [("apc", C.c_uint32), ("cells", C.POINTER(PwApcCell)), ("n_cells", C.c_size_t), ("d_out", C.c_void_p), ("out_height", C.c_uint64),
+                ("out_width", C.c_uint32)]
+
+
+assert C.sizeof(PwApcCell) == 12 and C.sizeof(PwApcTraceJob) == 48
+
 _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 lib.pw_trace_gather_rows.restype = C.c_int
 lib.pw_trace_gather_rows.argtypes = [C.POINTER(PwGatherJob), C.c_size_t]
 lib.pw_apc_sources_from_traces.restype = C.c_int
 lib.pw_apc_sources_from_traces.argtypes = [C.POINTER(prover.PwSegmentAir), _u32p, C.c_size_t, C.c_uint32, _u32p, C.c_size_t, _u32p, _u64p, _u64p, C.c_size_t, C.c_uint32,
                                            C.c_size_t, C.POINTER(C.c_void_p), _u32p, _u64p]
+lib.pw_apc_sources_from_traces_flags.restype = C.c_int
+lib.pw_apc_sources_from_traces_flags.argtypes = lib.pw_apc_sources_from_traces.argtypes[:12] + [C.c_uint32] + lib.pw_apc_sources_from_traces.argtypes[12:]
+lib.pw_apc_sources_index_bytes.restype = C.c_uint64
+lib.pw_apc_sources_index_bytes.argtypes = [C.c_void_p]
+lib.pw_apc_sources_tracegen.restype = C.c_int
+lib.pw_apc_sources_tracegen.argtypes = [C.c_void_p, C.POINTER(PwApcTraceJob), C.c_size_t]
+lib.pw_apc_sources_tracegen_last_stats.restype = None
+lib.pw_apc_sources_tracegen_last_stats.argtypes = [_u64p]
 lib.pw_apc_sources_destroy.restype = None
 lib.pw_apc_sources_destroy.argtypes = [C.c_void_p]
 lib.pw_apc_sources_sizes.restype = None
@@ -71,6 +97,24 @@ def last_stats() -> dict:
     return dict(zip(STATS, (int(x) for x in out)))
 
 
+def tracegen_last_stats() -> dict:
+    """of the calling thread's last `ApcSources.apc_traces` (`pw_apc_sources_tracegen_last_stats`)"""
+    out = (C.c_uint64 * 6)()
+    lib.pw_apc_sources_tracegen_last_stats(out)
+    return dict(zip(TRACEGEN_STATS, (int(x) for x in out)))
+
+
+def trace_jobs(jobs):
+    """[(apc, [(instr, col, apc_col)], out_ptr, out_height, out_width)] -> (the PwApcTraceJob array, what keeps its cell arrays alive)"""
+    recs, keep = (PwApcTraceJob * max(len(jobs), 1))(), []
+    for k, (apc, cells, out_ptr, out_height, out_width) in enumerate(jobs):
+        flat = np.ascontiguousarray(np.asarray(list(cells), dtype=np.uint32).reshape(-1, 3))
+        keep.append(flat)
+        recs[k] = PwApcTraceJob(int(apc), flat.ctypes.data_as(C.POINTER(PwApcCell)) if len(flat) else None, len(flat), int(out_ptr) if out_ptr else None, int(out_height),
+                                int(out_width))
+    return recs, keep
+
+
 def gather_rows(jobs) -> None:
     """jobs: [GatherJob(src, h_in, width, idx, out, h_out)] with device pointers: out[c * h_out + i] = src[c * h_in + idx[i]], an index
     0xFFFFFFFF gives a zero row; every word of every output is written, all jobs in one launch (`pw_trace_gather_rows`)"""
@@ -82,21 +126,26 @@ def gather_rows(jobs) -> None:
     abi.check(rc, "pw_trace_gather_rows")
 
 
-def from_traces_raw(recs, n_airs, segments, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
+def from_traces_raw(recs, n_airs, segments, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes, flags=None):
+    """the C call itself (flags None: pw_apc_sources_from_traces, else pw_apc_sources_from_traces_flags) -> (return code, status, info,
+    handle or None); the caller destroys the handle"""
     out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_apc_sources_from_traces(recs, segments, n_airs, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes, C.byref(out),
-                                        C.byref(status), C.byref(info))
+    head = (recs, segments, n_airs, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes)
+    tail = (C.byref(out), C.byref(status), C.byref(info))
+    rc = lib.pw_apc_sources_from_traces(*head, *tail) if flags is None else lib.pw_apc_sources_from_traces_flags(*head, int(flags), *tail)
     return rc, int(status.value), int(info.value), out.value
 
 
 class ApcSources:
     """`.layout[a]` Layout(n_calls, [(air, occ)]); `.source(a, air)` Source(ptr, width, height, rbs), height 0 where APC a does not
     use the AIR; `.residual(air)` Residual(ptr, rows, log_height) or None for an AIR that takes no part; `.positions`, `.covered`,
-    `.source_bytes`, `.residual_bytes`. The device pointers are valid until close()."""
+    `.source_bytes`, `.residual_bytes`. The device pointers are valid until close(). `.direct`: made by `apply_calls(direct=True)` — no
+    source matrix exists (`source()` has height 0 everywhere), `.index_bytes` are the handle's index lists and `apc_traces` writes the
+    APC traces from the chips' traces."""
 
-    def __init__(self, handle, widths):
-        self._h, self._widths = handle, [int(w) for w in widths]
+    def __init__(self, handle, widths, direct=False):
+        self._h, self._widths, self.direct = handle, [int(w) for w in widths], bool(direct)
+        self.index_bytes = int(lib.pw_apc_sources_index_bytes(handle))
         sizes = (C.c_uint64 * 6)()
         lib.pw_apc_sources_sizes(handle, sizes)
         self.n_apcs, self.n_airs, self.positions, self.covered, self.source_bytes, self.residual_bytes = (int(x) for x in sizes)
@@ -146,6 +195,7 @@ class ApcSources:
     def original_airs(self, apc: int):
         """the `OriginalAir` array of APC apc (device pointers inside), one entry per AIR of `source_airs(apc)`: what
         `powdr_apc_tracegen_host_tables` takes as h_original_airs"""
+        self._needs_matrices("original_airs")
         used = self.source_airs(apc)
         recs = (abi.OriginalAir * max(len(used), 1))()
         for i, air in enumerate(used):
@@ -155,9 +205,24 @@ class ApcSources:
 
     def substs(self, apc: int, cells) -> np.ndarray:
         """cells: [(instr_idx, col, apc_col)] -> the `Subst` rows int32 [n, 4] = {air_index into original_airs(apc), col, row = occ, apc_col}"""
+        self._needs_matrices("substs")
         index = {air: i for i, air in enumerate(self.source_airs(apc))}
         ins = self.layout[apc].instructions
         return np.array([(index[ins[k][0]], col, ins[k][1], apc_col) for k, col, apc_col in cells], np.int32).reshape(-1, 4)
+
+    def _needs_matrices(self, what):
+        if self.direct:
+            raise ValueError(f"{what}: a direct handle has no source matrices; use apc_traces")
+
+    def apc_traces(self, jobs) -> None:
+        """jobs: [(apc, [(instr, col, apc_col)], out_ptr, out_height, out_width)], out_ptr a column-major out_width x out_height device
+        matrix: out[apc_col * out_height + r] = the cell (instr, col) of call r of the APC, 0 for r >= its calls; columns no cell names
+        are not touched. All jobs in one launch (`pw_apc_sources_tracegen`); a direct handle only."""
+        recs, keep = trace_jobs(list(jobs))
+        rc = lib.pw_apc_sources_tracegen(self._h, recs, len(keep))
+        if rc == -1:
+            raise ValueError("pw_apc_sources_tracegen: malformed arguments" + ("" if self.direct else " (the handle is not direct)"))
+        abi.check(rc, "pw_apc_sources_tracegen")
 
     def residual_segment(self, seg) -> list:
         """seg with the AIRs that took part replaced by their residuals: the AIR list `prove_segment` and `check_segment_buses` take"""
@@ -183,10 +248,11 @@ class ApcSources:
         self.close()
 
 
-def apply_calls(seg, calls, apcs, segments=None, bus: int = BUS_EXEC, min_log_height: int = 0, scratch_bytes: int = 0) -> ApcSources:
+def apply_calls(seg, calls, apcs, segments=None, bus: int = BUS_EXEC, min_log_height: int = 0, scratch_bytes: int = 0, direct: bool = False) -> ApcSources:
     """seg: the AIR list [(Prover, device trace pointer, log_height)] `select_calls` took; calls: its `ApcCalls`, or a list of
     ApcCall(apc_id, start, end) ascending in start; apcs: [Apc] or the cycle counts, apc_id = the index; segments: one segment number
-    for all AIRs. A non-zero status raises ApcSourcesError."""
+    for all AIRs. direct: keep the index lists instead of source matrices (`ApcSources.apc_traces`); the traces of seg must then stay
+    alive and unchanged while the handle is used. A non-zero status raises ApcSourcesError."""
     if isinstance(calls, ApcCalls):
         calls = calls.calls
     calls = [ApcCall(*c) for c in calls]
@@ -197,10 +263,11 @@ def apply_calls(seg, calls, apcs, segments=None, bus: int = BUS_EXEC, min_log_he
     t_ids = (C.c_uint32 * max(n, 1))(*[int(c.apc_id) for c in calls])
     t_from = (C.c_uint64 * max(n, 1))(*[int(c.start) for c in calls])
     t_to = (C.c_uint64 * max(n, 1))(*[int(c.end) for c in calls])
-    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), t_cycles, m, t_ids, t_from, t_to, n, int(min_log_height), int(scratch_bytes))
+    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), t_cycles, m, t_ids, t_from, t_to, n, int(min_log_height), int(scratch_bytes),
+                                               DIRECT if direct else None)
     if rc == -1:
         raise ValueError("pw_apc_sources_from_traces: malformed arguments")
     abi.check(rc, "pw_apc_sources_from_traces")
     if status:
         raise ApcSourcesError(status, info)
-    return ApcSources(handle, [pr.width for pr, _, _ in seg])
+    return ApcSources(handle, [pr.width for pr, _, _ in seg], direct=direct)

@@ -21,6 +21,13 @@
 //                                           four 4-byte loads. Heights below 4, and outputs or index lists that are not 16-byte
 //                                           aligned, go word by word. Elements are addressed with 64 bits. The kernel writes every
 //                                           word of the output, zero rows included.
+// Direct mode (pw_apc_sources_from_traces_flags with PW_APC_SOURCES_DIRECT, pw_apc_sources_tracegen): no source matrix is
+// built; the handle keeps the index lists of the place stage and the AIRs' trace pointers, and
+//   tracegen   apc_sources_tracegen_kernel  out[apc_col * H + r] = r < n_calls ? trace_A[col * H_A + L[r * rbs + occ]] : 0, ONE launch for
+//                                           all jobs: a workgroup is (job, instruction, tile of kTileRows rows, group of up to kColGroup of
+//                                           the instruction's cells) and finds its item by binary search over the items' first tiles. A
+//                                           lane owns 4 consecutive rows, reads its 4 list entries once (a strided read) and reuses them
+//                                           over the group's cells; stores and loads as in the gather. Only the named columns are written.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
 #include "time_index.hpp"
@@ -89,6 +96,68 @@ __global__ __launch_bounds__(kBlock) void apc_sources_gather_kernel(const Gather
                 v.z = s.z < J.h_in ? in[s.z] : 0u;
                 v.w = s.w < J.h_in ? in[s.w] : 0u;
                 *reinterpret_cast<uint4*>(out + (u64)c * J.h_out) = v;
+            }
+        }
+    }
+    const int any_words = __syncthreads_or(words);
+    if (threadIdx.x == 0u) atomicAdd(counters + (any_words ? 1 : 0), 1ull);
+}
+
+struct TraceItemDev {
+    const uint32_t* in;    // the trace of the instruction's AIR (NULL with h_in = 0: an APC without calls)
+    const uint32_t* list;  // the index list of (APC, AIR) from occ on: call r reads list[r * rbs]
+    uint32_t* out;
+    u64 h_in, h_out, n_calls, tile0;  // tile0: the item's first tile among all tiles of the launch
+    uint32_t rbs, cell0, n_cells, word;  // cells cell0 .. cell0 + n_cells - 1 of the cell table: (col, apc_col)
+};
+
+// counters: as apc_sources_gather_kernel's
+__global__ __launch_bounds__(kBlock) void apc_sources_tracegen_kernel(const TraceItemDev* __restrict__ items, uint32_t n_items, const uint2* __restrict__ cells,
+                                                                       u64 tile_base, u64* __restrict__ counters) {
+    const u64 t = tile_base + blockIdx.x;
+    uint32_t lo = 0, hi = n_items;  // the last item with tile0 <= t
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (items[mid].tile0 <= t) lo = mid + 1;
+        else hi = mid;
+    }
+    const TraceItemDev I = items[lo - 1];
+    const u64 r0 = (t - I.tile0) * kTileRows + (u64)threadIdx.x * 4;
+    const uint2* __restrict__ cell = cells + I.cell0;
+    bool words = false;
+    if (I.word) {
+        for (uint32_t k = 0; k < 4u && r0 + k < I.h_out; ++k) {
+            const u64 r = r0 + k;
+            const uint32_t s = r < I.n_calls ? I.list[r * I.rbs] : ~0u;
+            for (uint32_t c = 0; c < I.n_cells; ++c) I.out[(u64)cell[c].y * I.h_out + r] = s < I.h_in ? I.in[(u64)cell[c].x * I.h_in + s] : 0u;
+            words = true;
+        }
+    } else if (r0 < I.h_out) {  // (h_out is a power of two >= 4 and r0 a multiple of 4: rows r0 .. r0 + 3 exist)
+        uint4 s;
+        s.x = r0 < I.n_calls ? I.list[r0 * I.rbs] : ~0u;
+        s.y = r0 + 1 < I.n_calls ? I.list[(r0 + 1) * I.rbs] : ~0u;
+        s.z = r0 + 2 < I.n_calls ? I.list[(r0 + 2) * I.rbs] : ~0u;
+        s.w = r0 + 3 < I.n_calls ? I.list[(r0 + 3) * I.rbs] : ~0u;
+        uint32_t* __restrict__ out = I.out + r0;
+        // (h_in is a power of two <= 2^31: s.x + 3 does not wrap, and with h_in >= 4 every column starts 16-byte aligned if `in` does)
+        const bool run = s.x < I.h_in && s.y == s.x + 1u && s.z == s.x + 2u && s.w == s.x + 3u && s.w < I.h_in && ((((uintptr_t)I.in >> 2) + s.x) & 3u) == 0u;
+        if (run) {
+            const uint32_t* __restrict__ in = I.in + s.x;
+#pragma unroll 4
+            for (uint32_t c = 0; c < I.n_cells; ++c) *reinterpret_cast<uint4*>(out + (u64)cell[c].y * I.h_out) = *reinterpret_cast<const uint4*>(in + (u64)cell[c].x * I.h_in);
+        } else if (s.x >= I.h_in && s.y >= I.h_in && s.z >= I.h_in && s.w >= I.h_in) {
+            for (uint32_t c = 0; c < I.n_cells; ++c) *reinterpret_cast<uint4*>(out + (u64)cell[c].y * I.h_out) = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            words = true;
+#pragma unroll 4
+            for (uint32_t c = 0; c < I.n_cells; ++c) {
+                const uint32_t* __restrict__ in = I.in + (u64)cell[c].x * I.h_in;
+                uint4 v;
+                v.x = s.x < I.h_in ? in[s.x] : 0u;
+                v.y = s.y < I.h_in ? in[s.y] : 0u;
+                v.z = s.z < I.h_in ? in[s.z] : 0u;
+                v.w = s.w < I.h_in ? in[s.w] : 0u;
+                *reinterpret_cast<uint4*>(out + (u64)cell[c].y * I.h_out) = v;
             }
         }
     }
@@ -198,6 +267,10 @@ struct AsCtx {
     }
 };
 thread_local AsCtx g_as;
+struct TracegenStats {
+    uint64_t jobs = 0, items = 0, tiles16 = 0, tiles4 = 0, bytes_written = 0;
+};
+thread_local TracegenStats g_tracegen;
 struct AsReleased {
     AsCtx& cx;
     ~AsReleased() {
@@ -317,6 +390,12 @@ struct PwApcSources {
     std::vector<uint64_t> n_calls;    // [n_apcs]
     std::vector<uint32_t> cycle, ioff, air_of, occ;  // per APC its cycle count and first entry; per instruction of an APC with calls (AIR, occ)
     uint64_t positions = 0, covered = 0, source_bytes = 0, residual_bytes = 0;
+    // direct mode: no source matrix (height 0 everywhere); the index lists, where each (APC, AIR) pair's begins, the callers' traces
+    struct Trace { const uint32_t* p = nullptr; u64 height = 0; uint32_t width = 0; };
+    bool direct = false;
+    DeviceBuf idx;
+    std::vector<u64> list_base;  // [n_apcs x n_airs] in words
+    std::vector<Trace> traces;   // [n_airs], set for the AIRs that take part
 };
 
 extern "C" void pw_apc_sources_destroy(PwApcSources* e) { delete e; }
@@ -391,6 +470,102 @@ extern "C" void pw_apc_sources_last_stats(uint64_t* out) {
     out[7] = g_as.held();
 }
 
+extern "C" uint64_t pw_apc_sources_index_bytes(const PwApcSources* e) { return e ? e->idx.bytes : 0; }
+
+extern "C" void pw_apc_sources_tracegen_last_stats(uint64_t* out) {
+    if (!out) return;
+    out[0] = g_tracegen.jobs;
+    out[1] = g_tracegen.items;
+    out[2] = g_tracegen.tiles16;
+    out[3] = g_tracegen.tiles4;
+    out[4] = g_tracegen.bytes_written;
+    out[5] = g_as.held();
+}
+
+extern "C" int pw_apc_sources_tracegen(const PwApcSources* e, const PwApcTraceJob* jobs, size_t n_jobs) {
+    if (!e || !e->direct || (!jobs && n_jobs) || n_jobs >= ((size_t)1 << 31)) return -1;
+    // ---- every refusal, and the tables (host): per job its cells by (instr, col), an item per instruction and group of kColGroup cells ----
+    std::vector<TraceItemDev> items;
+    std::vector<uint2> cells;
+    std::vector<std::pair<uintptr_t, uintptr_t>> spans;  // the jobs' output matrices [begin, end)
+    std::vector<PwApcCell> sorted;
+    std::vector<uint32_t> apc_cols;
+    u64 tiles = 0, bytes_written = 0;
+    for (size_t k = 0; k < n_jobs; ++k) {
+        const PwApcTraceJob& j = jobs[k];
+        if ((!j.cells && j.n_cells) || !j.d_out || j.apc >= e->n_apcs || !j.out_width || !power_of_two(j.out_height) || j.out_height > ((u64)1 << 32) ||
+            j.out_height < e->n_calls[j.apc] || j.n_cells >= ((size_t)1 << 32))
+            return -1;
+        const uint32_t apc = j.apc, cycle = e->cycle[apc], at = e->ioff[apc];
+        const u64 n_calls = e->n_calls[apc];
+        sorted.assign(j.cells, j.cells + j.n_cells);
+        apc_cols.resize(j.n_cells);
+        for (size_t c = 0; c < j.n_cells; ++c) {
+            const PwApcCell& x = sorted[c];
+            if (x.instr >= cycle || x.apc_col >= j.out_width || (n_calls && x.col >= e->traces[e->air_of[at + x.instr]].width)) return -1;
+            apc_cols[c] = x.apc_col;
+        }
+        std::sort(apc_cols.begin(), apc_cols.end());
+        if (std::adjacent_find(apc_cols.begin(), apc_cols.end()) != apc_cols.end()) return -1;
+        std::sort(sorted.begin(), sorted.end(), [](const PwApcCell& a, const PwApcCell& b) {
+            return a.instr != b.instr ? a.instr < b.instr : a.col != b.col ? a.col < b.col : a.apc_col < b.apc_col;
+        });
+        const uintptr_t begin = (uintptr_t)j.d_out;
+        spans.emplace_back(begin, begin + (uintptr_t)j.out_width * j.out_height * 4);
+        const u64 row_tiles = (j.out_height + kTileRows - 1) / kTileRows;
+        const uint32_t word = j.out_height < 4 || (begin & 15u) != 0 ? 1u : 0u;
+        for (size_t c = 0; c < j.n_cells;) {
+            size_t c1 = c;
+            while (c1 < j.n_cells && c1 - c < kColGroup && sorted[c1].instr == sorted[c].instr) ++c1;
+            TraceItemDev it{nullptr, nullptr, j.d_out, 0, j.out_height, n_calls, tiles, 1u, (uint32_t)cells.size(), (uint32_t)(c1 - c), word};
+            if (n_calls) {
+                const uint32_t air = e->air_of[at + sorted[c].instr];
+                const PwApcSources::Source& s = e->sources[(size_t)apc * e->n_airs + air];
+                it.in = e->traces[air].p;
+                it.h_in = e->traces[air].height;
+                it.list = (const uint32_t*)e->idx.p + e->list_base[(size_t)apc * e->n_airs + air] + e->occ[at + sorted[c].instr];
+                it.rbs = s.rbs;
+            }
+            items.push_back(it);
+            for (; c < c1; ++c) cells.push_back(make_uint2(sorted[c].col, sorted[c].apc_col));
+            tiles += row_tiles;
+        }
+        bytes_written += (u64)j.n_cells * j.out_height * 4;
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); ++k)
+        if (spans[k].first < spans[k - 1].second) return -1;
+    if (cells.size() >= ((size_t)1 << 32) || items.size() >= ((size_t)1 << 31)) return -1;
+    g_tracegen = TracegenStats{};
+    g_tracegen.jobs = n_jobs;
+    g_tracegen.items = items.size();
+    if (items.empty()) return 0;
+
+    // ---- one launch (more than 2^30 tiles: one launch per 2^30); the call returns after the stream has run it ----
+    AsCtx& cx = g_as;
+    (void)hipGetLastError();
+    const AsReleased released{cx};
+    hipStream_t st = stream();
+    Image im;
+    const size_t at_counters = im.put(std::vector<u64>(8, 0)), at_items = im.put(items), at_cells = im.put(cells);
+    if (im.bytes.size() + 16 > default_bound(cx.held())) return (int)hipErrorOutOfMemory;
+    ScopedKernelTimer timer("apc_sources_tracegen");
+    PW_TRY(im.upload(cx.jobs, st));
+    char* tab = cx.jobs.as<char>();
+    const u64 per_launch = (u64)1 << 30;
+    for (u64 base = 0; base < tiles; base += per_launch)
+        hipLaunchKernelGGL(apc_sources_tracegen_kernel, dim3((unsigned)std::min(per_launch, tiles - base)), dim3(kBlock), 0, st, (const TraceItemDev*)(tab + at_items),
+                           (uint32_t)items.size(), (const uint2*)(tab + at_cells), base, (u64*)(tab + at_counters));
+    PW_HIP_TRY(hipGetLastError());
+    u64 counters[2] = {0, 0};
+    PW_HIP_TRY(hipMemcpyAsync(counters, tab + at_counters, sizeof counters, hipMemcpyDeviceToHost, st));
+    PW_HIP_TRY(hipStreamSynchronize(st));  // (the image and counters are locals)
+    g_tracegen.tiles16 = counters[0];
+    g_tracegen.tiles4 = counters[1];
+    g_tracegen.bytes_written = bytes_written;
+    return 0;
+}
+
 extern "C" int pw_trace_gather_rows(const PwGatherJob* jobs, size_t n_jobs) {
     if (!jobs_well_formed(jobs, n_jobs)) return -1;
     AsCtx& cx = g_as;
@@ -401,10 +576,10 @@ extern "C" int pw_trace_gather_rows(const PwGatherJob* jobs, size_t n_jobs) {
     return gather(cx, jobs, n_jobs);
 }
 
-extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, const uint32_t* cycle_counts,
-                                          size_t n_apcs, const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to, size_t n_calls,
-                                          uint32_t min_log_height, size_t scratch_bytes, PwApcSources** out, uint32_t* status, uint64_t* info) {
-    if (!out || !status || !info || bridge_bus >= bb::P || (!airs && n_airs) || (!cycle_counts && n_apcs) || ((!call_apc_ids || !call_from || !call_to) && n_calls) ||
+extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, const uint32_t* cycle_counts,
+                                                size_t n_apcs, const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to, size_t n_calls,
+                                                uint32_t min_log_height, size_t scratch_bytes, uint32_t flags, PwApcSources** out, uint32_t* status, uint64_t* info) {
+    if ((flags & ~PW_APC_SOURCES_DIRECT) || !out || !status || !info || bridge_bus >= bb::P || (!airs && n_airs) || (!cycle_counts && n_apcs) || ((!call_apc_ids || !call_from || !call_to) && n_calls) ||
         min_log_height > 31u || n_apcs >= ((size_t)1 << 31) || n_calls >= ((size_t)1 << 31))
         return -1;
     if (segment_of_air)
@@ -419,6 +594,7 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
     const long long rows = time_index::bridge_rows(airs, n_airs, bridge_bus);
     if (rows < 0 || (u64)rows + 1 >= ((u64)1 << 32)) return -1;
     const u64 M = (u64)rows, min_h = (u64)1 << min_log_height;
+    const bool direct = (flags & PW_APC_SOURCES_DIRECT) != 0;
     AsCtx& cx = g_as;
     cx.reset();
     *out = nullptr;
@@ -463,7 +639,8 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
     const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
     {
         // per APC with n calls of L instructions: its rows in an AIR are distinct rows of that AIR, and over all AIRs n * L rows
-        // (a power of two at most doubles them); the residual of an AIR is at most the AIR
+        // (a power of two at most doubles them); the residual of an AIR is at most the AIR. Direct mode has no source matrices, and its
+        // lists are not padded to a matrix's height: n * L entries per APC
         size_t out_bytes = 0, list_rows = 0, width_max = 0, floor_bytes = 0;
         for (size_t k = 0; k < n_parts; ++k) {
             const size_t w = airs[part_air[k]].prover->width, h = std::max<u64>(min_h, (u64)1 << airs[part_air[k]].log_height);
@@ -475,6 +652,10 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
         for (size_t a = 0; a < n_apcs; ++a) {
             if (!calls_of[a]) continue;
             const u64 cover = calls_of[a] * cycle_counts[a], cover2 = next_power_of_two(cover);
+            if (direct) {
+                list_rows += cover;
+                continue;
+            }
             size_t by_air = 0, rows_by_air = 0;
             for (size_t k = 0; k < n_parts; ++k) {
                 const u64 h = std::max<u64>(min_h, std::min<u64>(cover2, (u64)1 << airs[part_air[k]].log_height));
@@ -500,6 +681,9 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
     PwApcSources& R = *result;
     R.n_apcs = n_apcs;
     R.n_airs = n_airs;
+    R.direct = direct;
+    R.traces.resize(n_airs);
+    R.list_base.assign(direct ? n_apcs * n_airs : 0, 0);
     R.sources.resize(n_apcs * n_airs);
     R.residuals.resize(n_airs);
     R.n_calls.assign(calls_of.begin(), calls_of.end());
@@ -584,9 +768,15 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
                 PwApcSources::Source& s = R.sources[a * n_airs + air];
                 s.width = airs[air].prover->width;
                 s.rbs = per_part[k];
+                list_base[a * n_parts + k] = list_total;
+                if (direct) {  // (height stays 0: no matrix)
+                    R.list_base[a * n_airs + air] = list_total;
+                    R.traces[air] = PwApcSources::Trace{airs[air].d_trace, (u64)1 << airs[air].log_height, s.width};
+                    list_total += (calls_of[a] * per_part[k] + 3) & ~(u64)3;
+                    continue;
+                }
                 s.height = std::max<u64>(min_h, next_power_of_two(calls_of[a] * per_part[k]));
                 s.at = place_matrix(src_total, (size_t)s.width * s.height);
-                list_base[a * n_parts + k] = list_total;
                 list_total += (s.height + 3) & ~(u64)3;
                 R.source_bytes += (u64)s.width * s.height * 4;
             }
@@ -595,12 +785,13 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
         R.air_of = air_of;
         R.occ = occ;
         PW_TRY(cx.covered.ensure(M));
-        PW_TRY(cx.lists.ensure(std::max<size_t>(list_total * 4, 16)));
+        DeviceBuf& lists = direct ? R.idx : cx.lists;  // direct: the handle keeps them
+        PW_TRY(lists.ensure(std::max<size_t>(list_total * 4, 16)));
         if (src_total) PW_TRY(R.src.ensure(src_total));
-        cx.extra = R.src.bytes;
+        cx.extra = R.src.bytes + R.idx.bytes;
         cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.covered.p, 0, M, st));
-        PW_HIP_TRY(hipMemsetAsync(cx.lists.p, 0xff, std::max<size_t>(list_total * 4, 16), st));
+        PW_HIP_TRY(hipMemsetAsync(lists.p, 0xff, std::max<size_t>(list_total * 4, 16), st));
         if (n_covered) {
             Image im2;
             const size_t at_occ = im2.put(occ), at_base = im2.put(list_base), at_rbs = im2.put(rbs);
@@ -608,7 +799,7 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
             cx.note();
             char* s2 = cx.small2.as<char>();
             hipLaunchKernelGGL(apc_sources_place_kernel, dim3(div_up(n_covered, kBlock)), block, 0, st, T, n_covered, (const uint32_t*)d_air_of, (const uint32_t*)(s2 + at_occ),
-                               (const u64*)(s2 + at_base), (const uint32_t*)(s2 + at_rbs), cx.lists.as<uint32_t>(), cx.covered.as<uint8_t>());
+                               (const u64*)(s2 + at_base), (const uint32_t*)(s2 + at_rbs), lists.as<uint32_t>(), cx.covered.as<uint8_t>());
             PW_HIP_TRY(hipGetLastError());
             PW_HIP_TRY(hipStreamSynchronize(st));  // (im2 is a local)
         }
@@ -653,7 +844,7 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
         }
         PW_TRY(cx.rlists.ensure(std::max<size_t>(rlist_total * 4, 16)));
         PW_TRY(R.res.ensure(std::max<size_t>(res_total, 16)));
-        cx.extra = R.src.bytes + R.res.bytes;
+        cx.extra = R.src.bytes + R.idx.bytes + R.res.bytes;
         cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.rlists.p, 0xff, std::max<size_t>(rlist_total * 4, 16), st));
         PW_HIP_TRY(hipMemcpyAsync(d_rbase, rlist_base.data(), n_parts * 8, hipMemcpyHostToDevice, st));
@@ -685,4 +876,11 @@ extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32
     cx.stat_residual_bytes = R.residual_bytes;
     *out = result.release();
     return 0;
+}
+
+extern "C" int pw_apc_sources_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, const uint32_t* cycle_counts,
+                                          size_t n_apcs, const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to, size_t n_calls,
+                                          uint32_t min_log_height, size_t scratch_bytes, PwApcSources** out, uint32_t* status, uint64_t* info) {
+    return pw_apc_sources_from_traces_flags(airs, segment_of_air, n_airs, bridge_bus, cycle_counts, n_apcs, call_apc_ids, call_from, call_to, n_calls, min_log_height,
+                                            scratch_bytes, 0, out, status, info);
 }

@@ -363,6 +363,27 @@ pub struct PwGatherJob {
     pub out: *mut u32,
     pub h_out: u64,
 }
+/// `flags` of `pw_apc_sources_from_traces_flags`: keep the index lists, build no source matrices
+pub const PW_APC_SOURCES_DIRECT: u32 = 1;
+/// a cell of `pw_apc_sources_tracegen`: column `col` of the AIR of the APC's instruction `instr` feeds APC column `apc_col`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PwApcCell {
+    pub instr: u32,
+    pub col: u32,
+    pub apc_col: u32,
+}
+/// a job of `pw_apc_sources_tracegen`: the named columns of one APC's trace (`cells` on the host, `d_out` on the device)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PwApcTraceJob {
+    pub apc: u32,
+    pub cells: *const PwApcCell,
+    pub n_cells: usize,
+    pub d_out: *mut u32,
+    pub out_height: u64,
+    pub out_width: u32,
+}
 /// the opaque result of `pw_execution_states_from_traces`: the states of a segment on the device
 #[repr(C)]
 pub struct PwExecutionStates {
@@ -600,6 +621,18 @@ extern "C" {
     pub fn pw_apc_sources_read_residual(e: *const PwApcSources, air: u32, words: *mut u32) -> c_int;
     /// out[8]: covered positions, source bytes, residual bytes, gather jobs, 16-byte-load tiles, 4-byte-load tiles, peak scratch, scratch held
     pub fn pw_apc_sources_last_stats(out: *mut u64);
+    /// `pw_apc_sources_from_traces` with `flags`: 0 = the same call; `PW_APC_SOURCES_DIRECT` = no source matrices, the handle keeps the
+    /// index lists and the AIRs' trace pointers — the traces must outlive the last `pw_apc_sources_tracegen`
+    pub fn pw_apc_sources_from_traces_flags(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, cycle_counts: *const u32,
+                                            n_apcs: usize, call_apc_ids: *const u32, call_from: *const u64, call_to: *const u64, n_calls: usize,
+                                            min_log_height: u32, scratch_bytes: usize, flags: u32, out: *mut *mut PwApcSources, status: *mut u32,
+                                            info: *mut u64) -> c_int;
+    /// the bytes of a direct handle's index lists (0 on a flags-0 handle)
+    pub fn pw_apc_sources_index_bytes(e: *const PwApcSources) -> u64;
+    /// the named columns of the APC traces straight from the chips' traces, all jobs in one launch; -1 = malformed, or no direct handle
+    pub fn pw_apc_sources_tracegen(e: *const PwApcSources, jobs: *const PwApcTraceJob, n_jobs: usize) -> c_int;
+    /// out[6]: jobs, work items, 16-byte-load tiles, 4-byte-load tiles, bytes written, scratch held
+    pub fn pw_apc_sources_tracegen_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
