@@ -1101,6 +1101,82 @@ int pw_merkle_commit_mixed(const uint32_t* const* d_cols, const uint32_t* n_cols
  * Poseidon2(v[i] || v[i + half] || 0^8), then the binary tree; half a power of two; d_digests gets (2 * half - 1) * 8 words. */
 int pw_merkle_commit_ext_pairs(const uint32_t* d_values, size_t half, uint32_t* d_digests);
 
+/* ---- single stages: the opening, DEEP, FRI, scan and layout kernels ----
+ *
+ * One entry point per kernel (family) between the commitments and the proof words, for kernel-level tests and per-stage measurement;
+ * an engine never calls them. Conventions of every call below:
+ *   - device matrices and vectors hold Montgomery words, matrices column-major; an extension element is 4 consecutive words;
+ *   - extension scalars (zeta, gzeta, beta, sum, sum1, sum2, gK, base, a) are HOST pointers to 4 canonical words;
+ *   - tables of opening weights and of gamma powers (d_w, d_w2, d_gpow, d_gq) are device arrays in the form the kernels consume:
+ *     per element 4 int32, the centred representatives (|.| <= (p - 1) / 2) of the element's Montgomery words. pw_stage_opening_weights
+ *     and pw_stage_ext_powers(centred = 1) write that form; a caller may pass any table of it;
+ *   - a call launches on the calling thread's stream and does not wait, except pw_stage_ext_dot and pw_stage_logup_scan, which own
+ *     scratch and release it before they return (they wait for the stream first);
+ *   - -1, before anything is launched: a NULL pointer where one is needed, a scalar word >= p, a log size out of range, a zero size,
+ *     and what a call lists; otherwise 0 or a HIP error code (hipErrorInvalidValue = 1 where a call says so).
+ * x_j = 31 * w^j with w the generator of the order-2^log_n subgroup is row j of the extended domain. */
+
+/* d_w[i] (2^log_h elements), log_h <= 26. on_coefficients = 0: the barycentric weights ((zeta^H - 1) / H) g^i / (zeta - g^i) of the
+ * trace domain, f(zeta) = sum_i f(g^i) w[i]; 1: zeta^bitrev(q) / H, for the coefficient arrays pw_lde_batch leaves. */
+int pw_stage_opening_weights(const uint32_t* zeta, uint32_t log_h, int on_coefficients, uint32_t* d_w);
+
+/* d_out[c] = sum_{q < len} d_w[q] * column c [q], column c at d_cols + c * stride (stride >= len), c < n_cols; with d_w2 (may be
+ * NULL) also d_out2[c] for the second weight vector, in the same pass. d_w / d_w2 not 16-byte aligned: hipErrorInvalidValue. */
+int pw_stage_ext_dot(const uint32_t* d_cols, size_t stride, uint32_t n_cols, size_t len, const uint32_t* d_w, const uint32_t* d_w2,
+                     uint32_t* d_out, uint32_t* d_out2);
+
+/* d_out[k] = base^k, or base^(n - 1 - k) when reversed, k < n; centred: in the table form above, else as Montgomery words.
+ * n > 2^24: hipErrorInvalidValue. */
+int pw_stage_ext_powers(const uint32_t* base, uint32_t n, int reversed, int centred, uint32_t* d_out);
+
+/* d_v[j] = (sum_{k < wa} g[k] a_k[j] + sum_{k < wb} g[wa + k] b_k[j] - sum) / (x_j - zeta), j < 2^log_n, for two matrices of wa and wb
+ * columns of 2^log_n rows (any widths, not both zero); 1 <= log_n <= 27; g = d_gpow, wa + wb elements. */
+int pw_stage_deep(const uint32_t* d_a, uint32_t wa, const uint32_t* d_b, uint32_t wb, uint32_t log_n, const uint32_t* d_gpow,
+                  const uint32_t* sum, const uint32_t* zeta, uint32_t* d_v);
+
+/* The two-term form over the main (W columns), permutation (Wp) and quotient (8) matrices, K1 = W + Wp + 8, g = d_gpow (K1 + Wp elements):
+ *   A1 = sum_{k < W} g[k] f_k + sum_{k < Wp} g[W + k] p_k + sum_{k < 8} g[W + Wp + k] q_k,   A2 = sum_{k < Wp} g[K1 + k] p_k,
+ *   d_v[j] = (A1[j] - sum1) / (x_j - zeta) + (A2[j] - sum2) / (x_j - gzeta).
+ * With gK (may be NULL) the two-point form: A2 += gK * sum_{k < W} g[k] f_k. Wp = 0 (d_plde NULL) is allowed. */
+int pw_stage_deep_logup(const uint32_t* d_lde, uint32_t W, const uint32_t* d_plde, uint32_t Wp, const uint32_t* d_qlde, uint32_t log_n,
+                        const uint32_t* d_gpow, const uint32_t* gK, const uint32_t* sum1, const uint32_t* sum2, const uint32_t* zeta,
+                        const uint32_t* gzeta, uint32_t* d_v);
+
+/* d_out = 4 columns of len words, the coordinates of sum_{k < wa} g[k] a_k + sum_{k < wb} g[wa + k] b_k; with second != 0 four more,
+ * those of sum_{k < wb} g[second + k] b_k. An odd len, or d_a / d_b / d_out not 8-byte aligned: hipErrorInvalidValue. */
+int pw_stage_ext_lincomb(const uint32_t* d_a, uint32_t wa, const uint32_t* d_b, uint32_t wb, size_t len, const uint32_t* d_gpow, uint32_t second,
+                         uint32_t* d_out);
+
+/* d_v[j] = (G1[j] + sum_{k < 8} gq[k] q_k[j] - sum1) / (x_j - zeta) [+ (G2[j] - sum2) / (x_j - gzeta) when two]; d_glde = the four
+ * coordinate columns of G1, then those of G2 (8 columns of 2^log_n; the last four are not read unless two). */
+int pw_stage_deep_from_combo(const uint32_t* d_glde, const uint32_t* d_qlde, uint32_t log_n, const uint32_t* d_gq, const uint32_t* sum1,
+                             const uint32_t* sum2, const uint32_t* zeta, const uint32_t* gzeta, int two, uint32_t* d_v);
+
+/* One FRI round: d_out[i] = (a + b) / 2 + beta (a - b) / (2 shift w^i), a = d_v[i], b = d_v[i + half], i < half = 2^(log_size - 1), w of
+ * order 2^log_size; shift: a canonical non-zero base-field word; 1 <= log_size <= 27. */
+int pw_stage_fri_fold(const uint32_t* d_v, uint32_t log_size, uint32_t shift, const uint32_t* beta, uint32_t* d_out);
+
+/* Inclusive prefix sums of H extension elements into four columns: d_phi_cols[k * H + r] = coordinate k of sum_{i <= r} d_rowsum[i]. */
+int pw_stage_logup_scan(const uint32_t* d_rowsum, size_t H, uint32_t* d_phi_cols);
+
+/* The quotient's two chunks from the unscaled DIF-iNTT of its four coordinate columns over N = 2H points (d_cbr: 4 x N):
+ * d_out[(4 ch + k) H + q] = d_cbr[k N + 2 q + ch] * 31^-(bitrev(q) + ch H) / 2 (8 x H). d_cbr not 8-byte aligned: hipErrorInvalidValue. */
+int pw_stage_quotient_split(const uint32_t* d_cbr, uint32_t log_h, uint32_t* d_out);
+
+/* The row layout behind the w1 columns of the n = 2^log_n-row matrix d_m (column stride n), in place: column w1 + i = column
+ * d_next_cols[i] (a device array, entries < w1) moved up by `step` rows, cyclically, i < n_next; then, when selectors, is_first_row,
+ * is_last_row and is_transition on the rows' points: x_j of the extended domain (trace_domain = 0; the trace has n / 2 rows) or the
+ * trace domain's own g^j (1). */
+int pw_stage_row_layout(uint32_t* d_m, uint32_t log_n, uint32_t w1, const uint32_t* d_next_cols, uint32_t n_next, uint32_t step, int selectors,
+                        int trace_domain);
+
+/* d_out[k N + r + (i << b)] = sum_{c < n_chunks} d_part[(4 c + k) m + i] mod p, k < 4, i < m (plain sums of words: canonical in,
+ * canonical out). r < 2^b and r + 2^b (m - 1) < N, else -1. */
+int pw_stage_part_scatter(const uint32_t* d_part, uint32_t n_chunks, size_t m, uint32_t b, uint32_t r, size_t N, uint32_t* d_out);
+
+/* d_y[i] += a * d_x[i] over n extension elements; a NULL: a = 1. */
+int pw_stage_ext_axpy(uint32_t* d_y, const uint32_t* a, const uint32_t* d_x, size_t n);
+
 /* Host-side Poseidon2 permutation used by the transcript (canonical words in/out). This is also the known-answer-test
  * hook: after pw_set_poseidon2_constants a maintainer feeds it the vector of the backend's own Poseidon2 test. */
 void pw_poseidon2_permute_host(uint32_t* state16);

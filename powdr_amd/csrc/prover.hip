@@ -1107,6 +1107,153 @@ extern "C" int pw_merkle_commit_ext_pairs(const uint32_t* d_values, size_t half,
     return merkle_commit_ext_pairs(reinterpret_cast<const bb::Ext*>(d_values), half, d_digests);
 }
 
+// ---- the opening, DEEP, FRI, scan and layout kernels, one entry point per function of prover_internal.hpp -------------------
+// Thin wrappers: arguments are validated (-1, nothing launched), host scalars converted (canonical -> Montgomery), the internal
+// function's own refusals passed through. No kernel code lives here. Launches go to stream() and are not waited for, except by
+// the two calls that own scratch (StageScratch below).
+namespace {
+
+constexpr uint32_t kStageMaxLog = 27;  // the field's two-adicity: field::root_of_unity and the kernels' 32-bit row powers end here
+
+// 4 canonical host words -> Ext; false: a NULL pointer or a word >= p
+bool stage_ext(const uint32_t* c4, bb::Ext* out) {
+    if (!c4) return false;
+    for (int k = 0; k < 4; ++k) {
+        if (c4[k] >= bb::P) return false;
+        out->c[k] = bb::to_monty(c4[k]);
+    }
+    return true;
+}
+
+// scratch of one stage call: released when the call returns, after the launch stream has drained (the kernels still read it)
+struct StageScratch {
+    void* p = nullptr;
+    int alloc(size_t bytes) { return (int)hipMalloc(&p, bytes ? bytes : 4); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    ~StageScratch() {
+        if (!p) return;
+        (void)hipStreamSynchronize(stream());
+        (void)hipFree(p);
+    }
+};
+
+}  // namespace
+
+extern "C" int pw_stage_opening_weights(const uint32_t* zeta, uint32_t log_h, int on_coefficients, uint32_t* d_w) {
+    (void)hipGetLastError();
+    bb::Ext z;
+    if (!stage_ext(zeta, &z) || !d_w || log_h > kStageMaxLog - 1) return -1;
+    return on_coefficients ? zeta_weights(z, (int)log_h, reinterpret_cast<bb::Ext*>(d_w))
+                           : barycentric_weights(z, (int)log_h, reinterpret_cast<bb::Ext*>(d_w));
+}
+
+extern "C" int pw_stage_ext_dot(const uint32_t* d_cols, size_t stride, uint32_t n_cols, size_t len, const uint32_t* d_w, const uint32_t* d_w2,
+                                uint32_t* d_out, uint32_t* d_out2) {
+    (void)hipGetLastError();
+    if (!d_cols || !d_w || !d_out || (d_w2 && !d_out2) || !n_cols || !len || stride < len) return -1;
+    if (misaligned16(d_w) || misaligned16(d_w2)) return (int)hipErrorInvalidValue;  // (the kernel loads a weight as one uint4)
+    const size_t n_chunks = (len + 8191) / 8192;  // (ext_dot_columns2's scratch, prover_internal.hpp)
+    StageScratch s;
+    TRY(s.alloc((d_w2 ? 2 : 1) * (size_t)n_cols * n_chunks * sizeof(bb::Ext)));
+    const bb::Ext* w = reinterpret_cast<const bb::Ext*>(d_w);
+    if (!d_w2) return ext_dot_columns(d_cols, stride, n_cols, len, w, reinterpret_cast<bb::Ext*>(d_out), s.as<bb::Ext>());
+    return ext_dot_columns2(d_cols, stride, n_cols, len, w, reinterpret_cast<const bb::Ext*>(d_w2), reinterpret_cast<bb::Ext*>(d_out),
+                            reinterpret_cast<bb::Ext*>(d_out2), s.as<bb::Ext>());
+}
+
+extern "C" int pw_stage_ext_powers(const uint32_t* base, uint32_t n, int reversed, int centred, uint32_t* d_out) {
+    (void)hipGetLastError();
+    bb::Ext b;
+    if (!stage_ext(base, &b) || !d_out) return -1;
+    return ext_powers(b, n, reversed != 0, centred != 0, reinterpret_cast<bb::Ext*>(d_out));
+}
+
+extern "C" int pw_stage_deep(const uint32_t* d_a, uint32_t wa, const uint32_t* d_b, uint32_t wb, uint32_t log_n, const uint32_t* d_gpow,
+                             const uint32_t* sum, const uint32_t* zeta, uint32_t* d_v) {
+    (void)hipGetLastError();
+    bb::Ext s, z;
+    if (!stage_ext(sum, &s) || !stage_ext(zeta, &z) || !d_gpow || !d_v || (wa && !d_a) || (wb && !d_b) || !(wa | wb)) return -1;
+    if (log_n < 1 || log_n > kStageMaxLog) return -1;
+    return deep_quotient(d_a, wa, d_b, wb, (size_t)1 << log_n, (int)log_n, reinterpret_cast<const bb::Ext*>(d_gpow), s, z,
+                         reinterpret_cast<bb::Ext*>(d_v));
+}
+
+extern "C" int pw_stage_deep_logup(const uint32_t* d_lde, uint32_t W, const uint32_t* d_plde, uint32_t Wp, const uint32_t* d_qlde, uint32_t log_n,
+                                   const uint32_t* d_gpow, const uint32_t* gK, const uint32_t* sum1, const uint32_t* sum2, const uint32_t* zeta,
+                                   const uint32_t* gzeta, uint32_t* d_v) {
+    (void)hipGetLastError();
+    bb::Ext s1, s2, z, gz, k = bb::ext_zero();
+    if (!stage_ext(sum1, &s1) || !stage_ext(sum2, &s2) || !stage_ext(zeta, &z) || !stage_ext(gzeta, &gz) || (gK && !stage_ext(gK, &k))) return -1;
+    if (!d_gpow || !d_qlde || !d_v || (W && !d_lde) || (Wp && !d_plde)) return -1;
+    if (log_n < 1 || log_n > kStageMaxLog) return -1;
+    const size_t N = (size_t)1 << log_n;
+    const bb::Ext* g = reinterpret_cast<const bb::Ext*>(d_gpow);
+    bb::Ext* v = reinterpret_cast<bb::Ext*>(d_v);
+    return gK ? deep_quotient_two_point(d_lde, W, d_plde, Wp, d_qlde, N, (int)log_n, g, k, s1, s2, z, gz, v)
+              : deep_quotient_logup(d_lde, W, d_plde, Wp, d_qlde, N, (int)log_n, g, s1, s2, z, gz, v);
+}
+
+extern "C" int pw_stage_ext_lincomb(const uint32_t* d_a, uint32_t wa, const uint32_t* d_b, uint32_t wb, size_t len, const uint32_t* d_gpow,
+                                    uint32_t second, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_gpow || !d_out || (wa && !d_a) || (wb && !d_b) || !(wa | wb) || !len) return -1;
+    return ext_lincomb(d_a, wa, d_b, wb, len, reinterpret_cast<const bb::Ext*>(d_gpow), second, d_out);
+}
+
+extern "C" int pw_stage_deep_from_combo(const uint32_t* d_glde, const uint32_t* d_qlde, uint32_t log_n, const uint32_t* d_gq, const uint32_t* sum1,
+                                        const uint32_t* sum2, const uint32_t* zeta, const uint32_t* gzeta, int two, uint32_t* d_v) {
+    (void)hipGetLastError();
+    bb::Ext s1, s2, z, gz;
+    if (!stage_ext(sum1, &s1) || !stage_ext(sum2, &s2) || !stage_ext(zeta, &z) || !stage_ext(gzeta, &gz)) return -1;
+    if (!d_glde || !d_qlde || !d_gq || !d_v || log_n < 1 || log_n > kStageMaxLog) return -1;
+    return deep_from_combo(d_glde, d_qlde, (size_t)1 << log_n, (int)log_n, reinterpret_cast<const bb::Ext*>(d_gq), s1, s2, z, gz, two != 0,
+                           reinterpret_cast<bb::Ext*>(d_v));
+}
+
+extern "C" int pw_stage_fri_fold(const uint32_t* d_v, uint32_t log_size, uint32_t shift, const uint32_t* beta, uint32_t* d_out) {
+    (void)hipGetLastError();
+    bb::Ext b;
+    if (!stage_ext(beta, &b) || !d_v || !d_out || log_size < 1 || log_size > kStageMaxLog || !shift || shift >= bb::P) return -1;
+    return fri_fold(reinterpret_cast<const bb::Ext*>(d_v), (size_t)1 << (log_size - 1), (int)log_size, bb::to_monty(shift), b,
+                    reinterpret_cast<bb::Ext*>(d_out));
+}
+
+extern "C" int pw_stage_logup_scan(const uint32_t* d_rowsum, size_t H, uint32_t* d_phi_cols) {
+    (void)hipGetLastError();
+    if (!d_rowsum || !d_phi_cols || !H || H > ((size_t)1 << kStageMaxLog)) return -1;
+    StageScratch s;
+    TRY(s.alloc((H / 4096 + 1) * sizeof(bb::Ext)));  // (logup_perm_trace's d_block_totals, prover_internal.hpp)
+    return logup_scan(reinterpret_cast<const bb::Ext*>(d_rowsum), H, s.as<bb::Ext>(), d_phi_cols);
+}
+
+extern "C" int pw_stage_quotient_split(const uint32_t* d_cbr, uint32_t log_h, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_cbr || !d_out || log_h > kStageMaxLog - 1) return -1;
+    if ((uintptr_t)d_cbr & 7) return (int)hipErrorInvalidValue;  // (the kernel loads a pair of rows as one uint2)
+    return quotient_split(d_cbr, (size_t)1 << log_h, (int)log_h, d_out);
+}
+
+extern "C" int pw_stage_row_layout(uint32_t* d_m, uint32_t log_n, uint32_t w1, const uint32_t* d_next_cols, uint32_t n_next, uint32_t step,
+                                   int selectors, int trace_domain) {
+    (void)hipGetLastError();
+    if (!d_m || (n_next && !d_next_cols) || log_n < 1 || log_n > kStageMaxLog) return -1;
+    return row_layout_columns(d_m, (size_t)1 << log_n, (int)log_n, w1, d_next_cols, n_next, step, selectors != 0, trace_domain != 0);
+}
+
+extern "C" int pw_stage_part_scatter(const uint32_t* d_part, uint32_t n_chunks, size_t m, uint32_t b, uint32_t r, size_t N, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_part || !d_out || !n_chunks || !m || b > kStageMaxLog || (r >> b)) return -1;
+    if (m > (N >> b) || r + ((m - 1) << b) >= N) return -1;  // the last row written, r + 2^b (m - 1), lies inside the N-row vector
+    return part_scatter(d_part, n_chunks, m, (int)b, r, N, d_out);
+}
+
+extern "C" int pw_stage_ext_axpy(uint32_t* d_y, const uint32_t* a, const uint32_t* d_x, size_t n) {
+    (void)hipGetLastError();
+    bb::Ext e;
+    if (!d_y || !d_x || !n || (a && !stage_ext(a, &e))) return -1;
+    return ext_axpy(reinterpret_cast<bb::Ext*>(d_y), a ? &e : nullptr, reinterpret_cast<const bb::Ext*>(d_x), n);
+}
+
 extern "C" int pw_set_poseidon2_constants(const uint32_t* ext_rc, const uint32_t* int_rc) {
     return poseidon2_set_constants(ext_rc, int_rc);
 }

@@ -17,6 +17,9 @@ class PwStarkConfig(C.Structure):
 PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create", "pw_prover_create_logup", "pw_verify_logup", "pw_prover_trace_root", "pw_prover_set_bus_seed", "pw_prover_logup_path", "pw_prove_airs", "pw_verify_airs", "pw_prove_segment", "pw_verify_segment", "pw_commitment_digest", "pw_logup_group_starts", "pw_prover_width", "pw_prover_reserve", "pw_prover_stream_log_blocks", "pw_prover_max_constraint_degree", "pw_prover_destroy", "pw_prover_prove", "pw_prover_prove_consuming", "pw_prover_stream_log_blocks_consuming", "pw_trace_from_coefficients", "pw_prover_device_bytes",
                   "pw_lde_batch", "pw_lde_fused", "pw_lde_subcoset", "pw_merkle_commit", "pw_poseidon2_permute_host",
                   "pw_merkle_leaf_hash", "pw_merkle_leaf_absorb", "pw_merkle_commit_mixed", "pw_merkle_commit_ext_pairs",
+                  "pw_stage_opening_weights", "pw_stage_ext_dot", "pw_stage_ext_powers", "pw_stage_deep", "pw_stage_deep_logup",
+                  "pw_stage_ext_lincomb", "pw_stage_deep_from_combo", "pw_stage_fri_fold", "pw_stage_logup_scan", "pw_stage_quotient_split",
+                  "pw_stage_row_layout", "pw_stage_part_scatter", "pw_stage_ext_axpy",
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
@@ -96,6 +99,27 @@ lib.pw_merkle_commit_mixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_u
 lib.pw_merkle_commit_ext_pairs.restype = C.c_int
 lib.pw_merkle_commit_ext_pairs.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
 lib.pw_poseidon2_permute_host.argtypes = [C.c_void_p]
+# the stage entry points of the opening, DEEP, FRI, scan and layout kernels (include/powdr_prover.h): device pointers and host
+# pointers to 4 canonical words alike travel as c_void_p
+_STAGE_ARGTYPES = {
+    "pw_stage_opening_weights": [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p],
+    "pw_stage_ext_dot": [C.c_void_p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pw_stage_ext_powers": [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p],
+    "pw_stage_deep": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pw_stage_deep_logup": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p],
+    "pw_stage_ext_lincomb": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p],
+    "pw_stage_deep_from_combo": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "pw_stage_fri_fold": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "pw_stage_logup_scan": [C.c_void_p, C.c_size_t, C.c_void_p],
+    "pw_stage_quotient_split": [C.c_void_p, C.c_uint32, C.c_void_p],
+    "pw_stage_row_layout": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int],
+    "pw_stage_part_scatter": [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p],
+    "pw_stage_ext_axpy": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+}
+for _name, _argtypes in _STAGE_ARGTYPES.items():
+    getattr(lib, _name).restype = C.c_int
+    getattr(lib, _name).argtypes = _argtypes
 
 
 def _vp(a):

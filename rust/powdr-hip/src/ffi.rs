@@ -727,6 +727,22 @@ extern "C" {
     pub fn pw_merkle_leaf_absorb(d_matrix: *const u32, col_stride: usize, d_cols: *const *const u32, n_cols: u32, pos0: u32, height: usize, row_stride: usize, row_offset: usize, d_state: *mut u32, d_digests: *mut u32, first: c_int, last: c_int) -> c_int;
     pub fn pw_merkle_commit_mixed(d_cols: *const *const u32, n_cols_by_log: *const u32, external_by_log: *const u32, l: u32, d_digests: *mut u32, d_inject: *mut u32) -> c_int;
     pub fn pw_merkle_commit_ext_pairs(d_values: *const u32, half: usize, d_digests: *mut u32) -> c_int;
+    // single stages of the opening, DEEP, FRI, scan and layout kernels (tests and measurement only; scalars: host, 4 canonical words)
+    pub fn pw_stage_opening_weights(zeta: *const u32, log_h: u32, on_coefficients: c_int, d_w: *mut u32) -> c_int;
+    pub fn pw_stage_ext_dot(d_cols: *const u32, stride: usize, n_cols: u32, len: usize, d_w: *const u32, d_w2: *const u32, d_out: *mut u32, d_out2: *mut u32) -> c_int;
+    pub fn pw_stage_ext_powers(base: *const u32, n: u32, reversed: c_int, centred: c_int, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_deep(d_a: *const u32, wa: u32, d_b: *const u32, wb: u32, log_n: u32, d_gpow: *const u32, sum: *const u32, zeta: *const u32, d_v: *mut u32) -> c_int;
+    pub fn pw_stage_deep_logup(d_lde: *const u32, w: u32, d_plde: *const u32, wp: u32, d_qlde: *const u32, log_n: u32, d_gpow: *const u32, g_k: *const u32,
+                               sum1: *const u32, sum2: *const u32, zeta: *const u32, gzeta: *const u32, d_v: *mut u32) -> c_int;
+    pub fn pw_stage_ext_lincomb(d_a: *const u32, wa: u32, d_b: *const u32, wb: u32, len: usize, d_gpow: *const u32, second: u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_deep_from_combo(d_glde: *const u32, d_qlde: *const u32, log_n: u32, d_gq: *const u32, sum1: *const u32, sum2: *const u32,
+                                    zeta: *const u32, gzeta: *const u32, two: c_int, d_v: *mut u32) -> c_int;
+    pub fn pw_stage_fri_fold(d_v: *const u32, log_size: u32, shift: u32, beta: *const u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_logup_scan(d_rowsum: *const u32, h: usize, d_phi_cols: *mut u32) -> c_int;
+    pub fn pw_stage_quotient_split(d_cbr: *const u32, log_h: u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_row_layout(d_m: *mut u32, log_n: u32, w1: u32, d_next_cols: *const u32, n_next: u32, step: u32, selectors: c_int, trace_domain: c_int) -> c_int;
+    pub fn pw_stage_part_scatter(d_part: *const u32, n_chunks: u32, m: usize, b: u32, r: u32, n: usize, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_ext_axpy(d_y: *mut u32, a: *const u32, d_x: *const u32, n: usize) -> c_int;
     pub fn pw_prover_specialise(p: *mut PwProver) -> c_int;
     pub fn pw_prover_specialised(p: *const PwProver, n_kernels: *mut usize, code_bytes: *mut usize, n_chunks: *mut usize) -> c_int;
     pub fn pw_prove_segments_multi(devices: *const c_int, n_workers: usize, segment_cells: *const u64, n_segments: usize,

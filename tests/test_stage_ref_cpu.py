@@ -1,0 +1,216 @@
+"""tests/_stage_ref.py (the reference the stage-kernel GPU tests compare with) held against things it did not define: the oracle's
+extension field and transforms, polynomial identities (an opening IS an evaluation, a fold IS f_even + beta f_odd), and, for every
+vectorised routine, a scalar twin in Python integers. No GPU."""
+import numpy as np
+
+from oracle import stark_model as sm
+from tests import _stage_ref as ref
+
+P = ref.P
+EDGE_WORDS = [0, 1, P - 1, (P - 1) // 2, (P + 1) // 2]
+
+
+def rand_ext(rng, n=None):
+    return rng.integers(0, P, 4 if n is None else (n, 4), dtype=np.uint64)
+
+
+def horner(coeffs, x):
+    """sum_k c_k x^k for coefficients in F or E, x in E"""
+    acc = ref.ZERO
+    for c in reversed(list(coeffs)):
+        acc = ref.ext_add(ref.ext_mul(acc, x), ref.ext(c))
+    return acc
+
+
+def as_tuples(a):
+    return [tuple(int(x) for x in e) for e in np.asarray(a).reshape(-1, 4)]
+
+
+def edge_elements(rng, n):
+    return [tuple(int(x) for x in rng.choice(EDGE_WORDS, 4)) for _ in range(n)] + [(0, 1, 0, 0), (P - 1,) * 4, ref.ONE]
+
+
+def test_extension_arithmetic_is_the_oracles():
+    rng = np.random.default_rng(1)
+    elems = as_tuples(rand_ext(rng, 20)) + edge_elements(rng, 30)
+    for a in elems:
+        for b in elems[::7]:
+            assert ref.ext_mul(a, b) == tuple(sm.ext_mul(a, b).tolist()), (a, b)
+        if a != ref.ZERO:
+            assert ref.ext_inv(a) == tuple(sm.ext_inv(a).tolist()), a
+            assert ref.ext_mul(a, ref.ext_inv(a)) == ref.ONE
+    assert ref.ext_inv(ref.ZERO) == ref.ZERO and ref.inv(0) == 0
+
+
+def test_domain_is_the_oracles_extended_domain():
+    """the polynomial X, given by its values g^i, extends to x_j itself: the shift and the order of the rows are the oracle's"""
+    for log_h in (1, 3, 6):
+        got = sm.lde(ref.domain(log_h, 1).astype(np.uint32), 1, log_h)
+        assert (got == ref.domain(log_h + 1)).all()
+        assert int(got[0]) == ref.SHIFT
+    assert pow(ref.root(5), 32, P) == 1 and pow(ref.root(5), 16, P) == P - 1 and ref.root(0) == 1
+
+
+def test_opening_weights_open_a_polynomial():
+    rng = np.random.default_rng(2)
+    for log_h in (3, 6):
+        H = 1 << log_h
+        c = rng.integers(0, P, H, dtype=np.uint64)
+        g = ref.domain(log_h, 1)
+        evals = np.array([horner(c, ref.ext(int(x)))[0] for x in g], np.uint64)
+        assert (sm.dft(evals.astype(np.uint32), inverse=True) == c).all()  # natural order, the oracle's root
+        for zeta in as_tuples(rand_ext(rng, 3)) + [ref.ext(0), (P - 1,) * 4, (0, 1, 0, 0)]:
+            want = horner(c, zeta)
+            assert as_tuples(ref.ext_dot(evals[None, :], ref.barycentric_weights(zeta, log_h))) == [want], (log_h, zeta)
+            # the layout of pw_lde_batch's d_coeffs: H c_bitrev(q)
+            scaled = np.array([H * int(c[ref.bitrev(q, log_h)]) % P for q in range(H)], np.uint64)
+            assert as_tuples(ref.ext_dot(scaled[None, :], ref.coefficient_weights(zeta, log_h))) == [want], (log_h, zeta)
+        # a zeta inside the trace domain: the factor zeta^H - 1 vanishes, every weight is 0 (no division by zero is relied on)
+        assert not ref.barycentric_weights(ref.ext(1), log_h).any()
+        assert not ref.barycentric_weights(ref.ext(int(g[3])), log_h).any()
+    assert as_tuples(ref.coefficient_weights((5, 6, 7, 8), 0)) == [ref.ONE]
+
+
+def test_fri_fold_halves_a_polynomial():
+    rng = np.random.default_rng(3)
+    log_n = 4
+    n = 1 << log_n
+    f = as_tuples(rand_ext(rng, n))
+    beta = tuple(int(x) for x in rand_ext(rng))
+    folded = [ref.ext_add(fe, ref.ext_mul(beta, fo)) for fe, fo in zip(f[0::2], f[1::2])]  # f_even + beta f_odd
+    for shift in (ref.SHIFT, 1):
+        v = np.array([horner(f, ref.ext(int(x))) for x in ref.domain(log_n, shift)], np.uint64)
+        want = [horner(folded, ref.ext(int(x))) for x in ref.domain(log_n - 1, shift * shift % P)]
+        assert as_tuples(ref.fri_fold(v, log_n, shift, beta)) == want, shift
+
+
+def test_vector_routines_equal_their_scalar_twins():
+    rng = np.random.default_rng(4)
+    a, b = rand_ext(rng, 40), rand_ext(rng, 40)
+    a[:10] = np.array(edge_elements(rng, 7), np.uint64)
+    assert as_tuples(ref.vmul(a, b)) == [ref.ext_mul(x, y) for x, y in zip(as_tuples(a), as_tuples(b))]
+    assert as_tuples(ref.vadd(a, b)) == [ref.ext_add(x, y) for x, y in zip(as_tuples(a), as_tuples(b))]
+    assert as_tuples(ref.vsub(a, b)) == [ref.ext_sub(x, y) for x, y in zip(as_tuples(a), as_tuples(b))]
+    a[11] = 0
+    assert as_tuples(ref.vext_inv(a)) == [ref.ext_inv(x) for x in as_tuples(a)]
+    k = rng.integers(0, P, 40, dtype=np.uint64)
+    k[:5] = EDGE_WORDS
+    assert ref.vinv(k).tolist() == [ref.inv(int(x)) for x in k] and ref.vpow(k, 12345).tolist() == [pow(int(x), 12345, P) for x in k]
+    assert as_tuples(ref.vscale(a, k)) == [ref.ext_scale(x, int(y)) for x, y in zip(as_tuples(a), k)]
+    # sums over rows and columns
+    log_n = 3
+    N = 1 << log_n
+    ma, mb = rng.integers(0, P, (3, N), dtype=np.uint64), rng.integers(0, P, (2, N), dtype=np.uint64)
+    g = rand_ext(rng, 5)
+    total, zeta = as_tuples(rand_ext(rng, 2))
+    assert as_tuples(ref.lincomb(ma, g[:3])) == ref.lincomb_scalar(ma, g[:3])
+    assert as_tuples(ref.deep(ma, mb, g, total, zeta, log_n)) == ref.deep_scalar(ma, mb, g, total, zeta, log_n)
+    assert as_tuples(ref.ext_dot(ma, rand_ext(np.random.default_rng(5), N))) == ref.ext_dot_scalar(ma, rand_ext(np.random.default_rng(5), N))
+    v = rand_ext(rng, 2 * N)
+    assert as_tuples(ref.fri_fold(v, log_n + 1, 31 * 31, zeta)) == ref.fri_fold_scalar(v, log_n + 1, 31 * 31, zeta)
+    assert ref.scan(v).tolist() == ref.scan_scalar(v)
+    assert as_tuples(ref.ext_powers(zeta, 6)) == [ref.ext_pow(zeta, e) for e in range(6)]
+    assert as_tuples(ref.ext_powers(zeta, 6, True)) == [ref.ext_pow(zeta, 5 - e) for e in range(6)]
+    y = rand_ext(rng, 2 * N)
+    assert as_tuples(ref.ext_axpy(y, zeta, v)) == [ref.ext_add(p, ref.ext_mul(zeta, q)) for p, q in zip(as_tuples(y), as_tuples(v))]
+    assert as_tuples(ref.ext_axpy(y, None, v)) == as_tuples(ref.vadd(y, v))
+
+
+def test_two_term_deep_forms_agree():
+    """deep_logup written out row by row with Python integers; the route over ext_lincomb + deep_from_combo gives the same vector"""
+    rng = np.random.default_rng(6)
+    log_n, W, Wp = 2, 3, 5
+    N, K1 = 1 << log_n, W + Wp + 8
+    lde, plde, qlde = (rng.integers(0, P, (w, N), dtype=np.uint64) for w in (W, Wp, 8))
+    g = rand_ext(rng, K1 + Wp)
+    gt = as_tuples(g)
+    sum1, sum2, zeta, gzeta, gK = as_tuples(rand_ext(rng, 5))
+    x = ref.domain(log_n)
+    for two_point in (False, True):
+        want = []
+        for j in range(N):
+            row = ref.lincomb_scalar(lde[:, j:j + 1], gt[:W])[0]
+            a1 = ref.ext_add(ref.ext_add(row, ref.lincomb_scalar(plde[:, j:j + 1], gt[W:W + Wp])[0]),
+                             ref.lincomb_scalar(qlde[:, j:j + 1], gt[W + Wp:K1])[0])
+            a2 = ref.lincomb_scalar(plde[:, j:j + 1], gt[K1:])[0]
+            if two_point:
+                a2 = ref.ext_add(a2, ref.ext_mul(gK, row))
+            xe = ref.ext(int(x[j]))
+            want.append(ref.ext_add(ref.ext_mul(ref.ext_sub(a1, sum1), ref.ext_inv(ref.ext_sub(xe, zeta))),
+                                    ref.ext_mul(ref.ext_sub(a2, sum2), ref.ext_inv(ref.ext_sub(xe, gzeta)))))
+        assert as_tuples(ref.deep_logup(lde, plde, qlde, g, sum1, sum2, zeta, gzeta, log_n, gK if two_point else None)) == want
+    combo = ref.ext_lincomb(lde, plde, g, K1)
+    assert combo.shape == (8, N) and ref.ext_lincomb(lde, plde, g, 0).shape == (4, N)
+    assert (ref.deep_from_combo(combo, qlde, g[W + Wp:K1], sum1, sum2, zeta, gzeta, True, log_n)
+            == ref.deep_logup(lde, plde, qlde, g, sum1, sum2, zeta, gzeta, log_n)).all()
+    # without the second term: the first quotient alone, i.e. deep over (lde | plde | qlde) with the first K1 powers
+    assert (ref.deep_from_combo(combo, qlde, g[W + Wp:K1], sum1, sum2, zeta, gzeta, False, log_n)
+            == ref.deep(np.concatenate([lde, plde]), qlde, g[:K1], sum1, zeta, log_n)).all()
+
+
+def test_small_kernels_equal_their_formulas():
+    rng = np.random.default_rng(7)
+    # quotient_split
+    log_h = 3
+    H = 1 << log_h
+    cbr = rng.integers(0, P, (4, 2 * H), dtype=np.uint64)
+    got = ref.quotient_split(cbr, log_h)
+    sinv = ref.inv(ref.SHIFT)
+    for ch in range(2):
+        for k in range(4):
+            for q in range(H):
+                assert int(got[4 * ch + k, q]) == int(cbr[k, 2 * q + ch]) * pow(sinv, ref.bitrev(q, log_h) + ch * H, P) * ref.inv(2) % P
+    assert ref.quotient_split(cbr[:, :2], 0).tolist() == [[int(cbr[k, 0]) * ref.inv(2) % P] for k in range(4)] + \
+        [[int(cbr[k, 1]) * sinv * ref.inv(2) % P] for k in range(4)]
+    # row_layout: shifted columns, and the selectors through the identities that define them
+    log_n = 3
+    n = 1 << log_n
+    m = rng.integers(0, P, (4, n), dtype=np.uint64)
+    for trace_domain in (False, True):
+        for step in (1, 2):
+            out = ref.row_layout(m, log_n, [2, 0, 2], step, True, trace_domain)
+            assert out.shape == (6, n)
+            for i, c in enumerate([2, 0, 2]):
+                assert [int(out[i, j]) for j in range(n)] == [int(m[c, (j + step) % n]) for j in range(n)]
+            w = ref.root(log_n)
+            Hh, g, s = (n, w, 1) if trace_domain else (n // 2, w * w % P, ref.SHIFT)
+            ginv = ref.inv(g)
+            for j in range(n):
+                x = s * pow(w, j, P) % P
+                z = (pow(x, Hh, P) - 1) % P
+                first, last, trans = (int(out[3 + t, j]) for t in range(3))
+                assert trans == (x - ginv) % P
+                assert first * (x - 1) % P == z and last * (x - ginv) % P == z
+                if trace_domain:  # Z_H = 0 on every row: the products above say nothing at the roots themselves
+                    assert first == (Hh if j == 0 else 0) and last == (Hh * g % P if j == n - 1 else 0)
+                    # the quotient polynomial's value at its root: (x^H - 1) / (x - 1) = 1 + x + ... + x^(H-1)
+                    assert sum(pow(x, e, P) for e in range(Hh)) % P == first
+        assert ref.row_layout(m, log_n, [], 1, False, trace_domain).shape == (0, n)
+        assert ref.row_layout(m, log_n, [1], 1, False, trace_domain).shape == (1, n)
+    # Z_H(x) / (x - g^-1) at x = g^-1 on the trace domain: sum_e x^e g^-(H-1-e) = H x^(H-1) = H g
+    assert int(ref.row_layout(m, log_n, [], 1, True, True)[1, n - 1]) == n * pow(ref.inv(ref.root(log_n)), n - 1, P) % P
+    # part_scatter
+    part = rng.integers(0, P, (3, 4, 5), dtype=np.uint64)
+    b, r, N = 2, 3, 24
+    before = rng.integers(0, P, (4, N), dtype=np.uint64)
+    got = ref.part_scatter(part, b, r, before)
+    want = before.copy()
+    for k in range(4):
+        for i in range(5):
+            want[k, r + (i << b)] = sum(int(part[c, k, i]) for c in range(3)) % P
+    assert (got == want).all()
+
+
+def test_centred_encoding_round_trips():
+    rng = np.random.default_rng(8)
+    c = np.concatenate([rng.integers(0, P, 1000, dtype=np.uint64), np.array(EDGE_WORDS, np.uint64), ref.from_word(np.array(EDGE_WORDS, np.uint64))])
+    t = ref.centred_encode(c)
+    assert t.dtype == np.int32 and (np.abs(t.astype(np.int64)) <= ref.HALF).all()
+    assert (ref.centred_decode(t) == c).all()
+    assert ((t.astype(np.int64) - ref.to_word(c).astype(np.int64)) % P == 0).all()
+    # the two neighbours of p / 2, as WORDS
+    assert ref.centred_encode(ref.from_word(np.array([(P - 1) // 2, (P + 1) // 2], np.uint64))).tolist() == [ref.HALF, -ref.HALF]
+    # and the oracle's Montgomery conversion is the one used here
+    from oracle import apc_model as om
+
+    assert (om.to_monty(c.astype(np.uint32)) == ref.to_word(c)).all() and (om.from_monty(c.astype(np.uint32)) == ref.from_word(c)).all()
