@@ -298,39 +298,16 @@ __global__ __launch_bounds__(kBlock) void apc_calls_tally_kernel(const u64* __re
     wave_count(counters, key);
 }
 
-struct AcCtx {
-    DeviceBuf small, count, off, cand, item_off, fail, done, V, end, mx, cflag, cfirst, longs, disc, keep, calls, temp, states, icount, tkey, tkey_s, idx, idx_s, pcs, pc_t, regtab, tkeys;
-    register_states::Ctx stage;  // of the trace route with registers (register_states.hpp)
-    size_t peak = 0;
+struct AcCtx : Scratch {
+    Buf small{*this}, count{*this}, off{*this}, cand{*this}, item_off{*this}, fail{*this}, done{*this}, V{*this}, end{*this}, mx{*this}, cflag{*this}, cfirst{*this},
+        longs{*this}, disc{*this}, keep{*this}, calls{*this}, temp{*this}, states{*this}, regtab{*this}, tkeys{*this};
+    time_index::Stage index{*this};      // of the trace route
+    register_states::Ctx stage{*this};  // of the trace route with registers (register_states.hpp)
     uint64_t long_threshold = 0;  // 0: kLongDefault
     uint64_t stat_candidates = 0, stat_valid = 0, stat_components = 0, stat_longest = 0, stat_long = 0;
-    DeviceBuf* all[27] = {&small, &count, &off, &cand, &item_off, &fail, &done, &V, &end, &mx, &cflag, &cfirst, &longs, &disc, &keep, &calls, &temp, &states, &icount,
-                          &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &regtab, &tkeys};
-    size_t held() const {
-        size_t s = stage.held();
-        for (DeviceBuf* b : all) s += b->bytes;
-        return s;
-    }
-    void note() { peak = std::max(peak, held()); }
+    void reset_stats() override { stat_candidates = stat_valid = stat_components = stat_longest = stat_long = 0; }
 };
 thread_local AcCtx g_ac;
-struct AcReleased {
-    AcCtx& cx;
-    ~AcReleased() {
-        for (DeviceBuf* b : cx.all) b->release();
-        cx.stage.release();
-    }
-};
-
-template <class F>
-int with_temp(AcCtx& cx, F f) {
-    size_t bytes = 0;
-    PW_HIP_TRY(f(nullptr, bytes));
-    PW_TRY(cx.temp.ensure(std::max<size_t>(bytes, 16)));
-    cx.note();
-    PW_HIP_TRY(f(cx.temp.p, bytes));
-    return 0;
-}
 
 // what the argument check leaves for the device: the tables in the kernels' layout
 struct HostTables {
@@ -405,7 +382,7 @@ extern "C" void pw_apc_calls_last_stats(uint64_t* out) {
     out[2] = g_ac.stat_components;
     out[3] = g_ac.stat_longest;
     out[4] = g_ac.stat_long;
-    out[5] = g_ac.peak;
+    out[5] = g_ac.peak();
     out[6] = g_ac.held();
 }
 
@@ -436,11 +413,6 @@ extern "C" void pw_apc_calls_read_time_keys(const PwApcCalls* e, uint64_t* keys)
 }
 
 namespace {
-
-void reset_stats(AcCtx& cx) {
-    cx.peak = 0;
-    cx.stat_candidates = cx.stat_valid = cx.stat_components = cx.stat_longest = cx.stat_long = 0;
-}
 
 std::unique_ptr<PwApcCalls> empty_result(size_t n_apcs, u64 n_states) {
     auto result = std::make_unique<PwApcCalls>();
@@ -491,10 +463,9 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
         ScopedKernelTimer timer("apc_calls_candidates");
         PW_TRY(cx.count.ensure(n_states * 4));
         PW_TRY(cx.off.ensure(n_states * 4));
-        cx.note();
         hipLaunchKernelGGL(apc_calls_match_kernel, dim3(div_up(n_states, kBlock)), block, 0, st, T, cx.count.as<uint32_t>(), d_counters);
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::exclusive_scan(t, b, cx.count.as<uint32_t>(), cx.off.as<uint32_t>(), 0u, (size_t)n_states, rocprim::plus<uint32_t>(), st);
         }));
         uint32_t last[2] = {0, 0};
@@ -505,7 +476,6 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
         cx.count.release();
         if (n_cand) {
             PW_TRY(cx.cand.ensure(n_cand * 8));
-            cx.note();
             hipLaunchKernelGGL(apc_calls_emit_kernel, dim3(div_up(n_states, kBlock)), block, 0, st, T, (const uint32_t*)cx.off.p, cx.cand.as<u64>());
             PW_HIP_TRY(hipGetLastError());
         }
@@ -519,10 +489,9 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
         PW_TRY(cx.fail.ensure(n_cand * 4));
         PW_TRY(cx.done.ensure(n_cand));
         PW_TRY(cx.V.ensure(n_cand * 8));
-        cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.fail.p, 0xff, n_cand * 4, st));
         const u64* d_cand = cx.cand.as<u64>();
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::exclusive_scan(t, b, rocprim::make_transform_iterator(d_cand, ChunksOf{T.apcs}), cx.item_off.as<u64>(), (u64)0, (size_t)n_cand,
                                            rocprim::plus<u64>(), st);
         }));
@@ -537,13 +506,13 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
         hipLaunchKernelGGL(apc_calls_classify_kernel, dim3(div_up(n_cand, kBlock)), block, 0, st, T, d_cand, (const uint32_t*)cx.fail.p, n_cand, cx.done.as<uint8_t>(),
                            d_counters);
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::select(t, b, d_cand, cx.done.as<uint8_t>(), cx.V.as<u64>(), d_n, (size_t)n_cand, st); }));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::select(t, b, d_cand, cx.done.as<uint8_t>(), cx.V.as<u64>(), d_n, (size_t)n_cand, st); }));
         uint32_t nv = 0;
         PW_HIP_TRY(hipMemcpyAsync(&nv, d_n, 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
         n_valid = nv;
     }
-    for (DeviceBuf* b : {&cx.off, &cx.cand, &cx.item_off, &cx.fail, &cx.done}) b->release();
+    for (Scratch::Buf* b : {&cx.off, &cx.cand, &cx.item_off, &cx.fail, &cx.done}) b->release();
     cx.stat_valid = n_valid;
     std::vector<u64> calls;
     if (n_valid) {
@@ -557,15 +526,14 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
             PW_TRY(cx.mx.ensure(n_valid * 4));
             PW_TRY(cx.cflag.ensure(n_valid));
             PW_TRY(cx.cfirst.ensure((n_valid + 1) * 4));
-            cx.note();
             hipLaunchKernelGGL(apc_calls_ends_kernel, grid, block, 0, st, V, T.apcs, n_valid, cx.end.as<uint32_t>());
             PW_HIP_TRY(hipGetLastError());
-            PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+            PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                 return rocprim::inclusive_scan(t, b, cx.end.as<uint32_t>(), cx.mx.as<uint32_t>(), (size_t)n_valid, rocprim::maximum<uint32_t>(), st);
             }));
             hipLaunchKernelGGL(apc_calls_cut_kernel, grid, block, 0, st, V, (const uint32_t*)cx.mx.p, n_valid, cx.cflag.as<uint8_t>());
             PW_HIP_TRY(hipGetLastError());
-            PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+            PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                 return rocprim::select(t, b, rocprim::counting_iterator<uint32_t>(0), cx.cflag.as<uint8_t>(), cx.cfirst.as<uint32_t>(), d_n, (size_t)n_valid, st);
             }));
             uint32_t nc = 0;
@@ -575,7 +543,7 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
             const uint32_t total = (uint32_t)n_valid;
             PW_HIP_TRY(hipMemcpyAsync(cx.cfirst.as<uint32_t>() + n_comp, &total, 4, hipMemcpyHostToDevice, st));
             PW_HIP_TRY(hipStreamSynchronize(st));  // (total is a local)
-            for (DeviceBuf* b : {&cx.end, &cx.mx, &cx.cflag}) b->release();
+            for (Scratch::Buf* b : {&cx.end, &cx.mx, &cx.cflag}) b->release();
         }
         cx.stat_components = n_comp;
         const u64 threshold = cx.long_threshold ? cx.long_threshold : kLongDefault, longs_cap = n_valid / (threshold + 1) + 1;
@@ -585,7 +553,6 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
             ScopedKernelTimer timer("apc_calls_fold");
             PW_TRY(cx.disc.ensure(n_valid));
             PW_TRY(cx.longs.ensure(longs_cap * 4));
-            cx.note();
             PW_HIP_TRY(hipMemsetAsync(cx.disc.p, 0, n_valid, st));
             hipLaunchKernelGGL(apc_calls_fold_kernel, dim3(div_up(n_comp, kBlock)), block, 0, st, V, T.apcs, (const uint32_t*)cx.cfirst.p, n_comp, threshold,
                                cx.disc.as<uint8_t>(), cx.longs.as<uint32_t>(), longs_cap, d_fold);
@@ -607,10 +574,9 @@ int select_calls(AcCtx& cx, const uint32_t* d_pcs, const uint32_t* d_regs, u64 n
             ScopedKernelTimer timer("apc_calls_readout");
             PW_TRY(cx.keep.ensure(n_valid));
             PW_TRY(cx.calls.ensure(n_valid * 8));
-            cx.note();
             hipLaunchKernelGGL(apc_calls_tally_kernel, grid, block, 0, st, V, (const uint8_t*)cx.disc.p, n_valid, cx.keep.as<uint8_t>(), d_counters);
             PW_HIP_TRY(hipGetLastError());
-            PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::select(t, b, V, cx.keep.as<uint8_t>(), cx.calls.as<u64>(), d_n, (size_t)n_valid, st); }));
+            PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::select(t, b, V, cx.keep.as<uint8_t>(), cx.calls.as<u64>(), d_n, (size_t)n_valid, st); }));
             uint32_t n_calls = 0;
             PW_HIP_TRY(hipMemcpyAsync(&n_calls, d_n, 4, hipMemcpyDeviceToHost, st));
             PW_HIP_TRY(hipStreamSynchronize(st));
@@ -643,18 +609,13 @@ extern "C" int pw_apc_calls_from_states(const uint32_t* d_pcs, const uint32_t* d
         !check_tables(apcs, n_apcs, constraints, n_constraints, n_regs, limb_bits, h) || n_states * h.max_share >= ((uint64_t)1 << 32))
         return -1;
     AcCtx& cx = g_ac;
-    reset_stats(cx);
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
+    const ScratchCall call(cx, out, status, info);
     auto result = empty_result(n_apcs, n_states);
     if (!n_states) {
         *out = result.release();
         return 0;
     }
-    (void)hipGetLastError();
-    const AcReleased released{cx};
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const size_t bound = call.bound(scratch_bytes);
     const int rc = select_calls(cx, d_pcs, d_regs, n_states, limb_bits, h, bound, 0, *result, status, info);
     if (!rc && !*status) *out = result.release();
     return rc;
@@ -673,14 +634,9 @@ extern "C" int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t
     if (rows < 0 || ((u64)rows + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32)) return -1;
     const u64 M = (u64)rows;
     AcCtx& cx = g_ac;
-    reset_stats(cx);
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
-    (void)hipGetLastError();
-    const AcReleased released{cx};
+    const ScratchCall call(cx, out, status, info);
     hipStream_t st = stream();
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; the sorted keys and the states stay through the selection
     const size_t index_need = 64 + (size_t)M * 32 + (M ? time_index::sort_pairs_temp(M) : 0), extra = 64 + (size_t)M * 8 + (size_t)(M + 1) * 4;
     {
@@ -695,33 +651,22 @@ extern "C" int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t
     if (M) {
         std::vector<Part> parts;
         PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
-        std::vector<u64> g0;
-        u64 g = 0;  // the parts' rows numbered through
-        for (const Part& part : parts) {
-            g0.push_back(g);
-            g += (u64)1 << airs[part.air].log_height;
-        }
-        PW_TRY(cx.icount.ensure(64));
-        const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
-        PW_HIP_TRY(hipMemcpyAsync(cx.icount.p, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
         u64 counters[8];
-        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, g0, M, cx.icount.as<u64>(),
-                                              time_index::Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
-                                              time_index::Names{"apc_calls_index_kernel", "apc_calls_sort_time", "apc_calls_time_kernel"}, [&] { cx.note(); }, counters,
-                                              status, info));
+        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
+                                              time_index::Names{"apc_calls_index_kernel", "apc_calls_sort_time", "apc_calls_time_kernel"}, counters, status, info));
         if (*status) return (int)hipGetLastError();
         N = counters[0];
     }
     // the states: the N pcs in time order and the pc after the last row
     PW_TRY(cx.states.ensure((N + 1) * 4));
-    cx.note();
-    if (N) PW_HIP_TRY(hipMemcpyAsync(cx.states.p, cx.pc_t.p, N * 4, hipMemcpyDeviceToDevice, st));
+    if (N) PW_HIP_TRY(hipMemcpyAsync(cx.states.p, cx.index.pc_t.p, N * 4, hipMemcpyDeviceToDevice, st));
     PW_HIP_TRY(hipMemcpyAsync(cx.states.as<uint32_t>() + N, &final_pc, 4, hipMemcpyHostToDevice, st));
     auto result = empty_result(n_apcs, N + 1);
     result->time_keys.resize(N);
-    if (N) PW_HIP_TRY(hipMemcpyAsync(result->time_keys.data(), cx.tkey_s.p, N * 8, hipMemcpyDeviceToHost, st));
+    if (N) PW_HIP_TRY(hipMemcpyAsync(result->time_keys.data(), cx.index.tkey_s.p, N * 8, hipMemcpyDeviceToHost, st));
     PW_HIP_TRY(hipStreamSynchronize(st));
-    for (DeviceBuf* b : {&cx.tkey, &cx.tkey_s, &cx.idx, &cx.idx_s, &cx.pcs, &cx.pc_t, &cx.temp, &cx.icount}) b->release();
+    cx.index.release();
+    cx.temp.release();
     const int rc = select_calls(cx, (const uint32_t*)cx.states.p, nullptr, N + 1, 8, h, bound, 0, *result, status, info);
     if (!rc && !*status) *out = result.release();
     return rc;
@@ -755,13 +700,8 @@ extern "C" int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, cons
         for (OpDev* o : {&q.l, &q.r})
             if (o->kind == 2u) o->reg = (uint32_t)(std::lower_bound(regs.begin(), regs.end(), o->reg) - regs.begin());
     AcCtx& cx = g_ac;
-    reset_stats(cx);
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
-    (void)hipGetLastError();
-    const AcReleased released{cx};
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const ScratchCall call(cx, out, status, info);
+    const size_t bound = call.bound(scratch_bytes);
     // the states, the table and the time keys stay through the selection
     const size_t extra = 64 + (size_t)(M + 1) * 4 * (regs.size() + 1) + (size_t)M * 8;
     {
@@ -773,7 +713,7 @@ extern "C" int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, cons
         }
     }
     u64 N = 0;
-    PW_TRY(rs::states_from_traces(a, regs, initial_regs ? initial.data() : nullptr, M, slots, cx.stage, cx.states, cx.regtab, cx.tkeys, [&] { cx.note(); }, &N, status, info));
+    PW_TRY(rs::states_from_traces(a, regs, initial_regs ? initial.data() : nullptr, M, slots, cx.stage, cx.states, cx.regtab, cx.tkeys, &N, status, info));
     if (*status) return (int)hipGetLastError();
     auto result = empty_result(n_apcs, N + 1);
     result->time_keys.resize(N);

@@ -250,34 +250,17 @@ __global__ __launch_bounds__(kBlock) void apc_sources_residual_kernel(PlaceTable
     lists[list_base[part] + (off[g] - starts[part])] = (uint32_t)(g - t.part_g0[part]);
 }
 
-struct AsCtx {
-    DeviceBuf icount, tkey, tkey_s, idx, idx_s, pcs, pc_t, temp, small, small2, small3, lists, rlists, covered, off, jobs;
-    DeviceBuf* all[16] = {&icount, &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &temp, &small, &small2, &small3, &lists, &rlists, &covered, &off, &jobs};
-    size_t peak = 0, extra = 0;  // extra: the matrices of the handle under construction
+struct AsCtx : Scratch {  // (its `extra`: the matrices of the handle under construction)
+    time_index::Stage index{*this};
+    Buf temp{*this}, small{*this}, small2{*this}, small3{*this}, lists{*this}, rlists{*this}, covered{*this}, off{*this}, jobs{*this};
     uint64_t stat_covered = 0, stat_source_bytes = 0, stat_residual_bytes = 0, stat_jobs = 0, stat_tiles16 = 0, stat_tiles4 = 0;
-    size_t held() const {
-        size_t s = 0;
-        for (DeviceBuf* b : all) s += b->bytes;
-        return s;
-    }
-    void note() { peak = std::max(peak, held() + extra); }
-    void reset() {
-        peak = extra = 0;
-        stat_covered = stat_source_bytes = stat_residual_bytes = stat_jobs = stat_tiles16 = stat_tiles4 = 0;
-    }
+    void reset_stats() override { stat_covered = stat_source_bytes = stat_residual_bytes = stat_jobs = stat_tiles16 = stat_tiles4 = 0; }
 };
 thread_local AsCtx g_as;
 struct TracegenStats {
     uint64_t jobs = 0, items = 0, tiles16 = 0, tiles4 = 0, bytes_written = 0;
 };
 thread_local TracegenStats g_tracegen;
-struct AsReleased {
-    AsCtx& cx;
-    ~AsReleased() {
-        for (DeviceBuf* b : cx.all) b->release();
-        cx.extra = 0;
-    }
-};
 
 bool power_of_two(u64 x) { return x && !(x & (x - 1)); }
 u64 next_power_of_two(u64 x) {
@@ -316,7 +299,6 @@ int gather(AsCtx& cx, const PwGatherJob* jobs, size_t n_jobs) {
     }
     ScopedKernelTimer timer("apc_sources_gather");
     PW_TRY(cx.jobs.ensure(image.size()));
-    cx.note();
     PW_HIP_TRY(hipMemcpyAsync(cx.jobs.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
     const u64 per_launch = (u64)1 << 30;
     for (u64 base = 0; base < tiles; base += per_launch)
@@ -332,23 +314,6 @@ int gather(AsCtx& cx, const PwGatherJob* jobs, size_t n_jobs) {
     return 0;
 }
 
-template <class F>
-int with_temp(AsCtx& cx, F f) {
-    size_t bytes = 0;
-    PW_HIP_TRY(f(nullptr, bytes));
-    PW_TRY(cx.temp.ensure(std::max<size_t>(bytes, 16)));
-    cx.note();
-    PW_HIP_TRY(f(cx.temp.p, bytes));
-    return 0;
-}
-
-size_t scan_temp(size_t n) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, rocprim::make_transform_iterator((const uint8_t*)nullptr, AsU32{}), (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(),
-                                  stream());
-    return std::max<size_t>(bytes, 16);
-}
-
 // a host image of device tables, every piece 16-byte aligned
 struct Image {
     std::vector<char> bytes;
@@ -359,7 +324,7 @@ struct Image {
         if (!v.empty()) memcpy(bytes.data() + at, v.data(), v.size() * sizeof(T));
         return at;
     }
-    int upload(DeviceBuf& b, hipStream_t st) {
+    int upload(Scratch::Buf& b, hipStream_t st) {
         bytes.resize(bytes.size() + 16);
         PW_TRY(b.ensure(bytes.size()));
         PW_HIP_TRY(hipMemcpyAsync(b.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
@@ -466,7 +431,7 @@ extern "C" void pw_apc_sources_last_stats(uint64_t* out) {
     out[3] = g_as.stat_jobs;
     out[4] = g_as.stat_tiles16;
     out[5] = g_as.stat_tiles4;
-    out[6] = g_as.peak;
+    out[6] = g_as.peak();
     out[7] = g_as.held();
 }
 
@@ -543,12 +508,11 @@ extern "C" int pw_apc_sources_tracegen(const PwApcSources* e, const PwApcTraceJo
 
     // ---- one launch (more than 2^30 tiles: one launch per 2^30); the call returns after the stream has run it ----
     AsCtx& cx = g_as;
-    (void)hipGetLastError();
-    const AsReleased released{cx};
+    const ScratchCall call(cx, ScratchCall::kContinues);
     hipStream_t st = stream();
     Image im;
     const size_t at_counters = im.put(std::vector<u64>(8, 0)), at_items = im.put(items), at_cells = im.put(cells);
-    if (im.bytes.size() + 16 > default_bound(cx.held())) return (int)hipErrorOutOfMemory;
+    if (im.bytes.size() + 16 > call.bound(0)) return (int)hipErrorOutOfMemory;
     ScopedKernelTimer timer("apc_sources_tracegen");
     PW_TRY(im.upload(cx.jobs, st));
     char* tab = cx.jobs.as<char>();
@@ -569,10 +533,7 @@ extern "C" int pw_apc_sources_tracegen(const PwApcSources* e, const PwApcTraceJo
 extern "C" int pw_trace_gather_rows(const PwGatherJob* jobs, size_t n_jobs) {
     if (!jobs_well_formed(jobs, n_jobs)) return -1;
     AsCtx& cx = g_as;
-    cx.reset();
-    if (!n_jobs) return 0;
-    (void)hipGetLastError();
-    const AsReleased released{cx};
+    const ScratchCall call(cx);
     return gather(cx, jobs, n_jobs);
 }
 
@@ -596,10 +557,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
     const u64 M = (u64)rows, min_h = (u64)1 << min_log_height;
     const bool direct = (flags & PW_APC_SOURCES_DIRECT) != 0;
     AsCtx& cx = g_as;
-    cx.reset();
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
+    const ScratchCall call(cx, out, status, info);
 
     // ---- the calls, per APC (host) ----
     std::vector<u64> cov_off(n_calls + 1, 0), first_from(n_apcs, 0), calls_of(n_apcs, 0);
@@ -634,9 +592,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
     for (size_t k = 0; k < n_parts; ++k) g0[k + 1] = g0[k] + ((u64)1 << airs[part_air[k]].log_height);
 
     // ---- status 2: what is known before a row is read ----
-    (void)hipGetLastError();
-    const AsReleased released{cx};
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const size_t bound = call.bound(scratch_bytes);
     {
         // per APC with n calls of L instructions: its rows in an AIR are distinct rows of that AIR, and over all AIRs n * L rows
         // (a power of two at most doubles them); the residual of an AIR is at most the AIR. Direct mode has no source matrices, and its
@@ -668,7 +624,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         const size_t n_lists = (n_apcs + 1) * n_parts;
         const size_t tables = 4096 + n_calls * 32 + n_apcs * 32 + n_instr * 8 + n_lists * 32 + job_table_bytes(n_lists) + 256 * (n_lists + 2);
         const size_t index_need = 64 + (size_t)M * 32 + (M ? time_index::sort_pairs_temp(M) : 0);
-        const size_t place_need = 64 + (size_t)M * 17 + (M ? scan_temp(M) : 0);
+        const size_t place_need = 64 + (size_t)M * 17 + (M ? time_index::scan_temp(rocprim::make_transform_iterator((const uint8_t*)nullptr, AsU32{}), M) : 0);
         const size_t need = ((size_t)1 << 20) + tables + std::max(index_need, place_need) + out_bytes + (list_rows + 4 * n_lists) * 4;
         if (bound < need) {
             *status = 2;
@@ -699,18 +655,14 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         std::vector<Part> parts;
         PW_TRY(collect_parts(airs, n_airs, bridge_bus, parts, nullptr));
         if (parts.size() != n_parts) return (int)hipErrorInvalidValue;  // (cannot happen: the same AIRs by the same rule)
-        PW_TRY(cx.icount.ensure(64));
-        const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
-        PW_HIP_TRY(hipMemcpyAsync(cx.icount.p, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
         u64 counters[8];
         const std::vector<u64> part_first(g0.begin(), g0.end() - 1);
-        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, part_first, M, cx.icount.as<u64>(),
-                                              time_index::Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
-                                              time_index::Names{"apc_sources_index_kernel", "apc_sources_sort_time", "apc_sources_time_kernel"}, [&] { cx.note(); }, counters,
-                                              status, info));
+        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, &part_first, M, cx.index, nullptr, cx.temp,
+                                              time_index::Names{"apc_sources_index_kernel", "apc_sources_sort_time", "apc_sources_time_kernel"}, counters, status, info));
         if (*status) return (int)hipGetLastError();
         N = counters[0];
-        for (DeviceBuf* b : {&cx.tkey_s, &cx.idx, &cx.pcs, &cx.pc_t, &cx.temp, &cx.icount}) b->release();
+        cx.index.release_except({&cx.index.tkey, &cx.index.idx_s});  // the keys say which rows are active, the order places the calls
+        cx.temp.release();
     }
     R.positions = N;
     for (size_t j = 0; j < n_calls; ++j)
@@ -738,9 +690,8 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
                      at_apc = im.put(std::vector<uint32_t>(call_apc_ids, call_apc_ids + n_calls)), at_rank = im.put(rank), at_first = im.put(first_from),
                      at_ioff = im.put(ioff), at_g0 = im.put(g0), at_air = im.put(air_of);
         PW_TRY(im.upload(cx.small, st));
-        cx.note();
         char* sm = cx.small.as<char>();
-        T = PlaceTables{(const uint32_t*)cx.idx_s.p, (const u64*)(sm + at_cov), (const u64*)(sm + at_from), (const uint32_t*)(sm + at_apc), (const uint32_t*)(sm + at_rank),
+        T = PlaceTables{(const uint32_t*)cx.index.idx_s.p, (const u64*)(sm + at_cov), (const u64*)(sm + at_from), (const uint32_t*)(sm + at_apc), (const uint32_t*)(sm + at_rank),
                         (const u64*)(sm + at_first), (const uint32_t*)(sm + at_ioff), (const u64*)(sm + at_g0), (uint32_t)n_calls, (uint32_t)n_parts};
         uint32_t* d_air_of = (uint32_t*)(sm + at_air);
         if (n_covered) {
@@ -788,15 +739,13 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         DeviceBuf& lists = direct ? R.idx : cx.lists;  // direct: the handle keeps them
         PW_TRY(lists.ensure(std::max<size_t>(list_total * 4, 16)));
         if (src_total) PW_TRY(R.src.ensure(src_total));
-        cx.extra = R.src.bytes + R.idx.bytes;
-        cx.note();
+        cx.set_extra(R.src.bytes + R.idx.bytes);
         PW_HIP_TRY(hipMemsetAsync(cx.covered.p, 0, M, st));
         PW_HIP_TRY(hipMemsetAsync(lists.p, 0xff, std::max<size_t>(list_total * 4, 16), st));
         if (n_covered) {
             Image im2;
             const size_t at_occ = im2.put(occ), at_base = im2.put(list_base), at_rbs = im2.put(rbs);
             PW_TRY(im2.upload(cx.small2, st));
-            cx.note();
             char* s2 = cx.small2.as<char>();
             hipLaunchKernelGGL(apc_sources_place_kernel, dim3(div_up(n_covered, kBlock)), block, 0, st, T, n_covered, (const uint32_t*)d_air_of, (const uint32_t*)(s2 + at_occ),
                                (const u64*)(s2 + at_base), (const uint32_t*)(s2 + at_rbs), lists.as<uint32_t>(), cx.covered.as<uint8_t>());
@@ -811,11 +760,10 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         ScopedKernelTimer timer("apc_sources_residual");
         PW_TRY(cx.off.ensure(M * 4));
         PW_TRY(cx.small3.ensure((n_parts + 1) * 4 + n_parts * 8 + 64));
-        cx.note();
         uint8_t* keep = cx.covered.as<uint8_t>();
-        hipLaunchKernelGGL(apc_sources_keep_kernel, dim3(div_up(M, kBlock)), block, 0, st, (const u64*)cx.tkey.p, keep, M);
+        hipLaunchKernelGGL(apc_sources_keep_kernel, dim3(div_up(M, kBlock)), block, 0, st, (const u64*)cx.index.tkey.p, keep, M);
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::exclusive_scan(t, b, rocprim::make_transform_iterator((const uint8_t*)keep, AsU32{}), cx.off.as<uint32_t>(), 0u, (size_t)M,
                                            rocprim::plus<uint32_t>(), st);
         }));
@@ -827,7 +775,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         std::vector<uint32_t> starts(n_parts + 1, 0);
         PW_HIP_TRY(hipMemcpyAsync(starts.data(), d_starts, (n_parts + 1) * 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
-        cx.tkey.release();
+        cx.index.tkey.release();
         size_t res_total = 0, rlist_total = 0;
         for (size_t k = 0; k < n_parts; ++k) {
             const size_t air = part_air[k];
@@ -844,8 +792,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         }
         PW_TRY(cx.rlists.ensure(std::max<size_t>(rlist_total * 4, 16)));
         PW_TRY(R.res.ensure(std::max<size_t>(res_total, 16)));
-        cx.extra = R.src.bytes + R.idx.bytes + R.res.bytes;
-        cx.note();
+        cx.set_extra(R.src.bytes + R.idx.bytes + R.res.bytes);
         PW_HIP_TRY(hipMemsetAsync(cx.rlists.p, 0xff, std::max<size_t>(rlist_total * 4, 16), st));
         PW_HIP_TRY(hipMemcpyAsync(d_rbase, rlist_base.data(), n_parts * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(apc_sources_residual_kernel, dim3(div_up(M, kBlock)), block, 0, st, T, (const uint8_t*)keep, (const uint32_t*)cx.off.p, (const uint32_t*)d_starts,
@@ -853,7 +800,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         PW_HIP_TRY(hipGetLastError());
         PW_HIP_TRY(hipStreamSynchronize(st));  // (rlist_base is a local)
     }
-    for (DeviceBuf* b : {&cx.covered, &cx.off, &cx.temp, &cx.idx_s, &cx.small, &cx.small2, &cx.small3}) b->release();
+    for (Scratch::Buf* b : {&cx.covered, &cx.off, &cx.temp, &cx.index.idx_s, &cx.small, &cx.small2, &cx.small3}) b->release();
 
     // ---- gather: every source and every residual in one launch ----
     std::vector<PwGatherJob> jobs;

@@ -7,7 +7,7 @@
 // The table itself — the claim loop, the load rule, the sizing and the growth from a small first table — is bus_shared.hpp's; what is
 // here is the table's payload (sum, witness, count).
 // One lane per row, interactions evaluated by eval_span / DenominatorAcc exactly as logup_perm_kernel evaluates them.
-#include "bus_shared.hpp"
+#include "scratch.hpp"
 #include "bus_witness_args.hpp"
 
 namespace pw {
@@ -137,19 +137,13 @@ __global__ __launch_bounds__(kBlock) void bus_compact_kernel(Table t, Unbalanced
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-struct BusCtx {
-    DeviceBuf small;               // accumulators | counters | class loads | challenge powers | bus runs | AIR table: stays
-    DeviceBuf table, list, args;   // released before the call returns, on every path (Released below)
-    size_t peak = 0;
+struct BusCtx : Scratch {
+    Buf small{*this, kStays};  // accumulators | counters | class loads | challenge powers | bus runs | AIR table
+    Buf table{*this}, list{*this}, args{*this};
     uint64_t stat_slots = 0, stat_occupied = 0, stat_inserted = 0, stat_tables = 0;
-    size_t held() const { return small.bytes + table.bytes + list.bytes + args.bytes; }
-    void note() { peak = std::max(peak, held()); }
+    void reset_stats() override { stat_slots = stat_occupied = stat_inserted = stat_tables = 0; }
 };
 thread_local BusCtx g_bus;
-struct Released {
-    BusCtx& cx;
-    ~Released() { cx.table.release(); cx.list.release(); cx.args.release(); }
-};
 
 }  // namespace
 
@@ -158,7 +152,7 @@ struct Released {
 using namespace pw;
 
 extern "C" size_t pw_bus_check_scratch_bytes(void) { return g_bus.held(); }
-extern "C" size_t pw_bus_check_peak_bytes(void) { return g_bus.peak; }
+extern "C" size_t pw_bus_check_peak_bytes(void) { return g_bus.peak(); }
 // for tools/bench_bus_check.py, deliberately not in the header: slots of the largest tally table kept, the most slots occupied in one
 // table, the triples inserted over all tallied buses, the tables tallied into (attempts that overflowed included) — of the calling
 // thread's last check (each NULL = skip)
@@ -192,11 +186,9 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     if (n_summaries) *n_summaries = n_sel;
     if (n_tuples) *n_tuples = 0;
     BusCtx& cx = g_bus;
-    cx.peak = 0;
-    cx.stat_slots = cx.stat_occupied = cx.stat_inserted = cx.stat_tables = 0;
+    const ScratchCall call(cx);
     if (!n_sel) return 0;
 
-    (void)hipGetLastError();
     // ---- the AIRs that take part, their bus runs, the challenge powers
     struct BusPart { size_t air; std::vector<BusSeg> segs; size_t seg_off; const uint32_t* vals; };
     std::vector<BusPart> parts;
@@ -226,9 +218,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
     // small: accumulators (5 u64 per bus) | the walker's head (counters: in use | unbalanced | written | unused) | powers | bus runs | AIR table
     const size_t off_head = n_sel * 5 * 8, off_pow = off_head + sizeof(WalkHead), off_seg = off_pow + blpow.size() * sizeof(Ext),
                  off_air = (off_seg + all_segs.size() * sizeof(BusSeg) + 15) & ~(size_t)15, small_bytes = off_air + n_airs * sizeof(AirDev);
-    const Released released{cx};
     PW_TRY(cx.small.ensure(small_bytes));
-    cx.note();
     char* base = cx.small.as<char>();
     u64* d_acc = (u64*)base;
     WalkHead* d_head = (WalkHead*)(base + off_head);
@@ -282,7 +272,7 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
         if ((zero_sum[b] && !(flags & PW_BUS_CHECK_TALLY_ALL)) || !sums[b].n_active) continue;
         // the table's bound: the caller's, or by default half of the device's room (asked once per call)
         if (!table_bytes && !room_known) {
-            room = default_bound(cx.held());
+            room = call.bound(0);
             room_known = true;
         }
         uint32_t stride = 1;
@@ -299,7 +289,6 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
             cx.table, d_head, sums[b].n_active, kSlotBytes, table_bytes ? table_bytes : room, kStartSlots, "bus_table_clear",
             [&](u64* tb, const TableRule& rule) -> int {
                 const u64 slots = rule.mask + 1;
-                cx.note();
                 T = Table{TableView{rule, tb, tb + slots}, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots};
                 PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 3 * slots * 8, st));
                 PW_HIP_TRY(hipMemsetAsync(tb + 3 * slots, 0, 2 * slots * 8, st));
@@ -334,7 +323,6 @@ extern "C" int pw_check_segment_buses(const PwSegmentAir* airs, size_t n_airs, c
         // the unbalanced slots, their tuple words at the witness rows, sorted on the host
         PW_TRY(cx.list.ensure(n_unb * sizeof(Unbalanced)));
         PW_TRY(cx.args.ensure(n_unb * stride * 4));
-        cx.note();
         PW_HIP_TRY(hipMemsetAsync(cx.args.p, 0, n_unb * stride * 4, st));
         hipLaunchKernelGGL(bus_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.list.as<Unbalanced>(), n_unb, d_counts);
         hipLaunchKernelGGL(witness_args_kernel, dim3(div_up(n_unb, kWaves)), dim3(kBlock), 0, st, (const u64*)cx.list.p, (uint32_t)(sizeof(Unbalanced) / 8), n_unb,

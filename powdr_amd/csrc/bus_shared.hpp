@@ -264,12 +264,13 @@ struct Grown {
 // times as large, up to the largest: lookup buses repeat a few hundred thousand tuples thousands of times, so the triples say little
 // about the table a walk needs, and an overflowing walk stops early (every lane leaves once the overflow word is set). What comes
 // out depends on the LAST table alone. A table the device cannot give is a table too large: try half, never an error.
+//   table            the walker's buffer, a Scratch::Buf (scratch.hpp): every table it becomes is noted in the context's peak
 //   clear(tb, rule)  the table at tb, of rule.mask + 1 slots, is the caller's from here on: bind its columns and issue their
 //                    0xFF / 0 patterns (timed as `clear_timer` together with the clearing of the head)
 //   walk()           the claiming kernels
 //   count()          the counting launch of the caller's compact kernel, into d_head->c.counts
-template <class Clear, class Walk, class Count>
-inline int grow_table(DeviceBuf& table, WalkHead* d_head, u64 triples, size_t slot_bytes, size_t bound, u64 first_slots, const char* clear_timer, Clear clear,
+template <class Table, class Clear, class Walk, class Count>
+inline int grow_table(Table& table, WalkHead* d_head, u64 triples, size_t slot_bytes, size_t bound, u64 first_slots, const char* clear_timer, Clear clear,
                       Walk walk, Count count, Grown* g) {
     *g = Grown{};
     u64 max_slots = 1024;
@@ -289,7 +290,7 @@ inline int grow_table(DeviceBuf& table, WalkHead* d_head, u64 triples, size_t sl
         if (!table.p) break;
         {
             ScopedKernelTimer timer(clear_timer);
-            PW_TRY(clear(table.as<u64>(), table_rule(slots, d_head)));
+            PW_TRY(clear(table.template as<u64>(), table_rule(slots, d_head)));
             PW_HIP_TRY(hipMemsetAsync(d_head, 0, sizeof(WalkHead), st));
         }
         walk();

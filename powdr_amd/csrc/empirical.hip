@@ -220,29 +220,16 @@ __global__ __launch_bounds__(kBlock) void empirical_verify_kernel(const VPair* _
     if (differ) mismatch[p] = 1u;
 }
 
-struct EmpCtx {
-    DeviceBuf small;
-    DeviceBuf tkey, tkey_s, idx, idx_s, pcs, pc_t, pc_p, idx_p, loc, uniq, cnt, start, run_of, run_air, range_off, ranges, fps, keys, sorted, temp, pairs, items,
-        mismatch;
-    size_t peak = 0;
+struct EmpCtx : Scratch {
+    Buf small{*this, kStays};  // the index stage's counters (the kernels here count in them too) | AIR table | part table | block table
+    time_index::Stage index{*this};
+    Buf pc_p{*this}, idx_p{*this}, loc{*this}, uniq{*this}, cnt{*this}, start{*this}, run_of{*this}, run_air{*this}, range_off{*this}, ranges{*this}, fps{*this},
+        keys{*this}, sorted{*this}, temp{*this}, pairs{*this}, items{*this}, mismatch{*this};
     uint64_t mask = 0;  // 0: the full width
     uint64_t stat_panels = 0, stat_seeds = 0, stat_rows = 0, stat_verified = 0;
-    DeviceBuf* all[24] = {&tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &pc_p, &idx_p, &loc, &uniq, &cnt, &start, &run_of, &run_air, &range_off, &ranges, &fps,
-                          &keys, &sorted, &temp, &pairs, &items, &mismatch, nullptr};
-    size_t held() const {
-        size_t s = small.bytes;
-        for (DeviceBuf* b : all) if (b) s += b->bytes;
-        return s;
-    }
-    void note() { peak = std::max(peak, held()); }
+    void reset_stats() override { stat_panels = stat_seeds = stat_rows = stat_verified = 0; }
 };
 thread_local EmpCtx g_emp;
-struct EmpReleased {
-    EmpCtx& cx;
-    ~EmpReleased() {
-        for (DeviceBuf* b : cx.all) if (b) b->release();
-    }
-};
 
 size_t sort_keys_temp(size_t n, unsigned end_bit) {
     size_t bytes = 0;
@@ -274,7 +261,7 @@ extern "C" void pw_empirical_last_stats(uint64_t* out) {
     out[1] = g_emp.stat_seeds;
     out[2] = g_emp.stat_rows;
     out[3] = g_emp.stat_verified;
-    out[4] = g_emp.peak;
+    out[4] = g_emp.peak();
     out[5] = g_emp.held();
 }
 
@@ -321,11 +308,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     const u64 M = (u64)rows;
     if (M >= ((u64)1 << 32)) return -1;  // row numbers and run positions are 32-bit words
     EmpCtx& cx = g_emp;
-    cx.peak = 0;
-    cx.stat_panels = cx.stat_seeds = cx.stat_rows = cx.stat_verified = 0;
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
+    const ScratchCall call(cx, out, status, info);
     auto result = std::make_unique<PwEmpirical>();
     result->range_off.push_back(0);
     result->class_off.push_back(0);
@@ -334,8 +317,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
         *out = result.release();
         return 0;
     }
-    (void)hipGetLastError();
-    const EmpReleased released{cx};
     hipStream_t st = stream();
 
     std::vector<Part> parts;
@@ -365,7 +346,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     const PwBasicBlock* d_blocks = (const PwBasicBlock*)(base + off_blocks);
 
     // the bound: the caller's, or half of what the device has room for
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; one column of a panel 16 bytes per active row (at most M)
     const size_t index_need = small_bytes + (size_t)M * 32 + sort_pairs_temp(M);
     auto panel_need = [&](u64 N, uint32_t C, u64 n_runs, u64 n_cells) {
@@ -379,8 +360,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
         return 0;
     }
 
-    const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
-    PW_HIP_TRY(hipMemcpyAsync(d_counters, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
     PW_HIP_TRY(hipMemcpyAsync((void*)d_airs, h_airs.data(), n_airs * sizeof(EAir), hipMemcpyHostToDevice, st));
     PW_HIP_TRY(hipMemcpyAsync((void*)d_parts, h_parts.data(), h_parts.size() * sizeof(EPart), hipMemcpyHostToDevice, st));
     if (n_blocks) PW_HIP_TRY(hipMemcpyAsync((void*)d_blocks, blocks, n_blocks * sizeof(PwBasicBlock), hipMemcpyHostToDevice, st));
@@ -390,8 +369,8 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     {
         std::vector<u64> g0;
         for (const EPart& part : h_parts) g0.push_back(part.g0);
-        PW_TRY(rows_in_time_order(airs, segment_of_air, parts, g0, M, d_counters, Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
-                                  Names{"empirical_index_kernel", "empirical_sort_time", "empirical_structure_kernel"}, [&] { cx.note(); }, counters, status, info));
+        PW_TRY(rows_in_time_order(airs, segment_of_air, parts, &g0, M, cx.index, d_counters, cx.temp,
+                                  Names{"empirical_index_kernel", "empirical_sort_time", "empirical_structure_kernel"}, counters, status, info));
         if (*status) return (int)hipGetLastError();
     }
     const u64 N = counters[0];
@@ -402,7 +381,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     }
     {
         ScopedKernelTimer timer("empirical_structure_kernel");
-        hipLaunchKernelGGL(empirical_structure_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.tkey_s.p, (const uint32_t*)cx.pc_t.p, N, d_blocks,
+        hipLaunchKernelGGL(empirical_structure_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.index.tkey_s.p, (const uint32_t*)cx.index.pc_t.p, N, d_blocks,
                            (uint32_t)n_blocks, pc_step, d_counters);
         PW_HIP_TRY(hipGetLastError());
         PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
@@ -413,10 +392,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
         *info = counters[3];
         return (int)hipGetLastError();
     }
-    cx.tkey.release();
-    cx.tkey_s.release();
-    cx.idx.release();
-    cx.pcs.release();
+    cx.index.release_except({&cx.index.pc_t, &cx.index.idx_s});
 
     // ---- runs ----
     PW_TRY(cx.pc_p.ensure(N * 4));
@@ -427,14 +403,13 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     {
         ScopedKernelTimer timer("empirical_sort_pc");
         size_t temp_bytes = 0, rle_bytes = 0;
-        PW_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, cx.pc_t.as<uint32_t>(), cx.pc_p.as<uint32_t>(), cx.idx_s.as<uint32_t>(), cx.idx_p.as<uint32_t>(), (size_t)N,
-                                             0u, 31u, st));
+        PW_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, cx.index.pc_t.as<uint32_t>(), cx.pc_p.as<uint32_t>(), cx.index.idx_s.as<uint32_t>(), cx.idx_p.as<uint32_t>(),
+                                             (size_t)N, 0u, 31u, st));
         PW_HIP_TRY(rocprim::run_length_encode(nullptr, rle_bytes, cx.pc_p.as<uint32_t>(), (unsigned int)N, cx.uniq.as<uint32_t>(), cx.cnt.as<uint32_t>(),
                                               (uint32_t*)(d_counters + 5), st));
         PW_TRY(cx.temp.ensure(std::max<size_t>(std::max(temp_bytes, rle_bytes), 16)));
-        cx.note();
-        PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.pc_t.as<uint32_t>(), cx.pc_p.as<uint32_t>(), cx.idx_s.as<uint32_t>(), cx.idx_p.as<uint32_t>(), (size_t)N,
-                                             0u, 31u, st));
+        PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.index.pc_t.as<uint32_t>(), cx.pc_p.as<uint32_t>(), cx.index.idx_s.as<uint32_t>(), cx.idx_p.as<uint32_t>(),
+                                             (size_t)N, 0u, 31u, st));
         hipLaunchKernelGGL(empirical_loc_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, st, (const uint32_t*)cx.pc_p.p, (const uint32_t*)cx.idx_p.p, N, d_parts,
                            (uint32_t)h_parts.size(), cx.loc.as<u64>(), d_counters);
         PW_HIP_TRY(hipGetLastError());
@@ -448,8 +423,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
         *info = counters[4];
         return (int)hipGetLastError();
     }
-    cx.pc_t.release();
-    cx.idx_s.release();
+    cx.index.release();
     cx.idx_p.release();
     cx.pc_p.release();
     cx.temp.release();
@@ -470,7 +444,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     PW_TRY(cx.run_air.ensure((size_t)n_runs * 4));
     PW_TRY(cx.run_of.ensure(N * 4));
     PW_TRY(cx.range_off.ensure(((size_t)n_runs + 1) * 8));
-    cx.note();
     PW_HIP_TRY(hipMemcpyAsync(cx.start.p, h_start.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(empirical_runs_kernel, dim3(div_up(std::max<u64>(N, n_runs), kBlock)), dim3(kBlock), 0, st, (const uint32_t*)cx.start.p, n_runs,
                        (const u64*)cx.loc.p, N, cx.run_of.as<uint32_t>(), cx.run_air.as<uint32_t>());
@@ -488,7 +461,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     PW_HIP_TRY(hipMemcpyAsync(cx.range_off.p, h_roff.data(), h_roff.size() * 8, hipMemcpyHostToDevice, st));
     PW_TRY(cx.ranges.ensure(std::max<size_t>(n_cells * 8, 16)));
     PW_TRY(cx.fps.ensure(std::max<size_t>(n_cells * 16, 16)));
-    cx.note();
 
     // ---- panels ----
     uint32_t C = 0;
@@ -503,7 +475,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
         PW_TRY(cx.keys.ensure((size_t)N * C * 8));
         PW_TRY(cx.sorted.ensure((size_t)N * C * 8));
         PW_TRY(cx.temp.ensure(sort_keys_temp(N * C, key_bits((u64)n_runs * C))));
-        cx.note();
     }
     auto run_panels = [&](bool with_ranges, u64 seed0, u64 seed1) -> int {
         PW_HIP_TRY(hipMemsetAsync(cx.fps.p, 0, std::max<size_t>(n_cells * 16, 16), st));
@@ -606,7 +577,6 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
             PW_TRY(cx.pairs.ensure(pairs.size() * sizeof(VPair)));
             PW_TRY(cx.items.ensure(items.size() * 4));
             PW_TRY(cx.mismatch.ensure(pairs.size() * 4));
-            cx.note();
             PW_HIP_TRY(hipMemcpyAsync(cx.pairs.p, pairs.data(), pairs.size() * sizeof(VPair), hipMemcpyHostToDevice, st));
             PW_HIP_TRY(hipMemcpyAsync(cx.items.p, items.data(), items.size() * 4, hipMemcpyHostToDevice, st));
             PW_HIP_TRY(hipMemsetAsync(cx.mismatch.p, 0, pairs.size() * 4, st));

@@ -238,40 +238,16 @@ __global__ __launch_bounds__(kBlock) void execution_blocks_remove_kernel(const u
     if (t < n && chosen[t]) S[(u64)mp[t] + x % L] = kNone;  // (inside [0, K): a match is a window that fits)
 }
 
-struct EbCtx {
-    DeviceBuf small, head, pc_s, uniq, cnt, B, packed, sflag, h0, h1, fp0, fp1, rkey, rkey_s, ridx, ridx_s, first_run, id_a, id_b, key, key_s, pos, pos_s, hflag,
-        rank, cval, cstart, val, st_a, st_b, gkey, gsum, guniq, temp, icount, tkey, tkey_s, idx, idx_s, pcs, pc_t, rs;
-    size_t peak = 0;
+struct EbCtx : Scratch {
+    Buf small{*this}, head{*this}, pc_s{*this}, uniq{*this}, cnt{*this}, B{*this}, packed{*this}, sflag{*this}, h0{*this}, h1{*this}, fp0{*this}, fp1{*this}, rkey{*this},
+        rkey_s{*this}, ridx{*this}, ridx_s{*this}, first_run{*this}, id_a{*this}, id_b{*this}, key{*this}, key_s{*this}, pos{*this}, pos_s{*this}, hflag{*this}, rank{*this},
+        cval{*this}, cstart{*this}, val{*this}, st_a{*this}, st_b{*this}, gkey{*this}, gsum{*this}, guniq{*this}, temp{*this}, rs{*this};
+    time_index::Stage index{*this};  // of the trace route
     uint64_t mask = 0;  // 0: the full width
     uint64_t stat_levels = 0, stat_jumping = 0, stat_seeds = 0, stat_heads = 0, stat_runs = 0;
-    DeviceBuf* all[41] = {&head, &pc_s, &uniq, &cnt, &B, &packed, &sflag, &h0, &h1, &fp0, &fp1, &rkey, &rkey_s, &ridx, &ridx_s, &first_run, &id_a, &id_b, &key,
-                          &key_s, &pos, &pos_s, &hflag, &rank, &cval, &cstart, &val, &st_a, &st_b, &gkey, &gsum, &guniq, &temp, &icount, &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &rs};
-    size_t held() const {
-        size_t s = small.bytes;
-        for (DeviceBuf* b : all) s += b->bytes;
-        return s;
-    }
-    void note(size_t kept = 0) { peak = std::max(peak, held() + kept); }
+    void reset_stats() override { stat_levels = stat_jumping = stat_seeds = stat_heads = stat_runs = 0; }
 };
 thread_local EbCtx g_eb;
-struct EbReleased {
-    EbCtx& cx;
-    ~EbReleased() {
-        for (DeviceBuf* b : cx.all) b->release();
-        cx.small.release();
-    }
-};
-
-// a rocPRIM call f(temporary storage, its size): asked for the size, then run
-template <class F>
-int with_temp(EbCtx& cx, F f) {
-    size_t bytes = 0;
-    PW_HIP_TRY(f(nullptr, bytes));
-    PW_TRY(cx.temp.ensure(std::max<size_t>(bytes, 16)));
-    cx.note();
-    PW_HIP_TRY(f(cx.temp.p, bytes));
-    return 0;
-}
 
 unsigned bits_for(u64 values) {  // bits that hold 0 .. values - 1
     unsigned b = 1;
@@ -294,8 +270,8 @@ int greedy_chains(EbCtx& cx, const u64* key_s, const uint32_t* pos_s, u64 n, uin
     PW_HIP_TRY(hipMemsetAsync(d_counters + 2, 0, 8, st));
     hipLaunchKernelGGL(execution_blocks_flag_kernel, grid, block, 0, st, key_s, pos_s, n, L, hflag, cx.cval.as<uint32_t>());
     if (hflag)
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, hflag, rank, (size_t)n, rocprim::plus<uint32_t>(), st); }));
-    PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, hflag, rank, (size_t)n, rocprim::plus<uint32_t>(), st); }));
+    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
         return rocprim::inclusive_scan(t, b, cx.cval.as<uint32_t>(), cx.cstart.as<uint32_t>(), (size_t)n, rocprim::maximum<uint32_t>(), st);
     }));
     hipLaunchKernelGGL(execution_blocks_level_kernel, grid, block, 0, st, pos_s, (const uint32_t*)rank, (const uint32_t*)cx.cstart.p, n, id_next, cx.val.as<u64>(), d_counters);
@@ -348,7 +324,7 @@ extern "C" void pw_execution_blocks_last_stats(uint64_t* out) {
     out[2] = g_eb.stat_seeds;
     out[3] = g_eb.stat_heads;
     out[4] = g_eb.stat_runs;
-    out[5] = g_eb.peak;
+    out[5] = g_eb.peak();
     out[6] = g_eb.held();
 }
 
@@ -385,11 +361,6 @@ extern "C" void pw_execution_blocks_read_superblocks(const PwExecutionBlocks* e,
 }
 
 namespace {
-
-void reset_stats(EbCtx& cx) {
-    cx.peak = 0;
-    cx.stat_levels = cx.stat_jumping = cx.stat_seeds = cx.stat_heads = cx.stat_runs = 0;
-}
 
 std::unique_ptr<PwExecutionBlocks> empty_result(const PwBasicBlock* blocks, size_t n_blocks) {
     auto result = std::make_unique<PwExecutionBlocks>();
@@ -430,7 +401,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         hipLaunchKernelGGL(execution_blocks_heads_kernel, dim3(div_up(N, kBlock)), dim3(kBlock), 0, st, d_pcs, N, d_blocks, (uint32_t)n_blocks, pc_step, d_tkey,
                            cx.head.as<uint32_t>(), d_counters);
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::select(t, b, cx.head.as<uint32_t>(), cx.B.as<uint32_t>(), d_n, (size_t)N, NotNone32(), st); }));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::select(t, b, cx.head.as<uint32_t>(), cx.B.as<uint32_t>(), d_n, (size_t)N, NotNone32(), st); }));
         PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
     }
@@ -449,8 +420,8 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         PW_TRY(cx.pc_s.ensure(N * 4));
         PW_TRY(cx.uniq.ensure(N * 4));
         PW_TRY(cx.cnt.ensure(N * 4));
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, d_pcs, cx.pc_s.as<uint32_t>(), (size_t)N, 0u, 32u, st); }));
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, d_pcs, cx.pc_s.as<uint32_t>(), (size_t)N, 0u, 32u, st); }));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::run_length_encode(t, b, cx.pc_s.as<uint32_t>(), (unsigned int)N, cx.uniq.as<uint32_t>(), cx.cnt.as<uint32_t>(), d_n + 1, st);
         }));
         uint32_t n_pcs = 0;
@@ -475,7 +446,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         ScopedKernelTimer timer("execution_blocks_cut_kernel");
         hipLaunchKernelGGL(execution_blocks_cut_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, (const uint32_t*)cx.B.p, M, d_blocks, cx.packed.as<u64>());
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::select(t, b, cx.packed.as<u64>(), cx.key.as<u64>(), d_n, (size_t)M, NotEmpty64(), st); }));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::select(t, b, cx.packed.as<u64>(), cx.key.as<u64>(), d_n, (size_t)M, NotEmpty64(), st); }));
         PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
         K = (uint32_t)counters[4];
@@ -494,13 +465,13 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         PW_TRY(R.rid.ensure(K * 4));
         PW_TRY(cx.sflag.ensure(K * 4));
         PW_TRY(cx.rs.ensure((K + 1) * 4));  // the run starts, rs[R] = K: kept through the levels
-        cx.note(K * 8);
+        cx.set_extra(R.S.bytes + R.rid.bytes);  // (the handle's part of the scratch from here on)
         hipLaunchKernelGGL(execution_blocks_unpack_kernel, dim3(div_up(K, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.key.p, K, R.S.as<uint32_t>(), cx.sflag.as<uint32_t>());
         PW_HIP_TRY(hipGetLastError());
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::inclusive_scan(t, b, cx.sflag.as<uint32_t>(), R.rid.as<uint32_t>(), (size_t)K, rocprim::plus<uint32_t>(), st);
         }));
-        PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
             return rocprim::select(t, b, rocprim::counting_iterator<uint32_t>(0), cx.sflag.as<uint32_t>(), cx.rs.as<uint32_t>(), d_n, (size_t)K, st);
         }));
         PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
@@ -521,7 +492,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
     // ---- distinct runs ----
     if (K) {
         const u64 Rn = n_runs;
-        DeviceBuf& rs = cx.rs;
+        Scratch::Buf& rs = cx.rs;
         PW_TRY(cx.h0.ensure(K * 8));
         PW_TRY(cx.h1.ensure(K * 8));
         PW_TRY(cx.fp0.ensure(Rn * 8));
@@ -532,7 +503,6 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         PW_TRY(cx.ridx.ensure(Rn * 4));
         PW_TRY(cx.ridx_s.ensure(Rn * 4));
         PW_TRY(cx.first_run.ensure(Rn * 4));
-        cx.note(K * 8);
         const u64 mask = cx.mask ? cx.mask : ~0ull;
         bool exact = false;
         for (int attempt = 0; attempt < kSeeds && !exact; ++attempt) {
@@ -544,7 +514,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
                                    cx.h0.as<u64>(), cx.h1.as<u64>());
                 PW_HIP_TRY(hipGetLastError());
                 for (int half = 0; half < 2; ++half)
-                    PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                         return rocprim::reduce_by_key(t, b, d_rid, (half ? cx.h1 : cx.h0).as<u64>(), (unsigned int)K, cx.guniq.as<uint32_t>(), (half ? cx.fp1 : cx.fp0).as<u64>(),
                                                       d_n, rocprim::plus<u64>(), rocprim::equal_to<uint32_t>(), st);
                     }));
@@ -555,12 +525,12 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
                 hipLaunchKernelGGL(execution_blocks_runkey_kernel, grid, block, 0, st, (const u64*)cx.fp0.p, (const u64*)cx.fp1.p, (const uint32_t*)rs.p, Rn, mask,
                                    cx.rkey.as<u64>(), cx.ridx.as<uint32_t>());
                 PW_HIP_TRY(hipGetLastError());
-                PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                     return rocprim::radix_sort_pairs(t, b, cx.rkey.as<u64>(), cx.rkey_s.as<u64>(), cx.ridx.as<uint32_t>(), cx.ridx_s.as<uint32_t>(), (size_t)Rn, 0u, 64u, st);
                 }));
                 hipLaunchKernelGGL(execution_blocks_group_kernel, grid, block, 0, st, (const u64*)cx.rkey_s.p, Rn, cx.ridx.as<uint32_t>());
                 PW_HIP_TRY(hipGetLastError());
-                PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                     return rocprim::inclusive_scan(t, b, cx.ridx.as<uint32_t>(), cx.guniq.as<uint32_t>(), (size_t)Rn, rocprim::maximum<uint32_t>(), st);
                 }));
                 hipLaunchKernelGGL(execution_blocks_first_kernel, grid, block, 0, st, (const uint32_t*)cx.ridx_s.p, (const uint32_t*)cx.guniq.p, Rn, cx.first_run.as<uint32_t>());
@@ -583,7 +553,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         std::vector<uint32_t> h_first(Rn);
         PW_HIP_TRY(hipMemcpyAsync(h_first.data(), cx.first_run.p, Rn * 4, hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));
-        for (DeviceBuf* b : {&cx.h0, &cx.h1, &cx.fp0, &cx.fp1, &cx.guniq, &cx.rkey, &cx.rkey_s, &cx.ridx, &cx.ridx_s, &cx.first_run, &cx.sflag}) b->release();
+        for (Scratch::Buf* b : {&cx.h0, &cx.h1, &cx.fp0, &cx.fp1, &cx.guniq, &cx.rkey, &cx.rkey_s, &cx.ridx, &cx.ridx_s, &cx.first_run, &cx.sflag}) b->release();
         // the distinct runs with their counts, in the order of a map keyed by the start pcs (= by the block indices)
         std::vector<u64> times(Rn, 0);
         std::vector<uint32_t> distinct;
@@ -631,7 +601,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
             len_of[c] += len_of[c + 1];
         }
         const uint32_t* d_rs = cx.rs.as<uint32_t>();
-        DeviceBuf& pos_s = cx.pos_s;
+        Scratch::Buf& pos_s = cx.pos_s;
         PW_TRY(cx.id_a.ensure(K * 4));
         PW_TRY(cx.id_b.ensure(K * 4));
         PW_TRY(cx.key.ensure(K * 8));
@@ -648,7 +618,6 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
         PW_TRY(cx.gkey.ensure(K * 8));
         PW_TRY(cx.gsum.ensure(K * 8));
         PW_TRY(cx.guniq.ensure(K * 4));
-        cx.note(K * 8);
         const unsigned bbits = bits_for(n_blocks);
         struct Level { std::vector<u64> key, count; };
         std::vector<Level> levels;
@@ -664,7 +633,7 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
                 hipLaunchKernelGGL(execution_blocks_key_kernel, dim3(div_up(K, kBlock)), dim3(kBlock), 0, st, d_S, d_rid, d_rs, (const uint32_t*)id_prev, K, L, bbits,
                                    (u64)1 << key_bits, cx.key.as<u64>(), cx.pos.as<uint32_t>());
                 PW_HIP_TRY(hipGetLastError());
-                PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                     return rocprim::radix_sort_pairs(t, b, cx.key.as<u64>(), cx.key_s.as<u64>(), cx.pos.as<uint32_t>(), pos_s.as<uint32_t>(), (size_t)K, 0u, key_bits + 1, st);
                 }));
             }
@@ -673,11 +642,11 @@ int detect_blocks(EbCtx& cx, const uint32_t* d_pcs, const u64* d_tkey, u64 N, ui
                 PW_HIP_TRY(hipMemsetAsync(d_counters + 3, 0, 8, st));
                 PW_TRY(greedy_chains(cx, (const u64*)cx.key_s.p, (const uint32_t*)pos_s.p, n_fit, L, cx.hflag.as<uint32_t>(), cx.rank.as<uint32_t>(), id_next, d_counters,
                                      nullptr, nullptr));
-                PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                     return rocprim::reduce_by_key(t, b, cx.rank.as<uint32_t>(), cx.val.as<u64>(), (unsigned int)n_fit, cx.guniq.as<uint32_t>(), cx.gsum.as<u64>(), d_n,
                                                   rocprim::plus<u64>(), rocprim::equal_to<uint32_t>(), st);
                 }));
-                PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+                PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
                     return rocprim::select(t, b, cx.key_s.as<u64>(), cx.hflag.as<uint32_t>(), cx.gkey.as<u64>(), d_n + 1, (size_t)n_fit, st);
                 }));
                 PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, st));
@@ -746,19 +715,13 @@ extern "C" int pw_execution_blocks_from_pcs(const uint32_t* d_pcs, uint64_t n, u
         !time_index::blocks_well_formed(blocks, n_blocks, pc_step))
         return -1;
     EbCtx& cx = g_eb;
-    reset_stats(cx);
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
+    const ScratchCall call(cx, out, status, info);
     auto result = empty_result(blocks, n_blocks);
     if (!n) {
         *out = result.release();
         return 0;
     }
-    (void)hipGetLastError();
-    const EbReleased released{cx};
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
-    const int rc = detect_blocks(cx, d_pcs, nullptr, n, pc_step, blocks, n_blocks, max_bb, bound, 0, result, status, info);
+    const int rc = detect_blocks(cx, d_pcs, nullptr, n, pc_step, blocks, n_blocks, max_bb, call.bound(scratch_bytes), 0, result, status, info);
     if (!rc && !*status) *out = result.release();
     return rc;
 }
@@ -773,29 +736,15 @@ extern "C" int pw_execution_blocks_from_traces(const PwSegmentAir* airs, const u
     if (rows < 0 || (u64)rows >= ((u64)1 << 32)) return -1;
     const u64 M = (u64)rows;
     EbCtx& cx = g_eb;
-    reset_stats(cx);
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
+    const ScratchCall call(cx, out, status, info);
     auto result = empty_result(blocks, n_blocks);
     if (!M) {
         *out = result.release();
         return 0;
     }
-    (void)hipGetLastError();
-    const EbReleased released{cx};
-    hipStream_t st = stream();
     std::vector<Part> parts;
     PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
-    std::vector<u64> g0;
-    {
-        u64 g = 0;  // the parts' rows numbered through
-        for (const Part& part : parts) {
-            g0.push_back(g);
-            g += (u64)1 << airs[part.air].log_height;
-        }
-    }
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.held());
+    const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; the sorted keys and pcs stay through the heads stage
     const size_t index_need = 64 + (size_t)M * 32 + time_index::sort_pairs_temp(M), extra = 64 + (size_t)M * 12;
     if (bound < index_need) {
@@ -803,22 +752,19 @@ extern "C" int pw_execution_blocks_from_traces(const PwSegmentAir* airs, const u
         *info = std::max({index_need, heads_need(M) + extra, levels_need(M)});  // (what is known before a row is read)
         return 0;
     }
-    PW_TRY(cx.icount.ensure(64));
-    const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
-    PW_HIP_TRY(hipMemcpyAsync(cx.icount.p, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
     u64 counters[8];
-    PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, g0, M, cx.icount.as<u64>(),
-                                          time_index::Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
-                                          time_index::Names{"execution_blocks_index_kernel", "execution_blocks_sort_time", "execution_blocks_time_kernel"},
-                                          [&] { cx.note(); }, counters, status, info));
+    PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
+                                          time_index::Names{"execution_blocks_index_kernel", "execution_blocks_sort_time", "execution_blocks_time_kernel"}, counters,
+                                          status, info));
     if (*status) return (int)hipGetLastError();
     const u64 N = counters[0];
     if (!N) {
         *out = result.release();
         return (int)hipGetLastError();
     }
-    for (DeviceBuf* b : {&cx.tkey, &cx.idx, &cx.idx_s, &cx.pcs, &cx.temp}) b->release();
-    const int rc = detect_blocks(cx, (const uint32_t*)cx.pc_t.p, (const u64*)cx.tkey_s.p, N, pc_step, blocks, n_blocks, max_bb, bound, extra, result, status, info);
+    cx.index.release_except({&cx.index.icount, &cx.index.tkey_s, &cx.index.pc_t});  // (`extra` above: the counters' 64 bytes and 12 per row)
+    cx.temp.release();
+    const int rc = detect_blocks(cx, (const uint32_t*)cx.index.pc_t.p, (const u64*)cx.index.tkey_s.p, N, pc_step, blocks, n_blocks, max_bb, bound, extra, result, status, info);
     if (!rc && !*status) *out = result.release();
     return rc;
 }
@@ -835,8 +781,7 @@ extern "C" int pw_execution_blocks_count(PwExecutionBlocks* e, const uint32_t* n
         needle[k] = (uint32_t)(at - e->blocks.begin());
     }
     EbCtx& cx = g_eb;
-    (void)hipGetLastError();
-    const EbReleased released{cx};
+    const ScratchCall call(cx, ScratchCall::kContinues);
     DeviceBuf tables;
     hipStream_t st = stream();
     const size_t off_needle = 64;
@@ -852,7 +797,7 @@ extern "C" int pw_execution_blocks_count(PwExecutionBlocks* e, const uint32_t* n
     hipLaunchKernelGGL(execution_blocks_match_kernel, dim3(div_up(K, kBlock)), dim3(kBlock), 0, st, (const uint32_t*)e->S.p, (const uint32_t*)e->rid.p, K,
                        (const uint32_t*)d_needle, len, cx.hflag.as<uint32_t>());
     PW_HIP_TRY(hipGetLastError());
-    PW_TRY(with_temp(cx, [&](void* t, size_t& b) {
+    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
         return rocprim::select(t, b, rocprim::counting_iterator<uint32_t>(0), cx.hflag.as<uint32_t>(), cx.pos.as<uint32_t>(), d_n, (size_t)K, st);
     }));
     uint32_t n32 = 0;
@@ -867,7 +812,7 @@ extern "C" int pw_execution_blocks_count(PwExecutionBlocks* e, const uint32_t* n
     PW_TRY(cx.st_b.ensure(n * 8));
     int rounds = 0;
     PW_TRY(greedy_chains(cx, nullptr, (const uint32_t*)cx.pos.p, n, len, nullptr, nullptr, nullptr, d_counters, remove ? &tables : nullptr, &rounds));
-    PW_TRY(with_temp(cx, [&](void* t, size_t& b) { return rocprim::reduce(t, b, cx.val.as<u64>(), d_counters + 5, (u64)0, (size_t)n, rocprim::plus<u64>(), st); }));
+    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::reduce(t, b, cx.val.as<u64>(), d_counters + 5, (u64)0, (size_t)n, rocprim::plus<u64>(), st); }));
     u64 total = 0;
     PW_HIP_TRY(hipMemcpyAsync(&total, d_counters + 5, 8, hipMemcpyDeviceToHost, st));
     if (remove) {

@@ -11,12 +11,7 @@ namespace {
 
 namespace rs = register_states;
 
-struct EsCtx {
-    rs::Ctx stage;
-    size_t peak = 0, extra = 0;  // extra: the arrays of the handle under construction
-    void note() { peak = std::max(peak, stage.held() + extra); }
-};
-thread_local EsCtx g_es;
+thread_local rs::Ctx g_es;  // (the arrays of the handle under construction are its `extra`)
 
 }  // namespace
 
@@ -60,11 +55,11 @@ extern "C" int pw_execution_states_read(const PwExecutionStates* e, uint32_t* pc
 
 extern "C" void pw_execution_states_last_stats(uint64_t* out) {
     if (!out) return;
-    out[0] = g_es.stage.sends;
-    out[1] = g_es.stage.kept;
+    out[0] = g_es.sends;
+    out[1] = g_es.kept;
     out[2] = rs::kTile;
-    out[3] = g_es.peak;
-    out[4] = g_es.stage.held();
+    out[3] = g_es.peak();
+    out[4] = g_es.held();
 }
 
 extern "C" int pw_execution_states_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, uint32_t memory_bus,
@@ -73,18 +68,9 @@ extern "C" int pw_execution_states_from_traces(const PwSegmentAir* airs, const u
     const rs::Args a{airs, segment_of_air, n_airs, bridge_bus, memory_bus, final_pc, reg_as, reg_ptr_step};
     u64 M = 0, slots = 0;
     if (!out || !status || !info || !rs::registers_ok(regs, n_regs, reg_ptr_step ? reg_ptr_step : 1u) || !rs::args_ok(a, &M, &slots)) return -1;
-    EsCtx& cx = g_es;
-    cx.peak = cx.extra = 0;
-    cx.stage.sends = cx.stage.kept = 0;
-    *out = nullptr;
-    *status = 0;
-    *info = 0;
-    (void)hipGetLastError();
-    struct Released {
-        rs::Ctx& c;
-        ~Released() { c.release(); }
-    } const released{cx.stage};
-    const size_t bound = scratch_bytes ? scratch_bytes : default_bound(cx.stage.held());
+    rs::Ctx& cx = g_es;
+    const ScratchCall call(cx, out, status, info);
+    const size_t bound = call.bound(scratch_bytes);
     const size_t need = rs::bytes_needed(M, slots, n_regs);
     if (bound < need) {
         *status = 2;
@@ -93,12 +79,12 @@ extern "C" int pw_execution_states_from_traces(const PwSegmentAir* airs, const u
     }
     auto result = std::make_unique<PwExecutionStates>();
     u64 N = 0;
-    const int rc = rs::states_from_traces(a, std::vector<uint32_t>(regs, regs + n_regs), initial_regs, M, slots, cx.stage, result->pcs, result->regs, result->keys,
-                                          [&] { cx.extra = result->bytes(); cx.note(); }, &N, status, info);
+    const int rc = rs::states_from_traces(a, std::vector<uint32_t>(regs, regs + n_regs), initial_regs, M, slots, cx, result->pcs, result->regs, result->keys, &N, status,
+                                          info);
     if (rc || *status) return rc;
     result->n_states = N + 1;
     result->n_regs = n_regs;
-    result->sends = cx.stage.sends;
+    result->sends = cx.sends;
     *out = result.release();
     return 0;
 }

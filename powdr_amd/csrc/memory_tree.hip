@@ -20,14 +20,13 @@
 // as it was. The permutation is p2::permute with the parameters as a kernel argument (scalar loads, as the __constant__ copy of
 // merkle.hip gives them).
 #include "prover_state.hpp"
+#include "scratch.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <memory>
 #include <vector>
-
-#define PW_TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)
 
 namespace pw {
 
@@ -451,31 +450,27 @@ __global__ __launch_bounds__(kBlock) void boundary_leaves_kernel(const uint32_t*
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
-struct TreeCtx {
-    DeviceBuf small;                                   // errors | a count | the tail's level sizes: stays (a few hundred bytes)
-    DeviceBuf found, before, flags, head, ping, pong, temp, tail_t;  // released before a call returns, on every path
-    // incremental mode: the touched sets above the tail's stay until the levels are merged (tset[l] = T_l, wherever it lives)
+struct TreeCtx : Scratch {
+    DeviceBuf small;  // errors | a count | the tail's level sizes: stays and is not accounted (a few hundred bytes)
+    Buf found{*this}, before{*this}, flags{*this}, head{*this}, ping{*this}, pong{*this}, temp{*this}, tail_t{*this};
+    // incremental mode: the touched sets above the tail's stay until the levels are merged (tset[l] = T_l, wherever it lives); as
+    // many buffers as the call has levels, so they are counted as the scratch's `extra`
     std::vector<std::unique_ptr<DeviceBuf>> kept;
     std::vector<const u64*> tset;
-    size_t peak = 0;
     uint64_t launches = 0;
-    size_t held() const {
-        size_t b = found.bytes + before.bytes + flags.bytes + head.bytes + ping.bytes + pong.bytes + temp.bytes + tail_t.bytes;
+    size_t kept_bytes() const {
+        size_t b = 0;
         for (const auto& k : kept) b += k->bytes;
         return b;
     }
-    void note() { peak = std::max(peak, held()); }
+    void release() override {
+        Scratch::release();
+        kept.clear();
+        tset.clear();
+    }
+    void reset_stats() override { launches = 0; }
 };
 thread_local TreeCtx g_tree;
-struct TreeReleased {
-    TreeCtx& cx;
-    ~TreeReleased() {
-        cx.found.release(); cx.before.release(); cx.flags.release(); cx.head.release(); cx.ping.release(); cx.pong.release(); cx.temp.release();
-        cx.tail_t.release();
-        cx.kept.clear();
-        cx.tset.clear();
-    }
-};
 constexpr size_t kErr = 0, kCount = 4, kTailCounts = 8;  // u64 places in TreeCtx::small
 constexpr size_t kSmallWords = kTailCounts + kMaxHeight + 1;
 
@@ -491,11 +486,9 @@ int select_heads(TreeCtx& cx, const u64* idx, u64 n, u64* count) {
     PW_HIP_TRY((hipError_t)cx.head.ensure(n * 8));
     hipLaunchKernelGGL(head_flag_kernel, dim3(div_up(n, kBlock)), dim3(kBlock), 0, st, idx, n, cx.flags.as<uint8_t>());
     u64* d_count = cx.small.as<u64>() + kCount;
-    size_t temp_bytes = 0;
-    PW_HIP_TRY(rocprim::select(nullptr, temp_bytes, rocprim::counting_iterator<u64>(0), cx.flags.as<uint8_t>(), cx.head.as<u64>(), d_count, (size_t)n, st));
-    PW_HIP_TRY((hipError_t)cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
-    cx.note();
-    PW_HIP_TRY(rocprim::select(cx.temp.p, temp_bytes, rocprim::counting_iterator<u64>(0), cx.flags.as<uint8_t>(), cx.head.as<u64>(), d_count, (size_t)n, st));
+    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
+        return rocprim::select(t, b, rocprim::counting_iterator<u64>(0), cx.flags.as<uint8_t>(), cx.head.as<u64>(), d_count, (size_t)n, st);
+    }));
     cx.launches += 2;
     if (count) {
         PW_HIP_TRY(hipMemcpyAsync(count, d_count, 8, hipMemcpyDeviceToHost, st));
@@ -550,7 +543,7 @@ int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64
         if (keep) cx.kept.emplace_back(new DeviceBuf);
         DeviceBuf& out = keep ? *cx.kept.back() : (l & 1) ? cx.ping : cx.pong;
         PW_HIP_TRY((hipError_t)out.ensure(keep ? sizes[l] * 8 : m * 8));
-        cx.note();
+        cx.set_extra(cx.kept_bytes());  // (and notes the peak, whichever buffer `out` is)
         hipLaunchKernelGGL(gather_parent_kernel, dim3(div_up(sizes[l], kBlock)), dim3(kBlock), 0, st, cur, cx.head.as<u64>(), sizes[l], out.as<u64>());
         ++cx.launches;
         cur = out.as<u64>();
@@ -563,7 +556,6 @@ int touched_levels(TreeCtx& cx, const PwMemoryTree* tree, const u64* d_keys, u64
     if (l <= H) {
         const int levels = H - l + 1;
         PW_HIP_TRY((hipError_t)cx.tail_t.ensure((size_t)levels * kTail * 8));
-        cx.note();
         u64* d_counts = cx.small.as<u64>() + kTailCounts;
         const TailArgs a{cur, nullptr, sizes[l - 1], l, H, cx.tail_t.as<u64>(), nullptr, d_counts, nullptr};
         hipLaunchKernelGGL(tail_kernel<false>, dim3(1), dim3(kTail), 0, st, a, P);
@@ -595,11 +587,9 @@ int merge_level(TreeCtx& cx, PwMemoryTree* tree, const PwMemoryTree::Data& old, 
     const u64* t = cx.tset[l];
     hipLaunchKernelGGL(lookup_kernel, dim3(div_up(m + 1, kBlock)), dim3(kBlock), 0, st, t, (const uint32_t*)nullptr, m, o, (const uint32_t*)nullptr, cx.found.as<u64>(),
                        cx.small.as<u64>() + kErr);
-    size_t temp_bytes = 0;
-    PW_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, m + 1, rocprim::plus<u64>(), st));
-    PW_HIP_TRY((hipError_t)cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
-    cx.note();
-    PW_HIP_TRY(rocprim::exclusive_scan(cx.temp.p, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, m + 1, rocprim::plus<u64>(), st));
+    PW_TRY(with_temp(cx.temp, [&](void* tmp, size_t& b) {
+        return rocprim::exclusive_scan(tmp, b, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, m + 1, rocprim::plus<u64>(), st);
+    }));
     u64 n_found = 0;
     PW_HIP_TRY(hipMemcpyAsync(&n_found, cx.before.as<u64>() + m, 8, hipMemcpyDeviceToHost, st));
     PW_HIP_TRY(hipStreamSynchronize(st));
@@ -759,9 +749,7 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
         return 0;
     }
     TreeCtx& cx = g_tree;
-    TreeReleased released{cx};
-    cx.peak = 0;
-    cx.launches = 0;
+    const ScratchCall call(cx);
     const int H = (int)tree->height;
     PW_HIP_TRY((hipError_t)cx.small.ensure(kSmallWords * 8));
     if (!tree->zbuf.p) {
@@ -786,14 +774,10 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
     PW_HIP_TRY((hipError_t)cx.before.ensure((n + 1) * 8));
     hipLaunchKernelGGL(lookup_kernel, dim3(div_up(n + 1, kBlock)), dim3(kBlock), 0, st, d_keys, d_init, (u64)n, old.lv[0], old.payload, cx.found.as<u64>(), d_err);
     ++cx.launches;
-    {
-        size_t temp_bytes = 0;
-        PW_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, n + 1, rocprim::plus<u64>(), st));
-        PW_HIP_TRY((hipError_t)cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
-        cx.note();
-        PW_HIP_TRY(rocprim::exclusive_scan(cx.temp.p, temp_bytes, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, n + 1, rocprim::plus<u64>(), st));
-        ++cx.launches;
-    }
+    PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, cx.found.as<u64>(), cx.before.as<u64>(), 0ull, n + 1, rocprim::plus<u64>(), st);
+    }));
+    ++cx.launches;
     u64 n_found = 0;
     PW_HIP_TRY(hipMemcpyAsync(err, d_err, sizeof err, hipMemcpyDeviceToHost, st));
     PW_HIP_TRY(hipMemcpyAsync(&n_found, cx.before.as<u64>() + n, 8, hipMemcpyDeviceToHost, st));
@@ -857,7 +841,7 @@ extern "C" int pw_memory_tree_update(PwMemoryTree* tree, const uint64_t* d_keys_
     std::swap(tree->data, fresh);
     tree->last_permutations = permutations;
     tree->last_launches = cx.launches;
-    tree->last_scratch = cx.peak;
+    tree->last_scratch = cx.peak();
     return 0;
 }
 

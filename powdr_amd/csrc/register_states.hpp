@@ -275,40 +275,32 @@ inline bool registers_ok(const uint32_t* regs, size_t n, uint32_t ptr_step) {
 }
 
 // the scratch of the stage: everything but the three arrays that leave
-struct Ctx {
-    DeviceBuf icount, tkey, tkey_s, idx, idx_s, pcs, pc_t, temp, small, skey, skey_s, sidx, sidx_s, sword, swit, pos, keep, off, kp, kw;
-    DeviceBuf* all[20] = {&icount, &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &temp, &small, &skey, &skey_s, &sidx, &sidx_s, &sword, &swit, &pos, &keep, &off, &kp, &kw};
+struct Ctx : Scratch {
+    Ctx() = default;  // a context of its own (execution_states.hip)
+    explicit Ctx(Scratch& owner) : Scratch(owner) {}  // a stage of another pipeline's (apc_calls.hip)
+    time_index::Stage index{*this};
+    Buf temp{*this}, small{*this}, skey{*this}, skey_s{*this}, sidx{*this}, sidx_s{*this}, sword{*this}, swit{*this}, pos{*this}, keep{*this}, off{*this}, kp{*this},
+        kw{*this};
     uint64_t sends = 0, kept = 0;
-    size_t held() const {
-        size_t s = 0;
-        for (DeviceBuf* b : all) s += b->bytes;
-        return s;
-    }
-    void release() {
-        for (DeviceBuf* b : all) b->release();
-    }
+    void reset_stats() override { sends = kept = 0; }
 };
-
-inline size_t scan_temp(size_t n) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(), stream());
-    return std::max<size_t>(bytes, 16);
-}
 
 // Bytes that always suffice, before a row is read: the three arrays that leave; the index stage's 32 bytes per bridge row; per slot
 // 28 while the walk appends (key, word, witness, index), 12 sorted, 12 placed (position, flag, offset) and 12 kept; the larger
 // temporary storage; the small tables per register.
 inline size_t bytes_needed(u64 M, u64 slots, u64 n_rows) {
-    const size_t temp = std::max({M ? time_index::sort_pairs_temp(M) : 16, slots ? time_index::sort_pairs_temp(slots) : 16, slots ? scan_temp(slots) : 16});
+    const size_t temp = std::max({M ? time_index::sort_pairs_temp(M) : 16, slots ? time_index::sort_pairs_temp(slots) : 16,
+                                  slots ? time_index::scan_temp((uint32_t*)nullptr, slots) : 16});
     return 4096 + (size_t)(M + 1) * 4 * (n_rows + 1) + (size_t)M * 8 + (size_t)M * 32 + (size_t)slots * 64 + temp + (size_t)n_rows * 32;
 }
 
 // The states of the traces into pcs[N + 1], table[n_rows x (N + 1)] (row k = register regs[k]) and keys[N]; *N_out = N. M, slots: of
 // args_ok. initial: NULL or one word per row. *status = 7, 4, 8, 9 or 10 with *info where there are none; then nothing is valid.
-// note() after every allocation. The caller releases cx.
-template <class Note>
-inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, const uint32_t* initial, u64 M, u64 slots, Ctx& cx, DeviceBuf& pcs, DeviceBuf& table,
-                              DeviceBuf& keys, Note note, u64* N_out, uint32_t* status, uint64_t* info) {
+// The three arrays are Scratch::Buf of the caller's context, or the plain DeviceBuf of a handle under construction, whose bytes are
+// then the scratch's `extra`. The caller releases cx.
+template <class Out>
+inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, const uint32_t* initial, u64 M, u64 slots, Ctx& cx, Out& pcs, Out& table, Out& keys,
+                              u64* N_out, uint32_t* status, uint64_t* info) {
     hipStream_t st = stream();
     const uint32_t n_rows = (uint32_t)regs.size();
     cx.sends = cx.kept = 0;
@@ -316,20 +308,9 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
     if (M) {
         std::vector<Part> parts;
         PW_TRY(collect_parts(a.airs, a.n_airs, a.bridge_bus, parts, nullptr));
-        std::vector<u64> g0;
-        u64 g = 0;  // the parts' rows numbered through
-        for (const Part& part : parts) {
-            g0.push_back(g);
-            g += (u64)1 << a.airs[part.air].log_height;
-        }
-        PW_TRY(cx.icount.ensure(64));
-        const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
-        PW_HIP_TRY(hipMemcpyAsync(cx.icount.p, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
         u64 counters[8];
-        PW_TRY(time_index::rows_in_time_order(a.airs, a.segment_of_air, parts, g0, M, cx.icount.as<u64>(),
-                                              time_index::Bufs{cx.tkey, cx.tkey_s, cx.idx, cx.idx_s, cx.pcs, cx.pc_t, cx.temp},
-                                              time_index::Names{"execution_states_index", "execution_states_sort_time", "execution_states_time"}, note, counters, status,
-                                              info));
+        PW_TRY(time_index::rows_in_time_order(a.airs, a.segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
+                                              time_index::Names{"execution_states_index", "execution_states_sort_time", "execution_states_time"}, counters, status, info));
         if (*status) return (int)hipGetLastError();
         N = counters[0];
     }
@@ -338,14 +319,14 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
     PW_TRY(pcs.ensure(n_states * 4));
     PW_TRY(keys.ensure(std::max<u64>(N, 1) * 8));
     PW_TRY(table.ensure(std::max<u64>((u64)n_rows * n_states, 1) * 4));
-    note();
+    if (!std::is_base_of<Scratch::Buf, Out>::value) cx.set_extra(pcs.bytes + keys.bytes + table.bytes);
     if (N) {
-        PW_HIP_TRY(hipMemcpyAsync(pcs.p, cx.pc_t.p, N * 4, hipMemcpyDeviceToDevice, st));
-        PW_HIP_TRY(hipMemcpyAsync(keys.p, cx.tkey_s.p, N * 8, hipMemcpyDeviceToDevice, st));
+        PW_HIP_TRY(hipMemcpyAsync(pcs.p, cx.index.pc_t.p, N * 4, hipMemcpyDeviceToDevice, st));
+        PW_HIP_TRY(hipMemcpyAsync(keys.p, cx.index.tkey_s.p, N * 8, hipMemcpyDeviceToDevice, st));
     }
-    PW_HIP_TRY(hipMemcpyAsync(pcs.as<uint32_t>() + N, &a.final_pc, 4, hipMemcpyHostToDevice, st));
+    PW_HIP_TRY(hipMemcpyAsync(pcs.template as<uint32_t>() + N, &a.final_pc, 4, hipMemcpyHostToDevice, st));
     PW_HIP_TRY(hipStreamSynchronize(st));
-    for (DeviceBuf* b : {&cx.tkey, &cx.tkey_s, &cx.idx, &cx.idx_s, &cx.pcs, &cx.pc_t, &cx.icount}) b->release();
+    cx.index.release();
     if (!n_rows) return (int)hipGetLastError();
 
     // small: counters (8 u64) | first (n_rows u64) | at0 (n_rows u32) | sorted registers | their rows
@@ -361,7 +342,6 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
     }
     const size_t head_bytes = head.size() * 8;
     PW_TRY(cx.small.ensure(head_bytes + tail.size() * 4));
-    note();
     char* sm = cx.small.as<char>();
     u64* d_counters = (u64*)sm;
     u64* d_first = d_counters + 8;
@@ -376,7 +356,6 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
         PW_TRY(cx.skey.ensure(slots * 8));
         PW_TRY(cx.sword.ensure(slots * 4));
         PW_TRY(cx.swit.ensure(slots * 8));
-        note();
         for (const Part& part : parts) {
             const Walked w = walked(a.airs[part.air]);
             with_fast(w.lp, [&](auto fast) {
@@ -400,26 +379,23 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
             PW_TRY(cx.skey_s.ensure(n_sends * 8));
             PW_TRY(cx.sidx.ensure(n_sends * 4));
             PW_TRY(cx.sidx_s.ensure(n_sends * 4));
-            size_t temp_bytes = time_index::sort_pairs_temp(n_sends);
-            PW_TRY(cx.temp.ensure(temp_bytes));
-            note();
             hipLaunchKernelGGL(time_index::empirical_iota_kernel, dim3(div_up(n_sends, kBlock)), dim3(kBlock), 0, st, cx.sidx.as<uint32_t>(), n_sends);
             PW_HIP_TRY(hipGetLastError());
-            PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.skey.as<u64>(), cx.skey_s.as<u64>(), cx.sidx.as<uint32_t>(), cx.sidx_s.as<uint32_t>(),
-                                                 (size_t)n_sends, 0u, 64u, st));
+            PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
+                return rocprim::radix_sort_pairs(t, b, cx.skey.as<u64>(), cx.skey_s.as<u64>(), cx.sidx.as<uint32_t>(), cx.sidx_s.as<uint32_t>(), (size_t)n_sends, 0u, 64u, st);
+            }));
         }
         {
             ScopedKernelTimer timer("execution_states_place");
             PW_TRY(cx.pos.ensure(n_sends * 4));
             PW_TRY(cx.keep.ensure(n_sends * 4));
             PW_TRY(cx.off.ensure(n_sends * 4));
-            size_t temp_bytes = scan_temp(n_sends);
-            PW_TRY(cx.temp.ensure(temp_bytes));
-            note();
             hipLaunchKernelGGL(execution_states_place_kernel, dim3(div_up(n_sends, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.skey_s.p, (const uint32_t*)cx.sidx_s.p,
                                (const u64*)cx.swit.p, n_sends, (const u64*)keys.p, N, cx.pos.as<uint32_t>(), cx.keep.as<uint32_t>(), d_counters);
             PW_HIP_TRY(hipGetLastError());
-            PW_HIP_TRY(rocprim::exclusive_scan(cx.temp.p, temp_bytes, cx.keep.as<uint32_t>(), cx.off.as<uint32_t>(), 0u, (size_t)n_sends, rocprim::plus<uint32_t>(), st));
+            PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
+                return rocprim::exclusive_scan(t, b, cx.keep.as<uint32_t>(), cx.off.as<uint32_t>(), 0u, (size_t)n_sends, rocprim::plus<uint32_t>(), st);
+            }));
             uint32_t last[2] = {0, 0};
             PW_HIP_TRY(hipMemcpyAsync(&last[0], cx.off.as<uint32_t>() + (n_sends - 1), 4, hipMemcpyDeviceToHost, st));
             PW_HIP_TRY(hipMemcpyAsync(&last[1], cx.keep.as<uint32_t>() + (n_sends - 1), 4, hipMemcpyDeviceToHost, st));
@@ -452,7 +428,6 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
         ScopedKernelTimer timer("execution_states_place");
         PW_TRY(cx.kp.ensure(n_kept * 8));
         PW_TRY(cx.kw.ensure(n_kept * 4));
-        note();
         hipLaunchKernelGGL(execution_states_keep_kernel, dim3(div_up(n_sends, kBlock)), dim3(kBlock), 0, st, (const u64*)cx.skey_s.p, (const uint32_t*)cx.sidx_s.p,
                            (const uint32_t*)cx.sword.p, (const uint32_t*)cx.pos.p, (const uint32_t*)cx.keep.p, (const uint32_t*)cx.off.p, n_sends, cx.kp.as<u64>(),
                            cx.kw.as<uint32_t>());
@@ -463,7 +438,7 @@ inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, 
         ScopedKernelTimer timer("execution_states_fill");
         const u64 tiles = div_up(n_states + 3, kTile);
         hipLaunchKernelGGL(execution_states_fill_kernel, dim3((unsigned)tiles, n_rows), dim3(kBlock), 0, st, (const u64*)cx.kp.p, (const uint32_t*)cx.kw.p, n_kept,
-                           (const uint32_t*)d_at0, n_states, table.as<uint32_t>());
+                           (const uint32_t*)d_at0, n_states, table.template as<uint32_t>());
         PW_HIP_TRY(hipGetLastError());
     }
     PW_HIP_TRY(hipStreamSynchronize(st));  // (at0 is a local)

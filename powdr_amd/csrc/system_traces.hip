@@ -16,7 +16,7 @@
 //                                     permutation that stores every committed intermediate
 // One lane per row, interactions evaluated by eval_span exactly as the prover and the bus check evaluate them. Both tables are the
 // bus check's (bus_shared.hpp: the claim loop, the load rule, the sizing and the growth), each with its own payload columns.
-#include "bus_shared.hpp"
+#include "scratch.hpp"
 #include "bus_witness_args.hpp"
 #include "prover_internal.hpp"
 
@@ -403,22 +403,13 @@ __global__ __launch_bounds__(kBlock) void compress_rows_kernel(const u64* __rest
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
-struct SysCtx {
-    DeviceBuf small;                      // counters | class loads | AIR table | one witness's arguments: stays
-    DeviceBuf sums, table, keys, sorted, temp, vals, sorted_vals;  // released before a call returns, on every path (SysReleased below)
-    size_t peak = 0;
+struct SysCtx : Scratch {
+    Buf small{*this, kStays};  // counters | class loads | AIR table | one witness's arguments
+    Buf sums{*this}, table{*this}, keys{*this}, sorted{*this}, temp{*this}, vals{*this}, sorted_vals{*this};
     uint64_t stat_slots = 0, stat_occupied = 0, stat_tables = 0, stat_triples = 0, stat_additions = 0, stat_lds_atomics = 0, stat_global_atomics = 0;
     uint32_t start_log_slots = 0;  // 0: kStartSlots (pw_memory_boundary_set_start_slots)
-    size_t held() const { return small.bytes + sums.bytes + table.bytes + keys.bytes + sorted.bytes + temp.bytes + vals.bytes + sorted_vals.bytes; }
-    void note() { peak = std::max(peak, held()); }
 };
 thread_local SysCtx g_sys;
-struct SysReleased {
-    SysCtx& cx;
-    ~SysReleased() {
-        cx.sums.release(); cx.table.release(); cx.keys.release(); cx.sorted.release(); cx.temp.release(); cx.vals.release(); cx.sorted_vals.release();
-    }
-};
 
 // before any GPU call: false when an interaction on `bus` has not `n_args` arguments
 bool bus_arity_is(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, uint32_t n_args) {
@@ -439,7 +430,6 @@ int begin_table_walk(SysCtx& cx, const PwSegmentAir* airs, size_t n_airs, uint32
     for (const Part& part : w->parts) w->triples += ((u64)1 << airs[part.air].log_height) * (part.end - part.begin);
     cx.stat_triples = w->triples;
     PW_TRY(cx.small.ensure(sizeof(WalkHead) + n_airs * sizeof(AirDev)));
-    cx.note();
     w->d_head = cx.small.as<WalkHead>();
     w->d_airs = (AirDev*)(w->d_head + 1);
     if (n_airs) PW_HIP_TRY(hipMemcpyAsync(w->d_airs, w->air_tab.data(), n_airs * sizeof(AirDev), hipMemcpyHostToDevice, stream()));
@@ -453,7 +443,7 @@ int begin_table_walk(SysCtx& cx, const PwSegmentAir* airs, size_t n_airs, uint32
 using namespace pw;
 
 extern "C" size_t pw_system_traces_scratch_bytes(void) { return g_sys.held(); }
-extern "C" size_t pw_system_traces_peak_bytes(void) { return g_sys.peak; }
+extern "C" size_t pw_system_traces_peak_bytes(void) { return g_sys.peak(); }
 extern "C" void pw_system_traces_last_stats(PwSystemTraceStats* out) {
     if (!out) return;
     *out = PwSystemTraceStats{g_sys.stat_slots, g_sys.stat_occupied, g_sys.stat_tables, g_sys.stat_triples, g_sys.stat_additions, g_sys.stat_lds_atomics,
@@ -469,11 +459,9 @@ extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, u
                                       uint32_t log_h, uint32_t* d_freq_out, uint64_t* n_foreign, PwBusTuple* first_foreign) {
     if (!airs_well_formed(airs, n_airs) || !d_program || !d_freq_out || !n_foreign || !pc_step || log_h > kRowBits || bus >= bb::P) return -1;
     SysCtx& cx = g_sys;
-    cx.peak = 0;
+    const ScratchCall call(cx);
     cx.stat_triples = 0;
     *n_foreign = 0;
-    (void)hipGetLastError();
-    const SysReleased released{cx};
     const uint32_t table_rows = 1u << log_h;
     std::vector<Part> parts;
     std::vector<AirDev> air_tab;
@@ -482,7 +470,6 @@ extern "C" int pw_program_frequencies(const PwSegmentAir* airs, size_t n_airs, u
     const size_t off_air = 48, off_args = off_air + n_airs * sizeof(AirDev), small_bytes = off_args + (1 + PW_BUS_MAX_ARGS) * 4;
     PW_TRY(cx.small.ensure(small_bytes));
     PW_TRY(cx.sums.ensure((size_t)table_rows * 8));
-    cx.note();
     char* base = cx.small.as<char>();
     u64* d_foreign = (u64*)base;
     AirDev* d_airs = (AirDev*)(base + off_air);
@@ -544,13 +531,11 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
         return -1;
     if (!bus_arity_is(airs, n_airs, bus, kMemoryArgs)) return -1;
     SysCtx& cx = g_sys;
-    cx.peak = 0;
+    const ScratchCall call(cx);
     cx.stat_slots = cx.stat_occupied = cx.stat_tables = cx.stat_triples = 0;
     *log_height = 0;
     *n_locations = 0;
     *status = 0;
-    (void)hipGetLastError();
-    const SysReleased released{cx};
     TableWalk tw;
     PW_TRY(begin_table_walk(cx, airs, n_airs, bus, &tw));
     hipStream_t st = stream();
@@ -568,11 +553,10 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     // pass 1 into tables that grow until one holds the locations (no segment touches more than its triples)
     Grown g;
     PW_TRY(grow_table(
-        cx.table, tw.d_head, tw.triples, kSlotBytes, table_bytes ? table_bytes : default_bound(cx.held()),
+        cx.table, tw.d_head, tw.triples, kSlotBytes, call.bound(table_bytes),
         cx.start_log_slots ? (u64)1 << cx.start_log_slots : kStartSlots, "boundary_table_clear",
         [&](u64* tb, const TableRule& rule) -> int {
             const u64 slots = rule.mask + 1;
-            cx.note();
             T = AddrTable{TableView{rule, tb, nullptr}, tb + slots, tb + 2 * slots, tb + 3 * slots, tb + 4 * slots};
             PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 4 * slots * 8, st));
             PW_HIP_TRY(hipMemsetAsync(tb + 4 * slots, 0, slots * 8, st));
@@ -614,15 +598,10 @@ extern "C" int pw_memory_boundary_trace(const PwSegmentAir* airs, size_t n_airs,
     if (n) {
         PW_TRY(cx.keys.ensure(n * 8));
         PW_TRY(cx.sorted.ensure(n * 8));
-        cx.note();
         hipLaunchKernelGGL(boundary_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.keys.as<u64>(), n, d_counts);
         PW_HIP_TRY(hipGetLastError());
         ScopedKernelTimer timer("boundary_sort");
-        size_t temp_bytes = 0;
-        PW_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), (size_t)n, 0u, 64u, st));
-        PW_TRY(cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
-        cx.note();
-        PW_HIP_TRY(rocprim::radix_sort_keys(cx.temp.p, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), (size_t)n, 0u, 64u, st));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, cx.keys.as<u64>(), cx.sorted.as<u64>(), (size_t)n, 0u, 64u, st); }));
     }
     {
         ScopedKernelTimer timer("boundary_rows_kernel");
@@ -640,13 +619,11 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
         return -1;
     if (!bus_arity_is(airs, n_airs, bus, kCompressArgs)) return -1;
     SysCtx& cx = g_sys;
-    cx.peak = 0;
+    const ScratchCall call(cx);
     cx.stat_slots = cx.stat_occupied = cx.stat_tables = cx.stat_triples = 0;
     *log_height = 0;
     *n_rows = 0;
     *status = 0;
-    (void)hipGetLastError();
-    const SysReleased released{cx};
     TableWalk tw;
     PW_TRY(begin_table_walk(cx, airs, n_airs, bus, &tw));
     hipStream_t st = stream();
@@ -673,11 +650,10 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
     P2Table T{};
     Grown g;
     PW_TRY(grow_table(
-        cx.table, tw.d_head, tw.triples, kP2SlotBytes, table_bytes ? table_bytes : default_bound(cx.held()),
+        cx.table, tw.d_head, tw.triples, kP2SlotBytes, call.bound(table_bytes),
         start_log_slots ? (u64)1 << start_log_slots : kStartSlots, "compress_table_clear",
         [&](u64* tb, const TableRule& rule) -> int {
             const u64 slots = rule.mask + 1;
-            cx.note();
             T = P2Table{TableView{rule, tb, tb + slots}, tb + 2 * slots, tb + 3 * slots};
             PW_HIP_TRY(hipMemsetAsync(tb, 0xFF, 2 * slots * 8, st));
             PW_HIP_TRY(hipMemsetAsync(tb + 2 * slots, 0, slots * 8, st));
@@ -719,17 +695,12 @@ extern "C" int pw_poseidon2_compress_trace(const PwSegmentAir* airs, size_t n_ai
         PW_TRY(cx.vals.ensure(n * 8));
         PW_TRY(cx.sorted.ensure(n * 8));
         PW_TRY(cx.sorted_vals.ensure(n * 8));
-        cx.note();
         hipLaunchKernelGGL(compress_compact_kernel, dim3(div_up(slots, kBlock)), dim3(kBlock), 0, st, T, cx.keys.as<u64>(), cx.vals.as<u64>(), n, d_counts);
         PW_HIP_TRY(hipGetLastError());
         ScopedKernelTimer timer("compress_sort");
-        size_t temp_bytes = 0;
-        PW_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), cx.vals.as<u64>(), cx.sorted_vals.as<u64>(), (size_t)n, 0u,
-                                             64u, st));
-        PW_TRY(cx.temp.ensure(std::max<size_t>(temp_bytes, 16)));
-        cx.note();
-        PW_HIP_TRY(rocprim::radix_sort_pairs(cx.temp.p, temp_bytes, cx.keys.as<u64>(), cx.sorted.as<u64>(), cx.vals.as<u64>(), cx.sorted_vals.as<u64>(), (size_t)n,
-                                             0u, 64u, st));
+        PW_TRY(with_temp(cx.temp, [&](void* t, size_t& b) {
+            return rocprim::radix_sort_pairs(t, b, cx.keys.as<u64>(), cx.sorted.as<u64>(), cx.vals.as<u64>(), cx.sorted_vals.as<u64>(), (size_t)n, 0u, 64u, st);
+        }));
     }
     {
         ScopedKernelTimer timer("compress_rows_kernel");

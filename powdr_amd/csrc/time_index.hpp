@@ -7,7 +7,7 @@
 //   time       empirical_time_kernel      neighbours with one key (status 4), the number of active rows, the pcs in time order
 // Not part of the C ABI.
 #pragma once
-#include "bus_shared.hpp"
+#include "scratch.hpp"
 #include "prover_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
@@ -102,6 +102,16 @@ inline size_t sort_pairs_temp(size_t n) {
     return std::max<size_t>(bytes, 16);
 }
 
+// The temporary storage of an exclusive scan that adds up n words read through `in`. rocPRIM sizes it by the input iterator's type as
+// well as by n, so a "bytes that always suffice" formula asks with the iterator its pipeline scans with: a plain pointer in
+// register_states.hpp, a transform iterator over bytes in apc_sources.hip.
+template <class In>
+inline size_t scan_temp(In in, size_t n) {
+    size_t bytes = 0;
+    (void)rocprim::exclusive_scan(nullptr, bytes, in, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(), stream());
+    return std::max<size_t>(bytes, 16);
+}
+
 // -1 where the block table is unsorted, overlapping or has a zero count
 inline bool blocks_well_formed(const PwBasicBlock* blocks, size_t n_blocks, uint32_t pc_step) {
     if ((!blocks && n_blocks) || n_blocks >= ((size_t)1 << 31)) return false;
@@ -131,24 +141,46 @@ inline long long bridge_rows(const PwSegmentAir* airs, size_t n_airs, uint32_t b
     return (long long)M;
 }
 
-// the buffers of the stage (the caller's, so that its accounting sees them) and the names its launches are timed under
-struct Bufs { DeviceBuf &tkey, &tkey_s, &idx, &idx_s, &pcs, &pc_t, &temp; };
+// The buffers of the stage, part of the scratch of the context that declares it. icount: the 8 device counters, for a caller whose
+// own kernels count in counters[3 ..] as well (counters()).
+struct Stage : Scratch {
+    explicit Stage(Scratch& owner) : Scratch(owner) {}
+    Buf icount{*this}, tkey{*this}, tkey_s{*this}, idx{*this}, idx_s{*this}, pcs{*this}, pc_t{*this};
+    u64* counters() { return icount.as<u64>(); }
+};
+// the names the stage's launches are timed under (the tools read them)
 struct Names { const char *index, *sort, *time; };
 
-// The M rows of `parts` (g0[k] = the global number of part k's first row) by time key: b.tkey_s / b.idx_s hold the sorted keys and row
-// numbers, b.pc_t the pcs in time order, counters[8] the device counters read back (d_counters set to {0, kEmpty, kEmpty, ...} by the
-// caller). *status = 7 or 4 with *info where the rows are no execution; then nothing else is valid. note() after every allocation.
-template <class Note>
-inline int rows_in_time_order(const PwSegmentAir* airs, const uint32_t* segment_of_air, const std::vector<Part>& parts, const std::vector<u64>& g0, u64 M,
-                              u64* d_counters, Bufs b, Names names, Note note, u64* counters, uint32_t* status, uint64_t* info) {
+// The M rows of `parts` by time key: s.tkey_s / s.idx_s hold the sorted keys and row numbers, s.pc_t the pcs in time order, counters[8]
+// the device counters read back. first_rows[k] = the global number of part k's first row, NULL = the parts' rows numbered through.
+// d_counters: where the caller keeps its 8 counters, NULL = in the stage's own icount; they start as {0, kEmpty, kEmpty, ...} here.
+// temp: the caller's temporary storage, which its later stages reuse. *status = 7 or 4 with *info where the rows are no execution;
+// then nothing else is valid.
+inline int rows_in_time_order(const PwSegmentAir* airs, const uint32_t* segment_of_air, const std::vector<Part>& parts, const std::vector<u64>* first_rows, u64 M,
+                              Stage& s, u64* d_counters, Scratch::Buf& temp, Names names, u64* counters, uint32_t* status, uint64_t* info) {
     hipStream_t st = stream();
-    PW_TRY(b.tkey.ensure(M * 8));
-    PW_TRY(b.tkey_s.ensure(M * 8));
-    PW_TRY(b.idx.ensure(M * 4));
-    PW_TRY(b.idx_s.ensure(M * 4));
-    PW_TRY(b.pcs.ensure(M * 4));
-    PW_TRY(b.pc_t.ensure(M * 4));
-    note();
+    std::vector<u64> g0;
+    if (first_rows) {
+        g0 = *first_rows;
+    } else {
+        u64 g = 0;
+        for (const Part& part : parts) {
+            g0.push_back(g);
+            g += (u64)1 << airs[part.air].log_height;
+        }
+    }
+    if (!d_counters) {
+        PW_TRY(s.icount.ensure(64));
+        d_counters = s.counters();
+    }
+    static const u64 counters0[8] = {0, kEmpty, kEmpty, kEmpty, kEmpty, 0, 0, 0};
+    PW_HIP_TRY(hipMemcpyAsync(d_counters, counters0, sizeof counters0, hipMemcpyHostToDevice, st));
+    PW_TRY(s.tkey.ensure(M * 8));
+    PW_TRY(s.tkey_s.ensure(M * 8));
+    PW_TRY(s.idx.ensure(M * 4));
+    PW_TRY(s.idx_s.ensure(M * 4));
+    PW_TRY(s.pcs.ensure(M * 4));
+    PW_TRY(s.pc_t.ensure(M * 4));
     {
         ScopedKernelTimer timer(names.index);
         for (size_t k = 0; k < parts.size(); ++k) {
@@ -157,24 +189,22 @@ inline int rows_in_time_order(const PwSegmentAir* airs, const uint32_t* segment_
             const uint32_t seg = segment_of_air ? segment_of_air[part.air] : 0u;
             with_fast(w.lp, [&](auto fast) {
                 hipLaunchKernelGGL(empirical_index_kernel<decltype(fast)::value>, dim3(div_up(w.H, kBlock)), dim3(kBlock), 0, st, part.vals, w.H, w.lp, w.order, part.begin,
-                                   part.end, (uint32_t)part.air, seg, g0[k], b.tkey.as<u64>(), b.pcs.as<uint32_t>(), d_counters);
+                                   part.end, (uint32_t)part.air, seg, g0[k], s.tkey.as<u64>(), s.pcs.as<uint32_t>(), d_counters);
             });
         }
-        hipLaunchKernelGGL(empirical_iota_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, b.idx.as<uint32_t>(), M);
+        hipLaunchKernelGGL(empirical_iota_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, s.idx.as<uint32_t>(), M);
     }
     PW_HIP_TRY(hipGetLastError());
     {
         ScopedKernelTimer timer(names.sort);
-        size_t temp_bytes = sort_pairs_temp(M);
-        PW_TRY(b.temp.ensure(temp_bytes));
-        note();
-        PW_HIP_TRY(rocprim::radix_sort_pairs(b.temp.p, temp_bytes, b.tkey.as<u64>(), b.tkey_s.as<u64>(), b.idx.as<uint32_t>(), b.idx_s.as<uint32_t>(), (size_t)M, 0u,
-                                             64u, st));
+        PW_TRY(with_temp(temp, [&](void* t, size_t& b) {
+            return rocprim::radix_sort_pairs(t, b, s.tkey.as<u64>(), s.tkey_s.as<u64>(), s.idx.as<uint32_t>(), s.idx_s.as<uint32_t>(), (size_t)M, 0u, 64u, st);
+        }));
     }
     {
         ScopedKernelTimer timer(names.time);
-        hipLaunchKernelGGL(empirical_time_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, (const u64*)b.tkey_s.p, (const uint32_t*)b.idx_s.p,
-                           (const uint32_t*)b.pcs.p, M, b.pc_t.as<uint32_t>(), d_counters);
+        hipLaunchKernelGGL(empirical_time_kernel, dim3(div_up(M, kBlock)), dim3(kBlock), 0, st, (const u64*)s.tkey_s.p, (const uint32_t*)s.idx_s.p,
+                           (const uint32_t*)s.pcs.p, M, s.pc_t.as<uint32_t>(), d_counters);
         PW_HIP_TRY(hipGetLastError());
         PW_HIP_TRY(hipMemcpyAsync(counters, d_counters, 8 * sizeof(u64), hipMemcpyDeviceToHost, st));
         PW_HIP_TRY(hipStreamSynchronize(st));

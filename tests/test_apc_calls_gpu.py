@@ -242,7 +242,7 @@ def test_status_2_and_the_bytes_it_names(gpu):
     pcs, regs, apcs = random_case(rng, 3000)
     with pytest.raises(ac.ApcCallsError) as e:
         ac.select_calls(pcs, to_apcs(apcs), regs=regs, scratch_bytes=1)
-    assert e.value.status == 2 and e.value.info > 1 and "bytes needed" in str(e.value)
+    assert e.value.status == 2 and e.value.info > 1 and "bytes needed" in str(e.value) and ac.last_stats()["scratch_bytes"] == 0
     _, stats = check(gpu, pcs, apcs, regs=regs, scratch_bytes=e.value.info)
     assert 0 < stats["peak_bytes"] <= e.value.info
     with pytest.raises(ac.ApcCallsError) as again:
@@ -289,19 +289,19 @@ def test_trace_statuses(gpu):
         assert [tuple(c) for c in got.calls] == [(0, 0, 2)] and got.counters[0]["aborted"] == 1
     with pytest.raises(ac.ApcCallsError) as e:  # 4: a duplicate time key
         traces_of(gpu, log(rows + [(4, 12, [0])]), apcs, 4)
-    assert (e.value.status, e.value.info) == (4, 12)
+    assert (e.value.status, e.value.info) == (4, 12) and ac.last_stats()["scratch_bytes"] == 0  # (raised after the index stage allocated)
     twice = eref.block_log(rows, 1)
     twice[0, 3] = 2
     with pytest.raises(ac.ApcCallsError) as e:  # 7: a multiplicity of 2, the smallest (air, row)
         traces_of(gpu, log(rows) + [(twice, it)], apcs, 4)
-    assert (e.value.status, e.value.info) == (7, (1 << 32) | 3)
+    assert (e.value.status, e.value.info) == (7, (1 << 32) | 3) and ac.last_stats()["scratch_bytes"] == 0
     with pytest.raises(ValueError):  # -1: two segment numbers
         traces_of(gpu, log(rows) + log(rows), apcs, 4, segments=[0, 1])
     with pytest.raises(ac.ApcCallsError) as e:
         traces_of(gpu, log(rows), apcs, 4, scratch_bytes=1)
     assert e.value.status == 2
     with traces_of(gpu, log(rows), apcs, 4, scratch_bytes=e.value.info) as got:
-        assert len(got.calls) == 1 and ac.last_stats()["peak_bytes"] <= e.value.info
+        assert len(got.calls) == 1 and ac.last_stats()["peak_bytes"] <= e.value.info and ac.last_stats()["scratch_bytes"] == 0
     with traces_of(gpu, log(rows), apcs, 0, bus=1) as got:  # no AIR on the bus: the final state alone
         assert got.calls == [] and got.n_states == 1 and got.counters[0]["aborted"] == 1
 

@@ -154,6 +154,6 @@ def test_without_a_register_literal_the_result_is_from_traces(gpu):
             ac.select_calls(s.seg, to_apcs([(0, 1, 1, [(("reg", 0, 1, 0), ("num", 0))])]), final_pc=ex.final_pc)  # as before: no registers
         with pytest.raises(ac.ApcCallsError) as e:
             ac.select_calls(s.seg, to_apcs([(0, 1, 1, [(("reg", 0, 7, 0), ("num", 0))])]), final_pc=ex.final_pc, registers=dict(n_regs=8))
-        assert (e.value.status, e.value.info) == (9, 7)
+        assert (e.value.status, e.value.info) == (9, 7) and ac.last_stats()["scratch_bytes"] == 0  # (raised inside the nested stage)
     finally:
         s.close()

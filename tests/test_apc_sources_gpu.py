@@ -215,6 +215,7 @@ def test_statuses_7_and_4_come_first_and_an_air_without_the_bridge_takes_no_part
         try:
             aps.apply_calls(s.seg, calls, [2], **kw).close()
         except aps.ApcSourcesError as e:
+            assert aps.last_stats()["scratch_bytes"] == 0  # (7 and 4 are raised after the index stage allocated)
             return e.status, e.info
         finally:
             s.close()

@@ -164,6 +164,7 @@ def test_the_table_grows_until_it_holds_the_bus(gpu, monkeypatch, interpret):
     for _ in range(2):
         got_s, got_t = prover.check_segment_buses(s.seg, tuple_cap=3, table_bytes=40 << 18)
         assert got_s == [dict(bus=11, status=2, n_active=H, n_unbalanced=0)] and got_t == []
+        assert prover.bus_check_scratch_bytes() <= 64 << 10  # (the table that overflowed at the bound is gone again)
     s.close()
 
 

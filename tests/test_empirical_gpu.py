@@ -59,6 +59,7 @@ def status_of(gpu, host, blocks, segments=None, **kw):
     with pytest.raises(ref.Status) as want:
         ref.detect(host, blocks, segments=segments)
     assert (e.value.status, e.value.info) == (want.value.status, want.value.info)
+    assert empirical.last_stats()["scratch_bytes"] < 64 << 10  # (a status raised after the stages allocated: only `small` stays)
     return e.value.status, e.value.info
 
 
@@ -211,7 +212,7 @@ def test_panels_within_a_scratch_bound(gpu):
     try:
         with pytest.raises(empirical.EmpiricalError) as e:
             empirical.detect(s.seg, blocks, scratch_bytes=1)  # below one column
-        assert e.value.status == 2 and e.value.info > 1
+        assert e.value.status == 2 and e.value.info > 1 and empirical.last_stats()["scratch_bytes"] < 64 << 10
         bound = e.value.info
         for _ in range(2):  # (the first figure is what is known before a row is read; a second one is exact)
             try:

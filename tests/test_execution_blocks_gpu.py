@@ -56,6 +56,7 @@ def status_of(gpu, pcs, blocks=BLOCKS, max_bb=1, **kw):
     with pytest.raises(ref.Status) as want:
         ref.detect(pcs, blocks, max_bb=max_bb)
     assert (e.value.status, e.value.info) == (want.value.status, want.value.info)
+    assert eb.last_stats()["scratch_bytes"] == 0  # (a status raised after the heads stage allocated)
     return e.value.status, e.value.info
 
 
@@ -254,13 +255,13 @@ def test_status_2_and_the_bytes_it_names(gpu):
     pcs = expand(([A, B, A, B, D] + [S1]) * 40)
     with pytest.raises(eb.ExecutionBlocksError) as e:
         eb.detect(pcs, BLOCKS, max_bb=3, scratch_bytes=1)
-    assert e.value.status == 2 and e.value.info > 1
+    assert e.value.status == 2 and e.value.info > 1 and eb.last_stats()["scratch_bytes"] == 0
     with check(gpu, pcs, max_bb=3, scratch_bytes=e.value.info) as got:
         stats = eb.last_stats()
         assert stats["peak_bytes"] <= e.value.info and stats["scratch_bytes"] == 0 and got.resident_heads == 200
     with pytest.raises(eb.ExecutionBlocksError) as again:
         eb.detect(pcs, BLOCKS, max_bb=3, scratch_bytes=e.value.info // 16)
-    assert again.value.status == 2
+    assert again.value.status == 2 and eb.last_stats()["scratch_bytes"] == 0  # (refused at the levels: the heads stage had its buffers)
 
 
 # ---- count / remove on the resident execution -------------------------------------------------------------------------------------------
@@ -270,8 +271,11 @@ def test_candidates_counted_and_removed_in_order(gpu):
     for _ in range(200):
         heads += [[A, B, C3][i] for i in rng.integers(0, 3, size=int(rng.integers(1, 9)))] + [S1]
     heads += [A] * 700 + [S2] + [A, B] * 300
+    from powdr_amd import execution_blocks as eb
+
     with check(gpu, expand(heads), max_bb=2) as got:
         runs = got.want["runs"]
+        peak = eb.last_stats()["peak_bytes"]
         steps = [([A, B], False), ([A, A], True), ([A, A, A], False), ([A, B], True), ([B, A], True), ([A, B], False), ([0x7000], True),
                  ([C3, A, 0x7000], False), ([A], True), ([B, C3], False), ([A] * 400, False), ([C3, C3], True), ([C3], True)]
         seen = []
@@ -282,6 +286,10 @@ def test_candidates_counted_and_removed_in_order(gpu):
                 want = ref.count(needle, runs)
             assert got.count(needle, remove=remove) == want, (needle, remove)
             seen.append(want)
+            # a count releases what it took; the detection's peak stands unless the count held more: at most 40 bytes per resident head
+            # (flags, positions, five arrays per match) and a scan's temporary storage, which is less than a level's 168 per head
+            stats = eb.last_stats()
+            assert stats["scratch_bytes"] == 0 and peak <= stats["peak_bytes"] <= max(peak, 65536 + 168 * len(heads))
         assert seen[0] > 300 and seen[1] >= 350 and seen[5] == 0 and seen[6] == 0 and seen[10] == 0  # [A, B] no longer occurs after its removal
         assert got.count([B]) == ref.count([B], runs) > 0
 
@@ -327,15 +335,15 @@ def test_trace_statuses(gpu):
     traces_of(gpu, log(rows), BLOCKS, 2).close()
     with pytest.raises(eb.ExecutionBlocksError) as e:  # 3: the time key of the offending row, not its position
         traces_of(gpu, log(rows[:3] + [(B + 8, 13, [0])] + rows[4:]), BLOCKS, 2, segments=[2])
-    assert (e.value.status, e.value.info) == (3, (2 << 32) | 13)
+    assert (e.value.status, e.value.info) == (3, (2 << 32) | 13) and eb.last_stats()["scratch_bytes"] == 0
     with pytest.raises(eb.ExecutionBlocksError) as e:  # 4: a duplicate time key
         traces_of(gpu, log(rows + [(S1, 12, [0])]), BLOCKS, 2)
-    assert (e.value.status, e.value.info) == (4, 12)
+    assert (e.value.status, e.value.info) == (4, 12) and eb.last_stats()["scratch_bytes"] == 0
     twice = eref.block_log(rows, 1)
     twice[0, 3] = 2
     with pytest.raises(eb.ExecutionBlocksError) as e:  # 7: a multiplicity of 2, the smallest (air, row)
         traces_of(gpu, log(rows) + [(twice, IT)], BLOCKS, 2)
-    assert (e.value.status, e.value.info) == (7, (1 << 32) | 3)
+    assert (e.value.status, e.value.info) == (7, (1 << 32) | 3) and eb.last_stats()["scratch_bytes"] == 0
     with pytest.raises(eb.ExecutionBlocksError) as e:
         traces_of(gpu, log(rows), BLOCKS, 2, scratch_bytes=1)
     assert e.value.status == 2 and e.value.info > 1

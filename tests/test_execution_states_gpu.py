@@ -53,6 +53,7 @@ def status_of(gpu, airs, regs, final_pc, **kw):
     with pytest.raises(es.ExecutionStatesError) as got:
         device_states(gpu, airs, regs, final_pc, **kw)
     assert (got.value.status, got.value.info) == (want.value.status, want.value.info)
+    assert es.last_stats()["scratch_bytes"] == 0  # (a status raised after the stages allocated: 8, 9, 10)
     return got.value
 
 
@@ -154,7 +155,7 @@ def test_status_2_and_the_bytes_it_names(gpu):
     ex = sref.Execution(3000, seed=9)
     with pytest.raises(es.ExecutionStatesError) as e:
         device_states(gpu, ex.airs(), range(6), ex.final_pc, initial_regs=ex.initial, scratch_bytes=1)
-    assert e.value.status == 2 and e.value.info > 1 and "bytes needed" in str(e.value)
+    assert e.value.status == 2 and e.value.info > 1 and "bytes needed" in str(e.value) and es.last_stats()["scratch_bytes"] == 0
     _, _, stats = same(gpu, ex.airs(), range(6), ex.final_pc, initial_regs=ex.initial, scratch_bytes=e.value.info)
     assert 0 < stats["peak_bytes"] <= e.value.info
     with pytest.raises(es.ExecutionStatesError) as again:

@@ -195,12 +195,13 @@ def test_statuses_one_to_four(gpu, monkeypatch):
     # 2: a table bound of 512 slots holds 448 locations, not 600 — the same answer every time
     for _ in range(2):
         assert sa.memory_boundary_trace(s.seg, 10, table_bytes=40 * 512)[1:] == (0, 0, 2)
+        assert sa.last_stats()["scratch_bytes"] < 64 << 10  # (the table that overflowed at the bound is gone again)
     assert sa.memory_boundary_trace(s.seg, 10, table_bytes=39)[3] == 2
     # 3: one row counts twice
     twice = cols.copy()
     twice[12, 17] = 2
     s3 = Segment(gpu, [(twice, it)])
-    assert sa.memory_boundary_trace(s3.seg, 10)[3] == 3
+    assert sa.memory_boundary_trace(s3.seg, 10)[3] == 3 and sa.last_stats()["scratch_bytes"] < 64 << 10  # (raised with the table allocated)
     # 4: a location that is only written: a second AIR with the send alone, at an address nobody else touches
     col = periphery._col
     lone = np.zeros((13, 4), np.uint32)
