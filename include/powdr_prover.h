@@ -713,6 +713,68 @@ uint64_t pw_apc_sources_index_bytes(const PwApcSources* e);
 int pw_apc_sources_tracegen(const PwApcSources* e, const PwApcTraceJob* jobs, size_t n_jobs);
 void pw_apc_sources_tracegen_last_stats(uint64_t* out);
 
+/* ---- cutting an execution into segments under APC-aware limits ----------------------------------------------------
+ * pw_execution_segments_from_traces: positions 0 .. N, their time keys and the map position -> (AIR, row) are exactly
+ * pw_apc_sources_from_traces' (the same bridge evaluation and time sort): original-instruction AIRs only, one instruction per active
+ * row, an AIR without a two-argument interaction on bridge_bus takes no part, one segment number for all AIRs. The calls (n_calls may
+ * be 0) are three host arrays as pw_apc_calls_read_calls returns them: strictly ascending in from, non-overlapping,
+ * to - from == cycle_counts[apc_id].
+ * Classes: there are n_airs + n_apcs. A position covered by call j has class n_airs + apc_id(j) if it is from_j and no class
+ * otherwise; an uncovered position has the class of its AIR. cnt_c(p, q) = the positions of class c in [p, q); width_c = the prover's
+ * width of an AIR class, apc_widths[a] of an APC class. padded(n) = 0 for n == 0, else max(2^min_log_height, next power of two >= n).
+ * fits(p, q): every cnt_c(p, q) <= 2^max_log_height, and max_cells == 0 or sum_c width_c * padded(cnt_c(p, q)) <= max_cells (the sum
+ * is compared as the integer it is: the device adds with saturation at 2^64 - 1). allowed(q): no call has from < q < to.
+ * Cuts: b_0 = 0; b_(s+1) = the largest allowed q in (b_s, N] with fits(b_s, q); until b_S == N. fits is monotone in q, so no valid
+ * cut has fewer segments. N == 0 gives S == 0. This definition is this project's own (the reference's metering code is not part of
+ * its checkout); it meters the ACCELERATED program: a call counts as one row of its APC and is never cut.
+ * Results (host side): S; b[0 .. S]; per segment the time key and pc of its first position, pc[S] = final_pc; first_call[0 .. S]: the
+ * calls of segment s are first_call[s] .. first_call[s + 1]; cnt_c(b_s, b_(s+1)) for every class. On the device, for every (segment,
+ * participating AIR A with a position in it) a row list: the rows of A at the positions of [b_s, b_(s+1)), COVERED ONES INCLUDED, in
+ * ascending position, padded with 0xFFFFFFFF to padded(rows), 16-byte aligned: what PwGatherJob.idx takes. The handle keeps the
+ * lists (4 bytes per entry) and no matrices; the caller gathers a segment into buffers of its own. With calls the ORIGINAL trace of a
+ * segment may be taller than the cap: the cap binds the residuals and the APC traces, which is what gets proven. System AIRs
+ * (boundary, Merkle, program, connector) are not metered.
+ * The contract of pw_apc_sources_from_traces: the call runs on the calling thread's launch stream and synchronises before it returns;
+ * scratch is per thread, bounded by scratch_bytes (0: half of what the device budget allows; the handle's lists count) and
+ * everything but the lists is released on every path. Results are identical on every run.
+ * -1 before any GPU call: whatever pw_apc_sources_from_traces refuses about the AIRs and the calls, a NULL limits pointer,
+ * max_log_height > 31, min_log_height > max_log_height, apc_widths == NULL with n_apcs > 0 and max_cells > 0, a zero apc_widths[a]
+ * under max_cells > 0.
+ * *status: 0 = *out is set (pw_execution_segments_destroy frees it); 2 = the bound is too small, *info = bytes that always suffice
+ * (decided before an element is read); 7 and 4 as for pw_apc_calls_from_traces; 11 = a call with to > N, *info = the smallest such
+ * call index; 13 = nothing fits: no allowed q > b_s satisfies fits(b_s, q) (only possible under max_cells), *info = b_s; 14 = more
+ * than max_segments segments (0 means 2^20), *info = the position reached. Checked in the order 2, 7, 4, 11, 13, 14 (13 and 14 in
+ * the order the cuts meet them). With a non-zero status no result exists and 0 is returned. */
+typedef struct { uint32_t max_log_height, min_log_height; uint64_t max_cells, max_segments; } PwSegmentLimits;
+typedef struct PwExecutionSegments PwExecutionSegments;
+int pw_execution_segments_from_traces(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                                      uint32_t final_pc, const uint32_t* cycle_counts, const uint32_t* apc_widths, size_t n_apcs,
+                                      const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to, size_t n_calls,
+                                      const PwSegmentLimits* limits, size_t scratch_bytes, PwExecutionSegments** out, uint32_t* status,
+                                      uint64_t* info);
+void pw_execution_segments_destroy(PwExecutionSegments* e);
+/* sizes[6] = segments (S), AIRs, APCs, positions (N), covered positions, bytes of the row lists. */
+void pw_execution_segments_sizes(const PwExecutionSegments* e, uint64_t* sizes);
+/* Read-outs into caller arrays (a NULL array is skipped): positions[S + 1] = b, time_keys[S], pcs[S + 1], first_call[S + 1]. */
+void pw_execution_segments_read_bounds(const PwExecutionSegments* e, uint64_t* positions, uint64_t* time_keys, uint32_t* pcs,
+                                       uint64_t* first_call);
+/* rows[s * (n_airs + n_apcs) + c] = cnt_c(b_s, b_(s+1)): class c < n_airs is AIR c (0 for an AIR that takes no part), class
+ * n_airs + a is APC a. */
+void pw_execution_segments_read_heights(const PwExecutionSegments* e, uint64_t* rows);
+/* The row list of (segment, air): device pointer, its rows and log2 of its padded length. Returns 1, 0 where the AIR has no row in
+ * the segment (no list: NULL, 0, 0), -1 for a NULL handle, segment >= S or air >= n_airs. The list lives until
+ * pw_execution_segments_destroy. */
+int pw_execution_segments_rows(const PwExecutionSegments* e, uint32_t segment, uint32_t air, const uint32_t** d_idx, uint64_t* rows,
+                               uint32_t* log_height);
+/* All row lists at once, for tests and tools: the lists lie in ONE device allocation of sizes[5] bytes, in (segment, AIR) order;
+ * *d_base = its first word (NULL without lists), so that the list of (segment, air) begins at word d_idx - *d_base; words (NULL:
+ * skipped) receives a copy of the whole allocation. -1: a NULL handle. */
+int pw_execution_segments_read_lists(const PwExecutionSegments* e, uint32_t* words, const uint32_t** d_base);
+/* Of the calling thread's last pw_execution_segments_from_traces, out[6]: segments, classes, cell-bound probes (workgroup sums of the
+ * bisection), cuts snapped to a call's start, the most scratch bytes held at once (the handle's lists included), scratch bytes held
+ * now. */
+void pw_execution_segments_last_stats(uint64_t* out);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

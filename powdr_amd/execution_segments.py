@@ -1,0 +1,198 @@
+"""Cutting one execution into segments (include/powdr_prover.h `pw_execution_segments_from_traces`): from the
+instruction-AIR traces of one long execution on the device, and optionally the calls `apc_calls.select_calls` chose for it, the greedy
+cut under a height cap per class and a cell budget that counts a call as ONE row of its APC and never falls inside a call. The
+handle keeps, per (segment, AIR), the list of the AIR's rows in the segment — what `apc_sources.gather_rows` takes — and no matrices:
+`ExecutionSegments.segment(s)` gathers a segment into tensors of its own. With calls the original trace of a segment may be taller
+than the cap: the cap binds the residuals and the APC traces, which is what gets proven."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import abi, prover
+from .apc_calls import Apc, ApcCall, ApcCalls
+from .apc_sources import GatherJob, gather_rows
+from .empirical import BUS_EXEC
+from .execution_states import describe, segment_records
+
+lib = abi.lib
+STATUS = {0: "cut", 2: "the scratch bound is too small", 4: "two rows with one time key",
+          7: "multiplicities on the bus that are no single receive with sends", 11: "a call that ends after the execution",
+          13: "nothing fits under max_cells", 14: "more than max_segments segments"}
+STATS = ("segments", "classes", "cell_probes", "snapped_cuts", "peak_bytes", "scratch_bytes")
+
+
+class PwSegmentLimits(C.Structure):
+    _fields_ = [("max_log_height", C.c_uint32), ("min_log_height", C.c_uint32), ("max_cells", C.c_uint64), ("max_segments", C.c_uint64)]
+
+
+assert C.sizeof(PwSegmentLimits) == 24
+
+_u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+lib.pw_execution_segments_from_traces.restype = C.c_int
+lib.pw_execution_segments_from_traces.argtypes = [C.POINTER(prover.PwSegmentAir), _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_size_t, _u32p, _u64p, _u64p,
+                                                  C.c_size_t, C.POINTER(PwSegmentLimits), C.c_size_t, C.POINTER(C.c_void_p), _u32p, _u64p]
+lib.pw_execution_segments_destroy.restype = None
+lib.pw_execution_segments_destroy.argtypes = [C.c_void_p]
+lib.pw_execution_segments_sizes.restype = None
+lib.pw_execution_segments_sizes.argtypes = [C.c_void_p, _u64p]
+lib.pw_execution_segments_read_bounds.restype = None
+lib.pw_execution_segments_read_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.pw_execution_segments_read_heights.restype = None
+lib.pw_execution_segments_read_heights.argtypes = [C.c_void_p, C.c_void_p]
+lib.pw_execution_segments_rows.restype = C.c_int
+lib.pw_execution_segments_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), _u64p, _u32p]
+lib.pw_execution_segments_read_lists.restype = C.c_int
+lib.pw_execution_segments_read_lists.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+lib.pw_execution_segments_last_stats.restype = None
+lib.pw_execution_segments_last_stats.argtypes = [_u64p]
+
+
+class ExecutionSegmentsError(ValueError):
+    """a non-zero status of pw_execution_segments_from_traces: `.status`, `.info` (the raw word), the decoded info in the message"""
+
+    def __init__(self, status: int, info: int):
+        self.status, self.info = int(status), int(info)
+        what = f"position {self.info}" if self.status in (13, 14) else describe(self.status, self.info)
+        super().__init__(f"pw_execution_segments: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+
+
+def last_stats() -> dict:
+    out = (C.c_uint64 * 6)()
+    lib.pw_execution_segments_last_stats(out)
+    return dict(zip(STATS, (int(x) for x in out)))
+
+
+def from_traces_raw(recs, n_airs, segments, bus, final_pc, cycle_counts, apc_widths, n_apcs, ids, start, end, n_calls, limits, scratch_bytes):
+    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
+    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
+    rc = lib.pw_execution_segments_from_traces(recs, segments, n_airs, bus, final_pc, cycle_counts, apc_widths, n_apcs, ids, start, end, n_calls, limits, scratch_bytes,
+                                               C.byref(out), C.byref(status), C.byref(info))
+    return rc, int(status.value), int(info.value), out.value
+
+
+class ExecutionSegments:
+    """`.bounds` [b_0 .. b_S]; `.starts` [(pc, time key)] per segment; `.final_pc`; `.first_call` [S + 1]; `.heights[s]` {air or
+    ("apc", a): rows} (classes without rows left out); `.calls(s)` the segment's ApcCalls re-based to it; `.rows(s, air)` (device
+    pointer of the row list, rows, log_height) or None; `.segment(s)` the segment's traces, gathered. `.n_segments`, `.n_airs`,
+    `.n_apcs`, `.positions`, `.covered`, `.list_bytes`. The lists are valid until close()."""
+
+    def __init__(self, handle, seg, calls):
+        self._h, self._seg, self._calls = handle, list(seg), list(calls)
+        sizes = (C.c_uint64 * 6)()
+        lib.pw_execution_segments_sizes(handle, sizes)
+        self.n_segments, self.n_airs, self.n_apcs, self.positions, self.covered, self.list_bytes = (int(x) for x in sizes)
+        S, classes = self.n_segments, self.n_airs + self.n_apcs
+        b, keys, pcs, first = np.zeros(S + 1, np.uint64), np.zeros(max(S, 1), np.uint64), np.zeros(S + 1, np.uint32), np.zeros(S + 1, np.uint64)
+        lib.pw_execution_segments_read_bounds(handle, *(x.ctypes.data_as(C.c_void_p) for x in (b, keys, pcs, first)))
+        rows = np.zeros(max(S * classes, 1), np.uint64)
+        lib.pw_execution_segments_read_heights(handle, rows.ctypes.data_as(C.c_void_p))
+        self.bounds = [int(x) for x in b]
+        self.starts = [(int(pcs[s]), int(keys[s])) for s in range(S)]
+        self.final_pc = int(pcs[S])
+        self.first_call = [int(x) for x in first]
+        self.heights = []
+        for s in range(S):
+            row = rows[s * classes:(s + 1) * classes]
+            self.heights.append({(int(c) if c < self.n_airs else ("apc", int(c) - self.n_airs)): int(row[c]) for c in np.nonzero(row)[0]})
+
+    def calls(self, s: int) -> list:
+        """the calls of segment s as positions of the segment: what `apply_calls(self.segment(s), ...)` takes"""
+        b = self.bounds[s]
+        return [ApcCall(c.apc_id, c.start - b, c.end - b) for c in self._calls[self.first_call[s]:self.first_call[s + 1]]]
+
+    def rows(self, s: int, air: int):
+        p, n, lh = C.c_void_p(), C.c_uint64(), C.c_uint32()
+        rc = lib.pw_execution_segments_rows(self._h, int(s), int(air), C.byref(p), C.byref(n), C.byref(lh))
+        if rc < 0:
+            raise IndexError(f"no segment {s} or no AIR {air}")
+        return (p.value, int(n.value), int(lh.value)) if rc else None
+
+    def read_lists(self) -> dict:
+        """{(segment, air): u32[2^log_height]} — every row list copied to the host in one copy (`pw_execution_segments_read_lists`)"""
+        words, base = np.zeros(max(self.list_bytes // 4, 1), np.uint32), C.c_void_p()
+        abi.check(lib.pw_execution_segments_read_lists(self._h, words.ctypes.data_as(C.c_void_p), C.byref(base)), "pw_execution_segments_read_lists")
+        out = {}
+        for s in range(self.n_segments):
+            for air in range(self.n_airs):
+                r = self.rows(s, air)
+                if r is not None:
+                    at = (r[0] - base.value) // 4
+                    out[(s, air)] = words[at:at + (1 << r[2])]
+        return out
+
+    def segment(self, s: int, buffers=None) -> list:
+        """[(air index, Prover, tensor i32[width, 2^log_height] column-major on the device, log_height)] for the AIRs with rows in
+        segment s: the tensors are allocated here (or taken from buffers {air: a contiguous i32 tensor of width x 2^log_height
+        words}) and filled by ONE `gather_rows` call, every word written; AIRs without rows are left out"""
+        import torch
+
+        out, jobs = [], []
+        for air, (pr, ptr, lh) in enumerate(self._seg):
+            r = self.rows(s, air)
+            if r is None:
+                continue
+            if buffers is not None and air in buffers:
+                t = buffers[air]
+                if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != pr.width << r[2]:
+                    raise ValueError(f"segment: the buffer of AIR {air} is no contiguous i32 tensor of {pr.width} x {1 << r[2]} words")
+                t = t.view(pr.width, 1 << r[2])
+            else:
+                t = torch.empty((pr.width, 1 << r[2]), dtype=torch.int32, device="cuda")
+            jobs.append(GatherJob(ptr, 1 << lh, pr.width, r[0], t.data_ptr(), 1 << r[2]))
+            out.append((air, pr, t, r[2]))
+        gather_rows(jobs)
+        return out
+
+    def close(self) -> None:
+        if self._h is not None:
+            lib.pw_execution_segments_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widths=None, min_log_height: int = 0, max_cells: int = 0, max_segments: int = 0,
+        segments=None, bus: int = BUS_EXEC, scratch_bytes: int = 0) -> ExecutionSegments:
+    """seg: the AIR list [(Prover, device trace pointer, log_height)] of ONE execution; calls: the `ApcCalls` of `select_calls` on it, or
+    a list of ApcCall(apc_id, start, end) ascending in start; apcs: [Apc] or the cycle counts, apc_id = the index; apc_widths: the
+    APC traces' widths (needed under max_cells). A class holds at most 2^max_log_height rows per segment; max_cells (0: no bound)
+    bounds the sum of width x padded height, heights padded to at least 2^min_log_height; max_segments 0 = 2^20. A non-zero status
+    raises ExecutionSegmentsError."""
+    if isinstance(calls, ApcCalls):
+        calls = calls.calls
+    calls = [ApcCall(*c) for c in (calls or [])]
+    apcs = list(apcs or [])
+    if calls and not apcs:
+        raise ValueError("cut: calls without apcs")
+    cycles = [int(a.cycle_count if isinstance(a, Apc) else a[1] if isinstance(a, (tuple, list)) else a) for a in apcs]
+    if apc_widths is not None and len(apc_widths) != len(cycles):
+        raise ValueError("cut: one width per APC")
+    for name, v, top in (("max_log_height", max_log_height, 1 << 32), ("min_log_height", min_log_height, 1 << 32), ("max_cells", max_cells, 1 << 64),
+                         ("max_segments", max_segments, 1 << 64), ("final_pc", final_pc, 1 << 32)):
+        if not 0 <= int(v) < top:
+            raise ValueError(f"cut: {name} out of range")
+    recs, numbers = segment_records(seg, segments)
+    n, m = len(calls), len(cycles)
+    t_cycles = (C.c_uint32 * max(m, 1))(*cycles)
+    t_widths = (C.c_uint32 * max(m, 1))(*[int(w) for w in apc_widths]) if apc_widths is not None else None
+    t_ids = (C.c_uint32 * max(n, 1))(*[int(c.apc_id) for c in calls])
+    t_from = (C.c_uint64 * max(n, 1))(*[int(c.start) for c in calls])
+    t_to = (C.c_uint64 * max(n, 1))(*[int(c.end) for c in calls])
+    limits = PwSegmentLimits(int(max_log_height), int(min_log_height), int(max_cells), int(max_segments))
+    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), int(final_pc), t_cycles, t_widths, m, t_ids, t_from, t_to, n, C.byref(limits),
+                                               int(scratch_bytes))
+    if rc == -1:
+        raise ValueError("pw_execution_segments_from_traces: malformed arguments")
+    abi.check(rc, "pw_execution_segments_from_traces")
+    if status:
+        raise ExecutionSegmentsError(status, info)
+    return ExecutionSegments(handle, seg, calls)

@@ -384,6 +384,21 @@ pub struct PwApcTraceJob {
     pub out_height: u64,
     pub out_width: u32,
 }
+/// the limits of `pw_execution_segments_from_traces`: a class holds at most `2^max_log_height` rows, heights are padded to at least
+/// `2^min_log_height`, `max_cells` bounds the sum of width x padded height (0 = no bound), `max_segments` 0 = 2^20
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PwSegmentLimits {
+    pub max_log_height: u32,
+    pub min_log_height: u32,
+    pub max_cells: u64,
+    pub max_segments: u64,
+}
+/// the opaque result of `pw_execution_segments_from_traces`: the cuts on the host, the per-(segment, AIR) row lists on the device
+#[repr(C)]
+pub struct PwExecutionSegments {
+    _private: [u8; 0],
+}
 /// the opaque result of `pw_execution_states_from_traces`: the states of a segment on the device
 #[repr(C)]
 pub struct PwExecutionStates {
@@ -633,6 +648,27 @@ extern "C" {
     pub fn pw_apc_sources_tracegen(e: *const PwApcSources, jobs: *const PwApcTraceJob, n_jobs: usize) -> c_int;
     /// out[6]: jobs, work items, 16-byte-load tiles, 4-byte-load tiles, bytes written, scratch held
     pub fn pw_apc_sources_tracegen_last_stats(out: *mut u64);
+    /// cutting ONE execution into segments under APC-aware limits: the greedy cut that never falls inside a call.
+    /// `status` 0 = `*out` is set (free it with `pw_execution_segments_destroy`); 11 = a call beyond the execution, 13 = nothing
+    /// fits under `max_cells`, 14 = more than `max_segments` segments
+    pub fn pw_execution_segments_from_traces(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, final_pc: u32,
+                                             cycle_counts: *const u32, apc_widths: *const u32, n_apcs: usize, call_apc_ids: *const u32,
+                                             call_from: *const u64, call_to: *const u64, n_calls: usize, limits: *const PwSegmentLimits,
+                                             scratch_bytes: usize, out: *mut *mut PwExecutionSegments, status: *mut u32, info: *mut u64) -> c_int;
+    pub fn pw_execution_segments_destroy(e: *mut PwExecutionSegments);
+    /// sizes[6] = segments, AIRs, APCs, positions, covered positions, bytes of the row lists
+    pub fn pw_execution_segments_sizes(e: *const PwExecutionSegments, sizes: *mut u64);
+    /// positions[S + 1], time_keys[S], pcs[S + 1], first_call[S + 1]; a NULL array is skipped
+    pub fn pw_execution_segments_read_bounds(e: *const PwExecutionSegments, positions: *mut u64, time_keys: *mut u64, pcs: *mut u32, first_call: *mut u64);
+    /// rows[S x (n_airs + n_apcs)]: the class counts of every segment
+    pub fn pw_execution_segments_read_heights(e: *const PwExecutionSegments, rows: *mut u64);
+    /// the row list of (segment, air) on the device, what `PwGatherJob::idx` takes: 1, 0 = no rows, -1 = out of range
+    pub fn pw_execution_segments_rows(e: *const PwExecutionSegments, segment: u32, air: u32, d_idx: *mut *const u32, rows: *mut u64,
+                                      log_height: *mut u32) -> c_int;
+    /// a host copy of all row lists (one allocation of sizes[5] bytes) and the device address of its first word
+    pub fn pw_execution_segments_read_lists(e: *const PwExecutionSegments, words: *mut u32, d_base: *mut *const u32) -> c_int;
+    /// out[6]: segments, classes, cell-bound probes, cuts snapped to a call's start, peak scratch, scratch held
+    pub fn pw_execution_segments_last_stats(out: *mut u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
