@@ -11,13 +11,11 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 from .empirical import BUS_EXEC
 
 lib = abi.lib
-STATUS = {0: "selected", 2: "the scratch bound is too small", 4: "two rows with one time key",
-          7: "multiplicities on the bus that are no single receive with sends", 8: "a register tuple that is none",
-          9: "a requested register without a value", 10: "the initial registers contradicted by the first receive"}
+STATUS = {0: "selected", **stage.texts(2, 4, 7, 8, 9, 10)}
 COUNTERS = ("matches", "refused", "failed", "aborted", "done", "discarded", "calls")
 KIND_NUMBER, KIND_PC, KIND_REGISTER_LIMB = 0, 1, 2
 
@@ -163,15 +161,9 @@ def instruction_indexed_start_pcs(blocks) -> list:
 
 
 # ---- the C call ---------------------------------------------------------------------------------------------------------------------
-class ApcCallsError(ValueError):
+class ApcCallsError(stage.StageError):
     """a non-zero status of pw_apc_calls_from_*: `.status`, `.info` (the raw word), the decoded info in the message"""
-
-    def __init__(self, status: int, info: int):
-        self.status, self.info = int(status), int(info)
-        from .execution_states import describe
-
-        what = describe(self.status, self.info)
-        super().__init__(f"pw_apc_calls: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+    PREFIX, STATUS = "pw_apc_calls", STATUS
 
 
 def set_long_threshold(n: int) -> None:
@@ -208,35 +200,12 @@ def tables(apcs):
     return t_apcs, len(rows), t_cons, len(flat)
 
 
-def from_states_raw(d_pcs, d_regs, n_states, n_regs, limb_bits, t_apcs, n_apcs, t_cons, n_cons, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_apc_calls_from_states(d_pcs, d_regs, n_states, n_regs, limb_bits, t_apcs, n_apcs, t_cons, n_cons, scratch_bytes, C.byref(out), C.byref(status),
-                                      C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-def from_traces_raw(recs, n_airs, segments, bus, final_pc, t_apcs, n_apcs, t_cons, n_cons, scratch_bytes):
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_apc_calls_from_traces(recs, segments, n_airs, bus, final_pc, t_apcs, n_apcs, t_cons, n_cons, scratch_bytes, C.byref(out), C.byref(status),
-                                      C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-def from_traces_registers_raw(recs, n_airs, segments, bus, memory_bus, final_pc, reg_as, ptr_step, n_regs, limb_bits, initial_regs, t_apcs, n_apcs, t_cons, n_cons,
-                              scratch_bytes):
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_apc_calls_from_traces_registers(recs, segments, n_airs, bus, memory_bus, final_pc, reg_as, ptr_step, n_regs, limb_bits, initial_regs, t_apcs, n_apcs,
-                                                t_cons, n_cons, scratch_bytes, C.byref(out), C.byref(status), C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-class ApcCalls:
+class ApcCalls(stage.Handle):
     """`.calls` [ApcCall(apc_id, start, end)] in insertion order; `.counters` per APC {matches, refused, failed, aborted, done,
     discarded, calls}; `.covered` the positions inside calls; `.time_keys` (trace route) the time key of every position."""
 
     def __init__(self, handle):
-        self._h = handle
+        super().__init__(handle, lib.pw_apc_calls_destroy)
         sizes = (C.c_uint64 * 5)()
         lib.pw_apc_calls_sizes(handle, sizes)
         n_calls, n_apcs, self.covered, self.n_states, n_keys = (int(x) for x in sizes)
@@ -251,32 +220,6 @@ class ApcCalls:
         lib.pw_apc_calls_read_time_keys(handle, ptr(keys))
         self.time_keys = keys.tolist()
 
-    def close(self) -> None:
-        if self._h is not None:
-            lib.pw_apc_calls_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
-
-def _device_words(x, what):
-    """a CUDA int32 / uint32 tensor read in place, or anything numpy turns into 32-bit words copied to the device -> (tensor, words)"""
-    import torch
-
-    if hasattr(x, "data_ptr"):
-        if not x.is_cuda or x.dtype not in (torch.int32, torch.uint32) or not x.is_contiguous():
-            raise ValueError(f"{what} on the device: a contiguous int32 / uint32 tensor")
-        return x, x.numel()
-    words = np.ascontiguousarray(np.asarray(x, dtype=np.uint32).reshape(-1))
-    return (torch.from_numpy(words.view(np.int32)).cuda() if len(words) else None), len(words)
-
 
 def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_pc=None, segments=None, bus: int = BUS_EXEC,
                  scratch_bytes: int = 0, registers=None) -> ApcCalls:
@@ -289,21 +232,14 @@ def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_p
     apcs: [Apc(start_pc, cycle_count, priority, constraints)], apc_id = the index.
     A non-zero status raises ApcCallsError."""
     t_apcs, n_apcs, t_cons, n_cons = tables(apcs)
-    traces = isinstance(states_or_segment, (list, tuple)) and len(states_or_segment) > 0 and isinstance(states_or_segment[0], tuple) and hasattr(states_or_segment[0][0], "_h")
-    if traces:
+    tail = (t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
+    if stage.is_air_list(states_or_segment):
         if final_pc is None or regs is not None:
             raise ValueError("the trace route: final_pc, and no registers")
-        n = len(states_or_segment)
-        recs = (prover.PwSegmentAir * n)()
-        for i, (pr, ptr, lh) in enumerate(states_or_segment):
-            recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
-        seg = None
-        if segments is not None:
-            assert len(segments) == n
-            seg = (C.c_uint32 * n)(*[int(s) for s in segments])
+        recs, numbers = stage.air_records(states_or_segment, segments)
+        head = (recs, numbers, len(states_or_segment), int(bus))
         if registers is None:
-            rc, status, info, handle = from_traces_raw(recs, n, seg, int(bus), int(final_pc), t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
-            what = "pw_apc_calls_from_traces"
+            fn, what, args = lib.pw_apc_calls_from_traces, "pw_apc_calls_from_traces", (*head, int(final_pc))
         else:
             unknown = set(registers) - {"n_regs", "initial", "reg_as", "ptr_step", "memory_bus"}
             if unknown:
@@ -312,16 +248,15 @@ def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_p
             if initial is not None and len(initial) != n_regs:
                 raise ValueError("registers: initial holds one word per register")
             t_init = None if initial is None else (C.c_uint32 * max(n_regs, 1))(*[int(w) for w in initial])
-            rc, status, info, handle = from_traces_registers_raw(recs, n, seg, int(bus), int(registers.get("memory_bus", 1)), int(final_pc),
-                                                                 int(registers.get("reg_as", 1)), int(registers.get("ptr_step", 4)), n_regs, int(limb_bits), t_init,
-                                                                 t_apcs, n_apcs, t_cons, n_cons, int(scratch_bytes))
-            what = "pw_apc_calls_from_traces_registers"
+            fn, what = lib.pw_apc_calls_from_traces_registers, "pw_apc_calls_from_traces_registers"
+            args = (*head, int(registers.get("memory_bus", 1)), int(final_pc), int(registers.get("reg_as", 1)), int(registers.get("ptr_step", 4)), n_regs, int(limb_bits),
+                    t_init)
     else:
         import torch
 
         if registers is not None:
             raise ValueError("registers: on the trace route only")
-        keep_pcs, n_states = _device_words(states_or_segment, "the pcs")
+        keep_pcs, n_states = stage.device_words(states_or_segment, "the pcs")
         keep_regs, n_regs = None, 0
         if regs is not None:
             if hasattr(regs, "data_ptr"):
@@ -329,17 +264,10 @@ def select_calls(states_or_segment, apcs, regs=None, limb_bits: int = 8, final_p
             else:
                 regs = np.asarray(regs, dtype=np.uint32).reshape(-1, n_states) if n_states else np.zeros((0, 0), np.uint32)
                 n_regs = regs.shape[0]
-            keep_regs, n_words = _device_words(regs, "the registers")
+            keep_regs, n_words = stage.device_words(regs, "the registers")
             if n_words != n_regs * n_states:
                 raise ValueError("the registers: one row of n_states values per register")
         torch.cuda.synchronize()  # the library reads on its own launch stream
-        rc, status, info, handle = from_states_raw(keep_pcs.data_ptr() if keep_pcs is not None else None,
-                                                   keep_regs.data_ptr() if keep_regs is not None else None, n_states, n_regs, int(limb_bits), t_apcs, n_apcs,
-                                                   t_cons, n_cons, int(scratch_bytes))
-        what = "pw_apc_calls_from_states"
-    if rc == -1:
-        raise ValueError(f"{what}: malformed arguments")
-    abi.check(rc, what)
-    if status:
-        raise ApcCallsError(status, info)
-    return ApcCalls(handle)
+        fn, what = lib.pw_apc_calls_from_states, "pw_apc_calls_from_states"
+        args = (keep_pcs.data_ptr() if keep_pcs is not None else None, keep_regs.data_ptr() if keep_regs is not None else None, n_states, n_regs, int(limb_bits))
+    return ApcCalls(stage.call(fn, what, *args, *tail, error=ApcCallsError))

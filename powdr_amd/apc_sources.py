@@ -13,15 +13,12 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 from .apc_calls import Apc, ApcCall, ApcCalls
 from .empirical import BUS_EXEC
-from .execution_states import describe, segment_records
 
 lib = abi.lib
-STATUS = {0: "applied", 2: "the scratch bound is too small", 4: "two rows with one time key",
-          7: "multiplicities on the bus that are no single receive with sends", 11: "a call that ends after the execution",
-          12: "two calls of one APC disagree on the AIR of an instruction"}
+STATUS = {0: "applied", **stage.texts(2, 4, 7, 11), 12: "two calls of one APC disagree on the AIR of an instruction"}
 DIRECT = 1  # PW_APC_SOURCES_DIRECT
 TRACEGEN_STATS = ("jobs", "work_items", "tiles_16_byte_loads", "tiles_4_byte_loads", "bytes_written", "scratch_bytes")
 STATS = ("covered", "source_bytes", "residual_bytes", "gather_jobs", "tiles_16_byte_loads", "tiles_4_byte_loads", "peak_bytes", "scratch_bytes")
@@ -82,13 +79,9 @@ lib.pw_apc_sources_last_stats.restype = None
 lib.pw_apc_sources_last_stats.argtypes = [_u64p]
 
 
-class ApcSourcesError(ValueError):
+class ApcSourcesError(stage.StageError):
     """a non-zero status of pw_apc_sources_from_traces: `.status`, `.info` (the raw word), the decoded info in the message"""
-
-    def __init__(self, status: int, info: int):
-        self.status, self.info = int(status), int(info)
-        what = describe(self.status, self.info)
-        super().__init__(f"pw_apc_sources: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+    PREFIX, STATUS = "pw_apc_sources", STATUS
 
 
 def last_stats() -> dict:
@@ -120,23 +113,10 @@ def gather_rows(jobs) -> None:
     0xFFFFFFFF gives a zero row; every word of every output is written, all jobs in one launch (`pw_trace_gather_rows`)"""
     jobs = [GatherJob(*j) for j in jobs]
     recs = (PwGatherJob * max(len(jobs), 1))(*[PwGatherJob(*(int(x) if x is not None else None for x in j)) for j in jobs])
-    rc = lib.pw_trace_gather_rows(recs, len(jobs))
-    if rc == -1:
-        raise ValueError("pw_trace_gather_rows: malformed arguments")
-    abi.check(rc, "pw_trace_gather_rows")
+    stage.check(lib.pw_trace_gather_rows(recs, len(jobs)), "pw_trace_gather_rows")
 
 
-def from_traces_raw(recs, n_airs, segments, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes, flags=None):
-    """the C call itself (flags None: pw_apc_sources_from_traces, else pw_apc_sources_from_traces_flags) -> (return code, status, info,
-    handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    head = (recs, segments, n_airs, bus, cycle_counts, n_apcs, ids, start, end, n_calls, min_log_height, scratch_bytes)
-    tail = (C.byref(out), C.byref(status), C.byref(info))
-    rc = lib.pw_apc_sources_from_traces(*head, *tail) if flags is None else lib.pw_apc_sources_from_traces_flags(*head, int(flags), *tail)
-    return rc, int(status.value), int(info.value), out.value
-
-
-class ApcSources:
+class ApcSources(stage.Handle):
     """`.layout[a]` Layout(n_calls, [(air, occ)]); `.source(a, air)` Source(ptr, width, height, rbs), height 0 where APC a does not
     use the AIR; `.residual(air)` Residual(ptr, rows, log_height) or None for an AIR that takes no part; `.positions`, `.covered`,
     `.source_bytes`, `.residual_bytes`. The device pointers are valid until close(). `.direct`: made by `apply_calls(direct=True)` — no
@@ -144,7 +124,8 @@ class ApcSources:
     APC traces from the chips' traces."""
 
     def __init__(self, handle, widths, direct=False):
-        self._h, self._widths, self.direct = handle, [int(w) for w in widths], bool(direct)
+        super().__init__(handle, lib.pw_apc_sources_destroy)
+        self._widths, self.direct = [int(w) for w in widths], bool(direct)
         self.index_bytes = int(lib.pw_apc_sources_index_bytes(handle))
         sizes = (C.c_uint64 * 6)()
         lib.pw_apc_sources_sizes(handle, sizes)
@@ -219,10 +200,7 @@ class ApcSources:
         matrix: out[apc_col * out_height + r] = the cell (instr, col) of call r of the APC, 0 for r >= its calls; columns no cell names
         are not touched. All jobs in one launch (`pw_apc_sources_tracegen`); a direct handle only."""
         recs, keep = trace_jobs(list(jobs))
-        rc = lib.pw_apc_sources_tracegen(self._h, recs, len(keep))
-        if rc == -1:
-            raise ValueError("pw_apc_sources_tracegen: malformed arguments" + ("" if self.direct else " (the handle is not direct)"))
-        abi.check(rc, "pw_apc_sources_tracegen")
+        stage.check(lib.pw_apc_sources_tracegen(self._h, recs, len(keep)), "pw_apc_sources_tracegen", "" if self.direct else " (the handle is not direct)")
 
     def residual_segment(self, seg) -> list:
         """seg with the AIRs that took part replaced by their residuals: the AIR list `prove_segment` and `check_segment_buses` take"""
@@ -232,20 +210,6 @@ class ApcSources:
             r = self.residual(air)
             out.append((pr, ptr, lh) if r is None else (pr, r.ptr, r.log_height))
         return out
-
-    def close(self) -> None:
-        if self._h is not None:
-            lib.pw_apc_sources_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def apply_calls(seg, calls, apcs, segments=None, bus: int = BUS_EXEC, min_log_height: int = 0, scratch_bytes: int = 0, direct: bool = False) -> ApcSources:
@@ -257,17 +221,12 @@ def apply_calls(seg, calls, apcs, segments=None, bus: int = BUS_EXEC, min_log_he
         calls = calls.calls
     calls = [ApcCall(*c) for c in calls]
     cycles = [int(a.cycle_count if isinstance(a, Apc) else a[1] if isinstance(a, (tuple, list)) else a) for a in apcs]
-    recs, numbers = segment_records(seg, segments)
+    recs, numbers = stage.air_records(seg, segments)
     n, m = len(calls), len(cycles)
     t_cycles = (C.c_uint32 * max(m, 1))(*cycles)
     t_ids = (C.c_uint32 * max(n, 1))(*[int(c.apc_id) for c in calls])
     t_from = (C.c_uint64 * max(n, 1))(*[int(c.start) for c in calls])
     t_to = (C.c_uint64 * max(n, 1))(*[int(c.end) for c in calls])
-    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), t_cycles, m, t_ids, t_from, t_to, n, int(min_log_height), int(scratch_bytes),
-                                               DIRECT if direct else None)
-    if rc == -1:
-        raise ValueError("pw_apc_sources_from_traces: malformed arguments")
-    abi.check(rc, "pw_apc_sources_from_traces")
-    if status:
-        raise ApcSourcesError(status, info)
-    return ApcSources(handle, [pr.width for pr, _, _ in seg], direct=direct)
+    head = (recs, numbers, len(seg), int(bus), t_cycles, m, t_ids, t_from, t_to, n, int(min_log_height), int(scratch_bytes))
+    fn, args = (lib.pw_apc_sources_from_traces_flags, (*head, DIRECT)) if direct else (lib.pw_apc_sources_from_traces, head)
+    return ApcSources(stage.call(fn, "pw_apc_sources_from_traces", *args, error=ApcSourcesError), [pr.width for pr, _, _ in seg], direct=direct)

@@ -22,7 +22,7 @@
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
 #include "register_states.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -625,20 +625,18 @@ extern "C" int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t
                                         size_t n_apcs, const PwApcConstraint* constraints, size_t n_constraints, size_t scratch_bytes, PwApcCalls** out,
                                         uint32_t* status, uint64_t* info) {
     HostTables h;
-    if (!out || !status || !info || bus >= bb::P || (!airs && n_airs)) return -1;
-    if (segment_of_air)
-        for (size_t a = 1; a < n_airs; ++a)
-            if (segment_of_air[a] != segment_of_air[0]) return -1;  // candidates end with their segment: one segment per call
-    if (!airs_well_formed(airs, n_airs) || !check_tables(apcs, n_apcs, constraints, n_constraints, 0, 8, h)) return -1;
-    const long long rows = time_index::bridge_rows(airs, n_airs, bus);
-    if (rows < 0 || ((u64)rows + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32)) return -1;
-    const u64 M = (u64)rows;
+    time_index::Bridge B;
+    if (!out || !status || !info || bus >= bb::P || !time_index::one_segment(segment_of_air, n_airs) || !airs_well_formed(airs, n_airs) ||
+        !check_tables(apcs, n_apcs, constraints, n_constraints, 0, 8, h) || !time_index::bridge_of(airs, n_airs, bus, &B) ||
+        (B.M + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32))
+        return -1;
+    const u64 M = B.M;
     AcCtx& cx = g_ac;
     const ScratchCall call(cx, out, status, info);
     hipStream_t st = stream();
     const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; the sorted keys and the states stay through the selection
-    const size_t index_need = 64 + (size_t)M * 32 + (M ? time_index::sort_pairs_temp(M) : 0), extra = 64 + (size_t)M * 8 + (size_t)(M + 1) * 4;
+    const size_t index_need = time_index::bytes_needed(M), extra = 64 + (size_t)M * 8 + (size_t)(M + 1) * 4;
     {
         const size_t need = std::max(index_need + (size_t)(M + 1) * 4, calls_need(M + 1, (M + 1) * h.max_share, h.bytes()) + extra);
         if (bound < need) {
@@ -648,15 +646,9 @@ extern "C" int pw_apc_calls_from_traces(const PwSegmentAir* airs, const uint32_t
         }
     }
     u64 N = 0;
-    if (M) {
-        std::vector<Part> parts;
-        PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
-        u64 counters[8];
-        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
-                                              time_index::Names{"apc_calls_index_kernel", "apc_calls_sort_time", "apc_calls_time_kernel"}, counters, status, info));
-        if (*status) return (int)hipGetLastError();
-        N = counters[0];
-    }
+    PW_TRY(time_index::open(airs, segment_of_air, n_airs, bus, B, cx.index, cx.temp, time_index::Names{"apc_calls_index_kernel", "apc_calls_sort_time", "apc_calls_time_kernel"},
+                            &N, status, info));
+    if (*status) return (int)hipGetLastError();
     // the states: the N pcs in time order and the pc after the last row
     PW_TRY(cx.states.ensure((N + 1) * 4));
     if (N) PW_HIP_TRY(hipMemcpyAsync(cx.states.p, cx.index.pc_t.p, N * 4, hipMemcpyDeviceToDevice, st));
@@ -681,10 +673,12 @@ extern "C" int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, cons
     namespace rs = register_states;
     HostTables h;
     const rs::Args a{airs, segment_of_air, n_airs, bridge_bus, memory_bus, final_pc, reg_as, reg_ptr_step};
-    u64 M = 0, slots = 0;
-    if (!out || !status || !info || !check_tables(apcs, n_apcs, constraints, n_constraints, n_regs, limb_bits, h) || !rs::args_ok(a, &M, &slots) ||
-        (M + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32))
+    time_index::Bridge B;
+    u64 slots = 0;
+    if (!out || !status || !info || !check_tables(apcs, n_apcs, constraints, n_constraints, n_regs, limb_bits, h) || !rs::args_ok(a, &B, &slots) ||
+        (B.M + 1) * std::max<u64>(h.max_share, 1) >= ((u64)1 << 32))
         return -1;
+    const u64 M = B.M;
     std::vector<uint32_t> regs;
     for (const ConDev& q : h.cons)
         for (const OpDev* o : {&q.l, &q.r})
@@ -713,7 +707,7 @@ extern "C" int pw_apc_calls_from_traces_registers(const PwSegmentAir* airs, cons
         }
     }
     u64 N = 0;
-    PW_TRY(rs::states_from_traces(a, regs, initial_regs ? initial.data() : nullptr, M, slots, cx.stage, cx.states, cx.regtab, cx.tkeys, &N, status, info));
+    PW_TRY(rs::states_from_traces(a, regs, initial_regs ? initial.data() : nullptr, B, slots, cx.stage, cx.states, cx.regtab, cx.tkeys, &N, status, info));
     if (*status) return (int)hipGetLastError();
     auto result = empty_result(n_apcs, N + 1);
     result->time_keys.resize(N);

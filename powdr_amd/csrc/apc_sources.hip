@@ -30,7 +30,7 @@
 //                                           over the group's cells; stores and loads as in the gather. Only the named columns are written.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -314,24 +314,6 @@ int gather(AsCtx& cx, const PwGatherJob* jobs, size_t n_jobs) {
     return 0;
 }
 
-// a host image of device tables, every piece 16-byte aligned
-struct Image {
-    std::vector<char> bytes;
-    template <class T>
-    size_t put(const std::vector<T>& v) {
-        const size_t at = (bytes.size() + 15) & ~(size_t)15;
-        bytes.resize(at + v.size() * sizeof(T));
-        if (!v.empty()) memcpy(bytes.data() + at, v.data(), v.size() * sizeof(T));
-        return at;
-    }
-    int upload(Scratch::Buf& b, hipStream_t st) {
-        bytes.resize(bytes.size() + 16);
-        PW_TRY(b.ensure(bytes.size()));
-        PW_HIP_TRY(hipMemcpyAsync(b.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-};
-
 // matrices laid out in one allocation, each 256-byte aligned
 size_t place_matrix(size_t& total, size_t words) {
     const size_t at = (total + 255) & ~(size_t)255;
@@ -540,21 +522,12 @@ extern "C" int pw_trace_gather_rows(const PwGatherJob* jobs, size_t n_jobs) {
 extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus, const uint32_t* cycle_counts,
                                                 size_t n_apcs, const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to, size_t n_calls,
                                                 uint32_t min_log_height, size_t scratch_bytes, uint32_t flags, PwApcSources** out, uint32_t* status, uint64_t* info) {
-    if ((flags & ~PW_APC_SOURCES_DIRECT) || !out || !status || !info || bridge_bus >= bb::P || (!airs && n_airs) || (!cycle_counts && n_apcs) || ((!call_apc_ids || !call_from || !call_to) && n_calls) ||
-        min_log_height > 31u || n_apcs >= ((size_t)1 << 31) || n_calls >= ((size_t)1 << 31))
+    if ((flags & ~PW_APC_SOURCES_DIRECT) || !out || !status || !info || bridge_bus >= bb::P || min_log_height > 31u || !time_index::one_segment(segment_of_air, n_airs) ||
+        !time_index::calls_well_formed(cycle_counts, n_apcs, call_apc_ids, call_from, call_to, n_calls))
         return -1;
-    if (segment_of_air)
-        for (size_t a = 1; a < n_airs; ++a)
-            if (segment_of_air[a] != segment_of_air[0]) return -1;
-    for (size_t a = 0; a < n_apcs; ++a)
-        if (!cycle_counts[a]) return -1;
-    for (size_t j = 0; j < n_calls; ++j)
-        if (call_apc_ids[j] >= n_apcs || call_to[j] < call_from[j] || call_to[j] - call_from[j] != cycle_counts[call_apc_ids[j]] || (j && call_from[j] < call_to[j - 1]))
-            return -1;
-    if (!airs_well_formed(airs, n_airs)) return -1;
-    const long long rows = time_index::bridge_rows(airs, n_airs, bridge_bus);
-    if (rows < 0 || (u64)rows + 1 >= ((u64)1 << 32)) return -1;
-    const u64 M = (u64)rows, min_h = (u64)1 << min_log_height;
+    time_index::Bridge B;
+    if (!airs_well_formed(airs, n_airs) || !time_index::bridge_of(airs, n_airs, bridge_bus, &B) || B.M + 1 >= ((u64)1 << 32)) return -1;
+    const u64 M = B.M, min_h = (u64)1 << min_log_height;
     const bool direct = (flags & PW_APC_SOURCES_DIRECT) != 0;
     AsCtx& cx = g_as;
     const ScratchCall call(cx, out, status, info);
@@ -576,20 +549,10 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
             n_instr += cycle_counts[a];
         }
 
-    // ---- the AIRs that take part: those with the bridge (host; collect_parts below stages their values) ----
-    std::vector<size_t> part_air;
-    for (size_t a = 0; a < n_airs; ++a) {
-        const PwProver* p = airs[a].prover;
-        if (!p->logup) continue;
-        for (const LogupInteraction& it : p->h_inter)
-            if (bb::from_monty(it.bus_monty) == bridge_bus) {
-                part_air.push_back(a);
-                break;
-            }
-    }
-    const size_t n_parts = part_air.size();
-    std::vector<u64> g0(n_parts + 1, 0);
-    for (size_t k = 0; k < n_parts; ++k) g0[k + 1] = g0[k] + ((u64)1 << airs[part_air[k]].log_height);
+    // ---- the AIRs that take part: those with the bridge ----
+    const std::vector<size_t>& part_air = B.part_air;
+    const std::vector<u64>& g0 = B.g0;
+    const size_t n_parts = B.n_parts();
 
     // ---- status 2: what is known before a row is read ----
     const size_t bound = call.bound(scratch_bytes);
@@ -623,7 +586,7 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
         }
         const size_t n_lists = (n_apcs + 1) * n_parts;
         const size_t tables = 4096 + n_calls * 32 + n_apcs * 32 + n_instr * 8 + n_lists * 32 + job_table_bytes(n_lists) + 256 * (n_lists + 2);
-        const size_t index_need = 64 + (size_t)M * 32 + (M ? time_index::sort_pairs_temp(M) : 0);
+        const size_t index_need = time_index::bytes_needed(M);
         const size_t place_need = 64 + (size_t)M * 17 + (M ? time_index::scan_temp(rocprim::make_transform_iterator((const uint8_t*)nullptr, AsU32{}), M) : 0);
         const size_t need = ((size_t)1 << 20) + tables + std::max(index_need, place_need) + out_bytes + (list_rows + 4 * n_lists) * 4;
         if (bound < need) {
@@ -651,26 +614,13 @@ extern "C" int pw_apc_sources_from_traces_flags(const PwSegmentAir* airs, const 
     // ---- index ----
     hipStream_t st = stream();
     u64 N = 0;
-    if (M) {
-        std::vector<Part> parts;
-        PW_TRY(collect_parts(airs, n_airs, bridge_bus, parts, nullptr));
-        if (parts.size() != n_parts) return (int)hipErrorInvalidValue;  // (cannot happen: the same AIRs by the same rule)
-        u64 counters[8];
-        const std::vector<u64> part_first(g0.begin(), g0.end() - 1);
-        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, &part_first, M, cx.index, nullptr, cx.temp,
-                                              time_index::Names{"apc_sources_index_kernel", "apc_sources_sort_time", "apc_sources_time_kernel"}, counters, status, info));
-        if (*status) return (int)hipGetLastError();
-        N = counters[0];
-        cx.index.release_except({&cx.index.tkey, &cx.index.idx_s});  // the keys say which rows are active, the order places the calls
-        cx.temp.release();
-    }
+    PW_TRY(time_index::open(airs, segment_of_air, n_airs, bridge_bus, B, cx.index, cx.temp,
+                            time_index::Names{"apc_sources_index_kernel", "apc_sources_sort_time", "apc_sources_time_kernel"}, &N, status, info));
+    if (*status) return (int)hipGetLastError();
+    cx.index.release_except({&cx.index.tkey, &cx.index.idx_s});  // the keys say which rows are active, the order places the calls
+    cx.temp.release();
     R.positions = N;
-    for (size_t j = 0; j < n_calls; ++j)
-        if (call_to[j] > N) {
-            *status = 11;
-            *info = j;
-            return 0;
-        }
+    if (!time_index::calls_within(call_to, n_calls, N, status, info)) return 0;
     if (!M) {  // no AIR takes part (and so no call): nothing to build
         *out = result.release();
         return 0;

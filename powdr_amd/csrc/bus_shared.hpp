@@ -190,16 +190,27 @@ inline int stage_values(const PwSegmentAir& a, const uint32_t** out) {
 // an AIR that has interactions on a bus: their run in the prover's bus order and the values its programs read
 struct Part { size_t air; uint32_t begin, end; const uint32_t* vals; };
 
+// THE rule for "this AIR is on `bus`": how many interactions its prover has there (0 = it takes no part). Whatever lists, counts or
+// numbers the AIRs of a bus asks here. *same_arity, where given, is cleared by an interaction on the bus that has not n_args arguments.
+inline uint32_t interactions_on(const PwProver* p, uint32_t bus, uint32_t n_args = 0, bool* same_arity = nullptr) {
+    uint32_t n = 0;
+    if (!p->logup) return 0;
+    for (const LogupInteraction& it : p->h_inter)
+        if (bb::from_monty(it.bus_monty) == bus) {
+            if (same_arity && it.n_args != n_args) *same_arity = false;
+            ++n;
+        }
+    return n;
+}
+
 // the parts of `bus` in AIR order, their values staged, and with `air_tab` the table a kernel that re-evaluates witnesses reads
 inline int collect_parts(const PwSegmentAir* airs, size_t n_airs, uint32_t bus, std::vector<Part>& parts, std::vector<AirDev>* air_tab) {
     if (air_tab) air_tab->assign(n_airs, AirDev{nullptr, 0, LogupProgram{}});
     for (size_t a = 0; a < n_airs; ++a) {
         PwProver* p = airs[a].prover;
-        if (!p->logup || !p->n_inter) continue;
+        if (!interactions_on(p, bus)) continue;
         PW_TRY(ensure_bus_order(p));
-        const auto at = std::lower_bound(p->h_bus_ids.begin(), p->h_bus_ids.end(), bus);
-        if (at == p->h_bus_ids.end() || *at != bus) continue;
-        const size_t k = at - p->h_bus_ids.begin();
+        const size_t k = std::lower_bound(p->h_bus_ids.begin(), p->h_bus_ids.end(), bus) - p->h_bus_ids.begin();  // (there: the order lists every bus)
         Part part{a, p->h_bus_starts[k], p->h_bus_starts[k + 1], nullptr};
         PW_TRY(stage_values(airs[a], &part.vals));
         if (air_tab) (*air_tab)[a] = AirDev{part.vals, (u64)1 << airs[a].log_height, program_of(p)};

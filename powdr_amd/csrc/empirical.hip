@@ -19,7 +19,7 @@
 // the default scratch bound.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -303,10 +303,9 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
                                    size_t n_blocks, size_t scratch_bytes, PwEmpirical** out, uint32_t* status, uint64_t* info) {
     if (!out || !status || !info || !pc_step || bus >= bb::P || !airs_well_formed(airs, n_airs)) return -1;
     if (!blocks_well_formed(blocks, n_blocks, pc_step)) return -1;
-    const long long rows = bridge_rows(airs, n_airs, bus);
-    if (rows < 0) return -1;
-    const u64 M = (u64)rows;
-    if (M >= ((u64)1 << 32)) return -1;  // row numbers and run positions are 32-bit words
+    Bridge B;
+    if (!bridge_of(airs, n_airs, bus, &B) || B.M >= ((u64)1 << 32)) return -1;  // row numbers and run positions are 32-bit words
+    const u64 M = B.M;
     EmpCtx& cx = g_emp;
     const ScratchCall call(cx, out, status, info);
     auto result = std::make_unique<PwEmpirical>();
@@ -319,24 +318,17 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     }
     hipStream_t st = stream();
 
-    std::vector<Part> parts;
     std::vector<EPart> h_parts;
     std::vector<EAir> h_airs(n_airs, EAir{nullptr, 0, 0, 0});
-    PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
     for (size_t a = 0; a < n_airs; ++a) h_airs[a] = EAir{airs[a].d_trace, (u64)1 << airs[a].log_height, airs[a].prover->width, 0};
-    {
-        u64 g0 = 0;  // the parts' rows numbered through
-        for (const Part& part : parts) {
-            h_parts.push_back(EPart{g0, (uint32_t)part.air, 0});
-            g0 += (u64)1 << airs[part.air].log_height;
-        }
+    uint32_t max_width = 0;
+    for (size_t k = 0; k < B.n_parts(); ++k) {
+        h_parts.push_back(EPart{B.g0[k], (uint32_t)B.part_air[k], 0});
+        max_width = std::max(max_width, airs[B.part_air[k]].prover->width);
     }
 
-    uint32_t max_width = 0;
-    for (const Part& part : parts) max_width = std::max(max_width, airs[part.air].prover->width);
-
     // small: counters (8 u64) | AIR table | part table | block table
-    const size_t off_air = 64, off_part = off_air + n_airs * sizeof(EAir), off_blocks = off_part + parts.size() * sizeof(EPart),
+    const size_t off_air = 64, off_part = off_air + n_airs * sizeof(EAir), off_blocks = off_part + h_parts.size() * sizeof(EPart),
                  small_bytes = off_blocks + std::max<size_t>(n_blocks, 1) * sizeof(PwBasicBlock);
     PW_TRY(cx.small.ensure(small_bytes));
     char* base = cx.small.as<char>();
@@ -348,7 +340,7 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     // the bound: the caller's, or half of what the device has room for
     const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; one column of a panel 16 bytes per active row (at most M)
-    const size_t index_need = small_bytes + (size_t)M * 32 + sort_pairs_temp(M);
+    const size_t index_need = small_bytes - 64 + bytes_needed(M);  // (its 64 bytes of counters lie in `small`)
     auto panel_need = [&](u64 N, uint32_t C, u64 n_runs, u64 n_cells) {
         // row locations, counts, runs | per run | ranges, fingerprints, the verification's pairs and items | the panel and its sort
         return small_bytes + (size_t)N * 16 + (size_t)n_runs * 16 + 64 + (size_t)n_cells * 56 + (size_t)N * max_width / 128 * 8 + (size_t)N * C * 16 +
@@ -365,15 +357,10 @@ extern "C" int pw_empirical_detect(const PwSegmentAir* airs, const uint32_t* seg
     if (n_blocks) PW_HIP_TRY(hipMemcpyAsync((void*)d_blocks, blocks, n_blocks * sizeof(PwBasicBlock), hipMemcpyHostToDevice, st));
 
     // ---- index (time_index.hpp) ----
-    u64 counters[8];
-    {
-        std::vector<u64> g0;
-        for (const EPart& part : h_parts) g0.push_back(part.g0);
-        PW_TRY(rows_in_time_order(airs, segment_of_air, parts, &g0, M, cx.index, d_counters, cx.temp,
-                                  Names{"empirical_index_kernel", "empirical_sort_time", "empirical_structure_kernel"}, counters, status, info));
-        if (*status) return (int)hipGetLastError();
-    }
-    const u64 N = counters[0];
+    u64 counters[8], N = 0;
+    PW_TRY(open(airs, segment_of_air, n_airs, bus, B, cx.index, cx.temp, Names{"empirical_index_kernel", "empirical_sort_time", "empirical_structure_kernel"}, &N, status, info,
+                d_counters, counters));
+    if (*status) return (int)hipGetLastError();
     cx.stat_rows = N;
     if (!N) {
         *out = result.release();

@@ -22,7 +22,7 @@
 //              marks the chain from coarse to fine and overwrites the chosen windows with a block no needle has
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -732,9 +732,9 @@ extern "C" int pw_execution_blocks_from_traces(const PwSegmentAir* airs, const u
     if (!out || !status || !info || !pc_step || !max_bb || max_bb > 255u || bus >= bb::P || !airs_well_formed(airs, n_airs) ||
         !time_index::blocks_well_formed(blocks, n_blocks, pc_step))
         return -1;
-    const long long rows = time_index::bridge_rows(airs, n_airs, bus);
-    if (rows < 0 || (u64)rows >= ((u64)1 << 32)) return -1;
-    const u64 M = (u64)rows;
+    time_index::Bridge B;
+    if (!time_index::bridge_of(airs, n_airs, bus, &B) || B.M >= ((u64)1 << 32)) return -1;
+    const u64 M = B.M;
     EbCtx& cx = g_eb;
     const ScratchCall call(cx, out, status, info);
     auto result = empty_result(blocks, n_blocks);
@@ -742,22 +742,18 @@ extern "C" int pw_execution_blocks_from_traces(const PwSegmentAir* airs, const u
         *out = result.release();
         return 0;
     }
-    std::vector<Part> parts;
-    PW_TRY(collect_parts(airs, n_airs, bus, parts, nullptr));
     const size_t bound = call.bound(scratch_bytes);
     // the index stage holds 32 bytes per row and a sort's temporary storage; the sorted keys and pcs stay through the heads stage
-    const size_t index_need = 64 + (size_t)M * 32 + time_index::sort_pairs_temp(M), extra = 64 + (size_t)M * 12;
+    const size_t index_need = time_index::bytes_needed(M), extra = 64 + (size_t)M * 12;
     if (bound < index_need) {
         *status = 2;
         *info = std::max({index_need, heads_need(M) + extra, levels_need(M)});  // (what is known before a row is read)
         return 0;
     }
-    u64 counters[8];
-    PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
-                                          time_index::Names{"execution_blocks_index_kernel", "execution_blocks_sort_time", "execution_blocks_time_kernel"}, counters,
-                                          status, info));
+    u64 N = 0;
+    PW_TRY(time_index::open(airs, segment_of_air, n_airs, bus, B, cx.index, cx.temp,
+                            time_index::Names{"execution_blocks_index_kernel", "execution_blocks_sort_time", "execution_blocks_time_kernel"}, &N, status, info));
     if (*status) return (int)hipGetLastError();
-    const u64 N = counters[0];
     if (!N) {
         *out = result.release();
         return (int)hipGetLastError();

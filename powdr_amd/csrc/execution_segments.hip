@@ -21,7 +21,7 @@
 // Nothing depends on an order of arrival: every output word has one writer, and the sort is stable.
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -285,24 +285,6 @@ size_t sort_class_temp(size_t n, unsigned bits) {
     return std::max<size_t>(bytes, 16);
 }
 
-// a host image of device tables, every piece 16-byte aligned
-struct Image {
-    std::vector<char> bytes;
-    template <class T>
-    size_t put(const std::vector<T>& v) {
-        const size_t at = (bytes.size() + 15) & ~(size_t)15;
-        bytes.resize(at + v.size() * sizeof(T));
-        if (!v.empty()) memcpy(bytes.data() + at, v.data(), v.size() * sizeof(T));
-        return at;
-    }
-    int upload(Scratch::Buf& b, hipStream_t st) {
-        bytes.resize(bytes.size() + 16);
-        PW_TRY(b.ensure(bytes.size()));
-        PW_HIP_TRY(hipMemcpyAsync(b.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-};
-
 }  // namespace
 
 }  // namespace pw
@@ -389,42 +371,23 @@ extern "C" int pw_execution_segments_from_traces(const PwSegmentAir* airs, const
                                                  const uint32_t* cycle_counts, const uint32_t* apc_widths, size_t n_apcs, const uint32_t* call_apc_ids,
                                                  const uint64_t* call_from, const uint64_t* call_to, size_t n_calls, const PwSegmentLimits* limits, size_t scratch_bytes,
                                                  PwExecutionSegments** out, uint32_t* status, uint64_t* info) {
-    if (!out || !status || !info || !limits || bridge_bus >= bb::P || (!airs && n_airs) || (!cycle_counts && n_apcs) || ((!call_apc_ids || !call_from || !call_to) && n_calls) ||
-        limits->max_log_height > 31u || limits->min_log_height > limits->max_log_height || n_apcs >= ((size_t)1 << 31) || n_calls >= ((size_t)1 << 31))
+    if (!out || !status || !info || !limits || bridge_bus >= bb::P || limits->max_log_height > 31u || limits->min_log_height > limits->max_log_height ||
+        !time_index::one_segment(segment_of_air, n_airs) || !time_index::calls_well_formed(cycle_counts, n_apcs, call_apc_ids, call_from, call_to, n_calls))
         return -1;
-    if (segment_of_air)
-        for (size_t a = 1; a < n_airs; ++a)
-            if (segment_of_air[a] != segment_of_air[0]) return -1;
     if (limits->max_cells && n_apcs && !apc_widths) return -1;
     for (size_t a = 0; a < n_apcs; ++a)
-        if (!cycle_counts[a] || (limits->max_cells && !apc_widths[a])) return -1;
-    for (size_t j = 0; j < n_calls; ++j)
-        if (call_apc_ids[j] >= n_apcs || call_to[j] < call_from[j] || call_to[j] - call_from[j] != cycle_counts[call_apc_ids[j]] || (j && call_from[j] < call_to[j - 1]))
-            return -1;
-    if (!airs_well_formed(airs, n_airs)) return -1;
-    const long long bridge = time_index::bridge_rows(airs, n_airs, bridge_bus);
-    if (bridge < 0 || (u64)bridge + 1 >= ((u64)1 << 32)) return -1;
-    const u64 M = (u64)bridge, min_h = (u64)1 << limits->min_log_height, cap = (u64)1 << limits->max_log_height;
+        if (limits->max_cells && !apc_widths[a]) return -1;
+    time_index::Bridge B;
+    if (!airs_well_formed(airs, n_airs) || !time_index::bridge_of(airs, n_airs, bridge_bus, &B) || B.M + 1 >= ((u64)1 << 32)) return -1;
+    const u64 M = B.M, min_h = (u64)1 << limits->min_log_height, cap = (u64)1 << limits->max_log_height;
     const u64 max_segments = limits->max_segments ? limits->max_segments : kDefaultMaxSegments;
     EsCtx& cx = g_es;
     const ScratchCall call(cx, out, status, info);
 
     // ---- the AIRs that take part: those with the bridge; the calls per APC (host) ----
-    std::vector<size_t> part_air;
-    std::vector<int64_t> part_of_air(n_airs, -1);
-    for (size_t a = 0; a < n_airs; ++a) {
-        const PwProver* p = airs[a].prover;
-        if (!p->logup) continue;
-        for (const LogupInteraction& it : p->h_inter)
-            if (bb::from_monty(it.bus_monty) == bridge_bus) {
-                part_of_air[a] = (int64_t)part_air.size();
-                part_air.push_back(a);
-                break;
-            }
-    }
-    const size_t n_parts = part_air.size(), n_classes = n_parts + n_apcs;
-    std::vector<u64> g0(n_parts + 1, 0);
-    for (size_t k = 0; k < n_parts; ++k) g0[k + 1] = g0[k] + ((u64)1 << airs[part_air[k]].log_height);
+    const std::vector<size_t>& part_air = B.part_air;
+    const std::vector<u64>& g0 = B.g0;
+    const size_t n_parts = B.n_parts(), n_classes = n_parts + n_apcs;
     std::vector<u64> astart(n_apcs + 1, 0);  // the APC's first entry among the call starts grouped by APC
     u64 n_covered = 0;
     for (size_t j = 0; j < n_calls; ++j) {
@@ -443,7 +406,7 @@ extern "C" int pw_execution_segments_from_traces(const PwSegmentAir* airs, const
         const size_t list_bytes = (size_t)(2 * M + n_lists * std::max<u64>(min_h, 4)) * 4 + 16;
         const size_t tables = 4096 + n_calls * 24 + (n_apcs + 1) * 8 + n_classes * 40 + (n_parts + 2) * 32;
         const size_t per_segment = (size_t)(seg_cap + 1) * (8 + 12 + n_parts * 16) + std::min<size_t>(kHeightChunk + n_classes, (size_t)(seg_cap + 1) * n_classes) * 4;
-        const size_t index_need = 64 + (size_t)M * 32 + (M ? time_index::sort_pairs_temp(M) : 0);
+        const size_t index_need = time_index::bytes_needed(M);
         const size_t class_need = 64 + (size_t)M * 32 + n_calls * 4 + (M ? sort_class_temp(M, key_bits) : 0);
         const size_t need = ((size_t)1 << 20) + tables + std::max(index_need, class_need) + per_segment + list_bytes;
         if (call.bound(scratch_bytes) < need) {
@@ -459,34 +422,20 @@ extern "C" int pw_execution_segments_from_traces(const PwSegmentAir* airs, const
     R.n_apcs = n_apcs;
     R.n_parts = n_parts;
     R.covered = n_covered;
-    R.part_of_air = part_of_air;
+    R.part_of_air = B.part_of_air;
     R.min_log_height = limits->min_log_height;
     cx.stat_classes = n_airs + n_apcs;
 
     // ---- index ----
     hipStream_t st = stream();
     u64 N = 0;
-    if (M) {
-        std::vector<Part> parts;
-        PW_TRY(collect_parts(airs, n_airs, bridge_bus, parts, nullptr));
-        if (parts.size() != n_parts) return (int)hipErrorInvalidValue;  // (cannot happen: the same AIRs by the same rule)
-        u64 counters[8];
-        const std::vector<u64> part_first(g0.begin(), g0.end() - 1);
-        PW_TRY(time_index::rows_in_time_order(airs, segment_of_air, parts, &part_first, M, cx.index, nullptr, cx.temp,
-                                              time_index::Names{"execution_segments_index_kernel", "execution_segments_sort_time", "execution_segments_time_kernel"},
-                                              counters, status, info));
-        if (*status) return (int)hipGetLastError();
-        N = counters[0];
-        cx.index.release_except({&cx.index.tkey_s, &cx.index.idx_s, &cx.index.pc_t});
-        cx.temp.release();
-    }
+    PW_TRY(time_index::open(airs, segment_of_air, n_airs, bridge_bus, B, cx.index, cx.temp,
+                            time_index::Names{"execution_segments_index_kernel", "execution_segments_sort_time", "execution_segments_time_kernel"}, &N, status, info));
+    if (*status) return (int)hipGetLastError();
+    cx.index.release_except({&cx.index.tkey_s, &cx.index.idx_s, &cx.index.pc_t});
+    cx.temp.release();
     R.positions = N;
-    for (size_t j = 0; j < n_calls; ++j)
-        if (call_to[j] > N) {
-            *status = 11;
-            *info = j;
-            return 0;
-        }
+    if (!time_index::calls_within(call_to, n_calls, N, status, info)) return 0;
     R.bounds.assign(1, 0);
     R.pcs.assign(1, final_pc);
     R.first_call.assign(1, n_calls);

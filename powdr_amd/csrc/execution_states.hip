@@ -66,12 +66,13 @@ extern "C" int pw_execution_states_from_traces(const PwSegmentAir* airs, const u
                                                uint32_t final_pc, uint32_t reg_as, uint32_t reg_ptr_step, const uint32_t* regs, size_t n_regs,
                                                const uint32_t* initial_regs, size_t scratch_bytes, PwExecutionStates** out, uint32_t* status, uint64_t* info) {
     const rs::Args a{airs, segment_of_air, n_airs, bridge_bus, memory_bus, final_pc, reg_as, reg_ptr_step};
-    u64 M = 0, slots = 0;
-    if (!out || !status || !info || !rs::registers_ok(regs, n_regs, reg_ptr_step ? reg_ptr_step : 1u) || !rs::args_ok(a, &M, &slots)) return -1;
+    time_index::Bridge B;
+    u64 slots = 0;
+    if (!out || !status || !info || !rs::registers_ok(regs, n_regs, reg_ptr_step ? reg_ptr_step : 1u) || !rs::args_ok(a, &B, &slots)) return -1;
     rs::Ctx& cx = g_es;
     const ScratchCall call(cx, out, status, info);
     const size_t bound = call.bound(scratch_bytes);
-    const size_t need = rs::bytes_needed(M, slots, n_regs);
+    const size_t need = rs::bytes_needed(B.M, slots, n_regs);
     if (bound < need) {
         *status = 2;
         *info = need;  // (what is known before a row is read: every row may be active, every interaction a send)
@@ -79,7 +80,7 @@ extern "C" int pw_execution_states_from_traces(const PwSegmentAir* airs, const u
     }
     auto result = std::make_unique<PwExecutionStates>();
     u64 N = 0;
-    const int rc = rs::states_from_traces(a, std::vector<uint32_t>(regs, regs + n_regs), initial_regs, M, slots, cx, result->pcs, result->regs, result->keys, &N, status,
+    const int rc = rs::states_from_traces(a, std::vector<uint32_t>(regs, regs + n_regs), initial_regs, B, slots, cx, result->pcs, result->regs, result->keys, &N, status,
                                           info);
     if (rc || *status) return rc;
     result->n_states = N + 1;

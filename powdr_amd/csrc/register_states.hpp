@@ -18,7 +18,7 @@
 #pragma once
 #include "bus_shared.hpp"
 #include "prover_internal.hpp"
-#include "time_index.hpp"
+#include "trace_entry.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -241,28 +241,16 @@ struct Args {
 };
 
 // false = -1: a NULL AIR list, a bus id >= p, reg_ptr_step == 0, two segment numbers, a malformed AIR list, an interaction on the
-// bridge with an arity other than 2 or on the memory bus with one other than 7. *M = the bridge's rows, *slots = the interactions
-// on the memory bus times their AIRs' rows: no walk appends more sends.
-inline bool args_ok(const Args& a, u64* M, u64* slots) {
-    if ((!a.airs && a.n_airs) || a.bridge_bus >= bb::P || a.memory_bus >= bb::P || !a.ptr_step) return false;
-    if (a.segment_of_air)
-        for (size_t k = 1; k < a.n_airs; ++k)
-            if (a.segment_of_air[k] != a.segment_of_air[0]) return false;
-    if (!airs_well_formed(a.airs, a.n_airs)) return false;
-    const long long rows = time_index::bridge_rows(a.airs, a.n_airs, a.bridge_bus);
-    if (rows < 0 || (u64)rows + 1 >= ((u64)1 << 32)) return false;
-    *M = (u64)rows;
+// bridge with an arity other than 2 or on the memory bus with one other than 7. *B = the bridge's AIRs and rows, *slots = the
+// interactions on the memory bus times their AIRs' rows: no walk appends more sends.
+inline bool args_ok(const Args& a, time_index::Bridge* B, u64* slots) {
+    if (a.bridge_bus >= bb::P || a.memory_bus >= bb::P || !a.ptr_step || !time_index::one_segment(a.segment_of_air, a.n_airs) || !airs_well_formed(a.airs, a.n_airs) ||
+        !time_index::bridge_of(a.airs, a.n_airs, a.bridge_bus, B) || B->M + 1 >= ((u64)1 << 32))
+        return false;
+    bool seven_args = true;
     *slots = 0;
-    for (size_t k = 0; k < a.n_airs; ++k) {
-        const PwProver* p = a.airs[k].prover;
-        if (!p->logup) continue;
-        for (const LogupInteraction& it : p->h_inter)
-            if (bb::from_monty(it.bus_monty) == a.memory_bus) {
-                if (it.n_args != kMemoryArgs) return false;
-                *slots += (u64)1 << a.airs[k].log_height;
-            }
-    }
-    return *slots < ((u64)1 << 32);
+    for (size_t k = 0; k < a.n_airs; ++k) *slots += (u64)interactions_on(a.airs[k].prover, a.memory_bus, kMemoryArgs, &seven_args) << a.airs[k].log_height;
+    return seven_args && *slots < ((u64)1 << 32);
 }
 
 // false = -1: a NULL list, more than kMaxRows rows, a register whose pointer is no field element, one register twice
@@ -294,26 +282,20 @@ inline size_t bytes_needed(u64 M, u64 slots, u64 n_rows) {
     return 4096 + (size_t)(M + 1) * 4 * (n_rows + 1) + (size_t)M * 8 + (size_t)M * 32 + (size_t)slots * 64 + temp + (size_t)n_rows * 32;
 }
 
-// The states of the traces into pcs[N + 1], table[n_rows x (N + 1)] (row k = register regs[k]) and keys[N]; *N_out = N. M, slots: of
+// The states of the traces into pcs[N + 1], table[n_rows x (N + 1)] (row k = register regs[k]) and keys[N]; *N_out = N. B, slots: of
 // args_ok. initial: NULL or one word per row. *status = 7, 4, 8, 9 or 10 with *info where there are none; then nothing is valid.
 // The three arrays are Scratch::Buf of the caller's context, or the plain DeviceBuf of a handle under construction, whose bytes are
 // then the scratch's `extra`. The caller releases cx.
 template <class Out>
-inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, const uint32_t* initial, u64 M, u64 slots, Ctx& cx, Out& pcs, Out& table, Out& keys,
+inline int states_from_traces(const Args& a, const std::vector<uint32_t>& regs, const uint32_t* initial, const time_index::Bridge& B, u64 slots, Ctx& cx, Out& pcs, Out& table, Out& keys,
                               u64* N_out, uint32_t* status, uint64_t* info) {
     hipStream_t st = stream();
     const uint32_t n_rows = (uint32_t)regs.size();
     cx.sends = cx.kept = 0;
     u64 N = 0;
-    if (M) {
-        std::vector<Part> parts;
-        PW_TRY(collect_parts(a.airs, a.n_airs, a.bridge_bus, parts, nullptr));
-        u64 counters[8];
-        PW_TRY(time_index::rows_in_time_order(a.airs, a.segment_of_air, parts, nullptr, M, cx.index, nullptr, cx.temp,
-                                              time_index::Names{"execution_states_index", "execution_states_sort_time", "execution_states_time"}, counters, status, info));
-        if (*status) return (int)hipGetLastError();
-        N = counters[0];
-    }
+    PW_TRY(time_index::open(a.airs, a.segment_of_air, a.n_airs, a.bridge_bus, B, cx.index, cx.temp,
+                            time_index::Names{"execution_states_index", "execution_states_sort_time", "execution_states_time"}, &N, status, info));
+    if (*status) return (int)hipGetLastError();
     *N_out = N;
     const u64 n_states = N + 1;
     PW_TRY(pcs.ensure(n_states * 4));

@@ -8,10 +8,12 @@
 //   ScratchCall    the guard of one entry-point call: a fresh peak and fresh statistics, the sticky HIP error cleared, everything
 //                  released on every exit; bound() = the caller's scratch bound, or by default half of what the device has room for.
 //   with_temp      a rocPRIM call, asked for its temporary storage and then run.
+//   Image          a host image of small device tables, uploaded into a Buf in one copy.
 // Not part of the C ABI.
 #pragma once
 #include "bus_shared.hpp"
 
+#include <cstring>
 #include <initializer_list>
 
 namespace pw {
@@ -122,5 +124,23 @@ inline int with_temp(Scratch::Buf& temp, F f) {
     PW_HIP_TRY(f(temp.p, bytes));
     return 0;
 }
+
+// a host image of device tables, every piece 16-byte aligned
+struct Image {
+    std::vector<char> bytes;
+    template <class T>
+    size_t put(const std::vector<T>& v) {
+        const size_t at = (bytes.size() + 15) & ~(size_t)15;
+        bytes.resize(at + v.size() * sizeof(T));
+        if (!v.empty()) memcpy(bytes.data() + at, v.data(), v.size() * sizeof(T));
+        return at;
+    }
+    int upload(Scratch::Buf& b, hipStream_t st) {
+        bytes.resize(bytes.size() + 16);
+        PW_TRY(b.ensure(bytes.size()));
+        PW_HIP_TRY(hipMemcpyAsync(b.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
 
 }  // namespace pw

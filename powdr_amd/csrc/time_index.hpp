@@ -122,25 +122,6 @@ inline bool blocks_well_formed(const PwBasicBlock* blocks, size_t n_blocks, uint
     return true;
 }
 
-// the rows of the AIRs that have a two-argument interaction on `bus`, or -1 for an interaction on it with another arity
-inline long long bridge_rows(const PwSegmentAir* airs, size_t n_airs, uint32_t bus) {
-    u64 M = 0;
-    for (size_t a = 0; a < n_airs; ++a) {
-        const PwProver* p = airs[a].prover;
-        if (!p->logup) continue;
-        bool on_bus = false;
-        for (const LogupInteraction& it : p->h_inter)
-            if (bb::from_monty(it.bus_monty) == bus) {
-                if (it.n_args != 2) return -1;
-                on_bus = true;
-            }
-        if (on_bus) {
-            M += (u64)1 << airs[a].log_height;
-        }
-    }
-    return (long long)M;
-}
-
 // The buffers of the stage, part of the scratch of the context that declares it. icount: the 8 device counters, for a caller whose
 // own kernels count in counters[3 ..] as well (counters()).
 struct Stage : Scratch {
@@ -152,23 +133,13 @@ struct Stage : Scratch {
 struct Names { const char *index, *sort, *time; };
 
 // The M rows of `parts` by time key: s.tkey_s / s.idx_s hold the sorted keys and row numbers, s.pc_t the pcs in time order, counters[8]
-// the device counters read back. first_rows[k] = the global number of part k's first row, NULL = the parts' rows numbered through.
+// the device counters read back. g0[k] = the global number of part k's first row (trace_entry.hpp's Bridge numbers them through).
 // d_counters: where the caller keeps its 8 counters, NULL = in the stage's own icount; they start as {0, kEmpty, kEmpty, ...} here.
 // temp: the caller's temporary storage, which its later stages reuse. *status = 7 or 4 with *info where the rows are no execution;
 // then nothing else is valid.
-inline int rows_in_time_order(const PwSegmentAir* airs, const uint32_t* segment_of_air, const std::vector<Part>& parts, const std::vector<u64>* first_rows, u64 M,
+inline int rows_in_time_order(const PwSegmentAir* airs, const uint32_t* segment_of_air, const std::vector<Part>& parts, const std::vector<u64>& g0, u64 M,
                               Stage& s, u64* d_counters, Scratch::Buf& temp, Names names, u64* counters, uint32_t* status, uint64_t* info) {
     hipStream_t st = stream();
-    std::vector<u64> g0;
-    if (first_rows) {
-        g0 = *first_rows;
-    } else {
-        u64 g = 0;
-        for (const Part& part : parts) {
-            g0.push_back(g);
-            g += (u64)1 << airs[part.air].log_height;
-        }
-    }
     if (!d_counters) {
         PW_TRY(s.icount.ensure(64));
         d_counters = s.counters();

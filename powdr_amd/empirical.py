@@ -13,12 +13,11 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 
 lib = abi.lib
 BUS_EXEC = 0
-STATUS = {0: "found", 2: "the scratch bound is too small", 3: "not block-structured", 4: "two rows with one time key", 5: "a pc executed by two AIRs",
-          6: "fingerprint collisions under every seed", 7: "multiplicities on the bus that are no single receive with sends"}
+STATUS = {0: "found", **stage.texts(2, 3, 4, 6, 7), 5: "a pc executed by two AIRs"}
 
 
 class PwBasicBlock(C.Structure):
@@ -49,15 +48,14 @@ lib.pw_empirical_last_stats.restype = None
 lib.pw_empirical_last_stats.argtypes = [_u64p]
 
 
-class EmpiricalError(ValueError):
+class EmpiricalError(stage.StageError):
     """a non-zero status of pw_empirical_detect: `.status`, `.info` (the raw word), the decoded info in the message"""
+    PREFIX, STATUS = "pw_empirical_detect", STATUS
 
-    def __init__(self, status: int, info: int):
-        self.status, self.info = int(status), int(info)
-        what = {2: f"{self.info} bytes needed", 3: f"head at segment {self.info >> 32}, timestamp {self.info & 0xFFFFFFFF}",
-                4: f"segment {self.info >> 32}, timestamp {self.info & 0xFFFFFFFF}", 5: f"pc {self.info:#x}",
-                7: f"air {self.info >> 32}, row {self.info & 0xFFFFFFFF}"}.get(self.status, "")
-        super().__init__(f"pw_empirical_detect: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+    def decode(self) -> str:
+        if self.status == 3:
+            return "head at " + stage.describe(4, self.info)
+        return f"pc {self.info:#x}" if self.status == 5 else super().decode()
 
 
 def _partition_map(classes) -> dict:
@@ -161,32 +159,16 @@ def last_stats() -> dict:
     return dict(zip(("panels", "seeds", "active_rows", "cells_verified", "peak_bytes", "scratch_bytes"), (int(x) for x in out)))
 
 
-def detect_raw(recs, n_airs, segments, bus, pc_step, blocks, n_blocks, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_empirical_detect(recs, segments, n_airs, bus, pc_step, blocks, n_blocks, scratch_bytes, C.byref(out), C.byref(status), C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
 def detect(airs, blocks, segments=None, bus: int = BUS_EXEC, pc_step: int = 4, scratch_bytes: int = 0, column_names=None) -> EmpiricalConstraints:
     """airs: [(Prover, device trace pointer, log_height)] as for check_segment_buses; blocks: [(start_pc, n_instructions)], ascending
     and non-overlapping; segments: one segment number per AIR entry (None: all 0); column_names: {AIR index: [names]} for the debug
     info. A non-zero status raises EmpiricalError."""
-    n = len(airs)
-    recs = (prover.PwSegmentAir * max(n, 1))()
-    for i, (pr, ptr, lh) in enumerate(airs):
-        recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
+    recs, numbers = stage.air_records(airs, segments)
     blk = (PwBasicBlock * max(len(blocks), 1))()
     for i, (start, count) in enumerate(blocks):
         blk[i] = PwBasicBlock(int(start), int(count))
-    seg = None
-    if segments is not None:
-        assert len(segments) == n
-        seg = (C.c_uint32 * max(n, 1))(*[int(s) for s in segments])
-    rc, status, info, handle = detect_raw(recs, n, seg, int(bus), int(pc_step), blk, len(blocks), int(scratch_bytes))
-    abi.check(rc, "pw_empirical_detect")
-    if status:
-        raise EmpiricalError(status, info)
+    handle = stage.call(lib.pw_empirical_detect, "pw_empirical_detect", recs, numbers, len(airs), int(bus), int(pc_step), blk, len(blocks), int(scratch_bytes),
+                        error=EmpiricalError)
     try:
         sizes = (C.c_uint64 * 5)()
         lib.pw_empirical_sizes(handle, sizes)

@@ -11,12 +11,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 from .empirical import BUS_EXEC, PwBasicBlock
 
 lib = abi.lib
-STATUS = {0: "found", 2: "the scratch bound is too small", 3: "not block-structured", 4: "two rows with one time key",
-          6: "fingerprint collisions under every seed", 7: "multiplicities on the bus that are no single receive with sends"}
+STATUS = {0: "found", **stage.texts(2, 3, 4, 6, 7)}
 
 _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _tail = [C.c_uint32, C.POINTER(PwBasicBlock), C.c_size_t, C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p), _u32p, _u64p]
@@ -42,15 +41,18 @@ lib.pw_execution_blocks_last_stats.restype = None
 lib.pw_execution_blocks_last_stats.argtypes = [_u64p]
 
 
-class ExecutionBlocksError(ValueError):
+class ExecutionBlocksError(stage.StageError):
     """a non-zero status of pw_execution_blocks_from_*: `.status`, `.info` (the raw word), the decoded info in the message"""
+    PREFIX, STATUS = "pw_execution_blocks", STATUS
 
     def __init__(self, status: int, info: int, from_traces: bool = False):
-        self.status, self.info = int(status), int(info)
-        key = f"segment {self.info >> 32}, timestamp {self.info & 0xFFFFFFFF}"
-        what = {2: f"{self.info} bytes needed", 3: key if from_traces else f"position {self.info}", 4: key,
-                7: f"air {self.info >> 32}, row {self.info & 0xFFFFFFFF}"}.get(self.status, "")
-        super().__init__(f"pw_execution_blocks: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+        self.from_traces = from_traces
+        super().__init__(status, info)
+
+    def decode(self) -> str:  # the head that fits no block: its time key on the trace route, its position in the pc list
+        if self.status == 3:
+            return stage.describe(4, self.info) if self.from_traces else f"position {self.info}"
+        return super().decode()
 
 
 def set_fingerprint_mask(mask: int) -> None:
@@ -90,26 +92,12 @@ def _block_table(blocks):
     return blk
 
 
-def from_pcs_raw(d_pcs, n, pc_step, blocks, n_blocks, max_bb, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_execution_blocks_from_pcs(d_pcs, n, pc_step, blocks, n_blocks, max_bb, scratch_bytes, C.byref(out), C.byref(status), C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-def from_traces_raw(recs, n_airs, segments, bus, pc_step, blocks, n_blocks, max_bb, scratch_bytes):
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_execution_blocks_from_traces(recs, segments, n_airs, bus, pc_step, blocks, n_blocks, max_bb, scratch_bytes, C.byref(out), C.byref(status),
-                                             C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-class ExecutionBlocks:
+class ExecutionBlocks(stage.Handle):
     """pc_count {pc: occurrences}; execution_bb_runs [(start pcs, count)] and superblock_counts {start pcs: count}, both in the
     reference's map order; the head sequence stays on the device for `count` until `close()`."""
 
     def __init__(self, handle, blocks):
-        self._h = handle
+        super().__init__(handle, lib.pw_execution_blocks_destroy)
         self.n_instructions = {int(s): int(n) for s, n in blocks}
         sizes = (C.c_uint64 * 6)()
         lib.pw_execution_blocks_sizes(handle, sizes)
@@ -146,20 +134,6 @@ class ExecutionBlocks:
         abi.check(lib.pw_execution_blocks_count(self._h, arr, len(needle), int(bool(remove)), C.byref(out)), "pw_execution_blocks_count")
         return int(out.value)
 
-    def close(self) -> None:
-        if self._h is not None:
-            lib.pw_execution_blocks_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
 
 def detect(seg_or_pcs, blocks, max_bb: int = 1, segments=None, bus: int = BUS_EXEC, pc_step: int = 4, scratch_bytes: int = 0) -> ExecutionBlocks:
     """seg_or_pcs: the execution's pcs in order — a CUDA int32 / uint32 torch tensor (read in place) or anything numpy turns into
@@ -168,40 +142,21 @@ def detect(seg_or_pcs, blocks, max_bb: int = 1, segments=None, bus: int = BUS_EX
     A non-zero status raises ExecutionBlocksError."""
     blocks = [(int(s), int(n)) for s, n in blocks]
     blk = _block_table(blocks)
-    traces = isinstance(seg_or_pcs, (list, tuple)) and len(seg_or_pcs) > 0 and isinstance(seg_or_pcs[0], tuple) and hasattr(seg_or_pcs[0][0], "_h")
+    tail = (int(pc_step), blk, len(blocks), int(max_bb), int(scratch_bytes))
+    traces = stage.is_air_list(seg_or_pcs)
     if traces:
-        n = len(seg_or_pcs)
-        recs = (prover.PwSegmentAir * n)()
-        for i, (pr, ptr, lh) in enumerate(seg_or_pcs):
-            recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
-        seg = None
-        if segments is not None:
-            assert len(segments) == n
-            seg = (C.c_uint32 * n)(*[int(s) for s in segments])
-        rc, status, info, handle = from_traces_raw(recs, n, seg, int(bus), int(pc_step), blk, len(blocks), int(max_bb), int(scratch_bytes))
-        what = "pw_execution_blocks_from_traces"
+        recs, numbers = stage.air_records(seg_or_pcs, segments)
+        fn, what, args = lib.pw_execution_blocks_from_traces, "pw_execution_blocks_from_traces", (recs, numbers, len(seg_or_pcs), int(bus))
     else:
-        keep = None
-        if hasattr(seg_or_pcs, "data_ptr"):
-            import torch
+        import torch
 
-            t = seg_or_pcs
-            if not t.is_cuda or t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError("the pcs on the device: a contiguous one-dimensional int32 / uint32 tensor")
-            keep, n = t, t.numel()
+        keep, n = stage.device_words(seg_or_pcs, "the pcs")
+        if keep is seg_or_pcs:
+            if keep.dim() != 1:
+                raise ValueError("the pcs on the device: a one-dimensional tensor")
             torch.cuda.current_stream().synchronize()  # the library reads on its own launch stream
-        else:
-            words = np.ascontiguousarray(np.asarray(seg_or_pcs, dtype=np.uint32).reshape(-1))
-            n = len(words)
-            if n:
-                import torch
-
-                keep = torch.from_numpy(words.view(np.int32)).cuda()
-                torch.cuda.synchronize()
-        d_ptr = keep.data_ptr() if n else None
-        rc, status, info, handle = from_pcs_raw(d_ptr, n, int(pc_step), blk, len(blocks), int(max_bb), int(scratch_bytes))
-        what = "pw_execution_blocks_from_pcs"
-    abi.check(rc, what)
-    if status:
-        raise ExecutionBlocksError(status, info, from_traces=traces)
+        elif n:
+            torch.cuda.synchronize()
+        fn, what, args = lib.pw_execution_blocks_from_pcs, "pw_execution_blocks_from_pcs", (keep.data_ptr() if n else None, n)
+    handle = stage.call(fn, what, *args, *tail, error=lambda status, info: ExecutionBlocksError(status, info, from_traces=traces))
     return ExecutionBlocks(handle, blocks)

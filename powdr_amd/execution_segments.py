@@ -10,16 +10,13 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 from .apc_calls import Apc, ApcCall, ApcCalls
 from .apc_sources import GatherJob, gather_rows
 from .empirical import BUS_EXEC
-from .execution_states import describe, segment_records
 
 lib = abi.lib
-STATUS = {0: "cut", 2: "the scratch bound is too small", 4: "two rows with one time key",
-          7: "multiplicities on the bus that are no single receive with sends", 11: "a call that ends after the execution",
-          13: "nothing fits under max_cells", 14: "more than max_segments segments"}
+STATUS = {0: "cut", **stage.texts(2, 4, 7, 11), 13: "nothing fits under max_cells", 14: "more than max_segments segments"}
 STATS = ("segments", "classes", "cell_probes", "snapped_cuts", "peak_bytes", "scratch_bytes")
 
 
@@ -49,13 +46,12 @@ lib.pw_execution_segments_last_stats.restype = None
 lib.pw_execution_segments_last_stats.argtypes = [_u64p]
 
 
-class ExecutionSegmentsError(ValueError):
+class ExecutionSegmentsError(stage.StageError):
     """a non-zero status of pw_execution_segments_from_traces: `.status`, `.info` (the raw word), the decoded info in the message"""
+    PREFIX, STATUS = "pw_execution_segments", STATUS
 
-    def __init__(self, status: int, info: int):
-        self.status, self.info = int(status), int(info)
-        what = f"position {self.info}" if self.status in (13, 14) else describe(self.status, self.info)
-        super().__init__(f"pw_execution_segments: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+    def decode(self) -> str:
+        return f"position {self.info}" if self.status in (13, 14) else super().decode()
 
 
 def last_stats() -> dict:
@@ -64,22 +60,15 @@ def last_stats() -> dict:
     return dict(zip(STATS, (int(x) for x in out)))
 
 
-def from_traces_raw(recs, n_airs, segments, bus, final_pc, cycle_counts, apc_widths, n_apcs, ids, start, end, n_calls, limits, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_execution_segments_from_traces(recs, segments, n_airs, bus, final_pc, cycle_counts, apc_widths, n_apcs, ids, start, end, n_calls, limits, scratch_bytes,
-                                               C.byref(out), C.byref(status), C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-class ExecutionSegments:
+class ExecutionSegments(stage.Handle):
     """`.bounds` [b_0 .. b_S]; `.starts` [(pc, time key)] per segment; `.final_pc`; `.first_call` [S + 1]; `.heights[s]` {air or
     ("apc", a): rows} (classes without rows left out); `.calls(s)` the segment's ApcCalls re-based to it; `.rows(s, air)` (device
     pointer of the row list, rows, log_height) or None; `.segment(s)` the segment's traces, gathered. `.n_segments`, `.n_airs`,
     `.n_apcs`, `.positions`, `.covered`, `.list_bytes`. The lists are valid until close()."""
 
     def __init__(self, handle, seg, calls):
-        self._h, self._seg, self._calls = handle, list(seg), list(calls)
+        super().__init__(handle, lib.pw_execution_segments_destroy)
+        self._seg, self._calls = list(seg), list(calls)
         sizes = (C.c_uint64 * 6)()
         lib.pw_execution_segments_sizes(handle, sizes)
         self.n_segments, self.n_airs, self.n_apcs, self.positions, self.covered, self.list_bytes = (int(x) for x in sizes)
@@ -145,20 +134,6 @@ class ExecutionSegments:
         gather_rows(jobs)
         return out
 
-    def close(self) -> None:
-        if self._h is not None:
-            lib.pw_execution_segments_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
 
 def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widths=None, min_log_height: int = 0, max_cells: int = 0, max_segments: int = 0,
         segments=None, bus: int = BUS_EXEC, scratch_bytes: int = 0) -> ExecutionSegments:
@@ -180,7 +155,7 @@ def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widt
                          ("max_segments", max_segments, 1 << 64), ("final_pc", final_pc, 1 << 32)):
         if not 0 <= int(v) < top:
             raise ValueError(f"cut: {name} out of range")
-    recs, numbers = segment_records(seg, segments)
+    recs, numbers = stage.air_records(seg, segments)
     n, m = len(calls), len(cycles)
     t_cycles = (C.c_uint32 * max(m, 1))(*cycles)
     t_widths = (C.c_uint32 * max(m, 1))(*[int(w) for w in apc_widths]) if apc_widths is not None else None
@@ -188,11 +163,6 @@ def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widt
     t_from = (C.c_uint64 * max(n, 1))(*[int(c.start) for c in calls])
     t_to = (C.c_uint64 * max(n, 1))(*[int(c.end) for c in calls])
     limits = PwSegmentLimits(int(max_log_height), int(min_log_height), int(max_cells), int(max_segments))
-    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), int(final_pc), t_cycles, t_widths, m, t_ids, t_from, t_to, n, C.byref(limits),
-                                               int(scratch_bytes))
-    if rc == -1:
-        raise ValueError("pw_execution_segments_from_traces: malformed arguments")
-    abi.check(rc, "pw_execution_segments_from_traces")
-    if status:
-        raise ExecutionSegmentsError(status, info)
+    handle = stage.call(lib.pw_execution_segments_from_traces, "pw_execution_segments_from_traces", recs, numbers, len(seg), int(bus), int(final_pc), t_cycles, t_widths,
+                        m, t_ids, t_from, t_to, n, C.byref(limits), int(scratch_bytes), error=ExecutionSegmentsError)
     return ExecutionSegments(handle, seg, calls)

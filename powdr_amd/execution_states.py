@@ -8,15 +8,12 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, prover
+from . import abi, prover, stage
 from .empirical import BUS_EXEC
 
 lib = abi.lib
 BUS_MEMORY, REGISTER_AS, REGISTER_PTR_STEP = 1, 1, 4
-STATUS = {0: "built", 2: "the scratch bound is too small", 4: "two rows with one time key",
-          7: "multiplicities on the bus that are no single receive with sends", 8: "a register tuple that is none",
-          9: "a requested register without a value", 10: "the initial registers contradicted by the first receive"}
-ROW_BITS, INTERACTION_BITS = 26, 20  # the packed witness (air | interaction | row) of status 8
+STATUS = {0: "built", **stage.texts(2, 4, 7, 8, 9, 10)}
 
 _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 lib.pw_execution_states_from_traces.restype = C.c_int
@@ -34,40 +31,9 @@ lib.pw_execution_states_last_stats.restype = None
 lib.pw_execution_states_last_stats.argtypes = [_u64p]
 
 
-def unpack_witness(w: int) -> tuple:
-    """the packed witness of status 8 -> (air, interaction, row)"""
-    return w >> (ROW_BITS + INTERACTION_BITS), (w >> ROW_BITS) & ((1 << INTERACTION_BITS) - 1), w & ((1 << ROW_BITS) - 1)
-
-
-def pack_witness(air: int, interaction: int, row: int) -> int:
-    return (air << (ROW_BITS + INTERACTION_BITS)) | (interaction << ROW_BITS) | row
-
-
-def describe(status: int, info: int) -> str:
-    if status == 2:
-        return f"{info} bytes needed"
-    if status == 4:
-        return f"segment {info >> 32}, timestamp {info & 0xFFFFFFFF}"
-    if status == 7:
-        return f"air {info >> 32}, row {info & 0xFFFFFFFF}"
-    if status == 8:
-        return "air %d, interaction %d, row %d" % unpack_witness(info)
-    if status in (9, 10):
-        return f"register {info}"
-    if status == 11:
-        return f"call {info}"
-    if status == 12:
-        return f"position {info}"
-    return ""
-
-
-class ExecutionStatesError(ValueError):
+class ExecutionStatesError(stage.StageError):
     """a non-zero status of pw_execution_states_from_traces: `.status`, `.info` (the raw word), the decoded info in the message"""
-
-    def __init__(self, status: int, info: int):
-        self.status, self.info = int(status), int(info)
-        what = describe(self.status, self.info)
-        super().__init__(f"pw_execution_states: status {self.status}, {STATUS.get(self.status, '?')}" + (f" ({what})" if what else ""))
+    PREFIX, STATUS = "pw_execution_states", STATUS
 
 
 def last_stats() -> dict:
@@ -76,33 +42,12 @@ def last_stats() -> dict:
     return dict(zip(("sends", "kept", "fill_tile", "peak_bytes", "scratch_bytes"), (int(x) for x in out)))
 
 
-def segment_records(seg, segments=None):
-    """[(Prover, device trace pointer, log_height)] -> the C call's AIR records and segment numbers (or None)"""
-    n = len(seg)
-    recs = (prover.PwSegmentAir * max(n, 1))()
-    for i, (pr, ptr, lh) in enumerate(seg):
-        recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
-    numbers = None
-    if segments is not None:
-        assert len(segments) == n
-        numbers = (C.c_uint32 * max(n, 1))(*[int(s) for s in segments])
-    return recs, numbers
-
-
-def from_traces_raw(recs, n_airs, segments, bus, memory_bus, final_pc, reg_as, ptr_step, regs, n_regs, initial_regs, scratch_bytes):
-    """the C call itself -> (return code, status, info, handle or None); the caller destroys the handle"""
-    out, status, info = C.c_void_p(), C.c_uint32(), C.c_uint64()
-    rc = lib.pw_execution_states_from_traces(recs, segments, n_airs, bus, memory_bus, final_pc, reg_as, ptr_step, regs, n_regs, initial_regs, scratch_bytes,
-                                             C.byref(out), C.byref(status), C.byref(info))
-    return rc, int(status.value), int(info.value), out.value
-
-
-class ExecutionStates:
+class ExecutionStates(stage.Handle):
     """`.n_states` = N + 1, `.n_regs`, `.sends` (register sends read), `.bytes` held on the device; `.d_pcs`, `.d_regs`, `.d_time_keys` the
     device pointers (valid until close()); `.pcs()` u32[N + 1], `.regs()` u32[n_regs, N + 1], `.time_keys` [N] copied to the host."""
 
     def __init__(self, handle):
-        self._h = handle
+        super().__init__(handle, lib.pw_execution_states_destroy)
         sizes = (C.c_uint64 * 4)()
         lib.pw_execution_states_sizes(handle, sizes)
         self.n_states, self.n_regs, self.sends, self.bytes = (int(x) for x in sizes)
@@ -135,20 +80,6 @@ class ExecutionStates:
             self._keys = out.tolist()
         return self._keys
 
-    def close(self) -> None:
-        if self._h is not None:
-            lib.pw_execution_states_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
 
 def states_from_traces(seg, regs, final_pc, initial_regs=None, segments=None, bus: int = BUS_EXEC, memory_bus: int = BUS_MEMORY, reg_as: int = REGISTER_AS,
                        ptr_step: int = REGISTER_PTR_STEP, scratch_bytes: int = 0) -> ExecutionStates:
@@ -156,18 +87,12 @@ def states_from_traces(seg, regs, final_pc, initial_regs=None, segments=None, bu
     k of the table is regs[k]; final_pc: the pc after the last row; initial_regs: None or one word per entry of regs, the machine at the
     segment's start; segments: one segment number for all AIRs. A non-zero status raises ExecutionStatesError."""
     regs = [int(r) for r in regs]
-    recs, numbers = segment_records(seg, segments)
+    recs, numbers = stage.air_records(seg, segments)
     t_regs = (C.c_uint32 * max(len(regs), 1))(*regs)
     t_init = None
     if initial_regs is not None:
         if len(initial_regs) != len(regs):
             raise ValueError("initial_regs: one word per requested register")
         t_init = (C.c_uint32 * max(len(regs), 1))(*[int(w) for w in initial_regs])
-    rc, status, info, handle = from_traces_raw(recs, len(seg), numbers, int(bus), int(memory_bus), int(final_pc), int(reg_as), int(ptr_step), t_regs, len(regs), t_init,
-                                               int(scratch_bytes))
-    if rc == -1:
-        raise ValueError("pw_execution_states_from_traces: malformed arguments")
-    abi.check(rc, "pw_execution_states_from_traces")
-    if status:
-        raise ExecutionStatesError(status, info)
-    return ExecutionStates(handle)
+    return ExecutionStates(stage.call(lib.pw_execution_states_from_traces, "pw_execution_states_from_traces", recs, numbers, len(seg), int(bus), int(memory_bus),
+                                      int(final_pc), int(reg_as), int(ptr_step), t_regs, len(regs), t_init, int(scratch_bytes), error=ExecutionStatesError))

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi
+from . import abi, stage
 
 lib = abi.lib
 
@@ -184,8 +184,7 @@ def verify_logup(proof, width: int, log_height: int, cons_bytecode, cons_spans, 
     return rc, (s if rc == 0 else None)
 
 
-class PwSegmentAir(C.Structure):
-    _fields_ = [("prover", C.c_void_p), ("d_trace", C.c_void_p), ("log_height", C.c_uint32), ("flags", C.c_uint32)]
+PwSegmentAir = stage.PwSegmentAir
 
 
 PW_AIR_HAND_OVER = 1
@@ -305,10 +304,7 @@ def prove_airs(airs, shared_bus_seed: bool = False, n_workers: int = 0, copy: bo
     """airs: [(Prover, device trace pointer, log_height)] -> ([proof words per AIR], bus seed).
     INDEPENDENT proofs, one per AIR, on `n_workers` host threads / HIP streams (0 = 4) — the flow AIR-level sharding
     over ranks uses; `prove_segment` is the one-proof-per-segment form."""
-    n = len(airs)
-    recs = (PwSegmentAir * max(n, 1))()
-    for i, (pr, ptr, lh) in enumerate(airs):
-        recs[i] = PwSegmentAir(pr._h, ptr, lh)
+    n, recs = len(airs), stage.air_records(airs)[0]
     proofs = (C.POINTER(C.c_uint32) * max(n, 1))()
     lens = (C.c_size_t * max(n, 1))()
     seed = np.zeros(8, np.uint32)
@@ -339,10 +335,8 @@ def prove_segment(airs, logup: bool = False, copy: bool = True, hand_over=None) 
     hand_over: None = pw_prove_segment; True / a list of bools = pw_prove_segment_consuming with those AIRs' traces handed over
     (a STREAMED AIR then leaves its coefficient arrays in the caller's buffer: segment_last_modes() says which did)."""
     n = len(airs)
-    recs = (PwSegmentAir * max(n, 1))()
     flags = [0] * n if hand_over is None else ([PW_AIR_HAND_OVER] * n if hand_over is True else [PW_AIR_HAND_OVER if f else 0 for f in hand_over])
-    for i, (pr, ptr, lh) in enumerate(airs):
-        recs[i] = PwSegmentAir(pr._h, ptr, lh, flags[i])
+    recs = stage.air_records(airs, flags=flags)[0]
     words = C.POINTER(C.c_uint32)()
     nw = C.c_size_t()
     if hand_over is None:
@@ -386,10 +380,7 @@ def check_segment_buses(airs, buses=None, seed: int = 0, table_bytes: int = 0, t
     name them;
     tuples, by (bus, n_args, args): dict(bus, n_args, args (canonical, the first 16), net_multiplicity, air, interaction, row,
     n_contributions) — at most tuple_cap of them, the first in that order. A tuple is (bus, n_args, args): (a, b) is not (a, b, 0)."""
-    n = len(airs)
-    recs = (PwSegmentAir * max(n, 1))()
-    for i, (pr, ptr, lh) in enumerate(airs):
-        recs[i] = PwSegmentAir(pr._h, ptr, lh, 0)
+    n, recs = len(airs), stage.air_records(airs)[0]
     ids = None if buses is None else np.ascontiguousarray(sorted(set(int(b) for b in buses)), dtype=np.uint32)
     if ids is not None and len(ids) == 0:
         return [], []

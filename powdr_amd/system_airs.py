@@ -21,7 +21,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import abi, air_text, prover
+from . import abi, air_text, prover, stage
 from .periphery import OP_PUSH_APC, OP_PUSH_CONST, _col, _join_tables, _neg_col, _tables
 
 lib = abi.lib
@@ -278,11 +278,7 @@ def poseidon2_air(bus: int = BUS_COMPRESS) -> SystemAir:
 
 # ---- traces -------------------------------------------------------------------------------------------------------------------------
 def _records(airs):
-    n = len(airs)
-    recs = (prover.PwSegmentAir * max(n, 1))()
-    for i, (pr, ptr, lh) in enumerate(airs):
-        recs[i] = prover.PwSegmentAir(pr._h, ptr, lh, 0)
-    return recs, n
+    return stage.air_records(airs)[0], len(airs)
 
 
 def _tuple_dict(t) -> dict:

@@ -213,9 +213,9 @@ def test_every_refusal_that_needs_no_gpu():
 
 
 def test_an_empty_execution_needs_no_gpu():
-    from powdr_amd import apc_calls as ac
+    from powdr_amd import apc_calls as ac, stage
 
-    rc, status, info, handle = ac.from_states_raw(None, None, 0, 0, 8, *ac.tables([ac.Apc(0, 2, 1), ac.Apc(4, 1, 9)]), 0)
+    rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_states, None, None, 0, 0, 8, *ac.tables([ac.Apc(0, 2, 1), ac.Apc(4, 1, 9)]), 0)
     assert (rc, status) == (0, 0) and handle
     with ac.ApcCalls(handle) as got:
         assert got.calls == [] and got.covered == 0 and got.counters == [dict.fromkeys(ac.COUNTERS, 0)] * 2

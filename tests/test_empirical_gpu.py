@@ -43,15 +43,15 @@ def run(gpu, host, blocks, segments=None, **kw):
 
 def status_of(gpu, host, blocks, segments=None, **kw):
     """(status, info) of a call that must fail, on the device and by the reference route; no result object exists"""
-    from powdr_amd import empirical
+    from powdr_amd import empirical, stage
 
     s = Segment(gpu, host)
     try:
         with pytest.raises(empirical.EmpiricalError) as e:
             empirical.detect(s.seg, blocks, segments=segments, **kw)
-        recs = (empirical.prover.PwSegmentAir * len(s.seg))(*[empirical.prover.PwSegmentAir(p._h, ptr, lh, 0) for p, ptr, lh in s.seg])
+        recs, _ = stage.air_records(s.seg)
         blk = (empirical.PwBasicBlock * max(len(blocks), 1))(*[empirical.PwBasicBlock(a, b) for a, b in blocks])
-        rc, status, info, handle = empirical.detect_raw(recs, len(s.seg), None, 0, 4, blk, len(blocks), 0)
+        rc, status, info, handle = stage.raw(empirical.lib.pw_empirical_detect, recs, None, len(s.seg), 0, 4, blk, len(blocks), 0)
         if segments is None:
             assert (rc, status, info, handle) == (0, e.value.status, e.value.info, None)
     finally:

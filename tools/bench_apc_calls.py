@@ -36,7 +36,7 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_apc_calls: needs a GPU")
-    from powdr_amd import abi
+    from powdr_amd import abi, stage
     from powdr_amd import apc_calls as ac
     from tests import _apc_calls_ref as ref
 
@@ -73,14 +73,14 @@ def main():
         dst = torch.empty_like(pcs)
 
         def select():
-            rc, status, info, handle = ac.from_states_raw(pcs.data_ptr(), None, n_states, 0, 8, *tabs, 0)
+            rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_states, pcs.data_ptr(), None, n_states, 0, 8, *tabs, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             with ac.ApcCalls(handle) as got:
                 return dict(calls=len(got.calls), covered=got.covered, first_calls=[tuple(c) for c in got.calls[:3]],
                             totals={k: sum(c[k] for c in got.counters) for k in ac.COUNTERS})
 
         def select_raw():  # the C call and its sizes alone: what a Rust caller pays
-            rc, status, info, handle = ac.from_states_raw(pcs.data_ptr(), None, n_states, 0, 8, *tabs, 0)
+            rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_states, pcs.data_ptr(), None, n_states, 0, 8, *tabs, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             ac.lib.pw_apc_calls_destroy(handle)
 

@@ -39,9 +39,8 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_apc_direct: needs a GPU")
-    from powdr_amd import abi, prover
+    from powdr_amd import abi, prover, stage
     from powdr_amd import apc_sources as aps
-    from powdr_amd import execution_states as es
     from tests import _execution_states_ref as sref
 
     note = lambda *a: print("[bench_apc_direct]", *a, file=sys.stderr, flush=True)
@@ -86,7 +85,7 @@ def main():
         trace, width = trace_of(log_positions, 3, random_order)
         n = 1 << log_positions
         pr = prover.Prover(width, *no_cons, num_queries=2, interactions=sref.state_log_interactions(3))
-        recs, _ = es.segment_records([(pr, trace.data_ptr(), log_positions)])
+        recs, _ = stage.air_records([(pr, trace.data_ptr(), log_positions)])
         n_calls = n // PERIOD
         start = np.arange(n_calls, dtype=np.uint64) * PERIOD
         end, ids, cycles = start + CYCLE, np.zeros(n_calls, np.uint32), (C.c_uint32 * 1)(CYCLE)
@@ -96,7 +95,8 @@ def main():
         theirs = torch.empty_like(out)
 
         def handle(direct):
-            rc, status, info, h = aps.from_traces_raw(recs, 1, None, 0, cycles, 1, u32p(ids), u64p(start), u64p(end), n_calls, 0, 0, aps.DIRECT if direct else None)
+            rc, status, info, h = stage.raw(aps.lib.pw_apc_sources_from_traces_flags, recs, None, 1, 0, cycles, 1, u32p(ids), u64p(start), u64p(end), n_calls, 0, 0,
+                                            aps.DIRECT if direct else 0)
             assert (rc, status) == (0, 0) and h, (rc, status, info)
             return aps.ApcSources(h, [width], direct=direct)
 

@@ -41,10 +41,9 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_apc_sources: needs a GPU")
-    from powdr_amd import abi, prover
+    from powdr_amd import abi, prover, stage
     from powdr_amd import apc_calls as ac
     from powdr_amd import apc_sources as aps
-    from powdr_amd import execution_states as es
     from tests import _execution_states_ref as sref
 
     note = lambda *a: print("[bench_apc_sources]", *a, file=sys.stderr, flush=True)
@@ -78,7 +77,7 @@ def main():
         trace, width = trace_of(log_positions, n_access, random_order)
         n = 1 << log_positions
         pr = prover.Prover(width, *no_cons, num_queries=2, interactions=sref.state_log_interactions(n_access))
-        recs, _ = es.segment_records([(pr, trace.data_ptr(), log_positions)])
+        recs, _ = stage.air_records([(pr, trace.data_ptr(), log_positions)])
         n_calls = n // PERIOD
         start = np.arange(n_calls, dtype=np.uint64) * PERIOD
         end, ids, cycles = start + CYCLE, np.zeros(n_calls, np.uint32), (C.c_uint32 * 1)(CYCLE)
@@ -87,13 +86,13 @@ def main():
         seen = {}
 
         def apply():
-            rc, status, info, handle = aps.from_traces_raw(recs, 1, None, 0, cycles, 1, u32p(ids), u64p(start), u64p(end), n_calls, 0, 0)
+            rc, status, info, handle = stage.raw(aps.lib.pw_apc_sources_from_traces, recs, None, 1, 0, cycles, 1, u32p(ids), u64p(start), u64p(end), n_calls, 0, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             with aps.ApcSources(handle, [width]) as got:
                 seen.update(written=got.source_bytes + got.residual_bytes, residual_rows=got.residual(0).rows, source_width_height_rbs=tuple(got.source(0, 0))[1:])
 
         def pcs_only():
-            rc, status, info, handle = ac.from_traces_raw(recs, 1, None, 0, 0, *tabs, 0)
+            rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_traces, recs, None, 1, 0, 0, *tabs, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             ac.lib.pw_apc_calls_destroy(handle)
 

@@ -37,7 +37,7 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_empirical: needs a GPU")
-    from powdr_amd import abi, empirical, prover
+    from powdr_amd import abi, empirical, prover, stage
     from tests import _empirical_ref as ref
 
     note = lambda *a: print("[bench_empirical]", *a, file=sys.stderr, flush=True)
@@ -76,13 +76,13 @@ def main():
     def measure(name, log_instances, log_blocks):
         trace, n, blocks = workload(log_instances, log_blocks)
         log_h = n.bit_length() - 1
-        recs = (prover.PwSegmentAir * 1)(prover.PwSegmentAir(p._h, trace.data_ptr(), log_h, 0))
+        recs, _ = stage.air_records([(p, trace.data_ptr(), log_h)])
         blk = (empirical.PwBasicBlock * len(blocks))(*[empirical.PwBasicBlock(s, c) for s, c in blocks])
         words = torch.randint(-(1 << 31), (1 << 31) - 1, (n * WIDTH,), device="cuda", dtype=torch.int32)
         dst = torch.empty_like(trace)
 
         def detect():
-            rc, status, info, handle = empirical.detect_raw(recs, 1, None, 0, 4, blk, len(blocks), 0)
+            rc, status, info, handle = stage.raw(empirical.lib.pw_empirical_detect, recs, None, 1, 0, 4, blk, len(blocks), 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             sizes = (C.c_uint64 * 5)()
             empirical.lib.pw_empirical_sizes(handle, sizes)

@@ -39,7 +39,7 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_execution_blocks: needs a GPU")
-    from powdr_amd import abi, empirical
+    from powdr_amd import abi, empirical, stage
     from powdr_amd import execution_blocks as eb
     from tests import _execution_blocks_ref as ref
 
@@ -85,7 +85,7 @@ def main():
         dst = torch.empty_like(pcs)
 
         def detect(keep=False):
-            rc, status, info, handle = eb.from_pcs_raw(pcs.data_ptr(), n, 4, blk, len(blocks), max_bb, 0)
+            rc, status, info, handle = stage.raw(eb.lib.pw_execution_blocks_from_pcs, pcs.data_ptr(), n, 4, blk, len(blocks), max_bb, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             sizes = (C.c_uint64 * 6)()
             eb.lib.pw_execution_blocks_sizes(handle, sizes)

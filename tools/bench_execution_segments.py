@@ -40,11 +40,10 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_execution_segments: needs a GPU")
-    from powdr_amd import abi, prover
+    from powdr_amd import abi, prover, stage
     from powdr_amd import apc_calls as ac
     from powdr_amd import apc_sources as aps
     from powdr_amd import execution_segments as xs
-    from powdr_amd import execution_states as es
     from tests import _execution_states_ref as sref
 
     note = lambda *a: print("[bench_execution_segments]", *a, file=sys.stderr, flush=True)
@@ -77,7 +76,7 @@ def main():
     def measure(name, trace, pr, log_positions, log_cap, with_calls):
         n = 1 << log_positions
         seg = [(pr, trace.data_ptr(), log_positions)]
-        recs, _ = es.segment_records(seg)
+        recs, _ = stage.air_records(seg)
         n_calls = n // PERIOD if with_calls else 0
         start = np.arange(max(n_calls, 1), dtype=np.uint64) * PERIOD
         end, ids = start + CYCLE, np.zeros(max(n_calls, 1), np.uint32)
@@ -87,7 +86,7 @@ def main():
         tabs = ac.tables([ac.Apc(0, 2, 1, [(ac.Pc(0), ac.Number(0))])])
 
         def raw_cut():
-            rc, status, info, handle = xs.from_traces_raw(recs, 1, None, 0, 0, cycles, widths, 1, u32p(ids), u64p(start), u64p(end), n_calls, C.byref(limits), 0)
+            rc, status, info, handle = stage.raw(xs.lib.pw_execution_segments_from_traces, recs, None, 1, 0, 0, cycles, widths, 1, u32p(ids), u64p(start), u64p(end), n_calls, C.byref(limits), 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             return handle
 
@@ -95,7 +94,7 @@ def main():
             xs.lib.pw_execution_segments_destroy(raw_cut())
 
         def pcs_only():
-            rc, status, info, handle = ac.from_traces_raw(recs, 1, None, 0, 0, *tabs, 0)
+            rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_traces, recs, None, 1, 0, 0, *tabs, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             ac.lib.pw_apc_calls_destroy(handle)
 

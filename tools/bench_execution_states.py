@@ -39,7 +39,7 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_execution_states: needs a GPU")
-    from powdr_amd import abi, prover
+    from powdr_amd import abi, prover, stage
     from powdr_amd import apc_calls as ac
     from powdr_amd import execution_states as es
     from tests import _execution_states_ref as sref
@@ -81,7 +81,7 @@ def main():
         n = 1 << log_positions
         pr = prover.Prover(width, *no_cons, num_queries=2, interactions=it)
         seg = [(pr, trace.data_ptr(), log_positions)]
-        recs, _ = es.segment_records(seg)
+        recs, _ = stage.air_records(seg)
         t_regs = (es.C.c_uint32 * len(regs))(*regs)
         tabs = ac.tables([ac.Apc(0, 2, 1, [(ac.Pc(0), ac.Number(0))])])
         table_words = len(regs) * (n + 1)
@@ -90,13 +90,13 @@ def main():
         sends = {}
 
         def states():
-            rc, status, info, handle = es.from_traces_raw(recs, 1, None, 0, 1, 0, 1, 4, t_regs, len(regs), None, 0)
+            rc, status, info, handle = stage.raw(es.lib.pw_execution_states_from_traces, recs, None, 1, 0, 1, 0, 1, 4, t_regs, len(regs), None, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             with es.ExecutionStates(handle) as got:
                 sends["n"], sends["states"], sends["bytes"] = got.sends, got.n_states, got.bytes
 
         def pcs_only():
-            rc, status, info, handle = ac.from_traces_raw(recs, 1, None, 0, 0, *tabs, 0)
+            rc, status, info, handle = stage.raw(ac.lib.pw_apc_calls_from_traces, recs, None, 1, 0, 0, *tabs, 0)
             assert (rc, status) == (0, 0) and handle, (rc, status, info)
             ac.lib.pw_apc_calls_destroy(handle)
 
