@@ -26,13 +26,13 @@
 #include "xbc.hpp"
 #include "xbc_compile.hpp"
 #include "small_form.hpp"
+#include "plan_cache.hpp"
 #include "../../include/powdr_gpu.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -328,66 +328,205 @@ __global__ __launch_bounds__(kHistBlock) void bus_histogram_kernel(
     }
 }
 
-// host-side classification of the interaction list, cached by content
+// host-side classification of the interaction list, cached by content (plan_cache.hpp). Every table is an allocation of its own
+// with spare entries at its end (+1 entry, +2 words on the xbc code): the kernels may read them.
 struct BusPlan {
-    int32_t* d_slot_of = nullptr;        // per interaction: item slot or -1
-    uint32_t* d_slots[3] = {nullptr, nullptr, nullptr};  // slot ids per table (var, tuple, bitwise)
+    pw::DeviceBuf slot_of;   // int32_t per interaction: item slot or -1
+    pw::DeviceBuf slots[3];  // uint32_t slot ids per table (var, tuple, bitwise)
     uint32_t n_slots[3] = {0, 0, 0};
     uint32_t total_slots = 0;
     // xbc form of the periphery interactions (absent if some expression did not compile)
     bool has_xbc = false;
-    XInteraction* d_xint = nullptr;
-    uint32_t* d_code = nullptr;
+    pw::DeviceBuf xint, code;  // XInteraction, xbc words
     // the same interactions split into those that are small forms throughout (fast kernel) and the rest (interpreter)
-    uint32_t* d_slot_range = nullptr;  // per item slot: expected partitions (first | last << 16)
-    FastInteraction* d_fint = nullptr;
-    XInteraction* d_xint_slow = nullptr;
+    pw::DeviceBuf slot_range;  // uint32_t per item slot: expected partitions (first | last << 16)
+    pw::DeviceBuf fint, xint_slow;  // FastInteraction, XInteraction
     uint32_t n_fast = 0, n_slow = 0;
-    // what the plan was compiled from (a cache hit is confirmed by content, not by the 64-bit hash alone)
-    std::vector<DevInteraction> key_inter;
-    std::vector<ExprSpan> key_spans;
-    std::vector<uint32_t> key_bc;
-    uint32_t key_ids[3] = {0, 0, 0};
-    int device = 0;
-    uint64_t last_use = 0;
-    BusPlan() = default;
-    BusPlan(const BusPlan&) = delete;
-    BusPlan& operator=(const BusPlan&) = delete;
-    ~BusPlan() {  // hipFree waits for kernels that may still read the tables
-        for (void* q : {(void*)d_slot_of, (void*)d_slots[0], (void*)d_slots[1], (void*)d_slots[2], (void*)d_xint, (void*)d_code,
-                        (void*)d_slot_range, (void*)d_fint, (void*)d_xint_slow})
-            if (q) (void)hipFree(q);
-    }
 };
-constexpr size_t kMaxBusPlans = 64;
-std::mutex g_bus_mu;
-std::unordered_map<uint64_t, std::shared_ptr<BusPlan>> g_bus_plans;
-uint64_t g_bus_clock = 0;
+// keyed by the three host tables, the three bus ids and the device
+pw::PlanCache<BusPlan> g_bus_plans(64);
+
 // item buffer of the binned path: one per host thread (= per launch stream)
 struct ItemBuffer {
     uint32_t* p = nullptr;
     size_t words = 0;
     int device = -1;  // the device the buffer lives on (a host thread may move to another GPU)
     ~ItemBuffer() { if (p) (void)hipFree(p); }  // a host thread that exits gives its buffer back
+    // false: the allocation failed (the caller falls through to the direct path)
+    bool ensure(int on_device, size_t need) {
+        if (need <= words && device == on_device) return true;
+        device = on_device;
+        if (p) (void)hipFree(p);
+        p = nullptr; words = 0;
+        if (hipMalloc(&p, need * 4) != hipSuccess) { (void)hipGetLastError(); return false; }
+        words = need;
+        return true;
+    }
 };
 thread_local ItemBuffer g_item_buf;
-#define g_items g_item_buf.p
-#define g_items_words g_item_buf.words
-#define g_items_device g_item_buf.device
 
-// 8 bytes per step (the bytecode of an un-optimised APC is megabytes)
-uint64_t hash_words(const void* p, size_t n, uint64_t h) {
-    const uint64_t* w = (const uint64_t*)p;
-    size_t k = n / 8;
-    for (size_t i = 0; i < k; ++i) { h ^= w[i]; h *= 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
-    const unsigned char* c = (const unsigned char*)p + k * 8;
-    for (size_t i = 0; i < n % 8; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-    return h;
+// The replay's knobs, read from the environment on every call (unset = default).
+struct BusKnobs {
+    int binned = -1;   // POWDR_BUS_BINNED; unset: by the length of the trace
+    bool xbc = true;   // POWDR_BUS_XBC=0: walk the reference's post-fix bytecode
+    bool fast = true;  // POWDR_BUS_FAST=0: small-form interactions go through the interpreter too
+    bool want_binned(int num_apc_calls) const { return binned < 0 ? num_apc_calls >= 16384 : binned != 0; }
+    static BusKnobs from_env() {
+        BusKnobs k;
+        if (const char* e = getenv("POWDR_BUS_BINNED")) k.binned = atoi(e) != 0;
+        if (const char* e = getenv("POWDR_BUS_XBC")) k.xbc = atoi(e) != 0;
+        if (const char* e = getenv("POWDR_BUS_FAST")) k.fast = atoi(e) != 0;
+        return k;
+    }
+};
+
+// host views of the tables a plan is compiled from: the caller's own memory (powdr_apc_apply_bus_host_tables) or copies fetched
+// from the device (reference entry)
+struct BusTables {
+    const DevInteraction* inter; size_t n_inter;
+    const ExprSpan* spans; size_t n_spans;
+    const uint32_t* bc; size_t bc_len;
+    uint32_t ids[3];  // var-range, tuple2, bitwise bus
+};
+
+int build_bus_plan(const BusTables& t, const uint32_t table_bins[3], BusPlan& bp) {
+    std::vector<int32_t> slot_of(t.n_inter, -1);
+    std::vector<uint32_t> per_table[3];
+    std::vector<XInteraction> xints, xints_slow;
+    std::vector<uint32_t> slot_range;
+    std::vector<FastInteraction> fints;
+    std::vector<uint32_t> code;
+    xbc::Compiler cc;
+    bool ok = true;
+    for (size_t i = 0; i < t.n_inter; ++i) {
+        const DevInteraction& in = t.inter[i];
+        int kind = in.bus_id == t.ids[0] ? 0 : in.bus_id == t.ids[1] ? 1 : in.bus_id == t.ids[2] ? 2 : -1;
+        if (kind < 0) continue;
+        slot_of[i] = (int32_t)bp.total_slots;
+        XInteraction xi{};
+        xi.kind = (uint32_t)kind;
+        xi.slot = bp.total_slots;
+        per_table[kind].push_back(bp.total_slots++);
+        const uint32_t which[4] = {0, 1, 2, 4};  // mult, arg0, arg1, (bitwise) selector = arg 3
+        FastInteraction fi{};
+        fi.kind = (uint32_t)kind;
+        fi.slot = xi.slot;
+        fi.f[3].flags = pw::SmallForm::IS_CONST;
+        bool fast = true;
+        for (int k = 0; k < (kind == 2 ? 4 : 3) && ok; ++k) {
+            const size_t si = (size_t)in.args_index_off + which[k];
+            if (si >= t.n_spans || (size_t)t.spans[si].off + t.spans[si].len > t.bc_len) { ok = false; break; }
+            xi.off[k] = (uint32_t)(code.size() / 2);
+            if (!cc.compile(t.bc + t.spans[si].off, t.spans[si].len, code)) { ok = false; break; }
+            xi.len[k] = (uint32_t)(code.size() / 2) - xi.off[k];
+            fast = fast && pw::analyze_small_form(t.bc + t.spans[si].off, t.spans[si].len, fi.f[k]);
+        }
+        xints.push_back(xi);
+        if (fast) fints.push_back(fi);
+        else xints_slow.push_back(xi);
+        // expected partitions of this slot's items
+        uint32_t first = 0, last = (table_bins[kind] - 1) / kPartBins;
+        if (ok) {
+            pw::SmallForm c;
+            const auto constant_arg = [&](uint32_t arg, uint32_t& value) {
+                const size_t si = (size_t)in.args_index_off + arg;
+                if (!pw::analyze_small_form(t.bc + t.spans[si].off, t.spans[si].len, c) || !(c.flags & pw::SmallForm::IS_CONST)) return false;
+                value = bb::from_monty(c.k0);
+                return true;
+            };
+            uint32_t v;
+            if (kind == 0 && constant_arg(2, v) && v < 31) {  // honest values of a `v`-bit check: [2^v - 1, 2^(v+1) - 2]
+                first = ((1u << v) - 1u) / kPartBins;
+                last = std::min(last, ((2u << v) - 2u) / kPartBins);
+                if (first > last) first = last;
+            } else if (kind == 2 && constant_arg(4, v) && v <= 1) {
+                first = bitwise_index(0, 0, v) / kPartBins;
+                last = bitwise_index(255, 255, v) / kPartBins;
+            }
+        }
+        slot_range.push_back(first | (last << 16));
+    }
+    if (int rc = pw::upload_table(bp.slot_range, slot_range.data(), slot_range.size(), 1)) return rc;
+    if (int rc = pw::upload_table(bp.slot_of, slot_of.data(), slot_of.size(), 1)) return rc;
+    for (int k = 0; k < 3; ++k) {
+        bp.n_slots[k] = (uint32_t)per_table[k].size();
+        if (int rc = pw::upload_table(bp.slots[k], per_table[k].data(), per_table[k].size(), 1)) return rc;
+    }
+    if (ok && !xints.empty()) {
+        if (int rc = pw::upload_table(bp.xint, xints.data(), xints.size())) return rc;
+        if (int rc = pw::upload_table(bp.code, code.data(), code.size(), 2)) return rc;
+        bp.has_xbc = true;
+        bp.n_fast = (uint32_t)fints.size();
+        bp.n_slow = (uint32_t)xints_slow.size();
+        if (int rc = pw::upload_table(bp.fint, fints.data(), fints.size(), 1)) return rc;
+        if (int rc = pw::upload_table(bp.xint_slow, xints_slow.data(), xints_slow.size(), 1)) return rc;
+    }
+    return 0;
 }
-uint64_t fnv1a64(const void* p, size_t n, uint64_t h) {
-    const unsigned char* c = (const unsigned char*)p;
-    for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-    return h;
+
+// chunking of an interaction list over blockIdx.y so that short traces still fill the chip
+struct Chunking { unsigned chunks = 1; uint32_t per_chunk = 1; };
+Chunking chunking(unsigned row_blocks, uint32_t n_list) {
+    const unsigned want_blocks = 256u * 8u;  // enough workgroups to cover 256 CUs x 8 blocks even for short traces
+    Chunking c;
+    if (n_list == 0) return c;
+    if (row_blocks < want_blocks) {
+        c.chunks = (want_blocks + row_blocks - 1) / row_blocks;
+        const unsigned max_chunks = (n_list + 15) / 16;
+        if (c.chunks > max_chunks) c.chunks = max_chunks;
+        if (c.chunks > 65535u) c.chunks = 65535u;
+        if (c.chunks == 0) c.chunks = 1;
+    }
+    c.per_chunk = (n_list + c.chunks - 1) / c.chunks;
+    c.chunks = (n_list + c.per_chunk - 1) / c.per_chunk;
+    return c;
+}
+
+// What the walkers of one call run over. The interpreter walks all periphery interactions (xbc), only the non-small-form ones
+// (fast mode), or the reference's full list (post-fix mode).
+struct Walk {
+    const uint32_t* trace; int num_calls; size_t col_stride;
+    BusParams p;
+    const uint32_t* d_bytecode; const DevInteraction* d_interactions; uint32_t n_interactions; const ExprSpan* d_arg_spans;  // post-fix mode
+    bool use_xbc, use_fast;
+    const XInteraction* x_list; uint32_t n_x;
+    Chunking x, f;
+};
+
+// the fast kernel, then the xbc kernel or the post-fix kernel, over `row_blocks` blocks of rows from row0. BINNED: into `items`
+template <bool BINNED>
+void launch_walkers(const BusPlan& plan, const Walk& w, unsigned row_blocks, uint32_t* items, size_t stride, size_t row0) {
+    pw::ScopedKernelTimer t("apc_apply_bus_kernel");
+    if (w.use_fast && plan.n_fast)
+        hipLaunchKernelGGL(apc_apply_bus_fast_kernel<BINNED>, dim3(row_blocks, w.f.chunks), dim3(kBlock), 0, pw::stream(), w.trace,
+                           w.num_calls, plan.fint.as<FastInteraction>(), plan.n_fast, w.p, w.f.per_chunk, items, stride, w.col_stride, row0);
+    if (w.use_xbc) {
+        if (w.n_x)
+            hipLaunchKernelGGL(apc_apply_bus_xbc_kernel<BINNED>, dim3(row_blocks, w.x.chunks), dim3(kBlock), 0, pw::stream(), w.trace,
+                               w.num_calls, plan.code.as<uint32_t>(), w.x_list, w.n_x, w.p, w.x.per_chunk, items, stride, w.col_stride, row0);
+    } else
+        hipLaunchKernelGGL(apc_apply_bus_kernel<BINNED>, dim3(row_blocks, w.x.chunks), dim3(kBlock), 0, pw::stream(), w.trace,
+                           w.num_calls, w.d_bytecode, w.d_interactions, w.n_interactions, w.d_arg_spans, w.p, w.x.per_chunk,
+                           BINNED ? plan.slot_of.as<int32_t>() : nullptr, items, stride, w.col_stride, row0);
+}
+
+// one 128-KB-LDS workgroup fits per CU, and the three launches run one after the other, so each launch gets ~2 x 256 workgroups
+// of its own: partitions x row chunks
+void launch_histograms(const BusPlan& plan, const uint32_t* items, size_t stride, uint32_t* const tables[3], const uint32_t table_bins[3]) {
+    for (int t = 0; t < 3; ++t) {
+        if (!plan.n_slots[t]) continue;
+        const unsigned parts = pw::div_up(table_bins[t], kPartBins);
+        unsigned n_chunks = (512 + parts - 1) / parts;
+        const unsigned max_chunks = pw::div_up(stride, 4096);
+        if (n_chunks > max_chunks) n_chunks = max_chunks;
+        if (n_chunks == 0) n_chunks = 1;
+        const uint32_t rows_per_chunk = (uint32_t)(((stride + n_chunks - 1) / n_chunks + 3) & ~(size_t)3);
+        n_chunks = pw::div_up(stride, rows_per_chunk);
+        pw::ScopedKernelTimer tt("bus_histogram_kernel");
+        hipLaunchKernelGGL(bus_histogram_kernel, dim3(parts, n_chunks), dim3(kHistBlock), 0, pw::stream(), items, stride,
+                           plan.slots[t].as<uint32_t>(), plan.n_slots[t], tables[t], table_bins[t], rows_per_chunk,
+                           plan.slot_range.as<uint32_t>());
+    }
 }
 
 }  // namespace
@@ -432,250 +571,75 @@ int apply_bus_impl(const PowdrFp* d_output, int num_apc_calls,
     if (num_apc_calls <= 0) return 0;  // apc_apply_bus.cu:146
     (void)hipGetLastError();
     if (n_interactions == 0) return (int)hipGetLastError();
-    const unsigned row_blocks = pw::div_up((size_t)num_apc_calls, kBlock);
-    // Enough workgroups to cover 256 CUs x 8 blocks even for short traces.
-    const unsigned want_blocks = 256u * 8u;
-    BusParams p;
-    p.var_bus = var_range_bus_id; p.tuple_bus = tuple2_bus_id; p.bitwise_bus = bitwise_bus_id;
-    p.var_hist = d_var_hist; p.tuple_hist = d_tuple2_hist; p.bitwise_hist = d_bitwise_hist;
-    p.var_bins = (uint32_t)var_num_bins; p.tuple_sz0 = tuple2_sz0; p.tuple_sz1 = tuple2_sz1;
-    p.slot_range = nullptr;
-    // ---- plan: host copy of the (small) tables, cached by content --------------------------------
-    const char* env = getenv("POWDR_BUS_BINNED");
-    const bool want_binned = env ? atoi(env) != 0 : num_apc_calls >= 16384;
-    const char* env_x = getenv("POWDR_BUS_XBC");
-    const bool want_xbc = env_x ? atoi(env_x) != 0 : true;
+    const BusKnobs knobs = BusKnobs::from_env();
     const uint32_t table_bins[3] = {(uint32_t)var_num_bins, tuple2_sz0 * tuple2_sz1, 2u << (2 * POWDR_BITWISE_NUM_BITS)};
-    std::vector<DevInteraction> h(n_interactions);
-    std::vector<ExprSpan> hs(n_arg_spans);
-    std::vector<uint32_t> hb(bytecode_len);
-    if (h_bytecode && h_interactions && (h_arg_spans || !n_arg_spans)) {
-        // the caller still holds the tables on the host (powdr_apc_apply_bus_host_tables): no copy back, no synchronisation
-        if (n_interactions) memcpy(h.data(), h_interactions, n_interactions * sizeof(DevInteraction));
-        if (n_arg_spans) memcpy(hs.data(), h_arg_spans, n_arg_spans * sizeof(ExprSpan));
-        if (bytecode_len) memcpy(hb.data(), h_bytecode, bytecode_len * 4);
-    } else {
+    uint32_t* const tables[3] = {d_var_hist, d_tuple2_hist, d_bitwise_hist};
+
+    // ---- tables: the caller's on the host (powdr_apc_apply_bus_host_tables: no copy, no synchronisation), or fetched ----
+    BusTables t{h_interactions, n_interactions, h_arg_spans, n_arg_spans, h_bytecode, bytecode_len,
+                {var_range_bus_id, tuple2_bus_id, bitwise_bus_id}};
+    std::vector<DevInteraction> h;
+    std::vector<ExprSpan> hs;
+    std::vector<uint32_t> hb;
+    if (!(h_bytecode && h_interactions && (h_arg_spans || !n_arg_spans))) {
+        h.resize(n_interactions); hs.resize(n_arg_spans); hb.resize(bytecode_len);
         PW_HIP_TRY(hipMemcpyAsync(h.data(), d_interactions, n_interactions * sizeof(DevInteraction), hipMemcpyDeviceToHost, pw::stream()));
         if (n_arg_spans) PW_HIP_TRY(hipMemcpyAsync(hs.data(), d_arg_spans, n_arg_spans * sizeof(ExprSpan), hipMemcpyDeviceToHost, pw::stream()));
         if (bytecode_len) PW_HIP_TRY(hipMemcpyAsync(hb.data(), d_bytecode, bytecode_len * 4, hipMemcpyDeviceToHost, pw::stream()));
         PW_HIP_TRY(hipStreamSynchronize(pw::stream()));
+        t.inter = h.data(); t.spans = hs.data(); t.bc = hb.data();
     }
-    uint64_t key = fnv1a64(h.data(), h.size() * sizeof(DevInteraction), 1469598103934665603ull);
-    key = hash_words(hs.data(), hs.size() * sizeof(ExprSpan), key);
-    key = hash_words(hb.data(), hb.size() * 4, key);
-    const uint32_t ids[3] = {var_range_bus_id, tuple2_bus_id, bitwise_bus_id};
-    key = fnv1a64(ids, sizeof ids, key);
+
+    // ---- plan ----
     int device = 0;
     PW_HIP_TRY(hipGetDevice(&device));
-    key = fnv1a64(&device, sizeof device, key);
-    std::shared_ptr<BusPlan> plan;
-    {
-        std::lock_guard<std::mutex> lk(g_bus_mu);
-        auto it = g_bus_plans.find(key);
-        if (it != g_bus_plans.end()) {
-            const BusPlan& c = *it->second;
-            const bool same = c.device == device && memcmp(c.key_ids, ids, sizeof ids) == 0 && c.key_inter.size() == h.size() &&
-                              c.key_spans.size() == hs.size() && c.key_bc == hb &&
-                              (h.empty() || memcmp(c.key_inter.data(), h.data(), h.size() * sizeof(DevInteraction)) == 0) &&
-                              (hs.empty() || memcmp(c.key_spans.data(), hs.data(), hs.size() * sizeof(ExprSpan)) == 0);
-            if (!same) { g_bus_plans.erase(it); it = g_bus_plans.end(); }  // hash collision: the newer tables take the slot
-        }
-        if (it == g_bus_plans.end()) {
-            if (g_bus_plans.size() >= kMaxBusPlans) {
-                auto victim = g_bus_plans.begin();
-                for (auto j = g_bus_plans.begin(); j != g_bus_plans.end(); ++j) if (j->second->last_use < victim->second->last_use) victim = j;
-                g_bus_plans.erase(victim);
-            }
-            auto bpp = std::make_shared<BusPlan>();
-            BusPlan& bp = *bpp;
-            std::vector<int32_t> slot_of(n_interactions, -1);
-            std::vector<uint32_t> per_table[3];
-            std::vector<XInteraction> xints, xints_slow;
-            std::vector<uint32_t> slot_range;
-            std::vector<FastInteraction> fints;
-            std::vector<uint32_t> code;
-            xbc::Compiler cc;
-            bool ok = true;
-            for (size_t i = 0; i < n_interactions; ++i) {
-                int kind = h[i].bus_id == ids[0] ? 0 : h[i].bus_id == ids[1] ? 1 : h[i].bus_id == ids[2] ? 2 : -1;
-                if (kind < 0) continue;
-                slot_of[i] = (int32_t)bp.total_slots;
-                XInteraction xi{};
-                xi.kind = (uint32_t)kind;
-                xi.slot = bp.total_slots;
-                per_table[kind].push_back(bp.total_slots++);
-                const uint32_t which[4] = {0, 1, 2, 4};  // mult, arg0, arg1, (bitwise) selector = arg 3
-                FastInteraction fi{};
-                fi.kind = (uint32_t)kind;
-                fi.slot = xi.slot;
-                fi.f[3].flags = pw::SmallForm::IS_CONST;
-                bool fast = true;
-                for (int k = 0; k < (kind == 2 ? 4 : 3) && ok; ++k) {
-                    const size_t si = (size_t)h[i].args_index_off + which[k];
-                    if (si >= hs.size() || (size_t)hs[si].off + hs[si].len > hb.size()) { ok = false; break; }
-                    xi.off[k] = (uint32_t)(code.size() / 2);
-                    if (!cc.compile(hb.data() + hs[si].off, hs[si].len, code)) { ok = false; break; }
-                    xi.len[k] = (uint32_t)(code.size() / 2) - xi.off[k];
-                    fast = fast && pw::analyze_small_form(hb.data() + hs[si].off, hs[si].len, fi.f[k]);
-                }
-                xints.push_back(xi);
-                if (fast) fints.push_back(fi);
-                else xints_slow.push_back(xi);
-                // expected partitions of this slot's items
-                uint32_t first = 0, last = (table_bins[kind] - 1) / kPartBins;
-                if (ok) {
-                    pw::SmallForm c;
-                    const auto constant_arg = [&](uint32_t arg, uint32_t& value) {
-                        const size_t si = (size_t)h[i].args_index_off + arg;
-                        if (!pw::analyze_small_form(hb.data() + hs[si].off, hs[si].len, c) || !(c.flags & pw::SmallForm::IS_CONST)) return false;
-                        value = bb::from_monty(c.k0);
-                        return true;
-                    };
-                    uint32_t v;
-                    if (kind == 0 && constant_arg(2, v) && v < 31) {  // honest values of a `v`-bit check: [2^v - 1, 2^(v+1) - 2]
-                        first = ((1u << v) - 1u) / kPartBins;
-                        last = std::min(last, ((2u << v) - 2u) / kPartBins);
-                        if (first > last) first = last;
-                    } else if (kind == 2 && constant_arg(4, v) && v <= 1) {
-                        first = bitwise_index(0, 0, v) / kPartBins;
-                        last = bitwise_index(255, 255, v) / kPartBins;
-                    }
-                }
-                slot_range.push_back(first | (last << 16));
-            }
-            PW_HIP_TRY(hipMalloc(&bp.d_slot_range, (slot_range.size() + 1) * 4));
-            if (!slot_range.empty()) PW_HIP_TRY(hipMemcpy(bp.d_slot_range, slot_range.data(), slot_range.size() * 4, hipMemcpyHostToDevice));
-            PW_HIP_TRY(hipMalloc(&bp.d_slot_of, (n_interactions + 1) * 4));
-            PW_HIP_TRY(hipMemcpy(bp.d_slot_of, slot_of.data(), n_interactions * 4, hipMemcpyHostToDevice));
-            for (int t = 0; t < 3; ++t) {
-                bp.n_slots[t] = (uint32_t)per_table[t].size();
-                PW_HIP_TRY(hipMalloc(&bp.d_slots[t], (per_table[t].size() + 1) * 4));
-                if (!per_table[t].empty())
-                    PW_HIP_TRY(hipMemcpy(bp.d_slots[t], per_table[t].data(), per_table[t].size() * 4, hipMemcpyHostToDevice));
-            }
-            if (ok && !xints.empty()) {
-                PW_HIP_TRY(hipMalloc(&bp.d_xint, xints.size() * sizeof(XInteraction)));
-                PW_HIP_TRY(hipMemcpy(bp.d_xint, xints.data(), xints.size() * sizeof(XInteraction), hipMemcpyHostToDevice));
-                PW_HIP_TRY(hipMalloc(&bp.d_code, (code.size() + 2) * 4));
-                if (!code.empty()) PW_HIP_TRY(hipMemcpy(bp.d_code, code.data(), code.size() * 4, hipMemcpyHostToDevice));
-                bp.has_xbc = true;
-                bp.n_fast = (uint32_t)fints.size();
-                bp.n_slow = (uint32_t)xints_slow.size();
-                PW_HIP_TRY(hipMalloc(&bp.d_fint, (fints.size() + 1) * sizeof(FastInteraction)));
-                if (!fints.empty()) PW_HIP_TRY(hipMemcpy(bp.d_fint, fints.data(), fints.size() * sizeof(FastInteraction), hipMemcpyHostToDevice));
-                PW_HIP_TRY(hipMalloc(&bp.d_xint_slow, (xints_slow.size() + 1) * sizeof(XInteraction)));
-                if (!xints_slow.empty())
-                    PW_HIP_TRY(hipMemcpy(bp.d_xint_slow, xints_slow.data(), xints_slow.size() * sizeof(XInteraction), hipMemcpyHostToDevice));
-            }
-            bp.key_inter = h; bp.key_spans = hs; bp.key_bc = hb;
-            memcpy(bp.key_ids, ids, sizeof ids);
-            bp.device = device;
-            it = g_bus_plans.emplace(key, std::move(bpp)).first;
-        }
-        plan = it->second;
-        plan->last_use = ++g_bus_clock;
-    }
+    std::shared_ptr<const BusPlan> plan;
+    if (int rc = g_bus_plans.get({pw::key_part(t.inter, t.n_inter), pw::key_part(t.spans, t.n_spans), pw::key_part(t.bc, t.bc_len),
+                                  pw::key_value(t.ids), pw::key_value(device)},
+                                 [&](BusPlan& bp) { return build_bus_plan(t, table_bins, bp); }, plan))
+        return rc;
     if (plan->total_slots == 0) return (int)hipGetLastError();
-    const bool use_xbc = want_xbc && plan->has_xbc;
-    const char* env_f = getenv("POWDR_BUS_FAST");
-    const bool use_fast = use_xbc && (env_f ? atoi(env_f) != 0 : true);
-    // chunking of an interaction list over blockIdx.y so that short traces still fill the chip
-    auto chunking = [&](uint32_t n_list, unsigned& chunks, uint32_t& per_chunk) {
-        chunks = 1;
-        if (n_list == 0) { per_chunk = 1; return; }
-        if (row_blocks < want_blocks) {
-            chunks = (want_blocks + row_blocks - 1) / row_blocks;
-            const unsigned max_chunks = (n_list + 15) / 16;
-            if (chunks > max_chunks) chunks = max_chunks;
-            if (chunks > 65535u) chunks = 65535u;
-            if (chunks == 0) chunks = 1;
-        }
-        per_chunk = (n_list + chunks - 1) / chunks;
-        chunks = (n_list + per_chunk - 1) / per_chunk;
-    };
-    unsigned xchunks, fchunks = 1;
-    uint32_t x_per_chunk, f_per_chunk = 1;
-    // the interpreter walks: all periphery interactions (xbc), only the non-small-form ones (fast mode), or the
-    // reference's full list (post-fix mode)
-    const XInteraction* x_list = use_fast ? plan->d_xint_slow : plan->d_xint;
-    const uint32_t n_x = use_fast ? plan->n_slow : plan->total_slots;
-    chunking(use_xbc ? n_x : (uint32_t)n_interactions, xchunks, x_per_chunk);
-    if (use_fast) chunking(plan->n_fast, fchunks, f_per_chunk);
-    uint64_t* stats = pw::call_stats();
-    stats[pw::kStatBusFastInteractions] += use_fast ? plan->n_fast : 0;
-    stats[pw::kStatBusInterpretedInteractions] += use_xbc ? n_x : plan->total_slots;
-    stats[pw::kStatBusXbcCalls] += use_xbc ? 1 : 0;
 
-    // ---- long traces: binned path ---------------------------------------------------------------
-    if (want_binned && table_bins[0] <= (1u << kItemBinBits) && table_bins[1] <= (1u << kItemBinBits)) {
+    Walk w;
+    w.trace = d_output; w.num_calls = num_apc_calls; w.col_stride = col_stride;
+    w.p.var_bus = var_range_bus_id; w.p.tuple_bus = tuple2_bus_id; w.p.bitwise_bus = bitwise_bus_id;
+    w.p.var_hist = d_var_hist; w.p.tuple_hist = d_tuple2_hist; w.p.bitwise_hist = d_bitwise_hist;
+    w.p.var_bins = (uint32_t)var_num_bins; w.p.tuple_sz0 = tuple2_sz0; w.p.tuple_sz1 = tuple2_sz1;
+    w.p.slot_range = nullptr;
+    w.d_bytecode = d_bytecode; w.d_interactions = d_interactions; w.n_interactions = (uint32_t)n_interactions; w.d_arg_spans = d_arg_spans;
+    w.use_xbc = knobs.xbc && plan->has_xbc;
+    w.use_fast = w.use_xbc && knobs.fast;
+    w.x_list = (w.use_fast ? plan->xint_slow : plan->xint).as<XInteraction>();
+    w.n_x = w.use_fast ? plan->n_slow : plan->total_slots;
+    const unsigned row_blocks = pw::div_up((size_t)num_apc_calls, kBlock);
+    w.x = chunking(row_blocks, w.use_xbc ? w.n_x : (uint32_t)n_interactions);
+    if (w.use_fast) w.f = chunking(row_blocks, plan->n_fast);
+
+    // ---- stats ----
+    uint64_t* stats = pw::call_stats();
+    stats[pw::kStatBusFastInteractions] += w.use_fast ? plan->n_fast : 0;
+    stats[pw::kStatBusInterpretedInteractions] += w.use_xbc ? w.n_x : plan->total_slots;
+    stats[pw::kStatBusXbcCalls] += w.use_xbc ? 1 : 0;
+
+    // ---- long traces: binned path ----
+    if (knobs.want_binned(num_apc_calls) && table_bins[0] <= (1u << kItemBinBits) && table_bins[1] <= (1u << kItemBinBits)) {
         // rows are processed in windows of at most 2^20 so that the item buffer stays bounded
         // (slots x 4 MiB): a 2^22-row trace with 1 600 periphery interactions would otherwise need 27 GB
         const size_t all_rows = ((size_t)num_apc_calls + 3) & ~(size_t)3;
         const size_t window = all_rows < ((size_t)1 << 20) ? all_rows : ((size_t)1 << 20);
-        const size_t need = (size_t)plan->total_slots * window;
-        bool have = true;
-        if (need > g_items_words || g_items_device != device) {
-            g_items_device = device;
-            if (g_items) (void)hipFree(g_items);
-            g_items = nullptr; g_items_words = 0;
-            if (hipMalloc(&g_items, need * 4) == hipSuccess) g_items_words = need;
-            else { (void)hipGetLastError(); have = false; }
-        }
-        if (have) {
-            uint32_t* tables[3] = {d_var_hist, d_tuple2_hist, d_bitwise_hist};
-            p.slot_range = plan->d_slot_range;
+        if (g_item_buf.ensure(device, (size_t)plan->total_slots * window)) {
+            w.p.slot_range = plan->slot_range.as<uint32_t>();
             for (size_t row0 = 0; row0 < all_rows; row0 += window) {
                 const size_t stride = all_rows - row0 < window ? all_rows - row0 : window;
                 stats[pw::kStatBusBinnedWindows] += 1;
-                {
-                    pw::ScopedKernelTimer t("apc_apply_bus_kernel");
-                    if (use_fast && plan->n_fast)
-                        hipLaunchKernelGGL(apc_apply_bus_fast_kernel<true>, dim3(pw::div_up(stride, kBlock), fchunks), dim3(kBlock), 0,
-                                           pw::stream(), d_output, num_apc_calls, plan->d_fint, plan->n_fast, p, f_per_chunk, g_items,
-                                           stride, col_stride, row0);
-                    if (use_xbc) {
-                        if (n_x)
-                            hipLaunchKernelGGL(apc_apply_bus_xbc_kernel<true>, dim3(pw::div_up(stride, kBlock), xchunks), dim3(kBlock), 0,
-                                               pw::stream(), d_output, num_apc_calls, plan->d_code, x_list, n_x, p, x_per_chunk, g_items,
-                                               stride, col_stride, row0);
-                    } else
-                        hipLaunchKernelGGL(apc_apply_bus_kernel<true>, dim3(pw::div_up(stride, kBlock), xchunks), dim3(kBlock), 0,
-                                           pw::stream(), d_output, num_apc_calls, d_bytecode, d_interactions, (uint32_t)n_interactions,
-                                           d_arg_spans, p, x_per_chunk, plan->d_slot_of, g_items, stride, col_stride, row0);
-                }
-                // one 128-KB-LDS workgroup fits per CU, and the three launches run one after the other, so each
-                // launch gets ~2 x 256 workgroups of its own: partitions x row chunks
-                for (int t = 0; t < 3; ++t) {
-                    if (!plan->n_slots[t]) continue;
-                    const unsigned parts = pw::div_up(table_bins[t], kPartBins);
-                    unsigned n_chunks = (512 + parts - 1) / parts;
-                    const unsigned max_chunks = pw::div_up(stride, 4096);
-                    if (n_chunks > max_chunks) n_chunks = max_chunks;
-                    if (n_chunks == 0) n_chunks = 1;
-                    const uint32_t rows_per_chunk = (uint32_t)(((stride + n_chunks - 1) / n_chunks + 3) & ~(size_t)3);
-                    n_chunks = pw::div_up(stride, rows_per_chunk);
-                    pw::ScopedKernelTimer tt("bus_histogram_kernel");
-                    hipLaunchKernelGGL(bus_histogram_kernel, dim3(parts, n_chunks), dim3(kHistBlock), 0,
-                                       pw::stream(), g_items, stride, plan->d_slots[t], plan->n_slots[t], tables[t], table_bins[t], rows_per_chunk,
-                                       plan->d_slot_range);
-                }
+                launch_walkers<true>(*plan, w, pw::div_up(stride, kBlock), g_item_buf.p, stride, row0);
+                launch_histograms(*plan, g_item_buf.p, stride, tables, table_bins);
             }
             return (int)hipGetLastError();
         }
     }
     stats[pw::kStatBusDirectCalls] += 1;
-    pw::ScopedKernelTimer t("apc_apply_bus_kernel");
-    if (use_fast && plan->n_fast)
-        hipLaunchKernelGGL(apc_apply_bus_fast_kernel<false>, dim3(row_blocks, fchunks), dim3(kBlock), 0, pw::stream(), d_output,
-                           num_apc_calls, plan->d_fint, plan->n_fast, p, f_per_chunk, nullptr, 0, col_stride, 0);
-    if (use_xbc) {
-        if (n_x)
-            hipLaunchKernelGGL(apc_apply_bus_xbc_kernel<false>, dim3(row_blocks, xchunks), dim3(kBlock), 0, pw::stream(),
-                               d_output, num_apc_calls, plan->d_code, x_list, n_x, p, x_per_chunk, nullptr, 0, col_stride, 0);
-    } else
-        hipLaunchKernelGGL(apc_apply_bus_kernel<false>, dim3(row_blocks, xchunks), dim3(kBlock), 0, pw::stream(),
-                           d_output, num_apc_calls, d_bytecode, d_interactions,
-                           (uint32_t)n_interactions, d_arg_spans, p, x_per_chunk, nullptr, nullptr, 0, col_stride, 0);
+    launch_walkers<false>(*plan, w, row_blocks, nullptr, 0, 0);
     return (int)hipGetLastError();
 }
 }  // namespace

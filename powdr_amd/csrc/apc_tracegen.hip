@@ -28,14 +28,14 @@
 // hash: the same APC is replayed for every segment.
 #include "babybear.hpp"
 #include "common.hpp"
+#include "gather_entry.hpp"
+#include "plan_cache.hpp"
 #include "../../include/powdr_gpu.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -69,23 +69,10 @@ struct RClass {
 };
 
 struct Plan {
-    GatherJob* d_jobs = nullptr;
-    PlanSub* d_subs = nullptr;
+    pw::DeviceBuf jobs, subs;  // GatherJob, PlanSub (freed with the plan: hipFree waits for kernels that may still read the tables)
     std::vector<RClass> classes;
     size_t n_jobs = 0, n_subs = 0;
     uint32_t n_sparse = 0, n_whole = 0, n_chunk = 0;  // jobs by form (powdr_gpu_call_stats)
-    // what the plan was built from: a cache hit is confirmed by comparing contents, never by the hash alone
-    std::vector<Subst> key_subs;
-    std::vector<int32_t> key_bsize;
-    int device = 0;           // the device d_jobs / d_subs live on
-    uint64_t last_use = 0;    // for eviction
-    ~Plan() {
-        if (d_jobs) (void)hipFree(d_jobs);  // hipFree waits for kernels that may still read the tables
-        if (d_subs) (void)hipFree(d_subs);
-    }
-    Plan() = default;
-    Plan(const Plan&) = delete;
-    Plan& operator=(const Plan&) = delete;
 };
 
 constexpr int kBlock = 256;
@@ -98,7 +85,6 @@ struct Knobs {
     int sparse = 1;                 // POWDR_GATHER_SPARSE=0: never use the cell-by-cell form
     int sparse_pct = 100;           // ... which must move at most this share of the streaming forms' bytes (POWDR_GATHER_SPARSE_PCT)
     int max_chunk_j() const { return max_tile_words / min_r - 1; }  // 319
-    bool operator==(const Knobs& o) const { return max_tile_words == o.max_tile_words && min_r == o.min_r && sparse == o.sparse && sparse_pct == o.sparse_pct; }
     static Knobs from_env() {
         Knobs k;
         if (const char* e = getenv("POWDR_GATHER_TILE_WORDS")) { const int v = atoi(e); if (v >= 2048 && v <= 16384) k.max_tile_words = v; }
@@ -257,31 +243,8 @@ __global__ __launch_bounds__(kBlock) void apc_gather_tile_kernel(
 // Host: plan construction + cache
 // ---------------------------------------------------------------------------------------------
 
-uint64_t fnv1a(const void* p, size_t n, uint64_t h) {
-    const unsigned char* c = (const unsigned char*)p;
-    for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-    return h;
-}
-
-struct PlanKey {
-    uint64_t hash;
-    size_t n_subs;
-    int device;
-    Knobs knobs;
-    bool operator==(const PlanKey& o) const { return hash == o.hash && n_subs == o.n_subs && device == o.device && knobs == o.knobs; }
-};
-struct PlanKeyHash {
-    size_t operator()(const PlanKey& k) const {
-        return (size_t)(k.hash ^ ((uint64_t)k.device << 56) ^ ((uint64_t)k.knobs.max_tile_words << 20) ^ ((uint64_t)k.knobs.min_r << 8) ^
-                        ((uint64_t)k.knobs.sparse << 40) ^ ((uint64_t)k.knobs.sparse_pct << 44));
-    }
-};
-
-// Plans are shared_ptrs: a launch keeps its plan alive while another host thread evicts it from the (bounded) cache.
-constexpr size_t kMaxCachedPlans = 64;
-std::mutex g_plan_mu;
-std::unordered_map<PlanKey, std::shared_ptr<Plan>, PlanKeyHash> g_plans;
-uint64_t g_plan_clock = 0;
+// keyed by the Subst table, the AIRs' row block sizes, the device and the knobs (plan_cache.hpp)
+pw::PlanCache<Plan> g_plans(64);
 
 int pick_R(int J, const Knobs& kn) {
     int pitch = J | 1;
@@ -290,24 +253,12 @@ int pick_R(int J, const Knobs& kn) {
     return R;
 }
 
-int build_plan(const std::vector<Subst>& subs_in, const std::vector<int32_t>& bsize, const Knobs& kn, Plan& plan) {
+int build_plan(const Subst* subs_in, size_t n, const std::vector<int32_t>& bsize, const Knobs& kn, Plan& plan) {
     const int max_chunk_j = kn.max_chunk_j();
     const bool sparse_jobs = kn.sparse != 0;
     const int sparse_pct = kn.sparse_pct;
-    const size_t n = subs_in.size();
     // 1. resolve duplicate destinations like the sequential reference loop: last wins
-    std::vector<uint32_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
-    std::vector<char> keep(n, 1);
-    {
-        std::unordered_map<int32_t, uint32_t> last;
-        last.reserve(n * 2);
-        for (size_t i = 0; i < n; ++i) {
-            auto it = last.find(subs_in[i].apc_col);
-            if (it != last.end()) keep[it->second] = 0;
-            last[subs_in[i].apc_col] = (uint32_t)i;
-        }
-    }
+    const std::vector<char> keep = pw::last_wins(n, [&](size_t i) { return subs_in[i].apc_col; });
     // 2. sort by (air, col, row)
     std::vector<uint32_t> idx;
     idx.reserve(n);
@@ -413,10 +364,8 @@ int build_plan(const std::vector<Subst>& subs_in, const std::vector<int32_t>& bs
     plan.n_jobs = sorted.size();
     plan.n_subs = psubs.size();
     if (plan.n_jobs) {
-        PW_HIP_TRY(hipMalloc(&plan.d_jobs, sorted.size() * sizeof(GatherJob)));
-        PW_HIP_TRY(hipMalloc(&plan.d_subs, psubs.size() * sizeof(PlanSub)));
-        PW_HIP_TRY(hipMemcpy(plan.d_jobs, sorted.data(), sorted.size() * sizeof(GatherJob), hipMemcpyHostToDevice));
-        PW_HIP_TRY(hipMemcpy(plan.d_subs, psubs.data(), psubs.size() * sizeof(PlanSub), hipMemcpyHostToDevice));
+        if (int rc = pw::upload_table(plan.jobs, sorted.data(), sorted.size())) return rc;
+        if (int rc = pw::upload_table(plan.subs, psubs.data(), psubs.size())) return rc;
     }
     return 0;
 }
@@ -430,56 +379,28 @@ void launch_class(const RClass& c, uint32_t* out, size_t H, const OriginalAir* a
         uint32_t cnt = std::min<uint32_t>(65535u, c.job_count - j);
         dim3 grid(tiles, cnt, 1);
         hipLaunchKernelGGL(apc_gather_tile_kernel<R>, grid, dim3(kBlock), c.lds_bytes, pw::stream(),
-                           out, H, airs, plan.d_jobs + c.job_begin + j, plan.d_subs, num_calls, inl, use_inl);
+                           out, H, airs, plan.jobs.as<GatherJob>() + c.job_begin + j, plan.subs.as<PlanSub>(), num_calls, inl, use_inl);
     }
 }
 
 }  // namespace
 
-// The gather proper: `subs` / `bsize` are host copies of the Subst table and of the AIRs' row_block_size; the kernels read
+// The gather proper: `subs` / `bsize` are the Subst table and the AIRs' row_block_size on the host; the kernels read
 // the OriginalAir records (buffer pointers, heights) from the device table.
 static int tracegen_with_host_tables(PowdrFp* d_output, size_t H, const OriginalAir* d_original_airs,
-                                     const std::vector<Subst>& subs, const std::vector<int32_t>& bsize, int num_apc_calls,
+                                     const Subst* subs, size_t n_subs, const std::vector<int32_t>& bsize, int num_apc_calls,
                                      const OriginalAir* h_airs = nullptr, size_t n_h_airs = 0) {
-    const size_t n_subs = subs.size();
     InlineAirs inl{};
     const int use_inl = h_airs && n_h_airs <= (size_t)kInlineAirs ? 1 : 0;
     if (use_inl) memcpy(inl.a, h_airs, n_h_airs * sizeof(OriginalAir));
     if (!use_inl && !d_original_airs) return (int)hipErrorInvalidValue;
     const Knobs knobs = Knobs::from_env();
-    uint64_t h = fnv1a(subs.data(), n_subs * sizeof(Subst), 1469598103934665603ull);
-    h = fnv1a(bsize.data(), bsize.size() * sizeof(int32_t), h);
     int device = 0;
     PW_HIP_TRY(hipGetDevice(&device));
-    const PlanKey key{h, n_subs, device, knobs};
-
-    std::shared_ptr<Plan> plan;
-    {
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        auto it = g_plans.find(key);
-        if (it != g_plans.end()) {
-            const Plan& c = *it->second;
-            const bool same = c.key_subs.size() == n_subs && c.key_bsize == bsize &&
-                              (n_subs == 0 || memcmp(c.key_subs.data(), subs.data(), n_subs * sizeof(Subst)) == 0);
-            if (!same) { g_plans.erase(it); it = g_plans.end(); }  // 64-bit hash collision: the newer table takes the slot
-        }
-        if (it == g_plans.end()) {
-            if (g_plans.size() >= kMaxCachedPlans) {  // evict the least recently used plan
-                auto victim = g_plans.begin();
-                for (auto j = g_plans.begin(); j != g_plans.end(); ++j) if (j->second->last_use < victim->second->last_use) victim = j;
-                g_plans.erase(victim);
-            }
-            auto p = std::make_shared<Plan>();
-            int rc = build_plan(subs, bsize, knobs, *p);
-            if (rc) return rc;
-            p->key_subs = subs;
-            p->key_bsize = bsize;
-            p->device = device;
-            it = g_plans.emplace(key, std::move(p)).first;
-        }
-        plan = it->second;
-        plan->last_use = ++g_plan_clock;
-    }
+    std::shared_ptr<const Plan> plan;
+    if (int rc = g_plans.get({pw::key_part(subs, n_subs), pw::key_part(bsize), pw::key_value(device), pw::key_value(knobs)},
+                             [&](Plan& p) { return build_plan(subs, n_subs, bsize, knobs, p); }, plan))
+        return rc;
 
     {
         uint64_t* st = pw::call_stats();
@@ -505,9 +426,10 @@ static int tracegen_with_host_tables(PowdrFp* d_output, size_t H, const Original
     return (int)hipGetLastError();
 }
 
-static int check_tables(const std::vector<Subst>& subs, size_t n_airs_known, int& max_air) {
+static int check_tables(const Subst* subs, size_t n_subs, size_t n_airs_known, int& max_air) {
     max_air = -1;
-    for (auto& s : subs) {
+    for (size_t i = 0; i < n_subs; ++i) {
+        const Subst& s = subs[i];
         if (s.air_index < 0 || s.col < 0 || s.row < 0 || s.apc_col < 0) return (int)hipErrorInvalidValue;
         max_air = std::max(max_air, s.air_index);
     }
@@ -519,12 +441,8 @@ constexpr size_t kAirCountUnknown = 0;  // _apc_tracegen: the table's length is 
 extern "C" int _apc_tracegen(PowdrFp* d_output, size_t output_height,
                              const OriginalAir* d_original_airs, const Subst* d_subs,
                              size_t n_subs, int num_apc_calls) {
-    (void)hipGetLastError();  // do not report a stale error of an unrelated earlier call
     const size_t H = output_height;
-    if ((H & (H - 1)) != 0) return (int)hipErrorInvalidValue;  // reference: assert, apc_tracegen.cu:134
-    if (H == 0 || n_subs == 0) return (int)hipGetLastError();
-    if (num_apc_calls < 0) num_apc_calls = 0;
-    if ((size_t)num_apc_calls > H) num_apc_calls = (int)H;  // rows r >= H do not exist
+    if (int rc = pw::gather_opening(H, n_subs, &num_apc_calls); rc != pw::kGatherProceeds) return rc;
 
     // The reference ABI hands over device tables only: D2H the (small) tables to look the plan up. Hosts that still hold
     // the tables (powdr_apc_generate_witness_gpu does) call powdr_apc_tracegen_host_tables and skip both round trips.
@@ -532,7 +450,7 @@ extern "C" int _apc_tracegen(PowdrFp* d_output, size_t output_height,
     PW_HIP_TRY(hipMemcpyAsync(subs.data(), d_subs, n_subs * sizeof(Subst), hipMemcpyDeviceToHost, pw::stream()));
     PW_HIP_TRY(hipStreamSynchronize(pw::stream()));
     int max_air = -1;
-    if (int rc = check_tables(subs, kAirCountUnknown, max_air)) return rc;
+    if (int rc = check_tables(subs.data(), n_subs, kAirCountUnknown, max_air)) return rc;
     std::vector<OriginalAir> airs((size_t)max_air + 1);
     PW_HIP_TRY(hipMemcpyAsync(airs.data(), d_original_airs, airs.size() * sizeof(OriginalAir), hipMemcpyDeviceToHost, pw::stream()));
     PW_HIP_TRY(hipStreamSynchronize(pw::stream()));
@@ -541,7 +459,7 @@ extern "C" int _apc_tracegen(PowdrFp* d_output, size_t output_height,
         bsize[i] = airs[i].row_block_size;
         if (bsize[i] < 0) return (int)hipErrorInvalidValue;
     }
-    return tracegen_with_host_tables(d_output, H, d_original_airs, subs, bsize, num_apc_calls);
+    return tracegen_with_host_tables(d_output, H, d_original_airs, subs.data(), n_subs, bsize, num_apc_calls);
 }
 
 // Extension (not in the reference ABI): the same gather for a caller that still has the tables on the host — the
@@ -550,23 +468,18 @@ extern "C" int _apc_tracegen(PowdrFp* d_output, size_t output_height,
 extern "C" int powdr_apc_tracegen_host_tables(PowdrFp* d_output, size_t output_height, const OriginalAir* d_original_airs,
                                               const OriginalAir* h_original_airs, size_t n_airs, const Subst* h_subs,
                                               size_t n_subs, int num_apc_calls) {
-    (void)hipGetLastError();
     const size_t H = output_height;
-    if ((H & (H - 1)) != 0) return (int)hipErrorInvalidValue;
-    if (H == 0 || n_subs == 0) return (int)hipGetLastError();
+    if (int rc = pw::gather_opening(H, n_subs, &num_apc_calls); rc != pw::kGatherProceeds) return rc;
     if (!h_original_airs || !h_subs) return (int)hipErrorInvalidValue;
-    if (num_apc_calls < 0) num_apc_calls = 0;
-    if ((size_t)num_apc_calls > H) num_apc_calls = (int)H;
-    std::vector<Subst> subs(h_subs, h_subs + n_subs);
     int max_air = -1;
-    if (int rc = check_tables(subs, kAirCountUnknown, max_air)) return rc;
+    if (int rc = check_tables(h_subs, n_subs, kAirCountUnknown, max_air)) return rc;
     if ((size_t)max_air >= n_airs) return (int)hipErrorInvalidValue;  // also n_airs == 0 with substitutions present
     std::vector<int32_t> bsize(n_airs);
     for (size_t i = 0; i < n_airs; ++i) {
         bsize[i] = h_original_airs[i].row_block_size;
         if (bsize[i] < 0) return (int)hipErrorInvalidValue;
     }
-    return tracegen_with_host_tables(d_output, H, d_original_airs, subs, bsize, num_apc_calls, h_original_airs, n_airs);
+    return tracegen_with_host_tables(d_output, H, d_original_airs, h_subs, n_subs, bsize, num_apc_calls, h_original_airs, n_airs);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -613,29 +526,42 @@ __global__ __launch_bounds__(256) void apc_gather_callmajor_kernel(uint32_t* __r
 }
 
 struct CMPlan {
-    CMJob* d_jobs = nullptr;
-    int32_t* d_col_of = nullptr;
+    pw::DeviceBuf jobs, col_of;  // CMJob (+1 entry), int32_t (never empty)
     size_t n_jobs = 0;
-    std::vector<PowdrSubstCM> key_subs;
-    std::vector<int32_t> key_cells;
-    int device = 0;
-    uint64_t last_use = 0;
-    ~CMPlan() { if (d_jobs) (void)hipFree(d_jobs); if (d_col_of) (void)hipFree(d_col_of); }
 };
-std::mutex g_cm_mu;
-std::unordered_map<uint64_t, std::shared_ptr<CMPlan>> g_cm_plans;
-uint64_t g_cm_clock = 0;
+// keyed by the PowdrSubstCM table, the AIRs' cells per call and the device
+pw::PlanCache<CMPlan> g_cm_plans(64);
+
+int build_cm_plan(const PowdrSubstCM* h_subs, size_t n_subs, const std::vector<int32_t>& cells, CMPlan& p) {
+    const size_t n_airs = cells.size();
+    // slot -> APC column per AIR
+    std::vector<size_t> off(n_airs + 1, 0);
+    for (size_t a = 0; a < n_airs; ++a) off[a + 1] = off[a] + (size_t)cells[a];
+    std::vector<int32_t> col_of(off[n_airs] ? off[n_airs] : 1, -1);
+    const std::vector<char> keep = pw::last_wins(n_subs, [&](size_t i) { return h_subs[i].apc_col; });
+    for (size_t i = 0; i < n_subs; ++i)
+        if (keep[i]) {
+            int32_t& dst = col_of[off[h_subs[i].air_index] + h_subs[i].slot];
+            // one slot, one APC column: a producer that feeds two columns from one cell writes it into two slots
+            if (dst >= 0 && dst != h_subs[i].apc_col) return (int)hipErrorInvalidValue;
+            dst = h_subs[i].apc_col;
+        }
+    std::vector<CMJob> jobs;
+    for (size_t a = 0; a < n_airs; ++a)
+        for (int32_t s0 = 0; s0 < cells[a]; s0 += 64)
+            jobs.push_back({(int32_t)a, s0, (int32_t)off[a], std::min<int32_t>(64, cells[a] - s0)});
+    p.n_jobs = jobs.size();
+    if (int rc = pw::upload_table(p.jobs, jobs.data(), jobs.size(), 1)) return rc;
+    return pw::upload_table(p.col_of, col_of.data(), col_of.size());
+}
 
 }  // namespace
 
 extern "C" int powdr_apc_tracegen_callmajor(PowdrFp* d_output, size_t output_height, const PowdrCallMajorAir* h_airs, size_t n_airs,
                                             const PowdrSubstCM* h_subs, size_t n_subs, int num_apc_calls) {
-    (void)hipGetLastError();
     const size_t H = output_height;
-    if ((H & (H - 1)) != 0 || n_airs > (size_t)kCmMaxAirs || (n_subs && (!h_airs || !h_subs))) return (int)hipErrorInvalidValue;
-    if (H == 0 || n_subs == 0) return (int)hipGetLastError();
-    if (num_apc_calls < 0) num_apc_calls = 0;
-    if ((size_t)num_apc_calls > H) num_apc_calls = (int)H;
+    if (n_airs > (size_t)kCmMaxAirs || (n_subs && (!h_airs || !h_subs))) return (int)hipErrorInvalidValue;
+    if (int rc = pw::gather_opening(H, n_subs, &num_apc_calls); rc != pw::kGatherProceeds) return rc;
     std::vector<int32_t> cells(n_airs);
     CMAirs airs{};
     for (size_t a = 0; a < n_airs; ++a) {
@@ -648,63 +574,18 @@ extern "C" int powdr_apc_tracegen_callmajor(PowdrFp* d_output, size_t output_hei
         if (h_subs[i].air_index < 0 || (size_t)h_subs[i].air_index >= n_airs || h_subs[i].slot < 0 ||
             h_subs[i].slot >= cells[h_subs[i].air_index] || h_subs[i].apc_col < 0)
             return (int)hipErrorInvalidValue;
-    uint64_t key = fnv1a(h_subs, n_subs * sizeof(PowdrSubstCM), 1469598103934665603ull);
-    key = fnv1a(cells.data(), cells.size() * 4, key);
     int device = 0;
     PW_HIP_TRY(hipGetDevice(&device));
-    key = fnv1a(&device, sizeof device, key);
-    std::shared_ptr<CMPlan> plan;
-    {
-        std::lock_guard<std::mutex> lk(g_cm_mu);
-        auto it = g_cm_plans.find(key);
-        if (it != g_cm_plans.end()) {
-            const CMPlan& c = *it->second;
-            if (c.device != device || c.key_cells != cells || c.key_subs.size() != n_subs ||
-                memcmp(c.key_subs.data(), h_subs, n_subs * sizeof(PowdrSubstCM)) != 0) { g_cm_plans.erase(it); it = g_cm_plans.end(); }
-        }
-        if (it == g_cm_plans.end()) {
-            if (g_cm_plans.size() >= kMaxCachedPlans) {
-                auto victim = g_cm_plans.begin();
-                for (auto j = g_cm_plans.begin(); j != g_cm_plans.end(); ++j) if (j->second->last_use < victim->second->last_use) victim = j;
-                g_cm_plans.erase(victim);
-            }
-            auto p = std::make_shared<CMPlan>();
-            // slot -> APC column per AIR (duplicate destinations resolve like the sequential reference loop: the last Subst wins)
-            std::vector<size_t> off(n_airs + 1, 0);
-            for (size_t a = 0; a < n_airs; ++a) off[a + 1] = off[a] + (size_t)cells[a];
-            std::vector<int32_t> col_of(off[n_airs] ? off[n_airs] : 1, -1);
-            std::unordered_map<int32_t, size_t> last;
-            for (size_t i = 0; i < n_subs; ++i) last[h_subs[i].apc_col] = i;
-            for (size_t i = 0; i < n_subs; ++i)
-                if (last[h_subs[i].apc_col] == i) {
-                    int32_t& dst = col_of[off[h_subs[i].air_index] + h_subs[i].slot];
-                    // one slot, one APC column: a producer that feeds two columns from one cell writes it into two slots
-                    if (dst >= 0 && dst != h_subs[i].apc_col) return (int)hipErrorInvalidValue;
-                    dst = h_subs[i].apc_col;
-                }
-            std::vector<CMJob> jobs;
-            for (size_t a = 0; a < n_airs; ++a)
-                for (int32_t s0 = 0; s0 < cells[a]; s0 += 64)
-                    jobs.push_back({(int32_t)a, s0, (int32_t)off[a], std::min<int32_t>(64, cells[a] - s0)});
-            p->n_jobs = jobs.size();
-            PW_HIP_TRY(hipMalloc(&p->d_jobs, (jobs.size() + 1) * sizeof(CMJob)));
-            PW_HIP_TRY(hipMalloc(&p->d_col_of, col_of.size() * 4));
-            if (!jobs.empty()) PW_HIP_TRY(hipMemcpy(p->d_jobs, jobs.data(), jobs.size() * sizeof(CMJob), hipMemcpyHostToDevice));
-            PW_HIP_TRY(hipMemcpy(p->d_col_of, col_of.data(), col_of.size() * 4, hipMemcpyHostToDevice));
-            p->key_subs.assign(h_subs, h_subs + n_subs);
-            p->key_cells = cells;
-            p->device = device;
-            it = g_cm_plans.emplace(key, std::move(p)).first;
-        }
-        plan = it->second;
-        plan->last_use = ++g_cm_clock;
-    }
+    std::shared_ptr<const CMPlan> plan;
+    if (int rc = g_cm_plans.get({pw::key_part(h_subs, n_subs), pw::key_part(cells), pw::key_value(device)},
+                                [&](CMPlan& p) { return build_cm_plan(h_subs, n_subs, cells, p); }, plan))
+        return rc;
     pw::ScopedKernelTimer t("apc_gather_callmajor_kernel");
     const unsigned row_tiles = pw::div_up(H, 64);
     for (size_t j = 0; j < plan->n_jobs; j += 65535) {
         const unsigned cnt = (unsigned)std::min<size_t>(65535, plan->n_jobs - j);
-        hipLaunchKernelGGL(apc_gather_callmajor_kernel, dim3(row_tiles, cnt), dim3(256), 0, pw::stream(), d_output, H, airs, plan->d_jobs + j,
-                           plan->d_col_of, num_apc_calls);
+        hipLaunchKernelGGL(apc_gather_callmajor_kernel, dim3(row_tiles, cnt), dim3(256), 0, pw::stream(), d_output, H, airs,
+                           plan->jobs.as<CMJob>() + j, plan->col_of.as<int32_t>(), num_apc_calls);
     }
     return (int)hipGetLastError();
 }

@@ -45,6 +45,39 @@ inline uint32_t ceil_log2_at_least_1(unsigned long long rows) {
     return lh;
 }
 
+struct DeviceBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int device = -1;  // the device the buffer lives on: a host thread (thread_local contexts) may have moved to another GPU
+    int ensure(size_t need) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return (int)e;
+        if (p && dev == device && need <= bytes) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        e = hipMalloc(&p, need);
+        if (e != hipSuccess) return (int)e;
+        bytes = need;
+        device = dev;
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf&) = delete;
+    DeviceBuf& operator=(const DeviceBuf&) = delete;
+    ~DeviceBuf() { release(); }  // thread_local owners (per-thread segment contexts) give their memory back when the thread exits
+};
+
+// a small host table into a buffer of its own, with `slack` spare entries at its end that kernels may read
+template <class T>
+inline int upload_table(DeviceBuf& b, const T* v, size_t n, size_t slack = 0) {
+    if (int rc = b.ensure((n + slack) * sizeof(T))) return rc;
+    if (n) PW_HIP_TRY(hipMemcpy(b.p, v, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // Which code paths the calling thread's library calls took (powdr_gpu_call_stats): parity tests assert that a workload
 // really exercised the job forms / kernels it is meant to cover instead of inferring it from sizes.
 enum CallStat : int {

@@ -2,6 +2,7 @@
 #include "../../../include/powdr_host.h"
 #include "../common.hpp"
 #include "../original_chips_tables.hpp"
+#include "../plan_cache.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -293,22 +294,18 @@ struct PowdrApc {
         std::shared_ptr<const std::vector<ExprSpan>> h_spans;
     };
     std::map<std::pair<int, size_t>, Compiled> compiled;  // (device, height): one process may drive several GPUs
-    // substitution tables keyed by the instr_air assignment hash (host only: the gather takes them from the host)
+    // substitution tables keyed by the instr_air assignment (host only: the gather takes them from the host)
     struct SubTables { std::vector<Subst> subs; std::vector<int32_t> air_ids, row_block; };
-    std::map<uint64_t, SubTables> sub_tables;
+    pw::PlanCache<SubTables> sub_tables{16};
     // OriginalAir tables reach the gather as kernel arguments (powdr_apc_tracegen_host_tables, <= 16 AIRs). Only an APC
-    // gathered from more AIRs than that needs a device copy: keyed by (device, content), immutable once uploaded, held by
+    // gathered from more AIRs than that needs a device copy: keyed by (content, device), immutable once uploaded, held by
     // shared_ptr so that a launch keeps its table alive while another host thread evicts it from the bounded cache.
-    struct AirTable {
-        std::vector<OriginalAir> h; OriginalAir* d = nullptr; int device = 0; uint64_t last_use = 0;
-        ~AirTable() { if (d) (void)hipFree(d); }  // hipFree waits for the kernels already enqueued that read it
-    };
-    std::vector<std::shared_ptr<AirTable>> air_tables;
+    struct AirTable { pw::DeviceBuf d; };  // OriginalAir; hipFree waits for the kernels already enqueued that read it
+    pw::PlanCache<AirTable> air_tables{16};
     // instruction table + record substitutions of the block (powdr_apc_generate_witness_from_records), built at first use
     struct RecordTables { std::vector<PowdrOrigInstr> instrs; std::vector<PowdrRecordSubst> subs; };
     std::shared_ptr<const RecordTables> record_tables;
-    uint64_t air_clock = 0;
-    std::mutex mu;  // guards the three caches (lookups and insertions; launches run outside it)
+    std::mutex mu;  // guards `compiled` and `record_tables` (lookups and insertions; launches run outside it)
 
     ~PowdrApc() {
         for (auto& kv : compiled) {
@@ -470,7 +467,6 @@ DerivedTables compile_derived(const PowdrApc& apc, size_t h) {
     return t;
 }
 
-uint64_t fnv(const void* p, size_t n) { uint64_t h = 1469598103934665603ull; auto c = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; } return h; }
 
 }  // namespace
 
@@ -837,55 +833,33 @@ int powdr_apc_generate_witness_gpu(PowdrApc* apc, const int32_t* instr_air, cons
     int rc = 0;
     int device = 0;
     PW_HIP_TRY(hipGetDevice(&device));
-    const PowdrApc::SubTables* stb_p = nullptr;
-    std::shared_ptr<PowdrApc::AirTable> air_table;  // only for more than 16 AIRs; alive until the launch is enqueued
-    std::vector<OriginalAir> airs;
-    {
-        std::lock_guard<std::mutex> lk(apc->mu);
-        uint64_t key = fnv(instr_air, apc->instructions.size() * sizeof(int32_t));
-        auto it = apc->sub_tables.find(key);
-        if (it == apc->sub_tables.end()) {
-            PowdrApc::SubTables t;
-            size_t n_airs = 0;
-            size_t n = powdr_apc_build_substitutions(apc, instr_air, nullptr, nullptr, nullptr, &n_airs);
-            t.subs.resize(n); t.air_ids.resize(n_airs); t.row_block.resize(n_airs);
-            powdr_apc_build_substitutions(apc, instr_air, t.subs.data(), t.air_ids.data(), t.row_block.data(), &n_airs);
-            it = apc->sub_tables.emplace(key, std::move(t)).first;
-        }
-        stb_p = &it->second;  // std::map nodes are stable; entries are never erased
-        const PowdrApc::SubTables& stb = *stb_p;
-        airs.resize(stb.air_ids.size());
-        for (size_t k = 0; k < airs.size(); ++k) {
-            int32_t id = stb.air_ids[k];
-            if (id < 0 || (size_t)id >= n_dummy) return -1;
-            memset(&airs[k], 0, sizeof(OriginalAir));  // padding bytes take part in the content compare
-            airs[k].width = dummy[id].width; airs[k].height = dummy[id].height; airs[k].buffer = dummy[id].buffer;
-            airs[k].row_block_size = stb.row_block[k];
-        }
-        if (airs.size() > 16) {
-            for (auto& t : apc->air_tables)
-                if (t->device == device && t->h.size() == airs.size() && memcmp(t->h.data(), airs.data(), airs.size() * sizeof(OriginalAir)) == 0) { air_table = t; break; }
-            if (!air_table) {
-                if (apc->air_tables.size() >= 16) {  // bounded: drop the least recently used table (a launch in flight holds its own reference)
-                    size_t v = 0;
-                    for (size_t k = 1; k < apc->air_tables.size(); ++k) if (apc->air_tables[k]->last_use < apc->air_tables[v]->last_use) v = k;
-                    apc->air_tables.erase(apc->air_tables.begin() + (long)v);
-                }
-                air_table = std::make_shared<PowdrApc::AirTable>();
-                air_table->h = airs;
-                air_table->device = device;
-                PW_HIP_TRY(hipMalloc((void**)&air_table->d, airs.size() * sizeof(OriginalAir)));
-                PW_HIP_TRY(hipMemcpy(air_table->d, airs.data(), airs.size() * sizeof(OriginalAir), hipMemcpyHostToDevice));
-                apc->air_tables.push_back(air_table);
-            }
-            air_table->last_use = ++apc->air_clock;
-        }
+    std::shared_ptr<const PowdrApc::SubTables> stb;
+    rc = apc->sub_tables.get({pw::key_part(instr_air, apc->instructions.size())}, [&](PowdrApc::SubTables& t) {
+        size_t n_airs = 0;
+        size_t n = powdr_apc_build_substitutions(apc, instr_air, nullptr, nullptr, nullptr, &n_airs);
+        t.subs.resize(n); t.air_ids.resize(n_airs); t.row_block.resize(n_airs);
+        powdr_apc_build_substitutions(apc, instr_air, t.subs.data(), t.air_ids.data(), t.row_block.data(), &n_airs);
+        return 0;
+    }, stb);
+    if (rc) return rc;
+    std::vector<OriginalAir> airs(stb->air_ids.size());
+    for (size_t k = 0; k < airs.size(); ++k) {
+        int32_t id = stb->air_ids[k];
+        if (id < 0 || (size_t)id >= n_dummy) return -1;
+        memset(&airs[k], 0, sizeof(OriginalAir));  // padding bytes take part in the content compare
+        airs[k].width = dummy[id].width; airs[k].height = dummy[id].height; airs[k].buffer = dummy[id].buffer;
+        airs[k].row_block_size = stb->row_block[k];
     }
-    const PowdrApc::SubTables& stb = *stb_p;
+    std::shared_ptr<const PowdrApc::AirTable> air_table;  // only for more than 16 AIRs; alive until the launch is enqueued
+    if (airs.size() > 16) {
+        rc = apc->air_tables.get({pw::key_part(airs), pw::key_value(device)},
+                                 [&](PowdrApc::AirTable& t) { return pw::upload_table(t.d, airs.data(), airs.size()); }, air_table);
+        if (rc) return rc;
+    }
     // host copies of both tables are at hand: no device-to-host round trip to find the gather plan, and (<= 16 AIRs) no
     // device table at all — the records travel as kernel arguments
-    rc = powdr_apc_tracegen_host_tables(d_output, height, air_table ? air_table->d : nullptr, airs.data(), airs.size(), stb.subs.data(),
-                                        stb.subs.size(), (int)num_calls);
+    rc = powdr_apc_tracegen_host_tables(d_output, height, air_table ? air_table->d.as<OriginalAir>() : nullptr, airs.data(), airs.size(),
+                                        stb->subs.data(), stb->subs.size(), (int)num_calls);
     if (rc) return rc;
     return apply_derived_and_bus(apc, height, num_calls, d_output, per);
 }

@@ -18,13 +18,13 @@
 // Record layout: include/powdr_gpu.h (PowdrOrigInstr); ours, since the reference's DenseRecordArena layouts are EXTERNAL.
 #include "babybear.hpp"
 #include "common.hpp"
+#include "gather_entry.hpp"
+#include "plan_cache.hpp"
 #include "../../include/powdr_gpu.h"
 #include "original_chips_tables.hpp"
 
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -426,27 +426,10 @@ __global__ __launch_bounds__(kCalls) void apc_tracegen_records_kernel(uint32_t* 
 
 // device copies of an instruction table (+ substitutions), cached by content
 struct RecordPlan {
-    PowdrOrigInstr* d_instrs = nullptr;
-    uint64_t* d_wanted = nullptr;
-    uint32_t* d_dst = nullptr;
-    std::vector<PowdrOrigInstr> key_instrs;
-    std::vector<PowdrRecordSubst> key_subs;
-    int device = 0;
-    uint64_t last_use = 0;
-    ~RecordPlan() {
-        for (void* q : {(void*)d_instrs, (void*)d_wanted, (void*)d_dst}) if (q) (void)hipFree(q);
-    }
+    pw::DeviceBuf instrs, wanted, dst;  // PowdrOrigInstr (+1 entry), uint64_t and uint32_t x kDstStride per instruction (+1)
 };
-std::mutex g_mu;
-std::unordered_map<uint64_t, std::shared_ptr<RecordPlan>> g_plans;
-uint64_t g_clock = 0;
-constexpr size_t kMaxPlans = 32;
-
-uint64_t fnv(const void* p, size_t n, uint64_t h) {
-    const unsigned char* c = (const unsigned char*)p;
-    for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-    return h;
-}
+// keyed by the instruction table, the substitutions and the device (plan_cache.hpp)
+pw::PlanCache<RecordPlan> g_plans(32);
 
 int check_instrs(const PowdrOrigInstr* h_instrs, size_t n) {
     for (size_t i = 0; i < n; ++i) {
@@ -457,56 +440,30 @@ int check_instrs(const PowdrOrigInstr* h_instrs, size_t n) {
     return 0;
 }
 
-int get_plan(const PowdrOrigInstr* h_instrs, size_t n_instrs, const PowdrRecordSubst* h_subs, size_t n_subs, std::shared_ptr<RecordPlan>& out) {
+// per instruction: which columns leave (bit mask) and where to (dst[instr * 64 + col]). One source cell has one destination (the
+// reference's Subst maps an original column to at most one APC column, cuda/mod.rs:272-328)
+int build_record_plan(const PowdrOrigInstr* h_instrs, size_t n_instrs, const PowdrRecordSubst* h_subs, size_t n_subs, RecordPlan& p) {
+    const std::vector<char> keep = pw::last_wins(n_subs, [&](size_t i) { return h_subs[i].apc_col; });
+    std::vector<uint64_t> wanted(n_instrs + 1, 0);
+    std::vector<uint32_t> dst((n_instrs + 1) * (size_t)kDstStride, 0);
+    for (size_t i = 0; i < n_subs; ++i) {
+        if (!keep[i]) continue;
+        const size_t ins = (size_t)h_subs[i].instr;
+        const uint64_t bit = 1ull << h_subs[i].col;
+        if (wanted[ins] & bit) return (int)hipErrorInvalidValue;  // the same cell to two APC columns
+        wanted[ins] |= bit;
+        dst[ins * kDstStride + (size_t)h_subs[i].col] = (uint32_t)h_subs[i].apc_col;
+    }
+    if (int rc = pw::upload_table(p.instrs, h_instrs, n_instrs, 1)) return rc;
+    if (int rc = pw::upload_table(p.wanted, wanted.data(), wanted.size())) return rc;
+    return pw::upload_table(p.dst, dst.data(), dst.size());
+}
+
+int get_plan(const PowdrOrigInstr* h_instrs, size_t n_instrs, const PowdrRecordSubst* h_subs, size_t n_subs, std::shared_ptr<const RecordPlan>& out) {
     int device = 0;
     PW_HIP_TRY(hipGetDevice(&device));
-    uint64_t key = fnv(h_instrs, n_instrs * sizeof(PowdrOrigInstr), 1469598103934665603ull);
-    key = fnv(h_subs, n_subs * sizeof(PowdrRecordSubst), key);
-    key = fnv(&device, sizeof device, key);
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) {
-        const RecordPlan& c = *it->second;
-        if (c.device != device || c.key_instrs.size() != n_instrs || c.key_subs.size() != n_subs ||
-            memcmp(c.key_instrs.data(), h_instrs, n_instrs * sizeof(PowdrOrigInstr)) != 0 ||
-            (n_subs && memcmp(c.key_subs.data(), h_subs, n_subs * sizeof(PowdrRecordSubst)) != 0)) { g_plans.erase(it); it = g_plans.end(); }
-    }
-    if (it == g_plans.end()) {
-        if (g_plans.size() >= kMaxPlans) {
-            auto victim = g_plans.begin();
-            for (auto j = g_plans.begin(); j != g_plans.end(); ++j) if (j->second->last_use < victim->second->last_use) victim = j;
-            g_plans.erase(victim);
-        }
-        auto p = std::make_shared<RecordPlan>();
-        // per instruction: which columns leave (bit mask) and where to (dst[instr * 64 + col]). Duplicate destinations resolve like the
-        // sequential reference loop: the last wins; one source cell has one destination (the reference's Subst maps an original column to
-        // at most one APC column, cuda/mod.rs:272-328)
-        std::unordered_map<int32_t, size_t> last;
-        for (size_t i = 0; i < n_subs; ++i) last[h_subs[i].apc_col] = i;
-        std::vector<uint64_t> wanted(n_instrs + 1, 0);
-        std::vector<uint32_t> dst((n_instrs + 1) * (size_t)kDstStride, 0);
-        for (size_t i = 0; i < n_subs; ++i) {
-            if (last[h_subs[i].apc_col] != i) continue;
-            const size_t ins = (size_t)h_subs[i].instr;
-            const uint64_t bit = 1ull << h_subs[i].col;
-            if (wanted[ins] & bit) return (int)hipErrorInvalidValue;  // the same cell to two APC columns
-            wanted[ins] |= bit;
-            dst[ins * kDstStride + (size_t)h_subs[i].col] = (uint32_t)h_subs[i].apc_col;
-        }
-        PW_HIP_TRY(hipMalloc(&p->d_instrs, (n_instrs + 1) * sizeof(PowdrOrigInstr)));
-        PW_HIP_TRY(hipMalloc(&p->d_wanted, wanted.size() * 8));
-        PW_HIP_TRY(hipMalloc(&p->d_dst, dst.size() * 4));
-        if (n_instrs) PW_HIP_TRY(hipMemcpy(p->d_instrs, h_instrs, n_instrs * sizeof(PowdrOrigInstr), hipMemcpyHostToDevice));
-        PW_HIP_TRY(hipMemcpy(p->d_wanted, wanted.data(), wanted.size() * 8, hipMemcpyHostToDevice));
-        PW_HIP_TRY(hipMemcpy(p->d_dst, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
-        p->key_instrs.assign(h_instrs, h_instrs + n_instrs);
-        p->key_subs.assign(h_subs, h_subs + n_subs);
-        p->device = device;
-        it = g_plans.emplace(key, std::move(p)).first;
-    }
-    out = it->second;
-    out->last_use = ++g_clock;
-    return 0;
+    return g_plans.get({pw::key_part(h_instrs, n_instrs), pw::key_part(h_subs, n_subs), pw::key_value(device)},
+                       [&](RecordPlan& p) { return build_record_plan(h_instrs, n_instrs, h_subs, n_subs, p); }, out);
 }
 
 }  // namespace
@@ -530,23 +487,21 @@ extern "C" int powdr_original_airs_expand(const uint32_t* d_records, size_t num_
             (size_t)a.row_block_size * num_calls > (size_t)a.height)
             return (int)hipErrorInvalidValue;
     }
-    std::shared_ptr<RecordPlan> plan;
+    std::shared_ptr<const RecordPlan> plan;
     if (int rc = get_plan(h_instrs, n_instrs, nullptr, 0, plan)) return rc;
     pw::ScopedKernelTimer t("original_airs_expand_kernel");
     for (size_t i0 = 0; i0 < n_instrs; i0 += 65535) {
         const unsigned cnt = (unsigned)std::min<size_t>(65535, n_instrs - i0);
         hipLaunchKernelGGL(original_airs_expand_kernel, dim3(pw::div_up(num_calls, kCalls), cnt), dim3(kCalls), 0, pw::stream(), d_records, num_calls,
-                           plan->d_instrs + i0, airs);
+                           plan->instrs.as<PowdrOrigInstr>() + i0, airs);
     }
     return (int)hipGetLastError();
 }
 
 extern "C" int powdr_apc_tracegen_records(PowdrFp* d_output, size_t output_height, const uint32_t* d_records, size_t num_apc_calls,
                                           const PowdrOrigInstr* h_instrs, size_t n_instrs, const PowdrRecordSubst* h_subs, size_t n_subs) {
-    (void)hipGetLastError();
     const size_t H = output_height;
-    if ((H & (H - 1)) != 0) return (int)hipErrorInvalidValue;
-    if (H == 0 || n_subs == 0) return (int)hipGetLastError();
+    if (int rc = pw::gather_opening(H, n_subs, nullptr); rc != pw::kGatherProceeds) return rc;
     if (!d_output || !h_instrs || !h_subs || (num_apc_calls && !d_records)) return (int)hipErrorInvalidValue;
     // the records are word-major with stride num_apc_calls: clamping the count would read them with the wrong stride
     if (num_apc_calls > H) return (int)hipErrorInvalidValue;
@@ -555,12 +510,13 @@ extern "C" int powdr_apc_tracegen_records(PowdrFp* d_output, size_t output_heigh
         if (h_subs[i].instr < 0 || (size_t)h_subs[i].instr >= n_instrs || h_subs[i].col < 0 || h_subs[i].col >= kWidths[h_instrs[h_subs[i].instr].kind] ||
             h_subs[i].apc_col < 0)
             return (int)hipErrorInvalidValue;
-    std::shared_ptr<RecordPlan> plan;
+    std::shared_ptr<const RecordPlan> plan;
     if (int rc = get_plan(h_instrs, n_instrs, h_subs, n_subs, plan)) return rc;
     pw::ScopedKernelTimer t("apc_tracegen_records_kernel");
     static_assert(kMaxWidth <= kDstStride && kDstStride <= 64, "one mask bit and one table entry per column");
     hipLaunchKernelGGL(apc_tracegen_records_kernel, dim3(pw::div_up(H, kCalls), pw::div_up(n_instrs, kInstrPerBlock)), dim3(kCalls), 0, pw::stream(),
-                       d_output, H, d_records, num_apc_calls, plan->d_instrs, plan->d_wanted, plan->d_dst, (uint32_t)n_instrs);
+                       d_output, H, d_records, num_apc_calls, plan->instrs.as<PowdrOrigInstr>(), plan->wanted.as<uint64_t>(), plan->dst.as<uint32_t>(),
+                       (uint32_t)n_instrs);
     return (int)hipGetLastError();
 }
 

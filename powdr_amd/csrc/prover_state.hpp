@@ -39,31 +39,6 @@ struct Challenger {
     uint32_t sample_bits(int b) { return bb::from_monty(sample()) & ((1u << b) - 1u); }
 };
 
-struct DeviceBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int device = -1;  // the device the buffer lives on: a host thread (thread_local contexts) may have moved to another GPU
-    int ensure(size_t need) {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return (int)e;
-        if (p && dev == device && need <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        e = hipMalloc(&p, need);
-        if (e != hipSuccess) return (int)e;
-        bytes = need;
-        device = dev;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-    DeviceBuf() = default;
-    DeviceBuf(const DeviceBuf&) = delete;
-    DeviceBuf& operator=(const DeviceBuf&) = delete;
-    ~DeviceBuf() { release(); }  // thread_local owners (per-thread segment contexts) give their memory back when the thread exits
-};
-
 // out[i] = arena[offsets[r] + w] for record r, word w (query answers: digests, FRI siblings)
 int gather_records(const uint32_t* arena, const uint64_t* d_offsets, uint32_t words_per_record, uint32_t n, uint32_t* out);
 

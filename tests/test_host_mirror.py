@@ -247,3 +247,63 @@ def test_small_form_analysis_preserves_values():
                    "inverse": x + [om.OP_INV_OR_ZERO], "malformed": x + [ADD]}
     for name, bc in must_refuse.items():
         assert run(bc, 0)[0] is None, name
+
+
+def split_air_assignment(s, apc, bufs, dims, calls, seed, labels=8):
+    """An instr_air assignment that cuts every original AIR of `s` into up to `labels` AIRs (drawn per instruction from `seed`), with
+    the dummy traces cut the same way: the rows an instruction had in its AIR's block are the rows it has in its part's block, so the
+    APC trace is the one of the uncut assignment. Returns (names per instruction, {name: (canonical buffer, width, height)})."""
+    rng = np.random.default_rng(seed)
+    instrs = s.doc["block"]["blocks"][0]["instructions"]
+    base_of = {n: (bufs[i].reshape(w, h), w, b) for i, (n, w, h, b) in enumerate(dims)}
+    names, rows_of, pos = [], {}, {}
+    for ins, subs in zip(instrs, apc.subs):
+        base = om.opcode_air(ins[0])
+        name = f"{base}#{int(rng.integers(labels))}"
+        names.append(name)
+        if subs:  # only instructions that keep a cell have a row (cuda/mod.rs:283-291)
+            rows_of.setdefault(name, []).append(pos.get(base, 0))
+            pos[base] = pos.get(base, 0) + 1
+    parts = {}
+    for name, rows in rows_of.items():
+        full, w, b = base_of[name.split("#")[0]]
+        h = max(synth.next_pow2_or_zero(len(rows) * calls), 4)
+        part = np.zeros((w, h), np.uint32)
+        part[:, :len(rows) * calls] = full[:, (np.arange(calls)[:, None] * b + np.array(rows)[None, :]).reshape(-1)]
+        parts[name] = (part.reshape(-1), w, h)
+    return names, parts
+
+
+@pytest.mark.gpu
+def test_generate_witness_gpu_under_more_assignments_than_the_caches_hold():
+    """One APC handle, 18 different instr_air assignments in a row (each of more than 16 AIRs: the OriginalAir table goes to the
+    device), then the first again: PowdrApc's substitution tables and device AIR tables hold 16 entries each, so the first was
+    evicted and is built anew. Every trace and every histogram equals the oracle's."""
+    import torch
+    from powdr_amd import host, tracegen as tg
+    from tests.test_oracle_apc import run_oracle_gpu_convention
+
+    s, calls = synth.generate("T1", seed=13), 40
+    apc, idx, want, hist, (bufs, dims, gt, order) = run_oracle_gpu_convention(s, calls, seed=13)
+    W, H = want.shape
+    h_apc = host.Apc(s.doc)
+    out = torch.full((H * W,), 7, dtype=torch.int32, device="cuda")  # zero-filled by the callee
+    per = tg.Periphery.fresh()
+    seen = set()
+    for seed in list(range(18)) + [0]:
+        names, parts = split_air_assignment(s, apc, bufs, dims, calls, seed)
+        ids, air_order = air_ids(None, names)
+        assert len(parts) > 16
+        seen.add(tuple(ids))
+        dev = {n: torch.from_numpy(om.to_monty(buf).view(np.int32)).cuda() for n, (buf, _, _) in parts.items()}
+        dummy = [(dev[n].data_ptr(), parts[n][1], parts[n][2]) if n in parts else (0, 0, 0) for n in air_order]
+        per.zero()
+        out.fill_(7)
+        h_apc.generate_witness_gpu(ids, dummy, calls, out.data_ptr(), per)
+        torch.cuda.synchronize()
+        assert (om.from_monty(out.cpu().numpy().view(np.uint32)).reshape(W, H) == want).all(), seed
+        assert (per.var_hist.cpu().numpy().view(np.uint32) == hist["var"]).all(), seed
+        assert (per.tuple_hist.cpu().numpy().view(np.uint32) == hist["tuple"]).all(), seed
+        assert (per.bitwise_hist.cpu().numpy().view(np.uint32) == hist["bitwise"]).all(), seed
+    assert len(seen) == 18
+    h_apc.close()

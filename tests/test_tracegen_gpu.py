@@ -719,3 +719,108 @@ def test_gather_knobs_are_part_of_the_plan_key(gpu, monkeypatch):
         forms.append((st["gather_sparse_jobs"], st["gather_whole_jobs"] + st["gather_chunk_jobs"]))
         assert (from_dev(out.buf) == want).all()
     assert forms[0] == forms[2] == (1, 0) and forms[1][0] == 0 and forms[1][1] >= 1, forms
+
+
+# ---- plan caches past their capacity (csrc/plan_cache.hpp: 64 gather, call-major and bus plans, 32 record plans) --------------------
+# The smallest shapes that still produce one job, more distinct tables than the cache holds, then the first table again (it was
+# evicted and is built anew): every output equals the oracle's.
+
+def test_gather_plan_cache_past_capacity(gpu):
+    import ctypes as C
+
+    torch, abi, tg = gpu
+    rng = np.random.default_rng(41)
+    w, b, H, calls, h = 2, 1, 16, 5, 8
+    src = rng.integers(0, om.P, size=w * h, dtype=np.uint32)
+    d_src = to_dev(torch, src)
+    airs = (abi.OriginalAir * 1)(abi.OriginalAir(w, h, d_src.data_ptr(), b))
+    f = abi.lib.powdr_apc_tracegen_host_tables
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
+    W = 33
+    tables = [np.array([[0, k % w, 0, k // w]], np.int32) for k in range(66)]
+    for subs in tables + tables[:1]:
+        want = om.c_apc_tracegen(H, W, [src], [h], [b], subs, calls)
+        out = tg.DeviceMatrix.zeros(H, W)
+        assert f(out.ptr(), H, None, airs, 1, subs.ctypes.data, len(subs), calls) == 0
+        torch.cuda.synchronize()
+        assert (from_dev(out.buf) == want).all(), subs.tolist()
+
+
+def test_callmajor_plan_cache_past_capacity(gpu):
+    torch, abi, tg = gpu
+    rng = np.random.default_rng(42)
+    U, H, calls, W = 2, 16, 5, 33
+    buf = rng.integers(0, om.P, calls * U, dtype=np.uint32)
+    t = to_dev(torch, buf)
+    tables = [np.array([[0, k % U, k // U]], np.int32) for k in range(66)]
+    for subs_cm in tables + tables[:1]:
+        want = om.c_apc_tracegen_callmajor(H, W, [buf], np.array([U], np.int32), subs_cm, calls)
+        out = tg.DeviceMatrix.zeros(H, W)
+        tg.apc_tracegen_callmajor(out, [(t, U)], subs_cm, calls)
+        torch.cuda.synchronize()
+        assert (from_dev(out.buf) == want).all(), subs_cm.tolist()
+
+
+def test_records_plan_cache_past_capacity(gpu):
+    """one ADD; the destination column varies (and with it the source column); against the library's own expander run on the host"""
+    from oracle import original_chips as oc
+    from powdr_amd import original_chips as pc
+
+    torch, abi, tg = gpu
+    ins = pc.sanitise_instructions([[512, 1, 2, 3, 1, 1, 0, 0]])
+    t = pc.InstructionTable(ins, [True], 0x200000)
+    table, _, _, wpc = oc.build_instruction_table(ins, [True], 0x200000)
+    H, calls, W = 16, 5, 34
+    rec = oc.random_records(table, wpc, calls, seed=43)
+    d_rec = torch.from_numpy(rec.view(np.int32).reshape(-1).copy()).cuda()
+    o, n = int(table[0]["rec_off"]), oc.RECORD_WORDS[int(table[0]["kind"])]
+    rows = np.stack([pc.expand_row_host(t.entries[0], rec[o:o + n, r], int(rec[0, r]) + int(table[0]["ts_delta"])) for r in range(calls)])  # [calls, width]
+    tables = [(k % pc.WIDTHS[pc.BASE_ALU], k) for k in range(34)]
+    for col, apc_col in tables + tables[:1]:
+        want = np.zeros((W, H), np.uint32)
+        want[apc_col, :calls] = rows[:, col]
+        out = tg.DeviceMatrix.zeros(H, W)
+        pc.tracegen_records(out.ptr(), H, d_rec.data_ptr(), calls, t, (pc.PowdrRecordSubst * 1)(pc.PowdrRecordSubst(0, col, apc_col)), 1)
+        torch.cuda.synchronize()
+        assert (from_dev(out.buf).reshape(W, H) == want).all(), (col, apc_col)
+
+
+@pytest.mark.parametrize("binned", ["1", "0"])
+def test_bus_plan_cache_past_capacity(gpu, monkeypatch, binned):
+    """three interactions, one per periphery bus; the tables differ in one constant argument (the tuple's first value)"""
+    torch, abi, tg = gpu
+    monkeypatch.setenv("POWDR_BUS_BINNED", binned)
+    H = calls = 16
+    rng = np.random.default_rng(44)
+    trace = rng.integers(0, 256, size=2 * H, dtype=np.uint32)  # two columns of bytes
+    out = tg.DeviceMatrix.zeros(H, 2)
+    out.buf.copy_(to_dev(torch, trace))
+    PA, PC = om.OP_PUSH_APC, om.OP_PUSH_CONST
+    inter = np.array([[6, 4, 0], [3, 2, 5], [7, 2, 8]], np.uint32)  # bitwise, var-range, tuple
+
+    def tables(k):
+        bc, spans = [], []
+        # bitwise: mult (one set of tables per case: plans are cached by content), x, y, x ^ y (never read), selector xor
+        for words in ([PC, 1 + int(binned)], [PA, 0], [PA, H], [PC, 0], [PC, 1],
+                      [PC, 2], [PA, 0], [PC, 9],     # var-range: mult 2, value x, 9 bits
+                      [PC, 1], [PC, k], [PA, H]):    # tuple: mult 1, v0 = k, v1 = y
+            spans.append((len(bc), len(words)))
+            bc.extend(words)
+        return np.array(bc, np.uint32), np.array(spans, np.uint32)
+
+    for k in list(range(66)) + [0]:
+        bc, spans = tables(k)
+        per = tg.Periphery.fresh()
+        abi.call_stats(reset=True)
+        keep = tg.apc_apply_bus(out, calls, bc, inter, spans, per)
+        torch.cuda.synchronize()
+        st = abi.call_stats()
+        assert (st["bus_binned_windows"], st["bus_direct_calls"]) == ((1, 0) if binned == "1" else (0, 1))
+        want = dict(var=np.zeros(1 << 18, np.uint32), tuple=np.zeros(256 * 2048, np.uint32), bitwise=np.zeros(2 * 65536, np.uint32))
+        om.c_apc_apply_bus(trace, calls, bc, inter, spans, 3, want["var"], 7, want["tuple"], 256, 2048, 6, want["bitwise"])
+        assert want["tuple"].sum() == calls and want["bitwise"].sum() == (1 + int(binned)) * calls
+        assert (hist_np(per.var_hist) == want["var"]).all(), k
+        assert (hist_np(per.tuple_hist) == want["tuple"]).all(), k
+        assert (hist_np(per.bitwise_hist) == want["bitwise"]).all(), k
+        del keep
