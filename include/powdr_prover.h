@@ -775,6 +775,41 @@ int pw_execution_segments_read_lists(const PwExecutionSegments* e, uint32_t* wor
  * now. */
 void pw_execution_segments_last_stats(uint64_t* out);
 
+/* ---- the same cut with the system AIRs' heights metered -----------------------------------------------------------
+ * pw_execution_segments_from_traces_metered: everything above, and per candidate segment the heights of the memory boundary AIR, the
+ * memory Merkle AIR and the Poseidon2 chip that close_segment will give it, as further limits of the cut.
+ * Access: an active interaction (non-zero multiplicity, either sign) on meter->memory_bus of the row at a position; the row's AIR
+ * takes part in the bridge; the interaction has the 7 arguments (as, ptr, d0..d3, t). Its key is (as - 1) * 2^29 + ptr, the key of
+ * pw_memory_tree_boundary_leaves; data words and timestamps are not read; covered positions count like uncovered ones.
+ * For a window [p, q): B(p, q) = the distinct keys of the accesses at its positions; M(p, q) = the distinct pairs (l, key >> l),
+ * l = 0 .. tree_height, over those keys (the nodes of the union of their root paths: pw_memory_merkle_trace's n_nodes);
+ * P(p, q) = 2 * M(p, q), an UPPER BOUND on the Poseidon2 chip's rows, not a count: the chip dedupes by input words.
+ * fits_sys(p, q): fits(p, q), B <= 2^max_log_height[0], M <= 2^max_log_height[1], P <= 2^max_log_height[2], and under max_cells > 0
+ * the cell sum gains width[k] * padded_sys(count_k) for every k with width[k] > 0 (still saturating), padded_sys(0) = 0, else
+ * padded_sys(n) = max(2, padded(n)). The cuts are the greedy cuts under fits_sys. The largest q that fits may now lie strictly
+ * inside a call (a covered position can touch a new block): it moves down to the call's start, last_stats' fourth word counts it,
+ * and a moved cut that lands on b_s is status 13, which can therefore occur without max_cells.
+ * -1 before any GPU call, besides the above: a NULL meter, memory_bus >= p, tree_height outside 1 .. 30, a max_log_height[k] > 31,
+ * an interaction on memory_bus with another arity than 7.
+ * *status 15 = an access without a key: as not 1 or 2, ptr >= 2^29 or key >= 2^tree_height; *info = the smallest packed witness
+ * (air << 46 | interaction << 26 | row). Checked in the order 2, 7, 4, 11, 15, 13 / 14.
+ * pw_execution_segments_from_traces itself is unchanged; a handle from it answers pw_execution_segments_read_system_heights with
+ * zeros. */
+typedef struct { uint32_t memory_bus, tree_height, max_log_height[3], width[3]; } PwSystemMeter; /* 0 boundary, 1 Merkle, 2 Poseidon2 */
+int pw_execution_segments_from_traces_metered(const PwSegmentAir* airs, const uint32_t* segment_of_air, size_t n_airs, uint32_t bridge_bus,
+                                              uint32_t final_pc, const uint32_t* cycle_counts, const uint32_t* apc_widths, size_t n_apcs,
+                                              const uint32_t* call_apc_ids, const uint64_t* call_from, const uint64_t* call_to,
+                                              size_t n_calls, const PwSegmentLimits* limits, const PwSystemMeter* meter,
+                                              size_t scratch_bytes, PwExecutionSegments** out, uint32_t* status, uint64_t* info);
+/* rows[s * 3 + k] = B, M, 2 M of segment s. */
+void pw_execution_segments_read_system_heights(const PwExecutionSegments* e, uint64_t* rows);
+/* Of the calling thread's last metered cut, out[6]: accesses walked, tiles inserted, the most slots the node table had, nodes
+ * inserted past the cuts (the overshoot: at most one tile per segment), host synchronisations of the per-segment loop, node tables
+ * cleared (growth restarts included). Zeros after an unmetered cut. */
+void pw_execution_segments_last_meter_stats(uint64_t* out);
+/* A test knob of the calling thread: the positions of one tile of the meter (0 = the default, 2^14). Results do not depend on it. */
+void pw_execution_segments_set_meter_tile(uint64_t n);
+
 /* ---- the sparse memory Merkle tree ---------------------------------------------------------------------------------
  * A binary Poseidon2 tree of `height` H over 2^H leaves of 8 field words, kept on the device from segment to segment: leaf digest =
  * the first 8 words of permute(payload | 0^8), node = the first 8 words of permute(left | right) — the tuple of the compression bus —

@@ -3,10 +3,16 @@ instruction-AIR traces of one long execution on the device, and optionally the c
 cut under a height cap per class and a cell budget that counts a call as ONE row of its APC and never falls inside a call. The
 handle keeps, per (segment, AIR), the list of the AIR's rows in the segment — what `apc_sources.gather_rows` takes — and no matrices:
 `ExecutionSegments.segment(s)` gathers a segment into tensors of its own. With calls the original trace of a segment may be taller
-than the cap: the cap binds the residuals and the APC traces, which is what gets proven."""
+than the cap: the cap binds the residuals and the APC traces, which is what gets proven.
+
+With `system=SystemMeter(...)` (`pw_execution_segments_from_traces_metered`) the cut also meters the system AIRs that
+`close_segment` gives a segment: the distinct memory blocks it touches (the boundary AIR's rows, B), the tree nodes above them (the
+memory Merkle AIR's rows, M) and 2 M, an upper BOUND on the Poseidon2 chip's rows (the chip dedupes by input words, so its true height
+depends on the hashes). Each is a limit of the cut and, under max_cells, a term of the cell sum."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -14,10 +20,14 @@ from . import abi, prover, stage
 from .apc_calls import Apc, ApcCall, ApcCalls
 from .apc_sources import GatherJob, gather_rows
 from .empirical import BUS_EXEC
+from .execution_states import BUS_MEMORY
 
 lib = abi.lib
-STATUS = {0: "cut", **stage.texts(2, 4, 7, 11), 13: "nothing fits under max_cells", 14: "more than max_segments segments"}
+STATUS = {0: "cut", **stage.texts(2, 4, 7, 11), 13: "nothing fits under max_cells", 14: "more than max_segments segments",
+          15: "a memory-bus tuple that has no key"}
 STATS = ("segments", "classes", "cell_probes", "snapped_cuts", "peak_bytes", "scratch_bytes")
+METER_STATS = ("accesses", "tiles", "table_peak_slots", "nodes_past_the_cuts", "synchronisations", "tables")
+BOUNDARY_WIDTH, MERKLE_WIDTH, POSEIDON2_WIDTH = 18, 55, 307  # system_airs.BOUNDARY_WIDTH, memory_tree.MERKLE_WIDTH, system_airs.POSEIDON2_WIDTH
 
 
 class PwSegmentLimits(C.Structure):
@@ -25,6 +35,40 @@ class PwSegmentLimits(C.Structure):
 
 
 assert C.sizeof(PwSegmentLimits) == 24
+
+
+class PwSystemMeter(C.Structure):
+    _fields_ = [("memory_bus", C.c_uint32), ("tree_height", C.c_uint32), ("max_log_height", C.c_uint32 * 3), ("width", C.c_uint32 * 3)]
+
+
+assert C.sizeof(PwSystemMeter) == 32
+
+
+@dataclass(frozen=True)
+class SystemMeter:
+    """what `cut(system=)` meters: the memory tree's height (1 .. 30), the log2 caps of the boundary AIR, the Merkle AIR and the
+    Poseidon2 bound — None: the cut's own max_log_height for all three, an int: that cap for all three, or (b, m, p) — the widths the
+    three count with under max_cells (0 leaves a term out) and the memory bus"""
+    tree_height: int = 30
+    max_log_height: object = None
+    widths: tuple = (BOUNDARY_WIDTH, MERKLE_WIDTH, POSEIDON2_WIDTH)
+    memory_bus: int = BUS_MEMORY
+
+    def record(self, max_log_height: int) -> PwSystemMeter:
+        caps = self.max_log_height
+        caps = (max_log_height,) * 3 if caps is None else (caps,) * 3 if isinstance(caps, int) else tuple(caps)
+        widths = tuple(self.widths)
+        if len(caps) != 3 or len(widths) != 3:
+            raise ValueError("SystemMeter: three caps and three widths (boundary, Merkle, Poseidon2)")
+        for name, v in (("tree_height", self.tree_height), ("memory_bus", self.memory_bus), *(("max_log_height", c) for c in caps), *(("widths", w) for w in widths)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError(f"SystemMeter: {name} out of range")
+        return PwSystemMeter(int(self.memory_bus), int(self.tree_height), (C.c_uint32 * 3)(*[int(c) for c in caps]), (C.c_uint32 * 3)(*[int(w) for w in widths]))
+
+
+def padded_sys(n: int, min_log_height: int = 0) -> int:
+    """the height a system AIR of n rows is counted with: 0 for none, else at least 2 (no generator returns one row)"""
+    return 0 if n == 0 else max(2, 1 << min_log_height, 1 << (int(n) - 1).bit_length())
 
 _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 lib.pw_execution_segments_from_traces.restype = C.c_int
@@ -44,6 +88,15 @@ lib.pw_execution_segments_read_lists.restype = C.c_int
 lib.pw_execution_segments_read_lists.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
 lib.pw_execution_segments_last_stats.restype = None
 lib.pw_execution_segments_last_stats.argtypes = [_u64p]
+lib.pw_execution_segments_from_traces_metered.restype = C.c_int
+lib.pw_execution_segments_from_traces_metered.argtypes = lib.pw_execution_segments_from_traces.argtypes[:13] + [C.POINTER(PwSystemMeter)] + \
+    lib.pw_execution_segments_from_traces.argtypes[13:]
+lib.pw_execution_segments_read_system_heights.restype = None
+lib.pw_execution_segments_read_system_heights.argtypes = [C.c_void_p, C.c_void_p]
+lib.pw_execution_segments_last_meter_stats.restype = None
+lib.pw_execution_segments_last_meter_stats.argtypes = [_u64p]
+lib.pw_execution_segments_set_meter_tile.restype = None
+lib.pw_execution_segments_set_meter_tile.argtypes = [C.c_uint64]
 
 
 class ExecutionSegmentsError(stage.StageError):
@@ -51,6 +104,8 @@ class ExecutionSegmentsError(stage.StageError):
     PREFIX, STATUS = "pw_execution_segments", STATUS
 
     def decode(self) -> str:
+        if self.status == 15:
+            return "air %d, interaction %d, row %d" % stage.unpack_witness(self.info)
         return f"position {self.info}" if self.status in (13, 14) else super().decode()
 
 
@@ -60,11 +115,25 @@ def last_stats() -> dict:
     return dict(zip(STATS, (int(x) for x in out)))
 
 
+def last_meter_stats() -> dict:
+    """of this thread's last metered cut: accesses walked, tiles, the node table's most slots, nodes inserted past the cuts, the host
+    synchronisations of the per-segment loop, node tables cleared; zeros after an unmetered cut"""
+    out = (C.c_uint64 * 6)()
+    lib.pw_execution_segments_last_meter_stats(out)
+    return dict(zip(METER_STATS, (int(x) for x in out)))
+
+
+def set_meter_tile(n: int) -> None:
+    """a test knob of this thread: the positions per tile of the meter (0 = the default); results do not depend on it"""
+    lib.pw_execution_segments_set_meter_tile(int(n))
+
+
 class ExecutionSegments(stage.Handle):
     """`.bounds` [b_0 .. b_S]; `.starts` [(pc, time key)] per segment; `.final_pc`; `.first_call` [S + 1]; `.heights[s]` {air or
     ("apc", a): rows} (classes without rows left out); `.calls(s)` the segment's ApcCalls re-based to it; `.rows(s, air)` (device
     pointer of the row list, rows, log_height) or None; `.segment(s)` the segment's traces, gathered. `.n_segments`, `.n_airs`,
-    `.n_apcs`, `.positions`, `.covered`, `.list_bytes`. The lists are valid until close()."""
+    `.n_apcs`, `.positions`, `.covered`, `.list_bytes`. `.system_heights[s]` = (B, M, P) of a metered cut — boundary rows, Merkle rows,
+    the bound 2 M on the Poseidon2 chip's rows — and (0, 0, 0) without `system=`. The lists are valid until close()."""
 
     def __init__(self, handle, seg, calls):
         super().__init__(handle, lib.pw_execution_segments_destroy)
@@ -81,6 +150,9 @@ class ExecutionSegments(stage.Handle):
         self.starts = [(int(pcs[s]), int(keys[s])) for s in range(S)]
         self.final_pc = int(pcs[S])
         self.first_call = [int(x) for x in first]
+        sys_rows = np.zeros(max(3 * S, 1), np.uint64)
+        lib.pw_execution_segments_read_system_heights(handle, sys_rows.ctypes.data_as(C.c_void_p))
+        self.system_heights = [tuple(int(x) for x in sys_rows[3 * s:3 * s + 3]) for s in range(S)]
         self.heights = []
         for s in range(S):
             row = rows[s * classes:(s + 1) * classes]
@@ -136,11 +208,12 @@ class ExecutionSegments(stage.Handle):
 
 
 def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widths=None, min_log_height: int = 0, max_cells: int = 0, max_segments: int = 0,
-        segments=None, bus: int = BUS_EXEC, scratch_bytes: int = 0) -> ExecutionSegments:
+        segments=None, bus: int = BUS_EXEC, scratch_bytes: int = 0, system: SystemMeter | None = None) -> ExecutionSegments:
     """seg: the AIR list [(Prover, device trace pointer, log_height)] of ONE execution; calls: the `ApcCalls` of `select_calls` on it, or
     a list of ApcCall(apc_id, start, end) ascending in start; apcs: [Apc] or the cycle counts, apc_id = the index; apc_widths: the
     APC traces' widths (needed under max_cells). A class holds at most 2^max_log_height rows per segment; max_cells (0: no bound)
-    bounds the sum of width x padded height, heights padded to at least 2^min_log_height; max_segments 0 = 2^20. A non-zero status
+    bounds the sum of width x padded height, heights padded to at least 2^min_log_height; max_segments 0 = 2^20. system: None (the
+    cut as it always was) or a SystemMeter, whose three heights become limits of the cut and terms of the cell sum. A non-zero status
     raises ExecutionSegmentsError."""
     if isinstance(calls, ApcCalls):
         calls = calls.calls
@@ -163,6 +236,11 @@ def cut(seg, max_log_height: int, final_pc: int, calls=None, apcs=None, apc_widt
     t_from = (C.c_uint64 * max(n, 1))(*[int(c.start) for c in calls])
     t_to = (C.c_uint64 * max(n, 1))(*[int(c.end) for c in calls])
     limits = PwSegmentLimits(int(max_log_height), int(min_log_height), int(max_cells), int(max_segments))
-    handle = stage.call(lib.pw_execution_segments_from_traces, "pw_execution_segments_from_traces", recs, numbers, len(seg), int(bus), int(final_pc), t_cycles, t_widths,
-                        m, t_ids, t_from, t_to, n, C.byref(limits), int(scratch_bytes), error=ExecutionSegmentsError)
+    if system is None:
+        handle = stage.call(lib.pw_execution_segments_from_traces, "pw_execution_segments_from_traces", recs, numbers, len(seg), int(bus), int(final_pc), t_cycles,
+                            t_widths, m, t_ids, t_from, t_to, n, C.byref(limits), int(scratch_bytes), error=ExecutionSegmentsError)
+    else:
+        meter = system.record(int(max_log_height))
+        handle = stage.call(lib.pw_execution_segments_from_traces_metered, "pw_execution_segments_from_traces_metered", recs, numbers, len(seg), int(bus), int(final_pc),
+                            t_cycles, t_widths, m, t_ids, t_from, t_to, n, C.byref(limits), C.byref(meter), int(scratch_bytes), error=ExecutionSegmentsError)
     return ExecutionSegments(handle, seg, calls)

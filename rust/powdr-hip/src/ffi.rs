@@ -394,6 +394,16 @@ pub struct PwSegmentLimits {
     pub max_cells: u64,
     pub max_segments: u64,
 }
+/// what `pw_execution_segments_from_traces_metered` meters: the memory bus, the memory tree's height (1 .. 30), and per
+/// system AIR (0 = boundary, 1 = memory Merkle, 2 = the Poseidon2 bound 2 M) its log2 cap and the width it counts with under `max_cells`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PwSystemMeter {
+    pub memory_bus: u32,
+    pub tree_height: u32,
+    pub max_log_height: [u32; 3],
+    pub width: [u32; 3],
+}
 /// the opaque result of `pw_execution_segments_from_traces`: the cuts on the host, the per-(segment, AIR) row lists on the device
 #[repr(C)]
 pub struct PwExecutionSegments {
@@ -669,6 +679,19 @@ extern "C" {
     pub fn pw_execution_segments_read_lists(e: *const PwExecutionSegments, words: *mut u32, d_base: *mut *const u32) -> c_int;
     /// out[6]: segments, classes, cell-bound probes, cuts snapped to a call's start, peak scratch, scratch held
     pub fn pw_execution_segments_last_stats(out: *mut u64);
+    /// the same cut with the system AIRs' heights metered: distinct memory blocks, Merkle nodes and the Poseidon2
+    /// bound as further limits; `status` 15 = a memory-bus tuple that has no key (`info` = the packed witness)
+    pub fn pw_execution_segments_from_traces_metered(airs: *const PwSegmentAir, segment_of_air: *const u32, n_airs: usize, bridge_bus: u32, final_pc: u32,
+                                                     cycle_counts: *const u32, apc_widths: *const u32, n_apcs: usize, call_apc_ids: *const u32,
+                                                     call_from: *const u64, call_to: *const u64, n_calls: usize, limits: *const PwSegmentLimits,
+                                                     meter: *const PwSystemMeter, scratch_bytes: usize, out: *mut *mut PwExecutionSegments,
+                                                     status: *mut u32, info: *mut u64) -> c_int;
+    /// rows[S x 3] = B, M, 2 M of every segment (zeros for a handle of the unmetered cut)
+    pub fn pw_execution_segments_read_system_heights(e: *const PwExecutionSegments, rows: *mut u64);
+    /// out[6]: accesses walked, tiles, the node table's most slots, nodes inserted past the cuts, host synchronisations, tables cleared
+    pub fn pw_execution_segments_last_meter_stats(out: *mut u64);
+    /// a test knob of the calling thread: the positions of one tile of the meter (0 = the default)
+    pub fn pw_execution_segments_set_meter_tile(n: u64);
     /// the sparse memory Merkle tree: NULL unless 1 <= height <= 40
     pub fn pw_memory_tree_create(height: u32) -> *mut PwMemoryTree;
     pub fn pw_memory_tree_destroy(tree: *mut PwMemoryTree);
