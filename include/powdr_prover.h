@@ -1274,6 +1274,64 @@ int pw_stage_part_scatter(const uint32_t* d_part, uint32_t n_chunks, size_t m, u
 /* d_y[i] += a * d_x[i] over n extension elements; a NULL: a = 1. */
 int pw_stage_ext_axpy(uint32_t* d_y, const uint32_t* a, const uint32_t* d_x, size_t n);
 
+/* ---- single stages: the LogUp permutation trace and the quotient ----
+ *
+ * The conventions above hold. These take a prover, because the programs live there, and run the path THAT prover would run in a proof:
+ * its run-time specialised kernels if it has them (pw_prover_specialise), else the interpreter kernels — small forms, or post-fix
+ * where the prover was created with POWDR_LOGUP_INTERPRET=1 / POWDR_QUOTIENT_XBC=0. Every path computes the same words. The challenge
+ * TABLES are the caller's device arrays of Montgomery extension elements, nominally powers of a challenge, but any table is taken:
+ *   d_blpow: max_args + 2 elements, beta^0 .. — argument j of an interaction meets d_blpow[j + 1];
+ *   d_apow:  one element per folded constraint: the n_constraints programs, then (LogUp) the G groups, then is_first, is_transition,
+ *            is_last — alpha_c^(M - 1) .. alpha_c^0 in a proof.
+ * `alpha` here is the BUS challenge: d_i = alpha + bus_i + sum_j d_blpow[j + 1] a_ij. G = the prover's LogUp groups
+ * (pw_logup_group_starts). -1 also for a prover with preprocessed columns, a row layout or public values (whole proofs cover those),
+ * for a LogUp call on a prover without interactions and the reverse. The specialised kernels keep their partial sums in the prover's
+ * own scratch, so one prover serves one such call at a time. */
+
+/* The permutation trace of 2^log_h rows (log_h <= 26) of d_values (the prover's columns, column-major): d_perm[(4 g + k) H + r] =
+ * coordinate k of q_g(r) = sum_{i in g} m_i(r) / d_i(r) — one shared inversion per group, the inverse of 0 being 0 —, then the 4
+ * columns of phi(r) = sum_{r' <= r} sum_g q_g(r'); d_rowsum[r] = sum_g q_g(r), H elements. A specialised prover also writes the row
+ * sums as 4 more columns behind phi: d_perm holds 4 G + 8 columns then, else 4 G + 4. Waits for the stream (it owns scratch). */
+int pw_stage_logup_perm(PwProver* p, const uint32_t* d_values, uint32_t log_h, const uint32_t* alpha, const uint32_t* d_blpow, uint32_t* d_perm,
+                        uint32_t* d_rowsum);
+
+/* The quotient over the N = 2^log_n rows (1 <= log_n <= 27) of the extended domain of a trace of H = N / 2 rows, 4 columns into d_q:
+ *   acc_j = sum_c apow[c] C_c(row j) + sum_g apow[nc + g] (q_g den_g - num_g)(row j) + apow[nc + G] is_first (phi - sum_g q_g)
+ *           + apow[nc + G + 1] is_transition (phi' - phi - sum_g q_g') + apow[nc + G + 2] is_last (phi - S),     d_q[k N + j] = acc_j / Z_H(x_j)
+ * with den_g = prod_{i in g} d_i, num_g = sum_{i in g} m_i prod_{l != i} d_l, ' = row (j + 2) mod N, Z_H(x) = x^H - 1, g the trace
+ * domain's generator and is_first = Z_H / (x - 1), is_last = Z_H / (x - 1 / g), is_transition = x - 1 / g. d_lde: the prover's columns
+ * extended; d_plde: the 4 G group columns and the 4 phi columns extended. A specialised LogUp prover reads sum_g q_g from 4 more
+ * columns of d_plde behind phi (the extended row sums): they must hold the sum of the group columns for the paths to agree.
+ * Without interactions d_plde, alpha, d_blpow and S are NULL and only the first sum is taken. n_chunks_out (may be NULL): how many
+ * partial sums were combined. The interpreter's constraints-only form owns scratch and waits for the stream. */
+int pw_stage_quotient(PwProver* p, const uint32_t* d_lde, const uint32_t* d_plde, uint32_t log_n, const uint32_t* d_apow, const uint32_t* alpha,
+                      const uint32_t* d_blpow, const uint32_t* S, uint32_t* d_q, uint32_t* n_chunks_out);
+
+/* The terms of acc that read the current row alone (the first two sums), unscaled, on `rows` rows of d_T (the prover's columns) and
+ * d_Pm (the 4 G group columns), column stride `rows` (1 <= rows <= 2^27): what the streamed route computes per sub-coset. The result is
+ * *n_parts_out partial sums d_part[(4 c + k) rows + j] whose sum over c is the value: 1 on the interpreter paths, the chunks of the
+ * specialised kernels otherwise. unit >= 0 (a specialised prover only, unit < pw_prover_quotient_units): that translation unit alone,
+ * which writes the parts of its own chunks and reads only the group columns 4 g0 .. 4 g1 - 1 of its groups
+ * (pw_prover_quotient_unit_groups) — d_Pm is then a PANEL of those 4 (g1 - g0) columns alone, as the streamed route extends them
+ * unit by unit; the kernel is handed the address column 0 would have, d_Pm - 4 g0 rows, by the same function as there.
+ * unit < 0: everything. log_n as above (the interpreter derives its unused domain constants from it). */
+int pw_stage_quotient_sums(PwProver* p, const uint32_t* d_T, const uint32_t* d_Pm, size_t rows, uint32_t log_n, const uint32_t* d_apow,
+                           const uint32_t* alpha, const uint32_t* d_blpow, int unit, uint32_t* d_part, uint32_t* n_parts_out);
+
+/* Translation units of a specialised prover's quotient kernels (0: not specialised), and the LogUp groups [*g0, *g1) unit `unit`
+ * reads (equal: none; -1: no such unit). */
+uint32_t pw_prover_quotient_units(const PwProver* p);
+int pw_prover_quotient_unit_groups(const PwProver* p, uint32_t unit, uint32_t* g0, uint32_t* g1);
+
+/* The boundary terms and the division on top of n_chunks partial sums (plain sums of words, as pw_stage_part_scatter):
+ *   d_q[k N + j] = (sum_c d_part[(4 c + k) N + j] + the three boundary terms of acc_j above, apow_tail[0 .. 2]) / Z_H(x_j)
+ * with phi from d_plde_phi and sum_g q_g from d_plde_sumq (4 columns of N each). d_q may be d_part when n_chunks = 1. */
+int pw_stage_logup_tail(const uint32_t* d_part, uint32_t n_chunks, const uint32_t* d_plde_phi, const uint32_t* d_plde_sumq, uint32_t log_n,
+                        const uint32_t* d_apow_tail, const uint32_t* S, uint32_t* d_q);
+
+/* d_rowsum[r] = sum_c d_part[(4 c + k) H + r] mod p as H extension elements, and the same as 4 columns d_cols4[k H + r]. */
+int pw_stage_rowsum_combine(const uint32_t* d_part, uint32_t n_chunks, size_t H, uint32_t* d_rowsum, uint32_t* d_cols4);
+
 /* Host-side Poseidon2 permutation used by the transcript (canonical words in/out). This is also the known-answer-test
  * hook: after pw_set_poseidon2_constants a maintainer feeds it the vector of the backend's own Poseidon2 test. */
 void pw_poseidon2_permute_host(uint32_t* state16);

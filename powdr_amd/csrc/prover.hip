@@ -1254,6 +1254,131 @@ extern "C" int pw_stage_ext_axpy(uint32_t* d_y, const uint32_t* a, const uint32_
     return ext_axpy(reinterpret_cast<bb::Ext*>(d_y), a ? &e : nullptr, reinterpret_cast<const bb::Ext*>(d_x), n);
 }
 
+// ---- the LogUp permutation and quotient stages of one prover --------------------------------------------------------------------
+// They take the prover because the programs live there, and run the path that prover would run: the specialised kernels if it has
+// them, else the interpreter (small forms, or post-fix where the prover was created so). The challenge TABLES are the caller's.
+namespace {
+
+// a prover these calls serve: no preprocessed columns, no row layout, no public values (whole proofs cover those)
+bool stage_prover(const PwProver* p) { return p && !p->pre_width && !p->row_flags && !p->n_public && !p->transition; }
+
+// the partial sums quotient_eval combines for nc constraints on `rows` rows (its own rounding of quotient_chunks)
+uint32_t quotient_eval_chunks(size_t rows, uint32_t nc) {
+    const uint32_t chunks = quotient_chunks(rows, nc);
+    if (chunks <= 1) return 1;
+    const uint32_t per_chunk = (nc + chunks - 1) / chunks;
+    return (nc + per_chunk - 1) / per_chunk;
+}
+
+}  // namespace
+
+extern "C" int pw_stage_logup_perm(PwProver* p, const uint32_t* d_values, uint32_t log_h, const uint32_t* alpha, const uint32_t* d_blpow,
+                                   uint32_t* d_perm, uint32_t* d_rowsum) {
+    (void)hipGetLastError();
+    bb::Ext al;
+    if (!stage_prover(p) || !p->logup || !stage_ext(alpha, &al) || !d_values || !d_blpow || !d_perm || !d_rowsum || log_h > kStageMaxLog - 1) return -1;
+    const size_t H = (size_t)1 << log_h;
+    StageScratch s;
+    TRY(s.alloc((H / 4096 + 1) * sizeof(bb::Ext)));  // (logup_perm_trace's d_block_totals, prover_internal.hpp)
+    const bb::Ext* bl = reinterpret_cast<const bb::Ext*>(d_blpow);
+    bb::Ext* rowsum = reinterpret_cast<bb::Ext*>(d_rowsum);
+    if (specialised(p)) return logup_perm_trace_jit(p, d_values, H, al, bl, d_perm, rowsum, s.as<bb::Ext>());
+    return logup_perm_trace(d_values, H, logup_program(p, air_shape(p, log_h, true)), al, bl, d_perm, rowsum, s.as<bb::Ext>());
+}
+
+extern "C" int pw_stage_quotient(PwProver* p, const uint32_t* d_lde, const uint32_t* d_plde, uint32_t log_n, const uint32_t* d_apow,
+                                 const uint32_t* alpha, const uint32_t* d_blpow, const uint32_t* S, uint32_t* d_q, uint32_t* n_chunks_out) {
+    (void)hipGetLastError();
+    if (!stage_prover(p) || !d_lde || !d_apow || !d_q || log_n < 1 || log_n > kStageMaxLog) return -1;
+    const bool lg = p->logup, jit = specialised(p);
+    bb::Ext al = bb::ext_zero(), sum = bb::ext_zero();
+    if (lg ? (!d_plde || !d_blpow || !stage_ext(alpha, &al) || !stage_ext(S, &sum)) : (d_plde || d_blpow || alpha || S)) return -1;
+    const size_t N = (size_t)1 << log_n;
+    const uint32_t nc = p->n_constraints;
+    uint32_t zv_even, zv_odd;
+    vanishing_on_coset(log_n - 1, &zv_even, &zv_odd);
+    const bb::Ext* apow = reinterpret_cast<const bb::Ext*>(d_apow);
+    const bb::Ext* bl = reinterpret_cast<const bb::Ext*>(d_blpow);
+    const ConstraintProgram prog = constraint_program(p, nc);
+    uint32_t chunks = 1;
+    int rc;
+    if (lg && jit) {
+        chunks = p->jit.quotient.n_chunks;
+        rc = quotient_eval_logup_jit(p, d_lde, d_plde, N, (int)log_n, apow, al, bl, sum, zv_even, zv_odd, d_q);
+    } else if (lg) {
+        rc = quotient_eval_logup(d_lde, d_plde, N, (int)log_n, prog, logup_program(p, air_shape(p, log_n - 1, true)), apow, al, bl, sum, zv_even, zv_odd, d_q);
+    } else if (jit && nc) {
+        chunks = p->jit.quotient.n_chunks;
+        rc = quotient_eval_jit(p, d_lde, N, apow, bb::inv(zv_even), bb::inv(zv_odd), d_q);
+    } else {
+        chunks = quotient_eval_chunks(N, nc);
+        StageScratch s;
+        TRY(s.alloc(chunks > 1 ? (size_t)chunks * 4 * N * 4 : 0));
+        rc = quotient_eval(d_lde, N, prog, apow, bb::inv(zv_even), bb::inv(zv_odd), d_q, chunks > 1 ? s.as<uint32_t>() : nullptr, chunks);
+    }
+    if (!rc && n_chunks_out) *n_chunks_out = chunks;
+    return rc;
+}
+
+extern "C" uint32_t pw_prover_quotient_units(const PwProver* p) { return p && specialised(p) ? quotient_units_jit(p) : 0u; }
+
+extern "C" int pw_prover_quotient_unit_groups(const PwProver* p, uint32_t unit, uint32_t* g0, uint32_t* g1) {
+    if (!p || !g0 || !g1 || !specialised(p) || unit >= quotient_units_jit(p)) return -1;
+    quotient_unit_groups(p, unit, g0, g1);
+    return 0;
+}
+
+extern "C" int pw_stage_quotient_sums(PwProver* p, const uint32_t* d_T, const uint32_t* d_Pm, size_t rows, uint32_t log_n, const uint32_t* d_apow,
+                                      const uint32_t* alpha, const uint32_t* d_blpow, int unit, uint32_t* d_part, uint32_t* n_parts_out) {
+    (void)hipGetLastError();
+    if (!stage_prover(p) || !d_T || !d_apow || !d_part || !rows || rows > ((size_t)1 << kStageMaxLog) || log_n < 1 || log_n > kStageMaxLog) return -1;
+    const bool lg = p->logup, jit = specialised(p);
+    bb::Ext al = bb::ext_zero();
+    if (lg ? (!d_Pm || !d_blpow || !stage_ext(alpha, &al)) : (d_Pm || d_blpow || alpha)) return -1;
+    if (unit >= 0 && (!jit || (uint32_t)unit >= quotient_units_jit(p))) return -1;
+    const uint32_t nc = p->n_constraints, one = bb::R_MOD_P;
+    const bb::Ext* apow = reinterpret_cast<const bb::Ext*>(d_apow);
+    const bb::Ext* bl = reinterpret_cast<const bb::Ext*>(d_blpow);
+    const ConstraintProgram prog = constraint_program(p, nc);
+    uint32_t n_parts = 1;
+    int rc;
+    if (unit >= 0) {
+        uint32_t g0 = 0, g1 = 0;
+        quotient_unit_groups(p, (uint32_t)unit, &g0, &g1);
+        n_parts = p->jit.quotient.n_chunks;
+        rc = quotient_unit_jit(p, (uint32_t)unit, d_T, lg ? streamed::unit_panel_origin(d_Pm, g0, rows) : nullptr, rows, apow, al, bl, d_part);
+    } else if (jit && (nc || lg)) {
+        rc = quotient_parts_jit(p, d_T, d_Pm, rows, apow, al, bl, d_part, &n_parts);
+    } else if (lg) {
+        rc = quotient_eval_logup(d_T, d_Pm, rows, (int)log_n, prog, logup_program(p, air_shape(p, log_n - 1, true)), apow, al, bl, bb::ext_zero(), one, one,
+                                 d_part, true);
+    } else {
+        const uint32_t chunks = quotient_eval_chunks(rows, nc);
+        StageScratch s;
+        TRY(s.alloc(chunks > 1 ? (size_t)chunks * 4 * rows * 4 : 0));
+        rc = quotient_eval(d_T, rows, prog, apow, one, one, d_part, chunks > 1 ? s.as<uint32_t>() : nullptr, chunks);
+    }
+    if (!rc && n_parts_out) *n_parts_out = n_parts;
+    return rc;
+}
+
+extern "C" int pw_stage_logup_tail(const uint32_t* d_part, uint32_t n_chunks, const uint32_t* d_plde_phi, const uint32_t* d_plde_sumq, uint32_t log_n,
+                                   const uint32_t* d_apow_tail, const uint32_t* S, uint32_t* d_q) {
+    (void)hipGetLastError();
+    bb::Ext sum;
+    if (!d_part || !n_chunks || !d_plde_phi || !d_plde_sumq || !d_apow_tail || !d_q || !stage_ext(S, &sum) || log_n < 1 || log_n > kStageMaxLog) return -1;
+    uint32_t zv_even, zv_odd;
+    vanishing_on_coset(log_n - 1, &zv_even, &zv_odd);
+    return quotient_logup_tail(d_part, n_chunks, d_plde_phi, d_plde_sumq, (size_t)1 << log_n, (int)log_n, reinterpret_cast<const bb::Ext*>(d_apow_tail), sum,
+                               zv_even, zv_odd, d_q);
+}
+
+extern "C" int pw_stage_rowsum_combine(const uint32_t* d_part, uint32_t n_chunks, size_t H, uint32_t* d_rowsum, uint32_t* d_cols4) {
+    (void)hipGetLastError();
+    if (!d_part || !n_chunks || !d_rowsum || !d_cols4 || !H || H > ((size_t)1 << kStageMaxLog)) return -1;
+    return logup_rowsum_combine(d_part, n_chunks, H, reinterpret_cast<bb::Ext*>(d_rowsum), d_cols4);
+}
+
 extern "C" int pw_set_poseidon2_constants(const uint32_t* ext_rc, const uint32_t* int_rc) {
     return poseidon2_set_constants(ext_rc, int_rc);
 }

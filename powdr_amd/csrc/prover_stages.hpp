@@ -216,13 +216,20 @@ inline int logup_stage(PwProver* p, const AirShape& s, AirMode m, const CommitLa
     return 0;
 }
 
+// Z_H(x) = x^H - 1 on the even / odd rows of the shifted domain of 2H points: x_j^H = s^H (-1)^j
+inline void vanishing_on_coset(uint32_t log_h, uint32_t* zv_even, uint32_t* zv_odd) {
+    const uint32_t one = bb::R_MOD_P;
+    uint32_t sH = bb::to_monty(field::kCosetShift);
+    for (uint32_t i = 0; i < log_h; ++i) sH = bb::sqr(sH);
+    *zv_even = bb::sub(sH, one);
+    *zv_odd = bb::sub(bb::neg(sH), one);
+}
+
 // From the alpha powers to the quotient's chunk coefficients in p->qcoef and their LDE in p->qlde (p->q: the quotient over N rows)
 inline int quotient_stage(PwProver* p, const AirShape& s, AirMode m, const CommitLayout& L, const AirBufs& B, bb::Ext al, bb::Ext S) {
     const bool lg = s.Wp != 0, jit = specialised(p);
-    const uint32_t one = bb::R_MOD_P;
-    uint32_t sH = bb::to_monty(field::kCosetShift);
-    for (uint32_t i = 0; i < s.log_h; ++i) sH = bb::sqr(sH);
-    const uint32_t zv_even = bb::sub(sH, one), zv_odd = bb::sub(bb::neg(sH), one);  // Z_H on the even / odd rows of the coset
+    uint32_t zv_even, zv_odd;
+    vanishing_on_coset(s.log_h, &zv_even, &zv_odd);
     const ConstraintProgram prog = constraint_program(p, s.nc);
     uint32_t* d_lde = p->lde.as<uint32_t>();
     uint32_t* d_plde = p->plde.as<uint32_t>();

@@ -51,6 +51,10 @@ inline int leaf_hashes(const Ctx& c, const uint32_t* coef, uint32_t cols, uint32
     });
 }
 
+// What quotient_unit_jit takes as Pm for a PANEL that holds only the permutation columns 4 g0 .. 4 g1 - 1 of the groups [g0, g1) a
+// unit reads (column stride `rows`): the address permutation column 0 would have. Never dereferenced below the panel itself.
+inline const uint32_t* unit_panel_origin(const uint32_t* d_panel, uint32_t g0, size_t rows) { return d_panel - (size_t)(4 * g0) * rows; }
+
 // The quotient's terms that read the CURRENT row only — sum_k apow[k] C_k + sum_g apow[nc + g] (q_g den_g - num_g) — unscaled, for all N
 // rows of the extended domain into d_q (4 x N), sub-coset by sub-coset. The caller adds the boundary terms (quotient_logup_tail with
 // part = d_q, one chunk) or divides by Z_H (quotient_combine, in place).
@@ -70,9 +74,7 @@ inline int quotient_sums(const Ctx& c, bool jit, bool lg, uint32_t nc, const Con
                 uint32_t g0 = 0, g1 = 0;
                 quotient_unit_groups(p, u, &g0, &g1);
                 if (g1 > g0) PW_STRY(subcoset_lde(d_pcoef + (size_t)(4 * g0) * c.H, d_panel, c.H, c.m, 4 * (g1 - g0), (int)c.log_h, c.b, r, fs));
-                // Pm = where permutation column 0 would be: the panel holds columns 4 g0 .. 4 g1 - 1
-                const uint32_t* Pm = d_panel - (size_t)(4 * g0) * c.m;
-                PW_STRY(quotient_unit_jit(p, u, d_blk, Pm, c.m, d_apow, al, d_blpow, d_part));
+                PW_STRY(quotient_unit_jit(p, u, d_blk, unit_panel_origin(d_panel, g0, c.m), c.m, d_apow, al, d_blpow, d_part));
             }
             return part_scatter(d_part, p->jit.quotient.n_chunks, c.m, c.b, r, c.N, d_q);
         });

@@ -20,6 +20,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_stage_opening_weights", "pw_stage_ext_dot", "pw_stage_ext_powers", "pw_stage_deep", "pw_stage_deep_logup",
                   "pw_stage_ext_lincomb", "pw_stage_deep_from_combo", "pw_stage_fri_fold", "pw_stage_logup_scan", "pw_stage_quotient_split",
                   "pw_stage_row_layout", "pw_stage_part_scatter", "pw_stage_ext_axpy",
+                  "pw_stage_logup_perm", "pw_stage_quotient", "pw_stage_quotient_sums", "pw_stage_logup_tail", "pw_stage_rowsum_combine",
+                  "pw_prover_quotient_units", "pw_prover_quotient_unit_groups",
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
@@ -116,10 +118,22 @@ _STAGE_ARGTYPES = {
     "pw_stage_row_layout": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int],
     "pw_stage_part_scatter": [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p],
     "pw_stage_ext_axpy": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    # the LogUp permutation and quotient stages of one prover (the first argument: Prover._h)
+    "pw_stage_logup_perm": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pw_stage_quotient": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.POINTER(C.c_uint32)],
+    "pw_stage_quotient_sums": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                               C.POINTER(C.c_uint32)],
+    "pw_stage_logup_tail": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pw_stage_rowsum_combine": [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p],
 }
 for _name, _argtypes in _STAGE_ARGTYPES.items():
     getattr(lib, _name).restype = C.c_int
     getattr(lib, _name).argtypes = _argtypes
+lib.pw_prover_quotient_units.restype = C.c_uint32
+lib.pw_prover_quotient_units.argtypes = [C.c_void_p]
+lib.pw_prover_quotient_unit_groups.restype = C.c_int
+lib.pw_prover_quotient_unit_groups.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 
 
 def _vp(a):
@@ -873,6 +887,16 @@ class Prover:
         k, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
         st = int(lib.pw_prover_specialised(self._h, C.byref(k), C.byref(b), C.byref(c)))
         return dict(state=st, kernels=k.value, code_bytes=b.value, chunks=c.value)
+
+    def quotient_units(self):
+        """[(g0, g1)] per translation unit of the specialised quotient kernels: the LogUp groups the unit reads (pw_prover_quotient_units,
+        pw_prover_quotient_unit_groups); [] for a prover that is not specialised."""
+        out = []
+        for u in range(int(lib.pw_prover_quotient_units(self._h))):
+            g0, g1 = C.c_uint32(), C.c_uint32()
+            abi.check(lib.pw_prover_quotient_unit_groups(self._h, u, C.byref(g0), C.byref(g1)), "pw_prover_quotient_unit_groups")
+            out.append((g0.value, g1.value))
+        return out
 
     def max_constraint_degree(self) -> int:
         lib.pw_prover_max_constraint_degree.restype = C.c_int

@@ -802,6 +802,17 @@ extern "C" {
     pub fn pw_stage_row_layout(d_m: *mut u32, log_n: u32, w1: u32, d_next_cols: *const u32, n_next: u32, step: u32, selectors: c_int, trace_domain: c_int) -> c_int;
     pub fn pw_stage_part_scatter(d_part: *const u32, n_chunks: u32, m: usize, b: u32, r: u32, n: usize, d_out: *mut u32) -> c_int;
     pub fn pw_stage_ext_axpy(d_y: *mut u32, a: *const u32, d_x: *const u32, n: usize) -> c_int;
+    pub fn pw_stage_logup_perm(p: *mut PwProver, d_values: *const u32, log_h: u32, alpha: *const u32, d_blpow: *const u32, d_perm: *mut u32,
+                               d_rowsum: *mut u32) -> c_int;
+    pub fn pw_stage_quotient(p: *mut PwProver, d_lde: *const u32, d_plde: *const u32, log_n: u32, d_apow: *const u32, alpha: *const u32,
+                             d_blpow: *const u32, s: *const u32, d_q: *mut u32, n_chunks_out: *mut u32) -> c_int;
+    pub fn pw_stage_quotient_sums(p: *mut PwProver, d_t: *const u32, d_pm: *const u32, rows: usize, log_n: u32, d_apow: *const u32,
+                                  alpha: *const u32, d_blpow: *const u32, unit: c_int, d_part: *mut u32, n_parts_out: *mut u32) -> c_int;
+    pub fn pw_stage_logup_tail(d_part: *const u32, n_chunks: u32, d_plde_phi: *const u32, d_plde_sumq: *const u32, log_n: u32,
+                               d_apow_tail: *const u32, s: *const u32, d_q: *mut u32) -> c_int;
+    pub fn pw_stage_rowsum_combine(d_part: *const u32, n_chunks: u32, h: usize, d_rowsum: *mut u32, d_cols4: *mut u32) -> c_int;
+    pub fn pw_prover_quotient_units(p: *const PwProver) -> u32;
+    pub fn pw_prover_quotient_unit_groups(p: *const PwProver, unit: u32, g0: *mut u32, g1: *mut u32) -> c_int;
     pub fn pw_prover_specialise(p: *mut PwProver) -> c_int;
     pub fn pw_prover_specialised(p: *const PwProver, n_kernels: *mut usize, code_bytes: *mut usize, n_chunks: *mut usize) -> c_int;
     pub fn pw_prove_segments_multi(devices: *const c_int, n_workers: usize, segment_cells: *const u64, n_segments: usize,

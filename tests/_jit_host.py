@@ -69,11 +69,16 @@ def ext_inv_tower(a):
 
 
 def eval_postfix(code, row):
+    """a post-fix program on one row's cells (-> a Python integer), or on every row at once when `row` is the whole W x n matrix
+    (-> n int64 words: a product of two words stays below 2^62, and % of a negative int64 is non-negative). Cells that are no integers
+    (elements of a ring with + - * and % of its own: openings in the extension field) are taken as they are."""
+    whole = getattr(row, "ndim", 1) == 2
     st, i = [], 0
     while i < len(code):
         op = int(code[i])
         if op in (PA, PC):
-            st.append(int(row[int(code[i + 1])]) if op == PA else int(code[i + 1]) % P)
+            cell = row[int(code[i + 1])] if op == PA else int(code[i + 1]) % P
+            st.append(cell.astype(np.int64) if whole and op == PA else int(cell) if isinstance(cell, (int, np.integer)) else cell)
             i += 2
         elif op == NEG:
             st.append(-st.pop() % P)

@@ -7,7 +7,11 @@ Two layers. Scalars (a challenge, an opened sum, one weight) are tuples of 4 Pyt
 numpy uint64 arrays with a last axis of 4 (v*): every product of two words below p is below 2^62 and is reduced at once, a sum of 2^14
 reduced words is below 2^45, so uint64 never wraps (the longest sums here: 16384 rows in ext_dot, 65536 in the scan — below 2^47).
 tests/test_stage_ref_cpu.py holds the scalar layer against the oracle's field and against polynomial identities, and every v* routine
-against its scalar twin."""
+against its scalar twin.
+
+The stage in front of those — the LogUp permutation trace and the quotient (logup_perm, quotient_sums, quotient, logup_tail,
+rowsum_combine) — is here too, over the post-fix evaluator of tests/_jit_host.py; test_stage_ref_cpu.py holds it to the identity a
+verifier checks at a random point, recomputed there scalar by scalar."""
 import functools
 
 import numpy as np
@@ -358,6 +362,142 @@ def part_scatter(part, b: int, r: int, out):
 def ext_axpy(y, a, x):
     """y + a x (a None: 1)"""
     return vadd(y, x if a is None else vmul(np.array(ext(a), np.uint64)[None, :], x))
+
+
+# ---------------------------------------------------------------------------------------------------------- LogUp and the quotient
+# The stage in front of the kernels above (csrc/logup_kernels.hip, stark_kernels.hip, the run-time specialised kernels). Every function
+# takes TABLES — blpow (max_args + 2, 4): argument j meets blpow[j + 1]; apow (folded constraints, 4) — not challenges, so a caller may
+# pass tables no transcript produces. The programs are evaluated by tests/_jit_host.eval_postfix on every row at once. `it` =
+# (inter, ispans, ibc) as powdr_amd.prover takes it, `starts` = the group boundaries (prover.logup_group_starts). The inverse of 0 is 0.
+def _ext_rows(a, n):
+    """an extension scalar on n rows"""
+    return np.broadcast_to(np.array(ext(a), np.uint64), (n, 4))
+
+
+def _base_rows(v, n):
+    """base-field words (eval_postfix's int64, or one integer for a constant program) as n extension elements"""
+    out = np.zeros((n, 4), np.uint64)
+    out[:, 0] = np.broadcast_to(np.asarray(v, np.int64) % P, (n,)).astype(np.uint64)
+    return out
+
+
+def interaction_values(T, it, alpha, blpow):
+    """per interaction: the multiplicity m_i on every row (n words) and d_i = alpha + bus_i + sum_j blpow[j + 1] a_ij (n, 4)"""
+    from tests._jit_host import eval_postfix
+
+    inter, ispans, ibc = (np.asarray(a) for a in it)
+    T = np.asarray(T, np.uint64)
+    n = T.shape[1]
+    blpow = vext(blpow)
+    span = lambda s: eval_postfix(ibc[int(ispans[s][0]):int(ispans[s][0]) + int(ispans[s][1])].tolist(), T)
+    ms, ds = [], []
+    for bus, n_args, s0 in inter.reshape(-1, 3).tolist():
+        ms.append(_base_rows(span(s0), n)[:, 0])
+        d = vadd(_ext_rows(alpha, n), _base_rows(bus, n))
+        for j in range(n_args):
+            d = vadd(d, vscale(blpow[j + 1][None, :], _base_rows(span(s0 + 1 + j), n)[:, 0]))
+        ds.append(d)
+    return ms, ds
+
+
+def _group_fraction(ms, ds, i0, i1):
+    """(num_g, den_g) of sum_{i0 <= i < i1} m_i / d_i: (num, den) <- (num d_i + m_i den, den d_i), as every kernel folds a group"""
+    n = len(ms[i0])
+    num, den = _base_rows(ms[i0].astype(np.int64), n), ds[i0]
+    for i in range(i0 + 1, i1):
+        num, den = vadd(vmul(num, ds[i]), vscale(den, ms[i])), vmul(den, ds[i])
+    return num, den
+
+
+def logup_perm(T, it, starts, alpha, blpow, vanishing=()):
+    """q_g(r) = num_g(r) / den_g(r) for every group — ONE inversion per group and row, 1 / 0 = 0: a vanishing denominator d_i zeroes
+    the whole group on that row —, the row sums sum_g q_g(r) and phi(r) = sum_(r' <= r) of them.
+    -> (q (G, n, 4), rowsum (n, 4), phi (n, 4)). vanishing: the (interaction, row) pairs whose denominator may be 0; any other is an
+    error of the CALLER's inputs (the kernels agree about 0 / 0 only where every member's multiplicity is non-zero)."""
+    ms, ds = interaction_values(T, it, alpha, blpow)
+    n = np.asarray(T).shape[1]
+    zero = {(i, int(r)) for i, d in enumerate(ds) for r in np.flatnonzero(~d.any(axis=1))}
+    assert zero <= set(vanishing), sorted(zero - set(vanishing))[:4]
+    starts = [int(s) for s in starts]
+    q = np.zeros((len(starts) - 1, n, 4), np.uint64)
+    for g in range(len(starts) - 1):
+        if starts[g + 1] > starts[g]:
+            num, den = _group_fraction(ms, ds, starts[g], starts[g + 1])
+            q[g] = vmul(num, vext_inv(den))
+    rowsum = q.sum(axis=0) % _p
+    return q, rowsum, scan(rowsum).T
+
+
+def quotient_sums(T, Pm, cons, it, starts, apow, alpha=None, blpow=None):
+    """the quotient's terms that read the current row alone, unscaled, on the n rows of T (W, n) and Pm (>= 4 G, n: the group columns):
+    sum_c apow[c] C_c + sum_g apow[nc + g] (q_g den_g - num_g) -> (n, 4); it None: the first sum only"""
+    from tests._jit_host import eval_postfix
+
+    bc, spans = cons
+    T = np.asarray(T, np.uint64)
+    n = T.shape[1]
+    apow = vext(apow)
+    acc = np.zeros((n, 4), np.uint64)
+    spans = np.asarray(spans).reshape(-1, 2).tolist()
+    for c, (off, ln) in enumerate(spans):
+        acc = vadd(acc, vscale(apow[c][None, :], _base_rows(eval_postfix(np.asarray(bc)[off:off + ln].tolist(), T), n)[:, 0]))
+    if it is None:
+        return acc
+    ms, ds = interaction_values(T, it, alpha, blpow)
+    Pm = np.asarray(Pm, np.uint64)
+    starts = [int(s) for s in starts]
+    for g in range(len(starts) - 1):
+        qg = Pm[4 * g:4 * g + 4].T
+        if starts[g + 1] > starts[g]:
+            num, den = _group_fraction(ms, ds, starts[g], starts[g + 1])
+            term = vsub(vmul(qg, den), num)
+        else:
+            term = qg  # an empty group: its column must vanish
+        acc = vadd(acc, vmul(apow[len(spans) + g][None, :], term))
+    return acc
+
+
+def _boundary_and_divide(acc, phi, sumq, log_n: int, apow_tail, S):
+    """(acc + apow_tail[0] is_first (phi - sumq) + apow_tail[1] is_transition (phi' - phi - sumq') + apow_tail[2] is_last (phi - S)) /
+    Z_H on the N = 2^log_n rows x_j of the extended domain of a trace of H = N / 2 rows, ' = row (j + 2) mod N (the next TRACE row),
+    Z_H = x^H - 1, g = root(log_n - 1): is_first = Z_H / (x - 1), is_last = Z_H / (x - 1 / g), is_transition = x - 1 / g.
+    phi, sumq: (N, 4); apow_tail None: no boundary terms (a constraints-only AIR)"""
+    x = domain(log_n)
+    z = (vpow(x, 1 << (log_n - 1)) + _p - np.uint64(1)) % _p
+    if apow_tail is not None:
+        t, N = vext(apow_tail), len(x)
+        ginv = np.uint64(inv(root(log_n - 1)))
+        is_first = z * vinv((x + _p - np.uint64(1)) % _p) % _p
+        is_last = z * vinv((x + _p - ginv) % _p) % _p
+        is_trans = (x + _p - ginv) % _p
+        nxt = lambda a: np.roll(a, -2, axis=0)
+        acc = vadd(acc, vmul(t[0][None, :], vscale(vsub(phi, sumq), is_first)))
+        acc = vadd(acc, vmul(t[1][None, :], vscale(vsub(vsub(nxt(phi), phi), nxt(sumq)), is_trans)))
+        acc = vadd(acc, vmul(t[2][None, :], vscale(vsub(phi, _ext_rows(S, N)), is_last)))
+    return vscale(acc, vinv(z))
+
+
+def quotient(lde, plde, log_n: int, cons, it, starts, apow, alpha=None, blpow=None, S=None):
+    """the quotient on the N rows of the extended domain -> (N, 4). lde (W, N); plde (>= 4 G + 4, N): the group columns, then phi —
+    sum_g q_g is taken from the group columns; it None (plde, alpha, blpow, S unused): constraints only"""
+    acc = quotient_sums(lde, plde, cons, it, starts, apow, alpha, blpow)
+    if it is None:
+        return _boundary_and_divide(acc, None, None, log_n, None, None)
+    G = len(starts) - 1
+    plde = np.asarray(plde, np.uint64)
+    sumq = plde[:4 * G].reshape(G, 4, -1).sum(axis=0).T % _p if G else np.zeros((plde.shape[1], 4), np.uint64)
+    nc = len(np.asarray(cons[1]).reshape(-1, 2))
+    return _boundary_and_divide(acc, plde[4 * G:4 * G + 4].T, sumq, log_n, vext(apow)[nc + G:nc + G + 3], S)
+
+
+def rowsum_combine(part):
+    """part (n_chunks, 4, H) -> (H, 4): plain sums mod p"""
+    return (np.asarray(part, np.uint64).sum(axis=0) % _p).T
+
+
+def logup_tail(part, phi_cols, sumq_cols, log_n: int, apow_tail, S):
+    """part (n_chunks, 4, N), phi_cols / sumq_cols (4, N) -> (N, 4): the boundary terms and the division on top of the summed parts"""
+    return _boundary_and_divide(rowsum_combine(part), np.asarray(phi_cols, np.uint64).T, np.asarray(sumq_cols, np.uint64).T, log_n, apow_tail, S)
 
 
 # ---------------------------------------------------------------------------------------------------------- scalar twins

@@ -1,10 +1,13 @@
 """tests/_stage_ref.py (the reference the stage-kernel GPU tests compare with) held against things it did not define: the oracle's
-extension field and transforms, polynomial identities (an opening IS an evaluation, a fold IS f_even + beta f_odd), and, for every
-vectorised routine, a scalar twin in Python integers. No GPU."""
+extension field and transforms, polynomial identities (an opening IS an evaluation, a fold IS f_even + beta f_odd; the LogUp
+permutation trace and the quotient satisfy the identity a verifier checks at a random point), and, for every vectorised routine, a
+scalar twin in Python integers. No GPU."""
 import numpy as np
 
+from oracle import apc_model as om
 from oracle import stark_model as sm
 from tests import _stage_ref as ref
+from tests._jit_host import eval_postfix
 
 P = ref.P
 EDGE_WORDS = [0, 1, P - 1, (P - 1) // 2, (P + 1) // 2]
@@ -211,6 +214,204 @@ def test_centred_encoding_round_trips():
     # the two neighbours of p / 2, as WORDS
     assert ref.centred_encode(ref.from_word(np.array([(P - 1) // 2, (P + 1) // 2], np.uint64))).tolist() == [ref.HALF, -ref.HALF]
     # and the oracle's Montgomery conversion is the one used here
-    from oracle import apc_model as om
-
     assert (om.to_monty(c.astype(np.uint32)) == ref.to_word(c)).all() and (om.from_monty(c.astype(np.uint32)) == ref.from_word(c)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- LogUp and the quotient
+class E:
+    """an extension element with operators: what eval_postfix needs to run a program on OPENINGS (cells in E); Python integers only"""
+
+    def __init__(self, v):
+        self.v = v.v if isinstance(v, E) else ref.ext(v)
+
+    __add__ = __radd__ = lambda a, b: E(ref.ext_add(a.v, E(b).v))
+    __mul__ = __rmul__ = lambda a, b: E(ref.ext_mul(a.v, E(b).v))
+    __sub__ = lambda a, b: E(ref.ext_sub(a.v, E(b).v))
+    __rsub__ = lambda a, b: E(ref.ext_sub(E(b).v, a.v))
+    __neg__ = lambda a: E(ref.ext_sub(ref.ZERO, a.v))
+    __mod__ = lambda a, _p: a
+    __eq__ = lambda a, b: a.v == E(b).v
+
+
+X = E((0, 1, 0, 0))
+
+
+def from_coordinates(cols4):
+    """four openings of coordinate columns -> the opening of the extension-valued column: sum_k X^k c_k"""
+    return cols4[0] + X * (cols4[1] + X * (cols4[2] + X * cols4[3]))
+
+
+def folded_combination(cells, perm, perm_next, selectors, cons, it, starts, apow, alpha, blpow, S):
+    """sum_c apow[c] C_c + sum_g apow[nc + g] (q_g den_g - num_g) + apow[nc + G] is_first (phi - sum q) + apow[nc + G + 1]
+    is_transition (phi' - phi - sum q') + apow[nc + G + 2] is_last (phi - S), from ONE point's values (a trace row or the openings at
+    zeta and g zeta), scalar by scalar: cells (W), perm / perm_next (4 G + 4 coordinate values at the point and at its successor),
+    selectors = (is_first, is_last, is_transition). -> (the combination, [q_g den_g - num_g per group])"""
+    (bc, spans), (inter, ispans, ibc) = cons, it
+    prog = lambda code, s: eval_postfix(code[int(s[0]):int(s[0]) + int(s[1])].tolist(), cells)
+    nc, G = len(spans), len(starts) - 1
+    acc = E(0)
+    for c in range(nc):
+        acc = acc + E(apow[c]) * prog(bc, spans[c])
+    ms, ds = [], []
+    for bus, n_args, s0 in inter.tolist():
+        ms.append(E(prog(ibc, ispans[s0])))
+        d = E(alpha) + bus
+        for j in range(n_args):
+            d = d + E(blpow[j + 1]) * prog(ibc, ispans[s0 + 1 + j])
+        ds.append(d)
+    terms, sumq, sumq_next = [], E(0), E(0)
+    for g in range(G):
+        members = range(int(starts[g]), int(starts[g + 1]))
+        den, num = E(1), E(0)
+        for i in members:
+            den = den * ds[i]
+            rest = E(1)
+            for l in members:
+                if l != i:
+                    rest = rest * ds[l]
+            num = num + ms[i] * rest
+        qg = from_coordinates(perm[4 * g:4 * g + 4])
+        terms.append(qg * den - num)
+        acc = acc + E(apow[nc + g]) * terms[-1]
+        sumq, sumq_next = sumq + qg, sumq_next + from_coordinates(perm_next[4 * g:4 * g + 4])
+    phi, phi_next = from_coordinates(perm[4 * G:4 * G + 4]), from_coordinates(perm_next[4 * G:4 * G + 4])
+    is_first, is_last, is_trans = selectors
+    acc = acc + E(apow[nc + G]) * (is_first * (phi - sumq))
+    acc = acc + E(apow[nc + G + 1]) * (is_trans * (phi_next - phi - sumq_next))
+    acc = acc + E(apow[nc + G + 2]) * (is_last * (phi - E(S)))
+    return acc, terms
+
+
+def test_logup_and_quotient_references_satisfy_the_verifiers_identity():
+    """A small AIR whose trace satisfies its constraints and whose bus balances: the reference's permutation trace and quotient, with
+    true powers of random challenges, satisfy what a verifier checks — at a random point zeta of E the folded combination of the
+    openings (trace and permutation matrix at zeta and g zeta, recomputed here scalar by scalar) equals Z_H(zeta) q(zeta); on the
+    trace domain every group's q_g den_g - num_g vanishes, and phi's differences are the row sums."""
+    from tests import _random_airs as ra
+
+    for seed in (1, 2, 3):
+        log_h = 4
+        H, N, log_n = 1 << log_h, 2 << log_h, log_h + 1
+        air = ra.derived_air(seed, log_h)
+        W, cons, it, T = air["W"], air["cons"], air["it"], air["T"]
+        assert air["check"](T)[0] == 0
+        starts = sm.group_starts(*it)
+        nc, G = len(cons[1]), len(starts) - 1
+        rng = np.random.default_rng(100 + seed)
+        alpha, beta, alpha_c, zeta = as_tuples(rand_ext(rng, 4))
+        blpow = ref.ext_powers(beta, int(it[0][:, 1].max()) + 2)
+        apow = ref.ext_powers(alpha_c, nc + G + 3, reversed_=True)
+        q, rowsum, phi = ref.logup_perm(T, it, starts, alpha, blpow)
+        assert q.shape == (G, H, 4) and as_tuples(phi[0]) == as_tuples(rowsum[0])
+        for r in range(1, H):
+            assert ref.ext_sub(as_tuples(phi[r])[0], as_tuples(phi[r - 1])[0]) == as_tuples(rowsum[r])[0]
+        S = as_tuples(phi[H - 1])[0]
+        assert S == ref.ZERO  # the bus balances
+        perm = np.concatenate([q.transpose(0, 2, 1).reshape(4 * G, H), phi.T]).astype(np.uint32)
+        # on the trace domain: the group terms vanish row by row, the boundary terms too (the selectors' values there: row_layout)
+        sel = ref.row_layout(np.zeros((0, H), np.uint64), log_h, [], 1, True, True)
+        for r in range(H):
+            nxt = (r + 1) % H
+            acc, terms = folded_combination([E(int(x)) for x in T[:, r]], [E(int(x)) for x in perm[:, r]], [E(int(x)) for x in perm[:, nxt]],
+                                            [E(int(sel[t, r])) for t in range(3)], cons, it, starts, as_tuples(apow), alpha, as_tuples(blpow), S)
+            assert all(t == 0 for t in terms) and acc == 0, (seed, r)
+        lde = sm.lde(T.reshape(-1), W, log_h).reshape(W, N)
+        plde = sm.lde(perm.reshape(-1), 4 * G + 4, log_h).reshape(4 * G + 4, N)
+        quot = ref.quotient(lde, plde, log_n, cons, it, starts, apow, alpha, blpow, S)
+        # openings
+        g = ref.root(log_h)
+        gzeta = ref.ext_scale(zeta, g)
+        w, w_next = ref.barycentric_weights(zeta, log_h), ref.barycentric_weights(gzeta, log_h)
+        cells = [E(e) for e in as_tuples(ref.ext_dot(T, w))]
+        p_z, p_gz = [E(e) for e in as_tuples(ref.ext_dot(perm, w))], [E(e) for e in as_tuples(ref.ext_dot(perm, w_next))]
+        # the quotient's interpolant over the shifted domain: v_j = sum_k c_k s^k w^(jk), so the inverse DFT gives c_k s^k
+        sinv = ref.inv(ref.SHIFT)
+        q_z = []
+        for k in range(4):
+            cs = sm.dft(quot[:, k].astype(np.uint32), inverse=True)
+            c = [int(cs[i]) * pow(sinv, i, P) % P for i in range(N)]
+            scaled = np.array([N * c[ref.bitrev(i, log_n)] % P for i in range(N)], np.uint64)
+            q_z.append(E(as_tuples(ref.ext_dot(scaled[None, :], ref.coefficient_weights(zeta, log_n)))[0]))
+        z_h = E(ref.ext_pow(zeta, H)) - 1
+        ginv = ref.inv(g)
+        selectors = (z_h * E(ref.ext_inv(ref.ext_sub(zeta, ref.ONE))), z_h * E(ref.ext_inv(ref.ext_sub(zeta, ref.ext(ginv)))), E(zeta) - ginv)
+        acc, _ = folded_combination(cells, p_z, p_gz, selectors, cons, it, starts, as_tuples(apow), alpha, as_tuples(blpow), S)
+        assert acc == z_h * from_coordinates(q_z), seed
+        # the unscaled current-row part is the quotient's own first two sums
+        sums = ref.quotient_sums(lde, plde, cons, it, starts, apow, alpha, blpow)
+        assert (ref.logup_tail(sums.T[None], plde[4 * G:], plde[:4 * G].reshape(G, 4, N).sum(axis=0) % P, log_n, apow[nc + G:], S) == quot).all()
+        # constraints only: C / Z_H, a polynomial of degree < N again
+        quot0 = ref.quotient(lde, None, log_n, cons, None, None, apow)
+        c0 = E(0)
+        for c in range(nc):
+            off, ln = cons[1][c]
+            c0 = c0 + E(as_tuples(apow)[c]) * eval_postfix(cons[0][int(off):int(off) + int(ln)].tolist(), cells)
+        q0_z = []
+        for k in range(4):
+            cs = sm.dft(quot0[:, k].astype(np.uint32), inverse=True)
+            q0_z.append(E(horner([int(cs[i]) * pow(sinv, i, P) % P for i in range(N)], zeta)))
+        assert c0 == z_h * from_coordinates(q0_z), seed
+
+
+def test_a_vanishing_denominator_zeroes_its_group_and_is_reported_elsewhere():
+    """1 / 0 = 0 for the group's ONE inversion; a denominator that vanishes where the caller did not say so is an error of the inputs"""
+    import pytest
+
+    from tests._edge_values import PA, PC, _programs
+
+    _, it = _programs([], [(3, [PC, 1], [[PA, 0]]), (3, [PA, 1], [[PC, 5]]), (4, [PC, 2], [[PA, 2]])])
+    starts = sm.group_starts(*it)
+    rng = np.random.default_rng(9)
+    T = rng.integers(1, P, (3, 8), dtype=np.uint64)
+    beta = as_tuples(rand_ext(rng))[0]
+    blpow = ref.ext_powers(beta, 3)
+    alpha = ref.ext_sub(ref.ZERO, ref.ext_add(ref.ext(3), ref.ext_scale(beta, int(T[0, 5]))))  # d_0 = 0 on row 5
+    with pytest.raises(AssertionError):
+        ref.logup_perm(T, it, starts, alpha, blpow)
+    q, rowsum, _ = ref.logup_perm(T, it, starts, alpha, blpow, vanishing=[(0, 5)])
+    g0 = [g for g in range(len(starts) - 1) if starts[g] <= 0 < starts[g + 1]][0]
+    assert not q[g0, 5].any() and q[g0, 4].any()
+    ms, ds = ref.interaction_values(T, it, alpha, blpow)
+    for g in range(len(starts) - 1):
+        for r in (4, 5):
+            want = ref.ZERO
+            if not (g == g0 and r == 5):
+                for i in range(int(starts[g]), int(starts[g + 1])):
+                    want = ref.ext_add(want, ref.ext_scale(ref.ext_inv(as_tuples(ds[i][r])[0]), int(ms[i][r])))
+            assert as_tuples(q[g, r])[0] == want, (g, r)
+
+
+def test_inputs_of_the_logup_stage_tests_are_what_they_claim():
+    """tests/test_stage_logup_gpu.py's AIRs and input families, without a GPU: the column AIR's groups; the jit-small chunking yields
+    several chunks and units; in every family of every permutation-trace case no denominator vanishes (logup_perm asserts it), in the
+    vanishing-denominator cases exactly the planted one does, where every multiplicity of its group is non-zero; the bound families put
+    the extreme words where they say"""
+    from powdr_amd import prover
+    from tests import test_stage_logup_gpu as t
+
+    W, cons, it = t.column_air()
+    starts = t.group_starts(it)
+    assert [b - a for a, b in zip(starts, starts[1:])] == [3, 2, 2, 2, 1] and (prover.logup_group_starts(it) == starts).all()
+    assert sorted(set(it[0][:, 1].tolist())) == [0, 1, 2, 3, 4, 5, 7] and len(cons[1]) >= 5
+    assert len(t.wide_air()[1][1]) >= 64
+    for name, make in t.AIRS.items():
+        W, cons, it = make()
+        units, total = prover.jit_generated_sources(W, cons[0], cons[1], it, 0, 200, 1)
+        n_perm = prover.jit_generated_sources(W, cons[0], cons[1], it, 1, 200, 1)[1] if it is not None else 0
+        assert total + n_perm >= 3 and len(units) >= 2, (name, total, n_perm)
+    assert int(om.to_monty(np.array([t.PM1, t.WORD_HI, t.WORD_LO], np.uint32))[0]) == P - 1
+    assert ref.centred_encode(np.array([t.WORD_HI, t.WORD_LO], np.uint64)).tolist() == [ref.HALF, -ref.HALF]
+    for name in ("hand", "column"):
+        W, cons, it = t.AIRS[name]()
+        starts = t.group_starts(it)
+        for log_h in (1, 2, 8, 9):
+            for family in t.PERM_FAMILIES[name]:
+                rng = np.random.default_rng([1, log_h, t.PERM_FAMILIES["column"].index(family)])
+                T, alpha, blpow = t.perm_inputs(name, family, rng, W, it, log_h)
+                q, rowsum, _ = ref.logup_perm(T, it, starts, alpha, blpow)
+                assert q.any() and (log_h < 8 or name == "hand" or not rowsum[3].any())  # row 3: every multiplicity column is zero
+        for log_h in (1, 9):
+            T, alpha, blpow, i, rows = t.vanishing_inputs(name, np.random.default_rng([2, log_h]), W, it, log_h)
+            ref.logup_perm(T, it, starts, alpha, blpow, vanishing=[(i, r) for r in rows])
+            ms, ds = ref.interaction_values(T, it, alpha, blpow)
+            assert not ds[i][rows].any() and all(int(m[r]) for m in ms for r in rows)
