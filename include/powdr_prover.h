@@ -1332,6 +1332,72 @@ int pw_stage_logup_tail(const uint32_t* d_part, uint32_t n_chunks, const uint32_
 /* d_rowsum[r] = sum_c d_part[(4 c + k) H + r] mod p as H extension elements, and the same as 4 columns d_cols4[k H + r]. */
 int pw_stage_rowsum_combine(const uint32_t* d_part, uint32_t n_chunks, size_t H, uint32_t* d_rowsum, uint32_t* d_cols4);
 
+/* ---- single stages: the query phase ----
+ *
+ * The conventions above hold: -1 before any launch for a NULL pointer, a zero size, a log out of range and a host word >= p; else 0 or
+ * a HIP error code. Every call runs the function the provers run; none owns a kernel. Indices that live on the DEVICE (d_idx, the
+ * offsets behind d_ptrs) are the caller's to keep inside the matrices, as they are the provers'. */
+
+/* Proof of work on a transcript given by its parts, HOST arrays of canonical words: the 16 words of the sponge state and the in_len
+ * (0 .. 7) observed words that are not absorbed yet. *witness_out = the SMALLEST w for which the transcript, having observed w, draws
+ * `bits` zero bits — the candidates are searched 2^20 at a time. bits: 1 .. 31 — a prover hands every non-zero pow_bits to this search
+ * (0 means no proof of work and no search) and a drawn word has 31 bits. Converts to Montgomery words, owns and releases its 25 words of
+ * scratch, waits for the stream. hipErrorUnknown: no witness below p. */
+int pw_stage_pow_grind(const uint32_t* state16, const uint32_t* pending, uint32_t in_len, uint32_t bits, uint32_t* witness_out);
+
+/* d_out[q * width + c] = d_m[c * height + d_idx[q]], q < n_idx <= 65535 (column-major matrix, device indices below `height`); with
+ * `canonical` the n_idx * width words are then taken from Montgomery to canonical form, as the proof's rows are. */
+int pw_stage_gather_rows(const uint32_t* d_m, size_t height, uint32_t width, const uint32_t* d_idx, uint32_t n_idx, int canonical,
+                         uint32_t* d_out);
+
+/* d_words[i] <- the canonical representative of the Montgomery word d_words[i], i < n, in place. */
+int pw_stage_canonicalize(uint32_t* d_words, size_t n);
+
+/* The rows of MANY matrices in one launch, as a segment's query phase takes them: for every job (a HOST array of records)
+ *   d_out[out_off + q * width + c] = d_m[c * height + d_idx[idx_off + q]],  q < n_idx.
+ * n_jobs, n_idx <= 65535. The grid is sized by the widest job, by the helper the segment prover uses. Owns the device copy of the
+ * records and waits for the stream. */
+typedef struct {
+    const uint32_t* d_m; /* device matrix, column-major */
+    uint64_t height;
+    uint32_t width;
+    uint32_t idx_off;    /* this job's first index in d_idx */
+    uint64_t out_off;    /* word offset of this job's rows in d_out */
+} PwStageGatherJob;
+int pw_stage_gather_rows_multi(const PwStageGatherJob* jobs, uint32_t n_jobs, const uint32_t* d_idx, uint32_t n_idx, uint32_t* d_out);
+
+/* d_out[r * words_per_record + w] = d_arena[offsets[r] + w], r < n: the digests (8 words) and extension elements (4) of the query
+ * answers. offsets: a HOST array of 64-bit WORD offsets into the arena; n * words_per_record < 2^32. Owns the device copy of the offsets. */
+int pw_stage_gather_records(const uint32_t* d_arena, const uint64_t* offsets, uint32_t words_per_record, uint32_t n, uint32_t* d_out);
+
+/* d_out[i] = *d_ptrs[i], i < n: d_ptrs is a DEVICE array of device pointers. */
+int pw_stage_gather_words(const uint32_t* const* d_ptrs, uint32_t n, uint32_t* d_out);
+
+/* d_cols4[k * len + q] = coordinate k of the extension element d_in[q]: a vector of len <= 2^27 elements as four base columns. */
+int pw_stage_ext_to_cols(const uint32_t* d_in, size_t len, uint32_t* d_cols4);
+
+/* The query pass of a STREAMED proof: rows idx[q] (q < n_idx <= 65535, HOST indices below 2 H) of the low-degree extension on the
+ * 2 H = 2^(log_h + 1) points 31 w^j of `cols` polynomials given by their coefficient arrays as pw_lde_batch leaves them in d_coeffs
+ * (bit-reversed, H-scaled, column stride H; 16-byte aligned): d_rows[q * cols + c], canonical Montgomery words (below p). The extended
+ * domain is walked as 2^log_blocks sub-cosets (1 <= log_blocks <= min(5, log_h), log_h <= 26) of m = 2 H / 2^log_blocks rows; the
+ * queries are bucketed by sub-coset and each sub-coset that holds one takes one of three forms, reported in forms[r] (may be NULL;
+ * 2^log_blocks bytes; 0 = no query there):
+ *   1  one pass, stored terms: the first stage group keeps every 2^12-row tile in LDS and stores the tile's term of each of the n_r
+ *      queried rows; a second kernel sums a column's T = m / 2^12 tiles;
+ *   2  one pass, 64-bit atomic sums in place of the stored terms;
+ *   3  the partial transform (first stage group) of all cols columns into d_work, finished for the queried rows alone.
+ * Forms 1 and 2 exist only where the sub-coset's transform has a first group of 12 stages on whole 2^12-row tiles and a second group
+ * (m >= 2^14), log_blocks <= 2 and cols <= 65535. POWDR_QUERY_SELECT, read per call: 0 = always 3; 2 = 2 where it fits, else 3;
+ * unset / 1 = 1 where it fits, else 2, else 3. With ev(x) = x rounded up to even, the one-pass forms need of d_work
+ *   form 2:  A = 2^13 + ev(n_r) + ev(n_r T) + 2 cols n_r  words,        form 1:  A + cols T n_r  words,
+ * and take the form only if that is at most select_words — the part of d_work OFFERED to them (a prover offers its whole sub-coset
+ * buffer). d_work: 8-byte aligned, work_words >= cols m words (form 3's need; -1 below it, and for select_words > work_words).
+ * d_scale: 2^13 words, as pw_lde_subcoset's. A d_coeffs that is not 16-byte aligned or a d_work that is not 8-byte aligned is refused
+ * before any launch too, with hipErrorInvalidValue (as pw_lde_subcoset answers a misaligned d_coeffs). Owns the 2 n_idx words of its
+ * bucketing tables and waits for the stream. */
+int pw_stage_query_rows(const uint32_t* d_coeffs, uint32_t cols, uint32_t log_h, uint32_t log_blocks, const uint32_t* idx, uint32_t n_idx,
+                        uint32_t* d_work, size_t work_words, size_t select_words, uint32_t* d_scale, uint32_t* d_rows, uint8_t* forms);
+
 /* Host-side Poseidon2 permutation used by the transcript (canonical words in/out). This is also the known-answer-test
  * hook: after pw_set_poseidon2_constants a maintainer feeds it the vector of the backend's own Poseidon2 test. */
 void pw_poseidon2_permute_host(uint32_t* state16);

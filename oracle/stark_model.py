@@ -65,6 +65,21 @@ def set_poseidon2_constants(ext_rc=None, int_rc=None) -> None:
         raise ValueError("round constants must be canonical field elements")
 
 
+POW_NONE = 0xFFFFFFFF
+
+
+def pow_witness(state16, pending, bits: int, lo: int = 0, hi: int = P) -> int:
+    """or_pow_witness: the smallest proof-of-work witness in [lo, hi) for a challenger with sponge state `state16` and the observed,
+    not yet absorbed words `pending` (at most 7; canonical words) — a copy observes the witness and draws `bits` zero bits, as the
+    oracle's provers grind. POW_NONE: no witness in the range (or a malformed call)."""
+    s = np.ascontiguousarray(state16, dtype=np.uint32)
+    q = np.ascontiguousarray(pending, dtype=np.uint32)
+    assert s.shape == (16,) and q.ndim == 1
+    lib = _lib()
+    lib.or_pow_witness.restype = C.c_uint32
+    return int(lib.or_pow_witness(_p(s), _p(q) if len(q) else None, C.c_uint32(len(q)), C.c_uint32(bits), C.c_uint64(lo), C.c_uint64(hi)))
+
+
 def root_of_unity(log_n: int) -> int:
     return int(_lib().or_root_of_unity(C.c_int(log_n)))
 

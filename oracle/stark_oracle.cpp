@@ -1128,6 +1128,31 @@ int or_set_poseidon2_constants(const uint32_t* ext_rc /*8*16*/, const uint32_t* 
     memcpy(p2c_mut().int_rc, int_rc, sizeof p2c().int_rc);
     return 0;
 }
+/* Proof of work as the provers above grind, on a transcript given by its parts: a challenger with the sponge state `state16`, the
+ * `in_len` <= 7 observed words `pending` not yet absorbed and nothing left to sample (canonical words). The smallest witness w in
+ * [lo, hi) — hi is cut at p — for which a COPY of that challenger observes w and then draws `bits` zero bits; 0xFFFFFFFF: none in the
+ * range, or a malformed call (in_len > 7, bits outside 1 .. 31, a word >= p). The candidates are tried 2^16 at a time, every one with
+ * the Challenger's own observe / sample_bits: no shortcut for "the witness fills the rate". */
+uint32_t or_pow_witness(const uint32_t* state16, const uint32_t* pending, uint32_t in_len, uint32_t bits, uint64_t lo, uint64_t hi) {
+    const uint32_t none = 0xFFFFFFFFu;
+    if (!state16 || (in_len && !pending) || in_len > 7 || bits < 1 || bits > 31) return none;
+    Challenger ch;
+    for (int i = 0; i < 16; ++i) { if (state16[i] >= P) return none; ch.st[i] = state16[i]; }
+    for (uint32_t i = 0; i < in_len; ++i) { if (pending[i] >= P) return none; ch.in.push_back(pending[i]); }
+    if (hi > P) hi = P;
+    for (uint64_t base = lo; base < hi; base += 1u << 16) {
+        const uint64_t end = base + (1u << 16) < hi ? base + (1u << 16) : hi;
+        uint32_t best = none;
+#pragma omp parallel for reduction(min : best) schedule(static)
+        for (long long w = (long long)base; w < (long long)end; ++w) {
+            Challenger c2 = ch;
+            c2.observe((u32)w);
+            if (c2.sample_bits((int)bits) == 0 && (u32)w < best) best = (u32)w;
+        }
+        if (best != none) return best;
+    }
+    return none;
+}
 uint32_t or_root_of_unity(int log_n) { return root_of_unity(log_n); }
 void or_ext_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { Ext x, y; memcpy(x.c, a, 16); memcpy(y.c, b, 16); Ext r = ext_mul(x, y); memcpy(o, r.c, 16); }
 void or_ext_inv(const uint32_t* a, uint32_t* o) { Ext x; memcpy(x.c, a, 16); Ext r = ext_inv(x); memcpy(o, r.c, 16); }

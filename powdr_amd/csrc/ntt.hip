@@ -1314,10 +1314,12 @@ __global__ __launch_bounds__(128) void select_reduce_kernel(const uint32_t* __re
 // (the tile stays in LDS, every selected output gets this tile's term through a 64-bit atomic sum) — the query phase of a streamed
 // proof reads the coefficients once and writes a few megabytes. Tall transforms only (one 2^12-tile per workgroup and at least one
 // strided stage left); returns 1 when the shape does not qualify and nothing was done (the caller then takes
-// subcoset_lde_first_group + subcoset_rows). d_work: 2^13 + n_idx * (2^k2 + 1) words + cols * n_idx 64-bit sums.
+// subcoset_lde_first_group + subcoset_rows). d_work: 2^13 + n_idx * (2^k2 + 1) words (each of the two terms rounded up to even) +
+// cols * n_idx 64-bit sums; the stored-terms form takes cols * 2^k2 * n_idx words more. *form_out: prover_internal.hpp.
 int subcoset_query_rows(const uint32_t* coeffs, size_t in_stride, uint32_t cols, int n, int b, uint32_t r, const uint32_t* d_local_idx,
-                        uint32_t n_idx, const uint32_t* d_slot, uint32_t* rows_out, uint32_t* d_work, size_t work_words) {
+                        uint32_t n_idx, const uint32_t* d_slot, uint32_t* rows_out, uint32_t* d_work, size_t work_words, int* form_out) {
     const int nm = n + 1 - b;
+    if (form_out) *form_out = 0;
     if (!n_idx || !cols) return 0;
     if (cols > 65535u) return 1;  // (one launch: blockIdx.y is the column)
     // POWDR_QUERY_SELECT: 0 = never (the stored partial transform + subcoset_rows), 2 = round 5's 64-bit atomic sums, default (1) =
@@ -1350,6 +1352,7 @@ int subcoset_query_rows(const uint32_t* coeffs, size_t in_stride, uint32_t cols,
                            field::root_of_unity(nm), d_xpow, d_pos, (1u << k1) - 1u);
     }
     if (!partial) PW_HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)cols * n_idx * sizeof(unsigned long long), stream()));
+    if (form_out) *form_out = partial ? 1 : 2;
     cs.n_sel = (int)n_idx; cs.sel_pos = d_pos; cs.sel_xpow = d_xpow; cs.sel_acc = d_acc; cs.sel_part = partial ? d_part : nullptr;
     int done = 0;
     // (`out` of the group is never written in SELECT mode: the coefficient array stands in for it)

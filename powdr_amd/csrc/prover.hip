@@ -1379,6 +1379,88 @@ extern "C" int pw_stage_rowsum_combine(const uint32_t* d_part, uint32_t n_chunks
     return logup_rowsum_combine(d_part, n_chunks, H, reinterpret_cast<bb::Ext*>(d_rowsum), d_cols4);
 }
 
+// ---- the query phase: grinding, the gathers, a streamed AIR's rows -------------------------------------------------------------
+// The same thin wrappers: each forwards to the function the provers call (grind_search, gather_rows, gather_rows_multi, gather_records,
+// gather_words, canonicalize_words, ext_to_cols, streamed::query_rows_core).
+static_assert(sizeof(PwStageGatherJob) == sizeof(GatherRowsJob), "PwStageGatherJob restates GatherRowsJob");
+
+extern "C" int pw_stage_pow_grind(const uint32_t* state16, const uint32_t* pending, uint32_t in_len, uint32_t bits, uint32_t* witness_out) {
+    (void)hipGetLastError();
+    // bits: the provers hand any non-zero pow_bits to the search (0 = no proof of work), and a sampled word has 31 bits (1u << bits)
+    if (!state16 || !witness_out || (in_len && !pending) || in_len > 7 || bits < 1 || bits > 31) return -1;
+    uint32_t st[16], in[8] = {0};
+    for (int i = 0; i < 16; ++i) { if (state16[i] >= bb::P) return -1; st[i] = bb::to_monty(state16[i]); }
+    for (uint32_t i = 0; i < in_len; ++i) { if (pending[i] >= bb::P) return -1; in[i] = bb::to_monty(pending[i]); }
+    StageScratch s;
+    TRY(s.alloc(25 * 4));
+    return grind_search(st, in, in_len, bits, s.as<uint32_t>(), witness_out);
+}
+
+extern "C" int pw_stage_canonicalize(uint32_t* d_words, size_t n) {
+    (void)hipGetLastError();
+    if (!d_words || !n) return -1;
+    return canonicalize_words(d_words, n);
+}
+
+extern "C" int pw_stage_gather_rows(const uint32_t* d_m, size_t height, uint32_t width, const uint32_t* d_idx, uint32_t n_idx, int canonical,
+                                    uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_m || !d_idx || !d_out || !height || !width || !n_idx || n_idx > 65535u) return -1;  // (blockIdx.y is the query)
+    TRY(gather_rows(d_m, height, width, d_idx, n_idx, d_out));
+    return canonical ? canonicalize_words(d_out, (size_t)n_idx * width) : 0;
+}
+
+extern "C" int pw_stage_gather_rows_multi(const PwStageGatherJob* jobs, uint32_t n_jobs, const uint32_t* d_idx, uint32_t n_idx, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!jobs || !d_idx || !d_out || !n_jobs || !n_idx || n_jobs > 65535u || n_idx > 65535u) return -1;
+    std::vector<GatherRowsJob> h(n_jobs);
+    for (uint32_t k = 0; k < n_jobs; ++k) {
+        if (!jobs[k].d_m || !jobs[k].height || !jobs[k].width) return -1;
+        h[k] = GatherRowsJob{jobs[k].d_m, jobs[k].height, jobs[k].width, jobs[k].idx_off, jobs[k].out_off};
+    }
+    StageScratch s;
+    TRY(s.alloc(h.size() * sizeof(GatherRowsJob)));
+    PW_HIP_TRY(hipMemcpyAsync(s.p, h.data(), h.size() * sizeof(GatherRowsJob), hipMemcpyHostToDevice, stream()));
+    return gather_rows_multi(s.as<GatherRowsJob>(), n_jobs, gather_rows_max_width(h.data(), h.size()), d_idx, n_idx, d_out);
+}
+
+extern "C" int pw_stage_gather_records(const uint32_t* d_arena, const uint64_t* offsets, uint32_t words_per_record, uint32_t n, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_arena || !offsets || !d_out || !words_per_record || !n || (uint64_t)n * words_per_record > 0xffffffffull) return -1;
+    StageScratch s;
+    TRY(s.alloc((size_t)n * 8));
+    PW_HIP_TRY(hipMemcpyAsync(s.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, stream()));
+    return gather_records(d_arena, s.as<uint64_t>(), words_per_record, n, d_out);
+}
+
+extern "C" int pw_stage_gather_words(const uint32_t* const* d_ptrs, uint32_t n, uint32_t* d_out) {
+    (void)hipGetLastError();
+    if (!d_ptrs || !d_out || !n) return -1;
+    return gather_words(d_ptrs, n, d_out);
+}
+
+extern "C" int pw_stage_ext_to_cols(const uint32_t* d_in, size_t len, uint32_t* d_cols4) {
+    (void)hipGetLastError();
+    if (!d_in || !d_cols4 || !len || len > ((size_t)1 << kStageMaxLog)) return -1;
+    return ext_to_cols(reinterpret_cast<const bb::Ext*>(d_in), len, d_cols4);
+}
+
+extern "C" int pw_stage_query_rows(const uint32_t* d_coeffs, uint32_t cols, uint32_t log_h, uint32_t log_blocks, const uint32_t* idx, uint32_t n_idx,
+                                   uint32_t* d_work, size_t work_words, size_t select_words, uint32_t* d_scale, uint32_t* d_rows, uint8_t* forms) {
+    (void)hipGetLastError();
+    if (!d_coeffs || !idx || !d_work || !d_scale || !d_rows || !cols || !n_idx || n_idx > 65535u) return -1;
+    if (log_blocks < 1 || log_blocks > 5 || log_blocks > log_h || log_h > 26) return -1;  // (pw_lde_subcoset's range; subcoset_spec: b <= 5)
+    const size_t H = (size_t)1 << log_h, m = (2 * H) >> log_blocks;
+    for (uint32_t q = 0; q < n_idx; ++q) if (idx[q] >= 2 * H) return -1;
+    if (work_words < (size_t)cols * m || select_words > work_words) return -1;
+    if (((uintptr_t)d_coeffs & 15) || ((uintptr_t)d_work & 7)) return (int)hipErrorInvalidValue;  // (16-byte staged loads; the 64-bit sums)
+    StageScratch s;
+    TRY(s.alloc((size_t)n_idx * 8));
+    uint32_t* d_loc = s.as<uint32_t>();
+    return streamed::query_rows_core(d_coeffs, cols, log_h, (int)log_blocks, idx, n_idx, d_loc, d_loc + n_idx, d_rows, d_work, select_words, d_scale,
+                                     forms);
+}
+
 extern "C" int pw_set_poseidon2_constants(const uint32_t* ext_rc, const uint32_t* int_rc) {
     return poseidon2_set_constants(ext_rc, int_rc);
 }

@@ -43,9 +43,10 @@ int values_from_coefficients(const uint32_t* coeffs, uint32_t* out, size_t in_st
 int subcoset_lde_first_group(const uint32_t* coeffs, uint32_t* out, size_t in_stride, size_t out_stride, uint32_t cols, int n, int b, uint32_t r,
                              uint32_t* d_scratch, int* stages_done);
 // The same rows in ONE pass that stores no partial transform (tall transforms; ntt.hip subcoset_query_rows): 0 = done, 1 = the shape
-// does not qualify (use the two calls above), else an error. d_work: 8-byte aligned scratch of work_words words.
+// does not qualify (use the two calls above), else an error. d_work: 8-byte aligned scratch of work_words words. *form_out (may be
+// null), when 0 is returned: 1 = every tile's terms were stored and summed, 2 = 64-bit atomic sums, 0 = nothing to do.
 int subcoset_query_rows(const uint32_t* coeffs, size_t in_stride, uint32_t cols, int n, int b, uint32_t r, const uint32_t* d_local_idx,
-                        uint32_t n_idx, const uint32_t* d_slot, uint32_t* rows_out, uint32_t* d_work, size_t work_words);
+                        uint32_t n_idx, const uint32_t* d_slot, uint32_t* rows_out, uint32_t* d_work, size_t work_words, int* form_out = nullptr);
 int subcoset_rows(const uint32_t* part, size_t stride, uint32_t cols, int n, int b, uint32_t r, int stages_done, const uint32_t* d_local_idx,
                   uint32_t n_idx, const uint32_t* d_slot, uint32_t* rows_out);  // row q goes to slot d_slot[q] (null: q)
 
@@ -150,6 +151,12 @@ int gamma_powers(bb::Ext gamma, uint32_t K, bb::Ext* d_gpow);
 // rows d_indices[idx_off + q] (q < n_idx) of n_jobs column-major matrices into out + out_off (row-major, q-th row at q * width): ONE launch
 struct GatherRowsJob { const uint32_t* m; uint64_t height; uint32_t width; uint32_t idx_off; uint64_t out_off; };
 int gather_rows_multi(const GatherRowsJob* d_jobs, uint32_t n_jobs, uint32_t max_width, const uint32_t* d_indices, uint32_t n_idx, uint32_t* out);
+// the max_width of a launch: the widest of the (host) job records
+inline uint32_t gather_rows_max_width(const GatherRowsJob* jobs, size_t n_jobs) {
+    uint32_t w = 0;
+    for (size_t k = 0; k < n_jobs; ++k) w = jobs[k].width > w ? jobs[k].width : w;
+    return w;
+}
 int fri_fold(const bb::Ext* v, size_t half, int log_size, uint32_t shift, bb::Ext beta, bb::Ext* out);
 // y[i] += a * x[i] (a == nullptr: a = 1), Ext vectors of length n
 int ext_axpy(bb::Ext* y, const bb::Ext* a_or_null, const bb::Ext* x, size_t n);

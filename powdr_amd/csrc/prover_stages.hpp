@@ -348,16 +348,20 @@ inline int fri_commit_round(const bb::Ext* v, size_t half, uint32_t* digests, ui
     return 0;
 }
 
+// The proof-of-work search on a transcript's parts: the sponge state and the in_len <= 7 observed words not yet absorbed (Montgomery
+// words); *witness = the smallest one. d_scratch: 25 words.
+inline int grind_search(const uint32_t* st16, const uint32_t* in, size_t in_len, uint32_t pow_bits, uint32_t* d_scratch, uint32_t* witness) {
+    uint32_t pending[8] = {0};
+    for (size_t i = 0; i < in_len; ++i) pending[i] = in[i];
+    PW_HIP_TRY(hipMemcpyAsync(d_scratch, st16, 64, hipMemcpyHostToDevice, stream()));
+    PW_HIP_TRY(hipMemcpyAsync(d_scratch + 16, pending, 32, hipMemcpyHostToDevice, stream()));
+    return pow_grind(d_scratch, d_scratch + 16, (uint32_t)in_len, pow_bits, d_scratch + 24, witness);
+}
+
 // Proof of work on the transcript as it stands: *witness (0 when pow_bits is 0) is observed and the bits are drawn. d_scratch: 25 words.
 inline int grind(Challenger& ch, uint32_t pow_bits, uint32_t* d_scratch, uint32_t* witness) {
     *witness = 0;
-    if (pow_bits) {
-        uint32_t pending[8] = {0};
-        for (size_t i = 0; i < ch.in.size(); ++i) pending[i] = ch.in[i];
-        PW_HIP_TRY(hipMemcpyAsync(d_scratch, ch.st, 64, hipMemcpyHostToDevice, stream()));
-        PW_HIP_TRY(hipMemcpyAsync(d_scratch + 16, pending, 32, hipMemcpyHostToDevice, stream()));
-        PW_STRY(pow_grind(d_scratch, d_scratch + 16, (uint32_t)ch.in.size(), pow_bits, d_scratch + 24, witness));
-    }
+    if (pow_bits) PW_STRY(grind_search(ch.st, ch.in.data(), ch.in.size(), pow_bits, d_scratch, witness));
     ch.observe_canonical(*witness);
     if (pow_bits) (void)ch.sample_bits((int)pow_bits);
     return 0;

@@ -93,36 +93,49 @@ inline int quotient_sums(const Ctx& c, bool jit, bool lg, uint32_t nc, const Con
     });
 }
 
-// LDE rows idx[q] (q < n) of the matrix given by `coef` into d_rows[q * cols ..] (canonical Montgomery words): one more pass over the
-// sub-cosets that hold a queried row, of which only the contiguous stage group runs over every row — the strided stages are finished
-// for the queried rows alone (subcoset_rows). d_loc / d_slot: n words of device scratch each (row inside its sub-coset; answer slot).
-inline int query_rows(const Ctx& c, const uint32_t* coef, uint32_t cols, const uint32_t* idx, uint32_t n, uint32_t* d_loc, uint32_t* d_slot,
-                      uint32_t* d_rows) {
+// LDE rows idx[q] (q < n) of the matrix given by `coef` (H = 2^log_h words a column) into d_rows[q * cols ..] (canonical Montgomery
+// words): one more pass over the 2^b sub-cosets that hold a queried row, of which only the contiguous stage group runs over every row —
+// the strided stages are finished for the queried rows alone (subcoset_rows). d_loc / d_slot: n words of device scratch each (row inside
+// its sub-coset; answer slot). d_work: 8-byte aligned scratch, cols * m words for the partial transform (m = 2^(log_h + 1 - b)), of
+// which the one-pass form (subcoset_query_rows) is offered select_words; d_scale: 2^13 words (the sub-coset's twiddle table).
+// forms (may be null; 2^b entries): per sub-coset 0 = no query there, 1 / 2 = one pass with stored terms / atomic sums, 3 = the
+// partial transform + subcoset_rows.
+inline int query_rows_core(const uint32_t* coef, uint32_t cols, uint32_t log_h, int b, const uint32_t* idx, uint32_t n, uint32_t* d_loc,
+                           uint32_t* d_slot, uint32_t* d_rows, uint32_t* d_work, size_t select_words, uint32_t* d_scale, uint8_t* forms) {
+    const uint32_t nb = 1u << b;
+    if (forms) std::fill(forms, forms + nb, (uint8_t)0);
     if (!n || !cols) return 0;
-    const uint32_t nb = 1u << c.b;
+    const size_t H = (size_t)1 << log_h, m = (2 * H) >> b;
     std::vector<uint32_t> order(n), loc(n), slot(n), first(nb + 1, 0);
     for (uint32_t q = 0; q < n; ++q) { order[q] = q; first[(idx[q] & (nb - 1)) + 1] += 1; }
     for (uint32_t r = 0; r < nb; ++r) first[r + 1] += first[r];
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b2) { return (idx[a] & (nb - 1)) < (idx[b2] & (nb - 1)); });
-    for (uint32_t k = 0; k < n; ++k) { loc[k] = idx[order[k]] >> c.b; slot[k] = order[k]; }
+    for (uint32_t k = 0; k < n; ++k) { loc[k] = idx[order[k]] >> b; slot[k] = order[k]; }
     hipStream_t st = pw::stream();
     PW_HIP_TRY(hipMemcpyAsync(d_loc, loc.data(), n * 4, hipMemcpyHostToDevice, st));
     PW_HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), n * 4, hipMemcpyHostToDevice, st));
     PW_HIP_TRY(hipStreamSynchronize(st));  // loc / slot are locals
-    uint32_t* d_blk = c.p->lde.as<uint32_t>();
-    uint32_t* fs = c.p->fscale.as<uint32_t>();
     for (uint32_t r = 0; r < nb; ++r) {
         const uint32_t k0 = first[r], cnt = first[r + 1] - first[r];
         if (!cnt) continue;
-        // tall sub-cosets: one pass that keeps the tiles in LDS and sums the queried rows' terms (p->lde is only scratch then)
-        const int sel = subcoset_query_rows(coef, c.H, cols, (int)c.log_h, c.b, r, d_loc + k0, cnt, d_slot + k0, d_rows, d_blk, c.p->lde.bytes / 4);
-        if (sel == 0) continue;
+        // tall sub-cosets: one pass that keeps the tiles in LDS and sums the queried rows' terms (d_work is only scratch then)
+        int form = 0;
+        const int sel = subcoset_query_rows(coef, H, cols, (int)log_h, b, r, d_loc + k0, cnt, d_slot + k0, d_rows, d_work, select_words, &form);
+        if (sel == 0) { if (forms) forms[r] = (uint8_t)form; continue; }
         if (sel != 1) return sel;
         int done = 0;
-        PW_STRY(subcoset_lde_first_group(coef, d_blk, c.H, c.m, cols, (int)c.log_h, c.b, r, fs, &done));
-        PW_STRY(subcoset_rows(d_blk, c.m, cols, (int)c.log_h, c.b, r, done, d_loc + k0, cnt, d_slot + k0, d_rows));
+        PW_STRY(subcoset_lde_first_group(coef, d_work, H, m, cols, (int)log_h, b, r, d_scale, &done));
+        PW_STRY(subcoset_rows(d_work, m, cols, (int)log_h, b, r, done, d_loc + k0, cnt, d_slot + k0, d_rows));
+        if (forms) forms[r] = 3;
     }
     return 0;
+}
+
+// The same for a prover's AIR: the scratch is p->lde (all of it offered to the one-pass form) and p->fscale.
+inline int query_rows(const Ctx& c, const uint32_t* coef, uint32_t cols, const uint32_t* idx, uint32_t n, uint32_t* d_loc, uint32_t* d_slot,
+                      uint32_t* d_rows) {
+    return query_rows_core(coef, cols, c.log_h, c.b, idx, n, d_loc, d_slot, d_rows, c.p->lde.as<uint32_t>(), c.p->lde.bytes / 4,
+                           c.p->fscale.as<uint32_t>(), nullptr);
 }
 
 // v[j] = (sum_k g^k P_k(x_j) - sum1) / (x_j - zeta) [+ (sum_k g^(K1+k) perm_k(x_j) - sum2) / (x_j - g zeta)] from the coefficient arrays:

@@ -555,7 +555,6 @@ int answer_queries(Seg& s) {
     // rows: tree by tree (proof order main, perm, quotient), AIR by AIR, nq rows each
     std::vector<size_t> row_off[3], pre_row_off(A, 0), pre_dig_off(A, 0);
     std::vector<GatherRowsJob> jobs;  // (alive until the synchronisation below)
-    uint32_t max_w = 0;
     size_t ro = 0;
     TRY(s.fan.fork());  // after the index upload
     for (int ph = 0; ph < 3; ++ph) {
@@ -574,7 +573,6 @@ int answer_queries(Seg& s) {
                                          s.m.rows + ro));
             } else {
                 jobs.push_back(GatherRowsJob{m, (uint64_t)s.sh[a].N, w, (uint32_t)(a * nq), (uint64_t)ro});
-                max_w = std::max(max_w, w);
             }
             ro += (size_t)nq * w;
         }
@@ -587,7 +585,6 @@ int answer_queries(Seg& s) {
         if (!sh.Wf) continue;
         pre_row_off[a] = ro;
         jobs.push_back(GatherRowsJob{s.prover(a)->pre_lde.as<uint32_t>(), (uint64_t)sh.N, sh.Wf, (uint32_t)(a * nq), (uint64_t)ro});
-        max_w = std::max(max_w, sh.Wf);
         ro += (size_t)nq * sh.Wf;
         pre_dig_off[a] = pre_offs.size();
         for (uint32_t qi = 0; qi < nq; ++qi)
@@ -598,7 +595,7 @@ int answer_queries(Seg& s) {
     }
     if (!jobs.empty()) {  // the resident matrices' rows: one launch for all AIRs and trees
         PW_HIP_TRY(hipMemcpyAsync(s.m.jobs, jobs.data(), jobs.size() * sizeof(GatherRowsJob), hipMemcpyHostToDevice, s.st));
-        TRY(gather_rows_multi(s.m.jobs, (uint32_t)jobs.size(), max_w, s.m.idx, nq, s.m.rows));
+        TRY(gather_rows_multi(s.m.jobs, (uint32_t)jobs.size(), gather_rows_max_width(jobs.data(), jobs.size()), s.m.idx, nq, s.m.rows));
     }
     // the mixed trees' siblings (digest arena order: main | quotient | perm), then the FRI part, query by query
     const int tree_of_phase[3] = {0, 2, 1};

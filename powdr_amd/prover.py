@@ -14,6 +14,11 @@ class PwStarkConfig(C.Structure):
     _fields_ = [("num_queries", C.c_uint32), ("pow_bits", C.c_uint32)]
 
 
+class PwStageGatherJob(C.Structure):
+    """One matrix of pw_stage_gather_rows_multi (include/powdr_prover.h)."""
+    _fields_ = [("d_m", C.c_void_p), ("height", C.c_uint64), ("width", C.c_uint32), ("idx_off", C.c_uint32), ("out_off", C.c_uint64)]
+
+
 PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create", "pw_prover_create_logup", "pw_verify_logup", "pw_prover_trace_root", "pw_prover_set_bus_seed", "pw_prover_logup_path", "pw_prove_airs", "pw_verify_airs", "pw_prove_segment", "pw_verify_segment", "pw_commitment_digest", "pw_logup_group_starts", "pw_prover_width", "pw_prover_reserve", "pw_prover_stream_log_blocks", "pw_prover_max_constraint_degree", "pw_prover_destroy", "pw_prover_prove", "pw_prover_prove_consuming", "pw_prover_stream_log_blocks_consuming", "pw_trace_from_coefficients", "pw_prover_device_bytes",
                   "pw_lde_batch", "pw_lde_fused", "pw_lde_subcoset", "pw_merkle_commit", "pw_poseidon2_permute_host",
                   "pw_merkle_leaf_hash", "pw_merkle_leaf_absorb", "pw_merkle_commit_mixed", "pw_merkle_commit_ext_pairs",
@@ -22,6 +27,8 @@ PROVER_SYMBOLS = ["pw_prover_check_constraints", "pw_verify", "pw_prover_create"
                   "pw_stage_row_layout", "pw_stage_part_scatter", "pw_stage_ext_axpy",
                   "pw_stage_logup_perm", "pw_stage_quotient", "pw_stage_quotient_sums", "pw_stage_logup_tail", "pw_stage_rowsum_combine",
                   "pw_prover_quotient_units", "pw_prover_quotient_unit_groups",
+                  "pw_stage_pow_grind", "pw_stage_gather_rows", "pw_stage_canonicalize", "pw_stage_gather_rows_multi", "pw_stage_gather_records",
+                  "pw_stage_gather_words", "pw_stage_ext_to_cols", "pw_stage_query_rows",
                   "pw_set_poseidon2_constants", "pw_get_poseidon2_constants", "pw_prover_specialise", "pw_prover_specialised", "pw_jit_compile_check", "pw_jit_cache_stats", "pw_jit_generated_source",
                   "pw_prove_segments_multi", "pw_multi_last_merge", "pw_assign_units",
                   "pw_prove_segment_consuming", "pw_segment_last_modes", "pw_segment_last_plan", "pw_set_device_budget", "pw_get_device_budget", "pw_provers_specialise",
@@ -126,6 +133,16 @@ _STAGE_ARGTYPES = {
                                C.POINTER(C.c_uint32)],
     "pw_stage_logup_tail": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
     "pw_stage_rowsum_combine": [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p],
+    # the query phase: grinding (host words in, the witness out), the gathers, a streamed AIR's rows (host indices, a byte per sub-coset out)
+    "pw_stage_pow_grind": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
+    "pw_stage_gather_rows": [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p],
+    "pw_stage_canonicalize": [C.c_void_p, C.c_size_t],
+    "pw_stage_gather_rows_multi": [C.POINTER(PwStageGatherJob), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "pw_stage_gather_records": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "pw_stage_gather_words": [C.c_void_p, C.c_uint32, C.c_void_p],
+    "pw_stage_ext_to_cols": [C.c_void_p, C.c_size_t, C.c_void_p],
+    "pw_stage_query_rows": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                            C.c_void_p, C.c_void_p],
 }
 for _name, _argtypes in _STAGE_ARGTYPES.items():
     getattr(lib, _name).restype = C.c_int

@@ -251,6 +251,16 @@ pub struct PwStarkConfig {
     pub num_queries: u32,
     pub pow_bits: u32,
 }
+/// One matrix of `pw_stage_gather_rows_multi`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct PwStageGatherJob {
+    pub d_m: *const u32,
+    pub height: u64,
+    pub width: u32,
+    pub idx_off: u32,
+    pub out_off: u64,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct PwSegmentAir {
@@ -813,6 +823,15 @@ extern "C" {
     pub fn pw_stage_rowsum_combine(d_part: *const u32, n_chunks: u32, h: usize, d_rowsum: *mut u32, d_cols4: *mut u32) -> c_int;
     pub fn pw_prover_quotient_units(p: *const PwProver) -> u32;
     pub fn pw_prover_quotient_unit_groups(p: *const PwProver, unit: u32, g0: *mut u32, g1: *mut u32) -> c_int;
+    pub fn pw_stage_pow_grind(state16: *const u32, pending: *const u32, in_len: u32, bits: u32, witness_out: *mut u32) -> c_int;
+    pub fn pw_stage_gather_rows(d_m: *const u32, height: usize, width: u32, d_idx: *const u32, n_idx: u32, canonical: c_int, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_canonicalize(d_words: *mut u32, n: usize) -> c_int;
+    pub fn pw_stage_gather_rows_multi(jobs: *const PwStageGatherJob, n_jobs: u32, d_idx: *const u32, n_idx: u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_gather_records(d_arena: *const u32, offsets: *const u64, words_per_record: u32, n: u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_gather_words(d_ptrs: *const *const u32, n: u32, d_out: *mut u32) -> c_int;
+    pub fn pw_stage_ext_to_cols(d_in: *const u32, len: usize, d_cols4: *mut u32) -> c_int;
+    pub fn pw_stage_query_rows(d_coeffs: *const u32, cols: u32, log_h: u32, log_blocks: u32, idx: *const u32, n_idx: u32, d_work: *mut u32,
+                               work_words: usize, select_words: usize, d_scale: *mut u32, d_rows: *mut u32, forms: *mut u8) -> c_int;
     pub fn pw_prover_specialise(p: *mut PwProver) -> c_int;
     pub fn pw_prover_specialised(p: *const PwProver, n_kernels: *mut usize, code_bytes: *mut usize, n_chunks: *mut usize) -> c_int;
     pub fn pw_prove_segments_multi(devices: *const c_int, n_workers: usize, segment_cells: *const u64, n_segments: usize,

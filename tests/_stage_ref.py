@@ -500,6 +500,65 @@ def logup_tail(part, phi_cols, sumq_cols, log_n: int, apow_tail, S):
     return _boundary_and_divide(rowsum_combine(part), np.asarray(phi_cols, np.uint64).T, np.asarray(sumq_cols, np.uint64).T, log_n, apow_tail, S)
 
 
+# ---------------------------------------------------------------------------------------------------------- the query phase
+# A streamed proof answers its queries from COEFFICIENTS: c[col][k], P_col(x) = sum_k c[col][k] x^k, k < H = 2^log_h. The reference
+# below starts there too, so a test of the query pass runs no transform of the code under test.
+def coefficient_arrays(c, log_h: int):
+    """canonical coefficients c[col][k] -> the values the device arrays hold (as Montgomery words: to_word), H c[col][bitrev(q)] at q:
+    bit-reversed and H-scaled, as the inverse transform of the provers leaves them"""
+    c = np.asarray(c, np.uint64).reshape(-1, 1 << log_h) % _p
+    br = np.array([bitrev(q, log_h) for q in range(1 << log_h)], np.int64)
+    return c[:, br] * np.uint64((1 << log_h) % P) % _p
+
+
+def power_vector(x: int, n: int):
+    """x^0 .. x^(n-1) for a power of two n, by doubling: the second half is the first times x^(half)"""
+    pw = np.ones(1, np.uint64)
+    while len(pw) < n:
+        pw = np.concatenate([pw, pw * np.uint64(pow(x, len(pw), P)) % _p])
+    return pw
+
+
+def lde_rows(c, log_h: int, idx):
+    """rows idx[q] of the extension on the 2^(log_h+1) points x_j = 31 w^j, w = root(log_h + 1): out[q][col] = sum_k c[col][k] x^k.
+    Every product is reduced before the sum: 2^log_h words below p, far inside uint64."""
+    c = np.asarray(c, np.uint64).reshape(-1, 1 << log_h) % _p
+    w, seen, out = root(log_h + 1), {}, np.zeros((len(idx), len(c)), np.uint64)
+    for q, j in enumerate(idx):
+        j = int(j)
+        if j not in seen:
+            pw = power_vector(SHIFT * pow(w, j, P) % P, 1 << log_h)
+            seen[j] = (c * pw % _p).sum(axis=1) % _p
+        out[q] = seen[j]
+    return out
+
+
+def pow_families(rng):
+    """inputs of the proof-of-work tests, (sponge state, 7 pending words) per family: random, all 0, all p - 1, the edge words"""
+    from tests import _edge_values as ev
+
+    return {"random": (rng.integers(0, P, 16, dtype=np.uint32), rng.integers(0, P, 7, dtype=np.uint32)),
+            "zero": (np.zeros(16, np.uint32), np.zeros(7, np.uint32)),
+            "pm1": (np.full(16, P - 1, np.uint32), np.full(7, P - 1, np.uint32)),
+            "edge": (ev.EDGE[rng.integers(0, len(ev.EDGE), 16)], ev.EDGE[rng.integers(0, len(ev.EDGE), 7)])}
+
+
+def gather_rows(m, idx):
+    """m[col][row] -> out[q][col] = m[col][idx[q]]"""
+    return np.asarray(m)[:, np.asarray(idx, np.int64)].T.copy()
+
+
+def gather_records(arena, offsets, words: int):
+    """out[r] = arena[offsets[r] : offsets[r] + words]"""
+    arena = np.asarray(arena)
+    return np.stack([arena[int(o):int(o) + words] for o in offsets])
+
+
+def ext_to_cols(v):
+    """len elements of 4 coordinates -> 4 columns of len"""
+    return np.asarray(v).reshape(-1, 4).T.copy()
+
+
 # ---------------------------------------------------------------------------------------------------------- scalar twins
 # The same stages with Python integers only, row by row: what test_stage_ref_cpu.py holds the vectorised routines above against.
 def lincomb_scalar(m, g):

@@ -62,7 +62,7 @@ def rust_struct_fields(name):
 
 def test_repr_c_structs_list_the_header_fields_in_order():
     for name in ("OriginalAir", "Subst", "ExprSpan", "DerivedExprSpec", "DevInteraction", "PowdrDeviceMatrix", "PowdrPeriphery", "PowdrCallMajorAir", "PowdrSubstCM", "PowdrOrigInstr", "PowdrRecordSubst",
-                 "PowdrAirStats", "PowdrApcCandidateInfo", "PwStarkConfig", "PwSegmentAir", "PwAirDescription"):
+                 "PowdrAirStats", "PowdrApcCandidateInfo", "PwStarkConfig", "PwSegmentAir", "PwAirDescription", "PwStageGatherJob"):
         c, r = c_struct_fields(name), rust_struct_fields(name)
         assert c and r, name
         assert c == r, (name, c, r)

@@ -415,3 +415,79 @@ def test_inputs_of_the_logup_stage_tests_are_what_they_claim():
             ref.logup_perm(T, it, starts, alpha, blpow, vanishing=[(i, r) for r in rows])
             ms, ds = ref.interaction_values(T, it, alpha, blpow)
             assert not ds[i][rows].any() and all(int(m[r]) for m in ms for r in rows)
+
+
+# ---- the query phase -------------------------------------------------------------------------------------------------------------------
+def numpy_pow_search(state, pending, bits, n, constants):
+    """the kernel's shortcut, restated: the pending words and the candidate overwrite the state, ONE permutation, word 7, its low bits"""
+    from tests import _poseidon2_air_ref as p2
+
+    st = np.tile(np.asarray(state, np.int64), (n, 1))
+    st[:, :len(pending)] = np.asarray(pending, np.int64)
+    st[:, len(pending)] = np.arange(n)
+    word7 = p2.permute(st, constants)[0][:, 7]
+    return [next((int(w) for w in np.nonzero((word7 & ((1 << b) - 1)) == 0)[0]), sm.POW_NONE) for b in bits]
+
+
+def test_pow_witness_observes_and_samples_like_one_overwrite_and_one_permutation():
+    """or_pow_witness grinds with the oracle's Challenger (copy, observe, sample_bits); for every in_len — the witness fills the rate
+    at 7, a sample forces the duplex below — that is the overwrite / permute / word 7 rule pow_kernel uses"""
+    constants = sm.poseidon2_constants()
+    bits, n = [1, 2, 4, 7, 8], 1 << 12
+    for name, (state, pending) in ref.pow_families(np.random.default_rng(200)).items():
+        for in_len in range(8):
+            want = numpy_pow_search(state, pending[:in_len], bits, n, constants)
+            got = [sm.pow_witness(state, pending[:in_len], b, 0, n) for b in bits]
+            assert got == want, (name, in_len, got, want)
+            assert want[0] != sm.POW_NONE and want[2] != sm.POW_NONE  # 2^12 candidates: a miss at 4 bits has probability e^-256
+            w = want[4]
+            if w != sm.POW_NONE and w > 0:  # the range is half-open on both sides of the witness
+                assert sm.pow_witness(state, pending[:in_len], 8, 0, w) == sm.POW_NONE
+                assert sm.pow_witness(state, pending[:in_len], 8, w, w + 1) == w
+                assert sm.pow_witness(state, pending[:in_len], 8, w + 1, n) == numpy_pow_search_from(state, pending[:in_len], 8, w + 1, n, constants)
+    s, q = np.zeros(16, np.uint32), np.zeros(7, np.uint32)
+    bad = s.copy()
+    bad[3] = P
+    assert sm.pow_witness(bad, q, 4) == sm.POW_NONE and sm.pow_witness(s, np.full(3, P, np.uint32), 4) == sm.POW_NONE
+    assert sm.pow_witness(s, q, 0) == sm.POW_NONE and sm.pow_witness(s, q, 32) == sm.POW_NONE
+    assert sm.pow_witness(s, np.zeros(8, np.uint32), 4) == sm.POW_NONE and sm.pow_witness(s, q, 4, 5, 5) == sm.POW_NONE
+
+
+def numpy_pow_search_from(state, pending, bits, lo, n, constants):
+    from tests import _poseidon2_air_ref as p2
+
+    st = np.tile(np.asarray(state, np.int64), (n - lo, 1))
+    st[:, :len(pending)] = np.asarray(pending, np.int64)
+    st[:, len(pending)] = np.arange(lo, n)
+    hits = np.nonzero((p2.permute(st, constants)[0][:, 7] & ((1 << bits) - 1)) == 0)[0]
+    return lo + int(hits[0]) if len(hits) else sm.POW_NONE
+
+
+def test_lde_rows_are_the_oracles_extension():
+    """values -> coefficients by the oracle's inverse DFT -> every row of the oracle's LDE, log_h 1 .. 6; and the device layout of the
+    coefficients: H c_bitrev(q), which the coefficient weights open at any point"""
+    rng = np.random.default_rng(201)
+    for log_h in range(1, 7):
+        H, W = 1 << log_h, 3
+        values = rng.integers(0, P, (W, H), dtype=np.uint32)
+        values[1] = P - 1
+        c = np.stack([sm.dft(v, inverse=True) for v in values])
+        want = sm.lde(values.reshape(-1), W, log_h).reshape(W, 2 * H).T
+        idx = list(range(2 * H))
+        assert (ref.lde_rows(c, log_h, idx) == want).all(), log_h
+        assert (ref.lde_rows(c, log_h, idx[::-1] + [0, 0]) == np.concatenate([want[::-1], want[:1], want[:1]])).all()
+        arrays = ref.coefficient_arrays(c, log_h)
+        for col in range(W):
+            idft = sm.dft(values[col], inverse=True)
+            assert arrays[col].tolist() == [H * int(idft[ref.bitrev(q, log_h)]) % P for q in range(H)]
+        zeta = tuple(int(x) for x in rng.integers(0, P, 4))
+        assert as_tuples(ref.ext_dot(arrays, ref.coefficient_weights(zeta, log_h))) == [horner(col, zeta) for col in c]
+    x = 123456789
+    assert ref.power_vector(x, 64).tolist() == [pow(x, k, P) for k in range(64)] and ref.power_vector(x, 1).tolist() == [1]
+
+
+def test_gathers_and_the_transpose_are_plain_indexing():
+    m = np.arange(15, dtype=np.uint32).reshape(3, 5)
+    assert ref.gather_rows(m, [4, 0, 4]).tolist() == [[4, 9, 14], [0, 5, 10], [4, 9, 14]]
+    assert ref.gather_records(np.arange(40), [8, 0, 8], 4).tolist() == [[8, 9, 10, 11], [0, 1, 2, 3], [8, 9, 10, 11]]
+    assert ref.ext_to_cols(np.arange(12)).tolist() == [[0, 4, 8], [1, 5, 9], [2, 6, 10], [3, 7, 11]]
