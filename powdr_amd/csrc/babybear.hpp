@@ -190,6 +190,43 @@ PW_HD int32_t smont(int64_t t) {
     return (int32_t)((t + (int64_t)m * (int64_t)P) >> 32);
 #endif
 }
+// The fold: T = Th 2^32 + Tl (Th the signed high word, Tl the unsigned low word) and Th kappa + Tl, kappa = R mod p, are the same
+// residue, and the second is small WHATEVER int64 went in: |sfold| <= kSfoldMax = 0.1422 p^2, far inside smont's domain. One
+// v_mad_i64_i32 plus a zero for the addend's high half. smont_any = smont o sfold therefore reduces ANY int64 to a representative
+// within kSmontAnyMax = 0.5667 p: sums of three and more products and long accumulations go through it and need no re-centring
+// afterwards; sums already inside smont's domain (one- and two-term products) keep the plain reduction.
+// The exact figures (tools/ext_signed_bounds.py recomputes them and reads this block back):
+namespace bounds {
+constexpr int64_t kSmontDomain = 4899916392431615999ll;  // max |t| of smont: |t| + 2^31 p <= 2^63 - 1 (1.209 p^2)
+constexpr int64_t kSfoldMax = 576460752034988033ll;      // max |sfold(t)| over all of int64: (2^31 - 1) kappa + 2^32 - 1
+constexpr int32_t kSmontAnyMax = 1140850688;             // max |smont_any(t)| over all of int64: (kSfoldMax + 2^31 p) >> 32
+}  // namespace bounds
+static_assert(bounds::kSmontDomain == 0x7fffffffffffffffll - ((int64_t)1 << 31) * (int64_t)P, "smont's domain");
+static_assert(bounds::kSfoldMax == (((int64_t)1 << 31) - 1) * (int64_t)R_MOD_P + 0xffffffffll, "the fold's range");
+static_assert(bounds::kSfoldMax <= bounds::kSmontDomain, "a folded value is an argument of smont");
+static_assert(bounds::kSmontAnyMax == (int32_t)((bounds::kSfoldMax + ((int64_t)1 << 31) * (int64_t)P) >> 32), "smont_any's range");
+PW_HD int64_t sfold(int64_t t) {
+    const int32_t hi = (int32_t)(t >> 32);
+    const int64_t lo = (int64_t)(uint64_t)(uint32_t)t;
+#if defined(__HIP_DEVICE_COMPILE__)
+    int64_t out;
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(out) : "v"(hi), "s"((int32_t)R_MOD_P), "v"(lo) : "vcc");
+    return out;
+#else
+    return (int64_t)hi * (int64_t)R_MOD_P + lo;
+#endif
+}
+PW_HD int32_t smont_any(int64_t t) { return smont(sfold(t)); }
+// acc + a b, both factors in vector registers
+PW_HD int64_t smad(int64_t acc, int32_t a, int32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int64_t out;
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(out) : "v"(a), "v"(b), "v"(acc) : "vcc");
+    return out;
+#else
+    return acc + (int64_t)a * b;
+#endif
+}
 // acc + x, acc + k x (k a small constant), c + k x for a wave-uniform c, acc + x u for a wave-uniform u, k x
 PW_HD int64_t swide_add(int64_t acc, int32_t x) {
 #if defined(__HIP_DEVICE_COMPILE__)

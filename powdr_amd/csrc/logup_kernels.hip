@@ -18,21 +18,21 @@ using bb::Ext;
 // Every coordinate is a sum of products accumulated RAW in a signed 64-bit register (one v_mad_i64_i32 per term) and reduced
 // by signed Montgomery reductions (bb::smont, no conditional subtraction): the challenge powers are wave-uniform, so their
 // centred representatives (|b| <= p/2) come from the scalar unit for free, an argument a is a canonical word, a product is
-// below p^2 / 2 and two of them fit the reduction's domain (1.209 p^2) on top of what is already there (<= 0.134 p^2);
-// after two products the accumulator is reduced and re-enters as r * (R mod p). Per coordinate and argument ~3.5
-// instructions where a Montgomery product and a modular addition took 8.
+// below p^2 / 2 and four of them fit an int64 on top of what a fold leaves (<= 0.1422 p^2); after four products the
+// accumulator is folded (bb::sfold). Per coordinate and argument ~1.5 instructions where a Montgomery product and a modular
+// addition took 8. The result is a signed class-S word (ext.hpp), and the num / den chain below stays in that form.
 // (one multiplicity / argument on row r: eval_span, logup_eval.hpp)
 
 using pwj::DenominatorSeeds;
 using pwj::denominator_seeds;
 // (the accumulation itself lives in jit_device.hpp, shared with the run-time specialised kernels)
 template <bool FAST>
-__device__ __forceinline__ Ext interaction_denominator(const LogupInteraction& it, const LogupProgram& lp, const uint32_t* __restrict__ m,
+__device__ __forceinline__ bb::SExt interaction_denominator(const LogupInteraction& it, const LogupProgram& lp, const uint32_t* __restrict__ m,
                                                        size_t stride, size_t r, uint32_t* stk, const DenominatorSeeds& sd,
                                                        const Ext* __restrict__ blpow) {
     pwj::DenominatorAcc acc(sd, it.bus_monty);
     for (uint32_t j = 0; j < it.n_args; ++j) acc.add(eval_span<FAST>(lp, it.first_span + 1 + j, m, stride, r, stk), blpow[j + 1]);
-    return acc.result();
+    return acc.result_signed();
 }
 template <bool FAST>
 __device__ __forceinline__ uint32_t interaction_mult(const LogupInteraction& it, const LogupProgram& lp, const uint32_t* __restrict__ m,
@@ -54,23 +54,24 @@ __global__ __launch_bounds__(kBlock) void logup_perm_kernel(const uint32_t* __re
     const DenominatorSeeds sd = denominator_seeds(al);
     Ext acc = bb::ext_zero();
     for (uint32_t g = 0; g < lp.n_groups; ++g) {
-        Ext num = bb::ext_zero(), den = bb::ext_one();
+        bb::SExt num = bb::sext_zero(), den = bb::sext_one();
         bool any = false;
         for (uint32_t i = lp.d_gstarts[g]; i < lp.d_gstarts[g + 1]; ++i) {
             const LogupInteraction it = lp.d_inter[i];
             const uint32_t m = interaction_mult<FAST>(it, lp, trace, H, r, stk);
             if (m == 0u) continue;
-            const Ext d = interaction_denominator<FAST>(it, lp, trace, H, r, stk, sd, blpow);
+            const bb::SExt d = interaction_denominator<FAST>(it, lp, trace, H, r, stk, sd, blpow);
             if (any) {
-                num = bb::ext_add(bb::ext_mul(num, d), bb::ext_scale(den, m));
-                den = bb::ext_mul(den, d);
+                const bb::SExtB pd = bb::sext_prepare(d);
+                num = bb::sext_mul_add_scaled(num, pd, den, bb::centred(m));
+                den = bb::sext_mul(den, pd);
             } else {
-                num = bb::ext_from_base(m);
+                num = {{bb::centred(m), 0, 0, 0}};
                 den = d;
                 any = true;
             }
         }
-        const Ext q = any ? bb::ext_mul(num, bb::ext_inv(den)) : bb::ext_zero();
+        const Ext q = any ? bb::sext_canonical(bb::sext_mul(num, bb::sext_inv(den))) : bb::ext_zero();
         uint32_t* out = perm + (size_t)(4 * g) * H + r;
         out[0] = q.c[0]; out[H] = q.c[1]; out[2 * H] = q.c[2]; out[3 * H] = q.c[3];
         acc = bb::ext_add(acc, q);
@@ -171,20 +172,21 @@ __global__ __launch_bounds__(kBlock) void quotient_logup_kernel(const uint32_t* 
             sumq_next = bb::ext_add(sumq_next, qn);
         }
         const uint32_t i0 = lp.d_gstarts[g], i1 = lp.d_gstarts[g + 1];
-        Ext num, den;
+        bb::SExt num = bb::sext_zero(), den = bb::sext_one();  // (an empty group: its column must vanish)
         for (uint32_t i = i0; i < i1; ++i) {
             const LogupInteraction it = lp.d_inter[i];
-            const Ext d = interaction_denominator<FAST>(it, lp, lde, N, j, stk, sd, blpow);
+            const bb::SExt d = interaction_denominator<FAST>(it, lp, lde, N, j, stk, sd, blpow);
             const uint32_t m = interaction_mult<FAST>(it, lp, lde, N, j, stk);
             if (i == i0) {
-                num = bb::ext_from_base(m);
+                num = {{bb::centred(m), 0, 0, 0}};
                 den = d;
             } else {
-                num = bb::ext_add(bb::ext_mul(num, d), bb::ext_scale(den, m));
-                den = bb::ext_mul(den, d);
+                const bb::SExtB pd = bb::sext_prepare(d);
+                num = bb::sext_mul_add_scaled(num, pd, den, bb::centred(m));
+                den = bb::sext_mul(den, pd);
             }
         }
-        wide.fma(apow[nc + g], bb::ext_sub(bb::ext_mul(qi, den), num));
+        wide.fma(apow[nc + g], bb::sext_canonical(bb::sext_mul_sub(bb::sext_centred(qi), bb::sext_prepare(den), num)));
     }
     Ext acc = wide.result();
     if (main_only) {  // the streamed path: `lde` / `plde` hold one sub-coset, the boundary terms are added by quotient_logup_tail_kernel
